@@ -5,10 +5,10 @@ A "step" is one pass of the hot path over splat records already resident in HBM:
     Clear -> key generation -> radix sort -> Draw (projection, tile lists, ordered compositing)
 exactly the call sequence of the reference's Scene::Render with sorting on (Scenes.h:312-339), through the C ABI.
 
-  N = 1   workload = BASELINE.json configs[1]: 1,000,000 random 3D splats in a 400^3 cube, one 1080p frame per step.  The same
-          invocation also times configs[2] (10^7 splats, the HBM-scale config) into the "c3" block of the line, the 10^6 TRUE 4D splats of
-          configs[3] at mid-sweep on this one GPU into "c4_n1" (96-byte records, moving keys), and the frame time with a single frame lane
-          (nothing overlaps: "latency_ms_one_lane").
+  N = 1   workload = BASELINE.json configs[1]: 1,000,000 random 3D splats in a 400^3 cube, one 1080p frame per step.  With --full the
+          same invocation also times configs[2] (10^7 splats, the HBM-scale config) into the "c3" block of the line, the 10^6 TRUE 4D splats of
+          configs[3] at mid-sweep on this one GPU into "c4_n1" (96-byte records, moving keys), the frame time with a single frame lane
+          (nothing overlaps: "latency_ms_one_lane"), the one-key-pair figure, the roofline block and the CPU baseline.
   N > 1   workload = BASELINE.json configs[3], exactly: 1,000,000 4D splats, the 256-frame time sweep t_k = 50 k / 255, frame k on rank
           k mod N — or, with --rank0-frames-pct below 100, fewer frames on rank 0, which also receives everybody's (one process per GPU, no
           data-path collective); the finished frames travel to rank 0 in the presentation format
@@ -17,10 +17,20 @@ exactly the call sequence of the reference's Scene::Render with sorting on (Scen
           "scaling": "strong".  The line carries, per rank, how long the comm stream was busy per sweep and how long it ran on after the
           rank's last frame (so that a scaling curve explains itself).
 
-Timing: W untimed warm-up steps, then windows of EXACTLY K steps, each bracketed by barrier + synchronize on both sides, maximum over
-ranks per window; `ms_per_step` / `value` are the MEDIAN window (all windows are listed: a 20-step window lasts 3 ms at N = 1, short
-enough for a clock ramp or a host hiccup to move it by tens of percent; --windows 1 gives the single-window contract reading).
+Timing: W untimed warm-up steps (a plain N = 1 run adds more until the warm-up has lasted 0.1 s: "warmup_steps_run"), then windows of EXACTLY K steps, each bracketed by barrier + synchronize on both sides, maximum over
+ranks per window; `ms_per_step` / `value` are the MEDIAN window.  By default there is one window, so --steps K times exactly K steps;
+--windows M times M windows of K steps and lists them all (a 20-step window lasts 3 ms at N = 1, short enough for a clock ramp or a host
+hiccup to move it by tens of percent).
 Prints ONE JSON line on rank 0.  `value` = splats processed by all ranks / wall time.
+
+A plain run sets up, warms up, times the steps and prints the line: no stage events, no side measurements.  --full adds everything else
+(the N = 1 side blocks above, per-stage HIP events for the roofline block, the CPU baseline; at N > 1 the whole sweep on rank 0's GPU alone).
+--dump-outputs DIR writes, after the timed steps, what the timed path computed in its last step as DIR/<name>.npy (float32 / float64):
+  N = 1   image.npy (the RGBA32F framebuffer, H x W x 4), sorted_keys.npy (the key buffer after the sort), sort_permutation.npy (the index
+          buffer after the sort); above 2^20 splats a fixed seeded sample of 2^20 positions of the two buffers, listed in sample_positions.npy.
+  N > 1   on rank 0: the RGBA8 frames of the sweep's last gathered batch as received (frames_rgba8.npy: frames x pixels x 4, at a fixed seeded
+          sample of pixels listed in pixel_positions.npy when they would exceed the budget) and their frame numbers in the sweep (frame_index.npy).
+The inputs are seeded: the same arguments give the same inputs in every run.
 """
 import argparse
 import importlib
@@ -118,6 +128,61 @@ def timed_windows(step, fence, steps, warmup, windows, reduce_max=None):
     return out
 
 
+WARMUP_MIN_S = 0.1          # plain N = 1 run: untimed frames until the warm-up has lasted this long (at least --warmup of them)
+DUMP_BUDGET = 64_000_000    # bytes of --dump-outputs in all
+DUMP_SAMPLE = 1 << 20       # N = 1: positions of the key / index buffers written above this many splats
+DUMP_SEED = 0
+
+
+def write_outputs(out_dir, arrays):
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        total += a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    assert total <= DUMP_BUDGET, f"--dump-outputs wrote {total} bytes, more than {DUMP_BUDGET}"
+
+
+def dump_single(out_dir, sc):
+    """N = 1: what the caller of the timed path holds after its last step — the framebuffer and the key / index buffer pair of the last frame
+    (the 32-bit key words and the permutation, as float64: exact)."""
+    ctx, n = sc.ctx, sc.n
+    keys, idx = sc.keybufs[(sc.k - 1) % len(sc.keybufs)]
+    out = {"image": ctx.read_pixels()}
+    skeys = ctx.read(keys, np.uint32, n)
+    perm = ctx.read(idx, np.uint32, n)
+    if n > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_SAMPLE, replace=False))
+        skeys, perm = skeys[pos], perm[pos]
+        out["sample_positions"] = pos.astype(np.float64)
+    out["sorted_keys"] = skeys.astype(np.float64)
+    out["sort_permutation"] = perm.astype(np.float64)
+    write_outputs(out_dir, out)
+
+
+def dump_sweep(out_dir, batch, frames_of_rank, most, every):
+    """N > 1, rank 0: the frames of the sweep's last batch as they arrived (batch[r][slot]: rank r's RGBA8 frame in that slot).  Slot s of the last
+    batch holds presentation (last batch) * every + s of every rank; a rank with fewer frames has no frame there."""
+    b = (most - 1) // every
+    frames, index = [], []
+    for r, mine in enumerate(frames_of_rank):
+        for s in range((most - 1) % every + 1):
+            p = b * every + s
+            if p < len(mine):
+                frames.append(batch[r][s].cpu().numpy().view(np.uint8).reshape(H * W, 4))
+                index.append(mine[p])
+    out = {}
+    npx = min(H * W, (DUMP_BUDGET - 8 * H * W) // (16 * max(1, len(frames))))
+    if npx < H * W:
+        pix = np.sort(np.random.default_rng(DUMP_SEED).choice(H * W, npx, replace=False))
+        frames = [f[pix] for f in frames]
+        out["pixel_positions"] = pix.astype(np.float64)
+    out["frames_rgba8"] = np.stack(frames).astype(np.float32) if frames else np.zeros((0, npx, 4), np.float32)
+    out["frame_index"] = np.asarray(index, np.float64)
+    write_outputs(out_dir, out)
+
+
 def roofline_block(gs4d_stats, stage_ms, warm_ms, n, ms_per_step, traffic_file, one=None):
     """The dominant credited kernel, priced per launch: achieved = algorithmic bytes per launch / average launch duration from HIP
     events on the stream the kernel is launched on (gs4d_set_profiling / gs4d_get_timings).
@@ -195,8 +260,11 @@ def morton_order(pos):
     return np.argsort(spread(g[:, 0]) | (spread(g[:, 1]) << np.uint64(1)) | (spread(g[:, 2]) << np.uint64(2)), kind="stable")
 
 
-def measure_single(gs4d, scenes, n, steps, warmup, windows, device, stage_events=True, lanes=None, keybufs=4, steady_stages=0, four_d=False, t=0.0, settle_window=False, spatial_order=False):
+def measure_single(gs4d, scenes, n, steps, warmup, windows, device, stage_events=True, lanes=None, keybufs=4, steady_stages=0, four_d=False, t=0.0, settle_window=False, spatial_order=False,
+                   profile=True, dump_dir=None, warmup_min_s=0.0):
     """One GPU: static 3D splats in the cube (configs[1] / configs[2]) or, four_d, the true 4D splats of configs[3] at time t.
+    profile=False: no HIP events at all (warm_ms / stage_ms are None).  dump_dir: --dump-outputs after the timed windows.
+    warmup_min_s > 0: more untimed frames after the `warmup` ones until the warm-up has lasted that long (0: exactly `warmup` frames).
     Returns (result dict, records, camera)."""
     cam = scenes.CAM_CUBE
     view = gs4d.look_at(cam[0], cam[1])
@@ -224,17 +292,30 @@ def measure_single(gs4d, scenes, n, steps, warmup, windows, device, stage_events
     # (the first frames of a context are not typical: the library learns the tile-list capacities of the scene in them — draws that are
     # aborted on the device and re-run — so the events start after the third warm-up frame where there are that many)
     learn = min(3, max(0, warmup - 1))
+    t_warm = time.perf_counter()
     for k in range(warmup):
         if k == learn:
             fence()
-            ctx.set_profiling(True)
+            if profile:
+                ctx.set_profiling(True)
         frame()
     fence()
-    warm_ms = ctx.timings()
-    alg = algorithmic_bytes(n, W, H)
-    cred = [k for k, v in warm_ms.items() if v > 0 and alg[k] > 0]
-    dominant = max(cred, key=lambda k: warm_ms[k]) if cred else None
-    ctx.set_profiling([dominant] if (dominant and stage_events) else False, every=8)
+    # the first tens of milliseconds at full load run slower than what follows: after 20 warm-up frames the first of five 200-step windows was
+    # 1.7-2.7 % slower than the mean of the other four in 8 runs of 8 (MI355X, configs[1]).  A plain run times ONE window, so it warms up until
+    # warmup_min_s have passed; --full and the side blocks render exactly `warmup` + windows * `steps` frames (the profiling tools count them)
+    warmup_run = warmup
+    while time.perf_counter() - t_warm < warmup_min_s:
+        for _ in range(32):
+            frame()
+        fence()
+        warmup_run += 32
+    warm_ms = None
+    if profile:
+        warm_ms = ctx.timings()
+        alg = algorithmic_bytes(n, W, H)
+        cred = [k for k, v in warm_ms.items() if v > 0 and alg[k] > 0]
+        dominant = max(cred, key=lambda k: warm_ms[k]) if cred else None
+        ctx.set_profiling([dominant] if (dominant and stage_events) else False, every=8)
     # Frames that aborted on the device (tile-list capacity, list length) and were cleared away before anything observed them are never
     # re-run: a timed window that contains one has timed an incomplete render.  The library counts them; the bench refuses such windows —
     # once more from the start (the context has learned from the aborted frames by then), and if they still contain one, not at all.
@@ -253,8 +334,12 @@ def measure_single(gs4d, scenes, n, steps, warmup, windows, device, stage_events
         print(f"bench.py: {aborted} timed frame(s) aborted on the device and were never completed; timing the windows again", file=sys.stderr)
     if aborted:
         raise RuntimeError(f"{aborted} timed frame(s) aborted on the device and were never completed: the measurement is invalid")
-    stage_ms = ctx.timings()
-    ctx.set_profiling(False)
+    stage_ms = None
+    if profile:
+        stage_ms = ctx.timings()
+        ctx.set_profiling(False)
+    if dump_dir:
+        dump_single(dump_dir, sc)
     steady_ms = None
     if steady_stages:
         # every stage timed over frames of the steady state (the warm-up frames above include the draws the library aborted and re-ran
@@ -270,6 +355,7 @@ def measure_single(gs4d, scenes, n, steps, warmup, windows, device, stage_events
     ms = sorted(1e3 * s / steps for s in secs)
     med = ms[len(ms) // 2]
     res = {"ms_per_step": med, "value": n / (med * 1e-3), "windows_ms_per_step": [round(1e3 * s / steps, 5) for s in secs], "aborted_in_timed_windows": aborted, "timed_window_attempts": attempts,
+           "warmup_steps_run": warmup_run,
            "stats": stats, "warm_ms": warm_ms, "stage_ms": stage_ms, "steady_ms": steady_ms}
     return res, rec, (cam, view, proj)
 
@@ -278,8 +364,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each; the line reports the median window")
+    ap.add_argument("--warmup", type=int, default=20, help="untimed warm-up steps; a plain N=1 run (no --full) adds more until the warm-up has lasted 0.1 s "
+                                                          "(the line's warmup_steps_run says how many ran)")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps steps each; the line reports the median window")
+    ap.add_argument("--full", action="store_true", help="also the side measurements: N=1 the c3 / c4_n1 blocks, one-lane and one-key-pair figures, stage events for the roofline block, "
+                                                        "the CPU baseline; N>1 the whole sweep on rank 0's GPU alone (the --no-* options below leave parts of it out)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--splats", type=int, default=1_000_000)
     ap.add_argument("--gather-every", type=int, default=8, help="N>1: frames of every rank per RCCL gather")
     ap.add_argument("--rank0-frames-pct", type=int, default=None, help="N>1: rank 0 renders this percentage of an equal share of the sweep (it also receives every other rank's frames); default: sharding.default_rank0_pct(N)")
@@ -326,33 +416,36 @@ def single_gpu(args, gs4d, scenes, device):
     n = args.splats
     kb = args.keybufs or args.lanes or 4          # one pair per frame lane (the library default is 4 lanes)
     fd = dict(four_d=True, t=25.0) if args.four_d else dict(spatial_order=True) if args.spatial_order else {}
-    res, rec, (cam, view, proj) = measure_single(gs4d, scenes, n, args.steps, args.warmup, args.windows, device, stage_events=not args.no_stage_events, lanes=args.lanes, keybufs=kb, **fd)
+    full = args.full
+    res, rec, (cam, view, proj) = measure_single(gs4d, scenes, n, args.steps, args.warmup, args.windows, device, stage_events=not args.no_stage_events, lanes=args.lanes, keybufs=kb,
+                                                 profile=full, dump_dir=args.dump_outputs, warmup_min_s=0.0 if full else WARMUP_MIN_S, **fd)
     tag = "c4" if args.four_d else "c2" if n == 1_000_000 else "c3" if n == 10_000_000 else "x"
     tfile = lambda t: os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_pmc_traffic_{t}.json")
     # The four-lane side measurements come first, the one-lane ones last: a context created after a context with another number of frame
     # lanes runs ~10 % slower (tools/order_effect.py: 0.110 -> 0.122 ms/frame after one one-lane context has been created and closed; HIP maps
     # the lanes' streams onto its hardware queues differently then) — an artefact of this process's history, not of the workload.
     n3 = 10_000_000
-    side = not args.no_c3 and n == 1_000_000 and not args.four_d
+    side = full and not args.no_c3 and n == 1_000_000 and not args.four_d
     r3 = r4 = None
     if side:
         r3, _, _ = measure_single(gs4d, scenes, n3, max(10, min(args.steps, 100) // 2), 8, 3, device, stage_events=not args.no_stage_events, lanes=args.lanes, keybufs=kb, spatial_order=args.spatial_order)
         # configs[3]'s workload on ONE GPU: 10^6 true 4D splats (96-byte records: nothing of sig is constant or symmetric-by-construction here), t mid-sweep
         r4, _, _ = measure_single(gs4d, scenes, n, min(args.steps, 100), 24, 5, device, stage_events=not args.no_stage_events, lanes=args.lanes, keybufs=kb, four_d=True, t=25.0, settle_window=True)
+    latency = full and not args.no_latency
     one_pair = None
-    if not args.no_latency:
+    if latency:
         # the reference's own buffer layout: ONE key / index pair for every frame (Scenes.h m_key_buf / m_values_buf).  Frame f + 1 writes the
         # buffers frame f's sort is still filling: the lanes order themselves on the device (events), consecutive frames overlap less.
         r1, _, _ = measure_single(gs4d, scenes, n, min(args.steps, 50), min(args.warmup, 10), 3, device, stage_events=False, lanes=args.lanes, keybufs=1, **fd)
         one_pair = {"ms_per_step": round(r1["ms_per_step"], 5), "value": r1["value"], "unit": "splats/s",
                     "note": "same workload with one key / sort-index buffer pair instead of one per frame lane (the reference's layout, Scenes.h:241-247): the drop-in figure"}
     one = one3 = one4 = None
-    if not args.no_latency:
+    if latency:
         one, _, _ = measure_single(gs4d, scenes, n, min(args.steps, 50), min(args.warmup, 10), 3, device, stage_events=False, lanes=1, steady_stages=16, **fd)
         if side:
             one3, _, _ = measure_single(gs4d, scenes, n3, 10, 5, 3, device, stage_events=False, lanes=1, steady_stages=8, spatial_order=args.spatial_order)
             one4, _, _ = measure_single(gs4d, scenes, n, 30, 10, 3, device, stage_events=False, lanes=1, steady_stages=16, four_d=True, t=25.0)
-    roofline = roofline_block(res["stats"], res["stage_ms"], res["warm_ms"], n, res["ms_per_step"], tfile(tag), one)
+    roofline = roofline_block(res["stats"], res["stage_ms"], res["warm_ms"], n, res["ms_per_step"], tfile(tag), one) if full else None
 
     def side_block(r, o, workload, nn, ptag):
         st_ = r["stats"]
@@ -364,15 +457,16 @@ def single_gpu(args, gs4d, scenes, device):
                 "roofline": roofline_block(st_, r["stage_ms"], r["warm_ms"], nn, r["ms_per_step"], tfile(ptag), o)}
     c3 = side_block(r3, one3, "10,000,000 random 3D splats in a 400^3 cube, single 1080p frame (BASELINE.json configs[2])", n3, "c3") if r3 else None
     c4 = side_block(r4, one4, "1,000,000 4D splats (BASELINE.json configs[3]'s set: mu_t ~ U[0,50], lifetime ~ U[0.5,2], velocity ~ U[-5,5]^3) at t = 25, single 1080p frame, ONE GPU", n, "c4") if r4 else None
-    cpu = None if args.no_cpu_baseline else cpu_baseline(rec, cam, view, proj)
+    cpu = cpu_baseline(rec, cam, view, proj) if full and not args.no_cpu_baseline else None
     st = res["stats"]
     return {
         "metric": "Gaussians/sec + ms/frame @1080p; sort permutation bit-exact",
         "value": res["value"], "unit": "splats/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": res["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
-        "timing": f"median of {args.windows} windows of {args.steps} steps, each window between two synchronisations; a step is pipelined throughput ({st['lanes']} frame lanes in flight)",
+        "timing": f"median of {args.windows} window(s) of {args.steps} steps, each window between two synchronisations; a step is pipelined throughput ({st['lanes']} frame lanes in flight)",
         "windows_ms_per_step": res["windows_ms_per_step"],
+        "warmup_steps_run": res["warmup_steps_run"],
         "timed_window_attempts": res["timed_window_attempts"],
         "latency_ms_one_lane": round(one["ms_per_step"], 5) if one else None,
         "config": {"workload": (f"{n:,} 4D splats of BASELINE.json configs[3]'s set at t = 25, single 1080p frame, one GPU" if args.four_d else
@@ -493,7 +587,7 @@ def multi_gpu(args, gs4d, scenes, torch, rank, local_rank, world, backend):
         torch.cuda.synchronize()
 
     one_gpu = None
-    if rank == 0:
+    if rank == 0 and args.full:
         so = timed_windows(sweep_one_gpu, fence_local, 1, 1, 3)
         so_ms = sorted(1e3 * x for x in so)[1]
         one_gpu = {"ms_per_step": round(so_ms, 4), "value": n * SWEEP_FRAMES / (so_ms * 1e-3), "unit": "splats/s",
@@ -521,6 +615,9 @@ def multi_gpu(args, gs4d, scenes, torch, rank, local_rank, world, backend):
         comm["busy_ms"] = comm["tail_ms"] = 0.0
         return timed_windows(sweep, fence, args.steps, 0, args.windows, reduce_max)
     secs = timed()
+    if args.dump_outputs and rank == 0:
+        # the gathers of the last batch of the last sweep went into gathered[b & 1] (run_sweep alternates the batch buffers per batch b)
+        dump_sweep(args.dump_outputs, gathered[((most - 1) // G) & 1], [sharding.frames_for_rank(SWEEP_FRAMES, r, world, pct) for r in range(world)], most, G)
     nsweeps = max(1, args.steps * args.windows)
     mine_comm = torch.tensor([comm["busy_ms"] / nsweeps, comm["tail_ms"] / max(1, args.windows)], dtype=torch.float64, device=gdev)
     all_comm = [torch.zeros(2, dtype=torch.float64, device=gdev) for _ in range(world)]

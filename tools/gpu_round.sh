@@ -7,8 +7,8 @@ timeout -k 10 900 python -m pytest tests -m gpu -q "$@" > $out/pytest.log 2>&1
 rc=$?
 tail -n 15 $out/pytest.log
 if [ $rc -gt 1 ]; then echo "pytest rc=$rc: no further GPU steps"; exit $rc; fi
-timeout -k 10 300 python bench.py --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_c2.json 2> $out/bench_c2.err || exit $?
-timeout -k 10 300 python bench.py --steps 100 --warmup 10 --splats 10000000 --no-cpu-baseline > $out/bench_c3.json 2> $out/bench_c3.err || exit $?
+timeout -k 10 300 python bench.py --full --windows 5 --steps 200 --warmup 20 --no-cpu-baseline > $out/bench_c2.json 2> $out/bench_c2.err || exit $?
+timeout -k 10 300 python bench.py --full --windows 5 --steps 100 --warmup 10 --splats 10000000 --no-cpu-baseline > $out/bench_c3.json 2> $out/bench_c3.err || exit $?
 python - <<PY
 import json
 for f in ("$out/bench_c2.json", "$out/bench_c3.json"):

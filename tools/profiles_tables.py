@@ -84,7 +84,10 @@ def main():
     d = line(f"{TAG}_bench_default_driver_settings.json")
     txt = ""
     if d:
-        txt += (f"Driver-style line (`{TAG}_bench_default_driver_settings.json`, `python bench.py --steps 20 --warmup 5`): C2 {d['ms_per_step']:.4f} ms/frame "
+        missing = [k for k in ("latency_ms_one_lane", "one_key_index_pair", "c3", "c4_n1") if d.get(k) is None]
+        if missing:
+            raise SystemExit(f"{TAG}_bench_default_driver_settings.json has no {', '.join(missing)}: make it with python bench.py --full --windows 5 --steps 20 --warmup 5")
+        txt += (f"Driver-style line (`{TAG}_bench_default_driver_settings.json`, `python bench.py --full --windows 5 --steps 20 --warmup 5`): C2 {d['ms_per_step']:.4f} ms/frame "
                 f"(windows {d['windows_ms_per_step']}), one lane {d['latency_ms_one_lane']:.4f}, one key / index pair {d['one_key_index_pair']['ms_per_step']:.4f}; "
                 f"C3 {d['c3']['ms_per_step']:.3f} ms/frame, one lane {d['c3']['latency_ms_one_lane']:.3f}; "
                 f"C4 on one GPU {d['c4_n1']['ms_per_step']:.4f} ms/frame, one lane {d['c4_n1']['latency_ms_one_lane']:.4f}.\n\n")
