@@ -63,6 +63,7 @@ def _load():
         "gs4d_host_camera_look_at_point": (None, [vp, vp]),
         "gs4d_host_camera_viewport": (None, [i32, i32, vp]),
         "gs4d_host_camera_focal": (None, [f32, i32, i32, vp]),
+        "gs4d_host_unproject": (None, [vp, vp, i32, i32, f32, f32, f32, vp]),
         "gs4d_read_pixels": (i32, [vp, vp, sz]),
         "gs4d_read_pixels_device": (i32, [vp, vp, sz]),
         "gs4d_read_pixels_rgba8_device": (i32, [vp, vp, sz]),
@@ -73,6 +74,9 @@ def _load():
         "gs4d_read_band_rgba8_device": (i32, [vp, vp, sz]),
         "gs4d_set_stream": (i32, [vp, vp]),
         "gs4d_finish": (i32, [vp]),
+        "gs4d_set_aux_outputs": (i32, [vp, i32]),
+        "gs4d_read_aux": (i32, [vp, vp, sz]),
+        "gs4d_read_aux_device": (i32, [vp, vp, sz]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -312,6 +316,14 @@ def camera_focal(fov, width, height):
     return out
 
 
+def unproject(view, proj, width, height, px, py, depth):
+    """World point at view depth `depth` (-z_view, e.g. Context.read_aux(normalized=True)[..., 0]) on the ray through the centre of pixel
+    (px, py): column px, row py counted from the bottom, as the images returned by read_pixels / read_aux are indexed ([py, px])."""
+    out = np.zeros(3, np.float32)
+    _lib.gs4d_host_unproject(_ptr(_f32(view)), _ptr(_f32(proj)), width, height, px, py, depth, _ptr(out))
+    return out
+
+
 def write_png(path, rgba8):
     """(H, W, 4) uint8 frame, bottom row first (the framebuffer's orientation) -> PNG file."""
     a = np.ascontiguousarray(rgba8, np.uint8)
@@ -446,6 +458,25 @@ class Context:
         """As read_frame_rgba8_device, but the pack waits only for `hip_event` (a hipEvent_t handle; None: for nothing) instead of for
         everything queued on the caller's stream: for callers that alternate between destination buffers."""
         self._chk(_lib.gs4d_read_frame_rgba8_device_after(self._h, frames_back, C.c_void_p(dptr), nbytes, C.c_void_p(hip_event or 0)))
+
+    # aux outputs: per-pixel depth and opacity (DESIGN.md §4)
+    def set_aux_outputs(self, on):
+        """Frames cleared from the next clear() on carry (D, O) per pixel beside the colour (default blend function only)."""
+        self._chk(_lib.gs4d_set_aux_outputs(self._h, 1 if on else 0))
+
+    def read_aux(self, normalized=False):
+        """(H, W, 2) float32, rows bottom-up like read_pixels: raw (D, O) — they compose across draws — or with normalized=True
+        (D / O, O): the expected depth, 0 where O == 0."""
+        out = np.empty((self.height, self.width, 2), np.float32)
+        self._chk(_lib.gs4d_read_aux(self._h, _ptr(out), out.nbytes))
+        if normalized:
+            d, o = out[..., 0], out[..., 1]
+            out = np.stack([np.divide(d, o, out=np.zeros_like(d), where=o > 0), o], axis=-1)
+        return out
+
+    def read_aux_device(self, dptr, nbytes):
+        """Raw (D, O) planes to device pointer `dptr` (e.g. a torch tensor's data_ptr()), asynchronously like read_pixels_device."""
+        self._chk(_lib.gs4d_read_aux_device(self._h, C.c_void_p(dptr), nbytes))
 
     def set_tile_shard(self, rank, world):
         """Single-frame sharding: this context bins and composites the tile rows ty % world == rank only."""

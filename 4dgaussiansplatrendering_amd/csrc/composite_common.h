@@ -85,8 +85,11 @@ __device__ __forceinline__ void blend_general(BlendFn bf, float sr, float sg, fl
 __device__ __forceinline__ float gauss_weight(float u, float v) { return __builtin_amdgcn_exp2f((u * u + v * v) * -46.16624130844683f); }      // -32 * log2(e)
 __device__ __forceinline__ float clamp01(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f); }
 
-template <bool PREMULT_C, bool GENERAL = false>
-__device__ __forceinline__ void blend_fragment(float u, float v, float alpha, float r_, float g_, float b_, float& T, float& Cr, float& Cg, float& Cb, float& A, BlendFn bf = BlendFn{ 0, 0 }) {
+// AUX (default function only): also D += w * d, with the weight w the colour uses and d the entry's depth (projected record, slot 15).
+template <bool PREMULT_C, bool GENERAL = false, bool AUX = false>
+__device__ __forceinline__ void blend_fragment(float u, float v, float alpha, float r_, float g_, float b_, float& T, float& Cr, float& Cg, float& Cb, float& A, BlendFn bf = BlendFn{ 0, 0 },
+                                               float d = 0.0f, float* D = nullptr) {
+    static_assert(!(AUX && GENERAL), "aux outputs are defined for the default blend function only");
     const float cg = gauss_weight(u, v);
     if (GENERAL) {
         if (cg >= 0.0001f) {                               // Splat4DFragShader.GLSL:30 discard
@@ -105,15 +108,18 @@ __device__ __forceinline__ void blend_fragment(float u, float v, float alpha, fl
     const float w = T * al;
     if (PREMULT_C) { r_ = clamp01(r_ * cg); g_ = clamp01(g_ * cg); b_ = clamp01(b_ * cg); }   // Splat3DFragShaderFull.GLSL:22
     Cr += w * r_; Cg += w * g_; Cb += w * b_; A += w * al;
+    if (AUX) *D += w * d;
     T *= (1.0f - al);
 }
 
 // One chunk of the tile's list, front to back: lane s < cnt carries record `rec` of list entry (end of chunk - 1 - s), so s = 0 is the
 // front-most entry.  stage: 64 x 3 float4, pmask: 64 x 2 words (per pixel: 64-bit mask of the chunk entries that cover it).
 // GENERAL: the chunk is walked in DRAW order instead — lane s carries list entry (start of chunk + s).
-template <bool PREMULT_C, bool GENERAL = false>
+// AUX: the entry's depth (the last float of the same 64-byte record) is staged beside it in dstage (64 floats) and accumulated into *D.
+template <bool PREMULT_C, bool GENERAL = false, bool AUX = false>
 __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj, uint32_t rec, uint32_t cnt, uint32_t lane, int tx0, int ty0, float fx, float fy,
-                                                float4* stage, uint32_t* pmask, int dbg, float& T, float& Cr, float& Cg, float& Cb, float& A, BlendFn bf = BlendFn{ 0, 0 }) {
+                                                float4* stage, uint32_t* pmask, int dbg, float& T, float& Cr, float& Cg, float& Cb, float& A, BlendFn bf = BlendFn{ 0, 0 },
+                                                float* dstage = nullptr, float* D = nullptr) {
     // lane s holds list entry hi-1-s : s = 0 is the LAST (front-most) entry of this chunk
     int lx0 = 0, ly0 = 0, bw = 0, bh = 0;
     float4 ra = make_float4(0, 0, 0, 0), rb = ra;
@@ -124,6 +130,7 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
         stage[lane * 3 + 0] = ra;
         stage[lane * 3 + 1] = rb;
         stage[lane * 3 + 2] = rc;
+        if (AUX) dstage[lane] = reinterpret_cast<const float*>(r)[15];
         const uint32_t r0 = __float_as_uint(rc.z), r1 = __float_as_uint(rc.w);
         lx0 = max((int)(r0 & 0xFFFFu) - tx0, 0); ly0 = max((int)(r0 >> 16) - ty0, 0);
         const int lx1 = min((int)(r1 & 0xFFFFu) - tx0, TILE - 1), ly1 = min((int)(r1 >> 16) - ty0, TILE - 1);
@@ -146,7 +153,8 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const bool cov = fabsf(u) <= 0.5f && fabsf(v) <= 0.5f;
             if (__ballot(cov) == 0ull) continue;
             const float4 c = stage[s * 3 + 2];          // b, alpha, -, -
-            if (cov) blend_fragment<PREMULT_C, GENERAL>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf);
+            if (AUX) { const float d = dstage[s]; if (cov) blend_fragment<PREMULT_C, false, true>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, d, D); }
+            else if (cov) blend_fragment<PREMULT_C, GENERAL>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf);
         }
     } else {
         // ---- phase A (lane = entry): mark the covered pixels of small footprints ----
@@ -205,6 +213,7 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const float u = __fmaf_rn(a.z, dx, __fmul_rn(b.x, dy));
             const float v = __fmaf_rn(a.w, dx, __fmul_rn(b.y, dy));
             if (GENERAL) { if (on) blend_fragment<PREMULT_C, true>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf); }
+            else if (AUX) blend_fragment<PREMULT_C, false, true>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, dstage[e], D);
             else blend_fragment<PREMULT_C, false>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, T, Cr, Cg, Cb, A);
         }
     }

@@ -14,7 +14,7 @@ constexpr int PROJ_FLOATS = 16;     // projected record: 64 B, one aligned segme
 
 // Projected record layout (float4 A,B,C,D), written by preprocess, gathered by binning/composite.
 //  A = cx, cy, a0x, a1x      B = a0y, a1y, r, g      C = b, alpha, rect0 (x0 | y0<<16), rect1 (x1 | y1<<16)   [pixel rect, inclusive]
-//  D = hx, hy, valid(1/0), 0      (gs4d_debug_read_projected hands them out in the order documented in gs4d.h)
+//  D = hx, hy, valid(1/0), depth   (depth = -z_view of the centre when the draw has aux outputs, else 0; gs4d_debug_read_projected hands them out in the order documented in gs4d.h)
 // rect0 > rect1 in x (x0 = 1, x1 = 0) marks "no coverage".
 
 struct Uniforms {
@@ -205,7 +205,8 @@ hipError_t tile_lists_reserve_blocks(hipStream_t st, TileLists& t, size_t entrie
 // the entry total is the sum of the statistics); rcap / scap / bcap: what the host guessed for it (longest run: no limit any more, 0xFFFFFFFF; fullest segment; fullest bucket)
 hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* entries, const uint32_t* tstart, const uint32_t* tcnt, const uint32_t* total, uint32_t* total_host, int tiles_x, int tiles_y, int W, int H,
                                int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, uint32_t hint, int keybits, int recbits, uint32_t slabs,
-                               const uint4* bstat = nullptr, uint32_t nb = 0, const uint32_t* sstat = nullptr, uint32_t rows = 0, uint32_t stage_seq = 0, uint32_t rcap = 0, uint32_t scap = 0, uint32_t bcap = 0, uint32_t box_blocks = 0xFFFFFFFFu);
+                               const uint4* bstat = nullptr, uint32_t nb = 0, const uint32_t* sstat = nullptr, uint32_t rows = 0, uint32_t stage_seq = 0, uint32_t rcap = 0, uint32_t scap = 0, uint32_t bcap = 0, uint32_t box_blocks = 0xFFFFFFFFu,
+                               float2* aux = nullptr);
 
 #ifdef __HIPCC__
 // tiles touched by a pixel rectangle (x0|y0<<16, x1|y1<<16; x0 > x1: none), restricted to the tile rows ty % world == rank
@@ -257,7 +258,8 @@ hipError_t launch_soa_repack(hipStream_t st, const float* aos96, size_t n, float
 // plane 0 holds pos.xyz in every layout; the plane of sig[3] (what key generation reads beside it), or null when it is one of the constants
 inline const float4* soa_sig3(const float4* soa, size_t n, const SoaInfo& info) { return info.layout == SOA_STATIC3D ? nullptr : soa + (info.layout == SOA_SYM ? 3 : 5) * n; }
 // Each preprocess launch also writes the packed tile rectangle of every record (pack_trect).
-struct PreOut { float4* proj; uint32_t* trects; };
+// aux: the draw's image has aux outputs — the projection stores each record's depth in the last float of its record (else 0).
+struct PreOut { float4* proj; uint32_t* trects; bool aux = false; };
 hipError_t launch_preprocess_4d(hipStream_t st, const float4* soa, size_t soa_n /* records in the buffer: the plane stride */, const SoaInfo& info, size_t n, const Uniforms& u, int W, int H, PreOut out, const TileCount& tc);
 hipError_t launch_preprocess_3d(hipStream_t st, const float* verts72, size_t n, const Uniforms& u, int W, int H, PreOut out, const TileCount& tc);
 hipError_t launch_preprocess_2d(hipStream_t st, const float* rec48, size_t n, const Uniforms& u, int W, int H, PreOut out, const TileCount& tc);
@@ -281,9 +283,10 @@ hipError_t launch_tile_ranges(hipStream_t st, BinScratch& b, const uint32_t* pai
 
 // ---- composite.hip ----
 // tstate / epoch: the image's tile state (composite.hip): tstate[tile] == epoch <=> the tile's pixels are in memory, else it is still the clear colour
+// aux: the image's aux plane (float2 {D, O} per pixel) when its frame was cleared with aux outputs on, else null
 hipError_t launch_composite(hipStream_t st, const float4* proj, const uint32_t* pair_vals, uint32_t* ranges, const uint32_t* total, int tiles_x, int tiles_y,
-                            int W, int H, int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, int blend_src, int blend_dst);
-hipError_t launch_fill_unwritten(hipStream_t st, float4* fb, uint32_t* tstate, uint32_t epoch, int tiles_x, int tiles_y, int W, int H, const float clear[4]);
+                            int W, int H, int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, int blend_src, int blend_dst, float2* aux = nullptr);
+hipError_t launch_fill_unwritten(hipStream_t st, float4* fb, uint32_t* tstate, uint32_t epoch, int tiles_x, int tiles_y, int W, int H, const float clear[4], float2* aux = nullptr);
 hipError_t launch_pack_rgba8(hipStream_t st, const float4* fb, const uint32_t* tstate, uint32_t epoch, const float clear[4], int W, int H, int tiles_x, uint32_t* out);
 // the pixel rows of the tile rows ty % world == rank, top of the band = the context's first tile row; band_rows pixel rows in all
 hipError_t launch_pack_rgba8_band(hipStream_t st, const float4* fb, const uint32_t* tstate, uint32_t epoch, const float clear[4], int W, int H, int tiles_x, int rank, int world, int band_rows, uint32_t* out);

@@ -142,9 +142,9 @@ __device__ __forceinline__ void eigen2(float u00, float u01, float u10, float u1
 
 __device__ __forceinline__ bool fin(float x) { return isfinite(x); }
 
-// Window-space set-up + record store.  ncx,ncy = NDC centre; kx,ky = NDC scale of the quad offset.
+// Window-space set-up + record store.  ncx,ncy = NDC centre; kx,ky = NDC scale of the quad offset; depth = -z_view of the centre (0: none).
 __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid, const Quad& q, float ncx, float ncy, float kx, float ky,
-                                      int W, int H, float r, float g, float b, float alpha, bool clamp_rgb) {
+                                      int W, int H, float r, float g, float b, float alpha, bool clamp_rgb, float depth) {
     float cx = 0, cy = 0, a0x = 0, a0y = 0, a1x = 0, a1y = 0, hx = 0, hy = 0;
     uint32_t rect0 = 1u, rect1 = 0u;           // empty
     if (valid) {
@@ -172,7 +172,7 @@ __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid,
             }
         }
     }
-    if (!valid) { cx = cy = a0x = a0y = a1x = a1y = hx = hy = 0.0f; alpha = 0.0f; rect0 = 1u; rect1 = 0u; }
+    if (!valid) { cx = cy = a0x = a0y = a1x = a1y = hx = hy = 0.0f; alpha = 0.0f; rect0 = 1u; rect1 = 0u; depth = 0.0f; }
     // the GL clamps a fragment's colour to [0, 1] before blending into the reference's RGBA8 framebuffer; where the fragment shader passes
     // the colour through unchanged that is a per-record operation (the 3D-Full shader multiplies by c first: clamped per fragment)
     if (clamp_rgb) { r = __saturatef(r); g = __saturatef(g); b = __saturatef(b); }
@@ -182,10 +182,11 @@ __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid,
     o[0] = make_float4(cx, cy, a0x, a1x);
     o[1] = make_float4(a0y, a1y, r, g);
     o[2] = make_float4(b, alpha, __uint_as_float(rect0), __uint_as_float(rect1));
-    // Nothing but gs4d_debug_read_projected reads the fourth float4 — and it is written all the same: the record is one 64-byte line, and a
-    // line written whole goes to memory as it is, while a line with 16 bytes missing has to be merged with what memory holds.  Measured
-    // with this store left out (round 3, 10^7 records): the projection kernel 373 -> 459 us; at 10^6 records no difference (40.1 / 40.4 us).
-    o[3] = make_float4(hx, hy, valid ? 1.0f : 0.0f, 0.0f);
+    // Nothing but gs4d_debug_read_projected and the compositor of a draw with aux outputs (the depth) reads the fourth float4 — and it is
+    // written all the same: the record is one 64-byte line, and a line written whole goes to memory as it is, while a line with 16 bytes
+    // missing has to be merged with what memory holds.  Measured with this store left out (round 3, 10^7 records): the projection kernel
+    // 373 -> 459 us; at 10^6 records no difference (40.1 / 40.4 us).
+    o[3] = make_float4(hx, hy, valid ? 1.0f : 0.0f, out.aux ? depth : 0.0f);
     return make_uint2(rect0, rect1);
 }
 
@@ -247,11 +248,13 @@ __device__ __forceinline__ uint32_t blend_key_4d(const KeySrc& ks, uint32_t i, c
 }
 
 // …Instanced.GLSL:97-147 == Splat3DVertexShaderFull.GLSL:45-95.  C[c][r] = 3x3 covariance.
-__device__ __forceinline__ bool project3d(const PU& u, float mx, float my, float mz, const float C[3][3], Quad& q, float& ncx, float& ncy) {
+// depth: -z_view of the centre (what aux outputs accumulate), set whether or not the record survives the clip
+__device__ __forceinline__ bool project3d(const PU& u, float mx, float my, float mz, const float C[3][3], Quad& q, float& ncx, float& ncy, float& depth) {
     const float* V = u.V; const float* P = u.P;
     float pcx = ((V[0] * mx + V[4] * my) + V[8] * mz) + V[12] * 1.0f;
     float pcy = ((V[1] * mx + V[5] * my) + V[9] * mz) + V[13] * 1.0f;
     float pcz = ((V[2] * mx + V[6] * my) + V[10] * mz) + V[14] * 1.0f;
+    depth = -pcz;
     float pcw = ((V[3] * mx + V[7] * my) + V[11] * mz) + V[15] * 1.0f;
     float psx = ((P[0] * pcx + P[4] * pcy) + P[8] * pcz) + P[12] * pcw;
     float psy = ((P[1] * pcx + P[5] * pcy) + P[9] * pcz) + P[13] * pcw;
@@ -345,10 +348,10 @@ __device__ __forceinline__ uint2 project_4d(const float4& pos, const float4& col
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int r = 0; r < 3; ++r) C[c][r] = S[c][r] - a[r] * tv[c];              // :89-95
-    Quad q; float ncx = 0, ncy = 0;
-    bool valid = project3d(u, mx, my, mz, C, q, ncx, ncy);
+    Quad q; float ncx = 0, ncy = 0, depth = 0;
+    bool valid = project3d(u, mx, my, mz, C, q, ncx, ncy, depth);
     key = blend_key_4d(ks, i, pos, s3);
-    return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, col.x, col.y, col.z, ot * col.w, true);
+    return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, col.x, col.y, col.z, ot * col.w, true, depth);
 }
 
 __device__ __forceinline__ uint2 project_record(const Src3D& src, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key) {
@@ -358,10 +361,10 @@ __device__ __forceinline__ uint2 project_record(const Src3D& src, uint32_t, uint
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int r = 0; r < 3; ++r) C[c][r] = v[9 + 3 * c + r];
-    Quad q; float ncx = 0, ncy = 0;
-    bool valid = project3d(u, v[2], v[3], v[4], C, q, ncx, ncy);
+    Quad q; float ncx = 0, ncy = 0, depth = 0;
+    bool valid = project3d(u, v[2], v[3], v[4], C, q, ncx, ncy, depth);
     key = i;
-    return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, v[5], v[6], v[7], v[8], false);
+    return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, v[5], v[6], v[7], v[8], false, depth);
 }
 
 __device__ __forceinline__ uint2 project_record(const Src2D& src, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key) {
@@ -384,7 +387,7 @@ __device__ __forceinline__ uint2 project_record(const Src2D& src, uint32_t, uint
     bool valid = (clipw > 0.0f) && !(clipz < -clipw || clipz > clipw);
     float kx = P[0] / clipw, ky = P[5] / clipw;
     key = i;
-    return emit(out, i, valid, q, kx * psx, ky * psy, kx, ky, u.W, u.H, rec[4], rec[5], rec[6], rec[7], true);
+    return emit(out, i, valid, q, kx * psx, ky * psy, kx, ky, u.W, u.H, rec[4], rec[5], rec[6], rec[7], true, 0.0f);      // 2D records have no depth
 }
 
 // One thread per record (the ordered path).

@@ -119,6 +119,35 @@ void gs4d_host_perspective(float fov_deg, int width, int height, float znear, fl
     std::memcpy(proj, m, sizeof m);
 }
 
+// Picking: the world point at view depth `depth` (= -z_view, what gs4d_read_aux's D/O is) on the ray through the centre of
+// pixel (px, py) — window coordinates (px + 0.5, py + 0.5), row 0 at the bottom, as the images are.  In double: with z_view fixed, the two
+// NDC equations are linear in (x_view, y_view) for any projection matrix; the view matrix is inverted by Gauss-Jordan elimination.
+void gs4d_host_unproject(const float view[16], const float proj[16], int width, int height, float px, float py, float depth, float world3[3]) {
+    const double nx = 2.0 * ((double)px + 0.5) / (double)width - 1.0, ny = 2.0 * ((double)py + 0.5) / (double)height - 1.0;
+    const double zv = -(double)depth;
+    auto P = [&](int c, int r) { return (double)proj[4 * c + r]; };
+    // clip_k - n_k * clip_w = 0 (k = x, y):  a_k * xv + b_k * yv = -c_k
+    const double ax = P(0, 0) - nx * P(0, 3), bx = P(1, 0) - nx * P(1, 3), cx = P(2, 0) * zv + P(3, 0) - nx * (P(2, 3) * zv + P(3, 3));
+    const double ay = P(0, 1) - ny * P(0, 3), by = P(1, 1) - ny * P(1, 3), cy = P(2, 1) * zv + P(3, 1) - ny * (P(2, 3) * zv + P(3, 3));
+    const double det = ax * by - bx * ay;
+    const double xv = (-cx * by + bx * cy) / det, yv = (-ax * cy + cx * ay) / det;
+    // world = view^-1 * (xv, yv, zv, 1)
+    double m[4][8];
+    for (int r = 0; r < 4; ++r) for (int c = 0; c < 4; ++c) { m[r][c] = (double)view[4 * c + r]; m[r][4 + c] = r == c ? 1.0 : 0.0; }
+    for (int k = 0; k < 4; ++k) {
+        int piv = k;
+        for (int r = k + 1; r < 4; ++r) if (std::fabs(m[r][k]) > std::fabs(m[piv][k])) piv = r;
+        if (piv != k) for (int c = 0; c < 8; ++c) std::swap(m[k][c], m[piv][c]);
+        const double inv = 1.0 / m[k][k];
+        for (int c = 0; c < 8; ++c) m[k][c] *= inv;
+        for (int r = 0; r < 4; ++r) if (r != k) { const double f = m[r][k]; for (int c = 0; c < 8; ++c) m[r][c] -= f * m[k][c]; }
+    }
+    const double v[4] = { xv, yv, zv, 1.0 };
+    double w[4];
+    for (int r = 0; r < 4; ++r) w[r] = m[r][4] * v[0] + m[r][5] * v[1] + m[r][6] * v[2] + m[r][7] * v[3];
+    for (int k = 0; k < 3; ++k) world3[k] = (float)(w[k] / w[3]);
+}
+
 // ---- Camera input model (Camera.cpp:90-99, 116-220) ----------------------------------------------------------------------
 static Vec3 v3(const float* p) { return { p[0], p[1], p[2] }; }
 static void put(float* p, Vec3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }

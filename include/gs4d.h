@@ -161,6 +161,22 @@ GS4D_API int gs4d_band_rows(gs4d_ctx* ctx, int* rows);
 GS4D_API int gs4d_read_band_rgba8_device(gs4d_ctx* ctx, void* dptr, size_t bytes);
 GS4D_API int gs4d_finish(gs4d_ctx* ctx);                                          /* blocks until every lane is idle; reports device-side check failures */
 
+/* ---- aux outputs: per-pixel depth and opacity (no reference counterpart) ----
+ * A frame cleared with aux outputs on keeps, beside its colour, one float2 {D, O} per pixel.  A draw with the default blend function
+ * accumulates, with exactly the weights w_i = T_i * al_i of its colour, D_draw = sum w_i * d_i (d_i = -z_view of record i's centre, 0 for
+ * GS4D_MODE_2D) and O_draw = 1 - T_final, and composes them over what the frame holds: D <- D_draw + T_final * D, O <- O_draw + T_final * O.
+ * A clear gives (0, 0); overlay lines (gs4d_draw_lines) leave D and O as they are.  Expected depth = D / O where O > 0.  While a frame has
+ * aux outputs, a draw with any other blend function returns GS4D_E_UNSUPPORTED and draws nothing. */
+/* enable != 0: the frames cleared from the next gs4d_clear on have aux outputs; 0: they do not (every draw then behaves as without this
+ * call).  The first enable allocates one W*H*8-byte plane per image of the swap chain (gs4d_resize reallocates them); nothing is allocated
+ * while aux outputs have never been on. */
+GS4D_API int gs4d_set_aux_outputs(gs4d_ctx* ctx, int enable);
+/* Blocking; bytes == width*height*8: interleaved {D, O} per pixel, rows in gs4d_read_pixels' order (row 0 = bottom).  GS4D_E_INVALID when
+ * the current frame was not cleared with aux outputs on. */
+GS4D_API int gs4d_read_aux(gs4d_ctx* ctx, float* depth_opacity, size_t bytes);
+/* The same, device-to-device and asynchronous, ordered as gs4d_read_pixels_device (into the caller's stream if one was given). */
+GS4D_API int gs4d_read_aux_device(gs4d_ctx* ctx, void* dptr, size_t bytes);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -172,7 +188,9 @@ GS4D_API int gs4d_get_stats(gs4d_ctx* ctx, uint64_t stats[8]);                  
                                                                                       [4] low 32 bits: radix passes launched by the last gs4d_sort_pairs, high 32 bits: candidate streams gs4d_create discarded because they shared a hardware queue with a frame lane chosen before them (0 in a process without other streams), [5] low 32 bits: by the last draw's tile sort (0: the draw built unordered tile lists), high 32 bits: gs4d_keygen calls that gave their output buffers fresh storage instead of waiting for another frame lane (one key / index pair shared by all frames),
                                                                                       [6] bits 0..15: frame lanes, bits 16..31: lanes whose stream shares a hardware queue with another lane's (0 unless the process has fewer free queues than lanes: such a context runs ~10 % slower), high 32 bits: draws that generated the depth keys of the preceding gs4d_keygen themselves (see gs4d_keygen), [7] low 32 bits: draws so far on the unordered tile-list path, high 32 bits: longest tile list of the last such draw */
 /* Projected records of the last draw, 16 floats per record in record order:
- * cx, cy, a0x, a0y, a1x, a1y, alpha, r, g, b, tile-rect (2 words, bit patterns), hx, hy, valid(1/0), 0 */
+ * cx, cy, a0x, a0y, a1x, a1y, alpha, r, g, b, tile-rect (2 words, bit patterns), hx, hy, valid(1/0), depth.
+ * depth (slot 15) is -z_view of the record's (time-conditioned) centre when the draw's frame has aux outputs (gs4d_set_aux_outputs) and the
+ * record is valid, else 0; GS4D_MODE_2D records always have 0. */
 GS4D_API int gs4d_debug_read_projected(gs4d_ctx* ctx, float* out16, size_t nrecords);
 
 /* ---- host-side parameterisation (CPU code inside libgs4d.so; mirrors the reference's host math so that a caller
@@ -229,6 +247,10 @@ GS4D_API void gs4d_host_camera_rotate(gs4d_camera_state* st, double mouse_x, dou
 GS4D_API void gs4d_host_camera_look_at_point(gs4d_camera_state* st, const float point[3]);              /* Camera.cpp:209-220 */
 GS4D_API void gs4d_host_camera_viewport(int width, int height, float out2[2]);                           /* Camera.cpp:90-93  */
 GS4D_API void gs4d_host_camera_focal(float fov, int width, int height, float out2[2]);                   /* Camera.cpp:95-99  */
+/* Picking: the world point at view depth `depth` (-z_view, e.g. D/O of gs4d_read_aux) on the ray through the centre of pixel (px, py) of a
+ * width x height image — window coordinates (px + 0.5, py + 0.5), row 0 = bottom, as the images; fractional px, py allowed.  With
+ * gs4d_read_aux and gs4d_host_camera_look_at_point this turns the press of a cursor into a camera that looks at what lies under it. */
+GS4D_API void gs4d_host_unproject(const float view[16], const float proj[16], int width, int height, float px, float py, float depth, float world3[3]);
 
 /* Presentation: an RGBA8 frame as produced by gs4d_read_pixels_rgba8_device (bottom row first) -> PNG file */
 GS4D_API int gs4d_host_write_png(const char* path, const uint8_t* rgba8, int width, int height);
