@@ -409,7 +409,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t
     __shared__ uint32_t h[COUNT ? 1024 : 1];
     __shared__ uint32_t kh[FUSE_KEYS ? OS_MAX_PASSES : 1][OS_MAX_BINS];
     __shared__ uint32_t ws[SEG_THREADS / 64 + 1];
-    extern __shared__ uint2 stage[];                       // COUNT == 2: tc.scap entries
+    extern __shared__ __attribute__((aligned(16))) uint2 stage[];      // COUNT == 2: tc.scap entries (copied out 16 bytes at a time: 16-byte base)
     if (COUNT) for (uint32_t b = threadIdx.x; b < tc.nb; b += SEG_THREADS) h[b] = 0u;
     if (FUSE_KEYS && threadIdx.x < 256u) os_hist_clear(kh, threadIdx.x);
     __syncthreads();

@@ -258,11 +258,14 @@ __global__ __launch_bounds__(THREADS) void k_bucket_tiles_staged(const uint2* __
     // ---- the bucket's counts -> prefix over the runs; total, longest run.  Thread t looks after runs [t * RPT, (t + 1) * RPT) ----
     constexpr uint32_t RPT = 1024u / THREADS;
     uint32_t c[RPT], tsum = 0, tmax = 0;
+    bool spill = false;                                     // one of this thread's runs ends beyond its segment's block
 #pragma unroll
     for (uint32_t k = 0; k < RPT; ++k) {
         const uint32_t wseg = tid * RPT + k;
+        const uint32_t o = wseg < rows ? offs[(size_t)b * rows + wseg] : 0u;
         c[k] = wseg < rows ? hist[(size_t)b * rows + wseg] : 0u;
-        ro[wseg] = wseg < rows ? wseg * scap + offs[(size_t)b * rows + wseg] : 0u;
+        ro[wseg] = wseg < rows ? wseg * scap + o : 0u;
+        spill |= o > scap || c[k] > scap - o;
         tsum += c[k]; tmax = max(tmax, c[k]);
     }
     uint32_t pinc = tsum;
@@ -270,21 +273,24 @@ __global__ __launch_bounds__(THREADS) void k_bucket_tiles_staged(const uint2* __
     for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(pinc, off, 64); if (lane >= (unsigned)off) pinc += v; }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) tmax = max(tmax, (uint32_t)__shfl_xor(tmax, off, 64));
+    const bool wspill = __ballot(spill) != 0ull;
     if (lane == 63u) ws[w] = pinc;
-    if (lane == 0u) wm[w] = tmax;
+    if (lane == 0u) { wm[w] = tmax; wb[w] = wspill ? 1u : 0u; }
     __syncthreads();
-    uint32_t T = 0, maxrun = 0, pbase = 0;
+    uint32_t T = 0, maxrun = 0, pbase = 0, spilled = 0;
 #pragma unroll
-    for (int k = 0; k < THREADS / 64; ++k) { if ((unsigned)k < w) pbase += ws[k]; T += ws[k]; maxrun = max(maxrun, wm[k]); }
+    for (int k = 0; k < THREADS / 64; ++k) { if ((unsigned)k < w) pbase += ws[k]; T += ws[k]; maxrun = max(maxrun, wm[k]); spilled |= wb[k]; }
     {
         uint32_t run = pbase + pinc - tsum;
 #pragma unroll
         for (uint32_t k = 0; k < RPT; ++k) { rp[tid * RPT + k] = run; run += c[k]; }
         if (tid == THREADS - 1u) rp[1024] = run;          // (= T; runs beyond `rows` are empty, so rp[rows..1024] == T)
     }
-    // (a segment that overflowed its block wrote no entries and raised the abort word itself; its counts are still true)
+    // A segment that overflowed its block wrote no entries and raised the abort word itself; its counts are still true, so its runs would be
+    // read out of the next segment's block or, for the last segment, past the end of the blocks: a bucket with such a run does not fit either
+    // (checked here rather than by loading the abort word: the bound on every read then follows from the counts this workgroup read itself)
     const uint32_t per = (T + THREADS - 1u) / THREADS;     // entries per thread
-    const bool fits = T <= bcap && per <= (uint32_t)KMAX;   // uniform
+    const bool fits = T <= bcap && per <= (uint32_t)KMAX && !spilled;   // uniform
     if (!fits) {
         if (tid == 0u) { bstat[b] = make_uint4(T, maxrun, 0u, BOX_EMPTY); *abort_word = seq; }
         return;

@@ -9,6 +9,7 @@ never observed.  Through the C ABI, against the CPU checker (image L-infinity <=
 * glClearColor between a draw and its re-run does not repaint the earlier frame.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import pytest
@@ -72,6 +73,8 @@ def test_overflow_rerun_seen_from_another_lane(gs4d, oracle, monkeypatch, path):
         monkeypatch.setenv("GS4D_DRAW_PATH", "ordered")
     else:
         monkeypatch.delenv("GS4D_DRAW_PATH", raising=False)
+    if int(os.environ.get("GS4D_LANES", "4")) < 2:
+        monkeypatch.setenv("GS4D_LANES", "2")                   # the premise: a second lane to move to (whatever the environment asks for)
     W, H = 1001, 701
     cam = ((0.0, 0.0, 30.0), (0.0, 0.0, -1.0))
     view, proj = cam_mats(gs4d, cam, W, H)
