@@ -77,6 +77,9 @@ def _load():
         "gs4d_set_aux_outputs": (i32, [vp, i32]),
         "gs4d_read_aux": (i32, [vp, vp, sz]),
         "gs4d_read_aux_device": (i32, [vp, vp, sz]),
+        "gs4d_set_id_outputs": (i32, [vp, i32]),
+        "gs4d_read_ids": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
+        "gs4d_read_ids_device": (i32, [vp, vp, vp, vp, sz]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -477,6 +480,40 @@ class Context:
     def read_aux_device(self, dptr, nbytes):
         """Raw (D, O) planes to device pointer `dptr` (e.g. a torch tensor's data_ptr()), asynchronously like read_pixels_device."""
         self._chk(_lib.gs4d_read_aux_device(self._h, C.c_void_p(dptr), nbytes))
+
+    # ID outputs: which splat record each pixel shows, for picking and selection (DESIGN.md §4)
+    ID_NONE = 0xFFFFFFFF
+
+    def set_id_outputs(self, on):
+        """Frames cleared from the next clear() on carry {record, draw, weight} per pixel beside the colour — and (D, O), as with
+        set_aux_outputs(True) (default blend function only)."""
+        self._chk(_lib.gs4d_set_id_outputs(self._h, 1 if on else 0))
+
+    def read_ids(self, rect=None):
+        """(record uint32, draw uint32, weight float32), each (h, w), rows bottom-up like read_pixels; rect = (x, y, w, h) with y counted
+        from the bottom row, None = the whole image.  A pixel no fragment reached holds record = draw = ID_NONE and weight 0."""
+        x, y, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        if w <= 0 or h <= 0:
+            self._chk(_lib.gs4d_read_ids(self._h, x, y, w, h, None, None, None))       # refused: the error names the rectangle
+        rec, drw, wt = np.empty((h, w), np.uint32), np.empty((h, w), np.uint32), np.empty((h, w), np.float32)
+        self._chk(_lib.gs4d_read_ids(self._h, x, y, w, h, _ptr(rec), _ptr(drw), _ptr(wt)))
+        return rec, drw, wt
+
+    def read_ids_device(self, record_ptr, draw_ptr, weight_ptr, bytes_per_plane):
+        """The full planes to device pointers (each W * H * 4 bytes; 0 / None skips a plane), asynchronously like read_aux_device."""
+        self._chk(_lib.gs4d_read_ids_device(self._h, C.c_void_p(record_ptr or 0), C.c_void_p(draw_ptr or 0), C.c_void_p(weight_ptr or 0), bytes_per_plane))
+
+    def pick(self, px, py, view, proj):
+        """What pixel (px, py) (column, row from the bottom) of the current frame shows: a dict with the record, its draw, its weight,
+        the pixel's expected depth D / O and the world point at that depth on the pixel's ray (unproject); None where no fragment reached
+        the pixel.  The frame must have been cleared with ID outputs on."""
+        rec, drw, wt = self.read_ids((px, py, 1, 1))
+        if int(rec[0, 0]) == self.ID_NONE:
+            return None
+        do = self.read_aux()[py, px]
+        depth = float(do[0] / do[1]) if do[1] > 0.0 else 0.0
+        return {"record": int(rec[0, 0]), "draw": int(drw[0, 0]), "weight": float(wt[0, 0]), "depth": depth,
+                "point": unproject(view, proj, self.width, self.height, px, py, depth)}
 
     def set_tile_shard(self, rank, world):
         """Single-frame sharding: this context bins and composites the tile rows ty % world == rank only."""

@@ -28,20 +28,23 @@ namespace gs4d {
 // overlay lines, which touch single pixels).  It is what a GL driver's fast clear does with glClear.
 
 // one wave per tile: tiles whose pixels are not in memory get the clear colour — and, in an image with aux outputs (aux != null), the
-// clear aux value (D, O) = (0, 0): a tile in memory has valid aux pixels too
-__global__ __launch_bounds__(64) void k_fill_unwritten(float4* __restrict__ fb, uint32_t* __restrict__ tstate, uint32_t epoch, float4 c, int tiles_x, int W, int H, float2* __restrict__ aux) {
+// clear aux value (D, O) = (0, 0), in an image with ID outputs (ids != null) the sentinel {0xFFFFFFFF, 0xFFFFFFFF, 0.0f}: a tile in
+// memory has valid aux and ID pixels too
+__global__ __launch_bounds__(64) void k_fill_unwritten(float4* __restrict__ fb, uint32_t* __restrict__ tstate, uint32_t epoch, float4 c, int tiles_x, int W, int H, float2* __restrict__ aux,
+                                                       uint32_t* __restrict__ ids) {
     const uint32_t tile = blockIdx.x, lane = threadIdx.x;
     if (tstate[tile] == epoch) return;                      // uniform
     const int px = (int)(tile % (uint32_t)tiles_x) * TILE + (int)(lane & 7u), py = (int)(tile / (uint32_t)tiles_x) * TILE + (int)(lane >> 3);
     if (px < W && py < H) {
         fb[(size_t)py * W + px] = c;
         if (aux) aux[(size_t)py * W + px] = make_float2(0.0f, 0.0f);
+        if (ids) { const size_t P = (size_t)W * H, o = (size_t)py * W + px; ids[o] = ID_NONE; ids[P + o] = ID_NONE; ids[2 * P + o] = 0u; }
     }
     if (lane == 0u) tstate[tile] = epoch;
 }
 
-hipError_t launch_fill_unwritten(hipStream_t st, float4* fb, uint32_t* tstate, uint32_t epoch, int tiles_x, int tiles_y, int W, int H, const float clear[4], float2* aux) {
-    k_fill_unwritten<<<dim3((unsigned)(tiles_x * tiles_y)), dim3(64), 0, st>>>(fb, tstate, epoch, make_float4(clear[0], clear[1], clear[2], clear[3]), tiles_x, W, H, aux);
+hipError_t launch_fill_unwritten(hipStream_t st, float4* fb, uint32_t* tstate, uint32_t epoch, int tiles_x, int tiles_y, int W, int H, const float clear[4], float2* aux, uint32_t* ids) {
+    k_fill_unwritten<<<dim3((unsigned)(tiles_x * tiles_y)), dim3(64), 0, st>>>(fb, tstate, epoch, make_float4(clear[0], clear[1], clear[2], clear[3]), tiles_x, W, H, aux, ids);
     return hipGetLastError();
 }
 
@@ -99,17 +102,20 @@ hipError_t launch_pack_rgba8_band(hipStream_t st, const float4* fb, const uint32
 
 // AUX (default blend function only): the image also has aux outputs — per pixel (D, O), D = sum of w * depth, O = 1 - T, composed onto what
 // the aux plane holds with the same "over" as the colour: (D, O) <- (D_draw + T * D, (1 - T) + T * O); a tile not in memory holds (0, 0).
-template <bool PREMULT_C, bool GENERAL, bool AUX = false>
+// ID (implies AUX): the image also has ID outputs — three W x H planes at ids (record, draw, weight bits); the draw's candidate (largest
+// w > 0, front-most on a tie) is composed over what they hold by id_over (composite_common.h); a tile not in memory holds the sentinel.
+template <bool PREMULT_C, bool GENERAL, bool AUX = false, bool ID = false>
 __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ proj, const uint32_t* __restrict__ pair_vals, uint32_t* __restrict__ ranges,
                                                   const uint32_t* __restrict__ total, int tiles_x, int W, int H, uint32_t* __restrict__ tstate, uint32_t epoch, float4 clear,
-                                                  float4* __restrict__ fb, int dbg_arg, BlendFn bf, float2* __restrict__ aux) {
+                                                  float4* __restrict__ fb, int dbg_arg, BlendFn bf, float2* __restrict__ aux, uint32_t* __restrict__ ids, uint32_t draw_ord) {
     static_assert(!(AUX && GENERAL), "aux outputs are defined for the default blend function only");
+    static_assert(!ID || AUX, "ID outputs come with aux outputs");
 #ifdef GS4D_TUNING
     const int dbg = dbg_arg;             // GS4D_COMPOSITE_DBG: tuning builds only (make TUNING=1)
 #else
     constexpr int dbg = 0; (void)dbg_arg;
 #endif
-    __shared__ float4 stage[64 * 3 + (AUX ? 16 : 0)];       // AUX: the entries' depths behind the three float4 per entry
+    __shared__ float4 stage[64 * 3 + (AUX ? 16 : 0) + (ID ? 16 : 0)];     // AUX: the entries' depths behind the three float4 per entry; ID: then their record indices
     __shared__ uint32_t pmask[64 * 2];                      // per pixel: 64-bit mask of the chunk entries that cover it
     if (total[1]) return;                                   // tile lists overflowed: nothing was emitted, the host re-runs
     uint32_t tile;
@@ -123,7 +129,8 @@ __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ pro
     if (start >= end) return;                               // uniform: nothing is drawn on this tile — its pixels, or its being clear, stay as they are
     const bool fb_is_clear = tstate[tile] != epoch;         // uniform: the tile's pixels are not in memory yet
 
-    float T = 1.0f, Cr = 0.0f, Cg = 0.0f, Cb = 0.0f, A = 0.0f, D = 0.0f;
+    float T = 1.0f, Cr = 0.0f, Cg = 0.0f, Cb = 0.0f, A = 0.0f, D = 0.0f, BW = 0.0f;
+    uint32_t BR = ID_NONE;
     if (GENERAL) {
         // a blend function other than the default: no transmittance form — the pixel's value is taken through the list in draw order
         const bool in = px < W && py < H;
@@ -143,7 +150,9 @@ __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ pro
         const uint32_t cnt = min(64u, hi - start);
         // lane s holds list entry hi-1-s : s = 0 is the LAST (front-most) entry of this chunk
         const uint32_t rec = lane < cnt ? pair_vals[hi - 1u - lane] : 0u;
-        if (AUX) composite_chunk<PREMULT_C, false, true>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, T, Cr, Cg, Cb, A, bf, reinterpret_cast<float*>(stage + 64 * 3), &D);
+        if (ID) composite_chunk<PREMULT_C, false, true, true>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, T, Cr, Cg, Cb, A, bf, reinterpret_cast<float*>(stage + 64 * 3), &D,
+                                                              reinterpret_cast<uint32_t*>(stage + 64 * 3 + 16), &BW, &BR);
+        else if (AUX) composite_chunk<PREMULT_C, false, true>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, T, Cr, Cg, Cb, A, bf, reinterpret_cast<float*>(stage + 64 * 3), &D);
         else composite_chunk<PREMULT_C>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, T, Cr, Cg, Cb, A);
         hi -= cnt;
         if (__ballot(T > 0.0f) == 0ull) break;              // exact: every remaining contribution is multiplied by T == 0
@@ -156,12 +165,14 @@ __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ pro
             const float2 q = fb_is_clear ? make_float2(0.0f, 0.0f) : aux[o];
             aux[o] = make_float2(D + T * q.x, (1.0f - T) + T * q.y);
         }
+        if (ID) id_over(ids, (size_t)W * H, o, fb_is_clear, T, BW, BR, draw_ord);
     }
     if (lane == 0u) tstate[tile] = epoch;
 }
 
 hipError_t launch_composite(hipStream_t st, const float4* proj, const uint32_t* pair_vals, uint32_t* ranges, const uint32_t* total, int tiles_x, int tiles_y,
-                            int W, int H, int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, int blend_src, int blend_dst, float2* aux) {
+                            int W, int H, int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, int blend_src, int blend_dst, float2* aux,
+                            uint32_t* ids, uint32_t draw_ord) {
     const float4 c = make_float4(clear[0], clear[1], clear[2], clear[3]);
     const dim3 grid(composite_grid(tiles_x, tiles_y));
 #ifdef GS4D_TUNING
@@ -172,16 +183,21 @@ hipError_t launch_composite(hipStream_t st, const float4* proj, const uint32_t* 
     const BlendFn bf{ blend_src, blend_dst };
     const bool general = !(blend_src == GS4D_SRC_ALPHA && blend_dst == GS4D_ONE_MINUS_SRC_ALPHA);
     if (general && aux) return hipErrorInvalidValue;       // the host refuses such a draw (GS4D_E_UNSUPPORTED) before it gets here
+    if (ids && !aux) return hipErrorInvalidValue;          // ID outputs come with aux outputs
     if (general) {
-        if (premult_c) k_composite<true, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr);
-        else           k_composite<false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr);
+        if (premult_c) k_composite<true, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr, nullptr, 0u);
+        else           k_composite<false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr, nullptr, 0u);
+    }
+    else if (ids) {
+        if (premult_c) k_composite<true, false, true, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux, ids, draw_ord);
+        else           k_composite<false, false, true, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux, ids, draw_ord);
     }
     else if (aux) {
-        if (premult_c) k_composite<true, false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux);
-        else           k_composite<false, false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux);
+        if (premult_c) k_composite<true, false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux, nullptr, 0u);
+        else           k_composite<false, false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux, nullptr, 0u);
     }
-    else if (premult_c) k_composite<true, false><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr);
-    else                k_composite<false, false><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr);
+    else if (premult_c) k_composite<true, false><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr, nullptr, 0u);
+    else                k_composite<false, false><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr, nullptr, 0u);
     return hipGetLastError();
 }
 

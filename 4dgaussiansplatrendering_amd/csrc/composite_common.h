@@ -86,10 +86,13 @@ __device__ __forceinline__ float gauss_weight(float u, float v) { return __built
 __device__ __forceinline__ float clamp01(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f); }
 
 // AUX (default function only): also D += w * d, with the weight w the colour uses and d the entry's depth (projected record, slot 15).
-template <bool PREMULT_C, bool GENERAL = false, bool AUX = false>
+// ID (implies AUX): also the draw's candidate — (*BW, *BR) <- (w, rid) when w > *BW: walked front to back from *BW = 0, that is the largest
+// w > 0, the front-most of equal weights.  A lane without a fragment blends with al = 0, so w = 0 and it never takes.
+template <bool PREMULT_C, bool GENERAL = false, bool AUX = false, bool ID = false>
 __device__ __forceinline__ void blend_fragment(float u, float v, float alpha, float r_, float g_, float b_, float& T, float& Cr, float& Cg, float& Cb, float& A, BlendFn bf = BlendFn{ 0, 0 },
-                                               float d = 0.0f, float* D = nullptr) {
+                                               float d = 0.0f, float* D = nullptr, uint32_t rid = 0u, float* BW = nullptr, uint32_t* BR = nullptr) {
     static_assert(!(AUX && GENERAL), "aux outputs are defined for the default blend function only");
+    static_assert(!ID || AUX, "ID outputs come with aux outputs");
     const float cg = gauss_weight(u, v);
     if (GENERAL) {
         if (cg >= 0.0001f) {                               // Splat4DFragShader.GLSL:30 discard
@@ -109,17 +112,36 @@ __device__ __forceinline__ void blend_fragment(float u, float v, float alpha, fl
     if (PREMULT_C) { r_ = clamp01(r_ * cg); g_ = clamp01(g_ * cg); b_ = clamp01(b_ * cg); }   // Splat3DFragShaderFull.GLSL:22
     Cr += w * r_; Cg += w * g_; Cb += w * b_; A += w * al;
     if (AUX) *D += w * d;
+    if (ID) { const bool take = w > *BW; *BW = take ? w : *BW; *BR = take ? rid : *BR; }
     T *= (1.0f - al);
+}
+
+// ID outputs: three W x H planes of u32 at ids, ids + P, ids + 2 P (P = W * H): the record, the draw ordinal and the bits of
+// the weight.  A pixel no fragment has reached holds the sentinel {ID_NONE, ID_NONE, 0.0f}.
+constexpr uint32_t ID_NONE = 0xFFFFFFFFu;
+// One pixel at the end of a draw: its candidate (BW, BR; BW == 0: none) composed over the stored triple with the colour's "over" — the stored
+// weight is scaled by the draw's final transmittance T, and the candidate replaces the triple when its weight is at least that (the newer
+// draw is in front: ties go to it).  fb_is_clear (uniform): the tile is not in memory, the stored triple is the sentinel.
+__device__ __forceinline__ void id_over(uint32_t* __restrict__ ids, size_t P, size_t o, bool fb_is_clear, float T, float BW, uint32_t BR, uint32_t draw) {
+    uint32_t r = ID_NONE, dr = ID_NONE;
+    float w = 0.0f;
+    if (!fb_is_clear) { r = ids[o]; dr = ids[P + o]; w = __uint_as_float(ids[2 * P + o]); }
+    w = T * w;
+    const bool take = BW > 0.0f && BW >= w;
+    ids[o] = take ? BR : r;
+    ids[P + o] = take ? draw : dr;
+    ids[2 * P + o] = __float_as_uint(take ? BW : w);
 }
 
 // One chunk of the tile's list, front to back: lane s < cnt carries record `rec` of list entry (end of chunk - 1 - s), so s = 0 is the
 // front-most entry.  stage: 64 x 3 float4, pmask: 64 x 2 words (per pixel: 64-bit mask of the chunk entries that cover it).
 // GENERAL: the chunk is walked in DRAW order instead — lane s carries list entry (start of chunk + s).
 // AUX: the entry's depth (the last float of the same 64-byte record) is staged beside it in dstage (64 floats) and accumulated into *D.
-template <bool PREMULT_C, bool GENERAL = false, bool AUX = false>
+// ID (implies AUX): the entry's record index is staged beside it in rstage (64 words); the pixel's candidate goes to (*BW, *BR).
+template <bool PREMULT_C, bool GENERAL = false, bool AUX = false, bool ID = false>
 __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj, uint32_t rec, uint32_t cnt, uint32_t lane, int tx0, int ty0, float fx, float fy,
                                                 float4* stage, uint32_t* pmask, int dbg, float& T, float& Cr, float& Cg, float& Cb, float& A, BlendFn bf = BlendFn{ 0, 0 },
-                                                float* dstage = nullptr, float* D = nullptr) {
+                                                float* dstage = nullptr, float* D = nullptr, uint32_t* rstage = nullptr, float* BW = nullptr, uint32_t* BR = nullptr) {
     // lane s holds list entry hi-1-s : s = 0 is the LAST (front-most) entry of this chunk
     int lx0 = 0, ly0 = 0, bw = 0, bh = 0;
     float4 ra = make_float4(0, 0, 0, 0), rb = ra;
@@ -131,6 +153,7 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
         stage[lane * 3 + 1] = rb;
         stage[lane * 3 + 2] = rc;
         if (AUX) dstage[lane] = reinterpret_cast<const float*>(r)[15];
+        if (ID) rstage[lane] = rec;
         const uint32_t r0 = __float_as_uint(rc.z), r1 = __float_as_uint(rc.w);
         lx0 = max((int)(r0 & 0xFFFFu) - tx0, 0); ly0 = max((int)(r0 >> 16) - ty0, 0);
         const int lx1 = min((int)(r1 & 0xFFFFu) - tx0, TILE - 1), ly1 = min((int)(r1 >> 16) - ty0, TILE - 1);
@@ -153,7 +176,8 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const bool cov = fabsf(u) <= 0.5f && fabsf(v) <= 0.5f;
             if (__ballot(cov) == 0ull) continue;
             const float4 c = stage[s * 3 + 2];          // b, alpha, -, -
-            if (AUX) { const float d = dstage[s]; if (cov) blend_fragment<PREMULT_C, false, true>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, d, D); }
+            if (ID) { const float d = dstage[s]; const uint32_t rid = rstage[s]; if (cov) blend_fragment<PREMULT_C, false, true, true>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, d, D, rid, BW, BR); }
+            else if (AUX) { const float d = dstage[s]; if (cov) blend_fragment<PREMULT_C, false, true>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, d, D); }
             else if (cov) blend_fragment<PREMULT_C, GENERAL>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf);
         }
     } else {
@@ -213,6 +237,7 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const float u = __fmaf_rn(a.z, dx, __fmul_rn(b.x, dy));
             const float v = __fmaf_rn(a.w, dx, __fmul_rn(b.y, dy));
             if (GENERAL) { if (on) blend_fragment<PREMULT_C, true>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf); }
+            else if (ID) blend_fragment<PREMULT_C, false, true, true>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, dstage[e], D, rstage[e], BW, BR);
             else if (AUX) blend_fragment<PREMULT_C, false, true>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, dstage[e], D);
             else blend_fragment<PREMULT_C, false>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, T, Cr, Cg, Cb, A);
         }

@@ -80,6 +80,8 @@ struct DrawArgs {
     bool exact_lists = false;         // the re-run of a staged draw whose blocks, runs or buckets did not fit: builds its lists exactly (scan + scatter)
     uint64_t stage_geom = 0;        // set by run_draw: the list geometry the draw's bucket statistics belong to (resolve_lane files them under it)
     bool aux = false;               // the image's frame was cleared with aux outputs on: depth into the projected records, (D, O) into the aux plane
+    bool ids = false;               // ... with ID outputs on (aux is then on too): the candidate {record, draw, weight} into the ID planes
+    uint32_t draw_ord = 0;          // the draw's ordinal within its frame (a re-run keeps it)
 };
 
 struct Framebuffer {
@@ -95,6 +97,9 @@ struct Framebuffer {
     // Aux outputs: one float2 {D, O} per pixel, allocated with the image once gs4d_set_aux_outputs has been on.  aux_on: this
     // image's frame was cleared with aux outputs on — its compositing kernels and k_fill_unwritten keep the plane valid for every tile in memory.
     float2* aux = nullptr; bool aux_on = false;
+    // ID outputs: three W * H u32 planes — record, draw, weight bits — in one allocation, made once gs4d_set_id_outputs has
+    // been on.  ids_on: this image's frame was cleared with ID outputs on (then aux_on too).  draws: splat draws into the frame since its clear.
+    uint32_t* ids = nullptr; bool ids_on = false; uint32_t draws = 0;
 };
 
 struct Lane {
@@ -170,6 +175,8 @@ struct gs4d_ctx {
     bool rename_storage = true;        // GS4D_RENAME=0 switches the storage exchange off (test hook)
     bool aux_enable = false;           // gs4d_set_aux_outputs: the frames cleared from now on have aux outputs
     bool aux_alloc = false;            // ... has been on once: every image has its aux plane (gs4d_resize reallocates it)
+    bool ids_enable = false;           // gs4d_set_id_outputs: the frames cleared from now on have ID outputs (and aux outputs)
+    bool ids_alloc = false;            // ... has been on once: every image has its ID planes (gs4d_resize reallocates them)
     int shrink_votes = 0;
     // Two ways to get a tile's list into blend order.  Lists of up to V2_MAX_LIST entries: built unordered, ordered by the wave that
     // composites the tile (k_composite_v2).  Longer lists, or a blend order that is not a key the library knows: the instance-ordered path
@@ -348,7 +355,7 @@ int materialise_fb(gs4d_ctx* c) {
     Framebuffer& F = c->fbs[c->cur_fb];
     if (!F.all_in_memory) {
         int rc = fb_access(c, F); if (rc) return rc;
-        HIPCHK(c, launch_fill_unwritten(lane(c).s, F.mem, F.tstate, F.epoch, c->tiles_x, c->tiles_y, c->W, c->H, F.clear, F.aux_on ? F.aux : nullptr));
+        HIPCHK(c, launch_fill_unwritten(lane(c).s, F.mem, F.tstate, F.epoch, c->tiles_x, c->tiles_y, c->W, c->H, F.clear, F.aux_on ? F.aux : nullptr, F.ids_on ? F.ids : nullptr));
         F.all_in_memory = true;
         F.is_clear = false;
     }
@@ -380,7 +387,7 @@ int enqueue_raster(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, cons
         StageTimer t(c, GS4D_T_COMPOSITE);      // the per-tile ranges and the compositing kernel
         HIPCHK(c, launch_tile_ranges(L.s, L.bin, L.pair_keys, L.pair_cap, ntiles));
         HIPCHK(c, launch_composite(L.s, L.proj, L.pair_vals, L.bin.ranges, L.bin.total, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, F.tstate, F.epoch, a.clear, F.mem, blend_src, blend_dst,
-                                   a.aux ? F.aux : nullptr));
+                                   a.aux ? F.aux : nullptr, a.ids ? F.ids : nullptr, a.draw_ord));
     }
     return GS4D_OK;
 }
@@ -418,7 +425,8 @@ int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, s
     {
         StageTimer t(c, GS4D_T_COMPOSITE);
         HIPCHK(c, launch_composite_v2(L.s, L.proj, entries, L.tl.tstart, L.tl.tcnt, L.bin.total, L.host_total_dev, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, F.tstate, F.epoch, a.clear, F.mem,
-                                      c->list_hint, a.keybits, recbits, L.tl.slabs, L.tl.bstat, L.tl.nb, L.tl.sstat, L.tl.rows, L.tl.staged ? L.tl.seq : 0u, 0xFFFFFFFFu, L.tl.scap, L.tl.bcap, L.tl.box, a.aux ? F.aux : nullptr));
+                                      c->list_hint, a.keybits, recbits, L.tl.slabs, L.tl.bstat, L.tl.nb, L.tl.sstat, L.tl.rows, L.tl.staged ? L.tl.seq : 0u, 0xFFFFFFFFu, L.tl.scap, L.tl.bcap, L.tl.box, a.aux ? F.aux : nullptr,
+                                      a.ids ? F.ids : nullptr, a.draw_ord));
     }
     { const uint32_t b = L.tl.staged ? L.tl.box : BOX_NONE; c->stat_composited_tiles = b == BOX_NONE ? ntiles : (uint64_t)std::min<uint32_t>((((b >> 16) & 255u) - (b & 255u) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_x) * std::min<uint32_t>(((b >> 24) - ((b >> 8) & 255u) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_y); }
     HIPCHK(c, hipEventRecord(L.ev_emit, L.s));         // totals, flags and the longest list are in pinned host memory behind this event (the compositor's first workgroup wrote them)
@@ -701,9 +709,11 @@ int alloc_fbs(gs4d_ctx* c, int w, int h) {
         if (c->fbs[i].tstate) { (void)hipFree(c->fbs[i].tstate); c->fbs[i].tstate = nullptr; }
         if (c->fbs[i].linecnt) { (void)hipFree(c->fbs[i].linecnt); c->fbs[i].linecnt = nullptr; }
         if (c->fbs[i].aux) { (void)hipFree(c->fbs[i].aux); c->fbs[i].aux = nullptr; }
-        c->fbs[i].aux_on = false;                                // no frame of this size has been cleared yet
+        if (c->fbs[i].ids) { (void)hipFree(c->fbs[i].ids); c->fbs[i].ids = nullptr; }
+        c->fbs[i].aux_on = false; c->fbs[i].ids_on = false;      // no frame of this size has been cleared yet
         HIPCHK(c, hipMalloc(&c->fbs[i].mem, (size_t)w * h * 16));
         if (c->aux_alloc) HIPCHK(c, hipMalloc(&c->fbs[i].aux, (size_t)w * h * 8));
+        if (c->ids_alloc) HIPCHK(c, hipMalloc(&c->fbs[i].ids, (size_t)w * h * 12));
         const size_t nt = (size_t)((w + TILE - 1) / TILE) * ((h + TILE - 1) / TILE);
         HIPCHK(c, hipMalloc(&c->fbs[i].tstate, nt * 4));
         HIPCHK(c, hipMemset(c->fbs[i].tstate, 0, nt * 4));      // no tile is in memory: epochs start at 1
@@ -844,6 +854,7 @@ void gs4d_destroy(gs4d_ctx* c) {
         if (c->fbs[i].tstate) (void)hipFree(c->fbs[i].tstate);
         if (c->fbs[i].linecnt) (void)hipFree(c->fbs[i].linecnt);
         if (c->fbs[i].aux) (void)hipFree(c->fbs[i].aux);
+        if (c->fbs[i].ids) (void)hipFree(c->fbs[i].ids);
         if (L.line_verts) (void)hipFree(L.line_verts);
         if (L.order_copy) (void)hipFree(L.order_copy);
         if (L.regen_keys) (void)hipFree(L.regen_keys);
@@ -1025,7 +1036,9 @@ int gs4d_clear(gs4d_ctx* c) {
     {
         Framebuffer& F = c->fbs[c->cur_fb];
         F.is_clear = true; F.all_in_memory = false;
-        F.aux_on = c->aux_enable && F.aux;                  // the new epoch makes every tile clear: (D, O) = (0, 0) without touching the plane
+        F.ids_on = c->ids_enable && F.ids && F.aux;         // the new epoch makes every tile clear: the ID sentinel without touching the planes
+        F.aux_on = (c->aux_enable || F.ids_on) && F.aux;    // ... and (D, O) = (0, 0); ID outputs imply aux outputs
+        F.draws = 0;
         if (++F.epoch == 0u) {                              // the 32-bit epoch wraps: forget every old tile word (the lane that used the image last has long finished)
             HIPCHK(c, fb_access(c, F) == GS4D_OK ? hipMemsetAsync(F.tstate, 0, (size_t)c->tiles_x * c->tiles_y * 4, lane(c).s) : hipErrorUnknown);
             F.epoch = 1;
@@ -1186,9 +1199,10 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
                      && P[12] == 0.0f && P[13] == 0.0f && P[15] == 0.0f && P[11] != 0.0f && P[0] != 0.0f && P[5] != 0.0f;
         if (!ok) return fail(c, GS4D_E_UNSUPPORTED, "draw: uProj must have the sparsity of glm::perspective (P00, P11, P22, P23, P32 only)");
     }
-    // aux outputs are the transmittance form of the default blend function: any other function has none (nothing is drawn)
+    // aux and ID outputs are the transmittance form of the default blend function: any other function has none (nothing is drawn)
     if (c->fbs[c->cur_fb].aux_on && !(c->blend_src == GS4D_SRC_ALPHA && c->blend_dst == GS4D_ONE_MINUS_SRC_ALPHA))
-        return fail(c, GS4D_E_UNSUPPORTED, "draw: aux outputs are defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only");
+        return fail(c, GS4D_E_UNSUPPORTED, c->fbs[c->cur_fb].ids_on ? "draw: ID outputs are defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only"
+                                                                    : "draw: aux outputs are defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only");
     // the lane's scratch still belongs to its previous draw, and the image this draw blends onto must be complete: validate those
     // (not the other lanes' draws: their frames are still in flight and nothing here depends on them)
     int rc = resolve_lane(c, c->cur); if (rc) return rc;
@@ -1204,6 +1218,7 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     a.blend_src = c->blend_src; a.blend_dst = c->blend_dst;
     const bool over = a.blend_src == GS4D_SRC_ALPHA && a.blend_dst == GS4D_ONE_MINUS_SRC_ALPHA;       // any other function is applied in draw order: instance-ordered lists
     a.aux = c->fbs[c->cur_fb].aux_on;
+    a.ids = c->fbs[c->cur_fb].ids_on; a.draw_ord = c->fbs[c->cur_fb].draws;
     if (c->atomic_rank && c->path_pref != 1 && over) {
         Buffer* data = getbuf(c, a.data);
         bool ok = false;
@@ -1247,6 +1262,7 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     rc = run_draw(c, a, true);
     a.fuse = false;                    // a re-run of this draw finds the keys written and the sort queued
     if (rc) { L.proj_n = before; return rc; }
+    c->fbs[a.fb].draws++;                                   // the next splat draw into this frame has the next ordinal
     if (L.proj_n) { L.pending = true; L.pending_args = a; c->fbs[c->cur_fb].is_clear = false; L.drawn = true; if (a.v2) c->stat_v2_draws++; }   // proj_n != 0 <=> raster work was enqueued
     else L.proj_n = before;
     if (c->profiling) { if (c->prof_frame < gs4d_ctx::PROF_FRAMES && c->prof_tick % (uint64_t)c->prof_every == 0) c->prof_frame++; c->prof_tick++; }
@@ -1334,8 +1350,10 @@ int gs4d_read_pixels(gs4d_ctx* c, float* rgba, size_t bytes) {
 // frames_back 0: the image the last clear / draw used.  1: the image the last gs4d_clear moved away from (the previous frame of the
 // swap chain) — it is packed on the lane that rendered it, behind its compositing kernel, so an application that reads frame f-1
 // after queueing frame f never waits for frame f.
-// aux: the image's aux plane instead of its colour (W * H float2, frames_back 0 only).
-static int read_device_common(gs4d_ctx* c, int frames_back, void* dptr, bool rgba8, bool named_event = false, hipEvent_t after = nullptr, bool aux = false) {
+// aux: the image's aux plane instead of its colour (W * H float2, frames_back 0 only).  ids_dst: the image's ID planes instead (W * H u32
+// each, into the non-null ones of record, draw, weight; frames_back 0 only).
+static int read_device_common(gs4d_ctx* c, int frames_back, void* dptr, bool rgba8, bool named_event = false, hipEvent_t after = nullptr, bool aux = false,
+                              void* const* ids_dst = nullptr) {
     if (frames_back != 0 && frames_back != 1) return fail(c, GS4D_E_INVALID, "read_frame: frames_back must be 0 or 1");
     const int fi = frames_back == 0 ? c->cur_fb : c->prev_fb;
     if (fi < 0) return fail(c, GS4D_E_INVALID, "read_frame: no previous image is retained (one frame lane, or no gs4d_clear yet)");
@@ -1351,8 +1369,9 @@ static int read_device_common(gs4d_ctx* c, int frames_back, void* dptr, bool rgb
     if (li == c->cur) { rc = fb_access(c, F); if (rc) return rc; }
     if (rgba8) HIPCHK(c, launch_pack_rgba8(L.s, F.mem, F.tstate, F.epoch, F.clear, c->W, c->H, c->tiles_x, (uint32_t*)dptr));      // lazily clear tiles are packed as the clear colour
     else {
-        if (!F.all_in_memory) { HIPCHK(c, launch_fill_unwritten(L.s, F.mem, F.tstate, F.epoch, c->tiles_x, c->tiles_y, c->W, c->H, F.clear, F.aux_on ? F.aux : nullptr)); F.all_in_memory = true; F.is_clear = false; }
-        if (aux) HIPCHK(c, hipMemcpyAsync(dptr, F.aux, (size_t)c->W * c->H * 8, hipMemcpyDeviceToDevice, L.s));
+        if (!F.all_in_memory) { HIPCHK(c, launch_fill_unwritten(L.s, F.mem, F.tstate, F.epoch, c->tiles_x, c->tiles_y, c->W, c->H, F.clear, F.aux_on ? F.aux : nullptr, F.ids_on ? F.ids : nullptr)); F.all_in_memory = true; F.is_clear = false; }
+        if (ids_dst) { for (int k = 0; k < 3; ++k) if (ids_dst[k]) HIPCHK(c, hipMemcpyAsync(ids_dst[k], F.ids + (size_t)k * c->W * c->H, (size_t)c->W * c->H * 4, hipMemcpyDeviceToDevice, L.s)); }
+        else if (aux) HIPCHK(c, hipMemcpyAsync(dptr, F.aux, (size_t)c->W * c->H * 8, hipMemcpyDeviceToDevice, L.s));
         else HIPCHK(c, hipMemcpyAsync(dptr, F.mem, (size_t)c->W * c->H * 16, hipMemcpyDeviceToDevice, L.s));
     }
     if (li != c->cur) HIPCHK(c, hipEventRecord(L.ev_tail, L.s));      // the lane's tail event keeps covering everything queued on it
@@ -1407,6 +1426,52 @@ int gs4d_read_aux_device(gs4d_ctx* c, void* dptr, size_t bytes) {
     if (bytes != (size_t)c->W * c->H * 8) return fail(c, GS4D_E_INVALID, "read_aux_device: bytes != width*height*8");
     if (!c->fbs[c->cur_fb].aux_on) return fail(c, GS4D_E_INVALID, "read_aux_device: the current frame was not cleared with aux outputs on");
     return read_device_common(c, 0, dptr, false, false, nullptr, true);
+}
+
+// ---- ID outputs ----
+int gs4d_set_id_outputs(gs4d_ctx* c, int enable) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    if (enable && !c->ids_alloc) {
+        // new planes beside the images (nothing running reads or writes them yet: no frame has been cleared with ID outputs on); ID outputs
+        // come with aux outputs, so the aux planes too
+        for (int i = 0; i < c->nlanes; ++i) {
+            if (!c->fbs[i].aux) HIPCHK(c, hipMalloc(&c->fbs[i].aux, (size_t)c->W * c->H * 8));
+            if (!c->fbs[i].ids) HIPCHK(c, hipMalloc(&c->fbs[i].ids, (size_t)c->W * c->H * 12));
+        }
+        c->aux_alloc = c->ids_alloc = true;
+    }
+    c->ids_enable = enable != 0;                            // takes effect at the next gs4d_clear
+    return GS4D_OK;
+}
+
+int gs4d_read_ids(gs4d_ctx* c, int x, int y, int w, int h, uint32_t* record, uint32_t* draw, float* weight) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    { int rcq = flush_order(c); if (rcq) return rcq; }
+    if (x < 0 || y < 0 || w <= 0 || h <= 0 || w > c->W - x || h > c->H - y) return fail(c, GS4D_E_INVALID, "read_ids: the rectangle is not inside the image");
+    if (!c->fbs[c->cur_fb].ids_on) return fail(c, GS4D_E_INVALID, "read_ids: the current frame was not cleared with ID outputs on");
+    int rc = resolve_image(c, c->cur_fb); if (rc) return rc;
+    rc = materialise_fb(c); if (rc) return rc;
+    Framebuffer& F = c->fbs[c->cur_fb];
+    rc = fb_access(c, F); if (rc) return rc;
+    void* const dst[3] = { record, draw, weight };
+    const size_t plane = (size_t)c->W * c->H, pitch = (size_t)c->W * 4;
+    for (int k = 0; k < 3; ++k)
+        if (dst[k]) HIPCHK(c, hipMemcpy2DAsync(dst[k], (size_t)w * 4, F.ids + k * plane + (size_t)y * c->W + x, pitch, (size_t)w * 4, (size_t)h, hipMemcpyDeviceToHost, lane(c).s));
+    HIPCHK(c, hipStreamSynchronize(lane(c).s));
+    if (device_error(c)) return fail(c, GS4D_E_DEVICE, DEVICE_CHECK_MSG);
+    return GS4D_OK;
+}
+
+int gs4d_read_ids_device(gs4d_ctx* c, void* record, void* draw, void* weight, size_t bytes_per_plane) {
+    if (!c || (!record && !draw && !weight)) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    { int rcq = flush_order(c); if (rcq) return rcq; }
+    if (bytes_per_plane != (size_t)c->W * c->H * 4) return fail(c, GS4D_E_INVALID, "read_ids_device: bytes_per_plane != width*height*4");
+    if (!c->fbs[c->cur_fb].ids_on) return fail(c, GS4D_E_INVALID, "read_ids_device: the current frame was not cleared with ID outputs on");
+    void* const dst[3] = { record, draw, weight };
+    return read_device_common(c, 0, nullptr, false, false, nullptr, false, dst);
 }
 
 int gs4d_read_pixels_rgba8_device(gs4d_ctx* c, void* dptr, size_t bytes) {

@@ -206,7 +206,7 @@ hipError_t tile_lists_reserve_blocks(hipStream_t st, TileLists& t, size_t entrie
 hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* entries, const uint32_t* tstart, const uint32_t* tcnt, const uint32_t* total, uint32_t* total_host, int tiles_x, int tiles_y, int W, int H,
                                int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, uint32_t hint, int keybits, int recbits, uint32_t slabs,
                                const uint4* bstat = nullptr, uint32_t nb = 0, const uint32_t* sstat = nullptr, uint32_t rows = 0, uint32_t stage_seq = 0, uint32_t rcap = 0, uint32_t scap = 0, uint32_t bcap = 0, uint32_t box_blocks = 0xFFFFFFFFu,
-                               float2* aux = nullptr);
+                               float2* aux = nullptr, uint32_t* ids = nullptr, uint32_t draw_ord = 0u);
 
 #ifdef __HIPCC__
 // tiles touched by a pixel rectangle (x0|y0<<16, x1|y1<<16; x0 > x1: none), restricted to the tile rows ty % world == rank
@@ -284,9 +284,13 @@ hipError_t launch_tile_ranges(hipStream_t st, BinScratch& b, const uint32_t* pai
 // ---- composite.hip ----
 // tstate / epoch: the image's tile state (composite.hip): tstate[tile] == epoch <=> the tile's pixels are in memory, else it is still the clear colour
 // aux: the image's aux plane (float2 {D, O} per pixel) when its frame was cleared with aux outputs on, else null
+// ids: the image's three ID planes (record, draw, weight bits; W * H u32 each) when its frame was cleared with ID outputs on (aux is then
+// set too), else null; draw_ord: the draw's ordinal within its frame
 hipError_t launch_composite(hipStream_t st, const float4* proj, const uint32_t* pair_vals, uint32_t* ranges, const uint32_t* total, int tiles_x, int tiles_y,
-                            int W, int H, int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, int blend_src, int blend_dst, float2* aux = nullptr);
-hipError_t launch_fill_unwritten(hipStream_t st, float4* fb, uint32_t* tstate, uint32_t epoch, int tiles_x, int tiles_y, int W, int H, const float clear[4], float2* aux = nullptr);
+                            int W, int H, int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, int blend_src, int blend_dst, float2* aux = nullptr,
+                            uint32_t* ids = nullptr, uint32_t draw_ord = 0u);
+hipError_t launch_fill_unwritten(hipStream_t st, float4* fb, uint32_t* tstate, uint32_t epoch, int tiles_x, int tiles_y, int W, int H, const float clear[4], float2* aux = nullptr,
+                                 uint32_t* ids = nullptr);
 hipError_t launch_pack_rgba8(hipStream_t st, const float4* fb, const uint32_t* tstate, uint32_t epoch, const float clear[4], int W, int H, int tiles_x, uint32_t* out);
 // the pixel rows of the tile rows ty % world == rank, top of the band = the context's first tile row; band_rows pixel rows in all
 hipError_t launch_pack_rgba8_band(hipStream_t st, const float4* fb, const uint32_t* tstate, uint32_t epoch, const float clear[4], int W, int H, int tiles_x, int rank, int world, int band_rows, uint32_t* out);

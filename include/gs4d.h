@@ -177,6 +177,30 @@ GS4D_API int gs4d_read_aux(gs4d_ctx* ctx, float* depth_opacity, size_t bytes);
 /* The same, device-to-device and asynchronous, ordered as gs4d_read_pixels_device (into the caller's stream if one was given). */
 GS4D_API int gs4d_read_aux_device(gs4d_ctx* ctx, void* dptr, size_t bytes);
 
+/* ---- ID outputs: which splat record a pixel shows, for picking and selection (no reference counterpart) ----
+ * A frame cleared with ID outputs on keeps, beside its colour, three values per pixel: the record that contributes most to the pixel's
+ * final colour, the draw of the frame it came from, and its weight in that colour.  Default blend function only.  Within one draw, each
+ * fragment has the weight w_j = T_j * al_j its colour accumulates with (T draw-local, from 1, front to back); the draw's candidate is the
+ * fragment with the largest w_j > 0, the front-most on a tie.  With T_final the draw's final transmittance at the pixel, the draw then
+ * composes its candidate over the stored {record, draw, weight} with the colour's "over":
+ *     weight <- T_final * weight;  if a candidate exists and w_cand >= weight: {record, draw, weight} <- {rec_cand, draw ordinal, w_cand}.
+ * record: the index into the data buffer of the record the fragment came from (GS4D_MODE_4D_SORTED: the sort index's entry, not the
+ * instance; GS4D_MODE_4D_DIRECT, GS4D_MODE_2D: the instance; gs4d_draw_quads: the quad).  draw: 0 for the first gs4d_draw_instanced /
+ * gs4d_draw_quads after gs4d_clear, 1 for the next, ...; overlay lines (gs4d_draw_lines) are no draw and leave the planes as they are.
+ * A pixel no fragment has reached holds record = draw = 0xFFFFFFFF and weight 0.  A frame with ID outputs also has aux outputs
+ * (gs4d_read_aux*), and a draw with any other blend function returns GS4D_E_UNSUPPORTED and draws nothing. */
+/* enable != 0: the frames cleared from the next gs4d_clear on have ID (and aux) outputs; 0: they do not.  The first enable allocates three
+ * W*H*4-byte planes (and the aux plane) per image of the swap chain (gs4d_resize reallocates them); nothing is allocated while ID outputs
+ * have never been on. */
+GS4D_API int gs4d_set_id_outputs(gs4d_ctx* ctx, int enable);
+/* Blocking: the w x h rectangle at (x, y) into w*h-element arrays, rows in gs4d_read_pixels' order (row 0 = bottom; element [r * w + c] is
+ * pixel (x + c, y + r)).  Any output pointer may be NULL.  A 1x1 read is a pick.  GS4D_E_INVALID for a rectangle not inside the image, or
+ * when the current frame was not cleared with ID outputs on. */
+GS4D_API int gs4d_read_ids(gs4d_ctx* ctx, int x, int y, int w, int h, uint32_t* record, uint32_t* draw, float* weight);
+/* The full planes (bytes_per_plane == width*height*4 each; NULL skips a plane, not all three), device-to-device and asynchronous, ordered as
+ * gs4d_read_aux_device. */
+GS4D_API int gs4d_read_ids_device(gs4d_ctx* ctx, void* record, void* draw, void* weight, size_t bytes_per_plane);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
