@@ -27,9 +27,8 @@ namespace gs4d {
 // substitutes the clear colour for the others (the RGBA8 packs) or writes it first (k_fill_unwritten: host read-backs, float copies,
 // overlay lines, which touch single pixels).  It is what a GL driver's fast clear does with glClear.
 
-// one wave per tile: tiles whose pixels are not in memory get the clear colour — and, in an image with aux outputs (aux != null), the
-// clear aux value (D, O) = (0, 0), in an image with ID outputs (ids != null) the sentinel {0xFFFFFFFF, 0xFFFFFFFF, 0.0f}: a tile in
-// memory has valid aux and ID pixels too
+// one wave per tile: tiles whose pixels are not in memory get the clear colour — and the clear value of every other output the image has
+// (aux, ids: null when it has none; Outputs, gs4d_internal.h): a tile in memory has valid aux and ID pixels too
 __global__ __launch_bounds__(64) void k_fill_unwritten(float4* __restrict__ fb, uint32_t* __restrict__ tstate, uint32_t epoch, float4 c, int tiles_x, int W, int H, float2* __restrict__ aux,
                                                        uint32_t* __restrict__ ids) {
     const uint32_t tile = blockIdx.x, lane = threadIdx.x;
@@ -43,8 +42,8 @@ __global__ __launch_bounds__(64) void k_fill_unwritten(float4* __restrict__ fb, 
     if (lane == 0u) tstate[tile] = epoch;
 }
 
-hipError_t launch_fill_unwritten(hipStream_t st, float4* fb, uint32_t* tstate, uint32_t epoch, int tiles_x, int tiles_y, int W, int H, const float clear[4], float2* aux, uint32_t* ids) {
-    k_fill_unwritten<<<dim3((unsigned)(tiles_x * tiles_y)), dim3(64), 0, st>>>(fb, tstate, epoch, make_float4(clear[0], clear[1], clear[2], clear[3]), tiles_x, W, H, aux, ids);
+hipError_t launch_fill_unwritten(hipStream_t st, const Target& t, int tiles_x, int tiles_y, int W, int H) {
+    k_fill_unwritten<<<dim3((unsigned)(tiles_x * tiles_y)), dim3(64), 0, st>>>(t.fb, t.tstate, t.epoch, t.clear, tiles_x, W, H, t.aux, t.ids);
     return hipGetLastError();
 }
 
@@ -100,23 +99,20 @@ hipError_t launch_pack_rgba8_band(hipStream_t st, const float4* fb, const uint32
     return hipGetLastError();
 }
 
-// AUX (default blend function only): the image also has aux outputs — per pixel (D, O), D = sum of w * depth, O = 1 - T, composed onto what
-// the aux plane holds with the same "over" as the colour: (D, O) <- (D_draw + T * D, (1 - T) + T * O); a tile not in memory holds (0, 0).
-// ID (implies AUX): the image also has ID outputs — three W x H planes at ids (record, draw, weight bits); the draw's candidate (largest
-// w > 0, front-most on a tie) is composed over what they hold by id_over (composite_common.h); a tile not in memory holds the sentinel.
-template <bool PREMULT_C, bool GENERAL, bool AUX = false, bool ID = false>
+// OUT: the outputs of the image's frame (Outputs, gs4d_internal.h); aux, ids: their planes.
+template <bool PREMULT_C, bool GENERAL, Outputs OUT>
 __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ proj, const uint32_t* __restrict__ pair_vals, uint32_t* __restrict__ ranges,
                                                   const uint32_t* __restrict__ total, int tiles_x, int W, int H, uint32_t* __restrict__ tstate, uint32_t epoch, float4 clear,
                                                   float4* __restrict__ fb, int dbg_arg, BlendFn bf, float2* __restrict__ aux, uint32_t* __restrict__ ids, uint32_t draw_ord) {
-    static_assert(!(AUX && GENERAL), "aux outputs are defined for the default blend function only");
-    static_assert(!ID || AUX, "ID outputs come with aux outputs");
+    static_assert(!GENERAL || OUT == Outputs::Colour, "aux and ID outputs are defined for the default blend function only");
 #ifdef GS4D_TUNING
     const int dbg = dbg_arg;             // GS4D_COMPOSITE_DBG: tuning builds only (make TUNING=1)
 #else
     constexpr int dbg = 0; (void)dbg_arg;
 #endif
-    __shared__ float4 stage[64 * 3 + (AUX ? 16 : 0) + (ID ? 16 : 0)];     // AUX: the entries' depths behind the three float4 per entry; ID: then their record indices
-    __shared__ uint32_t pmask[64 * 2];                      // per pixel: 64-bit mask of the chunk entries that cover it
+    __shared__ float4 sh_stage[stage_words(OUT) / 4];
+    __shared__ uint32_t pmask[64 * 2];
+    const Stage<OUT> stage(sh_stage);
     if (total[1]) return;                                   // tile lists overflowed: nothing was emitted, the host re-runs
     uint32_t tile;
     if (!composite_tile(blockIdx.x, tiles_x, (H + TILE - 1) / TILE, tile)) return;        // uniform: padding of the XCD-aware grid
@@ -129,20 +125,19 @@ __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ pro
     if (start >= end) return;                               // uniform: nothing is drawn on this tile — its pixels, or its being clear, stay as they are
     const bool fb_is_clear = tstate[tile] != epoch;         // uniform: the tile's pixels are not in memory yet
 
-    float T = 1.0f, Cr = 0.0f, Cg = 0.0f, Cb = 0.0f, A = 0.0f, D = 0.0f, BW = 0.0f;
-    uint32_t BR = ID_NONE;
+    PixelAcc acc;
     if (GENERAL) {
         // a blend function other than the default: no transmittance form — the pixel's value is taken through the list in draw order
         const bool in = px < W && py < H;
         const size_t o = in ? (size_t)py * W + px : 0;
         const float4 d = (fb_is_clear || !in) ? clear : fb[o];
-        Cr = d.x; Cg = d.y; Cb = d.z; A = d.w;
+        acc.Cr = d.x; acc.Cg = d.y; acc.Cb = d.z; acc.A = d.w;
         for (uint32_t lo = start; lo < end; lo += 64u) {
             const uint32_t cnt = min(64u, end - lo);
             const uint32_t rec = lane < cnt ? pair_vals[lo + lane] : 0u;         // lane s holds list entry lo+s: s = 0 is drawn first
-            composite_chunk<PREMULT_C, true>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, T, Cr, Cg, Cb, A, bf);
+            composite_chunk<PREMULT_C, GENERAL, OUT>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, acc, bf);
         }
-        if (in) fb[o] = make_float4(Cr, Cg, Cb, A);
+        if (in) fb[o] = make_float4(acc.Cr, acc.Cg, acc.Cb, acc.A);
         if (lane == 0u) tstate[tile] = epoch;
         return;
     }
@@ -150,30 +145,20 @@ __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ pro
         const uint32_t cnt = min(64u, hi - start);
         // lane s holds list entry hi-1-s : s = 0 is the LAST (front-most) entry of this chunk
         const uint32_t rec = lane < cnt ? pair_vals[hi - 1u - lane] : 0u;
-        if (ID) composite_chunk<PREMULT_C, false, true, true>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, T, Cr, Cg, Cb, A, bf, reinterpret_cast<float*>(stage + 64 * 3), &D,
-                                                              reinterpret_cast<uint32_t*>(stage + 64 * 3 + 16), &BW, &BR);
-        else if (AUX) composite_chunk<PREMULT_C, false, true>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, T, Cr, Cg, Cb, A, bf, reinterpret_cast<float*>(stage + 64 * 3), &D);
-        else composite_chunk<PREMULT_C>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, T, Cr, Cg, Cb, A);
+        composite_chunk<PREMULT_C, GENERAL, OUT>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, acc, bf);
         hi -= cnt;
-        if (__ballot(T > 0.0f) == 0ull) break;              // exact: every remaining contribution is multiplied by T == 0
+        if (__ballot(acc.T > 0.0f) == 0ull) break;          // exact: every remaining contribution is multiplied by T == 0
     }
     if (px < W && py < H) {
         const size_t o = (size_t)py * W + px;
-        const float4 d = fb_is_clear ? clear : fb[o];
-        fb[o] = make_float4(Cr + T * d.x, Cg + T * d.y, Cb + T * d.z, A + T * d.w);
-        if (AUX) {
-            const float2 q = fb_is_clear ? make_float2(0.0f, 0.0f) : aux[o];
-            aux[o] = make_float2(D + T * q.x, (1.0f - T) + T * q.y);
-        }
-        if (ID) id_over(ids, (size_t)W * H, o, fb_is_clear, T, BW, BR, draw_ord);
+        store_over<OUT>(acc, o, fb_is_clear, clear, fb, aux);
+        if (has_ids(OUT)) id_over(ids, (size_t)W * H, o, fb_is_clear, acc.T, acc.BW, acc.BR, draw_ord);
     }
     if (lane == 0u) tstate[tile] = epoch;
 }
 
 hipError_t launch_composite(hipStream_t st, const float4* proj, const uint32_t* pair_vals, uint32_t* ranges, const uint32_t* total, int tiles_x, int tiles_y,
-                            int W, int H, int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, int blend_src, int blend_dst, float2* aux,
-                            uint32_t* ids, uint32_t draw_ord) {
-    const float4 c = make_float4(clear[0], clear[1], clear[2], clear[3]);
+                            int W, int H, int premult_c, const Target& t, int blend_src, int blend_dst, uint32_t draw_ord) {
     const dim3 grid(composite_grid(tiles_x, tiles_y));
 #ifdef GS4D_TUNING
     static const int dbg = getenv("GS4D_COMPOSITE_DBG") ? atoi(getenv("GS4D_COMPOSITE_DBG")) : 0;   // tuning knob: 1 = broadcast only, 2 = splat-parallel only
@@ -182,22 +167,11 @@ hipError_t launch_composite(hipStream_t st, const float4* proj, const uint32_t* 
 #endif
     const BlendFn bf{ blend_src, blend_dst };
     const bool general = !(blend_src == GS4D_SRC_ALPHA && blend_dst == GS4D_ONE_MINUS_SRC_ALPHA);
-    if (general && aux) return hipErrorInvalidValue;       // the host refuses such a draw (GS4D_E_UNSUPPORTED) before it gets here
-    if (ids && !aux) return hipErrorInvalidValue;          // ID outputs come with aux outputs
-    if (general) {
-        if (premult_c) k_composite<true, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr, nullptr, 0u);
-        else           k_composite<false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr, nullptr, 0u);
-    }
-    else if (ids) {
-        if (premult_c) k_composite<true, false, true, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux, ids, draw_ord);
-        else           k_composite<false, false, true, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux, ids, draw_ord);
-    }
-    else if (aux) {
-        if (premult_c) k_composite<true, false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux, nullptr, 0u);
-        else           k_composite<false, false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, aux, nullptr, 0u);
-    }
-    else if (premult_c) k_composite<true, false><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr, nullptr, 0u);
-    else                k_composite<false, false><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, tstate, epoch, c, fb, dbg, bf, nullptr, nullptr, 0u);
+    if (general && t.out != Outputs::Colour) return hipErrorInvalidValue;       // the host refuses such a draw (GS4D_E_UNSUPPORTED) before it gets here
+    for_outputs(premult_c != 0, t.out, [&](auto pc, auto out) {
+        if (general) k_composite<pc(), true, Outputs::Colour><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, nullptr, nullptr, 0u);
+        else k_composite<pc(), false, out()><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, t.aux, t.ids, draw_ord);
+    });
     return hipGetLastError();
 }
 

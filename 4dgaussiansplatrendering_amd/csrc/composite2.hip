@@ -72,23 +72,20 @@ struct WaveSort {
     }
 };
 
-// AUX: the image also has aux outputs (D, O) per pixel, accumulated and composed as in k_composite<.., AUX> (composite.hip).
-// ID (implies AUX): the image also has ID outputs, as in k_composite<.., ID>; draw_ord is the draw's ordinal within its frame.
-template <bool PREMULT_C, int PER, bool AUX = false, bool ID = false>
+// OUT: the outputs of the image's frame (Outputs, gs4d_internal.h); aux, ids: their planes; draw_ord: the draw's ordinal within its frame.
+template <bool PREMULT_C, int PER, Outputs OUT>
 __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ proj, const uint2* __restrict__ entries, const uint32_t* __restrict__ tstart, const uint32_t* __restrict__ tcnt,
                                                      const uint32_t* __restrict__ total, uint32_t* __restrict__ total_host, int tiles_x, int W, int H, uint32_t* __restrict__ tstate, uint32_t epoch, float4 clear,
                                                      float4* __restrict__ fb, int key_passes, int rec_passes, uint32_t slabs,
                                                      const uint4* __restrict__ bstat, uint32_t nb, const uint32_t* __restrict__ sstat, uint32_t rows, uint32_t stage_seq, uint32_t rcap, uint32_t scap, uint32_t bcap,
                                                      TileBox box, uint32_t box_blocks, unsigned long long* __restrict__ stamps, float2* __restrict__ aux, uint32_t* __restrict__ ids, uint32_t draw_ord) {
-    static_assert(!ID || AUX, "ID outputs come with aux outputs");
-    // the sort's key plane and the blend's record staging (AUX: and the entries' depths behind it; ID: then their record indices) never live at the same time: one piece of LDS serves both
-    constexpr int STAGE_WORDS = 64 * 3 * 4 + (AUX ? 64 : 0) + (ID ? 64 : 0);
-    constexpr int SHARED_WORDS = 64 * PER > STAGE_WORDS ? 64 * PER : STAGE_WORDS;
+    // the sort's key plane and the blend's staging never live at the same time: one piece of LDS serves both
+    constexpr int SHARED_WORDS = 64 * PER > stage_words(OUT) ? 64 * PER : stage_words(OUT);
     __shared__ __attribute__((aligned(16))) uint32_t sh_a[SHARED_WORDS];
     __shared__ uint32_t pmask[64 * 2];
     __shared__ __attribute__((aligned(16))) uint32_t cnt[WS_BINS];
     __shared__ uint32_t er[64 * PER];
-    float4* stage = reinterpret_cast<float4*>(sh_a);
+    const Stage<OUT> stage(reinterpret_cast<float4*>(sh_a));
     uint32_t* ek = sh_a;
     uint32_t tile;
     const bool real = composite_tile(blockIdx.x, tiles_x, box, tile);     // false: padding of the XCD-aware grid
@@ -136,8 +133,7 @@ __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ 
     const int tx0 = (int)(tile % (uint32_t)tiles_x) * TILE, ty0 = (int)(tile / (uint32_t)tiles_x) * TILE;
     const int px = tx0 + (int)(lane & 7u), py = ty0 + (int)(lane >> 3);
     const float fx = (float)px + 0.5f, fy = (float)py + 0.5f;
-    float T = 1.0f, Cr = 0.0f, Cg = 0.0f, Cb = 0.0f, A = 0.0f, D = 0.0f, BW = 0.0f;
-    uint32_t BR = ID_NONE;
+    PixelAcc acc;
     // the tile's list is `slabs` sub-lists by the top bits of the key; larger key = nearer: the last slab is blended first
     if (__ballot(my_cnt != 0u) == 0ull) return;             // nothing is drawn on this tile: its pixels, or its being clear (composite.hip: tile state), stay as they are
     const bool fb_is_clear = tstate_word != epoch;          // uniform: the tile's pixels are not in memory yet
@@ -179,24 +175,16 @@ __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ 
         for (uint32_t hi = E; hi > 0u;) {
             const uint32_t c = min(64u, hi);
             const uint32_t rec = lane < c ? er[hi - 1u - lane] : 0u;       // lane s holds list entry hi-1-s : s = 0 is the front-most of the chunk
-            if (ID) composite_chunk<PREMULT_C, false, true, true>(proj, rec, c, lane, tx0, ty0, fx, fy, stage, pmask, 0, T, Cr, Cg, Cb, A, BlendFn{ 0, 0 }, reinterpret_cast<float*>(sh_a + 64 * 3 * 4), &D,
-                                                                  sh_a + 64 * 3 * 4 + 64, &BW, &BR);
-            else if (AUX) composite_chunk<PREMULT_C, false, true>(proj, rec, c, lane, tx0, ty0, fx, fy, stage, pmask, 0, T, Cr, Cg, Cb, A, BlendFn{ 0, 0 }, reinterpret_cast<float*>(sh_a + 64 * 3 * 4), &D);
-            else composite_chunk<PREMULT_C>(proj, rec, c, lane, tx0, ty0, fx, fy, stage, pmask, 0, T, Cr, Cg, Cb, A);
+            composite_chunk<PREMULT_C, false, OUT>(proj, rec, c, lane, tx0, ty0, fx, fy, stage, pmask, 0, acc, BlendFn{ 0, 0 });
             hi -= c;
-            if (__ballot(T > 0.0f) == 0ull) break;          // exact: every remaining contribution is multiplied by T == 0
+            if (__ballot(acc.T > 0.0f) == 0ull) break;      // exact: every remaining contribution is multiplied by T == 0
         }
-        if (__ballot(T > 0.0f) == 0ull) break;
+        if (__ballot(acc.T > 0.0f) == 0ull) break;
     }
     if (px < W && py < H) {
         const size_t o = (size_t)py * W + px;
-        const float4 d = fb_is_clear ? clear : fb[o];
-        fb[o] = make_float4(Cr + T * d.x, Cg + T * d.y, Cb + T * d.z, A + T * d.w);
-        if (AUX) {
-            const float2 q = fb_is_clear ? make_float2(0.0f, 0.0f) : aux[o];
-            aux[o] = make_float2(D + T * q.x, (1.0f - T) + T * q.y);
-        }
-        if (ID) id_over(ids, (size_t)W * H, o, fb_is_clear, T, BW, BR, draw_ord);
+        store_over<OUT>(acc, o, fb_is_clear, clear, fb, aux);
+        if (has_ids(OUT)) id_over(ids, (size_t)W * H, o, fb_is_clear, acc.T, acc.BW, acc.BR, draw_ord);
     }
     if (lane == 0u) tstate[tile] = epoch;
 #ifdef GS4D_TUNING
@@ -204,31 +192,11 @@ __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ 
 #endif
 }
 
-template <bool PREMULT_C, bool AUX, bool ID>
-static hipError_t launch_v2(hipStream_t st, int per, dim3 grid, const float4* proj, const uint2* entries, const uint32_t* tstart, const uint32_t* tcnt, const uint32_t* total, uint32_t* total_host, int tiles_x, int W, int H,
-                            uint32_t* tstate, uint32_t epoch, float4 c, float4* fb, int kp, int rp, uint32_t slabs, const uint4* bstat, uint32_t nb, const uint32_t* sstat, uint32_t rows, uint32_t stage_seq, uint32_t rcap, uint32_t scap, uint32_t bcap, TileBox box, uint32_t box_blocks, unsigned long long* stamps, float2* aux, uint32_t* ids, uint32_t draw_ord) {
-#define GS4D_V2(P) k_composite_v2<PREMULT_C, P, AUX, ID><<<grid, dim3(64), 0, st>>>(proj, entries, tstart, tcnt, total, total_host, tiles_x, W, H, tstate, epoch, c, fb, kp, rp, slabs, bstat, nb, sstat, rows, stage_seq, rcap, scap, bcap, box, box_blocks, stamps, aux, ids, draw_ord)
-    switch (per) {
-    case 1: GS4D_V2(1); break;
-    case 2: GS4D_V2(2); break;
-    case 3: GS4D_V2(3); break;
-    case 4: GS4D_V2(4); break;
-    case 6: GS4D_V2(6); break;
-    case 8: GS4D_V2(8); break;
-    case 12: GS4D_V2(12); break;
-    default: GS4D_V2(16); break;
-    }
-#undef GS4D_V2
-    return hipGetLastError();
-}
-
 hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* entries, const uint32_t* tstart, const uint32_t* tcnt, const uint32_t* total, uint32_t* total_host, int tiles_x, int tiles_y, int W, int H,
-                               int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, uint32_t hint, int keybits, int recbits, uint32_t slabs,
-                               const uint4* bstat, uint32_t nb, const uint32_t* sstat, uint32_t rows, uint32_t stage_seq, uint32_t rcap, uint32_t scap, uint32_t bcap, uint32_t box_blocks, float2* aux, uint32_t* ids, uint32_t draw_ord) {
+                               int premult_c, const Target& t, uint32_t hint, int keybits, int recbits, uint32_t slabs,
+                               const uint4* bstat, uint32_t nb, const uint32_t* sstat, uint32_t rows, uint32_t stage_seq, uint32_t rcap, uint32_t scap, uint32_t bcap, uint32_t box_blocks, uint32_t draw_ord) {
     if (hint > V2_MAX_LIST) return hipErrorInvalidValue;
-    if (ids && !aux) return hipErrorInvalidValue;          // ID outputs come with aux outputs
     const int per = (int)(v2_list_capacity(hint) / 64u);
-    const float4 c = make_float4(clear[0], clear[1], clear[2], clear[3]);
     // staged draws: only the box of tiles the list kernel has checked every entry to lie in (TileLists::box); the first workgroup reports, so there is always one
     TileBox box = tile_box(stage_seq ? box_blocks : BOX_NONE, tiles_x, tiles_y);
     if (box.w == 0u || box.h == 0u) box = TileBox{ 0u, 0u, 1u, 1u };
@@ -246,10 +214,21 @@ hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* 
     const bool stamp_now = stampf && ++calls == stamp_call;
     if (stamp_now && (hipMalloc(&stamps, (size_t)grid.x * 48) != hipSuccess || hipMemsetAsync(stamps, 0, (size_t)grid.x * 48, st) != hipSuccess)) stamps = nullptr;
 #endif
-#define GS4D_V2L(PC, AX, ID) launch_v2<PC, AX, ID>(st, per, grid, proj, entries, tstart, tcnt, total, total_host, tiles_x, W, H, tstate, epoch, c, fb, kp, rp, slabs, bstat, nb, sstat, rows, stage_seq, rcap, scap, bcap, box, box_blocks, stamps, aux, ids, draw_ord)
-    const hipError_t le = ids ? (premult_c ? GS4D_V2L(true, true, true) : GS4D_V2L(false, true, true))
-                        : aux ? (premult_c ? GS4D_V2L(true, true, false) : GS4D_V2L(false, true, false)) : (premult_c ? GS4D_V2L(true, false, false) : GS4D_V2L(false, false, false));
-#undef GS4D_V2L
+    for_outputs(premult_c != 0, t.out, [&](auto pc, auto out) {
+#define GS4D_V2(P) k_composite_v2<pc(), P, out()><<<grid, dim3(64), 0, st>>>(proj, entries, tstart, tcnt, total, total_host, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, kp, rp, slabs, bstat, nb, sstat, rows, stage_seq, rcap, scap, bcap, box, box_blocks, stamps, t.aux, t.ids, draw_ord)
+        switch (per) {
+        case 1: GS4D_V2(1); break;
+        case 2: GS4D_V2(2); break;
+        case 3: GS4D_V2(3); break;
+        case 4: GS4D_V2(4); break;
+        case 6: GS4D_V2(6); break;
+        case 8: GS4D_V2(8); break;
+        case 12: GS4D_V2(12); break;
+        default: GS4D_V2(16); break;
+        }
+#undef GS4D_V2
+    });
+    const hipError_t le = hipGetLastError();
 #ifdef GS4D_TUNING
     if (stamps) {
         (void)hipStreamSynchronize(st);

@@ -1,6 +1,7 @@
 // composite_common.h — what the two compositing kernels (composite.hip: ordered lists; composite2.hip: lists ordered in LDS) share.
 #pragma once
 #include "gs4d_internal.h"
+#include <type_traits>
 
 namespace gs4d {
 
@@ -85,20 +86,30 @@ __device__ __forceinline__ void blend_general(BlendFn bf, float sr, float sg, fl
 __device__ __forceinline__ float gauss_weight(float u, float v) { return __builtin_amdgcn_exp2f((u * u + v * v) * -46.16624130844683f); }      // -32 * log2(e)
 __device__ __forceinline__ float clamp01(float x) { return __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f); }
 
-// AUX (default function only): also D += w * d, with the weight w the colour uses and d the entry's depth (projected record, slot 15).
-// ID (implies AUX): also the draw's candidate — (*BW, *BR) <- (w, rid) when w > *BW: walked front to back from *BW = 0, that is the largest
-// w > 0, the front-most of equal weights.  A lane without a fragment blends with al = 0, so w = 0 and it never takes.
-template <bool PREMULT_C, bool GENERAL = false, bool AUX = false, bool ID = false>
-__device__ __forceinline__ void blend_fragment(float u, float v, float alpha, float r_, float g_, float b_, float& T, float& Cr, float& Cg, float& Cb, float& A, BlendFn bf = BlendFn{ 0, 0 },
-                                               float d = 0.0f, float* D = nullptr, uint32_t rid = 0u, float* BW = nullptr, uint32_t* BR = nullptr) {
-    static_assert(!(AUX && GENERAL), "aux outputs are defined for the default blend function only");
-    static_assert(!ID || AUX, "ID outputs come with aux outputs");
+// A pixel no fragment has reached holds the ID sentinel {ID_NONE, ID_NONE, 0.0f} (Outputs, gs4d_internal.h).
+constexpr uint32_t ID_NONE = 0xFFFFFFFFu;
+
+// What one pixel accumulates over one draw.  Default function: colour C and alpha A front to back, transmittance T; from Outputs::Aux on the
+// weighted depth D; from Outputs::Ids on the draw's candidate (BW, BR) — the largest weight w > 0 so far and its record, the front-most of
+// equal weights (walked front to back from BW = 0).  GENERAL: (Cr, Cg, Cb, A) is the pixel's value itself; T is unused.
+// A level's kernels never read the members of the levels above it: they cost no register.  (BR stands first: the generated code sets the
+// registers up in member order, and this order is the one the kernels had with loose locals.)
+struct PixelAcc {
+    uint32_t BR = ID_NONE;
+    float T = 1.0f, Cr = 0.0f, Cg = 0.0f, Cb = 0.0f, A = 0.0f, D = 0.0f, BW = 0.0f;
+};
+
+// d: the entry's depth (Outputs::Aux on), rid: its record index (Outputs::Ids); a lane without a fragment blends with al = 0, so w = 0 and
+// it never becomes the candidate.
+template <bool PREMULT_C, bool GENERAL, Outputs OUT>
+__device__ __forceinline__ void blend_fragment(float u, float v, float alpha, float r_, float g_, float b_, PixelAcc& p, BlendFn bf, float d, uint32_t rid) {
+    static_assert(!GENERAL || OUT == Outputs::Colour, "aux and ID outputs are defined for the default blend function only");
     const float cg = gauss_weight(u, v);
     if (GENERAL) {
         if (cg >= 0.0001f) {                               // Splat4DFragShader.GLSL:30 discard
             const float al = clamp01(alpha * cg);
             if (PREMULT_C) { r_ = clamp01(r_ * cg); g_ = clamp01(g_ * cg); b_ = clamp01(b_ * cg); }
-            blend_general(bf, r_, g_, b_, al, Cr, Cg, Cb, A);
+            blend_general(bf, r_, g_, b_, al, p.Cr, p.Cg, p.Cb, p.A);
         }
         return;
     }
@@ -108,20 +119,19 @@ __device__ __forceinline__ void blend_fragment(float u, float v, float alpha, fl
     // with al = 0, which leaves C and T as they are, exactly (C + 0 * c, T * 1).  The compositor is bound by instruction issue; a divergent
     // region costs four wave instructions whether or not a lane takes it.
     const float al = cg >= 0.0001f ? clamp01(alpha * cg) : 0.0f;
-    const float w = T * al;
+    const float w = p.T * al;
     if (PREMULT_C) { r_ = clamp01(r_ * cg); g_ = clamp01(g_ * cg); b_ = clamp01(b_ * cg); }   // Splat3DFragShaderFull.GLSL:22
-    Cr += w * r_; Cg += w * g_; Cb += w * b_; A += w * al;
-    if (AUX) *D += w * d;
-    if (ID) { const bool take = w > *BW; *BW = take ? w : *BW; *BR = take ? rid : *BR; }
-    T *= (1.0f - al);
+    p.Cr += w * r_; p.Cg += w * g_; p.Cb += w * b_; p.A += w * al;
+    if (has_aux(OUT)) p.D += w * d;
+    if (has_ids(OUT)) { const bool take = w > p.BW; p.BW = take ? w : p.BW; p.BR = take ? rid : p.BR; }
+    p.T *= (1.0f - al);
 }
 
-// ID outputs: three W x H planes of u32 at ids, ids + P, ids + 2 P (P = W * H): the record, the draw ordinal and the bits of
-// the weight.  A pixel no fragment has reached holds the sentinel {ID_NONE, ID_NONE, 0.0f}.
-constexpr uint32_t ID_NONE = 0xFFFFFFFFu;
-// One pixel at the end of a draw: its candidate (BW, BR; BW == 0: none) composed over the stored triple with the colour's "over" — the stored
-// weight is scaled by the draw's final transmittance T, and the candidate replaces the triple when its weight is at least that (the newer
-// draw is in front: ties go to it).  fb_is_clear (uniform): the tile is not in memory, the stored triple is the sentinel.
+// The end of a draw of the default blend function for the pixel at offset o: what the draw accumulated, composed over what the image holds
+// with the colour's "over" (Outputs, gs4d_internal.h).  fb_is_clear (uniform): the tile is not in memory, it holds the clear values.
+// The kernels call store_over, then (Outputs::Ids) id_over: with id_over nested in store_over the compiler orders six instructions differently.
+// id_over, the ID triple (planes at ids, ids + P, ids + 2 P, P = W * H): the stored weight is scaled by the draw's final transmittance T, and the draw's
+// candidate (BW, BR; BW == 0: none) replaces the triple when its weight is at least that (the newer draw is in front: ties go to it).
 __device__ __forceinline__ void id_over(uint32_t* __restrict__ ids, size_t P, size_t o, bool fb_is_clear, float T, float BW, uint32_t BR, uint32_t draw) {
     uint32_t r = ID_NONE, dr = ID_NONE;
     float w = 0.0f;
@@ -132,16 +142,49 @@ __device__ __forceinline__ void id_over(uint32_t* __restrict__ ids, size_t P, si
     ids[P + o] = take ? draw : dr;
     ids[2 * P + o] = __float_as_uint(take ? BW : w);
 }
+// store_over: the colour and (from Outputs::Aux on) the aux value
+template <Outputs OUT>
+__device__ __forceinline__ void store_over(const PixelAcc& p, size_t o, bool fb_is_clear, float4 clear, float4* fb, float2* aux) {
+    const float4 d = fb_is_clear ? clear : fb[o];
+    fb[o] = make_float4(p.Cr + p.T * d.x, p.Cg + p.T * d.y, p.Cb + p.T * d.z, p.A + p.T * d.w);
+    if (has_aux(OUT)) {
+        const float2 q = fb_is_clear ? make_float2(0.0f, 0.0f) : aux[o];
+        aux[o] = make_float2(p.D + p.T * q.x, (1.0f - p.T) + p.T * q.y);
+    }
+}
+
+// The LDS a chunk of <= 64 list entries is staged in: three float4 of every entry's projected record; from Outputs::Aux on the entries' depths
+// (the last float of the same 64-byte record) behind them; from Outputs::Ids on their record indices behind those.  A kernel gives it
+// stage_words(OUT) words, 16-byte aligned.
+constexpr int stage_words(Outputs o) { return 64 * 3 * 4 + (has_aux(o) ? 64 : 0) + (has_ids(o) ? 64 : 0); }
+template <Outputs OUT>
+struct Stage {
+    float4* rec; float* depth; uint32_t* rid;
+    __device__ __forceinline__ explicit Stage(float4* records) : rec(records), depth(has_aux(OUT) ? reinterpret_cast<float*>(records + 64 * 3) : nullptr),
+                                                                 rid(has_ids(OUT) ? reinterpret_cast<uint32_t*>(records + 64 * 3 + 16) : nullptr) {}
+};
+
+// Host side of a launch: f(premultiplied colours?, output set) with both as compile-time constants (std::integral_constant).
+template <class F>
+inline void for_outputs(bool premult_c, Outputs out, F&& f) {
+    auto with = [&](auto pc) {
+        switch (out) {
+        case Outputs::Ids: f(pc, std::integral_constant<Outputs, Outputs::Ids>{}); break;
+        case Outputs::Aux: f(pc, std::integral_constant<Outputs, Outputs::Aux>{}); break;
+        default: f(pc, std::integral_constant<Outputs, Outputs::Colour>{}); break;
+        }
+    };
+    if (premult_c) with(std::true_type{}); else with(std::false_type{});
+}
 
 // One chunk of the tile's list, front to back: lane s < cnt carries record `rec` of list entry (end of chunk - 1 - s), so s = 0 is the
-// front-most entry.  stage: 64 x 3 float4, pmask: 64 x 2 words (per pixel: 64-bit mask of the chunk entries that cover it).
-// GENERAL: the chunk is walked in DRAW order instead — lane s carries list entry (start of chunk + s).
-// AUX: the entry's depth (the last float of the same 64-byte record) is staged beside it in dstage (64 floats) and accumulated into *D.
-// ID (implies AUX): the entry's record index is staged beside it in rstage (64 words); the pixel's candidate goes to (*BW, *BR).
-template <bool PREMULT_C, bool GENERAL = false, bool AUX = false, bool ID = false>
-__device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj, uint32_t rec, uint32_t cnt, uint32_t lane, int tx0, int ty0, float fx, float fy,
-                                                float4* stage, uint32_t* pmask, int dbg, float& T, float& Cr, float& Cg, float& Cb, float& A, BlendFn bf = BlendFn{ 0, 0 },
-                                                float* dstage = nullptr, float* D = nullptr, uint32_t* rstage = nullptr, float* BW = nullptr, uint32_t* BR = nullptr) {
+// front-most entry.  GENERAL: the chunk is walked in DRAW order instead — lane s carries list entry (start of chunk + s).
+// pmask: 64 x 2 words of LDS (per pixel: 64-bit mask of the chunk entries that cover it).
+template <bool PREMULT_C, bool GENERAL, Outputs OUT>
+__device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj, uint32_t rec, uint32_t cnt, uint32_t lane, int tx0, int ty0, float fx, float fy, const Stage<OUT>& st, uint32_t* pmask, int dbg,
+                                                PixelAcc& acc, BlendFn bf) {
+    float4* const stage = st.rec;
+
     // lane s holds list entry hi-1-s : s = 0 is the LAST (front-most) entry of this chunk
     int lx0 = 0, ly0 = 0, bw = 0, bh = 0;
     float4 ra = make_float4(0, 0, 0, 0), rb = ra;
@@ -152,8 +195,8 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
         stage[lane * 3 + 0] = ra;
         stage[lane * 3 + 1] = rb;
         stage[lane * 3 + 2] = rc;
-        if (AUX) dstage[lane] = reinterpret_cast<const float*>(r)[15];
-        if (ID) rstage[lane] = rec;
+        if (has_aux(OUT)) st.depth[lane] = reinterpret_cast<const float*>(r)[15];
+        if (has_ids(OUT)) st.rid[lane] = rec;
         const uint32_t r0 = __float_as_uint(rc.z), r1 = __float_as_uint(rc.w);
         lx0 = max((int)(r0 & 0xFFFFu) - tx0, 0); ly0 = max((int)(r0 >> 16) - ty0, 0);
         const int lx1 = min((int)(r1 & 0xFFFFu) - tx0, TILE - 1), ly1 = min((int)(r1 >> 16) - ty0, TILE - 1);
@@ -176,9 +219,9 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const bool cov = fabsf(u) <= 0.5f && fabsf(v) <= 0.5f;
             if (__ballot(cov) == 0ull) continue;
             const float4 c = stage[s * 3 + 2];          // b, alpha, -, -
-            if (ID) { const float d = dstage[s]; const uint32_t rid = rstage[s]; if (cov) blend_fragment<PREMULT_C, false, true, true>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, d, D, rid, BW, BR); }
-            else if (AUX) { const float d = dstage[s]; if (cov) blend_fragment<PREMULT_C, false, true>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, d, D); }
-            else if (cov) blend_fragment<PREMULT_C, GENERAL>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf);
+            const float d = has_aux(OUT) ? st.depth[s] : 0.0f;
+            const uint32_t rid = has_ids(OUT) ? st.rid[s] : 0u;
+            if (cov) blend_fragment<PREMULT_C, GENERAL, OUT>(u, v, c.y, b.z, b.w, c.x, acc, bf, d, rid);
         }
     } else {
         // ---- phase A (lane = entry): mark the covered pixels of small footprints ----
@@ -236,10 +279,8 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const float dx = __fsub_rn(fx, a.x), dy = __fsub_rn(fy, a.y);
             const float u = __fmaf_rn(a.z, dx, __fmul_rn(b.x, dy));
             const float v = __fmaf_rn(a.w, dx, __fmul_rn(b.y, dy));
-            if (GENERAL) { if (on) blend_fragment<PREMULT_C, true>(u, v, c.y, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf); }
-            else if (ID) blend_fragment<PREMULT_C, false, true, true>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, dstage[e], D, rstage[e], BW, BR);
-            else if (AUX) blend_fragment<PREMULT_C, false, true>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, T, Cr, Cg, Cb, A, bf, dstage[e], D);
-            else blend_fragment<PREMULT_C, false>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, T, Cr, Cg, Cb, A);
+            if constexpr (GENERAL) { if (on) blend_fragment<PREMULT_C, true, OUT>(u, v, c.y, b.z, b.w, c.x, acc, bf, 0.0f, 0u); }
+            else blend_fragment<PREMULT_C, false, OUT>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, acc, bf, has_aux(OUT) ? st.depth[e] : 0.0f, has_ids(OUT) ? st.rid[e] : 0u);
         }
     }
     __syncthreads();

@@ -21,6 +21,7 @@
 #include <cstdlib>
 #include <new>
 #include <algorithm>
+#include <functional>
 #include <vector>
 #include <cmath>
 
@@ -79,8 +80,7 @@ struct DrawArgs {
     bool regen_order = false;
     bool exact_lists = false;         // the re-run of a staged draw whose blocks, runs or buckets did not fit: builds its lists exactly (scan + scatter)
     uint64_t stage_geom = 0;        // set by run_draw: the list geometry the draw's bucket statistics belong to (resolve_lane files them under it)
-    bool aux = false;               // the image's frame was cleared with aux outputs on: depth into the projected records, (D, O) into the aux plane
-    bool ids = false;               // ... with ID outputs on (aux is then on too): the candidate {record, draw, weight} into the ID planes
+    Outputs out = Outputs::Colour;  // what the image's frame was cleared with: from Aux on the projection stores depths in its records
     uint32_t draw_ord = 0;          // the draw's ordinal within its frame (a re-run keeps it)
 };
 
@@ -94,12 +94,21 @@ struct Framebuffer {
     uint32_t* tstate = nullptr; uint32_t epoch = 1; bool all_in_memory = false;
     float clear[4] = { 0, 0, 0, 0 };   // the clear colour: the context's at the gs4d_clear that cleared this image
     int last_lane = -1;            // lane that touched it last
-    // Aux outputs: one float2 {D, O} per pixel, allocated with the image once gs4d_set_aux_outputs has been on.  aux_on: this
-    // image's frame was cleared with aux outputs on — its compositing kernels and k_fill_unwritten keep the plane valid for every tile in memory.
-    float2* aux = nullptr; bool aux_on = false;
-    // ID outputs: three W * H u32 planes — record, draw, weight bits — in one allocation, made once gs4d_set_id_outputs has
-    // been on.  ids_on: this image's frame was cleared with ID outputs on (then aux_on too).  draws: splat draws into the frame since its clear.
-    uint32_t* ids = nullptr; bool ids_on = false; uint32_t draws = 0;
+    // The planes of the other outputs (Outputs, gs4d_internal.h), allocated with the image up to the level the context has asked for so far
+    // (reserve_planes).  out: what this image's frame was cleared with — its compositing kernels and k_fill_unwritten keep those planes valid
+    // for every tile in memory.  draws: splat draws into the frame since its clear.
+    float2* aux = nullptr; uint32_t* ids = nullptr; Outputs out = Outputs::Colour; uint32_t draws = 0;
+    // the image as a draw or a fill of output set `o` sees it, with what "clear" means for it (a draw: DrawArgs::clear)
+    Target target(Outputs o, const float c[4]) const { return Target{ mem, tstate, epoch, make_float4(c[0], c[1], c[2], c[3]), o, has_aux(o) ? aux : nullptr, has_ids(o) ? ids : nullptr }; }
+    Target target() const { return target(out, clear); }
+    // planes up to level `want` for a w x h image (the one place that knows their sizes); free_planes: all of them
+    hipError_t reserve_planes(Outputs want, int w, int h) {
+        hipError_t e = hipSuccess;
+        if (has_aux(want) && !aux) e = hipMalloc(&aux, (size_t)w * h * sizeof(float2));
+        if (e == hipSuccess && has_ids(want) && !ids) e = hipMalloc(&ids, (size_t)w * h * 3 * sizeof(uint32_t));
+        return e;
+    }
+    void free_planes() { if (aux) (void)hipFree(aux); if (ids) (void)hipFree(ids); aux = nullptr; ids = nullptr; out = Outputs::Colour; }
 };
 
 struct Lane {
@@ -173,10 +182,8 @@ struct gs4d_ctx {
     uint64_t stat_composited_tiles = 0;      // tiles the compositing kernel of the last unordered draw was launched for (staged draws: the launch box)
     uint64_t stat_fused = 0, stat_renamed = 0, stat_shadow_bytes = 0, stat_streams_rejected = 0, stat_lanes_sharing = 0;      // lanes_sharing: lanes that had to take a stream which shares a hardware queue with another lane
     bool rename_storage = true;        // GS4D_RENAME=0 switches the storage exchange off (test hook)
-    bool aux_enable = false;           // gs4d_set_aux_outputs: the frames cleared from now on have aux outputs
-    bool aux_alloc = false;            // ... has been on once: every image has its aux plane (gs4d_resize reallocates it)
-    bool ids_enable = false;           // gs4d_set_id_outputs: the frames cleared from now on have ID outputs (and aux outputs)
-    bool ids_alloc = false;            // ... has been on once: every image has its ID planes (gs4d_resize reallocates them)
+    bool aux_enable = false, ids_enable = false;      // gs4d_set_aux_outputs, gs4d_set_id_outputs: what the frames cleared from now on have (gs4d_clear)
+    Outputs planes = Outputs::Colour;  // the highest level that has been asked for so far: every image has its planes (gs4d_resize reallocates them)
     int shrink_votes = 0;
     // Two ways to get a tile's list into blend order.  Lists of up to V2_MAX_LIST entries: built unordered, ordered by the wave that
     // composites the tile (k_composite_v2).  Longer lists, or a blend order that is not a key the library knows: the instance-ordered path
@@ -351,15 +358,20 @@ int fb_access(gs4d_ctx* c, Framebuffer& F) {
 }
 
 // every tile of the current image into memory (the lazily clear ones get their clear colour): for whoever reads or writes single pixels
-int materialise_fb(gs4d_ctx* c) {
-    Framebuffer& F = c->fbs[c->cur_fb];
+// (on lane L, which the caller has ordered after the image's last user)
+int materialise_fb(gs4d_ctx* c, Framebuffer& F, Lane& L) {
     if (!F.all_in_memory) {
-        int rc = fb_access(c, F); if (rc) return rc;
-        HIPCHK(c, launch_fill_unwritten(lane(c).s, F.mem, F.tstate, F.epoch, c->tiles_x, c->tiles_y, c->W, c->H, F.clear, F.aux_on ? F.aux : nullptr, F.ids_on ? F.ids : nullptr));
+        HIPCHK(c, launch_fill_unwritten(L.s, F.target(), c->tiles_x, c->tiles_y, c->W, c->H));
         F.all_in_memory = true;
         F.is_clear = false;
     }
     return GS4D_OK;
+}
+// ... the current image, on the current lane
+int materialise_fb(gs4d_ctx* c) {
+    Framebuffer& F = c->fbs[c->cur_fb];
+    if (!F.all_in_memory) { int rc = fb_access(c, F); if (rc) return rc; }
+    return materialise_fb(c, F, lane(c));
 }
 
 // Enqueue binning -> tile sort -> ranges -> composite for the projected records in L.proj.
@@ -386,8 +398,7 @@ int enqueue_raster(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, cons
     {
         StageTimer t(c, GS4D_T_COMPOSITE);      // the per-tile ranges and the compositing kernel
         HIPCHK(c, launch_tile_ranges(L.s, L.bin, L.pair_keys, L.pair_cap, ntiles));
-        HIPCHK(c, launch_composite(L.s, L.proj, L.pair_vals, L.bin.ranges, L.bin.total, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, F.tstate, F.epoch, a.clear, F.mem, blend_src, blend_dst,
-                                   a.aux ? F.aux : nullptr, a.ids ? F.ids : nullptr, a.draw_ord));
+        HIPCHK(c, launch_composite(L.s, L.proj, L.pair_vals, L.bin.ranges, L.bin.total, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, F.target(a.out, a.clear), blend_src, blend_dst, a.draw_ord));
     }
     return GS4D_OK;
 }
@@ -424,9 +435,8 @@ int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, s
 #endif
     {
         StageTimer t(c, GS4D_T_COMPOSITE);
-        HIPCHK(c, launch_composite_v2(L.s, L.proj, entries, L.tl.tstart, L.tl.tcnt, L.bin.total, L.host_total_dev, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, F.tstate, F.epoch, a.clear, F.mem,
-                                      c->list_hint, a.keybits, recbits, L.tl.slabs, L.tl.bstat, L.tl.nb, L.tl.sstat, L.tl.rows, L.tl.staged ? L.tl.seq : 0u, 0xFFFFFFFFu, L.tl.scap, L.tl.bcap, L.tl.box, a.aux ? F.aux : nullptr,
-                                      a.ids ? F.ids : nullptr, a.draw_ord));
+        HIPCHK(c, launch_composite_v2(L.s, L.proj, entries, L.tl.tstart, L.tl.tcnt, L.bin.total, L.host_total_dev, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, F.target(a.out, a.clear),
+                                      c->list_hint, a.keybits, recbits, L.tl.slabs, L.tl.bstat, L.tl.nb, L.tl.sstat, L.tl.rows, L.tl.staged ? L.tl.seq : 0u, 0xFFFFFFFFu, L.tl.scap, L.tl.bcap, L.tl.box, a.draw_ord));
     }
     { const uint32_t b = L.tl.staged ? L.tl.box : BOX_NONE; c->stat_composited_tiles = b == BOX_NONE ? ntiles : (uint64_t)std::min<uint32_t>((((b >> 16) & 255u) - (b & 255u) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_x) * std::min<uint32_t>(((b >> 24) - ((b >> 8) & 255u) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_y); }
     HIPCHK(c, hipEventRecord(L.ev_emit, L.s));         // totals, flags and the longest list are in pinned host memory behind this event (the compositor's first workgroup wrote them)
@@ -518,7 +528,7 @@ int run_draw(gs4d_ctx* c, const DrawArgs& a, bool preprocess) {
         if (ob && !v2) { int rc = lane_access(c, *ob, false); if (rc) return rc; ob->rd_mask |= 1u << a.lane; }
         {
             StageTimer t(c, GS4D_T_PREPROCESS);
-            const PreOut po = { L.proj, (v2 && L.tl.staged) ? nullptr : L.trects, a.aux };
+            const PreOut po = { L.proj, (v2 && L.tl.staged) ? nullptr : L.trects, has_aux(a.out) };
             L.trects_in_order = false;
             TileCount tc;
             if (v2 && L.tl.staged) { tc.stage_out = L.tl.blocks; tc.scap = L.tl.scap; tc.offs = L.tl.hist + L.tl.hist_cap; tc.abort_word = L.bin.total + TL_ABORT_WORD; tc.seq = L.tl.seq; }
@@ -708,12 +718,9 @@ int alloc_fbs(gs4d_ctx* c, int w, int h) {
         if (c->fbs[i].mem) { (void)hipFree(c->fbs[i].mem); c->fbs[i].mem = nullptr; }
         if (c->fbs[i].tstate) { (void)hipFree(c->fbs[i].tstate); c->fbs[i].tstate = nullptr; }
         if (c->fbs[i].linecnt) { (void)hipFree(c->fbs[i].linecnt); c->fbs[i].linecnt = nullptr; }
-        if (c->fbs[i].aux) { (void)hipFree(c->fbs[i].aux); c->fbs[i].aux = nullptr; }
-        if (c->fbs[i].ids) { (void)hipFree(c->fbs[i].ids); c->fbs[i].ids = nullptr; }
-        c->fbs[i].aux_on = false; c->fbs[i].ids_on = false;      // no frame of this size has been cleared yet
+        c->fbs[i].free_planes();                                 // (no frame of this size has been cleared yet: back to Outputs::Colour)
         HIPCHK(c, hipMalloc(&c->fbs[i].mem, (size_t)w * h * 16));
-        if (c->aux_alloc) HIPCHK(c, hipMalloc(&c->fbs[i].aux, (size_t)w * h * 8));
-        if (c->ids_alloc) HIPCHK(c, hipMalloc(&c->fbs[i].ids, (size_t)w * h * 12));
+        HIPCHK(c, c->fbs[i].reserve_planes(c->planes, w, h));
         const size_t nt = (size_t)((w + TILE - 1) / TILE) * ((h + TILE - 1) / TILE);
         HIPCHK(c, hipMalloc(&c->fbs[i].tstate, nt * 4));
         HIPCHK(c, hipMemset(c->fbs[i].tstate, 0, nt * 4));      // no tile is in memory: epochs start at 1
@@ -853,8 +860,7 @@ void gs4d_destroy(gs4d_ctx* c) {
         if (c->fbs[i].mem) (void)hipFree(c->fbs[i].mem);
         if (c->fbs[i].tstate) (void)hipFree(c->fbs[i].tstate);
         if (c->fbs[i].linecnt) (void)hipFree(c->fbs[i].linecnt);
-        if (c->fbs[i].aux) (void)hipFree(c->fbs[i].aux);
-        if (c->fbs[i].ids) (void)hipFree(c->fbs[i].ids);
+        c->fbs[i].free_planes();
         if (L.line_verts) (void)hipFree(L.line_verts);
         if (L.order_copy) (void)hipFree(L.order_copy);
         if (L.regen_keys) (void)hipFree(L.regen_keys);
@@ -1036,8 +1042,8 @@ int gs4d_clear(gs4d_ctx* c) {
     {
         Framebuffer& F = c->fbs[c->cur_fb];
         F.is_clear = true; F.all_in_memory = false;
-        F.ids_on = c->ids_enable && F.ids && F.aux;         // the new epoch makes every tile clear: the ID sentinel without touching the planes
-        F.aux_on = (c->aux_enable || F.ids_on) && F.aux;    // ... and (D, O) = (0, 0); ID outputs imply aux outputs
+        // the new epoch makes every tile clear — (D, O) = (0, 0), the ID sentinel — without touching the planes; ID outputs include aux outputs
+        F.out = (c->ids_enable && F.ids && F.aux) ? Outputs::Ids : ((c->ids_enable || c->aux_enable) && F.aux) ? Outputs::Aux : Outputs::Colour;
         F.draws = 0;
         if (++F.epoch == 0u) {                              // the 32-bit epoch wraps: forget every old tile word (the lane that used the image last has long finished)
             HIPCHK(c, fb_access(c, F) == GS4D_OK ? hipMemsetAsync(F.tstate, 0, (size_t)c->tiles_x * c->tiles_y * 4, lane(c).s) : hipErrorUnknown);
@@ -1200,8 +1206,8 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
         if (!ok) return fail(c, GS4D_E_UNSUPPORTED, "draw: uProj must have the sparsity of glm::perspective (P00, P11, P22, P23, P32 only)");
     }
     // aux and ID outputs are the transmittance form of the default blend function: any other function has none (nothing is drawn)
-    if (c->fbs[c->cur_fb].aux_on && !(c->blend_src == GS4D_SRC_ALPHA && c->blend_dst == GS4D_ONE_MINUS_SRC_ALPHA))
-        return fail(c, GS4D_E_UNSUPPORTED, c->fbs[c->cur_fb].ids_on ? "draw: ID outputs are defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only"
+    if (c->fbs[c->cur_fb].out != Outputs::Colour && !(c->blend_src == GS4D_SRC_ALPHA && c->blend_dst == GS4D_ONE_MINUS_SRC_ALPHA))
+        return fail(c, GS4D_E_UNSUPPORTED, has_ids(c->fbs[c->cur_fb].out) ? "draw: ID outputs are defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only"
                                                                     : "draw: aux outputs are defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only");
     // the lane's scratch still belongs to its previous draw, and the image this draw blends onto must be complete: validate those
     // (not the other lanes' draws: their frames are still in flight and nothing here depends on them)
@@ -1217,8 +1223,7 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     a.v2 = false;
     a.blend_src = c->blend_src; a.blend_dst = c->blend_dst;
     const bool over = a.blend_src == GS4D_SRC_ALPHA && a.blend_dst == GS4D_ONE_MINUS_SRC_ALPHA;       // any other function is applied in draw order: instance-ordered lists
-    a.aux = c->fbs[c->cur_fb].aux_on;
-    a.ids = c->fbs[c->cur_fb].ids_on; a.draw_ord = c->fbs[c->cur_fb].draws;
+    a.out = c->fbs[c->cur_fb].out; a.draw_ord = c->fbs[c->cur_fb].draws;
     if (c->atomic_rank && c->path_pref != 1 && over) {
         Buffer* data = getbuf(c, a.data);
         bool ok = false;
@@ -1332,28 +1337,40 @@ int gs4d_finish(gs4d_ctx* c) {
     return GS4D_OK;
 }
 
-int gs4d_read_pixels(gs4d_ctx* c, float* rgba, size_t bytes) {
-    if (!c || !rgba) return GS4D_E_INVALID;
+// What every gs4d_read_* checks first, in this order (after its own null check): the queued order, the size, the frame's outputs.
+static int read_begin(gs4d_ctx* c, bool size_ok, const char* size_msg, Outputs need = Outputs::Colour, const char* need_msg = nullptr) {
     (void)hipSetDevice(c->device);
     { int rcq = flush_order(c); if (rcq) return rcq; }
-    if (bytes != (size_t)c->W * c->H * 16) return fail(c, GS4D_E_INVALID, "read_pixels: bytes != width*height*16");
+    if (!size_ok) return fail(c, GS4D_E_INVALID, size_msg);
+    if (c->fbs[c->cur_fb].out < need) return fail(c, GS4D_E_INVALID, need_msg);
+    return GS4D_OK;
+}
+
+// A read of the current image into host memory: every tile in memory, copy(F, stream) queued on the current lane, and waited for.
+static int read_host(gs4d_ctx* c, const std::function<hipError_t(Framebuffer&, hipStream_t)>& copy) {
     int rc = resolve_image(c, c->cur_fb); if (rc) return rc;
     rc = materialise_fb(c); if (rc) return rc;
     Framebuffer& F = c->fbs[c->cur_fb];
     rc = fb_access(c, F); if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(rgba, F.mem, bytes, hipMemcpyDeviceToHost, lane(c).s));
+    HIPCHK(c, copy(F, lane(c).s));
     HIPCHK(c, hipStreamSynchronize(lane(c).s));
     if (device_error(c)) return fail(c, GS4D_E_DEVICE, DEVICE_CHECK_MSG);
     return GS4D_OK;
 }
 
+int gs4d_read_pixels(gs4d_ctx* c, float* rgba, size_t bytes) {
+    if (!c || !rgba) return GS4D_E_INVALID;
+    int rc = read_begin(c, bytes == (size_t)c->W * c->H * 16, "read_pixels: bytes != width*height*16"); if (rc) return rc;
+    return read_host(c, [&](Framebuffer& F, hipStream_t st) { return hipMemcpyAsync(rgba, F.mem, bytes, hipMemcpyDeviceToHost, st); });
+}
+
+// What a device read copies out of an image: its colour as floats or packed to RGBA8, its aux plane (W * H float2), or its ID planes
+// (W * H u32 each, into the non-null ones of dst[0..2] = record, draw, weight).  Aux and Ids: frames_back 0 only.
+enum class ReadPlane { ColourF32, ColourRGBA8, Aux, Ids };
 // frames_back 0: the image the last clear / draw used.  1: the image the last gs4d_clear moved away from (the previous frame of the
 // swap chain) — it is packed on the lane that rendered it, behind its compositing kernel, so an application that reads frame f-1
 // after queueing frame f never waits for frame f.
-// aux: the image's aux plane instead of its colour (W * H float2, frames_back 0 only).  ids_dst: the image's ID planes instead (W * H u32
-// each, into the non-null ones of record, draw, weight; frames_back 0 only).
-static int read_device_common(gs4d_ctx* c, int frames_back, void* dptr, bool rgba8, bool named_event = false, hipEvent_t after = nullptr, bool aux = false,
-                              void* const* ids_dst = nullptr) {
+static int read_device_common(gs4d_ctx* c, int frames_back, ReadPlane what, void* const* dst, bool named_event = false, hipEvent_t after = nullptr) {
     if (frames_back != 0 && frames_back != 1) return fail(c, GS4D_E_INVALID, "read_frame: frames_back must be 0 or 1");
     const int fi = frames_back == 0 ? c->cur_fb : c->prev_fb;
     if (fi < 0) return fail(c, GS4D_E_INVALID, "read_frame: no previous image is retained (one frame lane, or no gs4d_clear yet)");
@@ -1367,12 +1384,13 @@ static int read_device_common(gs4d_ctx* c, int frames_back, void* dptr, bool rgb
         HIPCHK(c, hipStreamWaitEvent(L.s, c->ev_user, 0));
     }
     if (li == c->cur) { rc = fb_access(c, F); if (rc) return rc; }
-    if (rgba8) HIPCHK(c, launch_pack_rgba8(L.s, F.mem, F.tstate, F.epoch, F.clear, c->W, c->H, c->tiles_x, (uint32_t*)dptr));      // lazily clear tiles are packed as the clear colour
+    const size_t npix = (size_t)c->W * c->H;
+    if (what == ReadPlane::ColourRGBA8) HIPCHK(c, launch_pack_rgba8(L.s, F.mem, F.tstate, F.epoch, F.clear, c->W, c->H, c->tiles_x, (uint32_t*)dst[0]));      // lazily clear tiles are packed as the clear colour
     else {
-        if (!F.all_in_memory) { HIPCHK(c, launch_fill_unwritten(L.s, F.mem, F.tstate, F.epoch, c->tiles_x, c->tiles_y, c->W, c->H, F.clear, F.aux_on ? F.aux : nullptr, F.ids_on ? F.ids : nullptr)); F.all_in_memory = true; F.is_clear = false; }
-        if (ids_dst) { for (int k = 0; k < 3; ++k) if (ids_dst[k]) HIPCHK(c, hipMemcpyAsync(ids_dst[k], F.ids + (size_t)k * c->W * c->H, (size_t)c->W * c->H * 4, hipMemcpyDeviceToDevice, L.s)); }
-        else if (aux) HIPCHK(c, hipMemcpyAsync(dptr, F.aux, (size_t)c->W * c->H * 8, hipMemcpyDeviceToDevice, L.s));
-        else HIPCHK(c, hipMemcpyAsync(dptr, F.mem, (size_t)c->W * c->H * 16, hipMemcpyDeviceToDevice, L.s));
+        rc = materialise_fb(c, F, L); if (rc) return rc;
+        if (what == ReadPlane::Ids) { for (int k = 0; k < 3; ++k) if (dst[k]) HIPCHK(c, hipMemcpyAsync(dst[k], F.ids + (size_t)k * npix, npix * 4, hipMemcpyDeviceToDevice, L.s)); }
+        else if (what == ReadPlane::Aux) HIPCHK(c, hipMemcpyAsync(dst[0], F.aux, npix * 8, hipMemcpyDeviceToDevice, L.s));
+        else HIPCHK(c, hipMemcpyAsync(dst[0], F.mem, npix * 16, hipMemcpyDeviceToDevice, L.s));
     }
     if (li != c->cur) HIPCHK(c, hipEventRecord(L.ev_tail, L.s));      // the lane's tail event keeps covering everything queued on it
     if (c->user) {                                          // work the caller queues on its stream after this call sees the pixels
@@ -1384,118 +1402,74 @@ static int read_device_common(gs4d_ctx* c, int frames_back, void* dptr, bool rgb
 
 int gs4d_read_pixels_device(gs4d_ctx* c, void* dptr, size_t bytes) {
     if (!c || !dptr) return GS4D_E_INVALID;
-    (void)hipSetDevice(c->device);
-    { int rcq = flush_order(c); if (rcq) return rcq; }
-    if (bytes != (size_t)c->W * c->H * 16) return fail(c, GS4D_E_INVALID, "read_pixels_device: bytes != width*height*16");
-    return read_device_common(c, 0, dptr, false);
+    int rc = read_begin(c, bytes == (size_t)c->W * c->H * 16, "read_pixels_device: bytes != width*height*16"); if (rc) return rc;
+    return read_device_common(c, 0, ReadPlane::ColourF32, &dptr);
 }
 
-// ---- aux outputs ----
-int gs4d_set_aux_outputs(gs4d_ctx* c, int enable) {
+// ---- aux and ID outputs ----
+// the user's two switches; the planes are made the first time a level is asked for (nothing running reads or writes them yet: no frame
+// has been cleared with it on), and the switch takes effect at the next gs4d_clear
+static int set_outputs(gs4d_ctx* c, bool& enable_flag, int enable, Outputs level) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    if (enable && !c->aux_alloc) {
-        // new planes beside the images (nothing running reads or writes them yet: no frame has been cleared with aux outputs on)
-        for (int i = 0; i < c->nlanes; ++i) if (!c->fbs[i].aux) HIPCHK(c, hipMalloc(&c->fbs[i].aux, (size_t)c->W * c->H * 8));
-        c->aux_alloc = true;
+    if (enable && c->planes < level) {
+        for (int i = 0; i < c->nlanes; ++i) HIPCHK(c, c->fbs[i].reserve_planes(level, c->W, c->H));
+        c->planes = level;
     }
-    c->aux_enable = enable != 0;                            // takes effect at the next gs4d_clear
+    enable_flag = enable != 0;
     return GS4D_OK;
 }
+int gs4d_set_aux_outputs(gs4d_ctx* c, int enable) { return c ? set_outputs(c, c->aux_enable, enable, Outputs::Aux) : GS4D_E_INVALID; }
+int gs4d_set_id_outputs(gs4d_ctx* c, int enable) { return c ? set_outputs(c, c->ids_enable, enable, Outputs::Ids) : GS4D_E_INVALID; }
 
 int gs4d_read_aux(gs4d_ctx* c, float* depth_opacity, size_t bytes) {
     if (!c || !depth_opacity) return GS4D_E_INVALID;
-    (void)hipSetDevice(c->device);
-    { int rcq = flush_order(c); if (rcq) return rcq; }
-    if (bytes != (size_t)c->W * c->H * 8) return fail(c, GS4D_E_INVALID, "read_aux: bytes != width*height*8");
-    if (!c->fbs[c->cur_fb].aux_on) return fail(c, GS4D_E_INVALID, "read_aux: the current frame was not cleared with aux outputs on");
-    int rc = resolve_image(c, c->cur_fb); if (rc) return rc;
-    rc = materialise_fb(c); if (rc) return rc;
-    Framebuffer& F = c->fbs[c->cur_fb];
-    rc = fb_access(c, F); if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(depth_opacity, F.aux, bytes, hipMemcpyDeviceToHost, lane(c).s));
-    HIPCHK(c, hipStreamSynchronize(lane(c).s));
-    if (device_error(c)) return fail(c, GS4D_E_DEVICE, DEVICE_CHECK_MSG);
-    return GS4D_OK;
+    int rc = read_begin(c, bytes == (size_t)c->W * c->H * 8, "read_aux: bytes != width*height*8", Outputs::Aux, "read_aux: the current frame was not cleared with aux outputs on"); if (rc) return rc;
+    return read_host(c, [&](Framebuffer& F, hipStream_t st) { return hipMemcpyAsync(depth_opacity, F.aux, bytes, hipMemcpyDeviceToHost, st); });
 }
 
 int gs4d_read_aux_device(gs4d_ctx* c, void* dptr, size_t bytes) {
     if (!c || !dptr) return GS4D_E_INVALID;
-    (void)hipSetDevice(c->device);
-    { int rcq = flush_order(c); if (rcq) return rcq; }
-    if (bytes != (size_t)c->W * c->H * 8) return fail(c, GS4D_E_INVALID, "read_aux_device: bytes != width*height*8");
-    if (!c->fbs[c->cur_fb].aux_on) return fail(c, GS4D_E_INVALID, "read_aux_device: the current frame was not cleared with aux outputs on");
-    return read_device_common(c, 0, dptr, false, false, nullptr, true);
-}
-
-// ---- ID outputs ----
-int gs4d_set_id_outputs(gs4d_ctx* c, int enable) {
-    if (!c) return GS4D_E_INVALID;
-    (void)hipSetDevice(c->device);
-    if (enable && !c->ids_alloc) {
-        // new planes beside the images (nothing running reads or writes them yet: no frame has been cleared with ID outputs on); ID outputs
-        // come with aux outputs, so the aux planes too
-        for (int i = 0; i < c->nlanes; ++i) {
-            if (!c->fbs[i].aux) HIPCHK(c, hipMalloc(&c->fbs[i].aux, (size_t)c->W * c->H * 8));
-            if (!c->fbs[i].ids) HIPCHK(c, hipMalloc(&c->fbs[i].ids, (size_t)c->W * c->H * 12));
-        }
-        c->aux_alloc = c->ids_alloc = true;
-    }
-    c->ids_enable = enable != 0;                            // takes effect at the next gs4d_clear
-    return GS4D_OK;
+    int rc = read_begin(c, bytes == (size_t)c->W * c->H * 8, "read_aux_device: bytes != width*height*8", Outputs::Aux, "read_aux_device: the current frame was not cleared with aux outputs on"); if (rc) return rc;
+    return read_device_common(c, 0, ReadPlane::Aux, &dptr);
 }
 
 int gs4d_read_ids(gs4d_ctx* c, int x, int y, int w, int h, uint32_t* record, uint32_t* draw, float* weight) {
     if (!c) return GS4D_E_INVALID;
-    (void)hipSetDevice(c->device);
-    { int rcq = flush_order(c); if (rcq) return rcq; }
-    if (x < 0 || y < 0 || w <= 0 || h <= 0 || w > c->W - x || h > c->H - y) return fail(c, GS4D_E_INVALID, "read_ids: the rectangle is not inside the image");
-    if (!c->fbs[c->cur_fb].ids_on) return fail(c, GS4D_E_INVALID, "read_ids: the current frame was not cleared with ID outputs on");
-    int rc = resolve_image(c, c->cur_fb); if (rc) return rc;
-    rc = materialise_fb(c); if (rc) return rc;
-    Framebuffer& F = c->fbs[c->cur_fb];
-    rc = fb_access(c, F); if (rc) return rc;
+    int rc = read_begin(c, !(x < 0 || y < 0 || w <= 0 || h <= 0 || w > c->W - x || h > c->H - y), "read_ids: the rectangle is not inside the image", Outputs::Ids,
+                        "read_ids: the current frame was not cleared with ID outputs on"); if (rc) return rc;
     void* const dst[3] = { record, draw, weight };
-    const size_t plane = (size_t)c->W * c->H, pitch = (size_t)c->W * 4;
-    for (int k = 0; k < 3; ++k)
-        if (dst[k]) HIPCHK(c, hipMemcpy2DAsync(dst[k], (size_t)w * 4, F.ids + k * plane + (size_t)y * c->W + x, pitch, (size_t)w * 4, (size_t)h, hipMemcpyDeviceToHost, lane(c).s));
-    HIPCHK(c, hipStreamSynchronize(lane(c).s));
-    if (device_error(c)) return fail(c, GS4D_E_DEVICE, DEVICE_CHECK_MSG);
-    return GS4D_OK;
+    return read_host(c, [&](Framebuffer& F, hipStream_t st) {
+        const size_t plane = (size_t)c->W * c->H, pitch = (size_t)c->W * 4;
+        for (int k = 0; k < 3; ++k)
+            if (dst[k]) { const hipError_t e = hipMemcpy2DAsync(dst[k], (size_t)w * 4, F.ids + k * plane + (size_t)y * c->W + x, pitch, (size_t)w * 4, (size_t)h, hipMemcpyDeviceToHost, st); if (e != hipSuccess) return e; }
+        return hipSuccess;
+    });
 }
 
 int gs4d_read_ids_device(gs4d_ctx* c, void* record, void* draw, void* weight, size_t bytes_per_plane) {
     if (!c || (!record && !draw && !weight)) return GS4D_E_INVALID;
-    (void)hipSetDevice(c->device);
-    { int rcq = flush_order(c); if (rcq) return rcq; }
-    if (bytes_per_plane != (size_t)c->W * c->H * 4) return fail(c, GS4D_E_INVALID, "read_ids_device: bytes_per_plane != width*height*4");
-    if (!c->fbs[c->cur_fb].ids_on) return fail(c, GS4D_E_INVALID, "read_ids_device: the current frame was not cleared with ID outputs on");
+    int rc = read_begin(c, bytes_per_plane == (size_t)c->W * c->H * 4, "read_ids_device: bytes_per_plane != width*height*4", Outputs::Ids, "read_ids_device: the current frame was not cleared with ID outputs on"); if (rc) return rc;
     void* const dst[3] = { record, draw, weight };
-    return read_device_common(c, 0, nullptr, false, false, nullptr, false, dst);
+    return read_device_common(c, 0, ReadPlane::Ids, dst);
 }
 
 int gs4d_read_pixels_rgba8_device(gs4d_ctx* c, void* dptr, size_t bytes) {
     if (!c || !dptr) return GS4D_E_INVALID;
-    (void)hipSetDevice(c->device);
-    { int rcq = flush_order(c); if (rcq) return rcq; }
-    if (bytes != (size_t)c->W * c->H * 4) return fail(c, GS4D_E_INVALID, "read_pixels_rgba8_device: bytes != width*height*4");
-    return read_device_common(c, 0, dptr, true);
+    int rc = read_begin(c, bytes == (size_t)c->W * c->H * 4, "read_pixels_rgba8_device: bytes != width*height*4"); if (rc) return rc;
+    return read_device_common(c, 0, ReadPlane::ColourRGBA8, &dptr);
 }
 
 int gs4d_read_frame_rgba8_device(gs4d_ctx* c, int frames_back, void* dptr, size_t bytes) {
     if (!c || !dptr) return GS4D_E_INVALID;
-    (void)hipSetDevice(c->device);
-    { int rcq = flush_order(c); if (rcq) return rcq; }
-    if (bytes != (size_t)c->W * c->H * 4) return fail(c, GS4D_E_INVALID, "read_frame_rgba8_device: bytes != width*height*4");
-    return read_device_common(c, frames_back, dptr, true);
+    int rc = read_begin(c, bytes == (size_t)c->W * c->H * 4, "read_frame_rgba8_device: bytes != width*height*4"); if (rc) return rc;
+    return read_device_common(c, frames_back, ReadPlane::ColourRGBA8, &dptr);
 }
 
 int gs4d_read_frame_rgba8_device_after(gs4d_ctx* c, int frames_back, void* dptr, size_t bytes, void* hip_event) {
     if (!c || !dptr) return GS4D_E_INVALID;
-    (void)hipSetDevice(c->device);
-    { int rcq = flush_order(c); if (rcq) return rcq; }
-    if (bytes != (size_t)c->W * c->H * 4) return fail(c, GS4D_E_INVALID, "read_frame_rgba8_device_after: bytes != width*height*4");
-    return read_device_common(c, frames_back, dptr, true, true, (hipEvent_t)hip_event);
+    int rc = read_begin(c, bytes == (size_t)c->W * c->H * 4, "read_frame_rgba8_device_after: bytes != width*height*4"); if (rc) return rc;
+    return read_device_common(c, frames_back, ReadPlane::ColourRGBA8, &dptr, true, (hipEvent_t)hip_event);
 }
 
 static int band_pixel_rows(const gs4d_ctx* c) {

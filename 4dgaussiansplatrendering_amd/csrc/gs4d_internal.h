@@ -17,6 +17,26 @@ constexpr int PROJ_FLOATS = 16;     // projected record: 64 B, one aligned segme
 //  D = hx, hy, valid(1/0), depth   (depth = -z_view of the centre when the draw has aux outputs, else 0; gs4d_debug_read_projected hands them out in the order documented in gs4d.h)
 // rect0 > rect1 in x (x0 = 1, x1 = 0) marks "no coverage".
 
+// ---- the outputs of a frame ----
+// What the compositing kernels write per pixel, fixed for a frame by its gs4d_clear; each level includes the ones below it.
+//   Colour  the RGBA32F image.
+//   Aux     also (D, O) per pixel in a float2 plane: D = sum of w * depth with the weight w the colour uses and the depth of the entry's
+//           projected record (slot 15), O = 1 - T; a draw is composed onto what the plane holds with the colour's "over":
+//           (D, O) <- (D_draw + T * D, (1 - T) + T * O).  A tile not in memory holds (0, 0).
+//   Ids     also three W x H planes of u32 in one allocation — record, draw ordinal within the frame, bits of the weight: per draw the
+//           fragment of the largest weight w > 0 (front-most on a tie), composed over the stored triple by id_over (composite_common.h).  A
+//           pixel no fragment has reached, and a tile not in memory, hold the sentinel {0xFFFFFFFF, 0xFFFFFFFF, 0.0f}.
+// Aux and Ids are the transmittance form of the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA); any other function has Colour only.
+enum class Outputs : int { Colour = 0, Aux = 1, Ids = 2 };
+constexpr bool has_aux(Outputs o) { return o >= Outputs::Aux; }
+constexpr bool has_ids(Outputs o) { return o >= Outputs::Ids; }
+// An image as a draw or a fill sees it.  tstate / epoch: the tile state (composite.hip): tstate[tile] == epoch <=> the tile's pixels are in
+// memory, else it is still the clear colour.  aux, ids: the planes of `out`, null above that level.  Made by Framebuffer::target (gs4d_api.hip).
+struct Target {
+    float4* fb; uint32_t* tstate; uint32_t epoch; float4 clear;
+    Outputs out; float2* aux; uint32_t* ids;
+};
+
 struct Uniforms {
     float view[16];
     float proj[16];
@@ -203,10 +223,10 @@ hipError_t launch_bucket_tiles_staged(hipStream_t st, TileLists& t, size_t ntile
 hipError_t tile_lists_reserve_blocks(hipStream_t st, TileLists& t, size_t entries);
 // bstat / nb, sstat / rows: per-bucket and per-segment statistics for the host report; stage_seq != 0: a staged draw (aborted <=> total[TL_ABORT_WORD] == stage_seq,
 // the entry total is the sum of the statistics); rcap / scap / bcap: what the host guessed for it (longest run: no limit any more, 0xFFFFFFFF; fullest segment; fullest bucket)
+// t: the image; draw_ord: the draw's ordinal within its frame (Outputs::Ids)
 hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* entries, const uint32_t* tstart, const uint32_t* tcnt, const uint32_t* total, uint32_t* total_host, int tiles_x, int tiles_y, int W, int H,
-                               int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, uint32_t hint, int keybits, int recbits, uint32_t slabs,
-                               const uint4* bstat = nullptr, uint32_t nb = 0, const uint32_t* sstat = nullptr, uint32_t rows = 0, uint32_t stage_seq = 0, uint32_t rcap = 0, uint32_t scap = 0, uint32_t bcap = 0, uint32_t box_blocks = 0xFFFFFFFFu,
-                               float2* aux = nullptr, uint32_t* ids = nullptr, uint32_t draw_ord = 0u);
+                               int premult_c, const Target& t, uint32_t hint, int keybits, int recbits, uint32_t slabs,
+                               const uint4* bstat, uint32_t nb, const uint32_t* sstat, uint32_t rows, uint32_t stage_seq, uint32_t rcap, uint32_t scap, uint32_t bcap, uint32_t box_blocks, uint32_t draw_ord);
 
 #ifdef __HIPCC__
 // tiles touched by a pixel rectangle (x0|y0<<16, x1|y1<<16; x0 > x1: none), restricted to the tile rows ty % world == rank
@@ -282,15 +302,11 @@ hipError_t launch_binning(hipStream_t st, BinScratch& b, const uint32_t* trects,
 hipError_t launch_tile_ranges(hipStream_t st, BinScratch& b, const uint32_t* pair_keys, size_t pair_cap, size_t ntiles);
 
 // ---- composite.hip ----
-// tstate / epoch: the image's tile state (composite.hip): tstate[tile] == epoch <=> the tile's pixels are in memory, else it is still the clear colour
-// aux: the image's aux plane (float2 {D, O} per pixel) when its frame was cleared with aux outputs on, else null
-// ids: the image's three ID planes (record, draw, weight bits; W * H u32 each) when its frame was cleared with ID outputs on (aux is then
-// set too), else null; draw_ord: the draw's ordinal within its frame
+// t: the image (Target); draw_ord: the draw's ordinal within its frame (Outputs::Ids)
 hipError_t launch_composite(hipStream_t st, const float4* proj, const uint32_t* pair_vals, uint32_t* ranges, const uint32_t* total, int tiles_x, int tiles_y,
-                            int W, int H, int premult_c, uint32_t* tstate, uint32_t epoch, const float clear[4], float4* fb, int blend_src, int blend_dst, float2* aux = nullptr,
-                            uint32_t* ids = nullptr, uint32_t draw_ord = 0u);
-hipError_t launch_fill_unwritten(hipStream_t st, float4* fb, uint32_t* tstate, uint32_t epoch, int tiles_x, int tiles_y, int W, int H, const float clear[4], float2* aux = nullptr,
-                                 uint32_t* ids = nullptr);
+                            int W, int H, int premult_c, const Target& t, int blend_src, int blend_dst, uint32_t draw_ord);
+hipError_t launch_fill_unwritten(hipStream_t st, const Target& t, int tiles_x, int tiles_y, int W, int H);
+// tstate / epoch / clear: as in Target
 hipError_t launch_pack_rgba8(hipStream_t st, const float4* fb, const uint32_t* tstate, uint32_t epoch, const float clear[4], int W, int H, int tiles_x, uint32_t* out);
 // the pixel rows of the tile rows ty % world == rank, top of the band = the context's first tile row; band_rows pixel rows in all
 hipError_t launch_pack_rgba8_band(hipStream_t st, const float4* fb, const uint32_t* tstate, uint32_t epoch, const float clear[4], int W, int H, int tiles_x, int rank, int world, int band_rows, uint32_t* out);

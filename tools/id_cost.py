@@ -1,8 +1,8 @@
 """What ID outputs (gs4d_set_id_outputs) cost a frame: the C2 set (configs[1]: 10^6 static 3D splats) and configs[3]'s 10^6 4D
 splats at t = 25, 1080p, the reference's frame loop (clear -> keygen -> sort -> draw), with IDs off, aux outputs on, and IDs on (which
 implies aux), in rotating windows of one context each.  Prints one JSON line.  Usage: python tools/id_cost.py [steps] [rounds].
-Kernel split: run it under rocprofv3 --kernel-trace --stats, where the ID compositor instances are the k_composite / k_composite_v2
-instantiations whose last two template arguments are both true."""
+Kernel split: run it under rocprofv3 --kernel-trace --stats, where the compositor instances of a mode are the k_composite / k_composite_v2
+instantiations whose last template argument is Outputs::Colour ((gs4d::Outputs)0), Outputs::Aux (1) or Outputs::Ids (2)."""
 import importlib
 import json
 import os
