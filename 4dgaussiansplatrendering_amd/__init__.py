@@ -80,6 +80,7 @@ def _load():
         "gs4d_set_id_outputs": (i32, [vp, i32]),
         "gs4d_read_ids": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "gs4d_read_ids_device": (i32, [vp, vp, vp, vp, sz]),
+        "gs4d_set_depth_test": (i32, [vp, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -514,6 +515,20 @@ class Context:
         depth = float(do[0] / do[1]) if do[1] > 0.0 else 0.0
         return {"record": int(rec[0, 0]), "draw": int(drw[0, 0]), "weight": float(wt[0, 0]), "depth": depth,
                 "point": unproject(view, proj, self.width, self.height, px, py, depth)}
+
+    # depth test against the caller's depth plane: splats among opaque geometry
+    def depth_plane(self, z):
+        """A buffer for set_depth_test from an (H, W) float32 array of view depths (-z_view, rows bottom-up like read_pixels; +inf = no
+        geometry)."""
+        a = np.ascontiguousarray(z, np.float32)
+        if a.shape != (self.height, self.width):
+            raise ValueError(f"depth_plane: expected shape {(self.height, self.width)}, got {a.shape}")
+        return self.buffer(a)
+
+    def set_depth_test(self, plane):
+        """Draws issued from now on blend a fragment of depth d at pixel p only where d < Z[p] (GL_LESS) against the buffer `plane`
+        (depth_plane); None or 0 turns the test off.  Draw state: it survives clear(); deleting the buffer turns it off."""
+        self._chk(_lib.gs4d_set_depth_test(self._h, int(plane or 0)))
 
     def set_tile_shard(self, rank, world):
         """Single-frame sharding: this context bins and composites the tile rows ty % world == rank only."""

@@ -99,20 +99,22 @@ hipError_t launch_pack_rgba8_band(hipStream_t st, const float4* fb, const uint32
     return hipGetLastError();
 }
 
-// OUT: the outputs of the image's frame (Outputs, gs4d_internal.h); aux, ids: their planes.
-template <bool PREMULT_C, bool GENERAL, Outputs OUT>
+// OUT: the outputs of the image's frame (Outputs, gs4d_internal.h); aux, ids: their planes.  ZTEST: the draw has a depth test against the
+// W x H plane zplane (Target::z).
+template <bool PREMULT_C, bool GENERAL, Outputs OUT, bool ZTEST>
 __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ proj, const uint32_t* __restrict__ pair_vals, uint32_t* __restrict__ ranges,
                                                   const uint32_t* __restrict__ total, int tiles_x, int W, int H, uint32_t* __restrict__ tstate, uint32_t epoch, float4 clear,
-                                                  float4* __restrict__ fb, int dbg_arg, BlendFn bf, float2* __restrict__ aux, uint32_t* __restrict__ ids, uint32_t draw_ord) {
-    static_assert(!GENERAL || OUT == Outputs::Colour, "aux and ID outputs are defined for the default blend function only");
+                                                  float4* __restrict__ fb, int dbg_arg, BlendFn bf, float2* __restrict__ aux, uint32_t* __restrict__ ids, uint32_t draw_ord,
+                                                  const float* __restrict__ zplane) {
+    static_assert(!GENERAL || (OUT == Outputs::Colour && !ZTEST), "aux and ID outputs and the depth test are defined for the default blend function only");
 #ifdef GS4D_TUNING
     const int dbg = dbg_arg;             // GS4D_COMPOSITE_DBG: tuning builds only (make TUNING=1)
 #else
     constexpr int dbg = 0; (void)dbg_arg;
 #endif
-    __shared__ float4 sh_stage[stage_words(OUT) / 4];
+    __shared__ float4 sh_stage[stage_words(OUT, ZTEST) / 4];
     __shared__ uint32_t pmask[64 * 2];
-    const Stage<OUT> stage(sh_stage);
+    const Stage<OUT, ZTEST> stage(sh_stage);
     if (total[1]) return;                                   // tile lists overflowed: nothing was emitted, the host re-runs
     uint32_t tile;
     if (!composite_tile(blockIdx.x, tiles_x, (H + TILE - 1) / TILE, tile)) return;        // uniform: padding of the XCD-aware grid
@@ -135,17 +137,19 @@ __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ pro
         for (uint32_t lo = start; lo < end; lo += 64u) {
             const uint32_t cnt = min(64u, end - lo);
             const uint32_t rec = lane < cnt ? pair_vals[lo + lane] : 0u;         // lane s holds list entry lo+s: s = 0 is drawn first
-            composite_chunk<PREMULT_C, GENERAL, OUT>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, acc, bf);
+            composite_chunk<PREMULT_C, GENERAL, OUT, ZTEST>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, acc, bf, 0.0f);
         }
         if (in) fb[o] = make_float4(acc.Cr, acc.Cg, acc.Cb, acc.A);
         if (lane == 0u) tstate[tile] = epoch;
         return;
     }
+    // the lane's pixel's depth-test value, loaded once per tile (a lane outside the image tests against +inf: its result is never stored)
+    const float z = (ZTEST && px < W && py < H) ? zplane[(size_t)py * W + px] : __builtin_inff();
     for (uint32_t hi = end; hi > start;) {
         const uint32_t cnt = min(64u, hi - start);
         // lane s holds list entry hi-1-s : s = 0 is the LAST (front-most) entry of this chunk
         const uint32_t rec = lane < cnt ? pair_vals[hi - 1u - lane] : 0u;
-        composite_chunk<PREMULT_C, GENERAL, OUT>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, acc, bf);
+        composite_chunk<PREMULT_C, GENERAL, OUT, ZTEST>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, acc, bf, z);
         hi -= cnt;
         if (__ballot(acc.T > 0.0f) == 0ull) break;          // exact: every remaining contribution is multiplied by T == 0
     }
@@ -167,10 +171,10 @@ hipError_t launch_composite(hipStream_t st, const float4* proj, const uint32_t* 
 #endif
     const BlendFn bf{ blend_src, blend_dst };
     const bool general = !(blend_src == GS4D_SRC_ALPHA && blend_dst == GS4D_ONE_MINUS_SRC_ALPHA);
-    if (general && t.out != Outputs::Colour) return hipErrorInvalidValue;       // the host refuses such a draw (GS4D_E_UNSUPPORTED) before it gets here
-    for_outputs(premult_c != 0, t.out, [&](auto pc, auto out) {
-        if (general) k_composite<pc(), true, Outputs::Colour><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, nullptr, nullptr, 0u);
-        else k_composite<pc(), false, out()><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, t.aux, t.ids, draw_ord);
+    if (general && (t.out != Outputs::Colour || t.z)) return hipErrorInvalidValue;       // the host refuses such a draw (GS4D_E_UNSUPPORTED) before it gets here
+    for_outputs(premult_c != 0, t.out, t.z != nullptr, [&](auto pc, auto out, auto zt) {
+        if (general) k_composite<pc(), true, Outputs::Colour, false><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, nullptr, nullptr, 0u, nullptr);
+        else k_composite<pc(), false, out(), zt()><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, t.aux, t.ids, draw_ord, t.z);
     });
     return hipGetLastError();
 }

@@ -99,11 +99,12 @@ struct PixelAcc {
     float T = 1.0f, Cr = 0.0f, Cg = 0.0f, Cb = 0.0f, A = 0.0f, D = 0.0f, BW = 0.0f;
 };
 
-// d: the entry's depth (Outputs::Aux on), rid: its record index (Outputs::Ids); a lane without a fragment blends with al = 0, so w = 0 and
-// it never becomes the candidate.
-template <bool PREMULT_C, bool GENERAL, Outputs OUT>
-__device__ __forceinline__ void blend_fragment(float u, float v, float alpha, float r_, float g_, float b_, PixelAcc& p, BlendFn bf, float d, uint32_t rid) {
-    static_assert(!GENERAL || OUT == Outputs::Colour, "aux and ID outputs are defined for the default blend function only");
+// d: the entry's depth (Outputs::Aux on, or ZTEST), rid: its record index (Outputs::Ids); a lane without a fragment blends with al = 0, so w = 0
+// and it never becomes the candidate.  ZTEST: z is the pixel's value of the draw's depth-test plane; a fragment with d < z false (GL_LESS: a
+// NaN hides) is hidden like a discarded one — al = 0 — so colour, aux and ID candidate all follow the test.
+template <bool PREMULT_C, bool GENERAL, Outputs OUT, bool ZTEST>
+__device__ __forceinline__ void blend_fragment(float u, float v, float alpha, float r_, float g_, float b_, PixelAcc& p, BlendFn bf, float d, uint32_t rid, float z) {
+    static_assert(!GENERAL || (OUT == Outputs::Colour && !ZTEST), "aux and ID outputs and the depth test are defined for the default blend function only");
     const float cg = gauss_weight(u, v);
     if (GENERAL) {
         if (cg >= 0.0001f) {                               // Splat4DFragShader.GLSL:30 discard
@@ -118,7 +119,8 @@ __device__ __forceinline__ void blend_fragment(float u, float v, float alpha, fl
     // No branch: a discarded fragment (Splat4DFragShader.GLSL:30) — and a lane that has no fragment at all, which passes alpha = 0 — blends
     // with al = 0, which leaves C and T as they are, exactly (C + 0 * c, T * 1).  The compositor is bound by instruction issue; a divergent
     // region costs four wave instructions whether or not a lane takes it.
-    const float al = cg >= 0.0001f ? clamp01(alpha * cg) : 0.0f;
+    // (The depth test is one more compare in the same select.)
+    const float al = (cg >= 0.0001f && (!ZTEST || d < z)) ? clamp01(alpha * cg) : 0.0f;
     const float w = p.T * al;
     if (PREMULT_C) { r_ = clamp01(r_ * cg); g_ = clamp01(g_ * cg); b_ = clamp01(b_ * cg); }   // Splat3DFragShaderFull.GLSL:22
     p.Cr += w * r_; p.Cg += w * g_; p.Cb += w * b_; p.A += w * al;
@@ -153,36 +155,39 @@ __device__ __forceinline__ void store_over(const PixelAcc& p, size_t o, bool fb_
     }
 }
 
-// The LDS a chunk of <= 64 list entries is staged in: three float4 of every entry's projected record; from Outputs::Aux on the entries' depths
-// (the last float of the same 64-byte record) behind them; from Outputs::Ids on their record indices behind those.  A kernel gives it
-// stage_words(OUT) words, 16-byte aligned.
-constexpr int stage_words(Outputs o) { return 64 * 3 * 4 + (has_aux(o) ? 64 : 0) + (has_ids(o) ? 64 : 0); }
-template <Outputs OUT>
+// The LDS a chunk of <= 64 list entries is staged in: three float4 of every entry's projected record; from Outputs::Aux on, or with the depth
+// test (ZTEST), the entries' depths (the last float of the same 64-byte record) behind them; from Outputs::Ids on their record indices behind
+// those.  A kernel gives it stage_words(OUT, ZTEST) words, 16-byte aligned.
+constexpr bool stages_depth(Outputs o, bool ztest) { return has_aux(o) || ztest; }
+constexpr int stage_words(Outputs o, bool ztest) { return 64 * 3 * 4 + (stages_depth(o, ztest) ? 64 : 0) + (has_ids(o) ? 64 : 0); }
+template <Outputs OUT, bool ZTEST>
 struct Stage {
     float4* rec; float* depth; uint32_t* rid;
-    __device__ __forceinline__ explicit Stage(float4* records) : rec(records), depth(has_aux(OUT) ? reinterpret_cast<float*>(records + 64 * 3) : nullptr),
+    __device__ __forceinline__ explicit Stage(float4* records) : rec(records), depth(stages_depth(OUT, ZTEST) ? reinterpret_cast<float*>(records + 64 * 3) : nullptr),
                                                                  rid(has_ids(OUT) ? reinterpret_cast<uint32_t*>(records + 64 * 3 + 16) : nullptr) {}
 };
 
-// Host side of a launch: f(premultiplied colours?, output set) with both as compile-time constants (std::integral_constant).
+// Host side of a launch: f(premultiplied colours?, output set, depth test?) with all three as compile-time constants (std::integral_constant).
 template <class F>
-inline void for_outputs(bool premult_c, Outputs out, F&& f) {
-    auto with = [&](auto pc) {
+inline void for_outputs(bool premult_c, Outputs out, bool ztest, F&& f) {
+    auto with = [&](auto pc, auto zt) {
         switch (out) {
-        case Outputs::Ids: f(pc, std::integral_constant<Outputs, Outputs::Ids>{}); break;
-        case Outputs::Aux: f(pc, std::integral_constant<Outputs, Outputs::Aux>{}); break;
-        default: f(pc, std::integral_constant<Outputs, Outputs::Colour>{}); break;
+        case Outputs::Ids: f(pc, std::integral_constant<Outputs, Outputs::Ids>{}, zt); break;
+        case Outputs::Aux: f(pc, std::integral_constant<Outputs, Outputs::Aux>{}, zt); break;
+        default: f(pc, std::integral_constant<Outputs, Outputs::Colour>{}, zt); break;
         }
     };
-    if (premult_c) with(std::true_type{}); else with(std::false_type{});
+    auto with_z = [&](auto pc) { if (ztest) with(pc, std::true_type{}); else with(pc, std::false_type{}); };
+    if (premult_c) with_z(std::true_type{}); else with_z(std::false_type{});
 }
 
 // One chunk of the tile's list, front to back: lane s < cnt carries record `rec` of list entry (end of chunk - 1 - s), so s = 0 is the
 // front-most entry.  GENERAL: the chunk is walked in DRAW order instead — lane s carries list entry (start of chunk + s).
-// pmask: 64 x 2 words of LDS (per pixel: 64-bit mask of the chunk entries that cover it).
-template <bool PREMULT_C, bool GENERAL, Outputs OUT>
-__device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj, uint32_t rec, uint32_t cnt, uint32_t lane, int tx0, int ty0, float fx, float fy, const Stage<OUT>& st, uint32_t* pmask, int dbg,
-                                                PixelAcc& acc, BlendFn bf) {
+// pmask: 64 x 2 words of LDS (per pixel: 64-bit mask of the chunk entries that cover it).  z: the lane's pixel's depth-test value (ZTEST).
+template <bool PREMULT_C, bool GENERAL, Outputs OUT, bool ZTEST>
+__device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj, uint32_t rec, uint32_t cnt, uint32_t lane, int tx0, int ty0, float fx, float fy, const Stage<OUT, ZTEST>& st, uint32_t* pmask, int dbg,
+                                                PixelAcc& acc, BlendFn bf, float z) {
+    constexpr bool DEPTH = stages_depth(OUT, ZTEST);
     float4* const stage = st.rec;
 
     // lane s holds list entry hi-1-s : s = 0 is the LAST (front-most) entry of this chunk
@@ -195,7 +200,7 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
         stage[lane * 3 + 0] = ra;
         stage[lane * 3 + 1] = rb;
         stage[lane * 3 + 2] = rc;
-        if (has_aux(OUT)) st.depth[lane] = reinterpret_cast<const float*>(r)[15];
+        if (DEPTH) st.depth[lane] = reinterpret_cast<const float*>(r)[15];
         if (has_ids(OUT)) st.rid[lane] = rec;
         const uint32_t r0 = __float_as_uint(rc.z), r1 = __float_as_uint(rc.w);
         lx0 = max((int)(r0 & 0xFFFFu) - tx0, 0); ly0 = max((int)(r0 >> 16) - ty0, 0);
@@ -219,9 +224,9 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const bool cov = fabsf(u) <= 0.5f && fabsf(v) <= 0.5f;
             if (__ballot(cov) == 0ull) continue;
             const float4 c = stage[s * 3 + 2];          // b, alpha, -, -
-            const float d = has_aux(OUT) ? st.depth[s] : 0.0f;
+            const float d = DEPTH ? st.depth[s] : 0.0f;
             const uint32_t rid = has_ids(OUT) ? st.rid[s] : 0u;
-            if (cov) blend_fragment<PREMULT_C, GENERAL, OUT>(u, v, c.y, b.z, b.w, c.x, acc, bf, d, rid);
+            if (cov) blend_fragment<PREMULT_C, GENERAL, OUT, ZTEST>(u, v, c.y, b.z, b.w, c.x, acc, bf, d, rid, z);
         }
     } else {
         // ---- phase A (lane = entry): mark the covered pixels of small footprints ----
@@ -279,8 +284,8 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const float dx = __fsub_rn(fx, a.x), dy = __fsub_rn(fy, a.y);
             const float u = __fmaf_rn(a.z, dx, __fmul_rn(b.x, dy));
             const float v = __fmaf_rn(a.w, dx, __fmul_rn(b.y, dy));
-            if constexpr (GENERAL) { if (on) blend_fragment<PREMULT_C, true, OUT>(u, v, c.y, b.z, b.w, c.x, acc, bf, 0.0f, 0u); }
-            else blend_fragment<PREMULT_C, false, OUT>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, acc, bf, has_aux(OUT) ? st.depth[e] : 0.0f, has_ids(OUT) ? st.rid[e] : 0u);
+            if constexpr (GENERAL) { if (on) blend_fragment<PREMULT_C, true, OUT, false>(u, v, c.y, b.z, b.w, c.x, acc, bf, 0.0f, 0u, 0.0f); }
+            else blend_fragment<PREMULT_C, false, OUT, ZTEST>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, acc, bf, DEPTH ? st.depth[e] : 0.0f, has_ids(OUT) ? st.rid[e] : 0u, z);
         }
     }
     __syncthreads();

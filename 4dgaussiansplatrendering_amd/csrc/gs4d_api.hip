@@ -82,6 +82,7 @@ struct DrawArgs {
     uint64_t stage_geom = 0;        // set by run_draw: the list geometry the draw's bucket statistics belong to (resolve_lane files them under it)
     Outputs out = Outputs::Colour;  // what the image's frame was cleared with: from Aux on the projection stores depths in its records
     uint32_t draw_ord = 0;          // the draw's ordinal within its frame (a re-run keeps it)
+    gs4d_buf zplane = 0;            // the depth-test plane bound when the draw was issued (gs4d_set_depth_test; 0: no test) — it, too, makes the projection store depths
 };
 
 struct Framebuffer {
@@ -183,6 +184,7 @@ struct gs4d_ctx {
     uint64_t stat_fused = 0, stat_renamed = 0, stat_shadow_bytes = 0, stat_streams_rejected = 0, stat_lanes_sharing = 0;      // lanes_sharing: lanes that had to take a stream which shares a hardware queue with another lane
     bool rename_storage = true;        // GS4D_RENAME=0 switches the storage exchange off (test hook)
     bool aux_enable = false, ids_enable = false;      // gs4d_set_aux_outputs, gs4d_set_id_outputs: what the frames cleared from now on have (gs4d_clear)
+    gs4d_buf depth_plane = 0;          // gs4d_set_depth_test: draw state like glBlendFunc's (survives gs4d_clear; deleting the buffer unbinds it); 0: no test
     Outputs planes = Outputs::Colour;  // the highest level that has been asked for so far: every image has its planes (gs4d_resize reallocates them)
     int shrink_votes = 0;
     // Two ways to get a tile's list into blend order.  Lists of up to V2_MAX_LIST entries: built unordered, ordered by the wave that
@@ -225,6 +227,12 @@ const char* const DEVICE_CHECK_MSG = "device-side check failed (a bounded look-b
 
 Buffer* getbuf(gs4d_ctx* c, gs4d_buf b) { return (b != 0 && b < c->bufs.size() && c->bufs[b].alive) ? &c->bufs[b] : nullptr; }
 Lane& lane(gs4d_ctx* c) { return c->lanes[c->cur]; }
+// the image as draw `a` sees it, with the draw's depth-test plane (run_draw has checked that it is alive and large enough)
+Target draw_target(gs4d_ctx* c, const Framebuffer& F, const DrawArgs& a) {
+    Target t = F.target(a.out, a.clear);
+    if (const Buffer* Z = getbuf(c, a.zplane)) t.z = (const float*)Z->d;
+    return t;
+}
 
 struct StageTimer {
     gs4d_ctx* c; int slot; hipStream_t s;
@@ -398,7 +406,7 @@ int enqueue_raster(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, cons
     {
         StageTimer t(c, GS4D_T_COMPOSITE);      // the per-tile ranges and the compositing kernel
         HIPCHK(c, launch_tile_ranges(L.s, L.bin, L.pair_keys, L.pair_cap, ntiles));
-        HIPCHK(c, launch_composite(L.s, L.proj, L.pair_vals, L.bin.ranges, L.bin.total, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, F.target(a.out, a.clear), blend_src, blend_dst, a.draw_ord));
+        HIPCHK(c, launch_composite(L.s, L.proj, L.pair_vals, L.bin.ranges, L.bin.total, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, draw_target(c, F, a), blend_src, blend_dst, a.draw_ord));
     }
     return GS4D_OK;
 }
@@ -435,7 +443,7 @@ int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, s
 #endif
     {
         StageTimer t(c, GS4D_T_COMPOSITE);
-        HIPCHK(c, launch_composite_v2(L.s, L.proj, entries, L.tl.tstart, L.tl.tcnt, L.bin.total, L.host_total_dev, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, F.target(a.out, a.clear),
+        HIPCHK(c, launch_composite_v2(L.s, L.proj, entries, L.tl.tstart, L.tl.tcnt, L.bin.total, L.host_total_dev, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, draw_target(c, F, a),
                                       c->list_hint, a.keybits, recbits, L.tl.slabs, L.tl.bstat, L.tl.nb, L.tl.sstat, L.tl.rows, L.tl.staged ? L.tl.seq : 0u, 0xFFFFFFFFu, L.tl.scap, L.tl.bcap, L.tl.box, a.draw_ord));
     }
     { const uint32_t b = L.tl.staged ? L.tl.box : BOX_NONE; c->stat_composited_tiles = b == BOX_NONE ? ntiles : (uint64_t)std::min<uint32_t>((((b >> 16) & 255u) - (b & 255u) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_x) * std::min<uint32_t>(((b >> 24) - ((b >> 8) & 255u) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_y); }
@@ -528,7 +536,7 @@ int run_draw(gs4d_ctx* c, const DrawArgs& a, bool preprocess) {
         if (ob && !v2) { int rc = lane_access(c, *ob, false); if (rc) return rc; ob->rd_mask |= 1u << a.lane; }
         {
             StageTimer t(c, GS4D_T_PREPROCESS);
-            const PreOut po = { L.proj, (v2 && L.tl.staged) ? nullptr : L.trects, has_aux(a.out) };
+            const PreOut po = { L.proj, (v2 && L.tl.staged) ? nullptr : L.trects, has_aux(a.out) || a.zplane != 0 };
             L.trects_in_order = false;
             TileCount tc;
             if (v2 && L.tl.staged) { tc.stage_out = L.tl.blocks; tc.scap = L.tl.scap; tc.offs = L.tl.hist + L.tl.hist_cap; tc.abort_word = L.bin.total + TL_ABORT_WORD; tc.seq = L.tl.seq; }
@@ -581,6 +589,14 @@ int run_draw(gs4d_ctx* c, const DrawArgs& a, bool preprocess) {
             StageTimer t(c, GS4D_T_SORT);
             HIPCHK(c, radix_sort_pairs(L.s, L.depth_sort, (uint32_t*)K->d, (uint32_t*)I->d, npre, nullptr, fuse_bits, true, true));
         }
+    }
+    if (a.zplane) {
+        // the depth-test plane: read by the compositing kernel (first run and re-runs alike), so the lane waits for whoever wrote it, and a
+        // later write waits for this lane's tail event (the compositor runs after the draw's binning-done event)
+        Buffer* Z = getbuf(c, a.zplane);
+        if (!Z || Z->bytes < (size_t)c->W * c->H * 4) return fail(c, GS4D_E_INVALID, "draw: the depth-test plane holds fewer than width*height floats");
+        int rc = lane_access(c, *Z, false); if (rc) return rc;
+        Z->tail_mask |= 1u << a.lane;
     }
     size_t want = a.instances * 2 + 65536;
     if (want < c->stat_entries + c->stat_entries / 2) want = c->stat_entries + c->stat_entries / 2;
@@ -953,6 +969,7 @@ int gs4d_buffer_destroy(gs4d_ctx* c, gs4d_buf b) {
     if (B->ev_fill) (void)hipEventDestroy(B->ev_fill);
     *B = Buffer();
     for (auto& s : c->slots) if (s == b) s = 0;     // a deleted buffer is unbound
+    if (c->depth_plane == b) c->depth_plane = 0;    // ... the depth-test plane too: the test is off
     for (int i = 0; i < c->nlanes; ++i) if (c->lanes[i].kg_buf == b) c->lanes[i].kg_buf = 0;
     return GS4D_OK;
 }
@@ -1027,6 +1044,12 @@ int gs4d_set_blend(gs4d_ctx* c, int src, int dst) {
     auto known = [](int f) { return f == GS4D_ZERO || f == GS4D_ONE || (f >= GS4D_SRC_COLOR && f <= GS4D_ONE_MINUS_DST_COLOR) || (f >= GS4D_CONSTANT_COLOR && f <= GS4D_ONE_MINUS_CONSTANT_ALPHA); };
     if (!known(src) || !known(dst)) return fail(c, GS4D_E_INVALID, "set_blend: not a glBlendFunc factor of the reference's menu (GL_INVALID_ENUM)");
     c->blend_src = src; c->blend_dst = dst;              // like the GL's: state for the draws that follow
+    return GS4D_OK;
+}
+int gs4d_set_depth_test(gs4d_ctx* c, gs4d_buf plane) {
+    if (!c) return GS4D_E_INVALID;
+    if (plane != 0 && !getbuf(c, plane)) return fail(c, GS4D_E_INVALID, "set_depth_test: bad buffer name");
+    c->depth_plane = plane;                              // like glBlendFunc: state for the draws that follow (their size is checked when they are issued)
     return GS4D_OK;
 }
 int gs4d_clear(gs4d_ctx* c) {
@@ -1209,6 +1232,13 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     if (c->fbs[c->cur_fb].out != Outputs::Colour && !(c->blend_src == GS4D_SRC_ALPHA && c->blend_dst == GS4D_ONE_MINUS_SRC_ALPHA))
         return fail(c, GS4D_E_UNSUPPORTED, has_ids(c->fbs[c->cur_fb].out) ? "draw: ID outputs are defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only"
                                                                     : "draw: aux outputs are defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only");
+    // so is the depth test, against a plane of at least W x H floats (a resize can leave it too small)
+    if (c->depth_plane) {
+        const Buffer* Z = getbuf(c, c->depth_plane);
+        if (!Z || Z->bytes < (size_t)c->W * c->H * 4) return fail(c, GS4D_E_INVALID, "draw: the depth-test plane holds fewer than width*height floats");
+        if (!(c->blend_src == GS4D_SRC_ALPHA && c->blend_dst == GS4D_ONE_MINUS_SRC_ALPHA))
+            return fail(c, GS4D_E_UNSUPPORTED, "draw: the depth test is defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only");
+    }
     // the lane's scratch still belongs to its previous draw, and the image this draw blends onto must be complete: validate those
     // (not the other lanes' draws: their frames are still in flight and nothing here depends on them)
     int rc = resolve_lane(c, c->cur); if (rc) return rc;
@@ -1223,7 +1253,7 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     a.v2 = false;
     a.blend_src = c->blend_src; a.blend_dst = c->blend_dst;
     const bool over = a.blend_src == GS4D_SRC_ALPHA && a.blend_dst == GS4D_ONE_MINUS_SRC_ALPHA;       // any other function is applied in draw order: instance-ordered lists
-    a.out = c->fbs[c->cur_fb].out; a.draw_ord = c->fbs[c->cur_fb].draws;
+    a.out = c->fbs[c->cur_fb].out; a.draw_ord = c->fbs[c->cur_fb].draws; a.zplane = c->depth_plane;
     if (c->atomic_rank && c->path_pref != 1 && over) {
         Buffer* data = getbuf(c, a.data);
         bool ok = false;

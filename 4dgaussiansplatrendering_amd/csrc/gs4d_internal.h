@@ -14,7 +14,7 @@ constexpr int PROJ_FLOATS = 16;     // projected record: 64 B, one aligned segme
 
 // Projected record layout (float4 A,B,C,D), written by preprocess, gathered by binning/composite.
 //  A = cx, cy, a0x, a1x      B = a0y, a1y, r, g      C = b, alpha, rect0 (x0 | y0<<16), rect1 (x1 | y1<<16)   [pixel rect, inclusive]
-//  D = hx, hy, valid(1/0), depth   (depth = -z_view of the centre when the draw has aux outputs, else 0; gs4d_debug_read_projected hands them out in the order documented in gs4d.h)
+//  D = hx, hy, valid(1/0), depth   (depth = -z_view of the centre when the draw has aux outputs or a depth test, else 0; gs4d_debug_read_projected hands them out in the order documented in gs4d.h)
 // rect0 > rect1 in x (x0 = 1, x1 = 0) marks "no coverage".
 
 // ---- the outputs of a frame ----
@@ -32,9 +32,12 @@ constexpr bool has_aux(Outputs o) { return o >= Outputs::Aux; }
 constexpr bool has_ids(Outputs o) { return o >= Outputs::Ids; }
 // An image as a draw or a fill sees it.  tstate / epoch: the tile state (composite.hip): tstate[tile] == epoch <=> the tile's pixels are in
 // memory, else it is still the clear colour.  aux, ids: the planes of `out`, null above that level.  Made by Framebuffer::target (gs4d_api.hip).
+// z: a draw's depth-test plane (gs4d_set_depth_test: W x H floats, -z_view units; a fragment of depth d is blended only where d < z), or
+// null: no test.  Only the default blend function has one.
 struct Target {
     float4* fb; uint32_t* tstate; uint32_t epoch; float4 clear;
     Outputs out; float2* aux; uint32_t* ids;
+    const float* z = nullptr;
 };
 
 struct Uniforms {
@@ -278,7 +281,7 @@ hipError_t launch_soa_repack(hipStream_t st, const float* aos96, size_t n, float
 // plane 0 holds pos.xyz in every layout; the plane of sig[3] (what key generation reads beside it), or null when it is one of the constants
 inline const float4* soa_sig3(const float4* soa, size_t n, const SoaInfo& info) { return info.layout == SOA_STATIC3D ? nullptr : soa + (info.layout == SOA_SYM ? 3 : 5) * n; }
 // Each preprocess launch also writes the packed tile rectangle of every record (pack_trect).
-// aux: the draw's image has aux outputs — the projection stores each record's depth in the last float of its record (else 0).
+// aux: the draw's image has aux outputs or the draw has a depth test — the projection stores each record's depth in the last float of its record (else 0).
 struct PreOut { float4* proj; uint32_t* trects; bool aux = false; };
 hipError_t launch_preprocess_4d(hipStream_t st, const float4* soa, size_t soa_n /* records in the buffer: the plane stride */, const SoaInfo& info, size_t n, const Uniforms& u, int W, int H, PreOut out, const TileCount& tc);
 hipError_t launch_preprocess_3d(hipStream_t st, const float* verts72, size_t n, const Uniforms& u, int W, int H, PreOut out, const TileCount& tc);

@@ -201,6 +201,21 @@ GS4D_API int gs4d_read_ids(gs4d_ctx* ctx, int x, int y, int w, int h, uint32_t* 
  * gs4d_read_aux_device. */
 GS4D_API int gs4d_read_ids_device(gs4d_ctx* ctx, void* record, void* draw, void* weight, size_t bytes_per_plane);
 
+/* ---- depth test against the caller's depth plane: splats among opaque geometry (no reference counterpart) ----
+ * What a GL application gets with glEnable(GL_DEPTH_TEST), glDepthFunc(GL_LESS), glDepthMask(GL_FALSE) when it draws the splats after its
+ * opaque meshes.  The plane is a buffer of W*H float32 view depths Z[y*W + x], rows in gs4d_read_pixels' order (row 0 = bottom), in the unit
+ * of the aux outputs: -z_view, positive in front of the camera (a frame's D/O, or a mesh renderer's linear depth); +inf = no geometry.
+ * A fragment of record i at pixel p is blended only if d_i < Z[p] in float32 (GL_LESS: a NaN hides everything at its pixel), where d_i is
+ * the record depth the aux outputs use (slot 15 of gs4d_debug_read_projected; 0 for GS4D_MODE_2D).  A fragment that fails is treated like
+ * a discarded one: the colour and transmittance stay as they are, its aux weight is 0 and it never becomes the ID candidate.  The plane is
+ * read when the draw runs, in call order: a later gs4d_buffer_subdata does not change an earlier draw; writes through
+ * gs4d_buffer_device_ptr follow the gs4d_buffer_invalidate contract.  gs4d_draw_lines ignores the test. */
+/* plane != 0: the gs4d_draw_instanced / gs4d_draw_quads calls issued from now on test against it (draw state like gs4d_set_blend: it survives
+ * gs4d_clear); 0: no test (the default).  A name that is not a live buffer: GS4D_E_INVALID, the state stays as it was.  gs4d_buffer_destroy
+ * of the plane turns the test off.  A draw issued while the plane holds fewer than width*height*4 bytes (e.g. after gs4d_resize) returns
+ * GS4D_E_INVALID, and one with a blend function other than the default GS4D_E_UNSUPPORTED; neither draws anything. */
+GS4D_API int gs4d_set_depth_test(gs4d_ctx* ctx, gs4d_buf plane);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -213,8 +228,8 @@ GS4D_API int gs4d_get_stats(gs4d_ctx* ctx, uint64_t stats[8]);                  
                                                                                       [6] bits 0..15: frame lanes, bits 16..31: lanes whose stream shares a hardware queue with another lane's (0 unless the process has fewer free queues than lanes: such a context runs ~10 % slower), high 32 bits: draws that generated the depth keys of the preceding gs4d_keygen themselves (see gs4d_keygen), [7] low 32 bits: draws so far on the unordered tile-list path, high 32 bits: longest tile list of the last such draw */
 /* Projected records of the last draw, 16 floats per record in record order:
  * cx, cy, a0x, a0y, a1x, a1y, alpha, r, g, b, tile-rect (2 words, bit patterns), hx, hy, valid(1/0), depth.
- * depth (slot 15) is -z_view of the record's (time-conditioned) centre when the draw's frame has aux outputs (gs4d_set_aux_outputs) and the
- * record is valid, else 0; GS4D_MODE_2D records always have 0. */
+ * depth (slot 15) is -z_view of the record's (time-conditioned) centre when the draw's frame has aux outputs (gs4d_set_aux_outputs) or the
+ * draw has a depth test (gs4d_set_depth_test), and the record is valid, else 0; GS4D_MODE_2D records always have 0. */
 GS4D_API int gs4d_debug_read_projected(gs4d_ctx* ctx, float* out16, size_t nrecords);
 
 /* ---- host-side parameterisation (CPU code inside libgs4d.so; mirrors the reference's host math so that a caller

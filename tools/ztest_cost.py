@@ -1,9 +1,7 @@
-"""What ID outputs (gs4d_set_id_outputs) cost a frame: the C2 set (configs[1]: 10^6 static 3D splats) and configs[3]'s 10^6 4D
-splats at t = 25, 1080p, the reference's frame loop (clear -> keygen -> sort -> draw), with IDs off, aux outputs on, and IDs on (which
-implies aux), in rotating windows of one context each.  Prints one JSON line.  Usage: python tools/id_cost.py [steps] [rounds].
-Kernel split: run it under rocprofv3 --kernel-trace --stats, where the compositor instances of a mode are the k_composite / k_composite_v2
-instantiations whose output-set template argument is Outputs::Colour ((gs4d::Outputs)0), Outputs::Aux (1) or Outputs::Ids (2), and whose
-last one (ZTEST, the depth test: tools/ztest_cost.py) is false."""
+"""What the depth test (gs4d_set_depth_test) costs a frame: the C2 set (configs[1]: 10^6 static 3D splats) and configs[3]'s 10^6
+4D splats at t = 25, 1080p, the reference's frame loop (clear -> keygen -> sort -> draw), in four cases: test off, a plane of +inf (every
+fragment passes), a constant plane at the median record depth (hides about half the records), and that plane with ID outputs on.  Rotating
+windows of one context each, medians.  Prints one JSON line.  Usage: python tools/ztest_cost.py [steps] [rounds]."""
 import importlib
 import json
 import os
@@ -20,19 +18,7 @@ gs4d = importlib.import_module("4dgaussiansplatrendering_amd")
 import scenes  # noqa: E402
 
 W, H, N = 1920, 1080, 1_000_000
-
-
-MODES = ("off", "aux", "ids")
-
-
-def make(rec, mode):
-    ctx = gs4d.Context(W, H)
-    ctx.set_clear_color(gs4d.CLEAR_COLOR)
-    ctx.set_aux_outputs(mode == "aux")
-    ctx.set_id_outputs(mode == "ids")
-    n = rec.shape[0]
-    b = (ctx.buffer(rec), ctx.buffer(nbytes=4 * n), ctx.buffer(nbytes=4 * n))
-    return ctx, b
+MODES = ("off", "zinf", "zhalf", "zhalf_ids")
 
 
 def frame(ctx, b, n, t):
@@ -47,6 +33,31 @@ def frame(ctx, b, n, t):
     ctx.draw_instanced(n)
 
 
+def median_depth(rec, t):
+    """the median depth of the valid records (slot 15 of an aux frame) and the fraction of them in front of it"""
+    ctx = gs4d.Context(W, H)
+    ctx.set_aux_outputs(True)
+    n = rec.shape[0]
+    b = (ctx.buffer(rec), ctx.buffer(nbytes=4 * n), ctx.buffer(nbytes=4 * n))
+    frame(ctx, b, n, t)
+    pj = ctx.debug_projected(n)
+    ctx.close()
+    d = pj[pj[:, 14] != 0, 15]
+    z = np.float32(np.median(d))
+    return float(z), float((d < z).mean())
+
+
+def make(rec, mode, zmid):
+    ctx = gs4d.Context(W, H)
+    ctx.set_clear_color(gs4d.CLEAR_COLOR)
+    ctx.set_id_outputs(mode == "zhalf_ids")
+    n = rec.shape[0]
+    b = (ctx.buffer(rec), ctx.buffer(nbytes=4 * n), ctx.buffer(nbytes=4 * n))
+    if mode != "off":
+        ctx.set_depth_test(ctx.depth_plane(np.full((H, W), np.inf if mode == "zinf" else zmid, np.float32)))
+    return ctx, b
+
+
 def window(ctx, b, n, t, steps):
     ctx.finish()
     t0 = time.perf_counter()
@@ -58,7 +69,8 @@ def window(ctx, b, n, t, steps):
 
 def measure(rec, t, steps, rounds):
     n = rec.shape[0]
-    ctxs = {m: make(rec, m) for m in MODES}
+    zmid, shown = median_depth(rec, t)
+    ctxs = {m: make(rec, m, zmid) for m in MODES}
     for ctx, b in ctxs.values():
         for _ in range(60):
             frame(ctx, b, n, t)
@@ -72,9 +84,13 @@ def measure(rec, t, steps, rounds):
         ctx.close()
     med = {m: float(np.median(ms[m])) for m in MODES}
     off = med["off"]
-    return {"ms_off": off, "ms_aux": med["aux"], "ms_ids": med["ids"], "aux_cost_pct": 100.0 * (med["aux"] - off) / off,
-            "ids_cost_pct": 100.0 * (med["ids"] - off) / off, "ids_over_aux_pct": 100.0 * (med["ids"] - med["aux"]) / med["aux"],
-            "windows": ms}
+    out = {"z_half": zmid, "shown_fraction": shown}
+    for m in MODES:
+        out["ms_" + m] = med[m]
+        if m != "off":
+            out[m + "_cost_pct"] = 100.0 * (med[m] - off) / off
+    out["windows"] = ms
+    return out
 
 
 def main():
@@ -85,7 +101,7 @@ def main():
     del pos, q, scale, rgba
     pos4, q, scale, life, fade, vel, rgba = scenes.cube_params_4d(N)
     c4 = measure(gs4d.build_records_4d(pos4, q, scale, life, fade, vel, rgba), 25.0, steps, rounds)
-    print(json.dumps({"tool": "id_cost", "W": W, "H": H, "splats": N, "steps": steps, "rounds": rounds, "c2": c2, "c4_t25": c4}))
+    print(json.dumps({"tool": "ztest_cost", "W": W, "H": H, "splats": N, "steps": steps, "rounds": rounds, "c2": c2, "c4_t25": c4}))
 
 
 if __name__ == "__main__":
