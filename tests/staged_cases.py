@@ -72,13 +72,13 @@ def rects_from_device(proj16):
     return r0 & 0xFFFF, r0 >> 16, r1 & 0xFFFF, r1 >> 16
 
 
-def rects_from_checker(p):
-    """the same rectangle from the checker's projected records (oracle_lib.preprocess), in the float32 arithmetic of emit"""
+def rects_from_checker(p, w=W, h=H):
+    """the same rectangle from the checker's projected records (oracle_lib.preprocess), in the float32 arithmetic of emit (w, h: the image)"""
     f = np.float32
     cx, cy, hx, hy = (p[k].astype(f) for k in ("cx", "cy", "hx", "hy"))
     mx, my = f(0.01) + f(1e-5) * hx, f(0.01) + f(1e-5) * hy
-    x0, x1 = np.maximum(np.ceil(cx - hx - mx - f(0.5)), f(0.0)), np.minimum(np.floor(cx + hx + mx - f(0.5)), f(W - 1))
-    y0, y1 = np.maximum(np.ceil(cy - hy - my - f(0.5)), f(0.0)), np.minimum(np.floor(cy + hy + my - f(0.5)), f(H - 1))
+    x0, x1 = np.maximum(np.ceil(cx - hx - mx - f(0.5)), f(0.0)), np.minimum(np.floor(cx + hx + mx - f(0.5)), f(w - 1))
+    y0, y1 = np.maximum(np.ceil(cy - hy - my - f(0.5)), f(0.0)), np.minimum(np.floor(cy + hy + my - f(0.5)), f(h - 1))
     ok = (p["valid"] != 0) & (x0 <= x1) & (y0 <= y1)
     return tuple(np.where(ok, v, e).astype(np.int64) for v, e in ((x0, 1), (y0, 0), (x1, 0), (y1, 0)))
 
@@ -86,8 +86,9 @@ def rects_from_checker(p):
 class Load:
     """entries per segment, per bucket and per tile of one frame, its longest list and the box of blocks that hold entries"""
 
-    def __init__(self, rects):
+    def __init__(self, rects, w=W, h=H):
         x0, y0, x1, y1 = rects
+        TX, TY = (w + TILE - 1) // TILE, (h + TILE - 1) // TILE             # (the module's own image unless told otherwise)
         n = x0.size
         rows, seg = plan(n)
         ok = (x0 <= x1) & (y0 <= y1)
