@@ -6,7 +6,7 @@
 // touches, in instance order; a stable radix sort on the tile id (sort.hip) then yields, per tile, the entries in
 // instance order — the order the ROP would have blended them in.
 //
-// Counts stay on the device: the total number of entries is written to total[0] (and an overflow flag to total[1] when it
+// Counts stay on the device: the total number of entries is written to total[TOT_ENTRIES] (and VF_CAPACITY to total[TOT_FLAGS] when it
 // exceeds the preallocated capacity); later kernels read it there, so a frame needs no host synchronisation.
 // Counting, scanning and emitting are ONE launch (chained scan over workgroup totals); the per-record tile rectangles are read
 // from a compact 4-byte array (pack_trect, gs4d_internal.h) instead of the 64-byte projected records — gathered through the sort index,
@@ -154,11 +154,11 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(const uint32_t* __rest
             s_prefix = prefix;
             if (blk == gridDim.x - 1) {                     // the last workgroup knows the grand total
                 const unsigned long long g = prefix + run;
-                total[0] = g > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)g;
-                total[1] = g > (unsigned long long)cap ? 1u : 0u;
-                total[2] = (uint32_t)g; total[3] = (uint32_t)(g >> 32);
+                total[TOT_ENTRIES] = g > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)g;
+                total[TOT_FLAGS] = g > (unsigned long long)cap ? VF_CAPACITY : 0u;
+                total[TOT_COUNT_LO] = (uint32_t)g; total[TOT_COUNT_HI] = (uint32_t)(g >> 32);
                 // copy for the host (pinned, mapped): read after the draw's event, no copy launch
-                total_host[0] = total[0]; total_host[1] = total[1]; total_host[2] = total[2]; total_host[3] = total[3];
+                total_host[HT_ENTRIES] = total[TOT_ENTRIES]; total_host[HT_FLAGS] = total[TOT_FLAGS]; total_host[HT_COUNT_LO] = total[TOT_COUNT_LO]; total_host[HT_COUNT_HI] = total[TOT_COUNT_HI];
             }
         }
     }
@@ -189,8 +189,8 @@ __global__ __launch_bounds__(BIN_THREADS) void k_bin_emit(const uint32_t* __rest
 
 // ranges[2t], ranges[2t+1] = first and one-past-last entry of tile t in the sorted tile lists.  Four entries per thread.
 __global__ __launch_bounds__(256) void k_tile_ranges(const uint32_t* __restrict__ pk, const uint32_t* __restrict__ total, uint32_t ntiles, uint32_t* __restrict__ ranges) {
-    if (total[1]) return;
-    const uint32_t m = total[0];
+    if (total[TOT_FLAGS]) return;                           // any flag (only VF_CAPACITY occurs on this path)
+    const uint32_t m = total[TOT_ENTRIES];
     const uint32_t j0 = (blockIdx.x * 256u + threadIdx.x) * 4u;
     if (j0 >= m) return;
     uint32_t k[4];
@@ -215,8 +215,8 @@ hipError_t bin_scratch_reserve(hipStream_t st, BinScratch& b, size_t ninst, size
     if (nb < 1) nb = 1;
     if (!b.total) {
         if (const char* e0 = getenv("GS4D_TEST_EPOCH0")) b.epoch = ((uint32_t)strtoul(e0, nullptr, 0) << 4) | 0xFu;     // test hook: 22-bit wrap within a short test
-        if ((e = hipMalloc(&b.total, 64)) != hipSuccess) return e;
-        if ((e = hipMemsetAsync(b.total, 0, 64, st)) != hipSuccess) return e;
+        if ((e = hipMalloc(&b.total, VERDICT_WORDS * 4)) != hipSuccess) return e;
+        if ((e = hipMemsetAsync(b.total, 0, VERDICT_WORDS * 4, st)) != hipSuccess) return e;
         b.ticket_base = 0;
     }
     if (b.block_cap < nb || b.tiles_cap < ntiles) {
@@ -253,7 +253,7 @@ hipError_t launch_binning(hipStream_t st, BinScratch& b, const uint32_t* trects,
         b.epoch = 1;
     }
     const uint32_t nb = (uint32_t)((ninst + BIN_THREADS * BIN_ITEMS - 1) / (BIN_THREADS * BIN_ITEMS));
-    k_bin_emit<<<dim3(nb), dim3(BIN_THREADS), 0, st>>>(trects, trects_in_order ? 1 : 0, proj, order, order_copy, (uint32_t)ninst, (uint32_t)nrecords, b.status, b.status + b.block_cap, b.total, (uint32_t)pair_cap, (uint32_t)tiles_x, pair_keys, pair_vals, err, ghist, passes, total_host, b.epoch, b.total + 8, b.ticket_base, dbg, (uint32_t)shard_rank, (uint32_t)shard_world);
+    k_bin_emit<<<dim3(nb), dim3(BIN_THREADS), 0, st>>>(trects, trects_in_order ? 1 : 0, proj, order, order_copy, (uint32_t)ninst, (uint32_t)nrecords, b.status, b.status + b.block_cap, b.total, (uint32_t)pair_cap, (uint32_t)tiles_x, pair_keys, pair_vals, err, ghist, passes, total_host, b.epoch, b.total + TOT_TICKET, b.ticket_base, dbg, (uint32_t)shard_rank, (uint32_t)shard_world);
     b.ticket_base += nb;
     return hipGetLastError();
 }

@@ -115,7 +115,7 @@ __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ pro
     __shared__ float4 sh_stage[stage_words(OUT, ZTEST) / 4];
     __shared__ uint32_t pmask[64 * 2];
     const Stage<OUT, ZTEST> stage(sh_stage);
-    if (total[1]) return;                                   // tile lists overflowed: nothing was emitted, the host re-runs
+    if (total[TOT_FLAGS]) return;                           // any flag (VF_CAPACITY on this path) — tile lists overflowed: nothing was emitted, the host re-runs
     uint32_t tile;
     if (!composite_tile(blockIdx.x, tiles_x, (H + TILE - 1) / TILE, tile)) return;        // uniform: padding of the XCD-aware grid
     const uint32_t lane = threadIdx.x;

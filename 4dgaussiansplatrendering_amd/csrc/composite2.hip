@@ -103,11 +103,11 @@ __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ 
     // Everything the tile needs before it can ask for its list is requested HERE, in one go — the verdict word, the tile's table row, its state
     // word: three independent loads, one round trip.  (Issued one behind the other's branch they were three round trips: per-tile stamps of a
     // TUNING build showed 3.9 us between a workgroup's start and its list being in order for lists of <= 64 entries — tools/v2_timeline.py.)
-    const uint32_t verdict = stage_seq ? total[TL_ABORT_WORD] : total[1];
+    const uint32_t verdict = stage_seq ? total[TOT_ABORT] : total[TOT_FLAGS];
     uint32_t my_start = 0u, my_cnt = 0u;                    // lane s: sub-list s of this tile (one load for the whole table row)
     if (real && lane < slabs) { my_start = tstart[(size_t)tile * slabs + lane]; my_cnt = tcnt[(size_t)tile * slabs + lane]; }
     const uint32_t tstate_word = real ? tstate[tile] : 0u;
-    const bool aborted = stage_seq ? verdict == stage_seq : verdict != 0u;
+    const bool aborted = stage_seq ? verdict == stage_seq : verdict != 0u;      // exact: ANY flag (VF_CAPACITY, VF_LIST)
     if (blockIdx.x == 0u) {
         unsigned long long sum = 0ull; uint32_t mrun = 0u, mbucket = 0u, mlist = 0u, mseg = 0u, used = BOX_EMPTY;
         if (bstat) for (uint32_t b = lane; b < nb; b += 64u) { const uint4 v = bstat[b]; sum += v.x; mrun = max(mrun, v.y); mbucket = max(mbucket, v.x); mlist = max(mlist, v.z); used = box_join(used, v.w); }
@@ -119,16 +119,16 @@ __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ 
             used = box_join(used, (uint32_t)__shfl_xor((int)used, off, 64));
         }
         if (lane == 0u) {
-            total_host[6] = mrun; total_host[7] = mbucket; total_host[8] = mseg;
-            total_host[9] = stage_seq ? used : BOX_NONE;         // the blocks of tiles that hold entries (staged draws: k_bucket_tiles_staged knows; BOX_EMPTY: none)
+            total_host[HT_LONGEST_RUN] = mrun; total_host[HT_FULLEST_BUCKET] = mbucket; total_host[HT_FULLEST_SEG] = mseg;
+            total_host[HT_USED_BOX] = stage_seq ? used : BOX_NONE;         // the blocks of tiles that hold entries (staged draws: k_bucket_tiles_staged knows; BOX_EMPTY: none)
             if (stage_seq) {
-                // flags: 4 = a segment, a run or a bucket did not fit what the host guessed, or an entry lies outside the launch box (re-run exactly), 2 = a list longer than the compositor was launched for.
+                // flags: VF_STAGED_MISS = a segment, a run or a bucket did not fit what the host guessed, or an entry lies outside the launch box (re-run exactly), VF_LIST = a list longer than the compositor was launched for.
                 // (A segment that overflowed wrote no entries: the bucket statistics then count entries that are not there, and the sum is still the true total.)
-                const bool in_box = used == BOX_EMPTY || (box_holds(box_blocks, used & 255u, (used >> 8) & 255u) && box_holds(box_blocks, (used >> 16) & 255u, used >> 24));
+                const bool in_box = used == BOX_EMPTY || (box_holds(box_blocks, box_x0(used), box_y0(used)) && box_holds(box_blocks, box_x1(used), box_y1(used)));
                 const bool guess_ok = mrun <= rcap && mbucket <= bcap && mseg <= scap && in_box;
-                const uint32_t fl = (guess_ok ? 0u : 4u) | ((aborted && guess_ok) ? 2u : 0u);
-                total_host[0] = sum > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sum; total_host[2] = (uint32_t)sum; total_host[3] = (uint32_t)(sum >> 32); total_host[5] = mlist; total_host[1] = fl;
-            } else { total_host[0] = total[0]; total_host[2] = total[2]; total_host[3] = total[3]; total_host[5] = total[4]; total_host[1] = total[1]; }
+                const uint32_t fl = (guess_ok ? 0u : VF_STAGED_MISS) | ((aborted && guess_ok) ? VF_LIST : 0u);
+                total_host[HT_ENTRIES] = sum > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)sum; total_host[HT_COUNT_LO] = (uint32_t)sum; total_host[HT_COUNT_HI] = (uint32_t)(sum >> 32); total_host[HT_LONGEST_LIST] = mlist; total_host[HT_FLAGS] = fl;
+            } else { total_host[HT_ENTRIES] = total[TOT_ENTRIES]; total_host[HT_COUNT_LO] = total[TOT_COUNT_LO]; total_host[HT_COUNT_HI] = total[TOT_COUNT_HI]; total_host[HT_LONGEST_LIST] = total[TOT_LONGEST_LIST]; total_host[HT_FLAGS] = total[TOT_FLAGS]; }
         }
     }
     if (aborted || !real) return;                           // aborted draw (capacity or list length): the host re-runs it
@@ -196,13 +196,13 @@ __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ 
 #endif
 }
 
-hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* entries, const uint32_t* tstart, const uint32_t* tcnt, const uint32_t* total, uint32_t* total_host, int tiles_x, int tiles_y, int W, int H,
-                               int premult_c, const Target& t, uint32_t hint, int keybits, int recbits, uint32_t slabs,
-                               const uint4* bstat, uint32_t nb, const uint32_t* sstat, uint32_t rows, uint32_t stage_seq, uint32_t rcap, uint32_t scap, uint32_t bcap, uint32_t box_blocks, uint32_t draw_ord) {
+hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* entries, const TileLists& tl, const uint32_t* total, uint32_t* total_host, int tiles_x, int tiles_y, int W, int H,
+                               int premult_c, const Target& t, uint32_t hint, int keybits, int recbits, uint32_t draw_ord) {
+    const uint32_t stage_seq = tl.staged ? tl.seq : 0u, rcap = 0xFFFFFFFFu;      // != 0: a staged draw; the longest run is no capacity of anything any more (a statistic only)
     if (hint > V2_MAX_LIST) return hipErrorInvalidValue;
     const int per = (int)(v2_list_capacity(hint) / 64u);
     // staged draws: only the box of tiles the list kernel has checked every entry to lie in (TileLists::box); the first workgroup reports, so there is always one
-    TileBox box = tile_box(stage_seq ? box_blocks : BOX_NONE, tiles_x, tiles_y);
+    TileBox box = tile_box(stage_seq ? tl.box : BOX_NONE, tiles_x, tiles_y);
     if (box.w == 0u || box.h == 0u) box = TileBox{ 0u, 0u, 1u, 1u };
     const dim3 grid(composite_grid((int)box.w, (int)box.h));
     int kp = (keybits + WS_DIGIT_BITS - 1) / WS_DIGIT_BITS, rp = (recbits + WS_DIGIT_BITS - 1) / WS_DIGIT_BITS;
@@ -219,7 +219,7 @@ hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* 
     if (stamp_now && (hipMalloc(&stamps, (size_t)grid.x * 48) != hipSuccess || hipMemsetAsync(stamps, 0, (size_t)grid.x * 48, st) != hipSuccess)) stamps = nullptr;
 #endif
     for_outputs(premult_c != 0, t.out, t.z != nullptr, [&](auto pc, auto out, auto zt) {
-#define GS4D_V2(P) k_composite_v2<pc(), P, out(), zt()><<<grid, dim3(64), 0, st>>>(proj, entries, tstart, tcnt, total, total_host, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, kp, rp, slabs, bstat, nb, sstat, rows, stage_seq, rcap, scap, bcap, box, box_blocks, stamps, t.aux, t.ids, draw_ord, t.z)
+#define GS4D_V2(P) k_composite_v2<pc(), P, out(), zt()><<<grid, dim3(64), 0, st>>>(proj, entries, tl.tstart, tl.tcnt, total, total_host, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, kp, rp, tl.slabs, tl.bstat, tl.nb, tl.sstat, tl.rows, stage_seq, rcap, tl.scap, tl.bcap, box, tl.box, stamps, t.aux, t.ids, draw_ord, t.z)
         switch (per) {
         case 1: GS4D_V2(1); break;
         case 2: GS4D_V2(2); break;

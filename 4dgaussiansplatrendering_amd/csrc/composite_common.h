@@ -42,8 +42,8 @@ static_assert(TBLOCK == BOX_BLOCK, "a launch box is whole blocks of the composit
 // box: TileLists::box (blocks, inclusive; BOX_NONE = everything), clipped to the image
 __host__ __device__ __forceinline__ TileBox tile_box(uint32_t box, int tiles_x, int tiles_y) {
     if (box == BOX_NONE) return TileBox{ 0u, 0u, (uint32_t)tiles_x, (uint32_t)tiles_y };
-    const uint32_t x0 = (box & 255u) * BOX_BLOCK, y0 = ((box >> 8) & 255u) * BOX_BLOCK;
-    const uint32_t x1 = (((box >> 16) & 255u) + 1u) * BOX_BLOCK, y1 = ((box >> 24) + 1u) * BOX_BLOCK;
+    const uint32_t x0 = box_x0(box) * BOX_BLOCK, y0 = box_y0(box) * BOX_BLOCK;
+    const uint32_t x1 = (box_x1(box) + 1u) * BOX_BLOCK, y1 = (box_y1(box) + 1u) * BOX_BLOCK;
     const uint32_t cx1 = x1 < (uint32_t)tiles_x ? x1 : (uint32_t)tiles_x, cy1 = y1 < (uint32_t)tiles_y ? y1 : (uint32_t)tiles_y;
     return TileBox{ x0, y0, cx1 > x0 ? cx1 - x0 : 0u, cy1 > y0 ? cy1 - y0 : 0u };
 }

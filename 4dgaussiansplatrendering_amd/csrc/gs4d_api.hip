@@ -126,8 +126,8 @@ struct Lane {
     SortScratch depth_sort, pair_sort;
     BinScratch bin;
     float* line_verts = nullptr; size_t line_cap = 0;   // device copy of the vertices of the latest gs4d_draw_lines (the lane's stream orders its reuse)
-    uint32_t* host_total = nullptr;     // pinned + mapped: [0..3] the binning total of the last draw, [4] the error word kernels raise
-    uint32_t* host_total_dev = nullptr; // the same memory as the device sees it
+    uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
+    uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
     gs4d_buf kg_buf = 0; uint64_t kg_ver = 0; size_t kg_n = 0;   // key buffer whose digit histograms k_keygen left for the next sort
     gs4d_buf kg_idx = 0, kg_data = 0; uint64_t kg_idx_ver = 0, kg_data_ver = 0; KeySrc kg_ks; int kg_bits = 32; uint32_t kg_span = 0xFFFFFFFFu;   // ... the identity index it wrote beside them, and what the keys were computed from
     // Storage renaming for per-frame key / index buffers.  A buffer object is a NAME; its device storage is the library's.  gs4d_keygen
@@ -248,7 +248,7 @@ int sync_all(gs4d_ctx* c) {
     return GS4D_OK;
 }
 
-bool device_error(gs4d_ctx* c) { for (int i = 0; i < c->nlanes; ++i) if (c->lanes[i].host_total[4]) return true; return false; }
+bool device_error(gs4d_ctx* c) { for (int i = 0; i < c->nlanes; ++i) if (c->lanes[i].host_total[HT_ERROR]) return true; return false; }
 
 // The current frame is complete (it has a draw in it) and a new one starts: move to the next lane.
 int next_frame_if_drawn(gs4d_ctx* c) {
@@ -394,13 +394,13 @@ int enqueue_raster(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, cons
         hipError_t he = hipSuccess;
         uint32_t* ph = sort_hist_slot(L.s, L.pair_sort, L.pair_cap, &he);      // the emit kernel also counts the tile-id digits
         if (!ph) return hipfail(c, he, "sort_hist_slot");
-        HIPCHK(c, launch_binning(L.s, L.bin, L.trects, L.trects_in_order, L.proj, order, order_copy, ninst, nrecords, c->tiles_x, c->tiles_y, L.pair_keys, L.pair_vals, L.pair_cap, L.host_total_dev + 4,
+        HIPCHK(c, launch_binning(L.s, L.bin, L.trects, L.trects_in_order, L.proj, order, order_copy, ninst, nrecords, c->tiles_x, c->tiles_y, L.pair_keys, L.pair_vals, L.pair_cap, L.err_word(),
                                  ph, tile_passes | (tile_rb << 8), L.host_total_dev, a.shard_rank, a.shard_world));
     }
     HIPCHK(c, hipEventRecord(L.ev_emit, L.s));     // the last binning workgroup wrote the total straight into pinned host memory
     {
         StageTimer t(c, GS4D_T_PAIRSORT);
-        HIPCHK(c, radix_sort_pairs(L.s, L.pair_sort, L.pair_keys, L.pair_vals, L.pair_cap, L.bin.total, tile_bits, true));
+        HIPCHK(c, radix_sort_pairs(L.s, L.pair_sort, L.pair_keys, L.pair_vals, L.pair_cap, L.bin.total + TOT_ENTRIES, tile_bits, true));
     }
     c->stat_tile_passes = (uint64_t)tile_passes;
     {
@@ -443,10 +443,10 @@ int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, s
 #endif
     {
         StageTimer t(c, GS4D_T_COMPOSITE);
-        HIPCHK(c, launch_composite_v2(L.s, L.proj, entries, L.tl.tstart, L.tl.tcnt, L.bin.total, L.host_total_dev, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, draw_target(c, F, a),
-                                      c->list_hint, a.keybits, recbits, L.tl.slabs, L.tl.bstat, L.tl.nb, L.tl.sstat, L.tl.rows, L.tl.staged ? L.tl.seq : 0u, 0xFFFFFFFFu, L.tl.scap, L.tl.bcap, L.tl.box, a.draw_ord));
+        HIPCHK(c, launch_composite_v2(L.s, L.proj, entries, L.tl, L.bin.total, L.host_total_dev, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, draw_target(c, F, a), c->list_hint, a.keybits, recbits, a.draw_ord));
     }
-    { const uint32_t b = L.tl.staged ? L.tl.box : BOX_NONE; c->stat_composited_tiles = b == BOX_NONE ? ntiles : (uint64_t)std::min<uint32_t>((((b >> 16) & 255u) - (b & 255u) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_x) * std::min<uint32_t>(((b >> 24) - ((b >> 8) & 255u) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_y); }
+    // (the box's width and height clipped to the image's: more tiles than tile_box() launches when a box starts away from the left / top edge and overhangs the far one)
+    { const uint32_t b = L.tl.staged ? L.tl.box : BOX_NONE; c->stat_composited_tiles = b == BOX_NONE ? ntiles : (uint64_t)std::min<uint32_t>((box_x1(b) - box_x0(b) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_x) * std::min<uint32_t>((box_y1(b) - box_y0(b) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_y); }
     HIPCHK(c, hipEventRecord(L.ev_emit, L.s));         // totals, flags and the longest list are in pinned host memory behind this event (the compositor's first workgroup wrote them)
     return GS4D_OK;
 }
@@ -501,9 +501,8 @@ int run_draw(gs4d_ctx* c, const DrawArgs& a, bool preprocess) {
                 // the compositor's launch box: where the last staged draw had entries, stage_box_margin blocks (of 4 x 4 tiles) wider on every side
                 const uint32_t nbx = (uint32_t)(c->tiles_x + BOX_BLOCK - 1) / BOX_BLOCK, nby = (uint32_t)(c->tiles_y + BOX_BLOCK - 1) / BOX_BLOCK;
                 if (c->stage_box_enable && c->stage_box != BOX_NONE && c->stage_box != BOX_EMPTY && nbx <= 256u && nby <= 256u) {
-                    const uint32_t b = c->stage_box, x0 = b & 255u, y0 = (b >> 8) & 255u, x1 = (b >> 16) & 255u, y1 = b >> 24;
-                    const uint32_t m = c->stage_box_margin;
-                    L.tl.box = box_pack(x0 > m ? x0 - m : 0u, y0 > m ? y0 - m : 0u, std::min(x1 + m, nbx - 1u), std::min(y1 + m, nby - 1u));
+                    const uint32_t b = c->stage_box, m = c->stage_box_margin;
+                    L.tl.box = box_pack(box_x0(b) > m ? box_x0(b) - m : 0u, box_y0(b) > m ? box_y0(b) - m : 0u, std::min(box_x1(b) + m, nbx - 1u), std::min(box_y1(b) + m, nby - 1u));
                 }
             }
         }
@@ -539,7 +538,7 @@ int run_draw(gs4d_ctx* c, const DrawArgs& a, bool preprocess) {
             const PreOut po = { L.proj, (v2 && L.tl.staged) ? nullptr : L.trects, has_aux(a.out) || a.zplane != 0 };
             L.trects_in_order = false;
             TileCount tc;
-            if (v2 && L.tl.staged) { tc.stage_out = L.tl.blocks; tc.scap = L.tl.scap; tc.offs = L.tl.hist + L.tl.hist_cap; tc.abort_word = L.bin.total + TL_ABORT_WORD; tc.seq = L.tl.seq; }
+            if (v2 && L.tl.staged) { tc.stage_out = L.tl.blocks; tc.scap = L.tl.scap; tc.offs = L.tl.hist + L.tl.hist_cap; tc.abort_word = L.bin.total + TOT_ABORT; tc.seq = L.tl.seq; }
             if (v2) { tc.sstat = L.tl.sstat; tc.hist = L.tl.hist; tc.skey = L.tl.skey; tc.nb = L.tl.nb; tc.seg = L.tl.seg; tc.rows = L.tl.rows; tc.tiles_x = c->tiles_x; tc.shard_rank = a.shard_rank; tc.shard_world = a.shard_world; tc.ks = a.ks; }
             if (a.fuse) {
                 tc.ks = a.ks;
@@ -548,7 +547,7 @@ int run_draw(gs4d_ctx* c, const DrawArgs& a, bool preprocess) {
                 hipError_t he = hipSuccess;
                 uint32_t* kh = sort_hist_slot(L.s, L.depth_sort, npre, &he);
                 if (!kh) return hipfail(c, he, "sort_hist_slot");
-                tc.keys_out = (float*)K->d; tc.idx_out = nullptr /* the depth sort below makes the identity index up */; (void)I; tc.ghist = kh; tc.span = a.fuse_span; tc.err = L.host_total_dev + 4;
+                tc.keys_out = (float*)K->d; tc.idx_out = nullptr /* the depth sort below makes the identity index up */; (void)I; tc.ghist = kh; tc.span = a.fuse_span; tc.err = L.err_word();
                 L.depth_sort.hist_bias = a.ks.bias;
                 tc.hist_rb = L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, npre, fuse_bits);
             }
@@ -577,7 +576,7 @@ int run_draw(gs4d_ctx* c, const DrawArgs& a, bool preprocess) {
             float view[16] = { 0 }; view[2] = a.ks.vr0; view[6] = a.ks.vr1; view[10] = a.ks.vr2; view[14] = a.ks.vr3;
             L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, npre, a.keybits);
             HIPCHK(c, launch_keygen(L.s, data->soa, soa_sig3(data->soa, data->soa_n, data->soa_info), data->soa_info, npre, a.ks.t, cam, view, a.ks.mode == KEYSRC_VIEWZ ? GS4D_KEY_VIEW_Z : GS4D_KEY_REF_INV_EUCLID,
-                                    (float*)L.regen_keys, L.order_copy, kh, L.depth_sort.hist_rb, a.ks.bias, 0xFFFFFFFFu, L.host_total_dev + 4));
+                                    (float*)L.regen_keys, L.order_copy, kh, L.depth_sort.hist_rb, a.ks.bias, 0xFFFFFFFFu, L.err_word()));
             L.depth_sort.hist_bias = a.ks.bias;
             HIPCHK(c, radix_sort_pairs(L.s, L.depth_sort, L.regen_keys, L.order_copy, npre, nullptr, a.keybits, true));
         }
@@ -620,6 +619,10 @@ int run_draw(gs4d_ctx* c, const DrawArgs& a, bool preprocess) {
     return enqueue_raster(c, L, F, a, order, order_copy, a.instances, npre, premult);
 }
 
+// What a draw's kernels left in the lane's host verdict words (HT_*, gs4d_internal.h), decoded once behind the lane's event.
+struct Verdict { uint64_t entries; uint32_t flags, longest_list, longest_run, fullest_bucket, fullest_seg, used_box; };
+Verdict read_verdict(const uint32_t* ht) { return Verdict{ (uint64_t)ht[HT_COUNT_LO] | ((uint64_t)ht[HT_COUNT_HI] << 32), ht[HT_FLAGS], ht[HT_LONGEST_LIST], ht[HT_LONGEST_RUN], ht[HT_FULLEST_BUCKET], ht[HT_FULLEST_SEG], ht[HT_USED_BOX] }; }
+
 // A draw's tile-list capacity is validated after the fact: the entry count comes back through pinned memory behind an event.
 // Called by every entry point that could observe the draw's result.  On overflow the raster stages are re-run with exact capacity
 // (the projected records and the copy of the sort index are still valid).
@@ -630,38 +633,35 @@ int resolve_lane(gs4d_ctx* c, int li) {
         L.pending = false;
         const bool discarded = L.discarded;             // the image was cleared before anybody looked: learn from the draw, do not repeat it
         L.discarded = false;
-        if (L.host_total[4]) return fail(c, GS4D_E_DEVICE, DEVICE_CHECK_MSG);
-        const uint64_t total = (uint64_t)L.host_total[2] | ((uint64_t)L.host_total[3] << 32);
-        const uint32_t flags = L.host_total[1];
-        if (L.pending_args.v2 && !(flags & 1u)) {
+        if (L.host_total[HT_ERROR]) return fail(c, GS4D_E_DEVICE, DEVICE_CHECK_MSG);
+        const Verdict v = read_verdict(L.host_total);
+        if (L.pending_args.v2 && !(v.flags & VF_CAPACITY)) {
             // longest (bucket, segment) run and fullest bucket of this draw: what sizes the staged blocks of the draws that follow
-            c->stage_max_run = L.host_total[6]; c->stage_max_bucket = L.host_total[7]; c->stage_max_seg = L.host_total[8]; c->stage_geom = L.pending_args.stage_geom; c->stage_known = true;
-            c->stage_box = L.host_total[9];
-            const uint32_t u = L.host_total[9];
-            if ((flags & 4u) && L.tl.box != BOX_NONE && u != BOX_NONE && u != BOX_EMPTY && !(box_holds(L.tl.box, u & 255u, (u >> 8) & 255u) && box_holds(L.tl.box, (u >> 16) & 255u, u >> 24)))
+            c->stage_max_run = v.longest_run; c->stage_max_bucket = v.fullest_bucket; c->stage_max_seg = v.fullest_seg; c->stage_geom = L.pending_args.stage_geom; c->stage_known = true;
+            c->stage_box = v.used_box;
+            if ((v.flags & VF_STAGED_MISS) && L.tl.box != BOX_NONE && v.used_box != BOX_NONE && v.used_box != BOX_EMPTY && !box_within(L.tl.box, v.used_box))
                 c->stage_box_margin = std::min(16u, c->stage_box_margin * 2u);      // the picture moves faster than the margin allowed
         }
         if (L.pending_args.v2) {
-            c->stat_longest = L.host_total[5];
+            c->stat_longest = v.longest_list;
             // the compositor's occupancy falls with the list capacity it is launched for: give capacity back when the lists stay short
-            const uint32_t fit = v2_list_capacity(std::min<uint32_t>(V2_MAX_LIST, L.host_total[5] + L.host_total[5] / 8u));
-            if (!flags && fit < c->list_hint) { if (++c->shrink_votes >= 8) { c->list_hint = fit; c->shrink_votes = 0; } } else c->shrink_votes = 0;
+            const uint32_t fit = v2_list_capacity(std::min<uint32_t>(V2_MAX_LIST, v.longest_list + v.longest_list / 8u));
+            if (!v.flags && fit < c->list_hint) { if (++c->shrink_votes >= 8) { c->list_hint = fit; c->shrink_votes = 0; } } else c->shrink_votes = 0;
         }
-        if (!flags) { c->stat_entries = total; break; }
-        if (total >= 0xFFFFFFF0ull) { if (discarded) break; return fail(c, GS4D_E_UNSUPPORTED, "draw: more than 2^32 tile-list entries (splats cover too many tiles)"); }
+        if (!v.flags) { c->stat_entries = v.entries; break; }
+        if (v.entries >= 0xFFFFFFF0ull) { if (discarded) break; return fail(c, GS4D_E_UNSUPPORTED, "draw: more than 2^32 tile-list entries (splats cover too many tiles)"); }
         if (discarded) c->stat_aborted_discarded++; else c->stat_reruns++;
-        c->stat_entries = total;
+        c->stat_entries = v.entries;
         const bool was_v2 = L.pending_args.v2;     // an unordered draw kept no copy of its sort index: whatever path the re-run takes, it starts from the projection
-        if (L.pending_args.v2 && (flags & 4u)) { L.pending_args.exact_lists = true; c->stat_staged_misses++; }      // a run or a bucket did not fit the guess: exact lists this time
-        if (L.pending_args.v2 && (flags & 2u)) {
+        if (L.pending_args.v2 && (v.flags & VF_STAGED_MISS)) { L.pending_args.exact_lists = true; c->stat_staged_misses++; }      // a run or a bucket did not fit the guess: exact lists this time
+        if (L.pending_args.v2 && (v.flags & VF_LIST)) {
             // A (sub-)list longer than the compositing wave was launched for.  What it can hold is a launch parameter (64 entries per lane
             // register: v2_list_capacity) that costs registers and LDS.  Up to V2_MAX_LIST entries: a capacity that fits.  Longer: this is a
             // scene for the instance-ordered path (the re-run regenerates the order the draw was issued with: DrawArgs::regen_order).
-            const uint32_t longest = L.host_total[5];
-            if (longest <= V2_MAX_LIST) c->list_hint = std::max(c->list_hint, v2_list_capacity(longest + longest / 8u));
+            if (v.longest_list <= V2_MAX_LIST) c->list_hint = std::max(c->list_hint, v2_list_capacity(v.longest_list + v.longest_list / 8u));
             else { c->long_lists = true; c->ordered_draws = 0; L.pending_args.v2 = false; L.pending_args.regen_order = true; }
         }
-        int rc = ensure_pairs(c, L, (size_t)(total + total / 8 + 1024));
+        int rc = ensure_pairs(c, L, (size_t)(v.entries + v.entries / 8 + 1024));
         if (rc) return rc;
         if (discarded) break;                           // the lane's next draw starts with what this one found out
         // the re-run goes to the draw's own lane: make it current while its kernels are queued
@@ -717,7 +717,7 @@ int flush_order(gs4d_ctx* c) {
         if (!kh) return hipfail(c, he, "sort_hist_slot");
         StageTimer tm(c, GS4D_T_KEYGEN);
         L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, po.n, span_bits(po.span));
-        HIPCHK(c, launch_keygen(L.s, D->soa, soa_sig3(D->soa, D->soa_n, D->soa_info), D->soa_info, po.n, po.t, po.cam, po.view, po.key_mode, (float*)K->d, (uint32_t*)I->d, kh, L.depth_sort.hist_rb, po.bias, po.span, L.host_total_dev + 4));
+        HIPCHK(c, launch_keygen(L.s, D->soa, soa_sig3(D->soa, D->soa_n, D->soa_info), D->soa_info, po.n, po.t, po.cam, po.view, po.key_mode, (float*)K->d, (uint32_t*)I->d, kh, L.depth_sort.hist_rb, po.bias, po.span, L.err_word()));
         L.depth_sort.hist_bias = po.bias;
     }
     if (po.sorted) {
@@ -841,10 +841,10 @@ int gs4d_create(int device, int width, int height, gs4d_ctx** out) {
             if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return bail(hipfail(c, e, "hipEventCreate"));
             if ((e = hipEventRecord(*ev, L.s)) != hipSuccess) return bail(hipfail(c, e, "hipEventRecord"));      // "already happened"
         }
-        if ((e = hipHostMalloc((void**)&L.host_total, 64, hipHostMallocMapped)) != hipSuccess) return bail(hipfail(c, e, "hipHostMalloc"));
-        memset(L.host_total, 0, 64);
+        if ((e = hipHostMalloc((void**)&L.host_total, VERDICT_WORDS * 4, hipHostMallocMapped)) != hipSuccess) return bail(hipfail(c, e, "hipHostMalloc"));
+        memset(L.host_total, 0, VERDICT_WORDS * 4);
         if ((e = hipHostGetDevicePointer((void**)&L.host_total_dev, L.host_total, 0)) != hipSuccess) return bail(hipfail(c, e, "hipHostGetDevicePointer"));
-        L.depth_sort.err = L.pair_sort.err = L.host_total_dev + 4;
+        L.depth_sort.err = L.pair_sort.err = L.err_word();
     }
     for (hipEvent_t* ev : { &c->ev_user, &c->ev_readback }) {
         if ((e = hipEventCreateWithFlags(ev, hipEventDisableTiming)) != hipSuccess) return bail(hipfail(c, e, "hipEventCreate"));

@@ -47,6 +47,44 @@ struct Uniforms {
     float min_opacity;
 };
 
+// ---- the verdict of a draw: two arrays of VERDICT_WORDS words ----
+// Every draw is validated after the fact.  Its kernels leave what they found in the lane's DEVICE words (BinScratch::total, TOT_*), the kernels that
+// follow read them there, and a copy for the host lands in the lane's pinned, mapped HOST words (Lane::host_total, HT_*), which resolve_lane
+// decodes behind the lane's event.  The two arrays do NOT share a layout.  Paths: ordered (binning.hip, composite.hip), exact = unordered with
+// exact lists (k_bucket_scan, k_bucket_scatter, k_bucket_tiles, k_composite_v2), staged = unordered with staged lists (k_project_count<.., 2>,
+// k_bucket_tiles_staged, k_composite_v2).  A word that a path does not write keeps what an earlier draw of the lane left.
+constexpr int VERDICT_WORDS = 16;                // 64 bytes each: bin_scratch_reserve, gs4d_create
+// Device words, zeroed when they are allocated:
+//   TOT_ENTRIES        tile-list entries of the draw, saturated at 2^32 - 1.  Written by the last workgroup of k_bin_emit (ordered) or of k_bucket_scan
+//                      (exact); read by the tile sort as its element count and by k_tile_ranges (ordered), copied to the host by k_composite_v2 (exact)
+//   TOT_FLAGS          VF_* (below).  Stored whole by the same two writers (VF_CAPACITY or 0); k_bucket_tiles ORs VF_LIST into it.  k_tile_ranges,
+//                      k_composite and k_composite_v2 (exact) stop on ANY flag; k_bucket_scatter and k_bucket_tiles stop on VF_CAPACITY only: other
+//                      workgroups of k_bucket_tiles raise VF_LIST while they run.  Copied to the host by k_bin_emit, k_composite_v2 (exact)
+//   TOT_COUNT_LO, _HI  the same count in 64 bits; writers and host copies as TOT_ENTRIES, no reader on the device
+//   TOT_LONGEST_LIST   exact: zeroed by k_bucket_scan, atomicMax by k_bucket_tiles, copied to HT_LONGEST_LIST by k_composite_v2
+//   TOT_UNUSED_5, _6   nothing writes or reads them
+//   TOT_SCAN_ARRIVALS  exact: workgroups of k_bucket_scan that have arrived; the last one sets it back to 0
+//   TOT_TICKET         ordered: ticket counter of the k_bin_emit workgroups, never reset (BinScratch::ticket_base is its value at the launch)
+//   TOT_ABORT          staged: == TileLists::seq <=> the draw was aborted.  Stored by k_project_count (a segment overflowed its block: TileCount::abort_word)
+//                      and k_bucket_tiles_staged (a bucket, a list or the box did not fit); read by k_composite_v2
+enum TotalWord : int { TOT_ENTRIES = 0, TOT_FLAGS = 1, TOT_COUNT_LO = 2, TOT_COUNT_HI = 3, TOT_LONGEST_LIST = 4, TOT_UNUSED_5 = 5, TOT_UNUSED_6 = 6, TOT_SCAN_ARRIVALS = 7, TOT_TICKET = 8, TOT_ABORT = 9 };
+// Host words, zeroed at gs4d_create; read by resolve_lane (HT_ERROR: device_error too):
+//   HT_ENTRIES         as TOT_ENTRIES.  Written by k_bin_emit (ordered), k_bucket_scan (exact, only when the capacity overflowed) and the first workgroup
+//                      of k_composite_v2 (exact: a copy; staged: the sum of the bucket statistics); the host reads the 64-bit count instead
+//   HT_FLAGS           VF_*; writers as HT_ENTRIES (staged: k_composite_v2 makes it up from TOT_ABORT and the statistics)
+//   HT_COUNT_LO, _HI   the entry count in 64 bits; writers as HT_ENTRIES
+//   HT_ERROR           raised by any kernel whose device-side check fails (Lane::err_word), never cleared: the context is unusable from then on
+//   HT_LONGEST_LIST    exact, staged: longest (sub-)list of a tile.  k_composite_v2; k_bucket_scan stores 0 when the capacity overflowed
+//   HT_LONGEST_RUN, HT_FULLEST_BUCKET, HT_FULLEST_SEG   exact, staged: longest (bucket, segment) run, entries of the fullest bucket and of the fullest
+//                      segment (TileLists::bstat, sstat), reduced by k_composite_v2: what sizes the staged draws that follow
+//   HT_USED_BOX        staged: the box of the tiles that hold entries (BOX_EMPTY: none); exact: BOX_NONE.  k_composite_v2
+enum HostWord : int { HT_ENTRIES = 0, HT_FLAGS = 1, HT_COUNT_LO = 2, HT_COUNT_HI = 3, HT_ERROR = 4, HT_LONGEST_LIST = 5, HT_LONGEST_RUN = 6, HT_FULLEST_BUCKET = 7, HT_FULLEST_SEG = 8, HT_USED_BOX = 9 };
+static_assert(TOT_ABORT < VERDICT_WORDS && HT_USED_BOX < VERDICT_WORDS, "the highest word of either layout fits the arrays");
+// The flags of TOT_FLAGS / HT_FLAGS: why a draw does not stand (resolve_lane re-runs it).  VF_CAPACITY: more entries than the lane's entry storage
+// holds (every path).  VF_LIST: a tile's (sub-)list is longer than the compositor was launched for (exact, staged).  VF_STAGED_MISS: a staged
+// guess missed — a segment, a bucket or the launch box (host word only).
+constexpr uint32_t VF_CAPACITY = 1u, VF_LIST = 2u, VF_STAGED_MISS = 4u;
+
 // ---- sort.hip ----
 struct SortScratch {
     uint32_t* keys2 = nullptr; uint32_t* vals2 = nullptr; size_t cap = 0;   // scratch B and C (keys2[2*cap], vals2[2*cap]; one allocation) — radix_sort.hpp:192-216 scratch
@@ -192,7 +230,7 @@ struct TileLists {
     uint4* bstat = nullptr;                                    // [nb_cap]
     uint32_t* sstat = nullptr;                                 // [1024]
     bool staged = false; uint32_t scap = 0, bcap = 0;         // the current draw is staged; entries a segment block holds, bucket capacity in the tile-ordered entry array
-    uint32_t seq = 0;                                          // sequence number of the lane's staged draws: total[TL_ABORT_WORD] == seq <=> this draw was aborted
+    uint32_t seq = 0;                                          // sequence number of the lane's staged draws: total[TOT_ABORT] == seq <=> this draw was aborted
     // staged draws: the BOX of tiles (in blocks of BOX_BLOCK x BOX_BLOCK tiles, both ends inclusive, box_pack) outside which the host expects no entry — a third guess
     // from the previous frames' statistics (bstat[b].w: the box of bucket b's non-empty tiles), checked by k_bucket_tiles_staged like the two capacities;
     // the compositor is launched for these tiles only.  BOX_NONE: the whole image.
@@ -200,36 +238,42 @@ struct TileLists {
 };
 constexpr uint32_t BOX_BLOCK = 4u, BOX_NONE = 0xFFFFFFFFu, BOX_EMPTY = 0x0000FFFFu;      // BOX_EMPTY: min 255, max 0 in both directions — the neutral element of box_join
 __host__ __device__ __forceinline__ uint32_t box_pack(uint32_t x0, uint32_t y0, uint32_t x1, uint32_t y1) { return x0 | (y0 << 8) | (x1 << 16) | (y1 << 24); }
+__host__ __device__ __forceinline__ uint32_t box_x0(uint32_t box) { return box & 255u; }
+__host__ __device__ __forceinline__ uint32_t box_y0(uint32_t box) { return (box >> 8) & 255u; }
+__host__ __device__ __forceinline__ uint32_t box_x1(uint32_t box) { return (box >> 16) & 255u; }
+__host__ __device__ __forceinline__ uint32_t box_y1(uint32_t box) { return box >> 24; }
+// (the fields are taken out by hand here: through the accessors the compiler orders the wave reductions of k_bucket_tiles_staged and k_composite_v2 differently)
 __host__ __device__ __forceinline__ uint32_t box_join(uint32_t a, uint32_t b) {
     const uint32_t x0 = (a & 255u) < (b & 255u) ? (a & 255u) : (b & 255u), y0 = ((a >> 8) & 255u) < ((b >> 8) & 255u) ? ((a >> 8) & 255u) : ((b >> 8) & 255u);
     const uint32_t x1 = ((a >> 16) & 255u) > ((b >> 16) & 255u) ? ((a >> 16) & 255u) : ((b >> 16) & 255u), y1 = (a >> 24) > (b >> 24) ? (a >> 24) : (b >> 24);
     return box_pack(x0, y0, x1, y1);
 }
 __host__ __device__ __forceinline__ bool box_holds(uint32_t box, uint32_t bx, uint32_t by) {      // block (bx, by) inside the box
-    return box == BOX_NONE || (bx >= (box & 255u) && bx <= ((box >> 16) & 255u) && by >= ((box >> 8) & 255u) && by <= (box >> 24));
+    return box == BOX_NONE || (bx >= box_x0(box) && bx <= box_x1(box) && by >= box_y0(box) && by <= box_y1(box));
 }
-constexpr int TL_ABORT_WORD = 9;                              // index into BinScratch::total
+// both corners of `inner` inside `outer` (always, for outer == BOX_NONE; what BOX_EMPTY or BOX_NONE as the inner box means is the caller's to decide).
+// Host code.  The two kernels that make this test (k_bucket_tiles_staged, k_composite_v2) spell out its two box_holds calls: wrapped in one
+// function they come out as different instructions.
+__host__ __device__ __forceinline__ bool box_within(uint32_t outer, uint32_t inner) { return box_holds(outer, box_x0(inner), box_y0(inner)) && box_holds(outer, box_x1(inner), box_y1(inner)); }
 // false: this frame / record count cannot use the unordered path (more than 256 * 1024 tiles, or 2^24 records)
 // key_span: host-proven largest blend key (the slabs divide [0, key_span] evenly)
 bool tile_lists_plan(TileLists& t, size_t ntiles, size_t nrecords, uint32_t slabs, int keybits, uint32_t key_span = 0xFFFFFFFFu, size_t expect_entries = 0);
 hipError_t tile_lists_reserve(hipStream_t st, TileLists& t, size_t ntiles, size_t nrecords);
 void tile_lists_free(TileLists& t);
-// total[0] entries (saturated), [1] abort flags (1: more entries than `cap`, 2: a list longer than `hint`), [2..3] 64-bit entry count, [4] longest list,
-// [6] workgroups of k_bucket_tiles that have finished, [7] of k_bucket_scan (back to 0 when the kernel ends); total_host (pinned, mapped) receives [0..3] and the longest list at [5]
+// total, total_host: the lane's device and host verdict words (TOT_*, HT_* above); the host words are written only when more than `cap` entries abort the draw here
 hipError_t launch_bucket_scan(hipStream_t st, TileLists& t, uint32_t* total, uint32_t* total_host, size_t cap);
 // skey == nullptr: the blend keys the projection left in t.skey; else an array of key bit patterns from which skey_bias is still to be subtracted (the caller's key buffer of a fused draw)
 hipError_t launch_bucket_scatter(hipStream_t st, TileLists& t, const uint32_t* trects, const float4* proj, const uint32_t* skey, uint32_t skey_bias, size_t nrecords, const uint32_t* total, uint2* tmp, int tiles_x, int shard_rank, int shard_world);
 hipError_t launch_bucket_tiles(hipStream_t st, TileLists& t, size_t ntiles, uint32_t* total, const uint2* tmp, uint2* entries, uint32_t hint);
 // staged draws: the segment blocks the projection kernel wrote (t.blocks, t.scap) -> tile lists at entries[b * t.bcap ...]; per-bucket statistics into t.bstat;
-// total[TL_ABORT_WORD] = t.seq when a run, a bucket or a list does not fit
+// total[TOT_ABORT] = t.seq when a segment's run, a bucket, a list or the box (t.box) does not fit
 hipError_t launch_bucket_tiles_staged(hipStream_t st, TileLists& t, size_t ntiles, int tiles_x, uint32_t* total, uint2* entries, uint32_t hint);
 hipError_t tile_lists_reserve_blocks(hipStream_t st, TileLists& t, size_t entries);
-// bstat / nb, sstat / rows: per-bucket and per-segment statistics for the host report; stage_seq != 0: a staged draw (aborted <=> total[TL_ABORT_WORD] == stage_seq,
-// the entry total is the sum of the statistics); rcap / scap / bcap: what the host guessed for it (longest run: no limit any more, 0xFFFFFFFF; fullest segment; fullest bucket)
+// tl: the draw's lists — the tile table, the per-bucket and per-segment statistics for the host report (bstat / nb, sstat / rows) and, of a staged draw
+// (tl.staged: aborted <=> total[TOT_ABORT] == tl.seq, the entry total is the sum of the statistics), what the host guessed for it: scap, bcap, box
 // t: the image; draw_ord: the draw's ordinal within its frame (Outputs::Ids)
-hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* entries, const uint32_t* tstart, const uint32_t* tcnt, const uint32_t* total, uint32_t* total_host, int tiles_x, int tiles_y, int W, int H,
-                               int premult_c, const Target& t, uint32_t hint, int keybits, int recbits, uint32_t slabs,
-                               const uint4* bstat, uint32_t nb, const uint32_t* sstat, uint32_t rows, uint32_t stage_seq, uint32_t rcap, uint32_t scap, uint32_t bcap, uint32_t box_blocks, uint32_t draw_ord);
+hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* entries, const TileLists& tl, const uint32_t* total, uint32_t* total_host, int tiles_x, int tiles_y, int W, int H,
+                               int premult_c, const Target& t, uint32_t hint, int keybits, int recbits, uint32_t draw_ord);
 
 #ifdef __HIPCC__
 // tiles touched by a pixel rectangle (x0|y0<<16, x1|y1<<16; x0 > x1: none), restricted to the tile rows ty % world == rank
@@ -289,11 +333,11 @@ hipError_t launch_preprocess_2d(hipStream_t st, const float* rec48, size_t n, co
 
 // ---- binning.hip ----
 struct BinScratch {
-    uint32_t* total = nullptr;        // [0] = number of tile-list entries (saturated), [1] = overflow flag, [2..3] = 64-bit count
+    uint32_t* total = nullptr;        // [VERDICT_WORDS]: the lane's device verdict words (TOT_*, above)
     uint32_t* ranges = nullptr; size_t tiles_cap = 0;           // [2*tiles] start,end — followed in the same allocation by
     unsigned long long* status = nullptr; size_t block_cap = 0; // the chained-scan words of the binning workgroups (epoch-tagged, never zeroed)
     uint32_t epoch = 0;
-    uint32_t ticket_base = 0;         // total[8] is the ticket counter of the binning workgroups
+    uint32_t ticket_base = 0;         // value of total[TOT_TICKET], the ticket counter of the binning workgroups, before the next launch
     // ranges are all-zero between draws: k_tile_ranges fills the non-empty tiles, the composite kernel clears each range it has read
 };
 hipError_t bin_scratch_reserve(hipStream_t st, BinScratch& b, size_t ninst, size_t ntiles);

@@ -22,7 +22,7 @@
 // Staged lists (round 4): once a draw of a scene has reported its fullest segment, longest (bucket, segment) run and fullest bucket, the draws
 // that follow skip the scan and the scatter: k_project_count<.., 2> counts, scans and PLACES its segment's entries in LDS and writes them out as
 // one dense block, k_bucket_tiles_staged reads bucket b's run out of every block.  Capacities are guesses (statistics + margin) that the
-// device checks; a draw that does not fit raises total[TL_ABORT_WORD] and is re-run with the exact kernels above.
+// device checks; a draw that does not fit raises total[TOT_ABORT] and is re-run with the exact kernels above.
 //
 // (A first version counted entries per tile with global atomics in the projection kernel and scattered with returning atomics:
 // 1.4e6 device-scope atomics cost 150 us each way on MI355X — they execute at the memory side, ~9e9/s when scattered.  Hence this.)
@@ -99,8 +99,8 @@ __global__ __launch_bounds__(256) void k_bucket_scan(const uint32_t* __restrict_
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
-        const bool last = atomicAdd(&total[7], 1u) == gridDim.x - 1u;
-        if (last) total[7] = 0u;
+        const bool last = atomicAdd(&total[TOT_SCAN_ARRIVALS], 1u) == gridDim.x - 1u;
+        if (last) total[TOT_SCAN_ARRIVALS] = 0u;
         s_last = last ? 1u : 0u;
     }
     __syncthreads();
@@ -110,9 +110,9 @@ __global__ __launch_bounds__(256) void k_bucket_scan(const uint32_t* __restrict_
     if (threadIdx.x == 0) {
         const bool over = grand > (unsigned long long)cap;
         const uint32_t sat = grand > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)grand;
-        total[0] = sat; total[1] = over ? 1u : 0u; total[2] = (uint32_t)grand; total[3] = (uint32_t)(grand >> 32); total[4] = 0u; total[6] = 0u;
+        total[TOT_ENTRIES] = sat; total[TOT_FLAGS] = over ? VF_CAPACITY : 0u; total[TOT_COUNT_LO] = (uint32_t)grand; total[TOT_COUNT_HI] = (uint32_t)(grand >> 32); total[TOT_LONGEST_LIST] = 0u;
         // an aborted draw stops here: tell the host now (otherwise k_bucket_tiles reports, once the longest list is known)
-        if (over) { total_host[0] = sat; total_host[1] = 1u; total_host[2] = (uint32_t)grand; total_host[3] = (uint32_t)(grand >> 32); total_host[5] = 0u; }
+        if (over) { total_host[HT_ENTRIES] = sat; total_host[HT_FLAGS] = VF_CAPACITY; total_host[HT_COUNT_LO] = (uint32_t)grand; total_host[HT_COUNT_HI] = (uint32_t)(grand >> 32); total_host[HT_LONGEST_LIST] = 0u; }
     }
 }
 
@@ -121,7 +121,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_bucket_scatter(const uint32_t* 
                                                         const uint32_t* __restrict__ offs, const uint32_t* __restrict__ bbase, const uint32_t* __restrict__ total, uint2* __restrict__ tmp,
                                                         uint32_t tiles_x, uint32_t shard_rank, uint32_t shard_world) {
     __shared__ uint32_t cur[1024];
-    if (total[1] & 1u) return;                             // aborted draw: slots would lie beyond the capacity
+    if (total[TOT_FLAGS] & VF_CAPACITY) return;            // aborted draw: slots would lie beyond the capacity
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     for (uint32_t b = tid; b < nb; b += SEG_THREADS) cur[b] = bbase[b] + offs[(size_t)blockIdx.x * nb + b];
     __syncthreads();
@@ -177,7 +177,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bucket_tiles(const uint2* __rest
                                                              uint32_t* __restrict__ total, uint32_t hint) {
     extern __shared__ uint32_t cnt[];                      // [nc]
     __shared__ uint32_t ws[BT_THREADS / 64];
-    if (total[1] & 1u) return;                             // capacity overflow (set by k_bucket_scan); bit 1 is raised HERE by other workgroups and must not stop this one
+    if (total[TOT_FLAGS] & VF_CAPACITY) return;            // capacity overflow (set by k_bucket_scan); VF_LIST is raised HERE by other workgroups and must not stop this one
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6, b = blockIdx.x;
     const uint32_t lo = bbase[b], hi = bbase[b + 1];
     const uint32_t sl = (uint32_t)__ffs((int)slabs) - 1u;  // log2(slabs)
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bucket_tiles(const uint2* __rest
             run += c;
         }
     }
-    if (lane == 0u && mx) { atomicMax(&total[4], mx); if (mx > hint) atomicOr(&total[1], 2u); }
+    if (lane == 0u && mx) { atomicMax(&total[TOT_LONGEST_LIST], mx); if (mx > hint) atomicOr(&total[TOT_FLAGS], VF_LIST); }
     __syncthreads();
     for (uint32_t r0 = lo; r0 < hi; r0 += ROUND) {
         if (!single) {
@@ -356,7 +356,7 @@ __global__ __launch_bounds__(THREADS) void k_bucket_tiles_staged(const uint2* __
         for (int k = 0; k < THREADS / 64; ++k) bb = box_join(bb, wb[k]);
         bstat[b] = make_uint4(T, maxrun, longest, bb);
         // an entry outside the box the compositor is launched for (a guess, like the capacities): the draw is re-run exactly, over the whole image
-        const bool outside = bb != BOX_EMPTY && !(box_holds(box, bb & 255u, (bb >> 8) & 255u) && box_holds(box, (bb >> 16) & 255u, bb >> 24));
+        const bool outside = bb != BOX_EMPTY && !(box_holds(box, box_x0(bb), box_y0(bb)) && box_holds(box, box_x1(bb), box_y1(bb)));
         if (longest > hint || outside) *abort_word = seq;
     }
     __syncthreads();
@@ -467,7 +467,7 @@ hipError_t launch_bucket_tiles_staged(hipStream_t st, TileLists& t, size_t ntile
     // frame at C2, alternating runs) — an 8-wave workgroup finds room on a busy CU sooner than a 16-wave one.  A thread holds up to 16 (buckets of <= 8192
     // entries: what tile_lists_plan aims at) or 32 entries.
 #define GS4D_BTS(K) k_bucket_tiles_staged<K, 512><<<dim3(t.nb), dim3(512), t.counters * 4u, st>>>(t.blocks, t.hist, t.hist + t.hist_cap, t.rows, t.scap, t.bcap, t.nb, (uint32_t)ntiles, t.slabs, t.slab_shift, \
-                                                                                                 t.counters, t.tstart, t.tcnt, entries, t.bstat, total + TL_ABORT_WORD, t.seq, hint, (uint32_t)tiles_x, t.box)
+                                                                                                 t.counters, t.tstart, t.tcnt, entries, t.bstat, total + TOT_ABORT, t.seq, hint, (uint32_t)tiles_x, t.box)
     if (t.bcap <= 16u * 512u) GS4D_BTS(16);
     else if (t.bcap <= 32u * 512u) GS4D_BTS(32);
     else return hipErrorInvalidValue;                      // run_draw does not stage such a draw
