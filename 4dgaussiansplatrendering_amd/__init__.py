@@ -88,6 +88,7 @@ def _load():
         "gs4d_debug_read_projected": (i32, [vp, vp, sz]),
         "gs4d_host_look_at": (None, [vp, vp, vp, vp]),
         "gs4d_host_perspective": (None, [f32, i32, i32, f32, f32, vp]),
+        "gs4d_host_key_bounds": (None, [vp, vp, f32, vp, i32, C.POINTER(u32), C.POINTER(u32)]),
         "gs4d_host_quat_look_at": (None, [vp, vp, vp]),
         "gs4d_host_splat3d_cov": (None, [vp, vp, vp]),
         "gs4d_host_splat3d_mesh": (None, [vp, vp, vp, vp, vp]),
@@ -326,6 +327,14 @@ def unproject(view, proj, width, height, px, py, depth):
     out = np.zeros(3, np.float32)
     _lib.gs4d_host_unproject(_ptr(_f32(view)), _ptr(_f32(proj)), width, height, px, py, depth, _ptr(out))
     return out
+
+
+def key_bounds(lo7, hi7, t, cam_pos, key_mode=KEY_REF_INV_EUCLID):
+    """(bias, span) gs4d_keygen proves for the keys of records inside the box lo7 .. hi7 of (x, y, z, mu_t, vx, vy, vz): every key's bit
+    pattern lies in [bias, bias + span]."""
+    bias, span = C.c_uint32(0), C.c_uint32(0)
+    _lib.gs4d_host_key_bounds(_ptr(_f32(lo7)), _ptr(_f32(hi7)), t, _ptr(_f32(cam_pos)), key_mode, C.byref(bias), C.byref(span))
+    return bias.value, span.value
 
 
 def write_png(path, rgba8):

@@ -1168,36 +1168,17 @@ int gs4d_keygen(gs4d_ctx* c, gs4d_buf data, float t, const float cam[3], gs4d_bu
     }
     { rc = lane_access(c, *D, false); if (rc) return rc; D->tail_mask |= 1u << c->cur; rc = lane_access(c, *K, true); if (rc) return rc; rc = lane_access(c, *I, true); if (rc) return rc; }
     Lane& L = lane(c);
-    // A proven lower bound of every key (1 / farthest possible distance, from the bounding box of the records) is subtracted inside
-    // the sort's digit extraction: when the keys span less than 2^24 bit patterns above it (camera outside the cloud, far/near < 4)
-    // the top digit becomes constant.  When the camera is provably outside the box the same reasoning gives an upper bound, hence
-    // the number of key bits above the bias: with <= 24 the sort is launched with three passes instead of four.  k_keygen re-checks
-    // both bounds for every key and raises the error word if one does not hold.
+    // A proven lower bound of every key (the key of the farthest point the records' bounding box allows) is subtracted inside the sort's
+    // digit extraction: when the keys span less than 2^24 bit patterns above it (camera outside the cloud, far/near < 4) the top digit
+    // becomes constant.  When the camera is provably outside the box the same reasoning gives an upper bound, hence the number of key bits
+    // above the bias: with <= 24 the sort is launched with three passes instead of four.  The bounds are gs4d_host_key_bounds' (gs4d_host.cpp:
+    // the kernel's own float32 operations on the ends of the box); k_keygen re-checks both for every key and raises the error word if one
+    // does not hold.
     uint32_t bias = 0, span = 0xFFFFFFFFu;
-    if (key_mode == GS4D_KEY_REF_INV_EUCLID && D->bb_ok) {          // the box covers all records of the buffer, a superset of the n keyed
-        const double c_lo = (double)t - D->bb_hi[3], c_hi = (double)t - D->bb_lo[3];
-        double d2 = 0.0, n2 = 0.0;
-        for (int ax = 0; ax < 3; ++ax) {
-            const double v_lo = D->bb_lo[4 + ax], v_hi = D->bb_hi[4 + ax];
-            const double p1 = v_lo * c_lo, p2 = v_lo * c_hi, p3 = v_hi * c_lo, p4 = v_hi * c_hi;
-            const double m_lo = D->bb_lo[ax] + std::min(std::min(p1, p2), std::min(p3, p4));
-            const double m_hi = D->bb_hi[ax] + std::max(std::max(p1, p2), std::max(p3, p4));
-            const double far = std::max(std::fabs(m_lo - (double)cam[ax]), std::fabs(m_hi - (double)cam[ax]));
-            d2 += far * far;
-            const double near = std::max(0.0, std::max(m_lo - (double)cam[ax], (double)cam[ax] - m_hi));
-            n2 += near * near;
-        }
-        const double dmax = std::sqrt(d2) * (1.0 + 1e-4) + 1e-3;       // generous against float rounding in the kernel's own arithmetic
-        const float lb = (float)((1.0 / dmax) * (1.0 - 1e-5));
-        if (std::isfinite(dmax) && lb > 0.0f && std::isfinite(lb)) {
-            memcpy(&bias, &lb, 4);
-            const double dmin = std::sqrt(n2) * (1.0 - 1e-4) - 1e-3;
-            if (dmin > 0.0) {
-                const float ub = (float)((1.0 / dmin) * (1.0 + 1e-5));
-                uint32_t ubits; memcpy(&ubits, &ub, 4);
-                if (std::isfinite(ub) && ubits >= bias) span = ubits - bias;
-            }
-        }
+    if (D->bb_ok) {                                                 // the box covers all records of the buffer, a superset of the n keyed
+        float lo[7], hi[7];
+        for (int k = 0; k < 7; ++k) { lo[k] = (float)D->bb_lo[k]; hi[k] = (float)D->bb_hi[k]; }      // (float values, kept as doubles)
+        gs4d_host_key_bounds(lo, hi, t, cam, key_mode, &bias, &span);
     }
     // Not launched yet (see gs4d_ctx::po): everything the launch needs is recorded, everything a later call may ask about the buffers
     // (versions, what the index will have been sorted by) is settled now.

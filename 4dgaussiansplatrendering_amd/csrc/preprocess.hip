@@ -175,7 +175,8 @@ __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid,
     if (!valid) { cx = cy = a0x = a0y = a1x = a1y = hx = hy = 0.0f; alpha = 0.0f; rect0 = 1u; rect1 = 0u; depth = 0.0f; }
     // the GL clamps a fragment's colour to [0, 1] before blending into the reference's RGBA8 framebuffer; where the fragment shader passes
     // the colour through unchanged that is a per-record operation (the 3D-Full shader multiplies by c first: clamped per fragment)
-    if (clamp_rgb) { r = __saturatef(r); g = __saturatef(g); b = __saturatef(b); }
+    // (fminf(fmaxf(x, 0), 1), the checker's form: a NaN colour clamps to 0 — __saturatef's compares let it through to every pixel of the footprint)
+    if (clamp_rgb) { r = fminf(fmaxf(r, 0.0f), 1.0f); g = fminf(fmaxf(g, 0.0f), 1.0f); b = fminf(fmaxf(b, 0.0f), 1.0f); }
     if (out.trects) out.trects[i] = pack_trect(rect0, rect1);      // (null: nothing downstream reads it — a staged draw writes its list entries itself)
     float4* o = out.proj + (size_t)i * 4;
     // (x components of the two affine rows side by side, likewise y: the compositor forms u and v with packed two-float instructions)

@@ -148,6 +148,44 @@ void gs4d_host_unproject(const float view[16], const float proj[16], int width, 
     for (int k = 0; k < 3; ++k) world3[k] = (float)(w[k] / w[3]);
 }
 
+// Bounds of the depth keys (arithmetic contract): every GS4D_KEY_REF_INV_EUCLID key of a record inside the box lo[7]..hi[7] of
+// (x, y, z, mu_t, velocity = sig[3].xyz), as a uint32 bit pattern, lies in [*bias, *bias + *span].  gs4d_keygen subtracts the bias inside the
+// sort's digit extraction and sizes the sort by the span.
+// The proof is monotonicity, not a margin: the key kernel (sort.hip k_keygen, preprocess.hip blend_key_4d) evaluates
+//     ct = t - mu_t;  x = p.x + v.x * ct;  dx = x - cam.x;  key = 1 / sqrt((dx*dx + dy*dy) + dz*dz)
+// in float32, and every one of these correctly rounded operations is monotone in each argument.  The same float32 operations applied to the
+// ends of the box (interval arithmetic; the product takes the four corners) therefore bound every intermediate of every record, rounding
+// included, whatever the size of the coordinates — and the ends overflow exactly where a record can, which leaves a bound of 0 (x = +-inf, key
+// = 0) by itself.  Only 0 * inf makes a NaN, and only a non-finite ct makes an inf factor: then, and for non-finite arguments, nothing is claimed.
+// No upper bound is claimed when the camera is inside or on the box (keys up to +inf).  Built with -ffp-contract=off like the kernels.
+void gs4d_host_key_bounds(const float lo[7], const float hi[7], float t, const float cam[3], int key_mode, uint32_t* bias, uint32_t* span) {
+    *bias = 0u; *span = 0xFFFFFFFFu;
+    if (key_mode != GS4D_KEY_REF_INV_EUCLID) return;
+    bool ok = std::isfinite(t) && std::isfinite(cam[0]) && std::isfinite(cam[1]) && std::isfinite(cam[2]);
+    for (int k = 0; k < 7; ++k) ok = ok && std::isfinite(lo[k]) && std::isfinite(hi[k]) && lo[k] <= hi[k];
+    const float ct_lo = t - hi[3], ct_hi = t - lo[3];
+    if (!ok || !std::isfinite(ct_lo) || !std::isfinite(ct_hi)) return;
+    float far2[3], near2[3];
+    for (int ax = 0; ax < 3; ++ax) {
+        const float v_lo = lo[4 + ax], v_hi = hi[4 + ax];
+        const float p1 = v_lo * ct_lo, p2 = v_lo * ct_hi, p3 = v_hi * ct_lo, p4 = v_hi * ct_hi;
+        const float m_lo = lo[ax] + std::min(std::min(p1, p2), std::min(p3, p4));
+        const float m_hi = hi[ax] + std::max(std::max(p1, p2), std::max(p3, p4));
+        const float d_lo = m_lo - cam[ax], d_hi = m_hi - cam[ax];
+        const float far = std::max(std::fabs(d_lo), std::fabs(d_hi));
+        const float near = d_lo > 0.0f ? d_lo : (d_hi < 0.0f ? -d_hi : 0.0f);
+        far2[ax] = far * far; near2[ax] = near * near;
+    }
+    const float key_lo = 1.0f / std::sqrt((far2[0] + far2[1]) + far2[2]);
+    const float n2 = (near2[0] + near2[1]) + near2[2];
+    std::memcpy(bias, &key_lo, 4);
+    if (n2 > 0.0f) {
+        const float key_hi = 1.0f / std::sqrt(n2);
+        uint32_t ubits; std::memcpy(&ubits, &key_hi, 4);
+        if (ubits >= *bias) *span = ubits - *bias;
+    }
+}
+
 // ---- Camera input model (Camera.cpp:90-99, 116-220) ----------------------------------------------------------------------
 static Vec3 v3(const float* p) { return { p[0], p[1], p[2] }; }
 static void put(float* p, Vec3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }

@@ -290,6 +290,11 @@ GS4D_API void gs4d_host_camera_focal(float fov, int width, int height, float out
  * width x height image — window coordinates (px + 0.5, py + 0.5), row 0 = bottom, as the images; fractional px, py allowed.  With
  * gs4d_read_aux and gs4d_host_camera_look_at_point this turns the press of a cursor into a camera that looks at what lies under it. */
 GS4D_API void gs4d_host_unproject(const float view[16], const float proj[16], int width, int height, float px, float py, float depth, float world3[3]);
+/* The bounds gs4d_keygen derives for its keys, as a pure function: every key (as a uint32 bit pattern) of a record whose position, mu_t and
+ * velocity sig[3].xyz lie in the box lo[7] .. hi[7] (x, y, z, mu_t, vx, vy, vz) is in [*bias, *bias + *span] at time t for a camera at cam.
+ * Proven by evaluating the kernel's own float32 operations, all monotone, on the ends of the box; *bias = 0 and *span = 0xFFFFFFFF where
+ * nothing can be claimed (non-finite arguments, t - mu_t overflowing, GS4D_KEY_VIEW_Z); no upper bound with the camera inside or on the box. */
+GS4D_API void gs4d_host_key_bounds(const float lo[7], const float hi[7], float t, const float cam[3], int key_mode, uint32_t* bias, uint32_t* span);
 
 /* Presentation: an RGBA8 frame as produced by gs4d_read_pixels_rgba8_device (bottom row first) -> PNG file */
 GS4D_API int gs4d_host_write_png(const char* path, const uint8_t* rgba8, int width, int height);
