@@ -219,7 +219,7 @@ hipError_t bin_scratch_reserve(hipStream_t st, BinScratch& b, size_t ninst, size
         if ((e = hipMemsetAsync(b.total, 0, VERDICT_WORDS * 4, st)) != hipSuccess) return e;
         b.ticket_base = 0;
     }
-    if (b.block_cap < nb || b.tiles_cap < ntiles) {
+    if (b.block_cap < nb || b.tiles_cap < ntiles) {      // (not grow_device_array: two arrays with a capacity each in one block, zeroed on the stream)
         if (b.ranges) { (void)hipStreamSynchronize(st); (void)hipFree(b.ranges); }
         const size_t nb2 = nb > b.block_cap ? nb : b.block_cap, nt2 = ntiles > b.tiles_cap ? ntiles : b.tiles_cap;
         b.ranges = nullptr; b.status = nullptr; b.block_cap = b.tiles_cap = 0;

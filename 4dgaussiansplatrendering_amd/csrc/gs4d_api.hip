@@ -53,10 +53,10 @@ struct Buffer {
     // waits for an event recorded on that stream at the first such use (the caller has queued the writes by then: that is the contract).
     hipEvent_t ev_fill = nullptr; unsigned fill_mask = 0; bool fill_recorded = false;
     // Provenance of a sort index: set when gs4d_sort_pairs has sorted exactly the keys and the identity index gs4d_keygen wrote for
-    // `prov_data` — the contents are then "records of prov_data in ascending (depth key, record index)" for as long as `version`
+    // prov.data — the contents are then "records of prov.data in ascending (depth key, record index)" for as long as `version`
     // still equals prov_ver, and a draw that binds it can take its blend order from the keys instead of reading it (tilelist.hip).
-    bool prov_valid = false; gs4d_buf prov_data = 0; uint64_t prov_data_ver = 0, prov_ver = 0; size_t prov_n = 0; int prov_bits = 32; uint32_t prov_span = 0xFFFFFFFFu;
-    KeySrc prov_ks;
+    bool prov_valid = false; uint64_t prov_ver = 0; SortedBy prov;
+    void sorted_by(bool valid, const SortedBy& by) { prov_valid = valid; if (valid) { prov = by; prov_ver = version; } }      // (after the sort has bumped `version`)
 };
 
 struct DrawArgs {
@@ -67,15 +67,15 @@ struct DrawArgs {
     bool quads = false;
     int lane = 0, fb = 0;          // where the draw ran
     bool v2 = false;               // unordered tile lists (tilelist.hip); false: instance-ordered lists (binning.hip)
-    KeySrc ks; int keybits = 32;   // v2: where the blend order comes from
-    uint32_t key_span = 0xFFFFFFFFu; // ... and the host-proven largest blend key (the depth slabs divide [0, key_span])
-    // the draw also executes the gs4d_keygen + gs4d_sort_pairs that were queued for it (first run only: a re-run finds the buffers sorted)
-    bool fuse = false; gs4d_buf fuse_keys = 0, fuse_idx = 0; uint32_t fuse_span = 0xFFFFFFFFu;
+    BlendOrder blend_order;        // v2, fuse, regen_order: where the blend order comes from, the largest blend key and its width
+    // the draw also executes the gs4d_keygen + gs4d_sort_pairs that were queued for it (first run only: a re-run finds the buffers sorted).  Its keys
+    // are blend_order's: draw_common fuses only the keygen whose sort made the draw's own index — one BlendOrder, copied to both; no span of its own.
+    bool fuse = false; gs4d_buf fuse_keys = 0, fuse_idx = 0;
     int blend_src = GS4D_SRC_ALPHA, blend_dst = GS4D_ONE_MINUS_SRC_ALPHA;       // glBlendFunc state at the draw
     float clear[4] = { 0, 0, 0, 0 };   // what "clear" meant for the image when the draw was issued (a re-run must not pick up a later glClearColor)
     int shard_rank = 0, shard_world = 1;       // ... and the tile-row shard
     // The re-run of an unordered draw on the ordered path: the draw never read the caller's sort index (it took its order from the keys), and by
-    // now the application may have overwritten it for a later frame.  The re-run regenerates "records in ascending (key, index)" from `ks`
+    // now the application may have overwritten it for a later frame.  The re-run regenerates "records in ascending (key, index)" from `blend_order`
     // into the lane's private index instead of reading the caller's buffer.
     bool regen_order = false;
     bool exact_lists = false;         // the re-run of a staged draw whose blocks, runs or buckets did not fit: builds its lists exactly (scan + scatter)
@@ -128,8 +128,9 @@ struct Lane {
     float* line_verts = nullptr; size_t line_cap = 0;   // device copy of the vertices of the latest gs4d_draw_lines (the lane's stream orders its reuse)
     uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
     uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
-    gs4d_buf kg_buf = 0; uint64_t kg_ver = 0; size_t kg_n = 0;   // key buffer whose digit histograms k_keygen left for the next sort
-    gs4d_buf kg_idx = 0, kg_data = 0; uint64_t kg_idx_ver = 0, kg_data_ver = 0; KeySrc kg_ks; int kg_bits = 32; uint32_t kg_span = 0xFFFFFFFFu;   // ... the identity index it wrote beside them, and what the keys were computed from
+    gs4d_buf kg_buf = 0; uint64_t kg_ver = 0;         // key buffer whose digit histograms k_keygen left for the next sort
+    gs4d_buf kg_idx = 0; uint64_t kg_idx_ver = 0;     // ... the identity index it wrote beside them
+    SortedBy keyed;                                    // ... and what the lane's last gs4d_keygen keyed: which records, in which order
     // Storage renaming for per-frame key / index buffers.  A buffer object is a NAME; its device storage is the library's.  gs4d_keygen
     // overwrites its two output buffers entirely, so when their storage is still being written or read by ANOTHER lane's frame (an
     // application with one key / index pair for all frames: the reference's layout, Scenes.h m_key_buf / m_values_buf) the new frame
@@ -176,8 +177,7 @@ struct gs4d_ctx {
     // A gs4d_keygen (and the gs4d_sort_pairs of its output) is not launched at once: if the draw that follows takes its blend order from
     // exactly that sort, the projection kernel generates the keys as a by-product (it recomputes them anyway) and the sort is queued
     // behind the draw.  Any other call that could observe the buffers launches the stand-alone kernels first (flush_order).
-    struct { bool keygen = false, sorted = false; int lane = 0; gs4d_buf data = 0, keys = 0, idx = 0; size_t n = 0; float t = 0; float cam[3] = { 0, 0, 0 };
-             int key_mode = 0; uint32_t bias = 0, span = 0xFFFFFFFFu; float view[16] = { 0 }; } po;
+    struct { bool keygen = false, sorted = false; int lane = 0; gs4d_buf data = 0, keys = 0, idx = 0; size_t n = 0; BlendOrder order; } po;
     int blend_src = GS4D_SRC_ALPHA, blend_dst = GS4D_ONE_MINUS_SRC_ALPHA;     // glBlendFunc state (Application.cpp:137-138, 150)
     bool defer_order = true;           // GS4D_FUSE_KEYGEN=0 switches the deferral off (test hook)
     uint64_t stat_composited_tiles = 0;      // tiles the compositing kernel of the last unordered draw was launched for (staged draws: the launch box)
@@ -236,8 +236,8 @@ Target draw_target(gs4d_ctx* c, const Framebuffer& F, const DrawArgs& a) {
 
 struct StageTimer {
     gs4d_ctx* c; int slot; hipStream_t s;
-    StageTimer(gs4d_ctx* c_, int id) : c(c_), slot(-1), s(c_->lanes[c_->cur].s) {      // run_draw re-runs make their lane current first (resolve_lane)
-        if (((c->profiling >> id) & 1u) && c->prof_frame < gs4d_ctx::PROF_FRAMES && c->prof_tick % (uint64_t)c->prof_every == 0) { slot = c->prof_frame * GS4D_T_COUNT + id; (void)hipEventRecord(c->ev0[slot], s); }
+    StageTimer(gs4d_ctx* c_, int id) : c(c_), slot(-1), s(c_->lanes[c_->cur].s) {      // run_draw re-runs make their lane current first (resolve_lane); id < 0: times nothing
+        if (id >= 0 && ((c->profiling >> id) & 1u) && c->prof_frame < gs4d_ctx::PROF_FRAMES && c->prof_tick % (uint64_t)c->prof_every == 0) { slot = c->prof_frame * GS4D_T_COUNT + id; (void)hipEventRecord(c->ev0[slot], s); }
     }
     ~StageTimer() { if (slot >= 0) { (void)hipEventRecord(c->ev1[slot], s); c->ran[slot] = 1; } }
 };
@@ -310,14 +310,9 @@ int lane_access(gs4d_ctx* c, Buffer& B, bool write) {
 int host_access(gs4d_ctx* c, Buffer& B);
 
 int ensure_pairs(gs4d_ctx* c, Lane& L, size_t cap) {
-    if (L.pair_cap >= cap) return GS4D_OK;
-    HIPCHK(c, hipStreamSynchronize(L.s));
-    if (L.pair_keys) (void)hipFree(L.pair_keys);
-    L.pair_keys = L.pair_vals = nullptr; L.pair_cap = 0;
-    HIPCHK(c, hipMalloc(&L.pair_keys, cap * 16));      // ordered path: tile ids | records (4 + 4 bytes per slot); unordered path: two arrays of (key, record)
-    L.pair_vals = L.pair_keys + cap;
-    L.pair_cap = cap;
-    return GS4D_OK;
+    const hipError_t e = grow_device_array(L.s, L.pair_keys, L.pair_cap, cap, 16);      // ordered path: tile ids | records (4 + 4 bytes per slot); unordered path: two arrays of (key, record)
+    L.pair_vals = L.pair_keys ? L.pair_keys + L.pair_cap : nullptr;
+    return e == hipSuccess ? GS4D_OK : hipfail(c, e, "grow_device_array(L.pair_keys)");
 }
 
 int ensure_soa(gs4d_ctx* c, Buffer& b) {
@@ -412,7 +407,8 @@ int enqueue_raster(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, cons
 }
 
 // Unordered path: the projection kernel has counted the entries per tile; scan, scatter, composite (tilelist.hip, composite2.hip).
-int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, size_t nrecords, int premult_c) {
+// fused_keys: the caller's key buffer of a fused draw (the projection wrote the keys there and nowhere else), else null
+int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, size_t nrecords, int premult_c, const uint32_t* fused_keys) {
     const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
     uint2* tmp = (uint2*)L.pair_keys;              // the lane's entry storage holds 16 bytes per slot: [0, cap) bucket order, [cap, 2 cap) tile order
     uint2* entries = tmp + L.pair_cap;
@@ -423,8 +419,6 @@ int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, s
 #ifdef GS4D_TUNING
         { static const bool sk = getenv("GS4D_ABLATE_SCATTER") != nullptr; static int warm = 0; skip_lists = sk && ++warm > 16; }      // ablation: steady-state frames reuse the bucket array of an earlier frame of their lane (same scene): what scan + scatter cost the frame
 #endif
-        const uint32_t* fused_keys = nullptr;
-        if (a.fuse) { Buffer* K = getbuf(c, a.fuse_keys); if (K) fused_keys = (const uint32_t*)K->d; }      // the projection wrote the keys there and nowhere else
         if (L.tl.staged) {
             // staged: the projection kernel wrote the segment blocks; one kernel turns them into tile lists and checks what the host guessed
             HIPCHK(c, launch_bucket_tiles_staged(L.s, L.tl, ntiles, c->tiles_x, L.bin.total, entries, c->list_hint));
@@ -432,7 +426,7 @@ int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, s
         } else {
             if (!skip_lists) {
             HIPCHK(c, launch_bucket_scan(L.s, L.tl, L.bin.total, L.host_total_dev, L.pair_cap));
-            HIPCHK(c, launch_bucket_scatter(L.s, L.tl, L.trects, L.proj, fused_keys, a.ks.bias, nrecords, L.bin.total, tmp, c->tiles_x, a.shard_rank, a.shard_world));
+            HIPCHK(c, launch_bucket_scatter(L.s, L.tl, L.trects, L.proj, fused_keys, a.blend_order.ks.bias, nrecords, L.bin.total, tmp, c->tiles_x, a.shard_rank, a.shard_world));
             }
             HIPCHK(c, launch_bucket_tiles(L.s, L.tl, ntiles, L.bin.total, tmp, entries, c->list_hint));
         }
@@ -443,7 +437,7 @@ int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, s
 #endif
     {
         StageTimer t(c, GS4D_T_COMPOSITE);
-        HIPCHK(c, launch_composite_v2(L.s, L.proj, entries, L.tl, L.bin.total, L.host_total_dev, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, draw_target(c, F, a), c->list_hint, a.keybits, recbits, a.draw_ord));
+        HIPCHK(c, launch_composite_v2(L.s, L.proj, entries, L.tl, L.bin.total, L.host_total_dev, c->tiles_x, c->tiles_y, c->W, c->H, premult_c, draw_target(c, F, a), c->list_hint, a.blend_order.bits, recbits, a.draw_ord));
     }
     // (the box's width and height clipped to the image's: more tiles than tile_box() launches when a box starts away from the left / top edge and overhangs the far one)
     { const uint32_t b = L.tl.staged ? L.tl.box : BOX_NONE; c->stat_composited_tiles = b == BOX_NONE ? ntiles : (uint64_t)std::min<uint32_t>((box_x1(b) - box_x0(b) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_x) * std::min<uint32_t>((box_y1(b) - box_y0(b) + 1u) * BOX_BLOCK, (uint32_t)c->tiles_y); }
@@ -451,172 +445,198 @@ int enqueue_raster_v2(gs4d_ctx* c, Lane& L, Framebuffer& F, const DrawArgs& a, s
     return GS4D_OK;
 }
 
-// `preprocess` false: the re-run of a draw whose tile lists overflowed (projected records and the sort-index copy are still valid).
 // width of a key span in bits (what the depth sort and the compositor's list sort have to look at)
 static int span_bits(uint32_t span) { return span == 0xFFFFFFFFu ? 32 : std::max(1, 32 - __builtin_clz(span | 1u)); }
 
-int run_draw(gs4d_ctx* c, const DrawArgs& a, bool preprocess) {
-    const int fuse_bits = span_bits(a.fuse_span);          // of the keys a fused draw generates (from the draw's own arguments: the lane's sorter may have been told about a later frame's keys by now)
-    Lane& L = c->lanes[a.lane];
-    Framebuffer& F = c->fbs[a.fb];
-    Buffer* data = getbuf(c, a.data);
-    if (!data) return fail(c, GS4D_E_INVALID, "draw: no splat data buffer bound");
-    const uint32_t* order = nullptr;
-    Buffer* ob = nullptr;
-    size_t nrec = 0, npre = 0;
-    int premult = 0;
-    if (a.quads) { nrec = data->bytes / 288; npre = nrec < a.instances ? nrec : a.instances; premult = 1; }
+// Enqueue on lane L: k_keygen for the first n records of D in order `ks` into (keys, idx), every key checked against `span`, and — `sort` — the
+// stable sort of those pairs on `bits` bits: idx then holds "records in ascending (depth key, record index)".  timed: as GS4D_T_KEYGEN / GS4D_T_SORT.
+int enqueue_keygen_sort(gs4d_ctx* c, Lane& L, const Buffer& D, size_t n, const KeySrc& ks, uint32_t span, int bits, uint32_t* keys, uint32_t* idx, bool sort, bool timed) {
+    {
+        hipError_t he = hipSuccess;
+        uint32_t* kh = sort_hist_slot(L.s, L.depth_sort, n, &he);
+        if (!kh) return hipfail(c, he, "sort_hist_slot");
+        StageTimer tm(c, timed ? GS4D_T_KEYGEN : -1);
+        L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, n, bits);
+        HIPCHK(c, launch_keygen(L.s, D.soa, soa_sig3(D.soa, D.soa_n, D.soa_info), D.soa_info, n, ks, (float*)keys, idx, kh, L.depth_sort.hist_rb, span, L.err_word()));
+        L.depth_sort.hist_bias = ks.bias;
+    }
+    StageTimer t(c, sort && timed ? GS4D_T_SORT : -1);
+    if (sort) HIPCHK(c, radix_sort_pairs(L.s, L.depth_sort, keys, idx, n, nullptr, bits, true));
+    return GS4D_OK;
+}
+
+// ---- the steps of run_draw, in the order it takes them ----
+// The shape of a draw, from its mode and buffers.  npre: records to project; ob: the caller's sort index (null when the draw regenerates its order)
+struct DrawShape { Buffer* data = nullptr; Buffer* ob = nullptr; size_t nrec = 0, npre = 0; int premult = 0; bool empty = false; };
+int draw_shape(gs4d_ctx* c, const DrawArgs& a, DrawShape& s) {
+    s.data = getbuf(c, a.data);
+    if (!s.data) return fail(c, GS4D_E_INVALID, "draw: no splat data buffer bound");
+    const size_t bytes = s.data->bytes;
+    if (a.quads) { s.nrec = bytes / 288; s.npre = std::min(s.nrec, a.instances); s.premult = 1; }
     else if (a.mode == GS4D_MODE_4D_SORTED) {
         if (!a.regen_order) {
-            ob = getbuf(c, a.order);
-            if (!ob) return fail(c, GS4D_E_INVALID, "draw: GS4D_MODE_4D_SORTED needs the sort-index buffer at slot 1");
-            if (ob->bytes < a.instances * 4) return fail(c, GS4D_E_INVALID, "draw: sort-index buffer smaller than the instance count");
-            order = (const uint32_t*)ob->d;
+            s.ob = getbuf(c, a.order);
+            if (!s.ob) return fail(c, GS4D_E_INVALID, "draw: GS4D_MODE_4D_SORTED needs the sort-index buffer at slot 1");
+            if (s.ob->bytes < a.instances * 4) return fail(c, GS4D_E_INVALID, "draw: sort-index buffer smaller than the instance count");
         }
-        nrec = data->bytes / 96; npre = nrec;
-    } else if (a.mode == GS4D_MODE_4D_DIRECT) { nrec = data->bytes / 96; npre = nrec < a.instances ? nrec : a.instances; }
-    else if (a.mode == GS4D_MODE_2D) { nrec = data->bytes / 48; npre = nrec < a.instances ? nrec : a.instances; }
+        s.nrec = s.npre = bytes / 96;
+    } else if (a.mode == GS4D_MODE_4D_DIRECT) { s.nrec = bytes / 96; s.npre = std::min(s.nrec, a.instances); }
+    else if (a.mode == GS4D_MODE_2D) { s.nrec = bytes / 48; s.npre = std::min(s.nrec, a.instances); }
     else return fail(c, GS4D_E_INVALID, "draw: mode does not match the draw call");
-    if (a.instances == 0 || nrec == 0) return GS4D_OK;
-    if (a.instances >= 0xFFFFFFFFull || nrec >= 0xFFFFFFFFull) return fail(c, GS4D_E_UNSUPPORTED, "draw: more than 2^32-1 instances");
+    s.empty = a.instances == 0 || s.nrec == 0;
+    if (!s.empty && (a.instances >= 0xFFFFFFFFull || s.nrec >= 0xFFFFFFFFull)) return fail(c, GS4D_E_UNSUPPORTED, "draw: more than 2^32-1 instances");
+    return GS4D_OK;
+}
 
-    HIPCHK(c, bin_scratch_reserve(L.s, L.bin, a.instances, (size_t)c->tiles_x * c->tiles_y));
-    bool v2 = a.v2 && tile_lists_plan(L.tl, (size_t)c->tiles_x * c->tiles_y, npre, c->slabs, a.keybits, a.key_span);
-    if (v2) { HIPCHK(c, tile_lists_reserve(L.s, L.tl, (size_t)c->tiles_x * c->tiles_y, npre)); preprocess = true; order = nullptr; }   // an unordered draw is always re-run from the projection
-    L.tl.staged = false; L.tl.scap = L.tl.bcap = 0; L.tl.box = BOX_NONE;
-    if (v2) {
-        // the statistics of a draw belong to a list geometry (buckets, segments, tiles, records, shard, data buffer): another one starts from scratch
-        uint64_t geom = 0xcbf29ce484222325ull;
-        for (uint64_t v : { (uint64_t)L.tl.nb, (uint64_t)L.tl.rows, (uint64_t)L.tl.seg, (uint64_t)c->tiles_x, (uint64_t)c->tiles_y, (uint64_t)npre, (uint64_t)a.shard_world, (uint64_t)a.shard_rank, (uint64_t)a.data })
-            geom = (geom ^ v) * 0x100000001b3ull;
-        const_cast<DrawArgs&>(a).stage_geom = geom;
-        if (c->stage_enable && c->stage_known && c->stage_geom == geom && !a.exact_lists && L.tl.seg <= (uint32_t)(STAGE_R * SEG_THREADS)) {
-            // margins: an eighth on the fullest segment and on the fullest bucket (the longest run is no capacity of anything any more: statistics only)
-            const uint64_t scap = ((uint64_t)c->stage_max_seg + c->stage_max_seg / 8 + 64 + 63) & ~63ull;
-            const uint64_t bcap = ((uint64_t)c->stage_max_bucket + c->stage_max_bucket / 8 + 512 + 63) & ~63ull;
-            if (scap <= STAGE_MAX_SCAP && bcap <= 32u * 512u && (uint64_t)L.tl.nb * bcap < 0xFFFFFFF0ull) {      // (k_bucket_tiles_staged: a thread holds at most 32 of its bucket's entries)
-                HIPCHK(c, tile_lists_reserve_blocks(L.s, L.tl, (size_t)L.tl.rows * scap));
-                L.tl.staged = true; L.tl.scap = (uint32_t)scap; L.tl.bcap = (uint32_t)bcap;
-                if (++L.tl.seq == 0u) L.tl.seq = 1u;
-                // the compositor's launch box: where the last staged draw had entries, stage_box_margin blocks (of 4 x 4 tiles) wider on every side
-                const uint32_t nbx = (uint32_t)(c->tiles_x + BOX_BLOCK - 1) / BOX_BLOCK, nby = (uint32_t)(c->tiles_y + BOX_BLOCK - 1) / BOX_BLOCK;
-                if (c->stage_box_enable && c->stage_box != BOX_NONE && c->stage_box != BOX_EMPTY && nbx <= 256u && nby <= 256u) {
-                    const uint32_t b = c->stage_box, m = c->stage_box_margin;
-                    L.tl.box = box_pack(box_x0(b) > m ? box_x0(b) - m : 0u, box_y0(b) > m ? box_y0(b) - m : 0u, std::min(box_x1(b) + m, nbx - 1u), std::min(box_y1(b) + m, nby - 1u));
-                }
-            }
+// the statistics of a draw belong to a list geometry (buckets, segments, tiles, records, shard, data buffer): another one starts from scratch
+uint64_t list_geometry(const gs4d_ctx* c, const TileLists& tl, const DrawArgs& a, size_t npre) {
+    uint64_t geom = 0xcbf29ce484222325ull;
+    for (uint64_t v : { (uint64_t)tl.nb, (uint64_t)tl.rows, (uint64_t)tl.seg, (uint64_t)c->tiles_x, (uint64_t)c->tiles_y, (uint64_t)npre, (uint64_t)a.shard_world, (uint64_t)a.shard_rank, (uint64_t)a.data })
+        geom = (geom ^ v) * 0x100000001b3ull;
+    return geom;
+}
+// Staged lists for an unordered draw whose geometry (a.stage_geom) has reported its statistics: capacities, blocks, sequence number and launch
+// box.  Leaves L.tl as it is (not staged) when the draw has to build exact lists.
+int plan_staged(gs4d_ctx* c, Lane& L, const DrawArgs& a) {
+    if (!(c->stage_enable && c->stage_known && c->stage_geom == a.stage_geom && !a.exact_lists && L.tl.seg <= (uint32_t)(STAGE_R * SEG_THREADS))) return GS4D_OK;
+    // margins: an eighth on the fullest segment and on the fullest bucket (the longest run is no capacity of anything any more: statistics only)
+    const uint64_t scap = ((uint64_t)c->stage_max_seg + c->stage_max_seg / 8 + 64 + 63) & ~63ull;
+    const uint64_t bcap = ((uint64_t)c->stage_max_bucket + c->stage_max_bucket / 8 + 512 + 63) & ~63ull;
+    if (!(scap <= STAGE_MAX_SCAP && bcap <= 32u * 512u && (uint64_t)L.tl.nb * bcap < 0xFFFFFFF0ull)) return GS4D_OK;      // (k_bucket_tiles_staged: a thread holds at most 32 of its bucket's entries)
+    HIPCHK(c, tile_lists_reserve_blocks(L.s, L.tl, (size_t)L.tl.rows * scap));
+    L.tl.staged = true; L.tl.scap = (uint32_t)scap; L.tl.bcap = (uint32_t)bcap;
+    if (++L.tl.seq == 0u) L.tl.seq = 1u;
+    // the compositor's launch box: where the last staged draw had entries, stage_box_margin blocks (of 4 x 4 tiles) wider on every side
+    const uint32_t nbx = (uint32_t)(c->tiles_x + BOX_BLOCK - 1) / BOX_BLOCK, nby = (uint32_t)(c->tiles_y + BOX_BLOCK - 1) / BOX_BLOCK;
+    if (c->stage_box_enable && c->stage_box != BOX_NONE && c->stage_box != BOX_EMPTY && nbx <= 256u && nby <= 256u) {
+        const uint32_t b = c->stage_box, m = c->stage_box_margin;
+        L.tl.box = box_pack(box_x0(b) > m ? box_x0(b) - m : 0u, box_y0(b) > m ? box_y0(b) - m : 0u, std::min(box_x1(b) + m, nbx - 1u), std::min(box_y1(b) + m, nby - 1u));
+    }
+    return GS4D_OK;
+}
+
+// The sort index of an ordered draw: `order` (in: the caller's, or null) is what the binning reads, `order_copy` where its emit kernel keeps a copy.
+int order_source(gs4d_ctx* c, Lane& L, const DrawArgs& a, bool regen, bool preprocess, const uint32_t*& order, uint32_t*& order_copy) {
+    if (!order && !regen) return GS4D_OK;
+    HIPCHK(c, grow_device_array(L.s, L.order_copy, L.order_cap, a.instances));
+    if (regen) order = L.order_copy;                   // filled by regenerate_order (first re-run) or by an earlier re-run of this draw
+    else if (preprocess) order_copy = L.order_copy;   // first run: the emit kernel reads the caller's buffer and keeps a copy
+    else order = L.order_copy;                         // re-run: the caller's buffer may have been overwritten since
+    return GS4D_OK;
+}
+// the key and index buffers of the queued key generation a fused draw executes, looked up once per run (null: deleted since)
+struct FusedBuffers { Buffer* keys = nullptr; Buffer* idx = nullptr; };
+// what the projection kernel does beside projecting: count or write the list entries (unordered: L.tl), generate depth keys and their histograms (fused)
+int fill_tile_count(gs4d_ctx* c, Lane& L, const DrawArgs& a, size_t npre, bool v2, const FusedBuffers& fused, TileCount& tc) {
+    if (v2 && L.tl.staged) { tc.stage_out = L.tl.blocks; tc.scap = L.tl.scap; tc.offs = L.tl.hist + L.tl.hist_cap; tc.abort_word = L.bin.total + TOT_ABORT; tc.seq = L.tl.seq; }
+    if (v2) { tc.sstat = L.tl.sstat; tc.hist = L.tl.hist; tc.skey = L.tl.skey; tc.nb = L.tl.nb; tc.seg = L.tl.seg; tc.rows = L.tl.rows; tc.tiles_x = c->tiles_x; tc.shard_rank = a.shard_rank; tc.shard_world = a.shard_world; tc.ks = a.blend_order.ks; }
+    if (a.fuse) {
+        tc.ks = a.blend_order.ks;
+        if (!fused.keys || !fused.idx) return fail(c, GS4D_E_INVALID, "draw: the key buffers of the queued key generation have been deleted");
+        hipError_t he = hipSuccess;
+        uint32_t* kh = sort_hist_slot(L.s, L.depth_sort, npre, &he);
+        if (!kh) return hipfail(c, he, "sort_hist_slot");
+        tc.keys_out = (float*)fused.keys->d; tc.idx_out = nullptr /* the depth sort that follows makes the identity index up */; tc.ghist = kh; tc.span = a.blend_order.span; tc.err = L.err_word();
+        L.depth_sort.hist_bias = a.blend_order.ks.bias;
+        tc.hist_rb = L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, npre, a.blend_order.bits);
+    }
+    return GS4D_OK;
+}
+
+// The projection of the draw's records into L.proj / L.trects, behind whoever wrote the data (and, on the ordered path, the sort index).
+int enqueue_projection(gs4d_ctx* c, Lane& L, const DrawArgs& a, const DrawShape& s, bool v2, const FusedBuffers& fused) {
+    Buffer* const data = s.data;
+    if (L.proj_cap < s.npre) {      // two arrays, one capacity: it stands only when both do
+        size_t pcap = L.proj_cap, tcap = L.proj_cap;
+        hipError_t e = grow_device_array(L.s, L.proj, pcap, s.npre, PROJ_FLOATS * 4);
+        if (e == hipSuccess) e = grow_device_array(L.s, L.trects, tcap, s.npre);
+        L.proj_cap = std::min(pcap, tcap);
+        if (e != hipSuccess) return hipfail(c, e, "grow_device_array(L.proj, L.trects)");
+    }
+    if (!a.quads && (a.mode == GS4D_MODE_4D_SORTED || a.mode == GS4D_MODE_4D_DIRECT)) { int rc = ensure_soa(c, *data); if (rc) return rc; }
+    { int rc = lane_access(c, *data, false); if (rc) return rc; data->rd_mask |= 1u << a.lane; }
+    if (s.ob && !v2) { int rc = lane_access(c, *s.ob, false); if (rc) return rc; s.ob->rd_mask |= 1u << a.lane; }
+    {
+        StageTimer t(c, GS4D_T_PREPROCESS);
+        const PreOut po = { L.proj, (v2 && L.tl.staged) ? nullptr : L.trects, has_aux(a.out) || a.zplane != 0 };
+        L.trects_in_order = false;
+        TileCount tc;
+        { int rc = fill_tile_count(c, L, a, s.npre, v2, fused, tc); if (rc) return rc; }
+        if (a.quads) HIPCHK(c, launch_preprocess_3d(L.s, (const float*)data->d, s.npre, a.u, c->W, c->H, po, tc));
+        else if (a.mode == GS4D_MODE_2D) HIPCHK(c, launch_preprocess_2d(L.s, (const float*)data->d, s.npre, a.u, c->W, c->H, po, tc));
+        else {
+            HIPCHK(c, launch_preprocess_4d(L.s, data->soa, data->soa_n, data->soa_info, s.npre, a.u, c->W, c->H, po, tc));
+            c->stat_shadow_bytes = data->soa_info.layout == SOA_STATIC3D ? 64 : data->soa_info.layout == SOA_SYM ? 72 : 96;
         }
     }
-    uint32_t* order_copy = nullptr;
-    const bool regen = a.regen_order && !v2 && a.mode == GS4D_MODE_4D_SORTED && !a.quads;
-    if (order || regen) {
-        if (L.order_cap < a.instances) {
-            HIPCHK(c, hipStreamSynchronize(L.s));
-            if (L.order_copy) (void)hipFree(L.order_copy);
-            L.order_copy = nullptr; L.order_cap = 0;
-            HIPCHK(c, hipMalloc(&L.order_copy, a.instances * 4));
-            L.order_cap = a.instances;
-        }
-        if (regen) order = L.order_copy;                   // filled below (first re-run) or by an earlier re-run of this draw
-        else if (preprocess) order_copy = L.order_copy;   // first run: the emit kernel reads the caller's buffer and keeps a copy
-        else order = L.order_copy;                         // re-run: the caller's buffer may have been overwritten since
-    }
-    if (preprocess) {
-        if (L.proj_cap < npre) {
-            HIPCHK(c, hipStreamSynchronize(L.s));
-            if (L.proj) (void)hipFree(L.proj);
-            if (L.trects) (void)hipFree(L.trects);
-            L.proj = nullptr; L.trects = nullptr; L.proj_cap = 0;
-            HIPCHK(c, hipMalloc(&L.proj, npre * 64)); HIPCHK(c, hipMalloc(&L.trects, npre * 4));
-            L.proj_cap = npre;
-        }
-        if (!a.quads && (a.mode == GS4D_MODE_4D_SORTED || a.mode == GS4D_MODE_4D_DIRECT)) { int rc = ensure_soa(c, *data); if (rc) return rc; }
-        { int rc = lane_access(c, *data, false); if (rc) return rc; data->rd_mask |= 1u << a.lane; }
-        if (ob && !v2) { int rc = lane_access(c, *ob, false); if (rc) return rc; ob->rd_mask |= 1u << a.lane; }
-        {
-            StageTimer t(c, GS4D_T_PREPROCESS);
-            const PreOut po = { L.proj, (v2 && L.tl.staged) ? nullptr : L.trects, has_aux(a.out) || a.zplane != 0 };
-            L.trects_in_order = false;
-            TileCount tc;
-            if (v2 && L.tl.staged) { tc.stage_out = L.tl.blocks; tc.scap = L.tl.scap; tc.offs = L.tl.hist + L.tl.hist_cap; tc.abort_word = L.bin.total + TOT_ABORT; tc.seq = L.tl.seq; }
-            if (v2) { tc.sstat = L.tl.sstat; tc.hist = L.tl.hist; tc.skey = L.tl.skey; tc.nb = L.tl.nb; tc.seg = L.tl.seg; tc.rows = L.tl.rows; tc.tiles_x = c->tiles_x; tc.shard_rank = a.shard_rank; tc.shard_world = a.shard_world; tc.ks = a.ks; }
-            if (a.fuse) {
-                tc.ks = a.ks;
-                Buffer* K = getbuf(c, a.fuse_keys); Buffer* I = getbuf(c, a.fuse_idx);
-                if (!K || !I) return fail(c, GS4D_E_INVALID, "draw: the key buffers of the queued key generation have been deleted");
-                hipError_t he = hipSuccess;
-                uint32_t* kh = sort_hist_slot(L.s, L.depth_sort, npre, &he);
-                if (!kh) return hipfail(c, he, "sort_hist_slot");
-                tc.keys_out = (float*)K->d; tc.idx_out = nullptr /* the depth sort below makes the identity index up */; (void)I; tc.ghist = kh; tc.span = a.fuse_span; tc.err = L.err_word();
-                L.depth_sort.hist_bias = a.ks.bias;
-                tc.hist_rb = L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, npre, fuse_bits);
-            }
-            if (a.quads) HIPCHK(c, launch_preprocess_3d(L.s, (const float*)data->d, npre, a.u, c->W, c->H, po, tc));
-            else if (a.mode == GS4D_MODE_2D) HIPCHK(c, launch_preprocess_2d(L.s, (const float*)data->d, npre, a.u, c->W, c->H, po, tc));
-            else {
-                HIPCHK(c, launch_preprocess_4d(L.s, data->soa, data->soa_n, data->soa_info, npre, a.u, c->W, c->H, po, tc));
-                c->stat_shadow_bytes = data->soa_info.layout == SOA_STATIC3D ? 64 : data->soa_info.layout == SOA_SYM ? 72 : 96;
-            }
-        }
-        L.proj_n = npre;
-        if (regen) {
-            // "records in ascending (depth key, record index)" — what the caller's index held when the draw was issued — from the key source
-            // the draw carries: k_keygen + the stable sort, into the lane's own buffers
-            if (L.regen_cap < npre) {
-                HIPCHK(c, hipStreamSynchronize(L.s));
-                if (L.regen_keys) (void)hipFree(L.regen_keys);
-                L.regen_keys = nullptr; L.regen_cap = 0;
-                HIPCHK(c, hipMalloc(&L.regen_keys, npre * 4));
-                L.regen_cap = npre;
-            }
-            hipError_t he = hipSuccess;
-            uint32_t* kh = sort_hist_slot(L.s, L.depth_sort, npre, &he);
-            if (!kh) return hipfail(c, he, "sort_hist_slot");
-            const float cam[3] = { a.ks.camx, a.ks.camy, a.ks.camz };
-            float view[16] = { 0 }; view[2] = a.ks.vr0; view[6] = a.ks.vr1; view[10] = a.ks.vr2; view[14] = a.ks.vr3;
-            L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, npre, a.keybits);
-            HIPCHK(c, launch_keygen(L.s, data->soa, soa_sig3(data->soa, data->soa_n, data->soa_info), data->soa_info, npre, a.ks.t, cam, view, a.ks.mode == KEYSRC_VIEWZ ? GS4D_KEY_VIEW_Z : GS4D_KEY_REF_INV_EUCLID,
-                                    (float*)L.regen_keys, L.order_copy, kh, L.depth_sort.hist_rb, a.ks.bias, 0xFFFFFFFFu, L.err_word()));
-            L.depth_sort.hist_bias = a.ks.bias;
-            HIPCHK(c, radix_sort_pairs(L.s, L.depth_sort, L.regen_keys, L.order_copy, npre, nullptr, a.keybits, true));
-        }
-        { int rc = fb_access(c, F); if (rc) return rc; }
-        if (a.fuse && !v2) {
-            // ordered path: the sort the application asked for runs here, between the projection (which wrote its keys and digit
-            // histograms) and the binning (which reads the sorted index)
-            Buffer* K = getbuf(c, a.fuse_keys); Buffer* I = getbuf(c, a.fuse_idx);
-            StageTimer t(c, GS4D_T_SORT);
-            HIPCHK(c, radix_sort_pairs(L.s, L.depth_sort, (uint32_t*)K->d, (uint32_t*)I->d, npre, nullptr, fuse_bits, true, true));
-        }
-    }
-    if (a.zplane) {
-        // the depth-test plane: read by the compositing kernel (first run and re-runs alike), so the lane waits for whoever wrote it, and a
-        // later write waits for this lane's tail event (the compositor runs after the draw's binning-done event)
-        Buffer* Z = getbuf(c, a.zplane);
-        if (!Z || Z->bytes < (size_t)c->W * c->H * 4) return fail(c, GS4D_E_INVALID, "draw: the depth-test plane holds fewer than width*height floats");
-        int rc = lane_access(c, *Z, false); if (rc) return rc;
-        Z->tail_mask |= 1u << a.lane;
-    }
+    L.proj_n = s.npre;
+    return GS4D_OK;
+}
+
+// "Records in ascending (depth key, record index)" — what the caller's index held when the draw was issued — from the order the draw
+// carries: k_keygen + the stable sort, into the lane's own buffers (DrawArgs::regen_order)
+int regenerate_order(gs4d_ctx* c, Lane& L, const DrawArgs& a, const Buffer& data, size_t npre) {
+    HIPCHK(c, grow_device_array(L.s, L.regen_keys, L.regen_cap, npre));
+    return enqueue_keygen_sort(c, L, data, npre, a.blend_order.ks, 0xFFFFFFFFu, a.blend_order.bits, L.regen_keys, L.order_copy, true, false);
+}
+// The depth sort a fused draw executes for the application, on the keys and digit histograms its projection left.  Ordered path: between projection
+// and binning, which reads the sorted index.  Unordered (`after_raster`): nothing in the draw waits for it; it fills the caller's buffers for the next reader.
+int enqueue_fused_sort(gs4d_ctx* c, Lane& L, const DrawArgs& a, const FusedBuffers& fused, size_t npre, bool after_raster) {
+    StageTimer t(c, GS4D_T_SORT);
+#ifdef GS4D_TUNING
+    static const bool skip_sort = getenv("GS4D_ABLATE_SORT") != nullptr;      // ablation (make TUNING=1): what the frame costs without its depth sort — an upper bound for any re-scheduling of it
+    if (after_raster && skip_sort) { L.depth_sort.hist_pending = false; L.depth_sort.flip ^= 1; return GS4D_OK; }
+#endif
+    HIPCHK(c, radix_sort_pairs(L.s, L.depth_sort, (uint32_t*)fused.keys->d, (uint32_t*)fused.idx->d, npre, nullptr, a.blend_order.bits, true, true));
+    return GS4D_OK;
+}
+
+// the depth-test plane: read by the compositing kernel (first run and re-runs alike), so the lane waits for whoever wrote it, and a
+// later write waits for this lane's tail event (the compositor runs after the draw's binning-done event)
+int order_depth_plane(gs4d_ctx* c, const DrawArgs& a) {
+    Buffer* Z = getbuf(c, a.zplane);
+    if (!Z || Z->bytes < (size_t)c->W * c->H * 4) return fail(c, GS4D_E_INVALID, "draw: the depth-test plane holds fewer than width*height floats");
+    int rc = lane_access(c, *Z, false); if (rc) return rc;
+    Z->tail_mask |= 1u << a.lane;
+    return GS4D_OK;
+}
+// entry storage for the draw: twice its instances, or one and a half times what the last draw needed, or the bucket regions of a staged draw
+int reserve_entries(gs4d_ctx* c, Lane& L, const DrawArgs& a, bool v2) {
     size_t want = a.instances * 2 + 65536;
     if (want < c->stat_entries + c->stat_entries / 2) want = c->stat_entries + c->stat_entries / 2;
     if (v2 && L.tl.staged && want < (size_t)L.tl.nb * L.tl.bcap) want = (size_t)L.tl.nb * L.tl.bcap;      // staged: the tile-ordered array holds a region of bcap entries per bucket
-    if (L.pair_cap < want) { int rc = ensure_pairs(c, L, want); if (rc) return rc; }
-    if (v2) {
-        int rc = enqueue_raster_v2(c, L, F, a, npre, premult);
-        if (rc == GS4D_OK && a.fuse) {
-            // the depth sort the application asked for: its keys and digit histograms came out of the projection kernel; nothing in this draw
-            // waits for it (the draw took its order from the keys), it fills the caller's buffers for whoever reads them next
-            Buffer* K = getbuf(c, a.fuse_keys); Buffer* I = getbuf(c, a.fuse_idx);
-            StageTimer t(c, GS4D_T_SORT);
-#ifdef GS4D_TUNING
-            static const bool skip_sort = getenv("GS4D_ABLATE_SORT") != nullptr;      // ablation (make TUNING=1): what the frame costs without its depth sort — an upper bound for any re-scheduling of it
-            if (skip_sort) { L.depth_sort.hist_pending = false; L.depth_sort.flip ^= 1; return rc; }
-#endif
-            HIPCHK(c, radix_sort_pairs(L.s, L.depth_sort, (uint32_t*)K->d, (uint32_t*)I->d, npre, nullptr, fuse_bits, true, true));
-        }
-        return rc;
+    return ensure_pairs(c, L, want);
+}
+
+// `preprocess` false: the re-run of a draw whose tile lists overflowed (projected records and the sort-index copy are still valid).  Sets a.stage_geom.
+int run_draw(gs4d_ctx* c, DrawArgs& a, bool preprocess) {
+    Lane& L = c->lanes[a.lane];
+    Framebuffer& F = c->fbs[a.fb];
+    const size_t ntiles = (size_t)c->tiles_x * c->tiles_y;
+    DrawShape s;
+    { int rc = draw_shape(c, a, s); if (rc || s.empty) return rc; }
+    HIPCHK(c, bin_scratch_reserve(L.s, L.bin, a.instances, ntiles));
+    const bool v2 = a.v2 && tile_lists_plan(L.tl, ntiles, s.npre, c->slabs, a.blend_order.bits, a.blend_order.span);
+    if (v2) { HIPCHK(c, tile_lists_reserve(L.s, L.tl, ntiles, s.npre)); preprocess = true; }   // an unordered draw is always re-run from the projection
+    L.tl.staged = false; L.tl.scap = L.tl.bcap = 0; L.tl.box = BOX_NONE;
+    if (v2) { a.stage_geom = list_geometry(c, L.tl, a, s.npre); int rc = plan_staged(c, L, a); if (rc) return rc; }
+    const bool regen = a.regen_order && !v2 && a.mode == GS4D_MODE_4D_SORTED && !a.quads;
+    const uint32_t* order = (s.ob && !v2) ? (const uint32_t*)s.ob->d : nullptr;      // (an unordered draw never reads its sort index)
+    uint32_t* order_copy = nullptr;
+    { int rc = order_source(c, L, a, regen, preprocess, order, order_copy); if (rc) return rc; }
+    const FusedBuffers fused = a.fuse ? FusedBuffers{ getbuf(c, a.fuse_keys), getbuf(c, a.fuse_idx) } : FusedBuffers{};
+    if (preprocess) {
+        { int rc = enqueue_projection(c, L, a, s, v2, fused); if (rc) return rc; }
+        if (regen) { int rc = regenerate_order(c, L, a, *s.data, s.npre); if (rc) return rc; }
+        { int rc = fb_access(c, F); if (rc) return rc; }
+        if (a.fuse && !v2) { int rc = enqueue_fused_sort(c, L, a, fused, s.npre, false); if (rc) return rc; }
     }
-    return enqueue_raster(c, L, F, a, order, order_copy, a.instances, npre, premult);
+    if (a.zplane) { int rc = order_depth_plane(c, a); if (rc) return rc; }
+    { int rc = reserve_entries(c, L, a, v2); if (rc) return rc; }
+    if (!v2) return enqueue_raster(c, L, F, a, order, order_copy, a.instances, s.npre, s.premult);
+    int rc = enqueue_raster_v2(c, L, F, a, s.npre, s.premult, fused.keys ? (const uint32_t*)fused.keys->d : nullptr);
+    if (rc == GS4D_OK && a.fuse) rc = enqueue_fused_sort(c, L, a, fused, s.npre, true);
+    return rc;
 }
 
 // What a draw's kernels left in the lane's host verdict words (HT_*, gs4d_internal.h), decoded once behind the lane's event.
@@ -711,20 +731,7 @@ int flush_order(gs4d_ctx* c) {
     Lane& L = c->lanes[po.lane];
     Buffer* D = getbuf(c, po.data); Buffer* K = getbuf(c, po.keys); Buffer* I = getbuf(c, po.idx);
     if (!D || !K || !I || !D->soa) return fail(c, GS4D_E_INVALID, "queued keygen: a buffer it names has been deleted");
-    {
-        hipError_t he = hipSuccess;
-        uint32_t* kh = sort_hist_slot(L.s, L.depth_sort, po.n, &he);
-        if (!kh) return hipfail(c, he, "sort_hist_slot");
-        StageTimer tm(c, GS4D_T_KEYGEN);
-        L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, po.n, span_bits(po.span));
-        HIPCHK(c, launch_keygen(L.s, D->soa, soa_sig3(D->soa, D->soa_n, D->soa_info), D->soa_info, po.n, po.t, po.cam, po.view, po.key_mode, (float*)K->d, (uint32_t*)I->d, kh, L.depth_sort.hist_rb, po.bias, po.span, L.err_word()));
-        L.depth_sort.hist_bias = po.bias;
-    }
-    if (po.sorted) {
-        StageTimer t(c, GS4D_T_SORT);
-        HIPCHK(c, radix_sort_pairs(L.s, L.depth_sort, (uint32_t*)K->d, (uint32_t*)I->d, po.n, nullptr, span_bits(po.span), true));
-    }
-    return GS4D_OK;
+    return enqueue_keygen_sort(c, L, *D, po.n, po.order.ks, po.order.span, po.order.bits, (uint32_t*)K->d, (uint32_t*)I->d, po.sorted, true);
 }
 
 int alloc_fbs(gs4d_ctx* c, int w, int h) {
@@ -748,9 +755,6 @@ int alloc_fbs(gs4d_ctx* c, int w, int h) {
     return GS4D_OK;
 }
 
-} // namespace
-
-namespace {
 // ---- frame-lane streams on hardware queues of their own ----
 // HIP maps streams onto a few hardware queues (four by default) in an order that depends on every stream the process has created so far;
 // two streams on one queue run their kernels one after the other.  Two frame lanes that share a queue do not overlap — measured: 0.110 ->
@@ -1097,14 +1101,14 @@ int gs4d_sort_pairs(gs4d_ctx* c, gs4d_buf keys, gs4d_buf vals, size_t n) {
         c->po.sorted = true;
         c->stat_depth_passes = (uint64_t)sort_plan_passes(Lq.depth_sort.hist_bits, sort_plan_rb(Lq.depth_sort, n, Lq.depth_sort.hist_bits));
         K->version++; V->version++;
-        V->prov_valid = true; V->prov_data = Lq.kg_data; V->prov_data_ver = Lq.kg_data_ver; V->prov_ver = V->version; V->prov_n = n; V->prov_bits = Lq.kg_bits; V->prov_ks = Lq.kg_ks; V->prov_span = Lq.kg_span;
+        V->sorted_by(true, Lq.keyed);                 // (n == po.n == keyed.n)
         return GS4D_OK;
     }
     { int rc = flush_order(c); if (rc) return rc; rc = next_frame_if_drawn(c); if (rc) return rc; }
     { int rc = lane_access(c, *K, true); if (rc) return rc; rc = lane_access(c, *V, true); if (rc) return rc; }
     Lane& L = lane(c);
     // k_keygen leaves the digit histograms of the keys it wrote: no histogram launch when this sort is of exactly those keys
-    const bool have_hist = L.depth_sort.hist_pending && keys == L.kg_buf && K->version == L.kg_ver && n == L.kg_n;
+    const bool have_hist = L.depth_sort.hist_pending && keys == L.kg_buf && K->version == L.kg_ver && n == L.keyed.n;
     const int key_bits = have_hist ? L.depth_sort.hist_bits : 32;
     c->stat_depth_passes = (uint64_t)sort_plan_passes(key_bits, have_hist ? L.depth_sort.hist_rb : sort_plan_rb(L.depth_sort, n, key_bits));
     // ... and when the payload is the identity index the same call wrote, the sorted payload is "the records in ascending (key, index)"
@@ -1112,8 +1116,7 @@ int gs4d_sort_pairs(gs4d_ctx* c, gs4d_buf keys, gs4d_buf vals, size_t n) {
     StageTimer t(c, GS4D_T_SORT);
     HIPCHK(c, radix_sort_pairs(L.s, L.depth_sort, (uint32_t*)K->d, (uint32_t*)V->d, n, nullptr, key_bits, have_hist));
     K->version++; V->version++;
-    V->prov_valid = identity_payload;
-    if (identity_payload) { V->prov_data = L.kg_data; V->prov_data_ver = L.kg_data_ver; V->prov_ver = V->version; V->prov_n = n; V->prov_bits = L.kg_bits; V->prov_ks = L.kg_ks; V->prov_span = L.kg_span; }
+    V->sorted_by(identity_payload, L.keyed);          // (have_hist: n == keyed.n)
     return GS4D_OK;
 }
 
@@ -1182,17 +1185,16 @@ int gs4d_keygen(gs4d_ctx* c, gs4d_buf data, float t, const float cam[3], gs4d_bu
     }
     // Not launched yet (see gs4d_ctx::po): everything the launch needs is recorded, everything a later call may ask about the buffers
     // (versions, what the index will have been sorted by) is settled now.
-    c->po.keygen = true; c->po.sorted = false; c->po.lane = c->cur; c->po.data = data; c->po.keys = keys; c->po.idx = idx; c->po.n = n; c->po.t = t;
-    c->po.cam[0] = cam[0]; c->po.cam[1] = cam[1]; c->po.cam[2] = cam[2]; c->po.key_mode = key_mode; c->po.bias = bias; c->po.span = span;
-    memcpy(c->po.view, c->u.view, sizeof c->po.view);
-    L.depth_sort.hist_bits = span_bits(span);
+    BlendOrder bo;                                                  // the one place that builds an order from the call's arguments
+    bo.ks.mode = key_mode == GS4D_KEY_REF_INV_EUCLID ? KEYSRC_REF : KEYSRC_VIEWZ;
+    bo.ks.t = t; bo.ks.camx = cam[0]; bo.ks.camy = cam[1]; bo.ks.camz = cam[2];
+    bo.ks.vr0 = c->u.view[2]; bo.ks.vr1 = c->u.view[6]; bo.ks.vr2 = c->u.view[10]; bo.ks.vr3 = c->u.view[14];
+    bo.ks.bias = bias; bo.span = span; bo.bits = span_bits(span);
+    c->po.keygen = true; c->po.sorted = false; c->po.lane = c->cur; c->po.data = data; c->po.keys = keys; c->po.idx = idx; c->po.n = n; c->po.order = bo;
+    L.depth_sort.hist_bits = bo.bits;
     K->version++; I->version++;
-    L.kg_buf = keys; L.kg_ver = K->version; L.kg_n = n;
-    L.kg_idx = idx; L.kg_idx_ver = I->version; L.kg_data = data; L.kg_data_ver = D->version; L.kg_bits = L.depth_sort.hist_bits; L.kg_span = span;
-    L.kg_ks.mode = key_mode == GS4D_KEY_REF_INV_EUCLID ? KEYSRC_REF : KEYSRC_VIEWZ;
-    L.kg_ks.t = t; L.kg_ks.camx = cam[0]; L.kg_ks.camy = cam[1]; L.kg_ks.camz = cam[2];
-    L.kg_ks.vr0 = c->u.view[2]; L.kg_ks.vr1 = c->u.view[6]; L.kg_ks.vr2 = c->u.view[10]; L.kg_ks.vr3 = c->u.view[14];
-    L.kg_ks.bias = bias;
+    L.kg_buf = keys; L.kg_ver = K->version; L.kg_idx = idx; L.kg_idx_ver = I->version;
+    L.keyed = SortedBy{ bo, data, D->version, n };
     if (!c->defer_order) return flush_order(c);
     return GS4D_OK;
 }
@@ -1241,13 +1243,13 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
         size_t nkeys = 0;
         if (data && (a.quads || a.mode == GS4D_MODE_4D_DIRECT || a.mode == GS4D_MODE_2D)) {
             nkeys = std::min(a.instances, data->bytes / (a.quads ? 288 : a.mode == GS4D_MODE_2D ? 48 : 96));
-            a.ks = KeySrc(); a.keybits = 1; while (a.keybits < 32 && ((size_t)1 << a.keybits) < nkeys) ++a.keybits;
-            a.key_span = nkeys ? (uint32_t)(nkeys - 1) : 0u;
+            int keybits = 1; while (keybits < 32 && ((size_t)1 << keybits) < nkeys) ++keybits;
+            a.blend_order = BlendOrder{ KeySrc(), keybits, nkeys ? (uint32_t)(nkeys - 1) : 0u };      // KEYSRC_INDEX: key = instance
             ok = nkeys > 0;
         } else if (data && a.mode == GS4D_MODE_4D_SORTED) {
             const Buffer* ob = getbuf(c, a.order);
-            if (ob && ob->prov_valid && ob->version == ob->prov_ver && a.data == ob->prov_data && data->version == ob->prov_data_ver && a.instances == ob->prov_n && data->bytes / 96 == ob->prov_n) {
-                a.ks = ob->prov_ks; a.keybits = ob->prov_bits; a.key_span = ob->prov_span; ok = true;
+            if (ob && ob->prov_valid && ob->version == ob->prov_ver && a.data == ob->prov.data && data->version == ob->prov.data_ver && a.instances == ob->prov.n && data->bytes / 96 == ob->prov.n) {
+                a.blend_order = ob->prov.order; ok = true;
             }
         }
         if (ok && (nkeys > V2_MAX_RECORDS || (a.mode == GS4D_MODE_4D_SORTED && a.instances > V2_MAX_RECORDS) || (size_t)c->tiles_x * c->tiles_y > 256u * 1024u)) ok = false;   // tilelist.hip's entry format
@@ -1265,11 +1267,11 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
         const Buffer* pd = getbuf(c, a.data);
         bool mine = a.mode == GS4D_MODE_4D_SORTED && !a.quads && c->po.sorted && c->po.idx == a.order && c->po.data == a.data && c->po.lane == c->cur
                  && pd && a.instances == c->po.n && pd->bytes / 96 == c->po.n;
-        if (mine && a.v2 && !tile_lists_plan(lane(c).tl, (size_t)c->tiles_x * c->tiles_y, a.instances, c->slabs, a.keybits, a.key_span)) a.v2 = false;
+        if (mine && a.v2 && !tile_lists_plan(lane(c).tl, (size_t)c->tiles_x * c->tiles_y, a.instances, c->slabs, a.blend_order.bits, a.blend_order.span)) a.v2 = false;
         if (mine) {
             // on the ordered path too: the projection writes the keys, the sort follows it, the binning reads the sorted index
-            if (!a.v2) { a.ks = lane(c).kg_ks; a.keybits = lane(c).kg_bits; a.key_span = lane(c).kg_span; }
-            a.fuse = true; a.fuse_keys = c->po.keys; a.fuse_idx = c->po.idx; a.fuse_span = c->po.span; c->po.keygen = c->po.sorted = false; c->stat_fused++;
+            if (!a.v2) a.blend_order = lane(c).keyed.order;      // (a.v2: the same record, through the index's provenance)
+            a.fuse = true; a.fuse_keys = c->po.keys; a.fuse_idx = c->po.idx; c->po.keygen = c->po.sorted = false; c->stat_fused++;
         }
         else { int rc2 = flush_order(c); if (rc2) return rc2; }
     }
@@ -1321,13 +1323,7 @@ int gs4d_draw_lines(gs4d_ctx* c, const float* verts, size_t nverts, int dims, in
         HIPCHK(c, hipMemsetAsync(F.linecnt, 0, (size_t)c->W * c->H * 4, L.s));
     }
     const size_t floats = nverts * (size_t)dims;
-    if (L.line_cap < floats) {
-        HIPCHK(c, hipStreamSynchronize(L.s));
-        if (L.line_verts) (void)hipFree(L.line_verts);
-        L.line_verts = nullptr; L.line_cap = 0;
-        HIPCHK(c, hipMalloc(&L.line_verts, std::max<size_t>(floats, 4096) * 4));
-        L.line_cap = std::max<size_t>(floats, 4096);
-    }
+    if (L.line_cap < floats) HIPCHK(c, grow_device_array(L.s, L.line_verts, L.line_cap, std::max<size_t>(floats, 4096)));
     HIPCHK(c, hipMemcpyAsync(L.line_verts, verts, floats * 4, hipMemcpyHostToDevice, L.s));     // the caller's array is reusable on return (pageable source)
     LineParams p;
     for (int i = 0; i < 16; ++i) p.vp[i] = viewproj ? viewproj[i] : (i % 5 == 0 ? 1.0f : 0.0f);

@@ -127,8 +127,21 @@ hipError_t lds_atomic_order_selftest(const hipStream_t* streams, int nstreams, b
 enum { SOA_FULL = 0, SOA_SYM = 1, SOA_STATIC3D = 2 };
 struct SoaInfo { int layout = SOA_FULL; float consts[8] = { 0 }; };      // consts: pos.w, sig[0][3], sig[1][3], sig[2][3], sig[3][0..3] of a static set
 // sig3 == nullptr: a static set (SOA_STATIC3D) — mu_t and sig[3] are info.consts for every record
-hipError_t launch_keygen(hipStream_t st, const float4* pos, const float4* sig3, const SoaInfo& info, size_t n, float t, const float cam[3], const float view[16], int key_mode, float* keys, uint32_t* idx, uint32_t* ghist, int rb,
-                         uint32_t bias, uint32_t span, uint32_t* err);
+// ks: what the keys are computed from (KEYSRC_REF / KEYSRC_VIEWZ, below); span: what k_keygen checks (key - ks.bias) against
+struct KeySrc;
+hipError_t launch_keygen(hipStream_t st, const float4* pos, const float4* sig3, const SoaInfo& info, size_t n, const KeySrc& ks, float* keys, uint32_t* idx, uint32_t* ghist, int rb, uint32_t span, uint32_t* err);
+
+// A grow-only device array used by kernels queued on `st`: nothing when `cap` elements suffice; else the stream is waited for, the old block freed
+// and one of `want` elements allocated.  After a failed allocation pointer and capacity are null / zero.
+template <class T> inline hipError_t grow_device_array(hipStream_t st, T*& p, size_t& cap, size_t want, size_t elem_bytes = sizeof(T)) {
+    if (cap >= want) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(st); if (e != hipSuccess) return e;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    if ((e = hipMalloc(&p, want * elem_bytes)) != hipSuccess) { p = nullptr; return e; }
+    cap = want;
+    return hipSuccess;
+}
 
 // ---- digit histograms for the radix sort, accumulated by whichever kernel produces the keys ----
 constexpr int OS_MAX_PASSES = 4;
@@ -189,6 +202,12 @@ struct KeySrc {
     float vr0 = 0, vr1 = 0, vr2 = 0, vr3 = 0;   // view row 2 at keygen time (KEYSRC_VIEWZ)
     uint32_t bias = 0;                           // subtracted from the key's bit pattern (host-proven lower bound, as in the depth sort)
 };
+// A blend order and how wide its keys are: span = the host-proven largest (key - ks.bias), which the depth slabs divide evenly; bits = its width.
+// gs4d_keygen builds it (KEYSRC_INDEX: draw_common); the queued launch, the lane, the sort index and the draw hold copies of the whole record.
+struct BlendOrder { KeySrc ks; int bits = 32; uint32_t span = 0xFFFFFFFFu; };
+// "The n records of buffer `data` at version data_ver, in that order": what a lane's last gs4d_keygen keyed, and what a sort index holds once
+// gs4d_sort_pairs has sorted exactly those keys with their identity index.
+struct SortedBy { BlendOrder order; gs4d_buf data = 0; uint64_t data_ver = 0; size_t n = 0; };
 struct TileCount {                               // hist == nullptr: the ordered path (no counting in the projection kernel)
     uint32_t* hist = nullptr;                    // [nb][rows]: entries that the records of segment `row` put into bucket b = tile % nb
     uint32_t rows = 0;

@@ -64,12 +64,12 @@ __global__ __launch_bounds__(256) void k_keygen(const float4* __restrict__ pos, 
     os_hist_flush(h, ghist, OS_MAX_PASSES, threadIdx.x);
 }
 
-hipError_t launch_keygen(hipStream_t st, const float4* pos, const float4* sig3, const SoaInfo& info, size_t n, float t, const float cam[3], const float view[16], int key_mode, float* keys, uint32_t* idx, uint32_t* ghist, int rb,
-                         uint32_t bias, uint32_t span, uint32_t* err) {
+hipError_t launch_keygen(hipStream_t st, const float4* pos, const float4* sig3, const SoaInfo& info, size_t n, const KeySrc& ks, float* keys, uint32_t* idx, uint32_t* ghist, int rb, uint32_t span, uint32_t* err) {
     if (n == 0) return hipSuccess;
-    float4 vr = make_float4(view[2], view[6], view[10], view[14]);
+    const float4 vr = make_float4(ks.vr0, ks.vr1, ks.vr2, ks.vr3);
+    const int key_mode = ks.mode == KEYSRC_VIEWZ ? GS4D_KEY_VIEW_Z : GS4D_KEY_REF_INV_EUCLID;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 1024);     // grid-stride: bounds the histogram flush to 1024 workgroups
-    k_keygen<<<dim3(blocks), dim3(256), 0, st>>>(pos, sig3, (uint32_t)n, t, cam[0], cam[1], cam[2], vr, key_mode, keys, idx, ghist, rb, bias, span, err,
+    k_keygen<<<dim3(blocks), dim3(256), 0, st>>>(pos, sig3, (uint32_t)n, ks.t, ks.camx, ks.camy, ks.camz, vr, key_mode, keys, idx, ghist, rb, ks.bias, span, err,
                                                      make_float4(info.consts[4], info.consts[5], info.consts[6], info.consts[7]), info.consts[0]);
     return hipGetLastError();
 }
@@ -537,17 +537,15 @@ hipError_t lds_atomic_order_selftest(const hipStream_t* streams, int nstreams, b
 hipError_t sort_scratch_reserve(hipStream_t st, SortScratch& s, size_t n) {
     hipError_t e;
     if (s.cap < n) {
-        if (s.keys2) { (void)hipStreamSynchronize(st); (void)hipFree(s.keys2); }
-        s.keys2 = s.vals2 = nullptr; s.cap = 0;
-        if ((e = hipMalloc(&s.keys2, n * 16)) != hipSuccess) return e;        // scratch B and C, keys and values
-        s.vals2 = s.keys2 + 2 * n;
-        s.cap = n;
+        e = grow_device_array(st, s.keys2, s.cap, n, 16);        // scratch B and C, keys and values
+        s.vals2 = s.keys2 ? s.keys2 + 2 * s.cap : nullptr;
+        if (e != hipSuccess) return e;
     }
     // control block: two [OS_REPL][4][OS_MAX_BINS] histogram slots (alternating), then the look-back words [tiles + groups][bins], sized for the widest digit
     const size_t tiles = (s.cap + 1023) / 1024;      // smallest tile = 1024 keys; sized for the largest sort seen (the layout depends on it)
     const size_t groups = tiles / OS_GROUP + 2, supers = groups / OS_SUPER + 2;
     const size_t words = 2 * OS_SLOT_WORDS + (tiles + 2 + 2 * 2 * (groups + supers)) * OS_MAX_BINS;       // tile words, two accumulator sets
-    if (s.hist_cap < words) {
+    if (s.hist_cap < words) {      // (not grow_device_array: the new block is filled from the old one before that is let go)
         uint32_t* nh = nullptr;
         if ((e = hipMalloc(&nh, words * 4)) != hipSuccess) return e;
         if ((e = hipMemsetAsync(nh, 0, words * 4, st)) != hipSuccess) return e;

@@ -403,13 +403,8 @@ bool tile_lists_plan(TileLists& t, size_t ntiles, size_t nrecords, uint32_t slab
 hipError_t tile_lists_reserve(hipStream_t st, TileLists& t, size_t ntiles, size_t nrecords) {
     hipError_t e;
     const size_t hist_words = (size_t)t.rows * t.nb;
-    if (t.hist_cap < hist_words) {
-        if (t.hist) { (void)hipStreamSynchronize(st); (void)hipFree(t.hist); }
-        t.hist = nullptr; t.hist_cap = 0;
-        if ((e = hipMalloc(&t.hist, hist_words * 8)) != hipSuccess) return e;      // [nb][rows] counts, then [rows][nb] run slots
-        t.hist_cap = hist_words;
-    }
-    if (t.tiles_cap < ntiles || t.nb_cap < t.nb || t.slabs_cap < t.slabs) {
+    if ((e = grow_device_array(st, t.hist, t.hist_cap, hist_words, 8)) != hipSuccess) return e;      // [nb][rows] counts, then [rows][nb] run slots
+    if (t.tiles_cap < ntiles || t.nb_cap < t.nb || t.slabs_cap < t.slabs) {      // (not grow_device_array: six arrays carved out of one block, three capacities)
         if (t.bbase) { (void)hipStreamSynchronize(st); (void)hipFree(t.bbase); }
         t.bbase = t.btot = t.tstart = t.tcnt = nullptr; t.bstat = nullptr; t.sstat = nullptr;
         const size_t nt = std::max(ntiles, t.tiles_cap), nbc = std::max<size_t>(t.nb, t.nb_cap), sc = std::max<size_t>(std::max<size_t>(t.slabs, t.slabs_cap), 4);
@@ -420,24 +415,10 @@ hipError_t tile_lists_reserve(hipStream_t st, TileLists& t, size_t ntiles, size_
         if ((e = hipMemsetAsync(t.bstat, 0, nbc * 16 + 1024 * 4, st)) != hipSuccess) return e;
         t.tiles_cap = nt; t.nb_cap = nbc; t.slabs_cap = sc;
     }
-    if (t.skey_cap < nrecords) {
-        if (t.skey) { (void)hipStreamSynchronize(st); (void)hipFree(t.skey); }
-        t.skey = nullptr; t.skey_cap = 0;
-        if ((e = hipMalloc(&t.skey, nrecords * 4)) != hipSuccess) return e;
-        t.skey_cap = nrecords;
-    }
-    return hipSuccess;
+    return grow_device_array(st, t.skey, t.skey_cap, nrecords);
 }
 
-hipError_t tile_lists_reserve_blocks(hipStream_t st, TileLists& t, size_t entries) {
-    if (t.blocks_cap >= entries) return hipSuccess;
-    if (t.blocks) { (void)hipStreamSynchronize(st); (void)hipFree(t.blocks); }
-    t.blocks = nullptr; t.blocks_cap = 0;
-    hipError_t e = hipMalloc(&t.blocks, entries * 8);
-    if (e != hipSuccess) return e;
-    t.blocks_cap = entries;
-    return hipSuccess;
-}
+hipError_t tile_lists_reserve_blocks(hipStream_t st, TileLists& t, size_t entries) { return grow_device_array(st, t.blocks, t.blocks_cap, entries); }
 
 void tile_lists_free(TileLists& t) {
     if (t.blocks) (void)hipFree(t.blocks);
