@@ -81,6 +81,7 @@ def _load():
         "gs4d_read_ids": (i32, [vp, i32, i32, i32, i32, vp, vp, vp]),
         "gs4d_read_ids_device": (i32, [vp, vp, vp, vp, sz]),
         "gs4d_set_depth_test": (i32, [vp, u32]),
+        "gs4d_set_record_stats": (i32, [vp, u32, sz]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -539,6 +540,23 @@ class Context:
         (depth_plane); None or 0 turns the test off.  Draw state: it survives clear(); deleting the buffer turns it off."""
         self._chk(_lib.gs4d_set_depth_test(self._h, int(plane or 0)))
 
+    # record statistics: what each record contributed to the picture (DESIGN.md §4)
+    RECORD_STAT = np.dtype([("pixels", "<u4"), ("wmax", "<f4"), ("wsum", "<u8")])
+
+    def record_stats(self, n):
+        """A zeroed buffer of n gs4d_record_stat for set_record_stats."""
+        return self.buffer(np.zeros(n, self.RECORD_STAT))
+
+    def set_record_stats(self, buf, n=0):
+        """Draws issued from now on add, per record, the fragments that entered the colour with weight w > 0 (pixels), the largest such w
+        (wmax) and the sum of rint(w * 2^24) (wsum) into `buf` (record_stats); None or 0 turns it off.  Draw state: it survives clear();
+        nothing zeroes the buffer (subdata zeros to start a new count); deleting it turns the statistics off."""
+        self._chk(_lib.gs4d_set_record_stats(self._h, int(buf or 0), int(n) if buf else 0))
+
+    def read_record_stats(self, buf, n):
+        """Structured array (pixels uint32, wmax float32, wsum uint64) of the first n records, after every draw issued so far."""
+        return self.read(buf, self.RECORD_STAT, n)
+
     def set_tile_shard(self, rank, world):
         """Single-frame sharding: this context bins and composites the tile rows ty % world == rank only."""
         self._chk(_lib.gs4d_set_tile_shard(self._h, rank, world))
@@ -592,6 +610,11 @@ class Context:
         out = np.empty((n, 16), np.float32)
         self._chk(_lib.gs4d_debug_read_projected(self._h, _ptr(out), n))
         return out
+
+
+def record_weight_sum(stats):
+    """wsum of read_record_stats in weight units (float64): the summed weight with which each record entered the colour."""
+    return np.asarray(stats["wsum"], np.uint64).astype(np.float64) * 2.0 ** -24
 
 
 def version():

@@ -100,21 +100,21 @@ hipError_t launch_pack_rgba8_band(hipStream_t st, const float4* fb, const uint32
 }
 
 // OUT: the outputs of the image's frame (Outputs, gs4d_internal.h); aux, ids: their planes.  ZTEST: the draw has a depth test against the
-// W x H plane zplane (Target::z).
-template <bool PREMULT_C, bool GENERAL, Outputs OUT, bool ZTEST>
+// W x H plane zplane (Target::z).  STATS: the draw adds its record statistics to so (Target::stats).
+template <bool PREMULT_C, bool GENERAL, Outputs OUT, bool ZTEST, bool STATS = false>
 __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ proj, const uint32_t* __restrict__ pair_vals, uint32_t* __restrict__ ranges,
                                                   const uint32_t* __restrict__ total, int tiles_x, int W, int H, uint32_t* __restrict__ tstate, uint32_t epoch, float4 clear,
                                                   float4* __restrict__ fb, int dbg_arg, BlendFn bf, float2* __restrict__ aux, uint32_t* __restrict__ ids, uint32_t draw_ord,
-                                                  const float* __restrict__ zplane) {
+                                                  const float* __restrict__ zplane, StatOut so) {
     static_assert(!GENERAL || (OUT == Outputs::Colour && !ZTEST), "aux and ID outputs and the depth test are defined for the default blend function only");
 #ifdef GS4D_TUNING
     const int dbg = dbg_arg;             // GS4D_COMPOSITE_DBG: tuning builds only (make TUNING=1)
 #else
     constexpr int dbg = 0; (void)dbg_arg;
 #endif
-    __shared__ float4 sh_stage[stage_words(OUT, ZTEST) / 4];
+    __shared__ float4 sh_stage[stage_words(OUT, ZTEST, STATS) / 4];
     __shared__ uint32_t pmask[64 * 2];
-    const Stage<OUT, ZTEST> stage(sh_stage);
+    const Stage<OUT, ZTEST, STATS> stage(sh_stage);
     if (total[TOT_FLAGS]) return;                           // any flag (VF_CAPACITY on this path) — tile lists overflowed: nothing was emitted, the host re-runs
     uint32_t tile;
     if (!composite_tile(blockIdx.x, tiles_x, (H + TILE - 1) / TILE, tile)) return;        // uniform: padding of the XCD-aware grid
@@ -145,11 +145,12 @@ __global__ __launch_bounds__(64) void k_composite(const float4* __restrict__ pro
     }
     // the lane's pixel's depth-test value, loaded once per tile (a lane outside the image tests against +inf: its result is never stored)
     const float z = (ZTEST && px < W && py < H) ? zplane[(size_t)py * W + px] : __builtin_inff();
+    if constexpr (STATS) { stage.so = so; stage.inimg = px < W && py < H; }
     for (uint32_t hi = end; hi > start;) {
         const uint32_t cnt = min(64u, hi - start);
         // lane s holds list entry hi-1-s : s = 0 is the LAST (front-most) entry of this chunk
         const uint32_t rec = lane < cnt ? pair_vals[hi - 1u - lane] : 0u;
-        composite_chunk<PREMULT_C, GENERAL, OUT, ZTEST>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, acc, bf, z);
+        composite_chunk<PREMULT_C, GENERAL, OUT, ZTEST, STATS>(proj, rec, cnt, lane, tx0, ty0, fx, fy, stage, pmask, dbg, acc, bf, z);
         hi -= cnt;
         if (__ballot(acc.T > 0.0f) == 0ull) break;          // exact: every remaining contribution is multiplied by T == 0
     }
@@ -172,9 +173,15 @@ hipError_t launch_composite(hipStream_t st, const float4* proj, const uint32_t* 
     const BlendFn bf{ blend_src, blend_dst };
     const bool general = !(blend_src == GS4D_SRC_ALPHA && blend_dst == GS4D_ONE_MINUS_SRC_ALPHA);
     if (general && (t.out != Outputs::Colour || t.z)) return hipErrorInvalidValue;       // the host refuses such a draw (GS4D_E_UNSUPPORTED) before it gets here
+    if (t.stats.rec) {                                                                   // record statistics: default function, colour only, no depth test (the host refuses the rest too)
+        if (general || t.out != Outputs::Colour || t.z) return hipErrorInvalidValue;
+        if (premult_c) k_composite<true, false, Outputs::Colour, false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, nullptr, nullptr, draw_ord, nullptr, t.stats);
+        else k_composite<false, false, Outputs::Colour, false, true><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, nullptr, nullptr, draw_ord, nullptr, t.stats);
+        return hipGetLastError();
+    }
     for_outputs(premult_c != 0, t.out, t.z != nullptr, [&](auto pc, auto out, auto zt) {
-        if (general) k_composite<pc(), true, Outputs::Colour, false><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, nullptr, nullptr, 0u, nullptr);
-        else k_composite<pc(), false, out(), zt()><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, t.aux, t.ids, draw_ord, t.z);
+        if (general) k_composite<pc(), true, Outputs::Colour, false><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, nullptr, nullptr, 0u, nullptr, StatOut{});
+        else k_composite<pc(), false, out(), zt()><<<grid, dim3(64), 0, st>>>(proj, pair_vals, ranges, total, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, dbg, bf, t.aux, t.ids, draw_ord, t.z, StatOut{});
     });
     return hipGetLastError();
 }

@@ -73,21 +73,21 @@ struct WaveSort {
 };
 
 // OUT: the outputs of the image's frame (Outputs, gs4d_internal.h); aux, ids: their planes; draw_ord: the draw's ordinal within its frame.
-// ZTEST: the draw has a depth test against the W x H plane zplane (Target::z).
-template <bool PREMULT_C, int PER, Outputs OUT, bool ZTEST>
+// ZTEST: the draw has a depth test against the W x H plane zplane (Target::z).  STATS: the draw adds its record statistics to so (Target::stats).
+template <bool PREMULT_C, int PER, Outputs OUT, bool ZTEST, bool STATS = false>
 __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ proj, const uint2* __restrict__ entries, const uint32_t* __restrict__ tstart, const uint32_t* __restrict__ tcnt,
                                                      const uint32_t* __restrict__ total, uint32_t* __restrict__ total_host, int tiles_x, int W, int H, uint32_t* __restrict__ tstate, uint32_t epoch, float4 clear,
                                                      float4* __restrict__ fb, int key_passes, int rec_passes, uint32_t slabs,
                                                      const uint4* __restrict__ bstat, uint32_t nb, const uint32_t* __restrict__ sstat, uint32_t rows, uint32_t stage_seq, uint32_t rcap, uint32_t scap, uint32_t bcap,
                                                      TileBox box, uint32_t box_blocks, unsigned long long* __restrict__ stamps, float2* __restrict__ aux, uint32_t* __restrict__ ids, uint32_t draw_ord,
-                                                     const float* __restrict__ zplane) {
+                                                     const float* __restrict__ zplane, StatOut so) {
     // the sort's key plane and the blend's staging never live at the same time: one piece of LDS serves both
-    constexpr int SHARED_WORDS = 64 * PER > stage_words(OUT, ZTEST) ? 64 * PER : stage_words(OUT, ZTEST);
+    constexpr int SHARED_WORDS = 64 * PER > stage_words(OUT, ZTEST, STATS) ? 64 * PER : stage_words(OUT, ZTEST, STATS);
     __shared__ __attribute__((aligned(16))) uint32_t sh_a[SHARED_WORDS];
     __shared__ uint32_t pmask[64 * 2];
     __shared__ __attribute__((aligned(16))) uint32_t cnt[WS_BINS];
     __shared__ uint32_t er[64 * PER];
-    const Stage<OUT, ZTEST> stage(reinterpret_cast<float4*>(sh_a));
+    const Stage<OUT, ZTEST, STATS> stage(reinterpret_cast<float4*>(sh_a));
     uint32_t* ek = sh_a;
     uint32_t tile;
     const bool real = composite_tile(blockIdx.x, tiles_x, box, tile);     // false: padding of the XCD-aware grid
@@ -141,6 +141,7 @@ __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ 
     const bool fb_is_clear = tstate_word != epoch;          // uniform: the tile's pixels are not in memory yet
     // the lane's pixel's depth-test value, loaded once per tile (a lane outside the image tests against +inf: its result is never stored)
     const float z = (ZTEST && px < W && py < H) ? zplane[(size_t)py * W + px] : __builtin_inff();
+    if constexpr (STATS) { stage.so = so; stage.inimg = px < W && py < H; }
     for (int sb = (int)slabs - 1; sb >= 0; --sb) {
         const uint32_t start = __shfl(my_start, sb, 64);
         const uint32_t E = min((uint32_t)__shfl(my_cnt, sb, 64), (uint32_t)(64 * PER));         // k_bucket_tiles guarantees the bound; min() keeps a broken promise inside LDS
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(64) void k_composite_v2(const float4* __restrict__ 
         for (uint32_t hi = E; hi > 0u;) {
             const uint32_t c = min(64u, hi);
             const uint32_t rec = lane < c ? er[hi - 1u - lane] : 0u;       // lane s holds list entry hi-1-s : s = 0 is the front-most of the chunk
-            composite_chunk<PREMULT_C, false, OUT, ZTEST>(proj, rec, c, lane, tx0, ty0, fx, fy, stage, pmask, 0, acc, BlendFn{ 0, 0 }, z);
+            composite_chunk<PREMULT_C, false, OUT, ZTEST, STATS>(proj, rec, c, lane, tx0, ty0, fx, fy, stage, pmask, 0, acc, BlendFn{ 0, 0 }, z);
             hi -= c;
             if (__ballot(acc.T > 0.0f) == 0ull) break;      // exact: every remaining contribution is multiplied by T == 0
         }
@@ -218,8 +219,12 @@ hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* 
     const bool stamp_now = stampf && ++calls == stamp_call;
     if (stamp_now && (hipMalloc(&stamps, (size_t)grid.x * 48) != hipSuccess || hipMemsetAsync(stamps, 0, (size_t)grid.x * 48, st) != hipSuccess)) stamps = nullptr;
 #endif
+    if (t.stats.rec && (t.out != Outputs::Colour || t.z)) return hipErrorInvalidValue;      // record statistics: colour only, no depth test (the host refuses such a draw before it gets here)
     for_outputs(premult_c != 0, t.out, t.z != nullptr, [&](auto pc, auto out, auto zt) {
-#define GS4D_V2(P) k_composite_v2<pc(), P, out(), zt()><<<grid, dim3(64), 0, st>>>(proj, entries, tl.tstart, tl.tcnt, total, total_host, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, kp, rp, tl.slabs, tl.bstat, tl.nb, tl.sstat, tl.rows, stage_seq, rcap, tl.scap, tl.bcap, box, tl.box, stamps, t.aux, t.ids, draw_ord, t.z)
+#define GS4D_V2_ARGS (proj, entries, tl.tstart, tl.tcnt, total, total_host, tiles_x, W, H, t.tstate, t.epoch, t.clear, t.fb, kp, rp, tl.slabs, tl.bstat, tl.nb, tl.sstat, tl.rows, stage_seq, rcap, tl.scap, tl.bcap, box, tl.box, stamps, t.aux, t.ids, draw_ord, t.z, t.stats)
+#define GS4D_V2(P) do { \
+            if constexpr (out() == Outputs::Colour && !zt()) { if (t.stats.rec) { k_composite_v2<pc(), P, Outputs::Colour, false, true><<<grid, dim3(64), 0, st>>>GS4D_V2_ARGS; break; } } \
+            k_composite_v2<pc(), P, out(), zt()><<<grid, dim3(64), 0, st>>>GS4D_V2_ARGS; } while (0)
         switch (per) {
         case 1: GS4D_V2(1); break;
         case 2: GS4D_V2(2); break;
@@ -231,6 +236,7 @@ hipError_t launch_composite_v2(hipStream_t st, const float4* proj, const uint2* 
         default: GS4D_V2(16); break;
         }
 #undef GS4D_V2
+#undef GS4D_V2_ARGS
     });
     const hipError_t le = hipGetLastError();
 #ifdef GS4D_TUNING

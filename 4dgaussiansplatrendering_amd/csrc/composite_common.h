@@ -102,9 +102,15 @@ struct PixelAcc {
 // d: the entry's depth (Outputs::Aux on, or ZTEST), rid: its record index (Outputs::Ids); a lane without a fragment blends with al = 0, so w = 0
 // and it never becomes the candidate.  ZTEST: z is the pixel's value of the draw's depth-test plane; a fragment with d < z false (GL_LESS: a
 // NaN hides) is hidden like a discarded one — al = 0 — so colour, aux and ID candidate all follow the test.
-template <bool PREMULT_C, bool GENERAL, Outputs OUT, bool ZTEST>
-__device__ __forceinline__ void blend_fragment(float u, float v, float alpha, float r_, float g_, float b_, PixelAcc& p, BlendFn bf, float d, uint32_t rid, float z) {
+// STATS (record statistics, gs4d_set_record_stats): slot is the entry's count word in the chunk's stage (Stage::scnt(); its max and sum words lie
+// STAT_PLANE and 2 * STAT_PLANE words behind it), inimg: the lane's pixel is inside the image.  A fragment with w > 0 there adds (1, bits of w,
+// q(w)) with LDS atomics; any other lane adds 0 and takes the max with 0 — no branch.  q(w) = rint(w * 2^24) <= 2^24: 64 pixels fit 32 bits.
+constexpr int STAT_PLANE = 64;
+template <bool PREMULT_C, bool GENERAL, Outputs OUT, bool ZTEST, bool STATS = false>
+__device__ __forceinline__ void blend_fragment(float u, float v, float alpha, float r_, float g_, float b_, PixelAcc& p, BlendFn bf, float d, uint32_t rid, float z,
+                                               uint32_t* slot = nullptr, bool inimg = false) {
     static_assert(!GENERAL || (OUT == Outputs::Colour && !ZTEST), "aux and ID outputs and the depth test are defined for the default blend function only");
+    static_assert(!STATS || (!GENERAL && OUT == Outputs::Colour && !ZTEST), "record statistics are built for the default blend function, colour only, no depth test");
     const float cg = gauss_weight(u, v);
     if (GENERAL) {
         if (cg >= 0.0001f) {                               // Splat4DFragShader.GLSL:30 discard
@@ -126,6 +132,12 @@ __device__ __forceinline__ void blend_fragment(float u, float v, float alpha, fl
     p.Cr += w * r_; p.Cg += w * g_; p.Cb += w * b_; p.A += w * al;
     if (has_aux(OUT)) p.D += w * d;
     if (has_ids(OUT)) { const bool take = w > p.BW; p.BW = take ? w : p.BW; p.BR = take ? rid : p.BR; }
+    if constexpr (STATS) {
+        const bool counts = inimg && w > 0.0f;
+        __hip_atomic_fetch_add(slot, counts ? 1u : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_max(slot + STAT_PLANE, counts ? __float_as_uint(w) : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(slot + 2 * STAT_PLANE, counts ? (uint32_t)rintf(__fmul_rn(w, 16777216.0f)) : 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
     p.T *= (1.0f - al);
 }
 
@@ -157,15 +169,25 @@ __device__ __forceinline__ void store_over(const PixelAcc& p, size_t o, bool fb_
 
 // The LDS a chunk of <= 64 list entries is staged in: three float4 of every entry's projected record; from Outputs::Aux on, or with the depth
 // test (ZTEST), the entries' depths (the last float of the same 64-byte record) behind them; from Outputs::Ids on their record indices behind
-// those.  A kernel gives it stage_words(OUT, ZTEST) words, 16-byte aligned.
+// those.  STATS: three more words per entry behind all that — fragments counted, bits of the largest w, sum of q(w) — zeroed when the chunk is
+// staged and flushed to the draw's statistics buffer when it is done (composite_chunk).  A kernel gives it stage_words(OUT, ZTEST, STATS)
+// words, 16-byte aligned.
 constexpr bool stages_depth(Outputs o, bool ztest) { return has_aux(o) || ztest; }
-constexpr int stage_words(Outputs o, bool ztest) { return 64 * 3 * 4 + (stages_depth(o, ztest) ? 64 : 0) + (has_ids(o) ? 64 : 0); }
-template <Outputs OUT, bool ZTEST>
-struct Stage {
+constexpr int stage_words(Outputs o, bool ztest, bool stats = false) { return 64 * 3 * 4 + (stages_depth(o, ztest) ? 64 : 0) + (has_ids(o) ? 64 : 0) + (stats ? 3 * STAT_PLANE : 0); }
+// (STATS also carries what only such a draw has — where its statistics go and whether the lane's pixel lies inside the image — set by the
+// kernel once it knows its pixel.  They travel here, in an empty base of every other instance: as two more parameters of composite_chunk, even
+// defaulted and unused, they move two instructions of every Ids instance.)
+template <bool STATS> struct StageStats {};
+template <> struct StageStats<true> { mutable StatOut so; mutable bool inimg = false; };
+template <Outputs OUT, bool ZTEST, bool STATS = false>
+struct Stage : StageStats<STATS> {
     float4* rec; float* depth; uint32_t* rid;
     __device__ __forceinline__ explicit Stage(float4* records) : rec(records), depth(stages_depth(OUT, ZTEST) ? reinterpret_cast<float*>(records + 64 * 3) : nullptr),
                                                                  rid(has_ids(OUT) ? reinterpret_cast<uint32_t*>(records + 64 * 3 + 16) : nullptr) {}
+    // STATS: the entries' count words (no member: one more pointer in the struct moves two instructions of the Ids instances)
+    __device__ __forceinline__ uint32_t* scnt() const { return reinterpret_cast<uint32_t*>(rec) + stage_words(OUT, ZTEST); }
 };
+
 
 // Host side of a launch: f(premultiplied colours?, output set, depth test?) with all three as compile-time constants (std::integral_constant).
 template <class F>
@@ -181,11 +203,18 @@ inline void for_outputs(bool premult_c, Outputs out, bool ztest, F&& f) {
     if (premult_c) with_z(std::true_type{}); else with_z(std::false_type{});
 }
 
+// what blend_fragment is given beside the fragment: null / false unless STATS
+template <Outputs OUT, bool ZTEST, bool STATS> __device__ __forceinline__ uint32_t* stat_slot(const Stage<OUT, ZTEST, STATS>& st, uint32_t e) { if constexpr (STATS) return st.scnt() + e; else return nullptr; }
+template <Outputs OUT, bool ZTEST, bool STATS> __device__ __forceinline__ bool stat_inimg(const Stage<OUT, ZTEST, STATS>& st) { if constexpr (STATS) return st.inimg; else return false; }
+
 // One chunk of the tile's list, front to back: lane s < cnt carries record `rec` of list entry (end of chunk - 1 - s), so s = 0 is the
 // front-most entry.  GENERAL: the chunk is walked in DRAW order instead — lane s carries list entry (start of chunk + s).
 // pmask: 64 x 2 words of LDS (per pixel: 64-bit mask of the chunk entries that cover it).  z: the lane's pixel's depth-test value (ZTEST).
-template <bool PREMULT_C, bool GENERAL, Outputs OUT, bool ZTEST>
-__device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj, uint32_t rec, uint32_t cnt, uint32_t lane, int tx0, int ty0, float fx, float fy, const Stage<OUT, ZTEST>& st, uint32_t* pmask, int dbg,
+// STATS: after the chunk's closing barrier lane s < cnt adds what its entry collected to the draw's statistics buffer (st.so), at so.rec[rec], if
+// anything and if rec < so.n (a hostile sort index is data): one 32-bit add, one 32-bit max, one
+// 64-bit add — relaxed, device scope, no return value.  One flush per (tile, chunk, entry), not per fragment.
+template <bool PREMULT_C, bool GENERAL, Outputs OUT, bool ZTEST, bool STATS = false>
+__device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj, uint32_t rec, uint32_t cnt, uint32_t lane, int tx0, int ty0, float fx, float fy, const Stage<OUT, ZTEST, STATS>& st, uint32_t* pmask, int dbg,
                                                 PixelAcc& acc, BlendFn bf, float z) {
     constexpr bool DEPTH = stages_depth(OUT, ZTEST);
     float4* const stage = st.rec;
@@ -212,6 +241,7 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
     const bool big = bw > SMALL_SIDE || bh > SMALL_SIDE;
     const uint64_t bigmask = __ballot(big);
     pmask[lane * 2] = 0u; pmask[lane * 2 + 1] = 0u;
+    if constexpr (STATS) { st.scnt()[lane] = 0u; st.scnt()[STAT_PLANE + lane] = 0u; st.scnt()[2 * STAT_PLANE + lane] = 0u; }
     __syncthreads();
     if (dbg != 2 && (dbg == 1 || (uint32_t)__popcll(bigmask) * 2u > cnt)) {
         // ---- pixel-parallel broadcast over the whole chunk ----
@@ -226,7 +256,7 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const float4 c = stage[s * 3 + 2];          // b, alpha, -, -
             const float d = DEPTH ? st.depth[s] : 0.0f;
             const uint32_t rid = has_ids(OUT) ? st.rid[s] : 0u;
-            if (cov) blend_fragment<PREMULT_C, GENERAL, OUT, ZTEST>(u, v, c.y, b.z, b.w, c.x, acc, bf, d, rid, z);
+            if (cov) blend_fragment<PREMULT_C, GENERAL, OUT, ZTEST, STATS>(u, v, c.y, b.z, b.w, c.x, acc, bf, d, rid, z, stat_slot(st, s), stat_inimg(st));
         }
     } else {
         // ---- phase A (lane = entry): mark the covered pixels of small footprints ----
@@ -285,10 +315,19 @@ __device__ __forceinline__ void composite_chunk(const float4* __restrict__ proj,
             const float u = __fmaf_rn(a.z, dx, __fmul_rn(b.x, dy));
             const float v = __fmaf_rn(a.w, dx, __fmul_rn(b.y, dy));
             if constexpr (GENERAL) { if (on) blend_fragment<PREMULT_C, true, OUT, false>(u, v, c.y, b.z, b.w, c.x, acc, bf, 0.0f, 0u, 0.0f); }
-            else blend_fragment<PREMULT_C, false, OUT, ZTEST>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, acc, bf, DEPTH ? st.depth[e] : 0.0f, has_ids(OUT) ? st.rid[e] : 0u, z);
+            else blend_fragment<PREMULT_C, false, OUT, ZTEST, STATS>(u, v, on ? c.y : 0.0f, b.z, b.w, c.x, acc, bf, DEPTH ? st.depth[e] : 0.0f, has_ids(OUT) ? st.rid[e] : 0u, z, stat_slot(st, (uint32_t)e), stat_inimg(st));
         }
     }
     __syncthreads();
+    if constexpr (STATS) {
+        const uint32_t n = st.scnt()[lane];                  // (the lane's own words: it zeroes them again when the next chunk is staged)
+        if (lane < cnt && n != 0u && rec < st.so.n) {
+            gs4d_record_stat* const o = st.so.rec + rec;
+            __hip_atomic_fetch_add(&o->pixels, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_max(&o->wmax, st.scnt()[STAT_PLANE + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add(&o->wsum, (uint64_t)st.scnt()[2 * STAT_PLANE + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 } // namespace gs4d

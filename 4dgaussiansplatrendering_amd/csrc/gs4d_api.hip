@@ -48,6 +48,7 @@ struct Buffer {
     unsigned tail_mask = 0;        // lanes whose other kernels (key generation) have read it since that write (their tail event does)
     uint64_t touch = 0;            // context op counter at the last device-side use (host writes compare it with the last full sync)
     bool alive = false;
+    bool stats_target = false;     // draws have added record statistics to it since the host last waited for it (gs4d_set_record_stats): a host read settles every lane's draws first
     bool ptr_exposed = false;      // gs4d_buffer_device_ptr has handed the storage's address out: the storage may never be exchanged (see Lane::spare)
     // The caller announced (gs4d_buffer_invalidate) that work on ITS stream rewrites the buffer: every lane that uses it afterwards first
     // waits for an event recorded on that stream at the first such use (the caller has queued the writes by then: that is the contract).
@@ -83,6 +84,7 @@ struct DrawArgs {
     Outputs out = Outputs::Colour;  // what the image's frame was cleared with: from Aux on the projection stores depths in its records
     uint32_t draw_ord = 0;          // the draw's ordinal within its frame (a re-run keeps it)
     gs4d_buf zplane = 0;            // the depth-test plane bound when the draw was issued (gs4d_set_depth_test; 0: no test) — it, too, makes the projection store depths
+    gs4d_buf stats = 0; size_t stats_n = 0;      // the record-statistics buffer bound when the draw was issued and its records (gs4d_set_record_stats; 0: none)
 };
 
 struct Framebuffer {
@@ -184,6 +186,7 @@ struct gs4d_ctx {
     uint64_t stat_fused = 0, stat_renamed = 0, stat_shadow_bytes = 0, stat_streams_rejected = 0, stat_lanes_sharing = 0;      // lanes_sharing: lanes that had to take a stream which shares a hardware queue with another lane
     bool rename_storage = true;        // GS4D_RENAME=0 switches the storage exchange off (test hook)
     bool aux_enable = false, ids_enable = false;      // gs4d_set_aux_outputs, gs4d_set_id_outputs: what the frames cleared from now on have (gs4d_clear)
+    gs4d_buf record_stats = 0; size_t record_stats_n = 0;      // gs4d_set_record_stats: draw state like the depth test's (survives gs4d_clear; deleting the buffer turns it off); 0: off
     gs4d_buf depth_plane = 0;          // gs4d_set_depth_test: draw state like glBlendFunc's (survives gs4d_clear; deleting the buffer unbinds it); 0: no test
     Outputs planes = Outputs::Colour;  // the highest level that has been asked for so far: every image has its planes (gs4d_resize reallocates them)
     int shrink_votes = 0;
@@ -227,10 +230,11 @@ const char* const DEVICE_CHECK_MSG = "device-side check failed (a bounded look-b
 
 Buffer* getbuf(gs4d_ctx* c, gs4d_buf b) { return (b != 0 && b < c->bufs.size() && c->bufs[b].alive) ? &c->bufs[b] : nullptr; }
 Lane& lane(gs4d_ctx* c) { return c->lanes[c->cur]; }
-// the image as draw `a` sees it, with the draw's depth-test plane (run_draw has checked that it is alive and large enough)
+// the image as draw `a` sees it, with the draw's depth-test plane and record-statistics buffer (run_draw has checked that they are alive and large enough)
 Target draw_target(gs4d_ctx* c, const Framebuffer& F, const DrawArgs& a) {
     Target t = F.target(a.out, a.clear);
     if (const Buffer* Z = getbuf(c, a.zplane)) t.z = (const float*)Z->d;
+    if (const Buffer* S = getbuf(c, a.stats)) t.stats = StatOut{ (gs4d_record_stat*)S->d, (uint32_t)std::min<size_t>(a.stats_n, 0xFFFFFFFFull) };
     return t;
 }
 
@@ -600,6 +604,18 @@ int order_depth_plane(gs4d_ctx* c, const DrawArgs& a) {
     Z->tail_mask |= 1u << a.lane;
     return GS4D_OK;
 }
+// The record-statistics buffer: the compositing kernel ADDS to it with atomics (first run and re-runs alike — an aborted run adds nothing), so
+// lanes need no order among themselves: the draw takes it as a reader does (behind whoever WROTE it with a kernel), and a later kernel write waits
+// for this lane's tail event.  A host access (read, subdata, invalidate, destroy) settles every lane's pending draws and waits for all of them.
+int order_record_stats(gs4d_ctx* c, const DrawArgs& a) {
+    Buffer* S = getbuf(c, a.stats);
+    if (!S || S->bytes / sizeof(gs4d_record_stat) < a.stats_n) return fail(c, GS4D_E_INVALID, "draw: the record-statistics buffer holds fewer than nrecords entries");
+    int rc = lane_access(c, *S, false); if (rc) return rc;
+    S->tail_mask |= 1u << a.lane;
+    S->stats_target = true;
+    S->version++;
+    return GS4D_OK;
+}
 // entry storage for the draw: twice its instances, or one and a half times what the last draw needed, or the bucket regions of a staged draw
 int reserve_entries(gs4d_ctx* c, Lane& L, const DrawArgs& a, bool v2) {
     size_t want = a.instances * 2 + 65536;
@@ -632,6 +648,7 @@ int run_draw(gs4d_ctx* c, DrawArgs& a, bool preprocess) {
         if (a.fuse && !v2) { int rc = enqueue_fused_sort(c, L, a, fused, s.npre, false); if (rc) return rc; }
     }
     if (a.zplane) { int rc = order_depth_plane(c, a); if (rc) return rc; }
+    if (a.stats) { int rc = order_record_stats(c, a); if (rc) return rc; }
     { int rc = reserve_entries(c, L, a, v2); if (rc) return rc; }
     if (!v2) return enqueue_raster(c, L, F, a, order, order_copy, a.instances, s.npre, s.premult);
     int rc = enqueue_raster_v2(c, L, F, a, s.npre, s.premult, fused.keys ? (const uint32_t*)fused.keys->d : nullptr);
@@ -718,7 +735,7 @@ int host_access(gs4d_ctx* c, Buffer& B) {
     if (B.touch <= c->synced) return GS4D_OK;
     int rc = resolve_pending(c); if (rc) return rc;
     rc = sync_all(c); if (rc) return rc;
-    B.wr_lane = -1; B.rd_mask = 0; B.tail_mask = 0; B.ordered_mask = 0;
+    B.wr_lane = -1; B.rd_mask = 0; B.tail_mask = 0; B.ordered_mask = 0; B.stats_target = false;
     return GS4D_OK;
 }
 
@@ -952,6 +969,8 @@ int gs4d_buffer_read(gs4d_ctx* c, gs4d_buf b, size_t offset, void* out, size_t b
     if (!B) return fail(c, GS4D_E_INVALID, "buffer_read: bad buffer name");
     if (offset > B->bytes || bytes > B->bytes - offset || (!out && bytes)) return fail(c, GS4D_E_INVALID, "buffer_read: range outside the buffer");
     if (!bytes) return GS4D_OK;
+    // a buffer draws add record statistics to: after every draw issued so far, on every lane, re-runs included
+    if (B->stats_target) { int rc = host_access(c, *B); if (rc) return rc; }
     // after the kernels that wrote it: they sit on the current lane, or on the lane recorded in the buffer
     HIPCHK(c, hipStreamSynchronize(lane(c).s));
     if (B->wr_lane >= 0 && B->wr_lane != c->cur) HIPCHK(c, hipStreamSynchronize(c->lanes[B->wr_lane].s));
@@ -974,6 +993,7 @@ int gs4d_buffer_destroy(gs4d_ctx* c, gs4d_buf b) {
     *B = Buffer();
     for (auto& s : c->slots) if (s == b) s = 0;     // a deleted buffer is unbound
     if (c->depth_plane == b) c->depth_plane = 0;    // ... the depth-test plane too: the test is off
+    if (c->record_stats == b) { c->record_stats = 0; c->record_stats_n = 0; }      // ... and the record statistics
     for (int i = 0; i < c->nlanes; ++i) if (c->lanes[i].kg_buf == b) c->lanes[i].kg_buf = 0;
     return GS4D_OK;
 }
@@ -1054,6 +1074,16 @@ int gs4d_set_depth_test(gs4d_ctx* c, gs4d_buf plane) {
     if (!c) return GS4D_E_INVALID;
     if (plane != 0 && !getbuf(c, plane)) return fail(c, GS4D_E_INVALID, "set_depth_test: bad buffer name");
     c->depth_plane = plane;                              // like glBlendFunc: state for the draws that follow (their size is checked when they are issued)
+    return GS4D_OK;
+}
+int gs4d_set_record_stats(gs4d_ctx* c, gs4d_buf stats, size_t nrecords) {
+    if (!c) return GS4D_E_INVALID;
+    if (stats != 0) {
+        const Buffer* S = getbuf(c, stats);
+        if (!S) return fail(c, GS4D_E_INVALID, "set_record_stats: bad buffer name");
+        if (S->bytes / sizeof(gs4d_record_stat) < nrecords) return fail(c, GS4D_E_INVALID, "set_record_stats: the buffer holds fewer than nrecords * 16 bytes");
+    }
+    c->record_stats = stats; c->record_stats_n = stats ? nrecords : 0;      // like gs4d_set_depth_test: state for the draws that follow
     return GS4D_OK;
 }
 int gs4d_clear(gs4d_ctx* c) {
@@ -1222,6 +1252,14 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
         if (!(c->blend_src == GS4D_SRC_ALPHA && c->blend_dst == GS4D_ONE_MINUS_SRC_ALPHA))
             return fail(c, GS4D_E_UNSUPPORTED, "draw: the depth test is defined for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only");
     }
+    // record statistics: built for the default blend function into a colour-only frame without a depth test
+    if (c->record_stats) {
+        if (!getbuf(c, c->record_stats)) return fail(c, GS4D_E_INVALID, "draw: the record-statistics buffer has been deleted");
+        if (!(c->blend_src == GS4D_SRC_ALPHA && c->blend_dst == GS4D_ONE_MINUS_SRC_ALPHA))
+            return fail(c, GS4D_E_UNSUPPORTED, "draw: record statistics are built for the default blend function (SRC_ALPHA, ONE_MINUS_SRC_ALPHA) only");
+        if (c->fbs[c->cur_fb].out != Outputs::Colour) return fail(c, GS4D_E_UNSUPPORTED, "draw: record statistics are not built for frames with aux or ID outputs");
+        if (c->depth_plane) return fail(c, GS4D_E_UNSUPPORTED, "draw: record statistics are not built for draws with a depth test");
+    }
     // the lane's scratch still belongs to its previous draw, and the image this draw blends onto must be complete: validate those
     // (not the other lanes' draws: their frames are still in flight and nothing here depends on them)
     int rc = resolve_lane(c, c->cur); if (rc) return rc;
@@ -1237,6 +1275,7 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     a.blend_src = c->blend_src; a.blend_dst = c->blend_dst;
     const bool over = a.blend_src == GS4D_SRC_ALPHA && a.blend_dst == GS4D_ONE_MINUS_SRC_ALPHA;       // any other function is applied in draw order: instance-ordered lists
     a.out = c->fbs[c->cur_fb].out; a.draw_ord = c->fbs[c->cur_fb].draws; a.zplane = c->depth_plane;
+    a.stats = c->record_stats; a.stats_n = c->record_stats_n;
     if (c->atomic_rank && c->path_pref != 1 && over) {
         Buffer* data = getbuf(c, a.data);
         bool ok = false;

@@ -34,10 +34,15 @@ constexpr bool has_ids(Outputs o) { return o >= Outputs::Ids; }
 // memory, else it is still the clear colour.  aux, ids: the planes of `out`, null above that level.  Made by Framebuffer::target (gs4d_api.hip).
 // z: a draw's depth-test plane (gs4d_set_depth_test: W x H floats, -z_view units; a fragment of depth d is blended only where d < z), or
 // null: no test.  Only the default blend function has one.
+// stats: where the draw adds its record statistics (gs4d_set_record_stats), rec == null: nowhere.  An entry whose record index is
+// >= n is skipped on the device.  Only a draw of the default blend function into a Colour frame without a depth test has them.
+static_assert(sizeof(gs4d_record_stat) == 16 && offsetof(gs4d_record_stat, wsum) == 8, "the 64-bit sum is naturally aligned in a 16-byte record");
+struct StatOut { gs4d_record_stat* rec = nullptr; uint32_t n = 0; };
 struct Target {
     float4* fb; uint32_t* tstate; uint32_t epoch; float4 clear;
     Outputs out; float2* aux; uint32_t* ids;
     const float* z = nullptr;
+    StatOut stats;
 };
 
 struct Uniforms {

@@ -216,6 +216,33 @@ GS4D_API int gs4d_read_ids_device(gs4d_ctx* ctx, void* record, void* draw, void*
  * GS4D_E_INVALID, and one with a blend function other than the default GS4D_E_UNSUPPORTED; neither draws anything. */
 GS4D_API int gs4d_set_depth_test(gs4d_ctx* ctx, gs4d_buf plane);
 
+/* ---- record statistics: what each record contributed to the picture (no reference counterpart) ----
+ * The ID outputs keep one record per pixel; this is the opposite question.  Within one draw a fragment of record i at pixel p enters the
+ * colour with the weight w = T * al (T draw-local, from 1, front to back; al after the 1e-4 discard and the clamp).  Every fragment with
+ * w > 0 at a pixel inside the image counts for its record:
+ *     pixels += 1;   wmax = max(wmax, w)  (as float32 bit patterns: w >= 0, so unsigned order is float order);
+ *     wsum += q(w),  q(w) = (uint32) rint(w * 2^24) in float32, round to nearest even — wsum is in units of 2^-24.
+ * Behind a pixel whose T has reached exactly 0 every w is 0 and nothing counts.  A tile-row shard (gs4d_set_tile_shard) counts its own tile
+ * rows only.  The record index is the one the ID outputs use (GS4D_MODE_4D_SORTED: the sort index's entry; GS4D_MODE_4D_DIRECT, GS4D_MODE_2D:
+ * the instance; gs4d_draw_quads: the quad).  All three fields are integers accumulated with atomics: the result does not depend on the order of
+ * anything, and it adds up across tiles, draws, frames, frame lanes and shards (pixels and wsum by +, wmax by max).  A draw the library has
+ * to run again (a tile-list capacity or a staged guess that did not fit) counts once: an attempt that aborts on the device adds nothing. */
+typedef struct gs4d_record_stat {
+    uint32_t pixels;   /* (pixel, draw) pairs in which the record had a fragment with w > 0 */
+    uint32_t wmax;     /* bit pattern of the largest such w (float32)                       */
+    uint64_t wsum;     /* sum of q(w) over those fragments, units of 2^-24                  */
+} gs4d_record_stat;
+/* stats != 0: every gs4d_draw_instanced / gs4d_draw_quads issued from now on ADDS its statistics into the buffer, an array of nrecords
+ * gs4d_record_stat (draw state like gs4d_set_depth_test: it survives gs4d_clear).  Nothing ever zeroes the buffer: upload zeros
+ * (gs4d_buffer_subdata) where a new count should start.  0: off (the default).  A name that is not a live buffer, or a buffer of fewer than
+ * nrecords * 16 bytes: GS4D_E_INVALID, the state stays as it was.  gs4d_buffer_destroy of the buffer turns the statistics off.  A list entry
+ * whose record index is >= nrecords is skipped on the device (it is still drawn).  gs4d_draw_lines never counts.
+ * The buffer is an ordinary buffer: gs4d_buffer_read, gs4d_buffer_subdata and gs4d_buffer_invalidate on it are ordered after every draw issued
+ * before them, on every frame lane (re-runs included); draws on different lanes accumulate concurrently.
+ * Out of scope, though meaningful — such a draw returns GS4D_E_UNSUPPORTED and draws nothing: statistics with a blend function other than the
+ * default, into a frame cleared with aux or ID outputs, or with a depth test set. */
+GS4D_API int gs4d_set_record_stats(gs4d_ctx* ctx, gs4d_buf stats, size_t nrecords);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
