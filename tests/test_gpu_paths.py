@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import scenes
+from sort_cases import FORMS
 from test_gpu_render import cam_mats, linf, TOL
 
 pytestmark = pytest.mark.gpu
@@ -294,8 +295,7 @@ def test_nine_bit_digits_for_wide_key_spans(gs4d, oracle, monkeypatch, path, fus
     monkeypatch.delenv("GS4D_FUSE_KEYGEN", raising=False)
 
 
-@pytest.mark.parametrize("rank", [1, 2])
-@pytest.mark.parametrize("shape,rb", [(1, 8), (2, 8), (3, 8), (4, 8), (5, 8), (6, 8), (7, 8), (2, 9), (3, 9), (5, 9), (6, 9), (7, 9)])
+@pytest.mark.parametrize("shape,rb,rank", FORMS)
 def test_sort_ranking_variants_and_tile_shapes(gs4d, oracle, monkeypatch, rank, shape, rb):
     """Every tile shape of a pass (threads x keys per thread), both rankings, and both digit widths: 8 bits (256 bins, four passes over
     32-bit keys) and 9 bits (512 bins, one thread per bin: the shapes of 512 threads and more; 4 x 9 bits cover the 32)."""
