@@ -22,6 +22,7 @@ ZERO, ONE, SRC_COLOR, ONE_MINUS_SRC_COLOR, SRC_ALPHA, ONE_MINUS_SRC_ALPHA = 0, 1
 DST_ALPHA, ONE_MINUS_DST_ALPHA, DST_COLOR, ONE_MINUS_DST_COLOR = 0x0304, 0x0305, 0x0306, 0x0307
 CONSTANT_COLOR, ONE_MINUS_CONSTANT_COLOR, CONSTANT_ALPHA, ONE_MINUS_CONSTANT_ALPHA = 0x8001, 0x8002, 0x8003, 0x8004
 KEY_REF_INV_EUCLID, KEY_VIEW_Z = 0, 1
+KEEP_INVERT = 1                                           # gs4d_keep_rule.flags: keep exactly the records the rule would drop
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
 
@@ -82,6 +83,7 @@ def _load():
         "gs4d_read_ids_device": (i32, [vp, vp, vp, vp, sz]),
         "gs4d_set_depth_test": (i32, [vp, u32]),
         "gs4d_set_record_stats": (i32, [vp, u32, sz]),
+        "gs4d_compact_records": (i32, [vp, u32, sz, vp, u32, sz, u32, u32, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -556,6 +558,41 @@ class Context:
     def read_record_stats(self, buf, n):
         """Structured array (pixels uint32, wmax float32, wsum uint64) of the first n records, after every draw issued so far."""
         return self.read(buf, self.RECORD_STAT, n)
+
+    # compaction: prune a record set by its record statistics, on the device (DESIGN.md §4)
+    KEEP_RULE = np.dtype([("min_pixels", "<u4"), ("min_wmax", "<u4"), ("min_wsum", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])
+    COMPACT_COUNT = np.dtype([("kept", "<u4"), ("written", "<u4")])
+
+    def compact_records(self, stats, n, src=None, stride=96, dst=None, kept_index=None, count=None, min_pixels=1, min_wmax=0.0, min_wsum=0, invert=False):
+        """Stable compaction on the device (gs4d_compact_records): record i of the n is kept iff (pixels >= min_pixels and wmax >= min_wmax
+        and wsum >= min_wsum) != invert, with the record_stats row stats[i]; the kept `stride`-byte records of `src` go to `dst` in
+        ascending i, their indices (uint32) to `kept_index`, and `count` (a new 8-byte buffer if None) receives COMPACT_COUNT {kept, written}.
+        Any of dst / kept_index may be None.  min_wmax is a weight (float32), min_wsum is in units of 2^-24.  Asynchronous; returns `count`."""
+        rule = np.zeros(1, self.KEEP_RULE)
+        rule["min_pixels"], rule["min_wmax"], rule["min_wsum"] = int(min_pixels), np.array([min_wmax], np.float32).view(np.uint32)[0], int(min_wsum)
+        rule["flags"] = KEEP_INVERT if invert else 0
+        if count is None:
+            count = self.buffer(nbytes=self.COMPACT_COUNT.itemsize)
+        self._chk(_lib.gs4d_compact_records(self._h, int(stats), int(n), _ptr(rule), int(src or 0), int(stride), int(dst or 0), int(kept_index or 0), int(count)))
+        return count
+
+    def read_compact_count(self, count):
+        """(kept, written) of a compact_records call; blocks until its kernels have finished."""
+        c = self.read(count, self.COMPACT_COUNT, 1)[0]
+        return int(c["kept"]), int(c["written"])
+
+    def prune(self, stats, n, src, stride=96, **rule):
+        """compact_records into exact-size new buffers: counts first, allocates, compacts.  Returns (dst, kept_index, kept); the buffers hold
+        at least 16 bytes, so kept == 0 still gives valid names."""
+        count = self.compact_records(stats, n, stride=stride, **rule)
+        kept, _ = self.read_compact_count(count)
+        dst, kept_index = self.buffer(nbytes=max(16, kept * int(stride))), self.buffer(nbytes=max(16, kept * 4))
+        self.compact_records(stats, n, src=src, stride=stride, dst=dst, kept_index=kept_index, count=count, **rule)
+        got, written = self.read_compact_count(count)
+        self.delete(count)
+        if (got, written) != (kept, kept):
+            raise Gs4dError(f"prune: the table changed between the two passes ({kept} kept, then {got} kept / {written} written)")
+        return dst, kept_index, kept
 
     def set_tile_shard(self, rank, world):
         """Single-frame sharding: this context bins and composites the tile rows ty % world == rank only."""

@@ -53,6 +53,10 @@ struct Buffer {
     // The caller announced (gs4d_buffer_invalidate) that work on ITS stream rewrites the buffer: every lane that uses it afterwards first
     // waits for an event recorded on that stream at the first such use (the caller has queued the writes by then: that is the contract).
     hipEvent_t ev_fill = nullptr; unsigned fill_mask = 0; bool fill_recorded = false;
+    // A gs4d_compact_records whose kernels read the buffer as their statistics table: draws ADD to a table as readers do (order_record_stats), and
+    // a reader waits for nobody but a writer — so the compaction leaves an event of its own behind its kernels, and a draw that is about to add to
+    // the table on another lane waits for it first (scan_wait: the lanes that have not yet).  Both of its kernels evaluate the rule: they must see one table.
+    hipEvent_t ev_scan = nullptr; unsigned scan_wait = 0;
     // Provenance of a sort index: set when gs4d_sort_pairs has sorted exactly the keys and the identity index gs4d_keygen wrote for
     // prov.data — the contents are then "records of prov.data in ascending (depth key, record index)" for as long as `version`
     // still equals prov_ver, and a draw that binds it can take its blend order from the keys instead of reading it (tilelist.hip).
@@ -128,6 +132,7 @@ struct Lane {
     SortScratch depth_sort, pair_sort;
     BinScratch bin;
     float* line_verts = nullptr; size_t line_cap = 0;   // device copy of the vertices of the latest gs4d_draw_lines (the lane's stream orders its reuse)
+    uint32_t* compact_counts = nullptr; size_t compact_cap = 0;   // gs4d_compact_records: one word per tile of COMPACT_TILE records (counts, then first slots); the lane's stream orders its reuse
     uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
     uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
     gs4d_buf kg_buf = 0; uint64_t kg_ver = 0;         // key buffer whose digit histograms k_keygen left for the next sort
@@ -611,6 +616,10 @@ int order_record_stats(gs4d_ctx* c, const DrawArgs& a) {
     Buffer* S = getbuf(c, a.stats);
     if (!S || S->bytes / sizeof(gs4d_record_stat) < a.stats_n) return fail(c, GS4D_E_INVALID, "draw: the record-statistics buffer holds fewer than nrecords entries");
     int rc = lane_access(c, *S, false); if (rc) return rc;
+    if (S->scan_wait & (1u << c->cur)) {                       // behind a compaction that is still reading the table on another lane
+        HIPCHK(c, hipStreamWaitEvent(lane(c).s, S->ev_scan, 0));
+        S->scan_wait &= ~(1u << c->cur);
+    }
     S->tail_mask |= 1u << a.lane;
     S->stats_target = true;
     S->version++;
@@ -735,7 +744,7 @@ int host_access(gs4d_ctx* c, Buffer& B) {
     if (B.touch <= c->synced) return GS4D_OK;
     int rc = resolve_pending(c); if (rc) return rc;
     rc = sync_all(c); if (rc) return rc;
-    B.wr_lane = -1; B.rd_mask = 0; B.tail_mask = 0; B.ordered_mask = 0; B.stats_target = false;
+    B.wr_lane = -1; B.rd_mask = 0; B.tail_mask = 0; B.ordered_mask = 0; B.stats_target = false; B.scan_wait = 0;
     return GS4D_OK;
 }
 
@@ -891,7 +900,7 @@ void gs4d_destroy(gs4d_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     for (int i = 0; i < MAX_LANES; ++i) if (c->lanes[i].s) (void)hipStreamSynchronize(c->lanes[i].s);
-    for (auto& b : c->bufs) { if (b.d) (void)hipFree(b.d); if (b.soa) (void)hipFree(b.soa); if (b.bbox_dev) (void)hipFree(b.bbox_dev); if (b.ev_fill) (void)hipEventDestroy(b.ev_fill); }
+    for (auto& b : c->bufs) { if (b.d) (void)hipFree(b.d); if (b.soa) (void)hipFree(b.soa); if (b.bbox_dev) (void)hipFree(b.bbox_dev); if (b.ev_fill) (void)hipEventDestroy(b.ev_fill); if (b.ev_scan) (void)hipEventDestroy(b.ev_scan); }
     for (int i = 0; i < MAX_LANES; ++i) {
         Lane& L = c->lanes[i];
         if (c->fbs[i].mem) (void)hipFree(c->fbs[i].mem);
@@ -901,6 +910,7 @@ void gs4d_destroy(gs4d_ctx* c) {
         if (L.line_verts) (void)hipFree(L.line_verts);
         if (L.order_copy) (void)hipFree(L.order_copy);
         if (L.regen_keys) (void)hipFree(L.regen_keys);
+        if (L.compact_counts) (void)hipFree(L.compact_counts);
         for (auto& sp : L.spare) { if (sp.d) (void)hipFree(sp.d); for (hipEvent_t e : sp.ev) if (e) (void)hipEventDestroy(e); }
         if (L.proj) (void)hipFree(L.proj);
         if (L.trects) (void)hipFree(L.trects);
@@ -990,6 +1000,7 @@ int gs4d_buffer_destroy(gs4d_ctx* c, gs4d_buf b) {
     if (B->soa) (void)hipFree(B->soa);
     if (B->bbox_dev) (void)hipFree(B->bbox_dev);
     if (B->ev_fill) (void)hipEventDestroy(B->ev_fill);
+    if (B->ev_scan) (void)hipEventDestroy(B->ev_scan);
     *B = Buffer();
     for (auto& s : c->slots) if (s == b) s = 0;     // a deleted buffer is unbound
     if (c->depth_plane == b) c->depth_plane = 0;    // ... the depth-test plane too: the test is off
@@ -1226,6 +1237,56 @@ int gs4d_keygen(gs4d_ctx* c, gs4d_buf data, float t, const float cam[3], gs4d_bu
     L.kg_buf = keys; L.kg_ver = K->version; L.kg_idx = idx; L.kg_idx_ver = I->version;
     L.keyed = SortedBy{ bo, data, D->version, n };
     if (!c->defer_order) return flush_order(c);
+    return GS4D_OK;
+}
+
+// ---- compaction ----
+int gs4d_compact_records(gs4d_ctx* c, gs4d_buf stats, size_t n, const gs4d_keep_rule* rule, gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    if (!rule) return fail(c, GS4D_E_INVALID, "compact_records: rule == NULL");
+    if (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u) return fail(c, GS4D_E_INVALID, "compact_records: unknown flag or non-zero reserved field in the rule");
+    if (n > 0xFFFFFFFFull) return fail(c, GS4D_E_INVALID, "compact_records: more than 2^32 - 1 records");
+    if (stride < 16 || stride > 1024 || stride % 16 != 0) return fail(c, GS4D_E_INVALID, "compact_records: stride must be a multiple of 16 from 16 to 1024");
+    if (dst != 0 && src == 0) return fail(c, GS4D_E_INVALID, "compact_records: dst given without src");
+    const gs4d_buf names[5] = { stats, src, dst, kept_index, count };
+    for (int i = 0; i < 5; ++i) {
+        if (names[i] == 0) continue;
+        if (!getbuf(c, names[i])) return fail(c, GS4D_E_INVALID, "compact_records: bad buffer name");
+        for (int j = 0; j < i; ++j) if (names[j] == names[i]) return fail(c, GS4D_E_INVALID, "compact_records: stats, src, dst, kept_index and count must be different buffers");
+    }
+    Buffer* S = getbuf(c, stats); Buffer* C = getbuf(c, count);
+    Buffer* R = dst ? getbuf(c, src) : nullptr;                 // (the records are read only when there is somewhere to put them)
+    Buffer* D = getbuf(c, dst); Buffer* X = getbuf(c, kept_index);
+    if (!S || !C) return fail(c, GS4D_E_INVALID, "compact_records: stats and count must name buffers");
+    if (S->bytes / sizeof(gs4d_record_stat) < n) return fail(c, GS4D_E_INVALID, "compact_records: the statistics buffer holds fewer than n rows");
+    if (src != 0 && getbuf(c, src)->bytes / stride < n) return fail(c, GS4D_E_INVALID, "compact_records: src holds fewer than n records");
+    if (C->bytes < sizeof(gs4d_compact_count)) return fail(c, GS4D_E_INVALID, "compact_records: count holds fewer than 8 bytes");
+    // slots the outputs hold: no slot >= cap is ever written
+    uint32_t cap = 0xFFFFFFFFu;
+    if (D) cap = (uint32_t)std::min<size_t>(cap, D->bytes / stride);
+    if (X) cap = (uint32_t)std::min<size_t>(cap, X->bytes / 4);
+    // a queued key generation / sort that names one of the buffers runs first
+    if (c->po.keygen) for (gs4d_buf b : names) if (b != 0 && (b == c->po.data || b == c->po.keys || b == c->po.idx)) { int rc = flush_order(c); if (rc) return rc; break; }
+    // the table as a host read takes it: behind every draw issued so far, on every lane, re-runs included
+    if (S->stats_target) { int rc = host_access(c, *S); if (rc) return rc; }
+    // a draw that is still unvalidated may have to be run again from the buffers it was given: none of those is overwritten before that is settled
+    for (Buffer* B : { D, X, C }) if (B && B->touch > c->synced) { int rc = resolve_pending(c); if (rc) return rc; break; }
+    // everything that can fail without a kernel comes before any buffer's state is touched
+    Lane& L = lane(c);
+    HIPCHK(c, grow_device_array(L.s, L.compact_counts, L.compact_cap, std::max<size_t>(1, compact_tiles(n))));
+    if (!S->ev_scan) HIPCHK(c, hipEventCreateWithFlags(&S->ev_scan, hipEventDisableTiming));
+    const unsigned me = 1u << c->cur;
+    for (Buffer* B : { S, R }) if (B) { int rc = lane_access(c, *B, false); if (rc) return rc; B->tail_mask |= me; }
+    // an earlier compaction of the same table that another lane's draws still have to wait for: this lane waits for it, so that the event recorded
+    // below covers both
+    if (S->scan_wait & me) HIPCHK(c, hipStreamWaitEvent(L.s, S->ev_scan, 0));
+    for (Buffer* B : { D, X, C }) if (B) { int rc = lane_access(c, *B, true); if (rc) return rc; B->version++; B->prov_valid = false; }
+    const KeepRule k{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT };
+    HIPCHK(c, launch_compact(L.s, (const gs4d_record_stat*)S->d, n, k, L.compact_counts, R ? R->d : nullptr, stride, D ? D->d : nullptr, X ? (uint32_t*)X->d : nullptr, cap, (gs4d_compact_count*)C->d));
+    // draws that add to the table on the other lanes from now on wait until these kernels have read it (order_record_stats)
+    HIPCHK(c, hipEventRecord(S->ev_scan, L.s));
+    S->scan_wait = ((1u << c->nlanes) - 1u) & ~me;
     return GS4D_OK;
 }
 

@@ -387,4 +387,14 @@ struct LineParams { float vp[16]; float rgba[4]; int W, H; int blend_src, blend_
 // verts_dev: nverts positions of `dims` floats on the device; cnt: W*H fragment counters, all-zero between calls
 hipError_t launch_lines(hipStream_t st, const float* verts_dev, size_t nverts, int dims, int strip, const LineParams& p, float width, uint32_t* cnt, float4* fb);
 
+// ---- compact.hip ----
+// gs4d_compact_records (gs4d.h): count per tile, scan of the tile counts, scatter — three launches on `st`, no workgroup waits for another.
+constexpr uint32_t COMPACT_TILE = 2048;          // records per workgroup of the counting and the scattering kernel (8 rows per thread; 4 KiB of LDS for the tile's kept list)
+struct KeepRule { uint32_t min_pixels, min_wmax; uint64_t min_wsum; uint32_t invert; };      // gs4d_keep_rule, validated
+inline size_t compact_tiles(size_t n) { return (n + COMPACT_TILE - 1) / COMPACT_TILE; }
+// tile_counts: compact_tiles(n) words of scratch (the lane's); src / dst: records of `stride` bytes (a multiple of 16), dst == null: none; kept_index == null:
+// none; cap: slots the outputs hold (no slot >= cap is written); count: receives {kept, min(kept, cap)}
+hipError_t launch_compact(hipStream_t st, const gs4d_record_stat* stats, size_t n, const KeepRule& rule, uint32_t* tile_counts,
+                          const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count);
+
 } // namespace gs4d

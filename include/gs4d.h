@@ -243,6 +243,39 @@ typedef struct gs4d_record_stat {
  * default, into a frame cleared with aux or ID outputs, or with a depth test set. */
 GS4D_API int gs4d_set_record_stats(gs4d_ctx* ctx, gs4d_buf stats, size_t nrecords);
 
+/* ---- compaction: prune a record set by its record statistics, on the device (no reference counterpart) ----
+ * A stable, order-preserving stream compaction.  Record i (0 <= i < n) has the statistics row stats[i] and the `stride` bytes at src + i*stride.
+ * It is KEPT iff (pixels >= min_pixels && wmax >= min_wmax && wsum >= min_wsum) != invert: {1, 0, 0, 0} is the visible set, {1, bits(1/255f), 0, 0}
+ * drops what never reached one 8-bit step of any pixel.  The kept records appear in dst in ascending i: record i goes to slot rank(i), the number
+ * of kept records before it, so time-ordered or spatially ordered uploads stay so; if kept_index != 0, kept_index[rank(i)] = i (uint32).  `count`
+ * always receives a gs4d_compact_count at offset 0: kept = the true number of kept records; written = min(kept, capacity), where capacity =
+ * min(dst bytes / stride, kept_index bytes / 4) over the outputs that are given (no outputs: written = kept).  Slots >= capacity are never
+ * written — no byte outside a buffer is touched, whatever the table holds — and bytes of dst / kept_index beyond `written` slots keep their
+ * contents: a caller that sees kept > written allocates and calls again.  dst == 0 && src == 0: index list and count only; dst == 0 &&
+ * kept_index == 0: count only.  stride: a multiple of 16, 16 .. 1024 (96: SplatData, 48: GS4D_MODE_2D records, 288: the four 72-byte vertices of
+ * a quad, 16: a statistics table itself).  n == 0 writes {0, 0}.
+ * GS4D_E_INVALID, with nothing queued and nothing written: n > 0xFFFFFFFF; a bad stride; a name that is not a live buffer; a buffer too small for n
+ * rows, n records or the 8-byte count; dst without src; any two of the named buffers being the same buffer; rule == NULL, reserved != 0 or an
+ * unknown flag.
+ * Ordering: the table is taken as gs4d_buffer_read takes it — every draw issued before the call, on every frame lane, has been settled (re-runs
+ * included) — and a queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first.  The kernels are then queued on the
+ * current frame lane and the call returns without waiting for them, like gs4d_sort_pairs; dst, kept_index and count are ordinary buffers
+ * afterwards (gs4d_keygen, gs4d_sort_pairs, draws, gs4d_buffer_read and other lanes order themselves behind the call; what the library derives
+ * from dst's contents is rebuilt).  The result is that of the table as it stands at the call: a draw issued afterwards that adds to the same
+ * table — statistics left on, the next frame on the next lane — waits on the device until the call's kernels have read it, and a host write
+ * (gs4d_buffer_subdata) waits as it does for any reader.  gs4d_buffer_invalidate hand-offs of any of the buffers are honoured. */
+enum { GS4D_KEEP_INVERT = 1 };            /* keep exactly the records the rule would drop */
+typedef struct gs4d_keep_rule {
+    uint32_t min_pixels;   /* keep needs stat.pixels >= min_pixels                                  */
+    uint32_t min_wmax;     /* ... and stat.wmax >= min_wmax, as uint32 bit patterns (float order)   */
+    uint64_t min_wsum;     /* ... and stat.wsum >= min_wsum (units of 2^-24)                         */
+    uint32_t flags;        /* 0 or GS4D_KEEP_INVERT; any other bit: GS4D_E_INVALID                   */
+    uint32_t reserved;     /* must be 0                                                              */
+} gs4d_keep_rule;
+typedef struct gs4d_compact_count { uint32_t kept, written; } gs4d_compact_count;
+GS4D_API int gs4d_compact_records(gs4d_ctx* ctx, gs4d_buf stats, size_t n, const gs4d_keep_rule* rule,
+                                  gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
