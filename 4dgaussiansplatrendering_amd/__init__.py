@@ -23,6 +23,7 @@ DST_ALPHA, ONE_MINUS_DST_ALPHA, DST_COLOR, ONE_MINUS_DST_COLOR = 0x0304, 0x0305,
 CONSTANT_COLOR, ONE_MINUS_CONSTANT_COLOR, CONSTANT_ALPHA, ONE_MINUS_CONSTANT_ALPHA = 0x8001, 0x8002, 0x8003, 0x8004
 KEY_REF_INV_EUCLID, KEY_VIEW_Z = 0, 1
 KEEP_INVERT = 1                                           # gs4d_keep_rule.flags: keep exactly the records the rule would drop
+TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
 
@@ -84,6 +85,8 @@ def _load():
         "gs4d_set_depth_test": (i32, [vp, u32]),
         "gs4d_set_record_stats": (i32, [vp, u32, sz]),
         "gs4d_compact_records": (i32, [vp, u32, sz, vp, u32, sz, u32, u32, u32]),
+        "gs4d_record_time_spans": (i32, [vp, u32, sz, f32, u32]),
+        "gs4d_compact_time_window": (i32, [vp, u32, sz, f32, f32, u32, sz, u32, u32, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -592,6 +595,45 @@ class Context:
         self.delete(count)
         if (got, written) != (kept, kept):
             raise Gs4dError(f"prune: the table changed between the two passes ({kept} kept, then {got} kept / {written} written)")
+        return dst, kept_index, kept
+
+    # time windows: the records of a 4D set that can show anything between two times
+    TIME_SPAN = np.dtype([("t_first", "<f4"), ("t_last", "<f4")])
+
+    def record_time_spans(self, data, n, min_opacity=0.0, spans=None):
+        """gs4d_record_time_spans: for each of the n 96-byte records of `data`, the closed interval of float32 times outside which it provably
+        contributes nothing to a draw with uMinOpacity == min_opacity, as TIME_SPAN rows into `spans` (a new buffer if None): {+inf, -inf}
+        never, {-inf, +inf} always.  Once per upload.  Asynchronous; returns `spans`."""
+        if spans is None:
+            spans = self.buffer(nbytes=max(16, int(n) * self.TIME_SPAN.itemsize))
+        self._chk(_lib.gs4d_record_time_spans(self._h, int(data), int(n), float(min_opacity), int(spans)))
+        return spans
+
+    def compact_time_window(self, spans, n, t0, t1, src=None, stride=96, dst=None, kept_index=None, count=None):
+        """gs4d_compact_time_window: compact_records with the table of record_time_spans and the rule "the span meets [t0, t1]" (t_first <= t1
+        and t_last >= t0; infinite ends allowed).  Asynchronous; returns `count` (a new 8-byte buffer if None)."""
+        if count is None:
+            count = self.buffer(nbytes=self.COMPACT_COUNT.itemsize)
+        self._chk(_lib.gs4d_compact_time_window(self._h, int(spans), int(n), float(t0), float(t1), int(src or 0), int(stride), int(dst or 0), int(kept_index or 0), int(count)))
+        return count
+
+    def time_window(self, data, n, t0, t1, min_opacity=0.0, spans=None, stride=96):
+        """The records of `data` that can show anything at a uTime in [t0, t1], in exact-size new buffers: computes the spans unless the caller
+        kept them from an earlier call (`spans`), counts, allocates, compacts.  Returns (dst, kept_index, kept); the buffers hold at least 16
+        bytes, so kept == 0 still gives valid names.  A draw of (dst, kept) at such a time gives the bits of a draw of (data, n)."""
+        own = spans is None
+        if own:
+            spans = self.record_time_spans(data, n, min_opacity)
+        count = self.compact_time_window(spans, n, t0, t1, stride=stride)
+        kept, _ = self.read_compact_count(count)
+        dst, kept_index = self.buffer(nbytes=max(16, kept * int(stride))), self.buffer(nbytes=max(16, kept * 4))
+        self.compact_time_window(spans, n, t0, t1, src=data, stride=stride, dst=dst, kept_index=kept_index, count=count)
+        got, written = self.read_compact_count(count)
+        self.delete(count)
+        if own:
+            self.delete(spans)
+        if (got, written) != (kept, kept):
+            raise Gs4dError(f"time_window: the spans changed between the two passes ({kept} kept, then {got} kept / {written} written)")
         return dst, kept_index, kept
 
     def set_tile_shard(self, rank, world):

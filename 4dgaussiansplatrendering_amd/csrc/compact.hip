@@ -1,8 +1,10 @@
-// compact.hip — gs4d_compact_records: stable stream compaction of a record set by its record statistics (include/gs4d.h).
+// compact.hip — stable stream compaction of a record set by a table of one row per record (include/gs4d.h):
+// gs4d_compact_records (16-byte statistics rows, KeepRule) and gs4d_compact_time_window (8-byte time spans, WindowRule) are the two instantiations
+// of the same three kernels; k_time_spans, at the end, writes the table of the second (gs4d_record_time_spans).
 //
 // Three launches on one stream, no workgroup ever waits for another (kernel boundaries are the only dependencies):
-//   k_compact_count    one workgroup per tile of COMPACT_TILE records: loads the 16-byte statistics rows, evaluates the keep rule, counts the kept
-//                      rows of the tile with wave ballots and stores ONE word per tile;
+//   k_compact_count    one workgroup per tile of COMPACT_TILE records: loads the table rows (16 bytes of statistics here; in general sizeof(Row)),
+//                      evaluates the keep rule, counts the kept rows of the tile with wave ballots and stores ONE word per tile;
 //   k_compact_scan     one workgroup: exclusive sum of the tile counts, in place (the words become the tiles' first destination slots), and the
 //                      caller's gs4d_compact_count {kept, written};
 //   k_compact_scatter  one workgroup per tile: evaluates the rule again (16 bytes per record read twice instead of a flag array written and
@@ -21,21 +23,29 @@ __device__ __forceinline__ bool keep_row(const uint4 row, const KeepRule k) {
     const uint64_t wsum = (uint64_t)row.z | ((uint64_t)row.w << 32);          // gs4d_record_stat: pixels, wmax, wsum (little endian)
     return (row.x >= k.min_pixels && row.y >= k.min_wmax && wsum >= k.min_wsum) != (k.invert != 0u);
 }
+// gs4d_time_span {t_first, t_last} against the window [t0, t1]: the two closed intervals meet (an empty span, {+inf, -inf}, meets nothing)
+__device__ __forceinline__ bool keep_row(const float2 row, const WindowRule k) { return row.x <= k.t1 && row.y >= k.t0; }
+
+// a row past the end of the table (never kept: keep_flags tests the index as well)
+__device__ __forceinline__ uint4 zero_row(const uint4*) { return make_uint4(0u, 0u, 0u, 0u); }
+__device__ __forceinline__ float2 zero_row(const float2*) { return make_float2(0.0f, 0.0f); }
 
 // Round r of a tile: thread t looks at local record r * CT_THREADS + t, so that a wave reads 1 KiB of consecutive rows and ascending
 // (round, wave, lane) is ascending record order.  All rows of a thread are loaded before the first is used.
-__device__ __forceinline__ void keep_flags(const uint4* __restrict__ stats, uint64_t tile0, uint64_t n, const KeepRule k, bool (&keep)[CT_ROUNDS]) {
-    uint4 row[CT_ROUNDS];
+template <class Row, class Rule>
+__device__ __forceinline__ void keep_flags(const Row* __restrict__ stats, uint64_t tile0, uint64_t n, const Rule k, bool (&keep)[CT_ROUNDS]) {
+    Row row[CT_ROUNDS];
 #pragma unroll
     for (uint32_t r = 0; r < CT_ROUNDS; ++r) {
         const uint64_t i = tile0 + r * CT_THREADS + threadIdx.x;
-        row[r] = i < n ? stats[i] : make_uint4(0u, 0u, 0u, 0u);
+        row[r] = i < n ? stats[i] : zero_row(stats);
     }
 #pragma unroll
     for (uint32_t r = 0; r < CT_ROUNDS; ++r) keep[r] = tile0 + r * CT_THREADS + threadIdx.x < n && keep_row(row[r], k);
 }
 
-__global__ __launch_bounds__(CT_THREADS) void k_compact_count(const uint4* __restrict__ stats, uint64_t n, KeepRule k, uint32_t* __restrict__ counts) {
+template <class Row, class Rule>
+__global__ __launch_bounds__(CT_THREADS) void k_compact_count(const Row* __restrict__ stats, uint64_t n, Rule k, uint32_t* __restrict__ counts) {
     __shared__ uint32_t wave_total[CT_WAVES];
     bool keep[CT_ROUNDS];
     keep_flags(stats, (uint64_t)blockIdx.x * COMPACT_TILE, n, k, keep);
@@ -73,7 +83,8 @@ __global__ __launch_bounds__(1024) void k_compact_scan(uint32_t* __restrict__ co
     if (threadIdx.x == 0u) { const uint32_t kept = carry_s; *count = make_uint2(kept, kept < cap ? kept : cap); }
 }
 
-__global__ __launch_bounds__(CT_THREADS) void k_compact_scatter(const uint4* __restrict__ stats, uint64_t n, KeepRule k, const uint32_t* __restrict__ bases,
+template <class Row, class Rule>
+__global__ __launch_bounds__(CT_THREADS) void k_compact_scatter(const Row* __restrict__ stats, uint64_t n, Rule k, const uint32_t* __restrict__ bases,
                                                                const uint4* __restrict__ src, uint32_t q, uint4* __restrict__ dst, uint32_t* __restrict__ kept_index, uint32_t cap) {
     __shared__ uint32_t part[64];                  // kept rows of (round, wave), then their exclusive sums
     __shared__ uint32_t total_s;
@@ -124,13 +135,68 @@ __global__ __launch_bounds__(CT_THREADS) void k_compact_scatter(const uint4* __r
     }
 }
 
-hipError_t launch_compact(hipStream_t st, const gs4d_record_stat* stats, size_t n, const KeepRule& rule, uint32_t* tile_counts,
-                          const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count) {
+template <class Row, class Rule>
+static hipError_t launch_compact_rows(hipStream_t st, const Row* table, size_t n, const Rule& rule, uint32_t* tile_counts,
+                                      const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count) {
     const uint32_t ntiles = (uint32_t)((n + COMPACT_TILE - 1) / COMPACT_TILE);
-    if (ntiles) k_compact_count<<<dim3(ntiles), dim3(CT_THREADS), 0, st>>>((const uint4*)stats, (uint64_t)n, rule, tile_counts);
+    if (ntiles) k_compact_count<Row, Rule><<<dim3(ntiles), dim3(CT_THREADS), 0, st>>>(table, (uint64_t)n, rule, tile_counts);
     k_compact_scan<<<dim3(1), dim3(1024), 0, st>>>(tile_counts, ntiles, cap, (uint2*)count);
     if (ntiles && cap && (dst || kept_index))
-        k_compact_scatter<<<dim3(ntiles), dim3(CT_THREADS), 0, st>>>((const uint4*)stats, (uint64_t)n, rule, tile_counts, (const uint4*)src, (uint32_t)(stride / 16), (uint4*)dst, kept_index, cap);
+        k_compact_scatter<Row, Rule><<<dim3(ntiles), dim3(CT_THREADS), 0, st>>>(table, (uint64_t)n, rule, tile_counts, (const uint4*)src, (uint32_t)(stride / 16), (uint4*)dst, kept_index, cap);
+    return hipGetLastError();
+}
+
+hipError_t launch_compact(hipStream_t st, const gs4d_record_stat* stats, size_t n, const KeepRule& rule, uint32_t* tile_counts,
+                          const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count) {
+    static_assert(sizeof(gs4d_record_stat) == sizeof(uint4), "a statistics row is one uint4");
+    return launch_compact_rows(st, (const uint4*)stats, n, rule, tile_counts, src, stride, dst, kept_index, cap, count);
+}
+hipError_t launch_compact(hipStream_t st, const gs4d_time_span* spans, size_t n, const WindowRule& rule, uint32_t* tile_counts,
+                          const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count) {
+    static_assert(sizeof(gs4d_time_span) == sizeof(float2), "a time span is one float2");
+    return launch_compact_rows(st, (const float2*)spans, n, rule, tile_counts, src, stride, dst, kept_index, cap, count);
+}
+
+// ---- gs4d_record_time_spans ----
+// The draw's own expression (project_4d, preprocess.hip): the argument of the opacity's exponential at time t, in float32, round to nearest, no
+// contraction (this file is built with the flags of preprocess.hip).  inv = 1.0f / s44, finite and positive.
+__device__ __forceinline__ float time_arg(float t, float mu, float inv) {
+    const float dt = t - mu;
+    return -0.5f * dt * inv * dt;
+}
+// float32 <-> a uint32 in the order of the floats (-0 just below +0)
+__device__ __forceinline__ uint32_t time_key(float t) { const uint32_t b = __float_as_uint(t); return (b & 0x80000000u) ? ~b : b | 0x80000000u; }
+__device__ __forceinline__ float key_time(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? k & 0x7FFFFFFFu : ~k); }
+// The last time, walking from mu towards `end` (+-FLT_MAX), whose argument is still >= GS4D_TIME_DEAD_ARG.  time_arg is monotone non-increasing in
+// |t - mu| and 0 at mu: the alive times on this side are a run of consecutive keys from mu's, and its end is found by bisection —
+// `a` alive, `d` dead, at most 32 halvings of a distance below 2^32.
+__device__ __forceinline__ float time_edge(float mu, float inv, float end) {
+    if (time_arg(end, mu, inv) >= GS4D_TIME_DEAD_ARG) return end;
+    uint32_t a = time_key(mu), d = time_key(end);
+    const bool up = d > a;
+    for (int step = 0; step < 32 && (up ? d - a : a - d) > 1u; ++step) {
+        const uint32_t m = up ? a + (d - a) / 2u : d + (a - d) / 2u;
+        if (time_arg(key_time(m), mu, inv) >= GS4D_TIME_DEAD_ARG) a = m; else d = m;
+    }
+    return key_time(a);
+}
+// One thread per record: three floats of the 96-byte record in, one float2 out.
+__global__ __launch_bounds__(256) void k_time_spans(const float* __restrict__ data, uint32_t n, float min_opacity, float2* __restrict__ spans) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float* rec = data + (size_t)i * 24;
+    const float mu = rec[3], cw = rec[7], s44 = rec[23];
+    const float inv = 1.0f / s44;
+    constexpr float INF = __builtin_huge_valf(), MAXF = 3.402823466e+38f;
+    float2 span;
+    if (!(cw > 0.0f)) span = make_float2(INF, -INF);                                              // never: alpha <= 0 or not finite
+    else if (!(min_opacity <= 0.0f) || !(s44 > 0.0f && s44 < INF) || !(inv > 0.0f && inv < INF) || !(fabsf(mu) < INF)) span = make_float2(-INF, INF);      // always
+    else span = make_float2(time_edge(mu, inv, -MAXF), time_edge(mu, inv, MAXF));
+    spans[i] = span;
+}
+
+hipError_t launch_time_spans(hipStream_t st, const void* data, size_t n, float min_opacity, gs4d_time_span* spans) {
+    if (n) k_time_spans<<<dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st>>>((const float*)data, (uint32_t)n, min_opacity, (float2*)spans);
     return hipGetLastError();
 }
 

@@ -834,6 +834,58 @@ static hipError_t create_lane_streams(gs4d_ctx* c) {
     return hipSuccess;
 }
 
+// What gs4d_compact_records and gs4d_compact_time_window share: a table of one row of `row_bytes` per record (`what` names it in the messages) decides
+// which of n records go from src to dst.  stats_table: the table is one that draws ADD to (Buffer::ev_scan).  launch(lane, table, records or null,
+// dst or null, kept_index or null, cap) queues the kernels.
+template <class Launch>
+int compact_by_table(gs4d_ctx* c, const char* fn, const char* what, bool stats_table, gs4d_buf table, size_t row_bytes, size_t n,
+                            gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count, Launch launch) {
+    auto bad = [&](const std::string& msg) { return fail(c, GS4D_E_INVALID, (std::string(fn) + ": " + msg).c_str()); };
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    if (stride < 16 || stride > 1024 || stride % 16 != 0) return bad("stride must be a multiple of 16 from 16 to 1024");
+    if (dst != 0 && src == 0) return bad("dst given without src");
+    const gs4d_buf names[5] = { table, src, dst, kept_index, count };
+    for (int i = 0; i < 5; ++i) {
+        if (names[i] == 0) continue;
+        if (!getbuf(c, names[i])) return bad("bad buffer name");
+        for (int j = 0; j < i; ++j) if (names[j] == names[i]) return bad(std::string(what) + ", src, dst, kept_index and count must be different buffers");
+    }
+    Buffer* S = getbuf(c, table); Buffer* C = getbuf(c, count);
+    Buffer* R = dst ? getbuf(c, src) : nullptr;                 // (the records are read only when there is somewhere to put them)
+    Buffer* D = getbuf(c, dst); Buffer* X = getbuf(c, kept_index);
+    if (!S || !C) return bad(std::string(what) + " and count must name buffers");
+    if (S->bytes / row_bytes < n) return bad(std::string("the ") + what + " buffer holds fewer than n rows");
+    if (src != 0 && getbuf(c, src)->bytes / stride < n) return bad("src holds fewer than n records");
+    if (C->bytes < sizeof(gs4d_compact_count)) return bad("count holds fewer than 8 bytes");
+    // slots the outputs hold: no slot >= cap is ever written
+    uint32_t cap = 0xFFFFFFFFu;
+    if (D) cap = (uint32_t)std::min<size_t>(cap, D->bytes / stride);
+    if (X) cap = (uint32_t)std::min<size_t>(cap, X->bytes / 4);
+    // a queued key generation / sort that names one of the buffers runs first
+    if (c->po.keygen) for (gs4d_buf b : names) if (b != 0 && (b == c->po.data || b == c->po.keys || b == c->po.idx)) { int rc = flush_order(c); if (rc) return rc; break; }
+    // a statistics table as a host read takes it: behind every draw issued so far, on every lane, re-runs included
+    if (S->stats_target) { int rc = host_access(c, *S); if (rc) return rc; }
+    // a draw that is still unvalidated may have to be run again from the buffers it was given: none of those is overwritten before that is settled
+    for (Buffer* B : { D, X, C }) if (B && B->touch > c->synced) { int rc = resolve_pending(c); if (rc) return rc; break; }
+    // everything that can fail without a kernel comes before any buffer's state is touched
+    Lane& L = lane(c);
+    HIPCHK(c, grow_device_array(L.s, L.compact_counts, L.compact_cap, std::max<size_t>(1, compact_tiles(n))));
+    if (stats_table && !S->ev_scan) HIPCHK(c, hipEventCreateWithFlags(&S->ev_scan, hipEventDisableTiming));
+    const unsigned me = 1u << c->cur;
+    for (Buffer* B : { S, R }) if (B) { int rc = lane_access(c, *B, false); if (rc) return rc; B->tail_mask |= me; }
+    // an earlier compaction of the same table that another lane's draws still have to wait for: this lane waits for it, so that the event recorded
+    // below covers both
+    if (stats_table && (S->scan_wait & me)) HIPCHK(c, hipStreamWaitEvent(L.s, S->ev_scan, 0));
+    for (Buffer* B : { D, X, C }) if (B) { int rc = lane_access(c, *B, true); if (rc) return rc; B->version++; B->prov_valid = false; }
+    HIPCHK(c, launch(L, S->d, R ? R->d : nullptr, D ? D->d : nullptr, X ? (uint32_t*)X->d : nullptr, cap, (gs4d_compact_count*)C->d));
+    if (stats_table) {
+        // draws that add to the table on the other lanes from now on wait until these kernels have read it (order_record_stats)
+        HIPCHK(c, hipEventRecord(S->ev_scan, L.s));
+        S->scan_wait = ((1u << c->nlanes) - 1u) & ~me;
+    }
+    return GS4D_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -1246,48 +1298,43 @@ int gs4d_compact_records(gs4d_ctx* c, gs4d_buf stats, size_t n, const gs4d_keep_
     (void)hipSetDevice(c->device);
     if (!rule) return fail(c, GS4D_E_INVALID, "compact_records: rule == NULL");
     if (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u) return fail(c, GS4D_E_INVALID, "compact_records: unknown flag or non-zero reserved field in the rule");
-    if (n > 0xFFFFFFFFull) return fail(c, GS4D_E_INVALID, "compact_records: more than 2^32 - 1 records");
-    if (stride < 16 || stride > 1024 || stride % 16 != 0) return fail(c, GS4D_E_INVALID, "compact_records: stride must be a multiple of 16 from 16 to 1024");
-    if (dst != 0 && src == 0) return fail(c, GS4D_E_INVALID, "compact_records: dst given without src");
-    const gs4d_buf names[5] = { stats, src, dst, kept_index, count };
-    for (int i = 0; i < 5; ++i) {
-        if (names[i] == 0) continue;
-        if (!getbuf(c, names[i])) return fail(c, GS4D_E_INVALID, "compact_records: bad buffer name");
-        for (int j = 0; j < i; ++j) if (names[j] == names[i]) return fail(c, GS4D_E_INVALID, "compact_records: stats, src, dst, kept_index and count must be different buffers");
-    }
-    Buffer* S = getbuf(c, stats); Buffer* C = getbuf(c, count);
-    Buffer* R = dst ? getbuf(c, src) : nullptr;                 // (the records are read only when there is somewhere to put them)
-    Buffer* D = getbuf(c, dst); Buffer* X = getbuf(c, kept_index);
-    if (!S || !C) return fail(c, GS4D_E_INVALID, "compact_records: stats and count must name buffers");
-    if (S->bytes / sizeof(gs4d_record_stat) < n) return fail(c, GS4D_E_INVALID, "compact_records: the statistics buffer holds fewer than n rows");
-    if (src != 0 && getbuf(c, src)->bytes / stride < n) return fail(c, GS4D_E_INVALID, "compact_records: src holds fewer than n records");
-    if (C->bytes < sizeof(gs4d_compact_count)) return fail(c, GS4D_E_INVALID, "compact_records: count holds fewer than 8 bytes");
-    // slots the outputs hold: no slot >= cap is ever written
-    uint32_t cap = 0xFFFFFFFFu;
-    if (D) cap = (uint32_t)std::min<size_t>(cap, D->bytes / stride);
-    if (X) cap = (uint32_t)std::min<size_t>(cap, X->bytes / 4);
-    // a queued key generation / sort that names one of the buffers runs first
-    if (c->po.keygen) for (gs4d_buf b : names) if (b != 0 && (b == c->po.data || b == c->po.keys || b == c->po.idx)) { int rc = flush_order(c); if (rc) return rc; break; }
-    // the table as a host read takes it: behind every draw issued so far, on every lane, re-runs included
-    if (S->stats_target) { int rc = host_access(c, *S); if (rc) return rc; }
-    // a draw that is still unvalidated may have to be run again from the buffers it was given: none of those is overwritten before that is settled
-    for (Buffer* B : { D, X, C }) if (B && B->touch > c->synced) { int rc = resolve_pending(c); if (rc) return rc; break; }
-    // everything that can fail without a kernel comes before any buffer's state is touched
-    Lane& L = lane(c);
-    HIPCHK(c, grow_device_array(L.s, L.compact_counts, L.compact_cap, std::max<size_t>(1, compact_tiles(n))));
-    if (!S->ev_scan) HIPCHK(c, hipEventCreateWithFlags(&S->ev_scan, hipEventDisableTiming));
-    const unsigned me = 1u << c->cur;
-    for (Buffer* B : { S, R }) if (B) { int rc = lane_access(c, *B, false); if (rc) return rc; B->tail_mask |= me; }
-    // an earlier compaction of the same table that another lane's draws still have to wait for: this lane waits for it, so that the event recorded
-    // below covers both
-    if (S->scan_wait & me) HIPCHK(c, hipStreamWaitEvent(L.s, S->ev_scan, 0));
-    for (Buffer* B : { D, X, C }) if (B) { int rc = lane_access(c, *B, true); if (rc) return rc; B->version++; B->prov_valid = false; }
     const KeepRule k{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT };
-    HIPCHK(c, launch_compact(L.s, (const gs4d_record_stat*)S->d, n, k, L.compact_counts, R ? R->d : nullptr, stride, D ? D->d : nullptr, X ? (uint32_t*)X->d : nullptr, cap, (gs4d_compact_count*)C->d));
-    // draws that add to the table on the other lanes from now on wait until these kernels have read it (order_record_stats)
-    HIPCHK(c, hipEventRecord(S->ev_scan, L.s));
-    S->scan_wait = ((1u << c->nlanes) - 1u) & ~me;
+    return compact_by_table(c, "compact_records", "stats", true, stats, sizeof(gs4d_record_stat), n, src, stride, dst, kept_index, count,
+        [&](Lane& L, const void* table, const void* records, void* out, uint32_t* index, uint32_t cap, gs4d_compact_count* cnt) {
+            return launch_compact(L.s, (const gs4d_record_stat*)table, n, k, L.compact_counts, records, stride, out, index, cap, cnt);
+        });
+}
+
+// ---- time windows ----
+int gs4d_record_time_spans(gs4d_ctx* c, gs4d_buf data, size_t n, float min_opacity, gs4d_buf spans) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    if (n > 0xFFFFFFFFull) return fail(c, GS4D_E_INVALID, "record_time_spans: more than 2^32 - 1 records");
+    Buffer* D = getbuf(c, data); Buffer* S = getbuf(c, spans);
+    if (!D || !S) return fail(c, GS4D_E_INVALID, "record_time_spans: bad buffer name");
+    if (D == S) return fail(c, GS4D_E_INVALID, "record_time_spans: data and spans must be different buffers");
+    if (D->bytes / 96 < n || S->bytes / sizeof(gs4d_time_span) < n) return fail(c, GS4D_E_INVALID, "record_time_spans: buffers smaller than n elements");
+    if (n == 0) return GS4D_OK;
+    // a queued key generation / sort that names one of the buffers runs first
+    if (c->po.keygen) for (gs4d_buf b : { data, spans }) if (b == c->po.data || b == c->po.keys || b == c->po.idx) { int rc = flush_order(c); if (rc) return rc; break; }
+    // a draw that is still unvalidated may have to be run again from the buffers it was given: spans is not overwritten before that is settled
+    if (S->touch > c->synced) { int rc = resolve_pending(c); if (rc) return rc; }
+    Lane& L = lane(c);
+    { int rc = lane_access(c, *D, false); if (rc) return rc; D->tail_mask |= 1u << c->cur; }
+    { int rc = lane_access(c, *S, true); if (rc) return rc; S->version++; S->prov_valid = false; }
+    HIPCHK(c, launch_time_spans(L.s, D->d, n, min_opacity, (gs4d_time_span*)S->d));
     return GS4D_OK;
+}
+
+int gs4d_compact_time_window(gs4d_ctx* c, gs4d_buf spans, size_t n, float t0, float t1, gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    if (!(t0 <= t1)) return fail(c, GS4D_E_INVALID, "compact_time_window: t0 or t1 is NaN, or t0 > t1");
+    const WindowRule k{ t0, t1 };
+    return compact_by_table(c, "compact_time_window", "spans", false, spans, sizeof(gs4d_time_span), n, src, stride, dst, kept_index, count,
+        [&](Lane& L, const void* table, const void* records, void* out, uint32_t* index, uint32_t cap, gs4d_compact_count* cnt) {
+            return launch_compact(L.s, (const gs4d_time_span*)table, n, k, L.compact_counts, records, stride, out, index, cap, cnt);
+        });
 }
 
 // ---- draw ----

@@ -396,5 +396,11 @@ inline size_t compact_tiles(size_t n) { return (n + COMPACT_TILE - 1) / COMPACT_
 // none; cap: slots the outputs hold (no slot >= cap is written); count: receives {kept, min(kept, cap)}
 hipError_t launch_compact(hipStream_t st, const gs4d_record_stat* stats, size_t n, const KeepRule& rule, uint32_t* tile_counts,
                           const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count);
+// gs4d_compact_time_window: the same three kernels on a table of gs4d_time_span rows; record i is kept iff t_first <= t1 && t_last >= t0
+struct WindowRule { float t0, t1; };
+hipError_t launch_compact(hipStream_t st, const gs4d_time_span* spans, size_t n, const WindowRule& rule, uint32_t* tile_counts,
+                          const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count);
+// gs4d_record_time_spans: spans[i] of the n 96-byte records in `data` (one launch; n == 0: none)
+hipError_t launch_time_spans(hipStream_t st, const void* data, size_t n, float min_opacity, gs4d_time_span* spans);
 
 } // namespace gs4d

@@ -276,6 +276,40 @@ typedef struct gs4d_compact_count { uint32_t kept, written; } gs4d_compact_count
 GS4D_API int gs4d_compact_records(gs4d_ctx* ctx, gs4d_buf stats, size_t n, const gs4d_keep_rule* rule,
                                   gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count);
 
+/* ---- time windows: the records of a 4D set that can show anything between two times (no reference counterpart) ----
+ * A 4D draw gives record i the opacity ot = max(expf(arg(uTime)), uMinOpacity) and the alpha ot * colour.a, with
+ *     arg(t) = ((-0.5f * dt) * (1.0f / s44)) * dt,  dt = t - mu_t     (float32, round to nearest, no contraction: the draw's own operations)
+ * where mu_t = float 3, colour.a = float 7 and s44 = float 23 of the 96-byte SplatData record.  Far from mu_t the exponential is exactly 0, and
+ * with it the alpha: no float32 exponential is non-zero below GS4D_TIME_DEAD_ARG (e^-106 is 0.13 x half the smallest denormal).  Such a record
+ * is still keyed, sorted, projected, binned and blended — with the default blend function as an exact no-op (C += 0, T *= 1, weight 0).
+ * gs4d_record_time_spans writes, for each of the n records of `data`, the closed interval of float32 times OUTSIDE which it provably contributes
+ * nothing — one gs4d_time_span per record at spans[i], once per upload:
+ *     never  {+inf, -inf}: !(colour.a > 0) — the alpha is <= 0 (clamped to 0 when blended) or not finite (the record is invalid) at every time;
+ *     always {-inf, +inf}: min_opacity > 0 or NaN (the floor keeps ot > 0), s44 not finite or not positive, 1.0f / s44 not finite (s44 below
+ *                          2^-128), mu_t not finite — the conservative answer for hostile records;
+ *     otherwise t_last = the largest and t_first = the smallest finite float32 t with arg(t) >= GS4D_TIME_DEAD_ARG.  arg is monotone non-increasing
+ *                          in |t - mu_t| and arg(mu_t) = 0: both ends are found by bisection over the ordered bit patterns of t, exactly.
+ * GS4D_E_INVALID, nothing queued: n > 0xFFFFFFFF, a name that is not a live buffer, data == spans, data smaller than n * 96 bytes or spans smaller
+ * than n * 8.  n == 0 is a no-op.  Ordering as gs4d_compact_records: queued on the current frame lane, the call returns at once; `spans` is an
+ * ordinary buffer that the call writes, `data` one that it reads.
+ *
+ * gs4d_compact_time_window keeps record i iff its span meets the window: t_first <= t1 && t_last >= t0.  EVERYTHING else is gs4d_compact_records
+ * with `spans` in the place of `stats`: the stable order, kept_index, gs4d_compact_count {kept, written}, the capacity clamp (no byte outside a
+ * buffer is touched, whatever the table holds), the stride rules, the count-only and index-only forms, the distinct-buffer rule, GS4D_E_INVALID
+ * with nothing queued and nothing written — additionally when t0 or t1 is NaN or t0 > t1 (infinite ends are allowed) or spans holds fewer than
+ * n * 8 bytes — and the ordering (a table needs no draws settled: it is a buffer the call reads).
+ *
+ * The guarantee.  With the default blend function, uMinOpacity equal to the min_opacity the spans were computed with, any finite uTime in
+ * [t0, t1], and GS4D_MODE_4D_SORTED after gs4d_keygen + gs4d_sort_pairs (of the respective set) or GS4D_MODE_4D_DIRECT: a draw of the compacted
+ * set gives the same bits as a draw of the full set in the colour image, the aux planes, the ID planes (record indices mapped through kept_index)
+ * and the record statistics (rows mapped through kept_index; the rows of the full set that were dropped are zero).  Nothing is promised for any
+ * other blend function: there a fragment of alpha 0 can change the destination (e.g. (ONE, ONE) adds its colour). */
+#define GS4D_TIME_DEAD_ARG (-106.0f)
+typedef struct gs4d_time_span { float t_first, t_last; } gs4d_time_span;
+GS4D_API int gs4d_record_time_spans(gs4d_ctx* ctx, gs4d_buf data, size_t n, float min_opacity, gs4d_buf spans);
+GS4D_API int gs4d_compact_time_window(gs4d_ctx* ctx, gs4d_buf spans, size_t n, float t0, float t1,
+                                      gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
