@@ -592,6 +592,10 @@ static inline void gs4do_blend(int sf, int df, const float src[4], float* d) {
     }
     d[0] = out[0]; d[1] = out[1]; d[2] = out[2]; d[3] = out[3];
 }
+// One blend step on n (src, dst) pairs of RGBA, dst in place: what tests/test_blend_host.py holds against its own statement of the GL tables.
+GS4DO_API void gs4do_blend_step(int sf, int df, const float* src, float* dst, size_t n) {
+    for (size_t i = 0; i < n; ++i) gs4do_blend(sf, df, src + 4 * i, dst + 4 * i);
+}
 
 // Ordered "over" blend into an RGBA32F image (row 0 = bottom), instance order = order[k] (or k if order == NULL).
 // Application.cpp:150-154 : dst = src*src.a + dst*(1-src.a) on all four channels, depth test off.

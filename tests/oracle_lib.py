@@ -167,6 +167,14 @@ def composite(proj_arr, order, frag_mode, W, H, rgba, nthreads=8, blend=BLEND_OV
     return rgba
 
 
+def blend_step(blend, src, dst):
+    """One blend step of the checker (gs4do_blend) on (n, 4) float32 sources and destinations; returns the new destinations."""
+    s, d = _f32(src).reshape(-1, 4), np.array(dst, dtype=np.float32).reshape(-1, 4)
+    assert s.shape == d.shape
+    lib().gs4do_blend_step(C.c_int(blend[0]), C.c_int(blend[1]), _p(s), _p(d), C.c_size_t(s.shape[0]))
+    return d
+
+
 def draw_lines(rgba, verts, color, width=1.0, viewproj=None, strip=False, blend=BLEND_OVER):
     """Overlay lines blended into `rgba` (H, W, 4) in place; verts (n, 3) with viewproj or (n, 2) NDC."""
     H, W = rgba.shape[:2]

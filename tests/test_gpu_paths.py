@@ -617,7 +617,8 @@ BLENDS = [("ONE", "ONE"), ("SRC_ALPHA", "ONE"), ("ONE", "ZERO"), ("ZERO", "ONE")
 
 @pytest.mark.parametrize("sf,df", BLENDS)
 def test_blend_functions_of_the_menu(gs4d, oracle, monkeypatch, sf, df):
-    """Lines, then 4D splats in sorted order, then 3D-Full quads (premultiplied colour), all with the selected function."""
+    """Lines, then 4D splats in sorted order, then half of them again in record order (4D direct), all with the selected function.  (3D-Full
+    quads, the 2D pipeline and all 196 pairs: tests/test_gpu_blend.py.)"""
     n, W, H = 6000, 480, 270
     blend = (getattr(gs4d, sf), getattr(gs4d, df))
     pos4, q, sc, life, fade, vel, rgba = scenes.cube_params_4d(n, seed=71)
