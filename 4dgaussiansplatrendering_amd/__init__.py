@@ -87,6 +87,8 @@ def _load():
         "gs4d_compact_records": (i32, [vp, u32, sz, vp, u32, sz, u32, u32, u32]),
         "gs4d_record_time_spans": (i32, [vp, u32, sz, f32, u32]),
         "gs4d_compact_time_window": (i32, [vp, u32, sz, f32, f32, u32, sz, u32, u32, u32]),
+        "gs4d_spatial_order": (i32, [vp, u32, sz, sz, sz, u32]),
+        "gs4d_gather_records": (i32, [vp, u32, sz, u32, sz, sz, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -635,6 +637,33 @@ class Context:
         if (got, written) != (kept, kept):
             raise Gs4dError(f"time_window: the spans changed between the two passes ({kept} kept, then {got} kept / {written} written)")
         return dst, kept_index, kept
+
+    # spatial order: a record set reordered so that neighbours in space are neighbours in memory
+    def spatial_order(self, src, n, stride=96, pos_offset=0, order_index=None):
+        """gs4d_spatial_order: the permutation that puts the n `stride`-byte records of `src` into Morton order of their positions (three
+        float32 at pos_offset; 10 bits per axis over the box of the finite positions; records with a non-finite coordinate last; equal codes
+        keep their order) as uint32 into `order_index` (a new buffer if None): order_index[j] = the record that comes j-th.  Once per upload.
+        Asynchronous; returns `order_index`."""
+        if order_index is None:
+            order_index = self.buffer(nbytes=max(16, int(n) * 4))
+        self._chk(_lib.gs4d_spatial_order(self._h, int(src), int(n), int(stride), int(pos_offset), int(order_index)))
+        return order_index
+
+    def gather_records(self, index, m, src, nsrc, stride=96, dst=None):
+        """gs4d_gather_records: slot j of `dst` (a new buffer if None) <- the `stride` bytes of record index[j] of the nsrc records of `src`,
+        j < m; an entry >= nsrc leaves its slot as it is.  stride: a multiple of 16 up to 1024, or 4 or 8 (index lists, TIME_SPAN rows).  Reorders a set by spatial_order's index, or carries a table with a row per record
+        along with a reorder or a compaction (its kept_index).  Asynchronous; returns `dst`."""
+        if dst is None:
+            dst = self.buffer(nbytes=max(16, int(m) * int(stride)))
+        self._chk(_lib.gs4d_gather_records(self._h, int(index), int(m), int(src), int(nsrc), int(stride), int(dst)))
+        return dst
+
+    def reorder_spatial(self, data, n, stride=96):
+        """The n records of `data` in spatial order, in new buffers: spatial_order, then gather_records.  Returns (dst, order_index); the
+        buffers hold at least 16 bytes, so n == 0 still gives valid names.  A GS4D_MODE_4D_SORTED draw of (dst, n) gives the bits of a draw of
+        (data, n) when no two records share a depth key (gs4d.h); gather a table with a row per record through the same order_index."""
+        order_index = self.spatial_order(data, n, stride=stride)
+        return self.gather_records(order_index, n, data, n, stride=stride), order_index
 
     def set_tile_shard(self, rank, world):
         """Single-frame sharding: this context bins and composites the tile rows ty % world == rank only."""

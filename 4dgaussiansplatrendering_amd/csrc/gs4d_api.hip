@@ -133,6 +133,7 @@ struct Lane {
     BinScratch bin;
     float* line_verts = nullptr; size_t line_cap = 0;   // device copy of the vertices of the latest gs4d_draw_lines (the lane's stream orders its reuse)
     uint32_t* compact_counts = nullptr; size_t compact_cap = 0;   // gs4d_compact_records: one word per tile of COMPACT_TILE records (counts, then first slots); the lane's stream orders its reuse
+    uint32_t* spatial_scratch = nullptr; size_t spatial_cap = 0;      // gs4d_spatial_order: the box and its partials (order_box_words()), then one key per record; the lane's stream orders its reuse
     uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
     uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
     gs4d_buf kg_buf = 0; uint64_t kg_ver = 0;         // key buffer whose digit histograms k_keygen left for the next sort
@@ -834,6 +835,37 @@ static hipError_t create_lane_streams(gs4d_ctx* c) {
     return hipSuccess;
 }
 
+// ---- what the record-set calls share (compaction, time windows, spatial order, gather) ----
+// the stride rule of every such call
+bool record_stride_ok(size_t stride) { return stride >= 16 && stride <= 1024 && stride % 16 == 0; }
+// names[i] != 0 must be a live buffer that none of names[0 .. i) names too.  0: they are; 1: a bad name; 2: two names of one buffer
+int check_record_names(gs4d_ctx* c, const gs4d_buf* names, int count) {
+    for (int i = 0; i < count; ++i) {
+        if (names[i] == 0) continue;
+        if (!getbuf(c, names[i])) return 1;
+        for (int j = 0; j < i; ++j) if (names[j] == names[i]) return 2;
+    }
+    return 0;
+}
+// a queued key generation / sort that names one of the buffers runs first
+int flush_order_if_named(gs4d_ctx* c, const gs4d_buf* names, int count) {
+    if (c->po.keygen) for (int i = 0; i < count; ++i) if (names[i] != 0 && (names[i] == c->po.data || names[i] == c->po.keys || names[i] == c->po.idx)) return flush_order(c);
+    return GS4D_OK;
+}
+// Kernels on the current frame lane that read the buffers `in` and overwrite the buffers `out` (null entries: not given).  prepare(lane): everything
+// that can fail without a kernel — it comes before any buffer's state is touched; launch(lane) queues the kernels.
+template <class Prepare, class Launch>
+int queue_on_lane(gs4d_ctx* c, std::initializer_list<Buffer*> in, std::initializer_list<Buffer*> out, Prepare prepare, Launch launch) {
+    // a draw that is still unvalidated may have to be run again from the buffers it was given: none of those is overwritten before that is settled
+    for (Buffer* B : out) if (B && B->touch > c->synced) { int rc = resolve_pending(c); if (rc) return rc; break; }
+    Lane& L = lane(c);
+    { int rc = prepare(L); if (rc) return rc; }
+    const unsigned me = 1u << c->cur;
+    for (Buffer* B : in) if (B) { int rc = lane_access(c, *B, false); if (rc) return rc; B->tail_mask |= me; }
+    for (Buffer* B : out) if (B) { int rc = lane_access(c, *B, true); if (rc) return rc; B->version++; B->prov_valid = false; }
+    return launch(L);
+}
+
 // What gs4d_compact_records and gs4d_compact_time_window share: a table of one row of `row_bytes` per record (`what` names it in the messages) decides
 // which of n records go from src to dst.  stats_table: the table is one that draws ADD to (Buffer::ev_scan).  launch(lane, table, records or null,
 // dst or null, kept_index or null, cap) queues the kernels.
@@ -842,14 +874,10 @@ int compact_by_table(gs4d_ctx* c, const char* fn, const char* what, bool stats_t
                             gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count, Launch launch) {
     auto bad = [&](const std::string& msg) { return fail(c, GS4D_E_INVALID, (std::string(fn) + ": " + msg).c_str()); };
     if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    if (stride < 16 || stride > 1024 || stride % 16 != 0) return bad("stride must be a multiple of 16 from 16 to 1024");
+    if (!record_stride_ok(stride)) return bad("stride must be a multiple of 16 from 16 to 1024");
     if (dst != 0 && src == 0) return bad("dst given without src");
     const gs4d_buf names[5] = { table, src, dst, kept_index, count };
-    for (int i = 0; i < 5; ++i) {
-        if (names[i] == 0) continue;
-        if (!getbuf(c, names[i])) return bad("bad buffer name");
-        for (int j = 0; j < i; ++j) if (names[j] == names[i]) return bad(std::string(what) + ", src, dst, kept_index and count must be different buffers");
-    }
+    if (const int wrong = check_record_names(c, names, 5)) return bad(wrong == 1 ? "bad buffer name" : std::string(what) + ", src, dst, kept_index and count must be different buffers");
     Buffer* S = getbuf(c, table); Buffer* C = getbuf(c, count);
     Buffer* R = dst ? getbuf(c, src) : nullptr;                 // (the records are read only when there is somewhere to put them)
     Buffer* D = getbuf(c, dst); Buffer* X = getbuf(c, kept_index);
@@ -861,29 +889,28 @@ int compact_by_table(gs4d_ctx* c, const char* fn, const char* what, bool stats_t
     uint32_t cap = 0xFFFFFFFFu;
     if (D) cap = (uint32_t)std::min<size_t>(cap, D->bytes / stride);
     if (X) cap = (uint32_t)std::min<size_t>(cap, X->bytes / 4);
-    // a queued key generation / sort that names one of the buffers runs first
-    if (c->po.keygen) for (gs4d_buf b : names) if (b != 0 && (b == c->po.data || b == c->po.keys || b == c->po.idx)) { int rc = flush_order(c); if (rc) return rc; break; }
+    { int rc = flush_order_if_named(c, names, 5); if (rc) return rc; }
     // a statistics table as a host read takes it: behind every draw issued so far, on every lane, re-runs included
     if (S->stats_target) { int rc = host_access(c, *S); if (rc) return rc; }
-    // a draw that is still unvalidated may have to be run again from the buffers it was given: none of those is overwritten before that is settled
-    for (Buffer* B : { D, X, C }) if (B && B->touch > c->synced) { int rc = resolve_pending(c); if (rc) return rc; break; }
-    // everything that can fail without a kernel comes before any buffer's state is touched
-    Lane& L = lane(c);
-    HIPCHK(c, grow_device_array(L.s, L.compact_counts, L.compact_cap, std::max<size_t>(1, compact_tiles(n))));
-    if (stats_table && !S->ev_scan) HIPCHK(c, hipEventCreateWithFlags(&S->ev_scan, hipEventDisableTiming));
-    const unsigned me = 1u << c->cur;
-    for (Buffer* B : { S, R }) if (B) { int rc = lane_access(c, *B, false); if (rc) return rc; B->tail_mask |= me; }
-    // an earlier compaction of the same table that another lane's draws still have to wait for: this lane waits for it, so that the event recorded
-    // below covers both
-    if (stats_table && (S->scan_wait & me)) HIPCHK(c, hipStreamWaitEvent(L.s, S->ev_scan, 0));
-    for (Buffer* B : { D, X, C }) if (B) { int rc = lane_access(c, *B, true); if (rc) return rc; B->version++; B->prov_valid = false; }
-    HIPCHK(c, launch(L, S->d, R ? R->d : nullptr, D ? D->d : nullptr, X ? (uint32_t*)X->d : nullptr, cap, (gs4d_compact_count*)C->d));
-    if (stats_table) {
-        // draws that add to the table on the other lanes from now on wait until these kernels have read it (order_record_stats)
-        HIPCHK(c, hipEventRecord(S->ev_scan, L.s));
-        S->scan_wait = ((1u << c->nlanes) - 1u) & ~me;
-    }
-    return GS4D_OK;
+    const unsigned me = 1u << c->cur;              // (settling draws does not move the current lane)
+    return queue_on_lane(c, { S, R }, { D, X, C },
+        [&](Lane& L) {
+            HIPCHK(c, grow_device_array(L.s, L.compact_counts, L.compact_cap, std::max<size_t>(1, compact_tiles(n))));
+            if (stats_table && !S->ev_scan) HIPCHK(c, hipEventCreateWithFlags(&S->ev_scan, hipEventDisableTiming));
+            return (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            // an earlier compaction of the same table that another lane's draws still have to wait for: this lane waits for it, so that the event recorded
+            // below covers both
+            if (stats_table && (S->scan_wait & me)) HIPCHK(c, hipStreamWaitEvent(L.s, S->ev_scan, 0));
+            HIPCHK(c, launch(L, S->d, R ? R->d : nullptr, D ? D->d : nullptr, X ? (uint32_t*)X->d : nullptr, cap, (gs4d_compact_count*)C->d));
+            if (stats_table) {
+                // draws that add to the table on the other lanes from now on wait until these kernels have read it (order_record_stats)
+                HIPCHK(c, hipEventRecord(S->ev_scan, L.s));
+                S->scan_wait = ((1u << c->nlanes) - 1u) & ~me;
+            }
+            return (int)GS4D_OK;
+        });
 }
 
 } // namespace
@@ -963,6 +990,7 @@ void gs4d_destroy(gs4d_ctx* c) {
         if (L.order_copy) (void)hipFree(L.order_copy);
         if (L.regen_keys) (void)hipFree(L.regen_keys);
         if (L.compact_counts) (void)hipFree(L.compact_counts);
+        if (L.spatial_scratch) (void)hipFree(L.spatial_scratch);
         for (auto& sp : L.spare) { if (sp.d) (void)hipFree(sp.d); for (hipEvent_t e : sp.ev) if (e) (void)hipEventDestroy(e); }
         if (L.proj) (void)hipFree(L.proj);
         if (L.trects) (void)hipFree(L.trects);
@@ -1334,6 +1362,62 @@ int gs4d_compact_time_window(gs4d_ctx* c, gs4d_buf spans, size_t n, float t0, fl
     return compact_by_table(c, "compact_time_window", "spans", false, spans, sizeof(gs4d_time_span), n, src, stride, dst, kept_index, count,
         [&](Lane& L, const void* table, const void* records, void* out, uint32_t* index, uint32_t cap, gs4d_compact_count* cnt) {
             return launch_compact(L.s, (const gs4d_time_span*)table, n, k, L.compact_counts, records, stride, out, index, cap, cnt);
+        });
+}
+
+// ---- spatial order ----
+int gs4d_spatial_order(gs4d_ctx* c, gs4d_buf src, size_t n, size_t stride, size_t pos_offset, gs4d_buf order_index) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("spatial_order: ") + msg).c_str()); };
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    if (n == 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
+    if (!record_stride_ok(stride)) return bad("stride must be a multiple of 16 from 16 to 1024");
+    if (pos_offset % 4 != 0 || pos_offset + 12 > stride) return bad("pos_offset must be a multiple of 4 with pos_offset + 12 <= stride");
+    const gs4d_buf names[2] = { src, order_index };
+    Buffer* S = getbuf(c, src); Buffer* O = getbuf(c, order_index);
+    if (!S || !O) return bad("bad buffer name");
+    if (check_record_names(c, names, 2)) return bad("src and order_index must be different buffers");
+    if (S->bytes / stride < n) return bad("src holds fewer than n records");
+    if (O->bytes / 4 < n) return bad("order_index holds fewer than n entries");
+    if (n == 0) return GS4D_OK;
+    { int rc = flush_order_if_named(c, names, 2); if (rc) return rc; }
+    const size_t box_words = order_box_words();
+    return queue_on_lane(c, { S }, { O },
+        [&](Lane& L) {
+            HIPCHK(c, grow_device_array(L.s, L.spatial_scratch, L.spatial_cap, box_words + n));
+            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));      // (the tile sort's scratch: a histogram a queued keygen has left in depth_sort stays where it is)
+            return (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            uint32_t* const keys = L.spatial_scratch + box_words;
+            HIPCHK(c, launch_order_keys(L.s, S->d, n, stride, pos_offset, (float*)L.spatial_scratch, keys));
+            // the stable sort of the identity by key: the first pass that moves keys makes the indices up
+            HIPCHK(c, radix_sort_pairs(L.s, L.pair_sort, keys, (uint32_t*)O->d, n, nullptr, ORDER_KEY_BITS, false, true));
+            return (int)GS4D_OK;
+        });
+}
+
+int gs4d_gather_records(gs4d_ctx* c, gs4d_buf index, size_t m, gs4d_buf src, size_t nsrc, size_t stride, gs4d_buf dst) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("gather_records: ") + msg).c_str()); };
+    if (m > 0xFFFFFFFFull || nsrc > 0xFFFFFFFFull) return bad("more than 2^32 - 1 entries or records");
+    if (!record_stride_ok(stride) && stride != 4 && stride != 8) return bad("stride must be a multiple of 16 from 16 to 1024, or 4 or 8");
+    const gs4d_buf names[3] = { index, src, dst };
+    Buffer* X = getbuf(c, index); Buffer* S = getbuf(c, src); Buffer* D = getbuf(c, dst);
+    if (!X || !S || !D) return bad("bad buffer name");
+    if (check_record_names(c, names, 3)) return bad("index, src and dst must be different buffers");
+    if (X->bytes / 4 < m) return bad("index holds fewer than m entries");
+    if (S->bytes / stride < nsrc) return bad("src holds fewer than nsrc records");
+    if (D->bytes / stride < m) return bad("dst holds fewer than m records");
+    if (m == 0) return GS4D_OK;
+    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
+    return queue_on_lane(c, { X, S }, { D },
+        [&](Lane&) { return (int)GS4D_OK; },
+        [&](Lane& L) {
+            HIPCHK(c, launch_gather_records(L.s, (const uint32_t*)X->d, m, S->d, nsrc, stride, D->d));
+            return (int)GS4D_OK;
         });
 }
 

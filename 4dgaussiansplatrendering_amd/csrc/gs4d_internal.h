@@ -403,4 +403,17 @@ hipError_t launch_compact(hipStream_t st, const gs4d_time_span* spans, size_t n,
 // gs4d_record_time_spans: spans[i] of the n 96-byte records in `data` (one launch; n == 0: none)
 hipError_t launch_time_spans(hipStream_t st, const void* data, size_t n, float min_opacity, gs4d_time_span* spans);
 
+// ---- reorder.hip ----
+// gs4d_spatial_order (gs4d.h): the box of the placed records, then one 31-bit key per record — the 30-bit Morton code of its cell, or
+// ORDER_KEY_UNPLACED — three launches on `st`, no workgroup waits for another; the caller sorts the identity by the keys (radix_sort_pairs).
+constexpr uint32_t ORDER_KEY_UNPLACED = 0x40000000u;
+constexpr int ORDER_KEY_BITS = 31;
+constexpr uint32_t ORDER_BOX_GROUPS = 1024;      // workgroups of the box kernel at most (256 threads each, a grid stride beyond): one partial of 6 floats each
+inline uint32_t order_box_groups(size_t n) { const size_t g = (n + 255) / 256; return g < ORDER_BOX_GROUPS ? (uint32_t)g : ORDER_BOX_GROUPS; }
+// box_scratch: order_box_words() floats of scratch (the lane's): the box (lo[3], hi[3], 2 unused), then the partials
+inline size_t order_box_words() { return 8 + (size_t)ORDER_BOX_GROUPS * 6; }
+hipError_t launch_order_keys(hipStream_t st, const void* src, size_t n, size_t stride, size_t pos_offset, float* box_scratch, uint32_t* keys);
+// gs4d_gather_records: dst slot j <- the `stride` bytes (a multiple of 16; or 4 or 8) of src record index[j], j < m; an entry >= nsrc leaves its slot as it is
+hipError_t launch_gather_records(hipStream_t st, const uint32_t* index, size_t m, const void* src, size_t nsrc, size_t stride, void* dst);
+
 } // namespace gs4d

@@ -310,6 +310,49 @@ GS4D_API int gs4d_record_time_spans(gs4d_ctx* ctx, gs4d_buf data, size_t n, floa
 GS4D_API int gs4d_compact_time_window(gs4d_ctx* ctx, gs4d_buf spans, size_t n, float t0, float t1,
                                       gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count);
 
+/* ---- spatial order: a record set reordered so that neighbours in space are neighbours in memory (no reference counterpart) ----
+ * The draws gather projected records per tile: a set uploaded in Morton order of its positions draws faster than the same set in random order
+ * (12 % at 10^7 splats), and the compactions above keep such an order.  Two explicit calls, once per upload:
+ * gs4d_spatial_order computes the permutation, gs4d_gather_records applies it — or any other index list — to the records and to every table that
+ * has a row per record (time spans, statistics rows, the caller's own attributes).
+ *
+ * gs4d_spatial_order: order_index[j] = the record that comes j-th in spatial order (uint32), j < n.  All arithmetic is float32, round to
+ * nearest, no contraction, correctly rounded division.  The position p of record i is the three floats at src + i*stride + pos_offset
+ * (SplatData: 0; the four 72-byte vertices of a quad: 0, its first vertex).
+ *     placed    record i is PLACED iff p[0], p[1] and p[2] are all finite; any other record is UNPLACED;
+ *     box       lo[a] / hi[a] = the smallest / largest p[a] over the placed records, a = 0, 1, 2;
+ *     cell      of a placed record: d = p[a] - lo[a], e = hi[a] - lo[a], g = (d / e) * 1023.0f, cell[a] = g >= 0 ? (uint32) min(g, 1023.0f) : 0 — a NaN
+ *               gives 0, so a degenerate axis (e == 0: 0 / 0) and a box whose extent overflows (e == inf) need no special case; the sign of a
+ *               zero lo or hi cannot change a cell;
+ *     key       placed: the 30-bit Morton code of the cell — bit k of cell[0] at bit 3k, of cell[1] at 3k + 1, of cell[2] at 3k + 2; unplaced:
+ *               0x40000000, so these records come last;
+ *     order     order_index = the stable ascending sort of 0 .. n-1 by key: records of equal key keep the caller's order, and nothing depends
+ *               on the order in which anything runs on the device.
+ * GS4D_E_INVALID, with nothing queued and nothing written: n > 0xFFFFFFFF (and n == 0xFFFFFFFF: the sort takes 2^32 - 2 elements at most); a stride
+ * that is not a multiple of 16 in 16 .. 1024; pos_offset % 4 != 0 or pos_offset + 12 > stride; a name that is not a live buffer; src ==
+ * order_index; src smaller than n * stride bytes or order_index smaller than 4n.  n == 0 is a no-op.
+ *
+ * gs4d_gather_records: slot j of dst (the `stride` bytes at dst + j*stride) <- the `stride` bytes of src record index[j], j < m; src holds nsrc
+ * records.  An entry index[j] >= nsrc leaves slot j as it is; no byte outside any buffer is read or written, whatever the list holds; entries may
+ * repeat.  With the order_index above it reorders a set; with the kept_index of a compaction it carries a side table along.  stride: a multiple of
+ * 16, 16 .. 1024, as everywhere — or 4 or 8, the rows of a table of words (an index list) or of gs4d_time_span.
+ * GS4D_E_INVALID, nothing queued, nothing written: m or nsrc > 0xFFFFFFFF; any other stride; a name that is not a live buffer; any two of the three
+ * buffers being the same buffer; index smaller than 4m bytes, src smaller than nsrc * stride or dst smaller than m * stride.  m == 0 is a no-op.
+ *
+ * Ordering of both, as gs4d_compact_time_window: a queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first; the
+ * kernels are queued on the current frame lane and the call returns at once; src and index are buffers the call reads, order_index and dst
+ * ordinary buffers it writes (draws that may still need them are settled first; later calls, other lanes and the host order themselves behind
+ * it; what the library derives from dst's contents is rebuilt).  gs4d_buffer_invalidate hand-offs of any of the buffers are honoured.
+ *
+ * The guarantee.  With the default blend function and GS4D_MODE_4D_SORTED after gs4d_keygen + gs4d_sort_pairs (of the respective set): if no two
+ * records of the set have the same depth key, a draw of the set gathered through order_index gives the same bits as a draw of the original set
+ * in the colour image, the aux planes, the ID planes (record r of the gathered set is record order_index[r] of the original) and the record
+ * statistics (row r of the gathered set's table equals row order_index[r] of the original's).  Records of EQUAL depth key blend in buffer order,
+ * which a reorder may swap: the picture then stays within the checker's tolerance but is not promised bit-equal.  GS4D_MODE_4D_DIRECT,
+ * GS4D_MODE_2D and gs4d_draw_quads blend in instance order: reordering their records changes the blend order and with it the picture. */
+GS4D_API int gs4d_spatial_order(gs4d_ctx* ctx, gs4d_buf src, size_t n, size_t stride, size_t pos_offset, gs4d_buf order_index);
+GS4D_API int gs4d_gather_records(gs4d_ctx* ctx, gs4d_buf index, size_t m, gs4d_buf src, size_t nsrc, size_t stride, gs4d_buf dst);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
