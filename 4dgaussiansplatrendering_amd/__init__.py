@@ -23,6 +23,7 @@ DST_ALPHA, ONE_MINUS_DST_ALPHA, DST_COLOR, ONE_MINUS_DST_COLOR = 0x0304, 0x0305,
 CONSTANT_COLOR, ONE_MINUS_CONSTANT_COLOR, CONSTANT_ALPHA, ONE_MINUS_CONSTANT_ALPHA = 0x8001, 0x8002, 0x8003, 0x8004
 KEY_REF_INV_EUCLID, KEY_VIEW_Z = 0, 1
 KEEP_INVERT = 1                                           # gs4d_keep_rule.flags: keep exactly the records the rule would drop
+STAT_PIXELS, STAT_WMAX, STAT_WSUM = 0, 1, 2               # gs4d_stat_cut: the field of gs4d_record_stat
 TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
@@ -85,6 +86,7 @@ def _load():
         "gs4d_set_depth_test": (i32, [vp, u32]),
         "gs4d_set_record_stats": (i32, [vp, u32, sz]),
         "gs4d_compact_records": (i32, [vp, u32, sz, vp, u32, sz, u32, u32, u32]),
+        "gs4d_stat_cut": (i32, [vp, u32, sz, i32, sz, u32]),
         "gs4d_record_time_spans": (i32, [vp, u32, sz, f32, u32]),
         "gs4d_compact_time_window": (i32, [vp, u32, sz, f32, f32, u32, sz, u32, u32, u32]),
         "gs4d_spatial_order": (i32, [vp, u32, sz, sz, sz, u32]),
@@ -597,6 +599,45 @@ class Context:
         self.delete(count)
         if (got, written) != (kept, kept):
             raise Gs4dError(f"prune: the table changed between the two passes ({kept} kept, then {got} kept / {written} written)")
+        return dst, kept_index, kept
+
+    # to a budget: the threshold of one statistics field that keeps the records that matter most
+    STAT_FIELDS = {"pixels": STAT_PIXELS, "wmax": STAT_WMAX, "wsum": STAT_WSUM}
+    CUT = np.dtype([("value", "<u8"), ("above", "<u4"), ("equal", "<u4")])
+
+    def stat_cut(self, stats, n, budget, field="wsum", out=None):
+        """gs4d_stat_cut: the k-th largest value, k = min(budget, n), of one field ("pixels", "wmax" as its bit pattern, "wsum"; or a
+        STAT_* constant) of the n record_stats rows of `stats`, with the number of rows above it and equal to it, as one CUT {value, above,
+        equal} into `out` (a new 16-byte buffer if None).  A selection on the device: no sort, no permutation.  Asynchronous; returns `out`."""
+        if out is None:
+            out = self.buffer(nbytes=self.CUT.itemsize)
+        self._chk(_lib.gs4d_stat_cut(self._h, int(stats), int(n), int(self.STAT_FIELDS.get(field, field)), int(budget), int(out)))
+        return out
+
+    def read_stat_cut(self, out):
+        """(value, above, equal) of a stat_cut call; blocks until its kernels have finished."""
+        c = self.read(out, self.CUT, 1)[0]
+        return int(c["value"]), int(c["above"]), int(c["equal"])
+
+    def prune_to_budget(self, stats, n, src, budget, field="wsum", stride=96):
+        """At most `budget` of the n records of `src`, those with the largest `field`, in exact-size new buffers and in their original order:
+        stat_cut, one 16-byte read-back, compact_records with the field's threshold at `value` if above + equal <= budget, else at value + 1
+        (a tie at the cut that does not fit is dropped whole) — no count-only pass, and no second read-back: `kept` follows from the cut.  Returns (dst, kept_index, kept), as prune does; the
+        buffers hold at least 16 bytes, so kept == 0 (nothing above a tie that does not fit) still gives valid names."""
+        out = self.stat_cut(stats, n, budget, field)
+        value, above, equal = self.read_stat_cut(out)
+        self.delete(out)
+        fits = above + equal <= int(budget)
+        kept = above + equal if fits else above
+        dst, kept_index = self.buffer(nbytes=max(16, kept * int(stride))), self.buffer(nbytes=max(16, kept * 4))
+        if kept == 0:
+            return dst, kept_index, 0
+        rule = np.zeros(1, self.KEEP_RULE)
+        name = {v: k for k, v in self.STAT_FIELDS.items()}.get(field, field)
+        rule["min_" + name] = value if fits else value + 1       # (kept > 0: value + 1 does not leave the field)
+        count = self.buffer(nbytes=self.COMPACT_COUNT.itemsize)
+        self._chk(_lib.gs4d_compact_records(self._h, int(stats), int(n), _ptr(rule), int(src), int(stride), int(dst), int(kept_index), int(count)))
+        self.delete(count)                                       # (nothing between the cut and the compaction adds to the table: the count is `kept`)
         return dst, kept_index, kept
 
     # time windows: the records of a 4D set that can show anything between two times (DESIGN.md §4)

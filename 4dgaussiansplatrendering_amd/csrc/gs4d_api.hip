@@ -134,6 +134,7 @@ struct Lane {
     float* line_verts = nullptr; size_t line_cap = 0;   // device copy of the vertices of the latest gs4d_draw_lines (the lane's stream orders its reuse)
     uint32_t* compact_counts = nullptr; size_t compact_cap = 0;   // gs4d_compact_records: one word per tile of COMPACT_TILE records (counts, then first slots); the lane's stream orders its reuse
     uint32_t* spatial_scratch = nullptr; size_t spatial_cap = 0;      // gs4d_spatial_order: the box and its partials (order_box_words()), then one key per record; the lane's stream orders its reuse
+    uint32_t* cut_scratch = nullptr; size_t cut_cap = 0;               // gs4d_stat_cut: the state block and one partial histogram per workgroup (cut_scratch_words()); the lane's stream orders its reuse
     uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
     uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
     gs4d_buf kg_buf = 0; uint64_t kg_ver = 0;         // key buffer whose digit histograms k_keygen left for the next sort
@@ -866,6 +867,28 @@ int queue_on_lane(gs4d_ctx* c, std::initializer_list<Buffer*> in, std::initializ
     return launch(L);
 }
 
+// A statistics table as a host read takes it: behind every draw issued so far, on every lane, re-runs included (settling draws does not move the
+// current lane)
+int settle_stats_table(gs4d_ctx* c, Buffer& S) { return S.stats_target ? host_access(c, S) : (int)GS4D_OK; }
+// Kernels on lane L that read a table draws ADD to (Buffer::ev_scan, scan_wait) — three steps around their launch.  reserve: the event, with
+// everything else that can fail without a kernel.
+int scan_reserve(gs4d_ctx* c, Buffer& S) {
+    if (!S.ev_scan) HIPCHK(c, hipEventCreateWithFlags(&S.ev_scan, hipEventDisableTiming));
+    return GS4D_OK;
+}
+// before the launch: an earlier scan of the same table that another lane's draws still have to wait for — this lane waits for it, so that the event
+// recorded behind the launch covers both
+int scan_begin(gs4d_ctx* c, Lane& L, Buffer& S) {
+    if (S.scan_wait & (1u << c->cur)) HIPCHK(c, hipStreamWaitEvent(L.s, S.ev_scan, 0));
+    return GS4D_OK;
+}
+// behind the launch: draws that add to the table on the other lanes from now on wait until these kernels have read it (order_record_stats)
+int scan_end(gs4d_ctx* c, Lane& L, Buffer& S) {
+    HIPCHK(c, hipEventRecord(S.ev_scan, L.s));
+    S.scan_wait = ((1u << c->nlanes) - 1u) & ~(1u << c->cur);
+    return GS4D_OK;
+}
+
 // What gs4d_compact_records and gs4d_compact_time_window share: a table of one row of `row_bytes` per record (`what` names it in the messages) decides
 // which of n records go from src to dst.  stats_table: the table is one that draws ADD to (Buffer::ev_scan).  launch(lane, table, records or null,
 // dst or null, kept_index or null, cap) queues the kernels.
@@ -890,26 +913,16 @@ int compact_by_table(gs4d_ctx* c, const char* fn, const char* what, bool stats_t
     if (D) cap = (uint32_t)std::min<size_t>(cap, D->bytes / stride);
     if (X) cap = (uint32_t)std::min<size_t>(cap, X->bytes / 4);
     { int rc = flush_order_if_named(c, names, 5); if (rc) return rc; }
-    // a statistics table as a host read takes it: behind every draw issued so far, on every lane, re-runs included
-    if (S->stats_target) { int rc = host_access(c, *S); if (rc) return rc; }
-    const unsigned me = 1u << c->cur;              // (settling draws does not move the current lane)
+    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
     return queue_on_lane(c, { S, R }, { D, X, C },
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.compact_counts, L.compact_cap, std::max<size_t>(1, compact_tiles(n))));
-            if (stats_table && !S->ev_scan) HIPCHK(c, hipEventCreateWithFlags(&S->ev_scan, hipEventDisableTiming));
-            return (int)GS4D_OK;
+            return stats_table ? scan_reserve(c, *S) : (int)GS4D_OK;
         },
         [&](Lane& L) {
-            // an earlier compaction of the same table that another lane's draws still have to wait for: this lane waits for it, so that the event recorded
-            // below covers both
-            if (stats_table && (S->scan_wait & me)) HIPCHK(c, hipStreamWaitEvent(L.s, S->ev_scan, 0));
+            if (stats_table) { int rc = scan_begin(c, L, *S); if (rc) return rc; }
             HIPCHK(c, launch(L, S->d, R ? R->d : nullptr, D ? D->d : nullptr, X ? (uint32_t*)X->d : nullptr, cap, (gs4d_compact_count*)C->d));
-            if (stats_table) {
-                // draws that add to the table on the other lanes from now on wait until these kernels have read it (order_record_stats)
-                HIPCHK(c, hipEventRecord(S->ev_scan, L.s));
-                S->scan_wait = ((1u << c->nlanes) - 1u) & ~me;
-            }
-            return (int)GS4D_OK;
+            return stats_table ? scan_end(c, L, *S) : (int)GS4D_OK;
         });
 }
 
@@ -991,6 +1004,7 @@ void gs4d_destroy(gs4d_ctx* c) {
         if (L.regen_keys) (void)hipFree(L.regen_keys);
         if (L.compact_counts) (void)hipFree(L.compact_counts);
         if (L.spatial_scratch) (void)hipFree(L.spatial_scratch);
+        if (L.cut_scratch) (void)hipFree(L.cut_scratch);
         for (auto& sp : L.spare) { if (sp.d) (void)hipFree(sp.d); for (hipEvent_t e : sp.ev) if (e) (void)hipEventDestroy(e); }
         if (L.proj) (void)hipFree(L.proj);
         if (L.trects) (void)hipFree(L.trects);
@@ -1330,6 +1344,35 @@ int gs4d_compact_records(gs4d_ctx* c, gs4d_buf stats, size_t n, const gs4d_keep_
     return compact_by_table(c, "compact_records", "stats", true, stats, sizeof(gs4d_record_stat), n, src, stride, dst, kept_index, count,
         [&](Lane& L, const void* table, const void* records, void* out, uint32_t* index, uint32_t cap, gs4d_compact_count* cnt) {
             return launch_compact(L.s, (const gs4d_record_stat*)table, n, k, L.compact_counts, records, stride, out, index, cap, cnt);
+        });
+}
+
+// ---- to a budget ----
+int gs4d_stat_cut(gs4d_ctx* c, gs4d_buf stats, size_t n, int field, size_t budget, gs4d_buf out) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("stat_cut: ") + msg).c_str()); };
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 rows");
+    if (budget == 0) return bad("budget == 0");
+    if (field != GS4D_STAT_PIXELS && field != GS4D_STAT_WMAX && field != GS4D_STAT_WSUM) return bad("unknown field");
+    const gs4d_buf names[2] = { stats, out };
+    Buffer* S = getbuf(c, stats); Buffer* O = getbuf(c, out);
+    if (!S || !O) return bad("bad buffer name");
+    if (check_record_names(c, names, 2)) return bad("stats and out must be different buffers");
+    if (S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (O->bytes < sizeof(gs4d_cut)) return bad("out holds fewer than 16 bytes");
+    const uint32_t k = (uint32_t)std::min(budget, n);
+    { int rc = flush_order_if_named(c, names, 2); if (rc) return rc; }
+    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    return queue_on_lane(c, { S }, { O },
+        [&](Lane& L) {
+            HIPCHK(c, grow_device_array(L.s, L.cut_scratch, L.cut_cap, cut_scratch_words(n)));
+            return scan_reserve(c, *S);
+        },
+        [&](Lane& L) {
+            { int rc = scan_begin(c, L, *S); if (rc) return rc; }
+            HIPCHK(c, launch_stat_cut(L.s, (const gs4d_record_stat*)S->d, n, field, k, L.cut_scratch, (gs4d_cut*)O->d));
+            return scan_end(c, L, *S);
         });
 }
 

@@ -416,4 +416,18 @@ hipError_t launch_order_keys(hipStream_t st, const void* src, size_t n, size_t s
 // gs4d_gather_records: dst slot j <- the `stride` bytes (a multiple of 16; or 4 or 8) of src record index[j], j < m; an entry >= nsrc leaves its slot as it is
 hipError_t launch_gather_records(hipStream_t st, const uint32_t* index, size_t m, const void* src, size_t nsrc, size_t stride, void* dst);
 
+// ---- cut.hip ----
+// gs4d_stat_cut (gs4d.h): a radix select over one field of a statistics table, most significant digit first — per digit one histogram
+// launch and one pick launch on `st`, no workgroup waits for another.
+constexpr uint32_t CUT_DIGIT_BITS = 8, CUT_BINS = 1u << CUT_DIGIT_BITS;      // 4 digits for pixels and wmax, 8 for wsum
+constexpr uint32_t CUT_TILE = 2048;              // rows per workgroup and round of the histogram kernel (256 threads, 8 rows each in flight)
+constexpr uint32_t CUT_GROUPS = 1024;            // workgroups of the histogram kernel at most (a grid stride beyond): one partial of CUT_BINS words each
+constexpr uint32_t CUT_STATE_WORDS = 4;          // {prefix (64 bits), rank remaining, above so far}: written by a pick kernel, read by the next digit's kernels
+inline int cut_passes(int field) { return (field == GS4D_STAT_WSUM ? 64 : 32) / (int)CUT_DIGIT_BITS; }
+inline uint32_t cut_groups(size_t n) { const size_t g = (n + CUT_TILE - 1) / CUT_TILE; return g < CUT_GROUPS ? (uint32_t)g : CUT_GROUPS; }
+// scratch: cut_scratch_words(n) words (the lane's): the state block, then the partials
+inline size_t cut_scratch_words(size_t n) { return CUT_STATE_WORDS + (size_t)cut_groups(n) * CUT_BINS; }
+// n rows of `stats`, field GS4D_STAT_*, k = min(budget, n) (>= 1 unless n == 0): *out receives the gs4d_cut; n == 0: {0, 0, 0}, one launch
+hipError_t launch_stat_cut(hipStream_t st, const gs4d_record_stat* stats, size_t n, int field, uint32_t k, uint32_t* scratch, gs4d_cut* out);
+
 } // namespace gs4d

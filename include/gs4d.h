@@ -276,6 +276,33 @@ typedef struct gs4d_compact_count { uint32_t kept, written; } gs4d_compact_count
 GS4D_API int gs4d_compact_records(gs4d_ctx* ctx, gs4d_buf stats, size_t n, const gs4d_keep_rule* rule,
                                   gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count);
 
+/* ---- to a budget: the threshold of one statistics field that keeps the k records that matter most (no reference counterpart) ----
+ * A k-th-largest selection over one field of the table, on the device: no sort, no permutation — the compaction that follows stays stable.
+ * f[i] is the chosen field of row i of the n rows of gs4d_record_stat in `stats`, as a uint64: GS4D_STAT_PIXELS and GS4D_STAT_WMAX are the
+ * uint32 zero-extended (wmax as its bit pattern, which is in float order: w >= 0), GS4D_STAT_WSUM is the uint64.  With k = min(budget, n):
+ *     value = the k-th largest of f[0 .. n), counted with multiplicity (the value at position k - 1 of f sorted in descending order);
+ *     above = #{i : f[i] >  value}, which is < k;
+ *     equal = #{i : f[i] == value}, and above + equal >= k.
+ * n == 0 writes {0, 0, 0}.  `out` receives the 16 bytes of a gs4d_cut at offset 0; no other byte of any buffer is written.
+ * What the caller does with it: a gs4d_keep_rule whose threshold for the field is `value` (the other two 0) keeps above + equal records — at
+ * least k, exactly k when there is no tie at the cut — and one whose threshold is value + 1 keeps `above` records, fewer than k (value at the
+ * field's maximum: above = 0, nothing to keep); in both cases `kept` is known without a count-only compaction pass.
+ * GS4D_E_INVALID, with nothing queued and nothing written: n > 0xFFFFFFFF; budget == 0; a field other than the three; a name that is not a live
+ * buffer; stats == out; stats smaller than 16 n bytes; out smaller than 16 bytes.
+ * Ordering: exactly that of gs4d_compact_records.  The table is taken as gs4d_buffer_read takes it — every draw issued before the call, on every
+ * frame lane, has been settled (re-runs included) — and a queued gs4d_keygen / gs4d_sort_pairs that names one of the two buffers is launched
+ * first.  The kernels are then queued on the current frame lane, the call returns without waiting for them and starts no new frame; `out` is an
+ * ordinary written buffer afterwards (gs4d_buffer_read of it waits for the kernels).  The result is that of the table as it stands at the call: a
+ * draw issued afterwards that adds to the same table, on any lane, waits on the device until the call's kernels have read it, and a host write
+ * (gs4d_buffer_subdata) waits as it does for any reader.  All sums are sums of integers: the result does not depend on the order of anything. */
+enum { GS4D_STAT_PIXELS = 0, GS4D_STAT_WMAX = 1, GS4D_STAT_WSUM = 2 };
+typedef struct gs4d_cut {
+    uint64_t value;    /* the k-th largest value of the field (a uint32 field zero-extended) */
+    uint32_t above;    /* rows whose field is greater than value: < k                       */
+    uint32_t equal;    /* rows whose field equals value: above + equal >= k                 */
+} gs4d_cut;
+GS4D_API int gs4d_stat_cut(gs4d_ctx* ctx, gs4d_buf stats, size_t n, int field, size_t budget, gs4d_buf out);
+
 /* ---- time windows: the records of a 4D set that can show anything between two times (no reference counterpart) ----
  * A 4D draw gives record i the opacity ot = max(expf(arg(uTime)), uMinOpacity) and the alpha ot * colour.a, with
  *     arg(t) = ((-0.5f * dt) * (1.0f / s44)) * dt,  dt = t - mu_t     (float32, round to nearest, no contraction: the draw's own operations)
