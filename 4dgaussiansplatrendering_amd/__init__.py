@@ -87,6 +87,7 @@ def _load():
         "gs4d_set_record_stats": (i32, [vp, u32, sz]),
         "gs4d_compact_records": (i32, [vp, u32, sz, vp, u32, sz, u32, u32, u32]),
         "gs4d_stat_cut": (i32, [vp, u32, sz, i32, sz, u32]),
+        "gs4d_count_ids": (i32, [vp, vp, u32, u32, sz]),
         "gs4d_record_time_spans": (i32, [vp, u32, sz, f32, u32]),
         "gs4d_compact_time_window": (i32, [vp, u32, sz, f32, f32, u32, sz, u32, u32, u32]),
         "gs4d_spatial_order": (i32, [vp, u32, sz, sz, sz, u32]),
@@ -298,6 +299,12 @@ class CameraState(C.Structure):
         st.sensitivity, st.speed, st.fast_speed = 100.0, 0.5, 2.0          # Camera.h:78-80
         st.first_capture = 1
         return st
+
+
+class IdRegion(C.Structure):
+    """gs4d_id_region (include/gs4d.h): the rectangle, the draws and the least weight of a gs4d_count_ids call."""
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("draw_first", C.c_uint32), ("draw_last", C.c_uint32),
+                ("min_weight", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class CameraInput(C.Structure):
@@ -639,6 +646,45 @@ class Context:
         self._chk(_lib.gs4d_compact_records(self._h, int(stats), int(n), _ptr(rule), int(src), int(stride), int(dst), int(kept_index), int(count)))
         self.delete(count)                                       # (nothing between the cut and the compaction adds to the table: the count is `kept`)
         return dst, kept_index, kept
+
+    # selection: a statistics table from a region of the ID planes
+    def count_ids(self, stats, n, rect=None, mask=None, draws=None, min_weight=0.0):
+        """gs4d_count_ids: every pixel of `rect` ((x, y, w, h), y from the bottom row; None: the whole image) of the current frame's ID planes
+        whose record is below n, whose draw ordinal lies in `draws` (an int, or a (first, last) pair; None: every draw), whose weight is >=
+        min_weight and whose `mask` byte is non-zero (a buffer of w*h bytes, rows bottom-up, or an (h, w) bool / uint8 array that is uploaded
+        for the call; None: no mask) adds one fragment to row record of the record_stats buffer `stats`: pixels += 1, wmax = max(wmax,
+        weight), wsum += rint(weight * 2^24).  Nothing zeroes `stats`: calls add up.  Asynchronous with a buffer mask or none; an array mask is
+        uploaded and deleted again, and deleting a buffer waits for every frame lane: keep the mask in a buffer where that matters."""
+        x, y, w, h = rect if rect is not None else (0, 0, self.width, self.height)
+        first, last = (0, 0xFFFFFFFF) if draws is None else (int(draws), int(draws)) if np.ndim(draws) == 0 else (int(draws[0]), int(draws[1]))
+        region = IdRegion(int(x), int(y), int(w), int(h), first, last, int(np.array([min_weight], np.float32).view(np.uint32)[0]), 0)
+        own = mask is not None and not isinstance(mask, (int, np.integer))
+        if own:
+            a = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if a.shape != (h, w):
+                raise ValueError(f"count_ids: expected a mask of shape {(h, w)}, got {a.shape}")
+            mask = self.buffer(a)
+        try:
+            self._chk(_lib.gs4d_count_ids(self._h, C.byref(region), int(mask or 0), int(stats), int(n)))
+        finally:
+            if own:
+                self.delete(mask)
+
+    def select(self, n, src=None, stride=96, rect=None, mask=None, draws=None, min_weight=0.0):
+        """The records of the n that some pixel of the region shows (count_ids into a zeroed table, then compact_records with min_pixels=1), in
+        exact-size new buffers and in their original order.  Returns (dst, kept_index, kept, stats): as prune does, and the table, whose rows
+        say how much of the region each record holds (stat_cut on it: the k most visible).  src None: no records are copied (dst is None).
+        Blocking, as prune is: it reads the count back."""
+        stats = self.record_stats(n)
+        self.count_ids(stats, n, rect=rect, mask=mask, draws=draws, min_weight=min_weight)
+        if src is not None:
+            return self.prune(stats, n, src, stride=stride, min_pixels=1) + (stats,)
+        count = self.compact_records(stats, n, stride=stride, min_pixels=1)
+        kept, _ = self.read_compact_count(count)
+        kept_index = self.buffer(nbytes=max(16, kept * 4))
+        self.compact_records(stats, n, stride=stride, kept_index=kept_index, count=count, min_pixels=1)
+        self.delete(count)
+        return None, kept_index, kept, stats
 
     # time windows: the records of a 4D set that can show anything between two times (DESIGN.md §4)
     TIME_SPAN = np.dtype([("t_first", "<f4"), ("t_last", "<f4")])

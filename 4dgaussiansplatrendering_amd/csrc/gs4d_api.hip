@@ -1735,6 +1735,41 @@ int gs4d_read_ids_device(gs4d_ctx* c, void* record, void* draw, void* weight, si
     return read_device_common(c, 0, ReadPlane::Ids, dst);
 }
 
+// ---- selection: a statistics table from a region of the ID planes ----
+int gs4d_count_ids(gs4d_ctx* c, const gs4d_id_region* region, gs4d_buf mask, gs4d_buf stats, size_t nrecords) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("count_ids: ") + msg).c_str()); };
+    const gs4d_id_region g = region ? *region : gs4d_id_region{ 0, 0, c->W, c->H, 0u, 0xFFFFFFFFu, 0u, 0u };
+    if (g.reserved != 0u) return bad("non-zero reserved field in the region");
+    if (g.draw_first > g.draw_last) return bad("draw_first > draw_last");
+    if (nrecords > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    const gs4d_buf names[2] = { stats, mask };
+    Buffer* S = getbuf(c, stats); Buffer* M = getbuf(c, mask);
+    if (!S || (mask != 0 && !M)) return bad("bad buffer name");
+    if (check_record_names(c, names, 2)) return bad("mask and stats must be different buffers");
+    if (S->bytes / sizeof(gs4d_record_stat) < nrecords) return bad("the stats buffer holds fewer than nrecords rows");
+    if (g.x < 0 || g.y < 0 || g.w <= 0 || g.h <= 0 || g.w > c->W - g.x || g.h > c->H - g.y) return bad("the rectangle is empty or not inside the image");
+    if (M && M->bytes < (size_t)g.w * (size_t)g.h) return bad("the mask holds fewer than w*h bytes");
+    if (c->fbs[c->cur_fb].out < Outputs::Ids) return bad("the current frame was not cleared with ID outputs on");      // (before read_begin launches the queued order: a refused call queues nothing)
+    if (nrecords == 0) return GS4D_OK;
+    // the planes as gs4d_read_ids_device takes them: the queued order launched, the frame's draws settled, every tile in memory
+    { int rc = flush_order(c); if (rc) return rc; }
+    { int rc = resolve_image(c, c->cur_fb); if (rc) return rc; }
+    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    // stats as an "out" of queue_on_lane: the lane waits for whoever wrote the table AND for whoever still reads it or adds to it, which is what a
+    // read-modify-write needs; the new version and the dropped provenance are those of any kernel write
+    return queue_on_lane(c, { M }, { S },
+        [&](Lane&) { return (int)GS4D_OK; },
+        [&](Lane& L) {
+            Framebuffer& F = c->fbs[c->cur_fb];
+            { int rc = fb_access(c, F); if (rc) return rc; }
+            { int rc = materialise_fb(c, F, L); if (rc) return rc; }
+            HIPCHK(c, launch_count_ids(L.s, F.ids, c->W, c->H, g, M ? (const uint8_t*)M->d : nullptr, (gs4d_record_stat*)S->d, (uint32_t)nrecords));
+            return (int)GS4D_OK;
+        });
+}
+
 int gs4d_read_pixels_rgba8_device(gs4d_ctx* c, void* dptr, size_t bytes) {
     if (!c || !dptr) return GS4D_E_INVALID;
     int rc = read_begin(c, bytes == (size_t)c->W * c->H * 4, "read_pixels_rgba8_device: bytes != width*height*4"); if (rc) return rc;

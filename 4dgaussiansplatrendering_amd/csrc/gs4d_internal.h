@@ -430,4 +430,10 @@ inline size_t cut_scratch_words(size_t n) { return CUT_STATE_WORDS + (size_t)cut
 // n rows of `stats`, field GS4D_STAT_*, k = min(budget, n) (>= 1 unless n == 0): *out receives the gs4d_cut; n == 0: {0, 0, 0}, one launch
 hipError_t launch_stat_cut(hipStream_t st, const gs4d_record_stat* stats, size_t n, int field, uint32_t k, uint32_t* scratch, gs4d_cut* out);
 
+// ---- select.hip ----
+// gs4d_count_ids (gs4d.h): every pixel of rectangle g of the ID planes (ids, ids + W*H, ids + 2*W*H: record, draw, weight) that takes
+// part adds one fragment to stats[record] — one launch on `st`.  g: validated (inside the W x H image, draw_first <= draw_last); mask: g.w * g.h
+// bytes, or null: none.  No row >= nrecords is touched and nothing outside the rectangle is read.
+hipError_t launch_count_ids(hipStream_t st, const uint32_t* ids, int W, int H, const gs4d_id_region& g, const uint8_t* mask, gs4d_record_stat* stats, uint32_t nrecords);
+
 } // namespace gs4d

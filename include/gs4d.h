@@ -303,6 +303,44 @@ typedef struct gs4d_cut {
 } gs4d_cut;
 GS4D_API int gs4d_stat_cut(gs4d_ctx* ctx, gs4d_buf stats, size_t n, int field, size_t budget, gs4d_buf out);
 
+/* ---- selection: a statistics table from a region of the ID planes (no reference counterpart) ----
+ * "What do I see in this region of this frame?", answered on the device as rows of an ordinary gs4d_record_stat table — so that everything
+ * that consumes such a table works on a selection unchanged: gs4d_compact_records with {1, 0, 0, 0} builds the selected set, its stable
+ * kept_index and its count; gs4d_stat_cut gives "the k most visible records of the region"; repeated calls add up into union selections.
+ * The call reads the planes {record, draw, weight} of the current frame, the ones gs4d_read_ids reads.  Pixel p = (x + c, y + r) of the
+ * rectangle (0 <= c < w, 0 <= r < h, row 0 = bottom) TAKES PART iff
+ *     record[p] != GS4D_ID_NONE  &&  record[p] < nrecords  &&  draw_first <= draw[p] <= draw_last  &&  bits(weight[p]) >= min_weight
+ *     && (mask == 0 || mask[r * w + c] != 0)
+ * where bits() is the weight's uint32 bit pattern (float order: w >= 0) and the mask is one byte per pixel of the rectangle, rows bottom-up,
+ * at least w*h bytes, any non-zero byte counting: a lasso is the rectangle around it and a mask.  Every pixel that takes part adds to row
+ * record[p] of `stats` exactly as one fragment of weight w = weight[p] adds in a draw with record statistics:
+ *     pixels += 1;   wmax = max(wmax, bits(w));   wsum += q(w),  the q of gs4d_record_stat.
+ * The call ADDS: nothing zeroes the table, and no byte outside rows [0, nrecords) is written, whatever the planes hold.  All three fields are
+ * integers: the result does not depend on the order of anything, and a table filled by several calls is the sum of the calls (pixels and wsum
+ * by +, wmax by max) — across rectangles, frames and tile-row shards (a sharded context's foreign rows hold the sentinel and count nothing),
+ * and on top of what draws have added to the same table.  region == NULL: the whole image, every draw, every weight.  nrecords == 0, with
+ * arguments that are otherwise valid, is a no-op: nothing is queued.  Not covered: the image the last gs4d_clear moved away from (frames_back 1 of gs4d_read_frame_*), and what lies behind the record a
+ * pixel shows — the planes keep one record per pixel; everything that contributes is a draw with gs4d_set_record_stats.
+ * GS4D_E_INVALID, with nothing queued and nothing written: the current frame was not cleared with ID outputs on; a rectangle that is empty or
+ * not inside the image; draw_first > draw_last; reserved != 0; nrecords > 0xFFFFFFFF; stats not a live buffer, or smaller than nrecords * 16
+ * bytes; mask neither 0 nor a live buffer, or smaller than w*h bytes; mask == stats.
+ * Ordering.  The planes are taken as gs4d_read_ids_device takes them: a queued gs4d_keygen / gs4d_sort_pairs is launched first, the frame's
+ * draws are settled (re-runs included), lazily clear tiles are materialised; the kernel is then queued on the current frame lane, and the
+ * call returns at once and starts no new frame.  A later draw into the same frame, or a later gs4d_clear that brings this image round again,
+ * does not change the result.  `stats` is a buffer the call writes with a kernel while keeping its contents: draws that add to it
+ * (gs4d_set_record_stats) and were issued before the call, on every frame lane, are settled first, as for gs4d_compact_records; draws issued
+ * afterwards, other lanes, the record-set calls and host accesses order themselves behind the call.  `mask` is a buffer the call reads: a
+ * later gs4d_buffer_subdata of it waits as it does for any reader.  gs4d_buffer_invalidate hand-offs of both buffers are honoured. */
+#define GS4D_ID_NONE 0xFFFFFFFFu          /* the record and draw of a pixel no fragment has reached */
+typedef struct gs4d_id_region {
+    int32_t  x, y, w, h;             /* rectangle inside the image, row 0 = bottom, as gs4d_read_ids                     */
+    uint32_t draw_first, draw_last;  /* a pixel takes part iff draw_first <= its draw ordinal <= draw_last                */
+    uint32_t min_weight;             /* ... and its weight, as a uint32 bit pattern, is >= min_weight (0: every weight)   */
+    uint32_t reserved;               /* must be 0                                                                         */
+} gs4d_id_region;                    /* 32 bytes */
+GS4D_API int gs4d_count_ids(gs4d_ctx* ctx, const gs4d_id_region* region /* NULL: whole image, every draw, every weight */,
+                            gs4d_buf mask /* 0: none */, gs4d_buf stats, size_t nrecords);
+
 /* ---- time windows: the records of a 4D set that can show anything between two times (no reference counterpart) ----
  * A 4D draw gives record i the opacity ot = max(expf(arg(uTime)), uMinOpacity) and the alpha ot * colour.a, with
  *     arg(t) = ((-0.5f * dt) * (1.0f / s44)) * dt,  dt = t - mu_t     (float32, round to nearest, no contraction: the draw's own operations)
