@@ -92,11 +92,13 @@ def _load():
         "gs4d_compact_time_window": (i32, [vp, u32, sz, f32, f32, u32, sz, u32, u32, u32]),
         "gs4d_spatial_order": (i32, [vp, u32, sz, sz, sz, u32]),
         "gs4d_gather_records": (i32, [vp, u32, sz, u32, sz, sz, u32]),
+        "gs4d_shade_sh": (i32, [vp, u32, sz, u32, sz, i32, f32, vp]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
         "gs4d_get_stats": (i32, [vp, vp]),
         "gs4d_debug_read_projected": (i32, [vp, vp, sz]),
+        "gs4d_debug_shadow_builds": (i32, [vp, u32, C.POINTER(C.c_uint64)]),
         "gs4d_host_look_at": (None, [vp, vp, vp, vp]),
         "gs4d_host_perspective": (None, [f32, i32, i32, f32, f32, vp]),
         "gs4d_host_key_bounds": (None, [vp, vp, f32, vp, i32, C.POINTER(u32), C.POINTER(u32)]),
@@ -361,6 +363,37 @@ def write_png(path, rgba8):
         raise ValueError("write_png: expected an (H, W, 4) uint8 array")
     if _lib.gs4d_host_write_png(os.fsencode(path), _ptr(a), a.shape[1], a.shape[0]) != 0:
         raise OSError(f"cannot write {path}")
+
+
+def sh_row_bytes(degree):
+    """The minimal row of gs4d_shade_sh's table for an SH degree: 12 (degree + 1)^2 bytes rounded up to 16 — 16 / 48 / 112 / 192."""
+    return (12 * (int(degree) + 1) ** 2 + 15) // 16 * 16
+
+
+def sh_rows(f_dc, f_rest, degree, stride=None):
+    """The table of gs4d_shade_sh from a 3DGS export's arrays: f_dc [n, 3] and f_rest [n, 3 ((D + 1)^2 - 1)] for the export's degree D >= degree,
+    channel-major as in the PLY (all R, then all G, then all B; None or empty for D = 0).  Returns uint8 [n, stride] (default: the minimal stride
+    of `degree`): float32 row[3k + channel], k < (degree + 1)^2, zero padded to the stride."""
+    f_dc = _f32(f_dc)
+    n = f_dc.shape[0]
+    if f_dc.shape != (n, 3):
+        raise ValueError("sh_rows: f_dc must be [n, 3]")
+    K = (int(degree) + 1) ** 2
+    if not 0 <= int(degree) <= 3:
+        raise ValueError("sh_rows: degree must be 0 .. 3")
+    stride = sh_row_bytes(degree) if stride is None else int(stride)
+    if stride % 16 or not 16 <= stride <= 1024 or stride < 12 * K:
+        raise ValueError("sh_rows: stride must be a multiple of 16 from 16 to 1024 that holds 12 (degree + 1)^2 bytes")
+    coeff = np.zeros((n, K, 3), np.float32)
+    coeff[:, 0, :] = f_dc
+    if K > 1:
+        rest = _f32(f_rest).reshape(n, -1)
+        if rest.shape[1] % 3 or rest.shape[1] // 3 < K - 1:
+            raise ValueError("sh_rows: f_rest must be [n, 3 ((D + 1)^2 - 1)] with D >= degree")
+        coeff[:, 1:, :] = rest.reshape(n, 3, -1)[:, :, :K - 1].transpose(0, 2, 1)
+    rows = np.zeros((n, stride), np.uint8)
+    rows[:, :12 * K] = coeff.reshape(n, 3 * K).view(np.uint8)
+    return rows
 
 
 # ---- device context -----------------------------------------------------------------------------
@@ -751,6 +784,22 @@ class Context:
         (data, n) when no two records share a depth key (gs4d.h); gather a table with a row per record through the same order_index."""
         order_index = self.spatial_order(data, n, stride=stride)
         return self.gather_records(order_index, n, data, n, stride=stride), order_index
+
+    # view-dependent colour: rgb from spherical harmonics (DESIGN.md §4)
+    def shade_sh(self, data, n, sh, degree, t, cam_pos, sh_stride=None):
+        """gs4d_shade_sh: floats 4..6 of the first n 96-byte records of `data` <- the colour of their rows of `sh` (float32 coefficients
+        row[3k + channel], see sh_rows) at SH degree 0..3, seen from cam_pos at time t.  sh_stride: bytes per row, a multiple of 16 up to 1024
+        (default: the minimal one for the degree, sh_row_bytes(degree)); a table of a higher degree is shaded through a prefix of its rows.
+        A colour-only write: a current SoA shadow is patched, not rebuilt.  Per frame: shade, keygen, sort, draw.  Asynchronous."""
+        if sh_stride is None:
+            sh_stride = sh_row_bytes(degree)
+        self._chk(_lib.gs4d_shade_sh(self._h, int(data), int(n), int(sh), int(sh_stride), int(degree), float(t), _ptr(_f32(cam_pos))))
+
+    def shadow_builds(self, buf):
+        """gs4d_debug_shadow_builds: how many times the SoA shadow of this record buffer has been (re)built."""
+        n = C.c_uint64(0)
+        self._chk(_lib.gs4d_debug_shadow_builds(self._h, int(buf), C.byref(n)))
+        return n.value
 
     def set_tile_shard(self, rank, world):
         """Single-frame sharding: this context bins and composites the tile rows ty % world == rank only."""

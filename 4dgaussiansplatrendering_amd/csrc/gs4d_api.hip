@@ -39,6 +39,7 @@ struct Buffer {
     SoaInfo soa_info;              // ... its layout (preprocess.hip): 64 B/record for static 3D splats, 72 for a symmetric sig, 96 otherwise
     size_t soa_n = 0;
     uint64_t soa_version = ~0ull;
+    uint64_t soa_builds = 0;       // times ensure_soa has (re)built the shadow (gs4d_debug_shadow_builds)
     uint32_t* bbox_dev = nullptr;  // 16 words: bounding box of pos / mu_t / velocity, reduced by the repack kernel
     double bb_lo[7] = { 0 }, bb_hi[7] = { 0 }; bool bb_ok = false;
     // cross-lane hazards
@@ -361,6 +362,7 @@ int ensure_soa(gs4d_ctx* c, Buffer& b) {
     b.bb_ok = n > 0 && got[14] == 0;
     for (int k = 0; k < 7; ++k) { b.bb_lo[k] = ord2f(got[k]); b.bb_hi[k] = ord2f(got[7 + k]); if (!(b.bb_lo[k] <= b.bb_hi[k])) b.bb_ok = false; }
     b.soa_version = b.version;
+    b.soa_builds++;
     return GS4D_OK;
 }
 
@@ -1464,6 +1466,38 @@ int gs4d_gather_records(gs4d_ctx* c, gs4d_buf index, size_t m, gs4d_buf src, siz
         });
 }
 
+// ---- view-dependent colour ----
+int gs4d_shade_sh(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_stride, int degree, float t, const float cam_pos[3]) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("shade_sh: ") + msg).c_str()); };
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    if (degree < 0 || degree > 3) return bad("degree must be 0, 1, 2 or 3");
+    if (!record_stride_ok(sh_stride)) return bad("sh_stride must be a multiple of 16 from 16 to 1024");
+    if (sh_stride < 12u * (size_t)((degree + 1) * (degree + 1))) return bad("sh_stride holds fewer than 12 (degree + 1)^2 bytes");
+    if (!cam_pos) return bad("cam_pos == NULL");
+    const gs4d_buf names[2] = { data, sh };
+    Buffer* D = getbuf(c, data); Buffer* S = getbuf(c, sh);
+    if (!D || !S) return bad("bad buffer name");
+    if (check_record_names(c, names, 2)) return bad("data and sh must be different buffers");
+    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
+    if (S->bytes / sh_stride < n) return bad("sh holds fewer than n rows");
+    if (n == 0) return GS4D_OK;
+    { int rc = flush_order_if_named(c, names, 2); if (rc) return rc; }
+    // A colour-only write: the shadow's layout choice, the bounding box and the key bounds read no colour, so a shadow that is current stays current —
+    // the kernel patches its colour plane (plane 1 in every layout: k_soa_repack) and soa_version moves on with version.  Decided once the pending
+    // draws are settled (a re-run may rebuild the shadow) and before any buffer state is touched.
+    bool patch = false;
+    const float cam[3] = { cam_pos[0], cam_pos[1], cam_pos[2] };
+    return queue_on_lane(c, { S }, { D },
+        [&](Lane&) { patch = D->soa && D->soa_n == D->bytes / 96 && D->soa_version == D->version; return (int)GS4D_OK; },
+        [&](Lane& L) {
+            HIPCHK(c, launch_shade_sh(L.s, D->d, n, S->d, sh_stride, degree, t, cam, patch ? D->soa + D->soa_n : nullptr));
+            if (patch) D->soa_version = D->version;
+            return (int)GS4D_OK;
+        });
+}
+
 // ---- draw ----
 static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     (void)hipSetDevice(c->device);
@@ -1932,6 +1966,14 @@ int gs4d_debug_read_projected(gs4d_ctx* c, float* out16, size_t nrecords) {
         const float a1x = r[3], a0y = r[4], cr = r[6], cg = r[7], cb = r[8], al = r[9];
         r[3] = a0y; r[4] = a1x; r[6] = al; r[7] = cr; r[8] = cg; r[9] = cb;
     }
+    return GS4D_OK;
+}
+
+int gs4d_debug_shadow_builds(gs4d_ctx* c, gs4d_buf buf, uint64_t* builds) {
+    if (!c || !builds) return GS4D_E_INVALID;
+    const Buffer* B = getbuf(c, buf);
+    if (!B) return fail(c, GS4D_E_INVALID, "debug_shadow_builds: bad buffer name");
+    *builds = B->soa_builds;
     return GS4D_OK;
 }
 

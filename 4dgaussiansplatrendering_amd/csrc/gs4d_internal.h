@@ -416,6 +416,13 @@ hipError_t launch_order_keys(hipStream_t st, const void* src, size_t n, size_t s
 // gs4d_gather_records: dst slot j <- the `stride` bytes (a multiple of 16; or 4 or 8) of src record index[j], j < m; an entry >= nsrc leaves its slot as it is
 hipError_t launch_gather_records(hipStream_t st, const uint32_t* index, size_t m, const void* src, size_t nsrc, size_t stride, void* dst);
 
+// ---- shade.hip ----
+// gs4d_shade_sh (gs4d.h): floats 4..6 of the first n 96-byte records <- the colour of row i of `sh` (sh_stride bytes per row, a multiple
+// of 16 that holds 12 (degree + 1)^2 bytes) seen from cam at time t.  plane1: the colour plane of the records' SoA shadow (soa + soa_n), which gets the
+// same three floats in .xyz, or null.  One workgroup per SHADE_TILE records.
+constexpr uint32_t SHADE_TILE = 256;
+hipError_t launch_shade_sh(hipStream_t st, void* records, size_t n, const void* sh, size_t sh_stride, int degree, float t, const float cam[3], float4* plane1);
+
 // ---- cut.hip ----
 // gs4d_stat_cut (gs4d.h): a radix select over one field of a statistics table, most significant digit first — per digit one histogram
 // launch and one pick launch on `st`, no workgroup waits for another.

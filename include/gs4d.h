@@ -418,6 +418,71 @@ GS4D_API int gs4d_compact_time_window(gs4d_ctx* ctx, gs4d_buf spans, size_t n, f
 GS4D_API int gs4d_spatial_order(gs4d_ctx* ctx, gs4d_buf src, size_t n, size_t stride, size_t pos_offset, gs4d_buf order_index);
 GS4D_API int gs4d_gather_records(gs4d_ctx* ctx, gs4d_buf index, size_t m, gs4d_buf src, size_t nsrc, size_t stride, gs4d_buf dst);
 
+/* ---- view-dependent colour: a record's rgb from spherical harmonics, evaluated on the device (no reference counterpart) ----
+ * Trained 3DGS-style sets store colour as spherical-harmonic (SH) coefficients per splat; the draws know the constant rgba at floats 4..7 of the
+ * record.  gs4d_shade_sh evaluates degree 0..3 for a camera position and a time and writes floats 4, 5 and 6 (r, g, b) of each record i < n of the
+ * 96-byte records in `data`.  Float 7 (alpha) and every other byte of the record stay as they are; no byte of data beyond record n - 1 is written;
+ * no byte of sh is written.
+ *
+ * The table.  Row i is the sh_stride bytes at sh + i*sh_stride.  sh_stride: a multiple of 16, 16 .. 1024, as everywhere — so gs4d_gather_records
+ * and both compactions carry a table along through kept_index / order_index unchanged — and sh_stride >= 12 (degree + 1)^2 (minimal rows: 16 / 48 /
+ * 112 / 192 bytes for degree 0 / 1 / 2 / 3).  A row is float32, coefficient-major with the channels interleaved: c_k of channel ch is row[3k + ch],
+ * k = 0 .. (degree + 1)^2 - 1, ch = 0, 1, 2 (r, g, b).  A lower degree reads a prefix of the same row: a degree-3 table shaded at degree 1 costs a
+ * quarter of the traffic.  The row is read in 16-byte pieces: nothing past the 12 (degree + 1)^2 bytes, rounded up to 16, is ever read, and
+ * nothing past the 12 (degree + 1)^2 bytes can change a result.
+ *
+ * The definition.  All arithmetic is float32, round to nearest, no contraction (every product and every sum below is rounded on its own, in the
+ * order its parentheses give), with correctly rounded division and square root.  p = floats 0..2 of the record, mu_t = float 3, sig3 = floats
+ * 20..22, s44 = float 23: the direction runs from the camera to the time-conditioned mean the draw projects (GS4D_KEY_VIEW_Z's mean, not the
+ * reference's Euclidean key):
+ *     k    = (1.0f / s44) * (t - mu_t)
+ *     m    = p + (k * sig3)                              per component: one product, one sum
+ *     d    = m - cam_pos
+ *     len2 = ((d.x*d.x) + (d.y*d.y)) + (d.z*d.z)
+ *     inv  = 1.0f / sqrtf(len2)
+ *     x = d.x*inv,  y = d.y*inv,  z = d.z*inv
+ * If !(len2 > 0) or len2 is not finite — a NaN or Inf position, s44 == 0, a camera on the mean — the record is DC-ONLY: the sum below stops after
+ * k = 0.  The basis, with the constants and signs of the 3DGS reference implementation (computeColorFromSH), each constant rounded to float32:
+ *     C0 = 0.28209479177387814   C1 = 0.4886025119029199
+ *     C2 = { 1.0925484305920792, -1.0925484305920792, 0.31539156525252005, -1.0925484305920792, 0.5462742152960396 }
+ *     C3 = { -0.5900435899266435, 2.890611442640554, -0.4570457994644658, 0.3731763325901154, -0.4570457994644658, 1.445305721320277,
+ *            -0.5900435899266435 }
+ *     xx = x*x, yy = y*y, zz = z*z, xy = x*y, yz = y*z, xz = x*z
+ *     b_0  = C0
+ *     b_1  = (-C1)*y             b_2  = C1*z                               b_3  = (-C1)*x
+ *     b_4  = C2[0]*xy            b_5  = C2[1]*yz                           b_6  = C2[2]*(((2.0f*zz) - xx) - yy)
+ *     b_7  = C2[3]*xz            b_8  = C2[4]*(xx - yy)
+ *     b_9  = (C3[0]*y)*((3.0f*xx) - yy)                                    b_10 = (C3[1]*xy)*z
+ *     b_11 = (C3[2]*y)*(((4.0f*zz) - xx) - yy)                             b_12 = (C3[3]*z)*(((2.0f*zz) - (3.0f*xx)) - (3.0f*yy))
+ *     b_13 = (C3[4]*x)*(((4.0f*zz) - xx) - yy)                             b_14 = (C3[5]*z)*(xx - yy)
+ *     b_15 = (C3[6]*x)*(xx - (3.0f*yy))
+ * and the colour, per channel:
+ *     acc = b_0*c_0
+ *     for k = 1 .. (degree + 1)^2 - 1 (DC-only: none):   acc = acc + (b_k*c_k)
+ *     v = acc + 0.5f
+ *     colour = v > 0 ? v : 0                             a NaN gives 0; +inf stays (the draws treat out-of-range colours as data)
+ * Nothing depends on the order in which anything runs on the device: the same inputs give the same bits.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: n > 0xFFFFFFFF; degree outside 0 .. 3; an sh_stride that is not a multiple of 16 in
+ * 16 .. 1024 or is smaller than 12 (degree + 1)^2; cam_pos == NULL; a name that is not a live buffer; data == sh; data smaller than 96 n bytes or
+ * sh smaller than n * sh_stride.  n == 0 is a no-op.  t and cam_pos may be non-finite: they are data, and the DC-only rule applies.
+ *
+ * Ordering, as gs4d_gather_records: a queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first; draws that may still
+ * have to be run again from data are settled; the kernel is queued on the current frame lane, the call returns at once and starts no new frame;
+ * sh is a buffer the call reads, data one it writes (it waits, on the device, for the lanes whose draws or key generation still read data or its
+ * shadow; later calls, other lanes and the host order themselves behind it).  gs4d_buffer_invalidate hand-offs of both buffers are honoured.
+ *
+ * What the write keeps.  Any other write to a record buffer makes the library rebuild what it derives from the contents at the next draw: the SoA
+ * shadow the draws and gs4d_keygen read, its layout choice, the bounding box and the key bounds — a blocking repack of the whole set.  None of those
+ * reads a colour, so gs4d_shade_sh is a COLOUR-ONLY write: if the shadow was current when the call was made, the same kernel writes the three floats
+ * into the shadow's colour plane as well (its alpha is left alone) and the shadow stays current — the next draw neither repacks nor waits.  If the
+ * shadow was not current (no draw or keygen since the last upload), only the records are written and the next draw builds the shadow, as it would
+ * have anyway.  What is NOT kept is the provenance of a sort index: a draw whose gs4d_keygen + gs4d_sort_pairs ran BEFORE the shade no longer
+ * takes its blend order from the keys but reads the sort index, which is correct but slower.  The call order per frame is therefore
+ * shade -> gs4d_keygen -> gs4d_sort_pairs -> draw. */
+GS4D_API int gs4d_shade_sh(gs4d_ctx* ctx, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_stride, int degree,
+                           float t, const float cam_pos[3]);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -433,6 +498,9 @@ GS4D_API int gs4d_get_stats(gs4d_ctx* ctx, uint64_t stats[8]);                  
  * depth (slot 15) is -z_view of the record's (time-conditioned) centre when the draw's frame has aux outputs (gs4d_set_aux_outputs) or the
  * draw has a depth test (gs4d_set_depth_test), and the record is valid, else 0; GS4D_MODE_2D records always have 0. */
 GS4D_API int gs4d_debug_read_projected(gs4d_ctx* ctx, float* out16, size_t nrecords);
+/* How many times the library has (re)built the SoA shadow of this record buffer (a repack of the whole set, at the first draw or gs4d_keygen after a
+ * write to it): gs4d_shade_sh on a buffer whose shadow is current does not add to it. */
+GS4D_API int gs4d_debug_shadow_builds(gs4d_ctx* ctx, gs4d_buf buf, uint64_t* builds);
 
 /* ---- host-side parameterisation (CPU code inside libgs4d.so; mirrors the reference's host math so that a caller
  *      without GLM can build SSBO contents).  Quaternions are w,x,y,z (GLM 0.9.9.9 order). ---- */
