@@ -24,6 +24,7 @@ CONSTANT_COLOR, ONE_MINUS_CONSTANT_COLOR, CONSTANT_ALPHA, ONE_MINUS_CONSTANT_ALP
 KEY_REF_INV_EUCLID, KEY_VIEW_Z = 0, 1
 KEEP_INVERT = 1                                           # gs4d_keep_rule.flags: keep exactly the records the rule would drop
 STAT_PIXELS, STAT_WMAX, STAT_WSUM = 0, 1, 2               # gs4d_stat_cut: the field of gs4d_record_stat
+PARAMS_3D, PARAMS_4D_VEL, PARAMS_4D_2Q = 0, 1, 2           # gs4d_splat_params.form
 TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
@@ -93,6 +94,7 @@ def _load():
         "gs4d_spatial_order": (i32, [vp, u32, sz, sz, sz, u32]),
         "gs4d_gather_records": (i32, [vp, u32, sz, u32, sz, sz, u32]),
         "gs4d_shade_sh": (i32, [vp, u32, sz, u32, sz, i32, f32, vp]),
+        "gs4d_build_records": (i32, [vp, vp, sz, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -111,6 +113,10 @@ def _load():
         "gs4d_host_splat4d_cov2q": (None, [vp, vp, vp, vp]),
         "gs4d_host_build_records_3d": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_build_records_4d": (None, [sz, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gs4d_host_time_variance": (f32, [f32, f32]),
+        "gs4d_host_time_variances": (None, [sz, vp, vp, vp]),
+        "gs4d_host_build_records_4d_tvar": (None, [sz, vp, vp, vp, vp, vp, vp, vp]),
+        "gs4d_host_build_records_4d_2q": (None, [sz, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
         "gs4d_host_scene_nonlinear": (None, [sz, vp, i32, f32, f32, f32, vp, f32, f32, f32, sz, vp]),
         "gs4d_host_scene_rotation": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, sz, vp]),
@@ -192,6 +198,39 @@ def build_records_4d(pos4, q_wxyz, scale3, lifetime, fade, dir3, rgba):
     assert all(x.shape[0] == n for x in (q, s, life, fd, d, col))
     rec = np.empty((n, 24), np.float32)
     _lib.gs4d_host_build_records_4d(n, _ptr(pos4), _ptr(q), _ptr(s), _ptr(life), _ptr(fd), _ptr(d), _ptr(col), _ptr(rec))
+    return rec
+
+
+def time_variance(lifetime, fade):
+    """gs4d_host_time_variance: the temporal variance (Sigma44) the reference gives a 4D splat of this lifetime and fade — lifetime^2 /
+    (-2 log(fade)), the quotient in double.  Scalars give a float32 scalar, arrays (broadcast against each other) a float32 array."""
+    life, fd = np.broadcast_arrays(_f32(lifetime), _f32(fade))
+    life, fd = _f32(life).reshape(-1), _f32(fd).reshape(-1)
+    out = np.empty(life.shape[0], np.float32)
+    _lib.gs4d_host_time_variances(out.shape[0], _ptr(life), _ptr(fd), _ptr(out))
+    shape = np.broadcast(np.asarray(lifetime), np.asarray(fade)).shape
+    return out.reshape(shape) if shape else out[0]
+
+
+def build_records_4d_tvar(pos4, q_wxyz, scale3, dir3, tvar, rgba):
+    """build_records_4d with the temporal variance given instead of (lifetime, fade): what gs4d_build_records' PARAMS_4D_VEL form computes."""
+    pos4, q, s = _f32(pos4).reshape(-1, 4), _f32(q_wxyz).reshape(-1, 4), _f32(scale3).reshape(-1, 3)
+    d, tv, col = _f32(dir3).reshape(-1, 3), _f32(tvar).reshape(-1), _f32(rgba).reshape(-1, 4)
+    n = pos4.shape[0]
+    assert all(x.shape[0] == n for x in (q, s, d, tv, col))
+    rec = np.empty((n, 24), np.float32)
+    _lib.gs4d_host_build_records_4d_tvar(n, _ptr(pos4), _ptr(q), _ptr(s), _ptr(d), _ptr(tv), _ptr(col), _ptr(rec))
+    return rec
+
+
+def build_records_4d_2q(pos4, q0_wxyz, q1_wxyz, scale4, rgba):
+    """Records of 4D splats given by a left and a right quaternion and four scales (splat4d_cov2q per record): PARAMS_4D_2Q."""
+    pos4, q0, q1 = _f32(pos4).reshape(-1, 4), _f32(q0_wxyz).reshape(-1, 4), _f32(q1_wxyz).reshape(-1, 4)
+    s, col = _f32(scale4).reshape(-1, 4), _f32(rgba).reshape(-1, 4)
+    n = pos4.shape[0]
+    assert all(x.shape[0] == n for x in (q0, q1, s, col))
+    rec = np.empty((n, 24), np.float32)
+    _lib.gs4d_host_build_records_4d_2q(n, _ptr(pos4), _ptr(q0), _ptr(q1), _ptr(s), _ptr(col), _ptr(rec))
     return rec
 
 
@@ -309,6 +348,12 @@ class IdRegion(C.Structure):
                 ("min_weight", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class SplatParams(C.Structure):
+    """gs4d_splat_params (include/gs4d.h): the form and the parameter buffers of a gs4d_build_records call."""
+    _fields_ = [("form", C.c_uint32), ("flags", C.c_uint32), ("pos", C.c_uint32), ("rot", C.c_uint32), ("rot_r", C.c_uint32), ("scale", C.c_uint32),
+                ("rgba", C.c_uint32), ("dir", C.c_uint32), ("tvar", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class CameraInput(C.Structure):
     _fields_ = [("keys", C.c_uint), ("mouse_x", C.c_double), ("mouse_y", C.c_double), ("imgui_active", C.c_int)]
 
@@ -394,6 +439,19 @@ def sh_rows(f_dc, f_rest, degree, stride=None):
     rows = np.zeros((n, stride), np.uint8)
     rows[:, :12 * K] = coeff.reshape(n, 3 * K).view(np.uint8)
     return rows
+
+
+_hip_runtime = None
+
+
+def _hip():
+    """the HIP runtime the process has loaded (libgs4d.so links it), for the one call write_tensor makes itself"""
+    global _hip_runtime
+    if _hip_runtime is None:
+        _hip_runtime = C.CDLL("libamdhip64.so")
+        _hip_runtime.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        _hip_runtime.hipMemcpyAsync.restype = C.c_int
+    return _hip_runtime
 
 
 # ---- device context -----------------------------------------------------------------------------
@@ -795,6 +853,46 @@ class Context:
             sh_stride = sh_row_bytes(degree)
         self._chk(_lib.gs4d_shade_sh(self._h, int(data), int(n), int(sh), int(sh_stride), int(degree), float(t), _ptr(_f32(cam_pos))))
 
+    # records from parameters: the records of a splat set built on the device
+    PARAM_BUFFERS = ("pos", "rot", "rot_r", "scale", "rgba", "dir", "tvar")
+
+    def build_records(self, form, n, dst=None, **buffers):
+        """gs4d_build_records: the first n 96-byte records of `dst` (a new buffer if None) from row i of the parameter buffers of the form —
+        PARAMS_3D: pos (3 floats), rot (w x y z), scale (3), rgba; PARAMS_4D_VEL: pos (x y z mu_t), rot, scale (3), dir (3), tvar (1: see
+        time_variance), rgba; PARAMS_4D_2Q: pos (4), rot, rot_r, scale (4), rgba — with the bits of build_records_3d / build_records_4d_tvar /
+        build_records_4d_2q.  A full write of dst: the next draw rebuilds its SoA shadow.  Per frame: build, (shade_sh), keygen, sort, draw.
+        Asynchronous; returns `dst`."""
+        unknown = set(buffers) - set(self.PARAM_BUFFERS)
+        if unknown:
+            raise TypeError(f"build_records: unknown parameter buffer(s) {sorted(unknown)}")
+        if dst is None:
+            dst = self.buffer(nbytes=max(16, int(n) * 96))
+        params = SplatParams(int(form), 0, *(int(buffers.get(k) or 0) for k in self.PARAM_BUFFERS), 0)
+        self._chk(_lib.gs4d_build_records(self._h, C.byref(params), int(n), int(dst)))
+        return dst
+
+    def write_tensor(self, buf, tensor, offset=0):
+        """A contiguous device tensor copied into the buffer `buf` at byte `offset`, with no host copy and no host synchronisation: the
+        contract of gs4d_buffer_device_ptr — gs4d_buffer_invalidate, then an asynchronous device-to-device copy on the tensor's current
+        stream, which the caller has named with set_stream (the legacy default stream cannot be named: run under a stream of your own).  The
+        library's next call that uses the buffer is ordered behind the copy."""
+        import torch                                             # lazily: the package imports without torch
+        if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.is_contiguous()):
+            raise ValueError("write_tensor: expected a contiguous device tensor")
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        if not stream or stream != getattr(self, "_stream", None):
+            raise Gs4dError("write_tensor: name the tensor's current stream with set_stream first (a stream of your own, not the default stream)")
+        nbytes = tensor.numel() * tensor.element_size()
+        dptr, size = self.device_ptr(buf)
+        if offset < 0 or offset + nbytes > size:
+            raise ValueError(f"write_tensor: {nbytes} bytes at offset {offset} do not fit a buffer of {size} bytes")
+        if nbytes == 0:
+            return
+        self.invalidate(buf)
+        rc = _hip().hipMemcpyAsync(C.c_void_p(dptr + offset), C.c_void_p(tensor.data_ptr()), nbytes, 3, C.c_void_p(stream))      # 3: hipMemcpyDeviceToDevice
+        if rc != 0:
+            raise Gs4dError(f"write_tensor: hipMemcpyAsync failed ({rc})")
+
     def shadow_builds(self, buf):
         """gs4d_debug_shadow_builds: how many times the SoA shadow of this record buffer has been (re)built."""
         n = C.c_uint64(0)
@@ -815,6 +913,7 @@ class Context:
 
     def set_stream(self, hip_stream):
         self._chk(_lib.gs4d_set_stream(self._h, C.c_void_p(hip_stream) if hip_stream else None))
+        self._stream = hip_stream or None
 
     def finish(self):
         self._chk(_lib.gs4d_finish(self._h))

@@ -1498,6 +1498,43 @@ int gs4d_shade_sh(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_s
         });
 }
 
+// ---- records from parameters ----
+int gs4d_build_records(gs4d_ctx* c, const gs4d_splat_params* params, size_t n, gs4d_buf dst) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const std::string& msg) { return fail(c, GS4D_E_INVALID, ("build_records: " + msg).c_str()); };
+    if (!params) return bad("params == NULL");
+    const gs4d_splat_params& p = *params;
+    if (p.form != GS4D_PARAMS_3D && p.form != GS4D_PARAMS_4D_VEL && p.form != GS4D_PARAMS_4D_2Q) return bad("unknown form");
+    if (p.flags != 0u || p.reserved != 0u) return bad("flags and reserved must be 0");
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    // bytes per row of every parameter in the form; 0: the form does not use it
+    const bool vel = p.form == GS4D_PARAMS_4D_VEL, twoq = p.form == GS4D_PARAMS_4D_2Q;
+    struct { const char* name; gs4d_buf buf; size_t row; } const rows[7] = {
+        { "pos", p.pos, p.form == GS4D_PARAMS_3D ? 12u : 16u }, { "rot", p.rot, 16 }, { "rot_r", p.rot_r, twoq ? 16u : 0u }, { "scale", p.scale, twoq ? 16u : 12u },
+        { "rgba", p.rgba, 16 }, { "dir", p.dir, vel ? 12u : 0u }, { "tvar", p.tvar, vel ? 4u : 0u } };
+    Buffer* B[7] = {};
+    for (int k = 0; k < 7; ++k) {
+        if (rows[k].row == 0) { if (rows[k].buf != 0) return bad(std::string(rows[k].name) + " must be 0 in this form"); continue; }
+        if (!(B[k] = getbuf(c, rows[k].buf))) return bad(std::string(rows[k].name) + " is not a live buffer");
+    }
+    Buffer* D = getbuf(c, dst);
+    if (!D) return bad("dst is not a live buffer");
+    const gs4d_buf names[8] = { p.pos, p.rot, p.rot_r, p.scale, p.rgba, p.dir, p.tvar, dst };
+    if (check_record_names(c, names, 8)) return bad("the parameter buffers and dst must be different buffers");
+    for (int k = 0; k < 7; ++k) if (B[k] && B[k]->bytes / rows[k].row < n) return bad(std::string(rows[k].name) + " holds fewer than n rows");
+    if (D->bytes / 96 < n) return bad("dst holds fewer than n records");
+    if (n == 0) return GS4D_OK;
+    { int rc = flush_order_if_named(c, names, 8); if (rc) return rc; }
+    return queue_on_lane(c, { B[0], B[1], B[2], B[3], B[4], B[5], B[6] }, { D },
+        [&](Lane&) { return (int)GS4D_OK; },
+        [&](Lane& L) {
+            const BuildParams bp = { B[0]->d, B[1]->d, B[2] ? B[2]->d : nullptr, B[3]->d, B[4]->d, B[5] ? B[5]->d : nullptr, B[6] ? B[6]->d : nullptr };
+            HIPCHK(c, launch_build_records(L.s, (int)p.form, bp, n, D->d));
+            return (int)GS4D_OK;
+        });
+}
+
 // ---- draw ----
 static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     (void)hipSetDevice(c->device);

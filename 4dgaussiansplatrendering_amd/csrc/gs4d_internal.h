@@ -423,6 +423,13 @@ hipError_t launch_gather_records(hipStream_t st, const uint32_t* index, size_t m
 constexpr uint32_t SHADE_TILE = 256;
 hipError_t launch_shade_sh(hipStream_t st, void* records, size_t n, const void* sh, size_t sh_stride, int degree, float t, const float cam[3], float4* plane1);
 
+// ---- build.hip ----
+// gs4d_build_records (gs4d.h): the first n 96-byte records of dst from row i of each parameter array of the form (GS4D_PARAMS_*; rows of
+// tightly packed float32, the arrays the form does not use: null).  One workgroup per BUILD_TILE records; nothing past row / record n - 1 is touched.
+constexpr uint32_t BUILD_TILE = 256;
+struct BuildParams { const void *pos, *rot, *rot_r, *scale, *rgba, *dir, *tvar; };
+hipError_t launch_build_records(hipStream_t st, int form, const BuildParams& p, size_t n, void* dst);
+
 // ---- cut.hip ----
 // gs4d_stat_cut (gs4d.h): a radix select over one field of a statistics table, most significant digit first — per digit one histogram
 // launch and one pick launch on `st`, no workgroup waits for another.

@@ -337,10 +337,18 @@ void gs4d_host_gaussians2d_record(float angle, float s0, float s1, float px, flo
     rec12[8] = g.m[0][0]; rec12[9] = g.m[0][1]; rec12[10] = g.m[1][0]; rec12[11] = g.m[1][1];
 }
 
-void gs4d_host_splat4d_cov(const float q_wxyz[4], const float scale3[3], float lifetime, float fade, const float dir[3], float cov16[16]) {
+float gs4d_host_time_variance(float lifetime, float fade) {
     // Splat.h:139: `log(fadeof)` on a float is the float overload; the -2.0 factor promotes the quotient to double
     const double denom = (fade == 0.5f) ? (double)1.3862943611198906f : -2.0 * (double)std::log(fade);
-    const float sd = (float)((double)(lifetime * lifetime) / denom);
+    return (float)((double)(lifetime * lifetime) / denom);
+}
+
+void gs4d_host_time_variances(size_t n, const float* lifetime, const float* fade, float* out) {
+    for (size_t i = 0; i < n; ++i) out[i] = gs4d_host_time_variance(lifetime[i], fade[i]);
+}
+
+// Splat.h:140-158 with the temporal variance sd given
+static void splat4d_cov_tvar(const float q_wxyz[4], const float scale3[3], float sd, const float dir[3], float cov16[16]) {
     const float td[3] = { dir[0] * sd, dir[1] * sd, dir[2] * sd };
     const Mat3 sig = sigma3({ q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3] }, scale3);
     const float inv = 1.0f / sd;
@@ -352,6 +360,10 @@ void gs4d_host_splat4d_cov(const float q_wxyz[4], const float scale3[3], float l
     }
     C.at(3, 3) = sd;
     std::memcpy(cov16, C.a, sizeof C.a);
+}
+
+void gs4d_host_splat4d_cov(const float q_wxyz[4], const float scale3[3], float lifetime, float fade, const float dir[3], float cov16[16]) {
+    splat4d_cov_tvar(q_wxyz, scale3, gs4d_host_time_variance(lifetime, fade), dir, cov16);
 }
 
 void gs4d_host_splat4d_cov2q(const float q0_wxyz[4], const float q1_wxyz[4], const float scale4[4], float cov16[16]) {
@@ -388,6 +400,24 @@ void gs4d_host_build_records_4d(size_t n, const float* pos4, const float* q_wxyz
     }
 }
 
+void gs4d_host_build_records_4d_tvar(size_t n, const float* pos4, const float* q_wxyz, const float* scale3, const float* dir3, const float* tvar,
+                                     const float* rgba, float* rec) {
+    for (size_t i = 0; i < n; ++i) {
+        float* o = rec + 24 * i;
+        std::memcpy(o, pos4 + 4 * i, 16);
+        std::memcpy(o + 4, rgba + 4 * i, 16);
+        splat4d_cov_tvar(q_wxyz + 4 * i, scale3 + 3 * i, tvar[i], dir3 + 3 * i, o + 8);
+    }
+}
+
+void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const float* q0_wxyz, const float* q1_wxyz, const float* scale4, const float* rgba, float* rec) {
+    for (size_t i = 0; i < n; ++i) {
+        float* o = rec + 24 * i;
+        std::memcpy(o, pos4 + 4 * i, 16);
+        std::memcpy(o + 4, rgba + 4 * i, 16);
+        gs4d_host_splat4d_cov2q(q0_wxyz + 4 * i, q1_wxyz + 4 * i, scale4 + 4 * i, o + 8);
+    }
+}
 
 // ---- scene generators: the loops of LinearMotion::init (Scenes.h:258-279) and NonLinearMotion::init
 //      (Scenes.h:517-545) with GetModelExtrema (:75-91) and GetColor (:58-68; Utils.cpp lerp/mapf, note mapf ignores `a` in the

@@ -483,6 +483,53 @@ GS4D_API int gs4d_gather_records(gs4d_ctx* ctx, gs4d_buf index, size_t m, gs4d_b
 GS4D_API int gs4d_shade_sh(gs4d_ctx* ctx, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_stride, int degree,
                            float t, const float cam_pos[3]);
 
+/* ---- records from parameters: the 96-byte records of a splat set built on the device (Splat4D / Splat3D constructors, Splat.h:91-159, 334-344) ----
+ * A caller whose splat parameters live on the device — an optimisation or animation loop, a trained 3DGS / 4DGS model, a simulation — gets its
+ * SplatData records without a round trip over the host: gs4d_build_records writes record i < n of dst from row i of each parameter buffer.  All rows
+ * are tightly packed float32, row i at i * row_bytes.  The call writes the first n 96-byte records of dst; it writes no other byte of dst and no byte
+ * of any parameter buffer.
+ *
+ * The definition is the host code below ("host-side parameterisation"), which the fixtures pin.  All arithmetic is float32, round to nearest, no
+ * contraction (every product and every sum is rounded on its own, in the order the host code gives), with correctly rounded division and square
+ * root.  Matrix products are FULL products, the zeros of the scale matrices included (inf * 0 is a NaN, and a signed zero term decides the sign of a
+ * zero sum).  The records have the bits of the host builders, except that a word that is a NaN on both sides may differ in sign and payload:
+ *     GS4D_PARAMS_3D      record i of gs4d_host_build_records_3d(pos, rot, scale, rgba): Sigma3 = ((R S) S) R^T with R the matrix of the quaternion
+ *                         as given (not normalised), each element ((a0*b0) + (a1*b1)) + (a2*b2); mu_t = 0, Sigma44 = 1, zeros in between;
+ *     GS4D_PARAMS_4D_VEL  record i of gs4d_host_build_records_4d_tvar(pos, rot, scale, dir, tvar, rgba): gs4d_host_splat4d_cov from td = dir * sd
+ *                         onwards with sd = tvar[i]: Sigma3 + (td td^T) * (1 / sd), td in row and column 3, Sigma44 = sd.  (lifetime, fade) -> sd is
+ *                         gs4d_host_time_variance, on the host: it takes a double-precision logarithm;
+ *     GS4D_PARAMS_4D_2Q   record i of gs4d_host_build_records_4d_2q(pos, rot, rot_r, scale, rgba): floats 8..23 = gs4d_host_splat4d_cov2q(rot[i],
+ *                         rot_r[i], scale[i]): both quaternions normalised (a length <= 0 gives the identity), rot = L R, ((rot S) S^T) rot^T, each
+ *                         element ((a0*b0 + a1*b1) + a2*b2) + a3*b3.
+ * Nothing depends on the order in which anything runs on the device: the same inputs give the same bits.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: params == NULL; an unknown form; flags or reserved != 0; n > 0xFFFFFFFF; a buffer the form
+ * needs that is not a live buffer; a buffer the form does not use that is not 0; any two of the named buffers (dst included) being the same buffer; a
+ * parameter buffer smaller than n rows; dst smaller than 96 n bytes.  n == 0 with otherwise valid arguments is a no-op.
+ *
+ * Ordering, as gs4d_gather_records: a queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first; draws that may still
+ * have to be run again from dst are settled; the kernel is queued on the current frame lane, the call returns at once and starts no new frame; the
+ * parameter buffers are buffers the call reads, dst one it writes (it waits, on the device, for the lanes whose draws or key generation still read
+ * dst or its shadow; later calls, other lanes and the host order themselves behind it).  gs4d_buffer_invalidate hand-offs of all the buffers are
+ * honoured: parameters written through gs4d_buffer_device_ptr on the caller's stream are read after those writes.
+ * It is a full write of dst, like an upload: the buffer's version moves, what a sort index was sorted by is forgotten, and the next draw or
+ * gs4d_keygen rebuilds the SoA shadow, its layout choice, the bounding box and the key bounds (gs4d_debug_shadow_builds goes up by one).  The call
+ * order per frame is therefore build -> (gs4d_shade_sh) -> gs4d_keygen -> gs4d_sort_pairs -> draw. */
+enum { GS4D_PARAMS_3D = 0, GS4D_PARAMS_4D_VEL = 1, GS4D_PARAMS_4D_2Q = 2 };
+typedef struct gs4d_splat_params {
+    uint32_t form;      /* GS4D_PARAMS_*                                                                 */
+    uint32_t flags;     /* must be 0                                                                     */
+    gs4d_buf pos;       /* 3D: 3 floats per record (x, y, z); 4D forms: 4 floats (x, y, z, mu_t)          */
+    gs4d_buf rot;       /* 4 floats, w x y z (3D, 4D_VEL: the rotation; 4D_2Q: the left quaternion)       */
+    gs4d_buf rot_r;     /* 4D_2Q: 4 floats, the right quaternion; other forms: must be 0                  */
+    gs4d_buf scale;     /* 3D, 4D_VEL: 3 floats; 4D_2Q: 4 floats                                          */
+    gs4d_buf rgba;      /* 4 floats, copied to floats 4..7 of the record                                  */
+    gs4d_buf dir;       /* 4D_VEL: 3 floats; other forms: must be 0                                       */
+    gs4d_buf tvar;      /* 4D_VEL: 1 float, the temporal variance (Sigma44); other forms: must be 0       */
+    uint32_t reserved;  /* must be 0                                                                     */
+} gs4d_splat_params;    /* 40 bytes */
+GS4D_API int gs4d_build_records(gs4d_ctx* ctx, const gs4d_splat_params* params, size_t n, gs4d_buf dst);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -518,6 +565,16 @@ GS4D_API void gs4d_host_splat4d_cov2q(const float q0_wxyz[4], const float q1_wxy
 GS4D_API void gs4d_host_build_records_3d(size_t n, const float* pos3, const float* q_wxyz, const float* scale3, const float* rgba, float* records24);
 GS4D_API void gs4d_host_build_records_4d(size_t n, const float* pos4, const float* q_wxyz, const float* scale3, const float* lifetime, const float* fade,
                                 const float* dir3, const float* rgba, float* records24);
+/* The temporal variance sd of gs4d_host_splat4d_cov (Splat.h:139): lifetime^2 / (-2 log(fade)), the quotient in double, rounded to float. */
+GS4D_API float gs4d_host_time_variance(float lifetime, float fade);
+GS4D_API void gs4d_host_time_variances(size_t n, const float* lifetime, const float* fade, float* out);
+/* The batch restatements gs4d_build_records is compared with.  _4d_tvar: gs4d_host_build_records_4d with the temporal variance given instead of
+ * (lifetime, fade): tvar[i] = gs4d_host_time_variance(lifetime[i], fade[i]) gives the same bits.  _4d_2q: floats 0..3 = pos4, 4..7 = rgba, 8..23 =
+ * gs4d_host_splat4d_cov2q(q0[i], q1[i], scale4[i]). */
+GS4D_API void gs4d_host_build_records_4d_tvar(size_t n, const float* pos4, const float* q_wxyz, const float* scale3, const float* dir3, const float* tvar,
+                                              const float* rgba, float* records24);
+GS4D_API void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const float* q0_wxyz, const float* q1_wxyz, const float* scale4, const float* rgba,
+                                            float* records24);
 
 /* Scene generators and the .vdata loader (f2): the CPU loops that fill the SSBO before the path starts. */
 GS4D_API void gs4d_host_scene_linear(size_t nverts, const float* verts6, int steps, float time_multiplier, float object_scale, const float splat_scale[3],
