@@ -95,6 +95,7 @@ def _load():
         "gs4d_gather_records": (i32, [vp, u32, sz, u32, sz, sz, u32]),
         "gs4d_shade_sh": (i32, [vp, u32, sz, u32, sz, i32, f32, vp]),
         "gs4d_build_records": (i32, [vp, vp, sz, u32]),
+        "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -117,6 +118,8 @@ def _load():
         "gs4d_host_time_variances": (None, [sz, vp, vp, vp]),
         "gs4d_host_build_records_4d_tvar": (None, [sz, vp, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_build_records_4d_2q": (None, [sz, vp, vp, vp, vp, vp, vp]),
+        "gs4d_host_transform_records": (None, [sz, vp, vp, vp]),
+        "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
         "gs4d_host_scene_nonlinear": (None, [sz, vp, i32, f32, f32, f32, vp, f32, f32, f32, sz, vp]),
         "gs4d_host_scene_rotation": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, sz, vp]),
@@ -232,6 +235,44 @@ def build_records_4d_2q(pos4, q0_wxyz, q1_wxyz, scale4, rgba):
     rec = np.empty((n, 24), np.float32)
     _lib.gs4d_host_build_records_4d_2q(n, _ptr(pos4), _ptr(q0), _ptr(q1), _ptr(s), _ptr(col), _ptr(rec))
     return rec
+
+
+class Affine4(C.Structure):
+    """gs4d_affine4 (include/gs4d.h): one 4D affine map x' = L x + o of gs4d_transform_records — l column-major (L[r, c] = l[4 c + r]), row and
+    column 3 = time; 80 bytes."""
+    _fields_ = [("l", C.c_float * 16), ("o", C.c_float * 4)]
+
+
+def affine4(q_wxyz=(1.0, 0.0, 0.0, 0.0), scale=1.0, translate=(0.0, 0.0, 0.0), velocity=(0.0, 0.0, 0.0), time_scale=1.0, time_offset=0.0):
+    """gs4d_host_affine4: one row of transform_records' table as 20 float32 (l[16], o[4]) — the upper 3x3 scale * R(q) (the quaternion as given),
+    column 3 = velocity, L[3, 3] = time_scale, o = (translate, time_offset).  A source time t shows at time_scale * t + time_offset."""
+    out = np.zeros(20, np.float32)
+    _lib.gs4d_host_affine4(_ptr(_f32(q_wxyz)), scale, _ptr(_f32(translate)), _ptr(_f32(velocity)), time_scale, time_offset, _ptr(out))
+    return out
+
+
+def _affine_rows(xf):
+    """(m, 20) float32 from an Affine4, a sequence of them, or an array of 20 m floats"""
+    if isinstance(xf, Affine4):
+        xf = [xf]
+    if isinstance(xf, (list, tuple)) and xf and isinstance(xf[0], Affine4):
+        xf = np.stack([np.frombuffer(bytes(a), np.float32) for a in xf])
+    rows = _f32(xf)
+    if rows.size % 20:
+        raise ValueError("expected rows of 20 float32 (l[16], o[4])")
+    return rows.reshape(-1, 20)
+
+
+def transform_records_host(records, xf):
+    """gs4d_host_transform_records, the definition of Context.transform_records: records [n, 24] under xf (20 floats or an Affine4: [n, 24]; m rows:
+    [m, n, 24], instance after instance)."""
+    rec = _f32(records).reshape(-1, 24)
+    single = isinstance(xf, Affine4) or np.ndim(xf) == 1
+    rows = _affine_rows(xf)
+    out = np.empty((rows.shape[0], rec.shape[0], 24), np.float32)
+    for j in range(rows.shape[0]):
+        _lib.gs4d_host_transform_records(rec.shape[0], _ptr(rec), _ptr(rows[j]), _ptr(out[j]))
+    return out[0] if single else out
 
 
 def scene_linear(verts6, steps=50, time_multiplier=1.0, object_scale=5.0, splat_scale=(4.0, 4.0, 1.0), lifetime=1.0, fade=0.5, speed=1.0):
@@ -869,6 +910,27 @@ class Context:
             dst = self.buffer(nbytes=max(16, int(n) * 96))
         params = SplatParams(int(form), 0, *(int(buffers.get(k) or 0) for k in self.PARAM_BUFFERS), 0)
         self._chk(_lib.gs4d_build_records(self._h, C.byref(params), int(n), int(dst)))
+        return dst
+
+    # placing a set: the records under 4D affine maps
+    def transform_records(self, src, n, xf, m=1, dst=None, dst_first=0):
+        """gs4d_transform_records: record dst_first + j * n + i of `dst` (a new buffer of dst_first + m * n records if None) <- record i < n of
+        `src` under row j < m of `xf` — a buffer of 80-byte rows (affine4, Affine4), or an (m, 20) float32 array, which is uploaded to a
+        temporary buffer (m is then its row count; deleting it waits for the device, so a frame loop keeps a buffer of its own) — with the bits
+        of transform_records_host.  A full write of dst: the next draw rebuilds its SoA
+        shadow.  Per frame: (shade_sh), transform, keygen, sort, draw.  Asynchronous; returns `dst`."""
+        own = not isinstance(xf, (int, np.integer))
+        if own:
+            rows = _affine_rows(xf)
+            m = rows.shape[0]
+            xf = self.buffer(rows) if m else self.buffer(nbytes=80)
+        try:
+            if dst is None:
+                dst = self.buffer(nbytes=max(16, (int(dst_first) + int(m) * int(n)) * 96))
+            self._chk(_lib.gs4d_transform_records(self._h, int(src), int(n), int(xf), int(m), int(dst), int(dst_first)))
+        finally:
+            if own:
+                self.delete(xf)
         return dst
 
     def write_tensor(self, buf, tensor, offset=0):

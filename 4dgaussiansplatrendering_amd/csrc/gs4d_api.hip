@@ -1535,6 +1535,31 @@ int gs4d_build_records(gs4d_ctx* c, const gs4d_splat_params* params, size_t n, g
         });
 }
 
+// ---- records under affine maps ----
+int gs4d_transform_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf dst, size_t dst_first) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("transform_records: ") + msg).c_str()); };
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull || dst_first > 0xFFFFFFFFull) return bad("n, m or dst_first above 2^32 - 1");
+    const uint64_t total = (uint64_t)n * m;                    // (both below 2^32: no overflow)
+    if (total > 0xFFFFFFFFull || dst_first + total > 0xFFFFFFFFull) return bad("dst_first + m * n above 2^32 - 1");
+    const gs4d_buf names[3] = { src, xf, dst };
+    Buffer* S = getbuf(c, src); Buffer* X = getbuf(c, xf); Buffer* D = getbuf(c, dst);
+    if (!S || !X || !D) return bad("bad buffer name");
+    if (check_record_names(c, names, 3)) return bad("src, xf and dst must be different buffers");
+    if (S->bytes / 96 < n) return bad("src holds fewer than n records");
+    if (X->bytes / sizeof(gs4d_affine4) < m) return bad("xf holds fewer than m rows");
+    if (D->bytes / 96 < dst_first + total) return bad("dst holds fewer than dst_first + m * n records");
+    if (n == 0 || m == 0) return GS4D_OK;
+    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
+    return queue_on_lane(c, { S, X }, { D },
+        [&](Lane&) { return (int)GS4D_OK; },
+        [&](Lane& L) {
+            HIPCHK(c, launch_transform_records(L.s, S->d, n, (const gs4d_affine4*)X->d, m, (char*)D->d + dst_first * 96));
+            return (int)GS4D_OK;
+        });
+}
+
 // ---- draw ----
 static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     (void)hipSetDevice(c->device);

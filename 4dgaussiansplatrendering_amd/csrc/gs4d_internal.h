@@ -430,6 +430,12 @@ constexpr uint32_t BUILD_TILE = 256;
 struct BuildParams { const void *pos, *rot, *rot_r, *scale, *rgba, *dir, *tvar; };
 hipError_t launch_build_records(hipStream_t st, int form, const BuildParams& p, size_t n, void* dst);
 
+// ---- transform.hip ----
+// gs4d_transform_records (gs4d.h): record j * n + i of dst <- record i of the n 96-byte records of src under row j of the m rows of xf.
+// One workgroup per TRANSFORM_TILE records and row; m * n <= 0xFFFFFFFF; nothing else of dst is touched.
+constexpr uint32_t TRANSFORM_TILE = 256;
+hipError_t launch_transform_records(hipStream_t st, const void* src, size_t n, const gs4d_affine4* xf, size_t m, void* dst);
+
 // ---- cut.hip ----
 // gs4d_stat_cut (gs4d.h): a radix select over one field of a statistics table, most significant digit first — per digit one histogram
 // launch and one pick launch on `st`, no workgroup waits for another.

@@ -419,6 +419,36 @@ void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const float* q0_
     }
 }
 
+// The definition of gs4d_transform_records (gs4d.h): mean L p + o, covariance (L Sigma) L^T as two full mat4 products, rgba copied
+void gs4d_host_transform_records(size_t n, const float* rec, const gs4d_affine4* xf, float* out) {
+    Mat4 L, Lt;
+    std::memcpy(L.a, xf->l, sizeof L.a);
+    Lt = tr(L);
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = rec + 24 * i;
+        float* o = out + 24 * i;
+        for (int r = 0; r < 4; ++r) o[r] = ((((L.at(0, r) * p[0]) + (L.at(1, r) * p[1])) + (L.at(2, r) * p[2])) + (L.at(3, r) * p[3])) + xf->o[r];
+        std::memcpy(o + 4, p + 4, 16);
+        Mat4 S;
+        std::memcpy(S.a, p + 8, sizeof S.a);
+        const Mat4 g = mm(mm(L, S), Lt);
+        std::memcpy(o + 8, g.a, sizeof g.a);
+    }
+}
+
+void gs4d_host_affine4(const float q_wxyz[4], float scale, const float translate[3], const float velocity[3], float time_scale, float time_offset,
+                       gs4d_affine4* out) {
+    const Mat3 R = rot_of({ q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3] });
+    for (int c = 0; c < 3; ++c) {
+        for (int r = 0; r < 3; ++r) out->l[4 * c + r] = scale * R.at(c, r);
+        out->l[4 * c + 3] = 0.0f;                              // the time row
+        out->l[12 + c] = velocity[c];
+        out->o[c] = translate[c];
+    }
+    out->l[15] = time_scale;
+    out->o[3] = time_offset;
+}
+
 // ---- scene generators: the loops of LinearMotion::init (Scenes.h:258-279) and NonLinearMotion::init
 //      (Scenes.h:517-545) with GetModelExtrema (:75-91) and GetColor (:58-68; Utils.cpp lerp/mapf, note mapf ignores `a` in the
 //      numerator, Utils.cpp:130-133).  Pinned by the CRCs of the reference-generated SSBOs in tests/golden/manifest.json. ----

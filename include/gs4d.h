@@ -530,6 +530,61 @@ typedef struct gs4d_splat_params {
 } gs4d_splat_params;    /* 40 bytes */
 GS4D_API int gs4d_build_records(gs4d_ctx* ctx, const gs4d_splat_params* params, size_t n, gs4d_buf dst);
 
+/* ---- placing a record set: the records under a 4D affine map ----
+ * A record carries a world-space mean and a 4x4 space-time covariance, and the draws have no model matrix.  gs4d_transform_records places a set
+ * on the device: a Gaussian under x' = L x + o stays a Gaussian, with mean L mu + o and covariance L Sigma L^T, and with L a full 4x4 matrix one
+ * call covers rotation, scale and translation; a time offset and a time scale (a clip played later, slower or faster); and a velocity column, which
+ * makes a static object move.  The time conditioning of the draws then gives the right picture; no draw changes.
+ *
+ * xf is a buffer of m rows of gs4d_affine4 (80 bytes, a multiple of 16: gs4d_gather_records can carry a table of them; written through
+ * gs4d_buffer_device_ptr + gs4d_buffer_invalidate the transforms come from the device).  The call writes m * n 96-byte records: record
+ * dst_first + j * n + i of dst is transform j applied to record i of src, i < n, j < m.  m = 1, dst_first = 0 is a plain placement, m > 1 makes
+ * instances, dst_first lets several calls assemble one scene buffer from several sets.  It writes no other byte of dst and no byte of src or xf.
+ *
+ * The definition (gs4d_host_transform_records is this text, for one transform).  All arithmetic is float32, round to nearest, no contraction:
+ * every product and every sum is rounded on its own, in the order given.  The products are FULL products, as in gs4d_build_records: inf * 0 is a
+ * NaN, and a signed zero decides the sign of a zero sum.  With l, o the row's fields, p = floats 0, 1, 2, 3 of the record and
+ * S[c][k] = float 8 + 4c + k:
+ *     p'[r]    = ((((l[r]*p[0]) + (l[4+r]*p[1])) + (l[8+r]*p[2])) + (l[12+r]*p[3])) + o[r]         r = 0..3   (floats 0..3; float 3 is mu_t)
+ *     T[c][r]  = (((l[r]*S[c][0]) + (l[4+r]*S[c][1])) + (l[8+r]*S[c][2])) + (l[12+r]*S[c][3])       T = L Sigma
+ *     S'[c][r] = (((T[0][r]*l[c]) + (T[1][r]*l[4+c])) + (T[2][r]*l[8+c])) + (T[3][r]*l[12+c])       Sigma' = T L^T  (floats 8 + 4c + r)
+ *     floats 4..7 (rgba) are copied.
+ * All 16 elements of Sigma' are evaluated; nothing is mirrored, so a symmetric Sigma does not promise a bit-symmetric Sigma'.  The records have the
+ * bits of the host function, except that a word that is a NaN on both sides may differ in sign and payload (the rule of gs4d_build_records).
+ * Nothing depends on the order in which anything runs on the device: the same inputs give the same bits.
+ *
+ * The other per-record tables of the set:
+ *     time spans (gs4d_record_time_spans)  are those of the SOURCE records.  When L touches time — a time row other than (0, 0, 0, 1), a time offset
+ *                or a velocity column — they must be computed again for the transformed set; a purely spatial placement keeps them.
+ *     SH table (gs4d_shade_sh)  is not rotated.  For a rigid map M, shade the SOURCE set with the camera mapped through the inverse (cam_pos' =
+ *                M^-1 cam_pos, the time mapped back likewise), then transform: the call order per frame is
+ *                shade -> transform -> gs4d_keygen -> gs4d_sort_pairs -> draw.  Under a map that is not rigid the colours are those of the source's
+ *                directions.
+ *     depth keys (gs4d_keygen, GS4D_KEY_REF_INV_EUCLID)  move a centre by sig[3].xyz * (t - mu_t) without the division by Sigma44 that the draws'
+ *                conditioning has, as the reference does: the key's centre is the conditional centre only where Sigma44 == 1.  A time scale a gives
+ *                both factors an a, so the key's displacement takes a^2 where the conditional centre's takes none: every splat of a retimed set is
+ *                drawn where it belongs, but GS4D_MODE_4D_SORTED blends the set in the order of ITS keys, which for |a| != 1 is not the order of
+ *                the source's.  Rotation, translation and a time offset keep the order.
+ *     statistics, spatial order and kept_index tables are indexed by record: instance j's record i is record dst_first + j * n + i.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: n, m, dst_first or dst_first + m * n above 0xFFFFFFFF; a name that is not a live buffer;
+ * any two of the three buffers being the same; src smaller than 96 n bytes; xf smaller than 80 m bytes; dst holding fewer than dst_first + m * n
+ * records.  n == 0 or m == 0 with otherwise valid arguments is a no-op.  The rows of xf are data: non-finite and singular maps give what the
+ * definition gives.
+ *
+ * Ordering, exactly that of gs4d_build_records: a queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first; draws that
+ * may still have to be run again from dst are settled; the kernel is queued on the current frame lane, the call returns at once and starts no new
+ * frame; src and xf are buffers the call reads, dst one it writes (it waits, on the device, for the lanes whose draws or key generation still read
+ * dst or its shadow; later calls, other lanes and the host order themselves behind it).  gs4d_buffer_invalidate hand-offs of all three buffers are
+ * honoured.  It counts as a full write of dst, even with dst_first > 0: the buffer's version moves, what a sort index was sorted by is forgotten, and
+ * the next draw or gs4d_keygen rebuilds the SoA shadow once (gs4d_debug_shadow_builds goes up by one) — assemble a scene buffer with all its calls
+ * before the frame's gs4d_keygen. */
+typedef struct gs4d_affine4 {
+    float l[16];        /* L, column-major: L[r, c] = l[4 * c + r]; row / column 3 = time */
+    float o[4];         /* the offset (x, y, z, t)                                        */
+} gs4d_affine4;         /* 80 bytes */
+GS4D_API int gs4d_transform_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf dst, size_t dst_first);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -575,6 +630,14 @@ GS4D_API void gs4d_host_build_records_4d_tvar(size_t n, const float* pos4, const
                                               const float* rgba, float* records24);
 GS4D_API void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const float* q0_wxyz, const float* q1_wxyz, const float* scale4, const float* rgba,
                                             float* records24);
+/* The definition of gs4d_transform_records for one transform: out24 record i = records24 record i under *xf, i < n (the text above the declaration
+ * of gs4d_transform_records).  out24 must not overlap records24. */
+GS4D_API void gs4d_host_transform_records(size_t n, const float* records24, const gs4d_affine4* xf, float* out24);
+/* One row of gs4d_transform_records' table: the upper 3x3 of L is scale * R(q) with the R of gs4d_host_splat3d_cov (the matrix of the quaternion as
+ * given, not normalised), each element one product; column 3, rows 0..2 = velocity (a source at time t lands velocity * t further on);
+ * L[3, 3] = time_scale and the time row is otherwise 0; o = (translate, time_offset).  A source time t shows at time_scale * t + time_offset. */
+GS4D_API void gs4d_host_affine4(const float q_wxyz[4], float scale, const float translate[3], const float velocity[3], float time_scale, float time_offset,
+                                gs4d_affine4* out);
 
 /* Scene generators and the .vdata loader (f2): the CPU loops that fill the SSBO before the path starts. */
 GS4D_API void gs4d_host_scene_linear(size_t nverts, const float* verts6, int steps, float time_multiplier, float object_scale, const float splat_scale[3],
