@@ -25,6 +25,7 @@ KEY_REF_INV_EUCLID, KEY_VIEW_Z = 0, 1
 KEEP_INVERT = 1                                           # gs4d_keep_rule.flags: keep exactly the records the rule would drop
 STAT_PIXELS, STAT_WMAX, STAT_WSUM = 0, 1, 2               # gs4d_stat_cut: the field of gs4d_record_stat
 PARAMS_3D, PARAMS_4D_VEL, PARAMS_4D_2Q = 0, 1, 2           # gs4d_splat_params.form
+EDIT_SET, EDIT_MUL, EDIT_LERP, EDIT_COPY = 0, 1, 2, 3      # gs4d_colour_edit.op
 TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
@@ -94,6 +95,7 @@ def _load():
         "gs4d_spatial_order": (i32, [vp, u32, sz, sz, sz, u32]),
         "gs4d_gather_records": (i32, [vp, u32, sz, u32, sz, sz, u32]),
         "gs4d_shade_sh": (i32, [vp, u32, sz, u32, sz, i32, f32, vp]),
+        "gs4d_edit_colours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_build_records": (i32, [vp, vp, sz, u32]),
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_set_profiling": (i32, [vp, i32]),
@@ -119,6 +121,7 @@ def _load():
         "gs4d_host_build_records_4d_tvar": (None, [sz, vp, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_build_records_4d_2q": (None, [sz, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_transform_records": (None, [sz, vp, vp, vp]),
+        "gs4d_host_edit_colours": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
         "gs4d_host_scene_nonlinear": (None, [sz, vp, i32, f32, f32, f32, vp, f32, f32, f32, sz, vp]),
@@ -273,6 +276,58 @@ def transform_records_host(records, xf):
     for j in range(rows.shape[0]):
         _lib.gs4d_host_transform_records(rec.shape[0], _ptr(rec), _ptr(rows[j]), _ptr(out[j]))
     return out[0] if single else out
+
+
+# gs4d_colour_edit and gs4d_keep_rule (include/gs4d.h) as numpy records
+COLOUR_EDIT = np.dtype([("op", "<u4"), ("channels", "<u4"), ("value", "<f4", (4,)), ("amount", "<f4"), ("reserved", "<u4")])
+KEEP_RULE = np.dtype([("min_pixels", "<u4"), ("min_wmax", "<u4"), ("min_wsum", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])
+RECORD_STAT = np.dtype([("pixels", "<u4"), ("wmax", "<f4"), ("wsum", "<u8")])
+EDIT_OPS = {"set": EDIT_SET, "mul": EDIT_MUL, "lerp": EDIT_LERP, "copy": EDIT_COPY}
+_CHANNEL_BITS = {"r": 1, "g": 2, "b": 4, "a": 8}
+
+
+def _keep_rule(min_pixels=1, min_wmax=0.0, min_wsum=0, invert=False):
+    """one gs4d_keep_rule from compact_records' keywords: min_wmax is a weight (float32), min_wsum is in units of 2^-24"""
+    rule = np.zeros(1, KEEP_RULE)
+    rule["min_pixels"], rule["min_wmax"], rule["min_wsum"] = int(min_pixels), np.array([min_wmax], np.float32).view(np.uint32)[0], int(min_wsum)
+    rule["flags"] = KEEP_INVERT if invert else 0
+    return rule
+
+
+def colour_edit(op, value=(0.0, 0.0, 0.0, 0.0), channels="rgb", amount=0.0):
+    """one gs4d_colour_edit (COLOUR_EDIT): op "set" / "mul" / "lerp" / "copy" or an EDIT_* constant; channels a string over "rgba" or the mask 1 .. 15
+    (1 r, 2 g, 4 b, 8 a); value: up to four operands, r first."""
+    e = np.zeros(1, COLOUR_EDIT)
+    e["op"] = EDIT_OPS[op] if isinstance(op, str) else int(op)
+    if isinstance(channels, str):
+        mask = 0
+        for ch in channels:
+            mask |= _CHANNEL_BITS[ch]
+        channels = mask
+    e["channels"] = int(channels)
+    v = _f32(value).ravel()
+    e["value"][0, :v.size] = v[:4]
+    e["amount"] = np.float32(amount)
+    return e
+
+
+def edit_colours_host(records, op, value=(0.0, 0.0, 0.0, 0.0), channels="rgb", amount=0.0, stats=None, from_=None, **rule):
+    """gs4d_host_edit_colours, the definition of Context.edit_colours: a copy of records [n, 24] with the rgba of the selected records edited.
+    stats: a RECORD_STAT array of n rows (the rule keywords of compact_records select by it) or None: every record; from_: [n, 24], for "copy"."""
+    rec = np.array(_f32(records).reshape(-1, 24), copy=True)
+    n = rec.shape[0]
+    e = colour_edit(op, value, channels, amount)
+    if stats is None and rule:
+        raise TypeError("edit_colours_host: a rule without stats")
+    st = None if stats is None else np.ascontiguousarray(stats, RECORD_STAT)
+    if st is not None and st.shape[0] < n:
+        raise ValueError("edit_colours_host: stats holds fewer than n rows")
+    fr = None if from_ is None else _f32(from_).reshape(-1, 24)
+    if int(e["op"][0]) == EDIT_COPY and (fr is None or fr.shape[0] < n):
+        raise ValueError("edit_colours_host: copy needs n records in from_")
+    k = _keep_rule(**rule)
+    _lib.gs4d_host_edit_colours(n, _ptr(rec), _ptr(st) if st is not None else None, _ptr(k) if st is not None else None, _ptr(e), _ptr(fr) if fr is not None else None)
+    return rec
 
 
 def scene_linear(verts6, steps=50, time_multiplier=1.0, object_scale=5.0, splat_scale=(4.0, 4.0, 1.0), lifetime=1.0, fade=0.5, speed=1.0):
@@ -689,7 +744,7 @@ class Context:
         self._chk(_lib.gs4d_set_depth_test(self._h, int(plane or 0)))
 
     # record statistics: what each record contributed to the picture
-    RECORD_STAT = np.dtype([("pixels", "<u4"), ("wmax", "<f4"), ("wsum", "<u8")])
+    RECORD_STAT = RECORD_STAT
 
     def record_stats(self, n):
         """A zeroed buffer of n gs4d_record_stat for set_record_stats."""
@@ -706,7 +761,7 @@ class Context:
         return self.read(buf, self.RECORD_STAT, n)
 
     # compaction: prune a record set by its record statistics, on the device
-    KEEP_RULE = np.dtype([("min_pixels", "<u4"), ("min_wmax", "<u4"), ("min_wsum", "<u8"), ("flags", "<u4"), ("reserved", "<u4")])
+    KEEP_RULE = KEEP_RULE
     COMPACT_COUNT = np.dtype([("kept", "<u4"), ("written", "<u4")])
 
     def compact_records(self, stats, n, src=None, stride=96, dst=None, kept_index=None, count=None, min_pixels=1, min_wmax=0.0, min_wsum=0, invert=False):
@@ -714,9 +769,7 @@ class Context:
         and wsum >= min_wsum) != invert, with the record_stats row stats[i]; the kept `stride`-byte records of `src` go to `dst` in
         ascending i, their indices (uint32) to `kept_index`, and `count` (a new 8-byte buffer if None) receives COMPACT_COUNT {kept, written}.
         Any of dst / kept_index may be None.  min_wmax is a weight (float32), min_wsum is in units of 2^-24.  Asynchronous; returns `count`."""
-        rule = np.zeros(1, self.KEEP_RULE)
-        rule["min_pixels"], rule["min_wmax"], rule["min_wsum"] = int(min_pixels), np.array([min_wmax], np.float32).view(np.uint32)[0], int(min_wsum)
-        rule["flags"] = KEEP_INVERT if invert else 0
+        rule = _keep_rule(min_pixels, min_wmax, min_wsum, invert)
         if count is None:
             count = self.buffer(nbytes=self.COMPACT_COUNT.itemsize)
         self._chk(_lib.gs4d_compact_records(self._h, int(stats), int(n), _ptr(rule), int(src or 0), int(stride), int(dst or 0), int(kept_index or 0), int(count)))
@@ -893,6 +946,31 @@ class Context:
         if sh_stride is None:
             sh_stride = sh_row_bytes(degree)
         self._chk(_lib.gs4d_shade_sh(self._h, int(data), int(n), int(sh), int(sh_stride), int(degree), float(t), _ptr(_f32(cam_pos))))
+
+    # colour edits by a selection: recolour, hide or restore selected records
+    COLOUR_EDIT = COLOUR_EDIT
+
+    def edit_colours(self, data, n, op, value=(0.0, 0.0, 0.0, 0.0), channels="rgb", amount=0.0, stats=None, from_=None, **rule):
+        """gs4d_edit_colours: the rgba (floats 4..7) of the selected ones of the first n 96-byte records of `data`, edited in place — op "set"
+        (c = value), "mul" (c = c * value), "lerp" (c = c + amount * (value - c)) or "copy" (c = the same float of record i of `from_`), on the
+        channels named ("rgba" letters or the mask 1 .. 15).  stats: a record_stats table (count_ids, set_record_stats) whose row i selects
+        record i by compact_records' rule keywords (min_pixels, min_wmax, min_wsum, invert); None: every record.  With the bits of
+        edit_colours_host.  A colour-only write: a current SoA shadow is patched, not rebuilt.  Per frame: (shade_sh), edit, keygen, sort,
+        draw.  Asynchronous."""
+        if stats is None and rule:
+            raise TypeError("edit_colours: a rule without stats")
+        e = colour_edit(op, value, channels, amount)
+        k = _keep_rule(**rule) if stats is not None else None
+        self._chk(_lib.gs4d_edit_colours(self._h, int(data), int(n), _ptr(e), int(stats or 0), _ptr(k) if k is not None else None, int(from_ or 0)))
+
+    def hide(self, data, n, stats, **rule):
+        """The selected records' alpha set to 0 (edit_colours "set" on "a"): with the default blend function they draw nothing, count nothing and
+        are never picked — the picture of the compacted complement without moving a record.  restore_colours puts them back."""
+        self.edit_colours(data, n, "set", (0.0, 0.0, 0.0, 0.0), "a", stats=stats, **rule)
+
+    def restore_colours(self, data, n, from_, stats=None, **rule):
+        """The rgba of the selected records (every record if stats is None) copied back from the pristine records `from_` (edit_colours "copy")."""
+        self.edit_colours(data, n, "copy", channels="rgba", stats=stats, from_=from_, **rule)
 
     # records from parameters: the records of a splat set built on the device (DESIGN.md §4)
     PARAM_BUFFERS = ("pos", "rot", "rot_r", "scale", "rgba", "dir", "tvar")

@@ -19,13 +19,7 @@ constexpr uint32_t CT_THREADS = 256, CT_WAVES = CT_THREADS / 64, CT_ROUNDS = COM
 static_assert(COMPACT_TILE >= 256 && COMPACT_TILE <= 4096 && (COMPACT_TILE & (COMPACT_TILE - 1)) == 0, "a power of two between 256 and 4096");
 static_assert(CT_ROUNDS * CT_WAVES <= 64, "one wave scans the (round, wave) counts of a tile");
 
-__device__ __forceinline__ bool keep_row(const uint4 row, const KeepRule k) {
-    const uint64_t wsum = (uint64_t)row.z | ((uint64_t)row.w << 32);          // gs4d_record_stat: pixels, wmax, wsum (little endian)
-    return (row.x >= k.min_pixels && row.y >= k.min_wmax && wsum >= k.min_wsum) != (k.invert != 0u);
-}
-// gs4d_time_span {t_first, t_last} against the window [t0, t1]: the two closed intervals meet (an empty span, {+inf, -inf}, meets nothing)
-__device__ __forceinline__ bool keep_row(const float2 row, const WindowRule k) { return row.x <= k.t1 && row.y >= k.t0; }
-
+// (keep_row, the rule of either table: gs4d_internal.h)
 // a row past the end of the table (never kept: keep_flags tests the index as well)
 __device__ __forceinline__ uint4 zero_row(const uint4*) { return make_uint4(0u, 0u, 0u, 0u); }
 __device__ __forceinline__ float2 zero_row(const float2*) { return make_float2(0.0f, 0.0f); }

@@ -1498,6 +1498,52 @@ int gs4d_shade_sh(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_s
         });
 }
 
+// ---- colour edits by a selection ----
+int gs4d_edit_colours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_colour_edit* edit, gs4d_buf stats, const gs4d_keep_rule* rule, gs4d_buf from) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("edit_colours: ") + msg).c_str()); };
+    if (!edit) return bad("edit == NULL");
+    if (edit->op != GS4D_EDIT_SET && edit->op != GS4D_EDIT_MUL && edit->op != GS4D_EDIT_LERP && edit->op != GS4D_EDIT_COPY) return bad("unknown op");
+    if (edit->channels == 0u || edit->channels > 15u) return bad("channels must be 1 .. 15");
+    if (edit->reserved != 0u) return bad("non-zero reserved field in the edit");
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    if ((stats != 0) != (rule != nullptr)) return bad("stats and rule are given together or not at all");
+    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
+    const bool copy = edit->op == GS4D_EDIT_COPY;
+    if (copy && from == 0) return bad("GS4D_EDIT_COPY needs from");
+    if (!copy && from != 0) return bad("from must be 0 unless the op is GS4D_EDIT_COPY");
+    const gs4d_buf names[3] = { data, stats, from };
+    Buffer* D = getbuf(c, data);
+    if (!D) return bad("data is not a live buffer");
+    if (const int wrong = check_record_names(c, names, 3)) return bad(wrong == 1 ? "bad buffer name" : "data, stats and from must be different buffers");
+    Buffer* S = getbuf(c, stats); Buffer* F = getbuf(c, from);
+    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
+    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (F && F->bytes / 96 < n) return bad("from holds fewer than n records");
+    if (n == 0) return GS4D_OK;
+    const EditOp e{ edit->op, edit->channels, { edit->value[0], edit->value[1], edit->value[2], edit->value[3] }, edit->amount };
+    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
+    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
+    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    // A colour-only write, as gs4d_shade_sh's, extended to the alpha: nothing the library derives from a record buffer reads floats 4..7 (k_soa_repack
+    // copies them to plane 1 whole; the bounding box and the key bounds read position, mu_t and sig[3].xyz, the layout choice sig and mu_t), so a shadow
+    // that is current stays current — the kernel reads the old colour from its plane 1 and writes the new one there too.  Decided once the pending
+    // draws are settled (a re-run may rebuild the shadow) and before any buffer state is touched.
+    bool patch = false;
+    return queue_on_lane(c, { S, F }, { D },
+        [&](Lane&) {
+            patch = D->soa && D->soa_n == D->bytes / 96 && D->soa_version == D->version;
+            return S ? scan_reserve(c, *S) : (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            if (S) { int rc = scan_begin(c, L, *S); if (rc) return rc; }
+            HIPCHK(c, launch_edit_colours(L.s, D->d, n, e, S ? (const gs4d_record_stat*)S->d : nullptr, k, F ? F->d : nullptr, patch ? D->soa + D->soa_n : nullptr));
+            if (patch) D->soa_version = D->version;
+            return S ? scan_end(c, L, *S) : (int)GS4D_OK;
+        });
+}
+
 // ---- records from parameters ----
 int gs4d_build_records(gs4d_ctx* c, const gs4d_splat_params* params, size_t n, gs4d_buf dst) {
     if (!c) return GS4D_E_INVALID;

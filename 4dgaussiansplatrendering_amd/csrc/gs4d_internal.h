@@ -402,6 +402,15 @@ hipError_t launch_compact(hipStream_t st, const gs4d_time_span* spans, size_t n,
                           const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count);
 // gs4d_record_time_spans: spans[i] of the n 96-byte records in `data` (one launch; n == 0: none)
 hipError_t launch_time_spans(hipStream_t st, const void* data, size_t n, float min_opacity, gs4d_time_span* spans);
+#ifdef __HIPCC__
+// the rule of a table row, for every kernel that selects by one (compact.hip, edit.hip)
+__device__ __forceinline__ bool keep_row(const uint4 row, const KeepRule k) {
+    const uint64_t wsum = (uint64_t)row.z | ((uint64_t)row.w << 32);          // gs4d_record_stat: pixels, wmax, wsum (little endian)
+    return (row.x >= k.min_pixels && row.y >= k.min_wmax && wsum >= k.min_wsum) != (k.invert != 0u);
+}
+// gs4d_time_span {t_first, t_last} against the window [t0, t1]: the two closed intervals meet (an empty span, {+inf, -inf}, meets nothing)
+__device__ __forceinline__ bool keep_row(const float2 row, const WindowRule k) { return row.x <= k.t1 && row.y >= k.t0; }
+#endif
 
 // ---- reorder.hip ----
 // gs4d_spatial_order (gs4d.h): the box of the placed records, then one 31-bit key per record — the 30-bit Morton code of its cell, or
@@ -422,6 +431,16 @@ hipError_t launch_gather_records(hipStream_t st, const uint32_t* index, size_t m
 // same three floats in .xyz, or null.  One workgroup per SHADE_TILE records.
 constexpr uint32_t SHADE_TILE = 256;
 hipError_t launch_shade_sh(hipStream_t st, void* records, size_t n, const void* sh, size_t sh_stride, int degree, float t, const float cam[3], float4* plane1);
+
+// ---- edit.hip ----
+// gs4d_edit_colours (gs4d.h): floats 4..7 of the selected ones of the first n 96-byte records edited by e (validated).  stats: the table
+// whose row i selects record i by `rule` (keep_row), or null: every record.  from: the n 96-byte records GS4D_EDIT_COPY takes the colour from, else
+// null.  plane1: the colour plane of the records' SoA shadow (soa + soa_n) — it is current: the old colour is read from it and the new one written to
+// it as well — or null.  One workgroup per EDIT_TILE records.
+constexpr uint32_t EDIT_TILE = 256;
+struct EditOp { uint32_t op, channels; float value[4]; float amount; };      // gs4d_colour_edit, validated
+hipError_t launch_edit_colours(hipStream_t st, void* records, size_t n, const EditOp& e, const gs4d_record_stat* stats, const KeepRule& rule,
+                               const void* from, float4* plane1);
 
 // ---- build.hip ----
 // gs4d_build_records (gs4d.h): the first n 96-byte records of dst from row i of each parameter array of the form (GS4D_PARAMS_*; rows of

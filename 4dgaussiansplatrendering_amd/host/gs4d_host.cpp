@@ -436,6 +436,32 @@ void gs4d_host_transform_records(size_t n, const float* rec, const gs4d_affine4*
     }
 }
 
+// The definition of gs4d_edit_colours (gs4d.h), in place: the selection by the rule of gs4d_compact_records, then the edit per channel of the mask.
+// This file is built with -ffp-contract=off: the product and the sums of MUL and LERP are rounded one by one.  SET and COPY move bits.  An edit
+// the device call would refuse (unknown op, channels outside 1 .. 15) edits nothing.
+void gs4d_host_edit_colours(size_t n, float* rec, const gs4d_record_stat* stats, const gs4d_keep_rule* rule, const gs4d_colour_edit* edit, const float* from) {
+    if (!edit || edit->op > (uint32_t)GS4D_EDIT_COPY || edit->channels == 0u || edit->channels > 15u) return;
+    if (edit->op == (uint32_t)GS4D_EDIT_COPY && !from) return;
+    if (stats && !rule) return;
+    const bool invert = stats && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    for (size_t i = 0; i < n; ++i) {
+        if (stats) {
+            const gs4d_record_stat& s = stats[i];
+            if ((s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) == invert) continue;
+        }
+        for (uint32_t ch = 0; ch < 4u; ++ch) {
+            if (!((edit->channels >> ch) & 1u)) continue;
+            float* const c = rec + 24 * i + 4 + ch;
+            switch (edit->op) {
+                case GS4D_EDIT_SET: std::memcpy(c, &edit->value[ch], 4); break;
+                case GS4D_EDIT_MUL: *c = *c * edit->value[ch]; break;
+                case GS4D_EDIT_LERP: { const float d = edit->value[ch] - *c; const float step = edit->amount * d; *c = *c + step; break; }
+                default: std::memcpy(c, from + 24 * i + 4 + ch, 4); break;
+            }
+        }
+    }
+}
+
 void gs4d_host_affine4(const float q_wxyz[4], float scale, const float translate[3], const float velocity[3], float time_scale, float time_offset,
                        gs4d_affine4* out) {
     const Mat3 R = rot_of({ q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3] });

@@ -585,6 +585,67 @@ typedef struct gs4d_affine4 {
 } gs4d_affine4;         /* 80 bytes */
 GS4D_API int gs4d_transform_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf dst, size_t dst_first);
 
+/* ---- colour edits by a selection: recolour, hide or restore selected records (no reference counterpart) ----
+ * What a selection is shown with.  The selection chain ends in a statistics table — gs4d_count_ids for what a region of the ID planes shows,
+ * gs4d_set_record_stats for what a draw showed, a gs4d_stat_cut threshold for the k most visible records; gs4d_edit_colours edits the rgba (floats
+ * 4..7) of the records of `data` that such a table selects, in place and on the device.
+ *
+ * Selection.  Record i < n of the 96-byte records in data is SELECTED iff stats == 0 (every record), or row i of the gs4d_record_stat table
+ * `stats` passes `rule` under exactly the predicate of gs4d_compact_records: (pixels >= min_pixels && wmax >= min_wmax && wsum >= min_wsum) != invert.
+ * A gs4d_count_ids table with {1, 0, 0, 0} selects what the region shows, the same with GS4D_KEEP_INVERT everything else (isolate).
+ *
+ * The edit.  For a selected record and each channel ch whose bit is set in `channels`, with c = float 4 + ch of the record:
+ *     GS4D_EDIT_SET    c' = value[ch]                                     (the bits)
+ *     GS4D_EDIT_MUL    c' = c * value[ch]
+ *     GS4D_EDIT_LERP   c' = c + (amount * (value[ch] - c))
+ *     GS4D_EDIT_COPY   c' = float 4 + ch of record i of `from`             (the bits)
+ * The arithmetic is float32, round to nearest, no contraction: every product and every sum is rounded on its own, in the order its parentheses
+ * give.  value and amount are data: non-finite operands give what these lines give.  A result that is a NaN may differ from
+ * gs4d_host_edit_colours' in sign and payload for MUL and LERP (the rule of gs4d_build_records); SET and COPY are bit copies, NaNs included.
+ *
+ * What is written.  Every other word of a selected record, every byte of a record that is not selected and every byte of data beyond record n - 1
+ * keep their bits; stats and from are never written.  Nothing depends on the order in which anything runs on the device.
+ *
+ * An alpha of 0.  What the time-window section says of a dead record holds for a record whose float 7 is exactly 0 (+0 or -0): with the default
+ * blend function and a finite time opacity its alpha is 0 at every pixel, so it is an exact no-op in the colour image and in the aux planes
+ * (C += 0, T *= 1, weight 0), it never becomes an ID candidate and it adds nothing to record statistics.  Hiding a selection with {GS4D_EDIT_SET,
+ * channels = 8, value[3] = 0} therefore gives the bits of a draw of the compacted complement (gs4d_compact_records with the inverted rule; record
+ * indices in the ID planes and statistics rows mapped through kept_index), in GS4D_MODE_4D_SORTED after gs4d_keygen + gs4d_sort_pairs of the
+ * respective set and in GS4D_MODE_4D_DIRECT — without moving a record, so the set, its tables and its shadow stay what they were.  A later
+ * GS4D_EDIT_COPY from a pristine copy puts the colours back.  Nothing is promised for any other blend function.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: edit == NULL, an unknown op, channels == 0 or > 15, reserved != 0; n > 0xFFFFFFFF; data not
+ * a live buffer or smaller than 96 n bytes; exactly one of stats / rule given; a rule with an unknown flag or reserved != 0; stats not a live buffer
+ * or smaller than 16 n bytes; GS4D_EDIT_COPY without a live `from` of at least 96 n bytes; any other op with from != 0; any two of the named buffers
+ * being the same buffer.  n == 0 with otherwise valid arguments is a no-op.
+ *
+ * Ordering: that of gs4d_shade_sh for data and from, that of gs4d_compact_records for stats.  A queued gs4d_keygen / gs4d_sort_pairs that names one
+ * of the buffers is launched first.  The table is taken as gs4d_buffer_read takes it: draws that add to it (gs4d_set_record_stats), issued before the
+ * call on any frame lane, are settled first, re-runs included; a draw issued afterwards that adds to it waits on the device until the call's kernel
+ * has read it, and a host write waits as it does for any reader.  Draws that may still have to be run again from data are settled before it is
+ * overwritten.  The kernel is queued on the current frame lane, the call returns at once and starts no new frame; data waits, on the device, for the
+ * lanes whose draws or key generation still read it or its shadow; later calls, other lanes and the host order themselves behind the call.
+ * gs4d_buffer_invalidate hand-offs of all three buffers are honoured.
+ *
+ * What the write keeps: gs4d_shade_sh's colour-only contract, extended to the alpha.  Nothing the library derives from a record buffer reads floats
+ * 4..7 — the shadow carries them in its colour plane, the bounding box and the key bounds read position, mu_t and sig[3].xyz, the layout choice sig
+ * and mu_t — so if the SoA shadow of data is current when the call is made, the same kernel writes the edited rgba into the shadow's colour plane and
+ * the shadow stays current: the next draw neither repacks nor waits, and gs4d_debug_shadow_builds does not move.  If it is not current, only the
+ * records are written and the next draw builds it, as it would have anyway.  As with gs4d_shade_sh the provenance of a sort index is NOT kept: the
+ * call order per frame is (gs4d_shade_sh) -> gs4d_edit_colours -> gs4d_keygen -> gs4d_sort_pairs -> draw.  Tables of the caller's that depend on
+ * the alpha (gs4d_record_time_spans: a record of alpha <= 0 has the span "never") are the caller's to recompute. */
+enum { GS4D_EDIT_SET = 0, GS4D_EDIT_MUL = 1, GS4D_EDIT_LERP = 2, GS4D_EDIT_COPY = 3 };
+typedef struct gs4d_colour_edit {
+    uint32_t op;         /* GS4D_EDIT_*                                                          */
+    uint32_t channels;   /* bit ch set: channel ch of rgba is edited (1 r, 2 g, 4 b, 8 a); 1 .. 15 */
+    float    value[4];   /* SET, MUL, LERP: the operand per channel; COPY: ignored                 */
+    float    amount;     /* LERP only; ignored otherwise                                           */
+    uint32_t reserved;   /* must be 0                                                              */
+} gs4d_colour_edit;      /* 32 bytes */
+GS4D_API int gs4d_edit_colours(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_colour_edit* edit,
+                               gs4d_buf stats /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff stats == 0 */,
+                               gs4d_buf from /* GS4D_EDIT_COPY: the source records; otherwise 0 */);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -601,7 +662,7 @@ GS4D_API int gs4d_get_stats(gs4d_ctx* ctx, uint64_t stats[8]);                  
  * draw has a depth test (gs4d_set_depth_test), and the record is valid, else 0; GS4D_MODE_2D records always have 0. */
 GS4D_API int gs4d_debug_read_projected(gs4d_ctx* ctx, float* out16, size_t nrecords);
 /* How many times the library has (re)built the SoA shadow of this record buffer (a repack of the whole set, at the first draw or gs4d_keygen after a
- * write to it): gs4d_shade_sh on a buffer whose shadow is current does not add to it. */
+ * write to it): gs4d_shade_sh or gs4d_edit_colours on a buffer whose shadow is current does not add to it. */
 GS4D_API int gs4d_debug_shadow_builds(gs4d_ctx* ctx, gs4d_buf buf, uint64_t* builds);
 
 /* ---- host-side parameterisation (CPU code inside libgs4d.so; mirrors the reference's host math so that a caller
@@ -633,6 +694,11 @@ GS4D_API void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const f
 /* The definition of gs4d_transform_records for one transform: out24 record i = records24 record i under *xf, i < n (the text above the declaration
  * of gs4d_transform_records).  out24 must not overlap records24. */
 GS4D_API void gs4d_host_transform_records(size_t n, const float* records24, const gs4d_affine4* xf, float* out24);
+/* The definition of gs4d_edit_colours, in place on the n records of records24 (the text above its declaration): stats == NULL selects every record
+ * (rule is then ignored), else rule is not NULL; from24 is read by GS4D_EDIT_COPY only and must not overlap records24.  An edit the device call
+ * would refuse (an unknown op, channels outside 1 .. 15) edits nothing. */
+GS4D_API void gs4d_host_edit_colours(size_t n, float* records24, const gs4d_record_stat* stats, const gs4d_keep_rule* rule,
+                                     const gs4d_colour_edit* edit, const float* from24);
 /* One row of gs4d_transform_records' table: the upper 3x3 of L is scale * R(q) with the R of gs4d_host_splat3d_cov (the matrix of the quaternion as
  * given, not normalised), each element one product; column 3, rows 0..2 = velocity (a source at time t lands velocity * t further on);
  * L[3, 3] = time_scale and the time row is otherwise 0; o = (translate, time_offset).  A source time t shows at time_scale * t + time_offset. */
