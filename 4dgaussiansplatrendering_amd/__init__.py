@@ -26,6 +26,8 @@ KEEP_INVERT = 1                                           # gs4d_keep_rule.flags
 STAT_PIXELS, STAT_WMAX, STAT_WSUM = 0, 1, 2               # gs4d_stat_cut: the field of gs4d_record_stat
 PARAMS_3D, PARAMS_4D_VEL, PARAMS_4D_2Q = 0, 1, 2           # gs4d_splat_params.form
 EDIT_SET, EDIT_MUL, EDIT_LERP, EDIT_COPY = 0, 1, 2, 3      # gs4d_colour_edit.op
+CQ_BOX, CQ_SPHERE, CQ_SCREEN, CQ_FRAME, CQ_SKIP_HIDDEN, CQ_SKIP_DEAD = 1, 2, 4, 8, 16, 32      # gs4d_centre_query.tests
+CQ_ADD, CQ_REMOVE = 0, 1                                   # gs4d_centre_query.op
 TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
@@ -96,6 +98,7 @@ def _load():
         "gs4d_gather_records": (i32, [vp, u32, sz, u32, sz, sz, u32]),
         "gs4d_shade_sh": (i32, [vp, u32, sz, u32, sz, i32, f32, vp]),
         "gs4d_edit_colours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
+        "gs4d_count_centres": (i32, [vp, u32, sz, vp, u32, u32]),
         "gs4d_build_records": (i32, [vp, vp, sz, u32]),
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_set_profiling": (i32, [vp, i32]),
@@ -122,6 +125,7 @@ def _load():
         "gs4d_host_build_records_4d_2q": (None, [sz, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_transform_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_edit_colours": (None, [sz, vp, vp, vp, vp, vp]),
+        "gs4d_host_count_centres": (None, [sz, vp, vp, i32, i32, vp, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
         "gs4d_host_scene_nonlinear": (None, [sz, vp, i32, f32, f32, f32, vp, f32, f32, f32, sz, vp]),
@@ -442,6 +446,64 @@ class IdRegion(C.Structure):
     """gs4d_id_region (include/gs4d.h): the rectangle, the draws and the least weight of a gs4d_count_ids call."""
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("draw_first", C.c_uint32), ("draw_last", C.c_uint32),
                 ("min_weight", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class CentreQuery(C.Structure):
+    """gs4d_centre_query (include/gs4d.h): the tests, the op and the operands of a gs4d_count_centres call."""
+    _fields_ = [("tests", C.c_uint32), ("op", C.c_uint32), ("t", C.c_float), ("reserved", C.c_uint32), ("frame", C.c_float * 12),
+                ("box_lo", C.c_float * 3), ("box_hi", C.c_float * 3), ("sphere", C.c_float * 4), ("view", C.c_float * 16), ("proj", C.c_float * 16),
+                ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("depth_min", C.c_float), ("depth_max", C.c_float)]
+
+
+def centre_query(box=None, sphere=None, frame=None, screen=None, rect=None, depth=(0.0, float("inf")), t=0.0, skip_hidden=False, skip_dead=False,
+                 remove=False):
+    """one gs4d_centre_query (CentreQuery).  box=(lo, hi): the centre inside the closed box; sphere=(c, r): inside the closed ball; frame: a 3x4
+    world -> volume-frame map, 12 floats column-major (or a [3, 4] array given as rows), applied before box and sphere; screen=(view, proj): the
+    centre projects into rect=(x, y, w, h) (y from the bottom row; required with screen) at a view depth inside depth=(min, max); t: the time the
+    centre is taken at; skip_hidden / skip_dead: leave out records of alpha <= 0 / dead at t; remove: zero the rows instead of adding to them."""
+    q = CentreQuery()
+    q.t = float(t)
+    q.op = CQ_REMOVE if remove else CQ_ADD
+    tests = (CQ_SKIP_HIDDEN if skip_hidden else 0) | (CQ_SKIP_DEAD if skip_dead else 0)
+    if box is not None:
+        tests |= CQ_BOX
+        q.box_lo[:], q.box_hi[:] = [float(v) for v in _f32(box[0]).ravel()[:3]], [float(v) for v in _f32(box[1]).ravel()[:3]]
+    if sphere is not None:
+        tests |= CQ_SPHERE
+        q.sphere[:] = [float(v) for v in _f32(sphere[0]).ravel()[:3]] + [float(np.float32(sphere[1]))]
+    if frame is not None:
+        tests |= CQ_FRAME
+        f = _f32(frame)
+        q.frame[:] = [float(v) for v in (f.T.ravel() if f.shape == (3, 4) else f.ravel())]
+    if screen is not None:
+        if rect is None:
+            raise TypeError("centre_query: screen needs rect")
+        tests |= CQ_SCREEN
+        q.view[:], q.proj[:] = [float(v) for v in _f32(screen[0]).ravel()], [float(v) for v in _f32(screen[1]).ravel()]
+        q.x, q.y, q.w, q.h = (int(v) for v in rect)
+        q.depth_min, q.depth_max = float(np.float32(depth[0])), float(np.float32(depth[1]))
+    elif rect is not None:
+        raise TypeError("centre_query: rect without screen")
+    q.tests = tests
+    return q
+
+
+def count_centres_host(records, query, width, height, mask=None, stats=None):
+    """gs4d_host_count_centres, the definition of Context.count_centres: the RECORD_STAT table (a copy of `stats`, rows of 16 bytes, or n zeroed rows
+    if None) after the query (centre_query) on records [n, 24] for a width x height image; mask: an (h, w) bool / uint8 array, rows bottom-up, or None."""
+    rec = _f32(records).reshape(-1, 24)
+    n = rec.shape[0]
+    st = np.zeros(n, RECORD_STAT) if stats is None else np.array(np.ascontiguousarray(stats), copy=True)
+    if st.dtype.itemsize != 16 or st.ndim != 1 or st.shape[0] < n:
+        raise ValueError("count_centres_host: stats must be at least n rows of 16 bytes")
+    st = st.view(RECORD_STAT)                                  # (the bytes as they are: a table whose wmax is kept as its bit pattern is not converted)
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+        if m.shape != (query.h, query.w):
+            raise ValueError(f"count_centres_host: expected a mask of shape {(query.h, query.w)}, got {m.shape}")
+    _lib.gs4d_host_count_centres(n, _ptr(rec), C.byref(query), int(width), int(height), _ptr(m) if m is not None else None, _ptr(st))
+    return st
 
 
 class SplatParams(C.Structure):
@@ -862,6 +924,46 @@ class Context:
         Blocking, as prune is: it reads the count back."""
         stats = self.record_stats(n)
         self.count_ids(stats, n, rect=rect, mask=mask, draws=draws, min_weight=min_weight)
+        if src is not None:
+            return self.prune(stats, n, src, stride=stride, min_pixels=1) + (stats,)
+        count = self.compact_records(stats, n, stride=stride, min_pixels=1)
+        kept, _ = self.read_compact_count(count)
+        kept_index = self.buffer(nbytes=max(16, kept * 4))
+        self.compact_records(stats, n, stride=stride, kept_index=kept_index, count=count, min_pixels=1)
+        self.delete(count)
+        return None, kept_index, kept, stats
+
+    # selection by where a record is: a statistics table from a volume or a screen region (DESIGN.md §4)
+    def count_centres(self, stats, n, data, mask=None, **query):
+        """gs4d_count_centres: row i of the record_stats buffer `stats` gets one fragment of weight 1 (remove=True: becomes zero) iff the centre of
+        record i < n of `data` at time t passes every test of the query — centre_query's keywords, or query=a CentreQuery — whether anything shows
+        it or not.  mask: a buffer of w*h bytes, rows bottom-up, or an (h, w) bool / uint8 array that is uploaded for the call, as count_ids takes
+        it; with screen= only.  Nothing zeroes `stats`: calls add up (rule min_pixels=1: the union; min_pixels=k: the intersection of k calls).
+        With the bits of count_centres_host.  Asynchronous with a buffer mask or none."""
+        q = query.pop("query", None)
+        if q is None:
+            q = centre_query(**query)
+        elif query:
+            raise TypeError("count_centres: query= excludes centre_query's keywords")
+        own = mask is not None and not isinstance(mask, (int, np.integer))
+        if own:
+            a = np.ascontiguousarray(np.asarray(mask) != 0, np.uint8)
+            if a.shape != (q.h, q.w):
+                raise ValueError(f"count_centres: expected a mask of shape {(q.h, q.w)}, got {a.shape}")
+            mask = self.buffer(a)
+        try:
+            self._chk(_lib.gs4d_count_centres(self._h, int(data), int(n), C.byref(q), int(mask or 0), int(stats)))
+        finally:
+            if own:
+                self.delete(mask)
+
+    def select_volume(self, n, data, src=None, stride=96, **query):
+        """The records of the n of `data` whose centre passes the query (count_centres into a zeroed table, then compact_records with
+        min_pixels=1), in exact-size new buffers and in their original order: the analogue of select for records that ARE somewhere.  Returns
+        (dst, kept_index, kept, stats), as select does.  src: the buffer whose `stride`-byte records are copied (usually `data` itself); None:
+        no records are copied (dst is None).  mask= goes to count_centres.  Blocking, as prune is: it reads the count back."""
+        stats = self.record_stats(n)
+        self.count_centres(stats, n, data, **query)
         if src is not None:
             return self.prune(stats, n, src, stride=stride, min_pixels=1) + (stats,)
         count = self.compact_records(stats, n, stride=stride, min_pixels=1)

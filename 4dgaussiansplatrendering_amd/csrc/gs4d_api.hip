@@ -1912,6 +1912,44 @@ int gs4d_count_ids(gs4d_ctx* c, const gs4d_id_region* region, gs4d_buf mask, gs4
         });
 }
 
+// ---- selection by where a record is: a statistics table from a volume or a screen region ----
+int gs4d_count_centres(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_centre_query* query, gs4d_buf mask, gs4d_buf stats) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("count_centres: ") + msg).c_str()); };
+    if (!query) return bad("query == NULL");
+    const gs4d_centre_query q = *query;
+    constexpr uint32_t known = GS4D_CQ_BOX | GS4D_CQ_SPHERE | GS4D_CQ_SCREEN | GS4D_CQ_FRAME | GS4D_CQ_SKIP_HIDDEN | GS4D_CQ_SKIP_DEAD;
+    if ((q.tests & ~known) != 0u) return bad("unknown test bit");
+    if (q.op != (uint32_t)GS4D_CQ_ADD && q.op != (uint32_t)GS4D_CQ_REMOVE) return bad("unknown op");
+    if (q.reserved != 0u) return bad("non-zero reserved field in the query");
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    const bool screen = (q.tests & (uint32_t)GS4D_CQ_SCREEN) != 0u;
+    const gs4d_buf names[3] = { data, stats, mask };
+    Buffer* D = getbuf(c, data); Buffer* S = getbuf(c, stats); Buffer* M = getbuf(c, mask);
+    if (!D || !S || (mask != 0 && !M)) return bad("bad buffer name");
+    if (check_record_names(c, names, 3)) return bad("data, stats and mask must be different buffers");
+    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
+    if (S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (M && !screen) return bad("a mask is given without GS4D_CQ_SCREEN");
+    if (screen && (q.x < 0 || q.y < 0 || q.w <= 0 || q.h <= 0 || q.w > c->W - q.x || q.h > c->H - q.y)) return bad("the rectangle is empty or not inside the image");
+    if (M && M->bytes < (size_t)q.w * (size_t)q.h) return bad("the mask holds fewer than w*h bytes");
+    if (n == 0) return GS4D_OK;
+    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
+    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    // stats as an "out" of queue_on_lane, as in gs4d_count_ids: a read-modify-write the lane has the table to itself for.  data and mask are read.
+    // Where the fields are read: a shadow of data that is current holds the bits of the records in dense planes (k_soa_repack) — decided once the
+    // pending draws are settled (a re-run may rebuild the shadow) and before any buffer state is touched.  The call reads: it never builds a shadow,
+    // and a reader leaves `version` alone, so a current shadow stays current.
+    bool shadow = false;
+    return queue_on_lane(c, { D, M }, { S },
+        [&](Lane&) { shadow = D->soa && D->soa_n == D->bytes / 96 && D->soa_version == D->version; return (int)GS4D_OK; },
+        [&](Lane& L) {
+            HIPCHK(c, launch_count_centres(L.s, D->d, shadow ? D->soa : nullptr, D->soa_n, D->soa_info, n, q, c->W, c->H, M ? (const uint8_t*)M->d : nullptr, (gs4d_record_stat*)S->d));
+            return (int)GS4D_OK;
+        });
+}
+
 int gs4d_read_pixels_rgba8_device(gs4d_ctx* c, void* dptr, size_t bytes) {
     if (!c || !dptr) return GS4D_E_INVALID;
     int rc = read_begin(c, bytes == (size_t)c->W * c->H * 4, "read_pixels_rgba8_device: bytes != width*height*4"); if (rc) return rc;

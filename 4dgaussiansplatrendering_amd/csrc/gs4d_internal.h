@@ -475,4 +475,13 @@ hipError_t launch_stat_cut(hipStream_t st, const gs4d_record_stat* stats, size_t
 // bytes, or null: none.  No row >= nrecords is touched and nothing outside the rectangle is read.
 hipError_t launch_count_ids(hipStream_t st, const uint32_t* ids, int W, int H, const gs4d_id_region& g, const uint8_t* mask, gs4d_record_stat* stats, uint32_t nrecords);
 
+// ---- centres.hip ----
+// gs4d_count_centres (gs4d.h): row i < n of stats gets one fragment of weight 1 (GS4D_CQ_ADD) or becomes {0, 0, 0} (GS4D_CQ_REMOVE) iff
+// record i takes part in q (validated; W, H: the context's image) — one launch on `st`, one workgroup per CENTRES_TILE records.  The fields come from
+// the 96-byte records, or — soa != null: the records' SoA shadow, which is current, its planes soa_n float4 apart, its layout info — from the shadow's
+// planes, which hold the same bits.  mask: q.w * q.h bytes, or null: none.  Rows of records that do not take part are neither read nor written.
+constexpr uint32_t CENTRES_TILE = 256;
+hipError_t launch_count_centres(hipStream_t st, const void* records, const float4* soa, size_t soa_n, const SoaInfo& info, size_t n, const gs4d_centre_query& q,
+                                int W, int H, const uint8_t* mask, gs4d_record_stat* stats);
+
 } // namespace gs4d

@@ -21,6 +21,7 @@
 #include <sstream>
 #include <string>
 #include <vector>
+#include "../csrc/centre_query.h"
 
 namespace {
 
@@ -459,6 +460,25 @@ void gs4d_host_edit_colours(size_t n, float* rec, const gs4d_record_stat* stats,
                 default: std::memcpy(c, from + 24 * i + 4 + ch, 4); break;
             }
         }
+    }
+}
+
+// The definition of gs4d_count_centres (gs4d.h), in place on the table: whether record i takes part is the text of csrc/centre_query.h, which the
+// kernel compiles too (this file is built with -ffp-contract=off); then the row.  A query the device call would refuse changes nothing.
+void gs4d_host_count_centres(size_t n, const float* rec, const gs4d_centre_query* q, int width, int height, const uint8_t* mask, gs4d_record_stat* stats) {
+    const uint32_t known = GS4D_CQ_BOX | GS4D_CQ_SPHERE | GS4D_CQ_SCREEN | GS4D_CQ_FRAME | GS4D_CQ_SKIP_HIDDEN | GS4D_CQ_SKIP_DEAD;
+    if (!q || (q->tests & ~known) != 0u || q->op > (uint32_t)GS4D_CQ_REMOVE || q->reserved != 0u) return;
+    const bool screen = (q->tests & (uint32_t)GS4D_CQ_SCREEN) != 0u;
+    if (mask && !screen) return;
+    if (screen && (q->x < 0 || q->y < 0 || q->w <= 0 || q->h <= 0 || q->w > width - q->x || q->h > height - q->y)) return;
+    const float hw = (float)width * 0.5f, hh = (float)height * 0.5f;
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = rec + 24 * i;
+        const gs4d_centre::Fields r{ { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] };
+        if (!gs4d_centre::takes_part(*q, hw, hh, r, mask)) continue;
+        gs4d_record_stat& s = stats[i];
+        if (q->op == (uint32_t)GS4D_CQ_ADD) { s.pixels += 1u; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += 1ull << 24; }
+        else s = gs4d_record_stat{ 0u, 0u, 0ull };
     }
 }
 

@@ -646,6 +646,79 @@ GS4D_API int gs4d_edit_colours(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4
                                gs4d_buf stats /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff stats == 0 */,
                                gs4d_buf from /* GS4D_EDIT_COPY: the source records; otherwise 0 */);
 
+/* ---- selection by where a record IS: a statistics table from a volume or a screen region (no reference counterpart) ----
+ * The second way into the selection chain.  gs4d_count_ids selects what a region of the ID planes SHOWS, one record per pixel; gs4d_count_centres
+ * selects the records whose centre at time t lies in a box or a sphere of the world and / or projects into a rectangle (a lasso) of the screen —
+ * visible or not, through every occluder — and writes the answer where gs4d_compact_records, gs4d_stat_cut and gs4d_edit_colours take it from: a
+ * gs4d_record_stat table.  gs4d_host_count_centres is this text as code.
+ *
+ * All arithmetic is float32, round to nearest, no contraction: every product and every sum is rounded on its own, in the order the parentheses
+ * give; division is correctly rounded; the two fmaf below are real fused operations.  For record i < n of the 96-byte records in data, with
+ * p = floats 0..2, mu_t = float 3, a = float 7, sig3 = floats 20..22, s44 = float 23:
+ *
+ * Centre (that of gs4d_shade_sh and GS4D_KEY_VIEW_Z).
+ *     dt = t - mu_t;   k = (1.0f / s44) * dt;   m = p + (k * sig3)   per component.
+ * The draws take floats 11, 15 and 19 in the place of sig3.  A symmetric covariance holds those bit-equal to sig3, and for such records m is the
+ * centre the draws project.
+ *
+ * Skips.  GS4D_CQ_SKIP_HIDDEN skips a record iff !(a > 0): the time-span table's "never", and what hiding with gs4d_edit_colours produces.
+ * GS4D_CQ_SKIP_DEAD skips a record iff ((-0.5f * dt) * (1.0f / s44)) * dt < GS4D_TIME_DEAD_ARG; a NaN is not skipped.
+ *
+ * Volume.  q = m; with GS4D_CQ_FRAME, f = frame: q[r] = (((f[r] * m.x) + (f[3 + r] * m.y)) + (f[6 + r] * m.z)) + f[9 + r].
+ *     GS4D_CQ_BOX     passes iff box_lo[a] <= q[a] && q[a] <= box_hi[a] for a = 0, 1, 2;
+ *     GS4D_CQ_SPHERE  with d = q - (sphere[0..2]) and r = sphere[3]: passes iff ((d.x * d.x) + (d.y * d.y)) + (d.z * d.z) <= r * r.
+ * A NaN anywhere fails the test it is in.  GS4D_CQ_FRAME without BOX or SPHERE is allowed and has no effect.
+ *
+ * Screen (GS4D_CQ_SCREEN).  The draws' own expressions for the centre, with W x H the context's image:
+ *     pc = view * (m, 1);   ps = proj * pc          ((a + b) + c) + d per row, column-major, the `* 1.0f` of the last product of pc included
+ *     rw = 1.0f / ps.w;   nx = rw * ps.x;   ny = rw * ps.y
+ *     hw = W * 0.5f;   hh = H * 0.5f;   wx = fmaf(nx, hw, hw);   wy = fmaf(ny, hh, hh)
+ * It passes iff  ps.w > 0  &&  depth_min <= -pc.z && -pc.z <= depth_max  &&  wx >= (float)x && wx < (float)(x + w)  &&  wy >= (float)y &&
+ * wy < (float)(y + h)  &&  (mask == 0 || mask[(floorf(wy) - y) * w + (floorf(wx) - x)] != 0).  The mask byte is looked at only once the comparisons
+ * have passed, so the index is inside the mask.  The mask is a gs4d_count_ids mask — w * h bytes, rows bottom-up, any non-zero byte counts — and
+ * one uploaded lasso serves both calls.  The draws' clip tests are NOT applied: a centre the draws would clip is selected if it passes the above.
+ *
+ * Taking part.  Record i takes part iff it is not skipped and every enabled test passes; with no test bit set, every record that is not skipped.
+ *
+ * The row.  GS4D_CQ_ADD adds to row i of stats what one fragment of weight 1 adds in a draw: pixels += 1; wmax = max(wmax, 0x3F800000);
+ * wsum += 1 << 24.  GS4D_CQ_REMOVE sets row i to {0, 0, 0}.  Rows of records that do not take part keep their bits; no byte beyond row n - 1, no
+ * byte of data and no byte of mask is written; nothing depends on the order in which anything runs.  On a zeroed table each ADD call adds at most
+ * one to pixels: after k calls the rule {1, 0, 0, 0} gives their union, {k, 0, 0, 0} their intersection, and REMOVE subtracts.  Rows also add on
+ * top of what draws and gs4d_count_ids put there.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: query == NULL; an unknown test bit or op; reserved != 0; n > 0xFFFFFFFF; data or stats
+ * not a live buffer; data smaller than 96 n bytes; stats smaller than 16 n bytes; mask neither 0 nor a live buffer; mask given without
+ * GS4D_CQ_SCREEN; mask smaller than w * h bytes; with GS4D_CQ_SCREEN a rectangle that is empty or not inside the image; any two of the three
+ * buffers being the same buffer.  n == 0 with otherwise valid arguments is a no-op.  Box ends, sphere, frame, matrices, t and the depth range are
+ * data, not errors: hostile values select what the lines above say they select.
+ *
+ * Ordering.  stats is handled exactly as in gs4d_count_ids: draws that add to it (gs4d_set_record_stats), issued before the call on any frame
+ * lane, are settled first, re-runs included; the call is a kernel write that keeps the contents, and later draws, other lanes and the host order
+ * themselves behind it.  data and mask are buffers the call reads (gs4d_record_time_spans' data, gs4d_count_ids' mask): a later write of either
+ * waits for the kernel.  A queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first.  The kernel is queued on the
+ * current frame lane; the call returns at once and starts no frame; it needs no frame and no outputs mode.  gs4d_buffer_invalidate hand-offs of
+ * all three buffers are honoured.  If the SoA shadow of data is current the kernel reads the shadow's planes, which hold the same bits, instead of
+ * the records; the call never builds or invalidates a shadow (gs4d_debug_shadow_builds does not move).
+ *
+ * Out of scope: per-pixel footprint selection (records whose quad merely touches the region); brush strokes as anything but a mask; 72-byte quad
+ * vertices and 48-byte 2D records; more than one volume per call; a tie-break of the centre using floats 11, 15 and 19. */
+enum { GS4D_CQ_BOX = 1, GS4D_CQ_SPHERE = 2, GS4D_CQ_SCREEN = 4, GS4D_CQ_FRAME = 8, GS4D_CQ_SKIP_HIDDEN = 16, GS4D_CQ_SKIP_DEAD = 32 };
+enum { GS4D_CQ_ADD = 0, GS4D_CQ_REMOVE = 1 };
+typedef struct gs4d_centre_query {
+    uint32_t tests;        /* OR of GS4D_CQ_*; any other bit: GS4D_E_INVALID            */
+    uint32_t op;           /* GS4D_CQ_ADD or GS4D_CQ_REMOVE                             */
+    float    t;            /* the time the centre is taken at                           */
+    uint32_t reserved;     /* must be 0                                                 */
+    float    frame[12];    /* GS4D_CQ_FRAME: 3x4, column-major, world -> the volume's frame */
+    float    box_lo[3], box_hi[3];
+    float    sphere[4];    /* centre x y z, radius                                      */
+    float    view[16], proj[16];   /* GS4D_CQ_SCREEN: as gs4d_set_uniform_mat4 takes them */
+    int32_t  x, y, w, h;   /* GS4D_CQ_SCREEN: rectangle inside the image, row 0 = bottom, as gs4d_count_ids */
+    float    depth_min, depth_max; /* GS4D_CQ_SCREEN: -z_view of the centre, the unit of the aux outputs */
+} gs4d_centre_query;       /* 256 bytes */
+GS4D_API int gs4d_count_centres(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_centre_query* query,
+                                gs4d_buf mask /* 0: none; GS4D_CQ_SCREEN only */, gs4d_buf stats);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -699,6 +772,11 @@ GS4D_API void gs4d_host_transform_records(size_t n, const float* records24, cons
  * would refuse (an unknown op, channels outside 1 .. 15) edits nothing. */
 GS4D_API void gs4d_host_edit_colours(size_t n, float* records24, const gs4d_record_stat* stats, const gs4d_keep_rule* rule,
                                      const gs4d_colour_edit* edit, const float* from24);
+/* The definition of gs4d_count_centres, in place on the n rows of stats (the text above its declaration), for a context whose image is width x
+ * height; mask is read with GS4D_CQ_SCREEN only.  A query the device call would refuse (NULL, an unknown test bit or op, reserved != 0, a mask
+ * without GS4D_CQ_SCREEN, with GS4D_CQ_SCREEN a rectangle that is empty or not inside the image) changes nothing. */
+GS4D_API void gs4d_host_count_centres(size_t n, const float* records24, const gs4d_centre_query* query, int width, int height,
+                                      const uint8_t* mask /* may be NULL */, gs4d_record_stat* stats);
 /* One row of gs4d_transform_records' table: the upper 3x3 of L is scale * R(q) with the R of gs4d_host_splat3d_cov (the matrix of the quaternion as
  * given, not normalised), each element one product; column 3, rows 0..2 = velocity (a source at time t lands velocity * t further on);
  * L[3, 3] = time_scale and the time row is otherwise 0; o = (translate, time_offset).  A source time t shows at time_scale * t + time_offset. */
