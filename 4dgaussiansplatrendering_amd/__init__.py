@@ -28,6 +28,7 @@ PARAMS_3D, PARAMS_4D_VEL, PARAMS_4D_2Q = 0, 1, 2           # gs4d_splat_params.f
 EDIT_SET, EDIT_MUL, EDIT_LERP, EDIT_COPY = 0, 1, 2, 3      # gs4d_colour_edit.op
 CQ_BOX, CQ_SPHERE, CQ_SCREEN, CQ_FRAME, CQ_SKIP_HIDDEN, CQ_SKIP_DEAD = 1, 2, 4, 8, 16, 32      # gs4d_centre_query.tests
 CQ_ADD, CQ_REMOVE = 0, 1                                   # gs4d_centre_query.op
+MS_SKIP_HIDDEN, MS_SKIP_DEAD = 1, 2                        # gs4d_measure_query.flags
 TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
@@ -99,6 +100,7 @@ def _load():
         "gs4d_shade_sh": (i32, [vp, u32, sz, u32, sz, i32, f32, vp]),
         "gs4d_edit_colours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_count_centres": (i32, [vp, u32, sz, vp, u32, u32]),
+        "gs4d_measure_records": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_build_records": (i32, [vp, vp, sz, u32]),
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_set_profiling": (i32, [vp, i32]),
@@ -126,6 +128,9 @@ def _load():
         "gs4d_host_transform_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_edit_colours": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_count_centres": (None, [sz, vp, vp, i32, i32, vp, vp]),
+        "gs4d_host_measure_records": (None, [sz, vp, vp, vp, vp, vp]),
+        "gs4d_host_measure_centre": (i32, [vp, vp]),
+        "gs4d_host_frame_box": (None, [vp, vp, vp, f32, i32, i32, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
         "gs4d_host_scene_nonlinear": (None, [sz, vp, i32, f32, f32, f32, vp, f32, f32, f32, sz, vp]),
@@ -504,6 +509,61 @@ def count_centres_host(records, query, width, height, mask=None, stats=None):
             raise ValueError(f"count_centres_host: expected a mask of shape {(query.h, query.w)}, got {m.shape}")
     _lib.gs4d_host_count_centres(n, _ptr(rec), C.byref(query), int(width), int(height), _ptr(m) if m is not None else None, _ptr(st))
     return st
+
+
+class MeasureQuery(C.Structure):
+    """gs4d_measure_query (include/gs4d.h): the time and the skips of a gs4d_measure_records call."""
+    _fields_ = [("t", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class Measure(C.Structure):
+    """gs4d_measure (include/gs4d.h): the 96 bytes a gs4d_measure_records call writes."""
+    _fields_ = [("count", C.c_uint32), ("unplaced", C.c_uint32), ("skipped", C.c_uint32), ("reserved0", C.c_uint32),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("ext_lo", C.c_float * 3), ("ext_hi", C.c_float * 3),
+                ("cell_sum", C.c_uint64 * 3), ("reserved1", C.c_uint64)]
+
+    def as_dict(self):
+        """count, unplaced, skipped, lo, hi, ext_lo, ext_hi (float32 [3]), cell_sum (uint64 [3]) and centre (gs4d_host_measure_centre: float32
+        [3], or None when nothing was measured)"""
+        centre = np.zeros(3, np.float32)
+        has = _lib.gs4d_host_measure_centre(C.byref(self), _ptr(centre))
+        out = {k: int(getattr(self, k)) for k in ("count", "unplaced", "skipped")}
+        out.update({k: np.array(getattr(self, k)[:], np.float32) for k in ("lo", "hi", "ext_lo", "ext_hi")})
+        out["cell_sum"] = np.array(self.cell_sum[:], np.uint64)
+        out["centre"] = centre if has else None
+        return out
+
+
+def measure_query(t=0.0, skip_hidden=False, skip_dead=False):
+    """one gs4d_measure_query (MeasureQuery)"""
+    q = MeasureQuery()
+    q.t, q.flags = float(t), (MS_SKIP_HIDDEN if skip_hidden else 0) | (MS_SKIP_DEAD if skip_dead else 0)
+    return q
+
+
+def measure_records_host(records, t=0.0, stats=None, skip_hidden=False, skip_dead=False, query=None, **rule):
+    """gs4d_host_measure_records, the definition of Context.measure_records: the Measure of records [n, 24] at time t.  stats: a RECORD_STAT array
+    of n rows (the rule keywords of compact_records select by it) or None: every record; query: a MeasureQuery instead of t and the skips."""
+    rec = _f32(records).reshape(-1, 24)
+    n = rec.shape[0]
+    if stats is None and rule:
+        raise TypeError("measure_records_host: a rule without stats")
+    st = None if stats is None else np.ascontiguousarray(stats)
+    if st is not None and (st.dtype.itemsize != 16 or st.ndim != 1 or st.shape[0] < n):
+        raise ValueError("measure_records_host: stats must be at least n rows of 16 bytes")
+    q = measure_query(t, skip_hidden, skip_dead) if query is None else query
+    k = _keep_rule(**rule)
+    out = Measure()
+    _lib.gs4d_host_measure_records(n, _ptr(rec), C.byref(q), _ptr(st) if st is not None else None, _ptr(k) if st is not None else None, C.byref(out))
+    return out
+
+
+def frame_box(lo, hi, orientation, fov_deg, width, height):
+    """gs4d_host_frame_box: the eye from which look_at(eye, orientation) and perspective(fov_deg, width, height, ..) show the whole box lo .. hi,
+    its centre in the middle of the image ("frame selection": lo, hi of a Measure)."""
+    out = np.zeros(3, np.float32)
+    _lib.gs4d_host_frame_box(_ptr(_f32(lo)), _ptr(_f32(hi)), _ptr(_f32(orientation)), fov_deg, int(width), int(height), _ptr(out))
+    return out
 
 
 class SplatParams(C.Structure):
@@ -972,6 +1032,28 @@ class Context:
         self.compact_records(stats, n, stride=stride, kept_index=kept_index, count=count, min_pixels=1)
         self.delete(count)
         return None, kept_index, kept, stats
+
+    # where a selection is: bounds and centroid of selected records
+    def measure_records(self, data, n, t=0.0, stats=None, skip_hidden=False, skip_dead=False, out=None, query=None, **rule):
+        """gs4d_measure_records: how many of the selected ones of the first n 96-byte records of `data` have a finite centre at time t, the box of
+        those centres, the box of centre -/+ reach and the cell sums of the centroid, as one 96-byte Measure into `out` (a new buffer if None).
+        stats: a record_stats buffer whose row i selects record i by compact_records' rule keywords (None: every record, and no rule);
+        skip_hidden / skip_dead: leave out records of alpha <= 0 / dead at t (they are counted in `skipped`); query: a MeasureQuery instead of
+        t and the skips.  With the bits of measure_records_host.  Asynchronous; returns `out`."""
+        if stats is None and rule:
+            raise TypeError("measure_records: a rule without stats")
+        q = measure_query(t, skip_hidden, skip_dead) if query is None else query
+        k = _keep_rule(**rule) if stats is not None else None
+        if out is None:
+            out = self.buffer(nbytes=C.sizeof(Measure))
+        self._chk(_lib.gs4d_measure_records(self._h, int(data), int(n), C.byref(q), int(stats or 0), _ptr(k) if k is not None else None, int(out)))
+        return out
+
+    def read_measure(self, out):
+        """The Measure of a measure_records call as a dict (Measure.as_dict: count, unplaced, skipped, lo, hi, ext_lo, ext_hi, cell_sum,
+        centre); blocks until its kernels have finished."""
+        raw = self.read(out, np.uint8, C.sizeof(Measure))
+        return Measure.from_buffer_copy(raw.tobytes()).as_dict()
 
     # time windows: the records of a 4D set that can show anything between two times (DESIGN.md §4)
     TIME_SPAN = np.dtype([("t_first", "<f4"), ("t_last", "<f4")])

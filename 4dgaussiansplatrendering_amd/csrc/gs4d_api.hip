@@ -136,6 +136,7 @@ struct Lane {
     uint32_t* compact_counts = nullptr; size_t compact_cap = 0;   // gs4d_compact_records: one word per tile of COMPACT_TILE records (counts, then first slots); the lane's stream orders its reuse
     uint32_t* spatial_scratch = nullptr; size_t spatial_cap = 0;      // gs4d_spatial_order: the box and its partials (order_box_words()), then one key per record; the lane's stream orders its reuse
     uint32_t* cut_scratch = nullptr; size_t cut_cap = 0;               // gs4d_stat_cut: the state block and one partial histogram per workgroup (cut_scratch_words()); the lane's stream orders its reuse
+    uint32_t* measure_scratch = nullptr; size_t measure_cap = 0;       // gs4d_measure_records: one partial row per workgroup (measure_scratch_words()); the lane's stream orders its reuse
     uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
     uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
     gs4d_buf kg_buf = 0; uint64_t kg_ver = 0;         // key buffer whose digit histograms k_keygen left for the next sort
@@ -1007,6 +1008,7 @@ void gs4d_destroy(gs4d_ctx* c) {
         if (L.compact_counts) (void)hipFree(L.compact_counts);
         if (L.spatial_scratch) (void)hipFree(L.spatial_scratch);
         if (L.cut_scratch) (void)hipFree(L.cut_scratch);
+        if (L.measure_scratch) (void)hipFree(L.measure_scratch);
         for (auto& sp : L.spare) { if (sp.d) (void)hipFree(sp.d); for (hipEvent_t e : sp.ev) if (e) (void)hipEventDestroy(e); }
         if (L.proj) (void)hipFree(L.proj);
         if (L.trects) (void)hipFree(L.trects);
@@ -1947,6 +1949,43 @@ int gs4d_count_centres(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_centre_q
         [&](Lane& L) {
             HIPCHK(c, launch_count_centres(L.s, D->d, shadow ? D->soa : nullptr, D->soa_n, D->soa_info, n, q, c->W, c->H, M ? (const uint8_t*)M->d : nullptr, (gs4d_record_stat*)S->d));
             return (int)GS4D_OK;
+        });
+}
+
+// ---- where a selection is: bounds and centroid of selected records ----
+int gs4d_measure_records(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_measure_query* query, gs4d_buf stats, const gs4d_keep_rule* rule, gs4d_buf out) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("measure_records: ") + msg).c_str()); };
+    if (!query) return bad("query == NULL");
+    const gs4d_measure_query q = *query;
+    if ((q.flags & ~(uint32_t)(GS4D_MS_SKIP_HIDDEN | GS4D_MS_SKIP_DEAD)) != 0u) return bad("unknown flag");
+    if (q.reserved[0] != 0u || q.reserved[1] != 0u) return bad("non-zero reserved field in the query");
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    if ((stats != 0) != (rule != nullptr)) return bad("stats and rule are given together or not at all");
+    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
+    const gs4d_buf names[3] = { data, out, stats };
+    Buffer* D = getbuf(c, data); Buffer* O = getbuf(c, out);
+    if (!D || !O) return bad("data and out must name live buffers");
+    if (const int wrong = check_record_names(c, names, 3)) return bad(wrong == 1 ? "bad buffer name" : "data, stats and out must be different buffers");
+    Buffer* S = getbuf(c, stats);
+    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
+    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (O->bytes < sizeof(gs4d_measure)) return bad("out holds fewer than 96 bytes");
+    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
+    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
+    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    // data and the table are read (gs4d_count_centres' data, gs4d_edit_colours' table), out is written whole (gs4d_stat_cut's out).  The kernels read
+    // the 96-byte records, never a shadow, and a reader leaves `version` alone: a current shadow stays current and none is built.
+    return queue_on_lane(c, { D, S }, { O },
+        [&](Lane& L) {
+            HIPCHK(c, grow_device_array(L.s, L.measure_scratch, L.measure_cap, measure_scratch_words()));
+            return S ? scan_reserve(c, *S) : (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            if (S) { int rc = scan_begin(c, L, *S); if (rc) return rc; }
+            HIPCHK(c, launch_measure_records(L.s, D->d, n, q.t, q.flags, S ? (const gs4d_record_stat*)S->d : nullptr, k, L.measure_scratch, (gs4d_measure*)O->d));
+            return S ? scan_end(c, L, *S) : (int)GS4D_OK;
         });
 }
 

@@ -484,4 +484,17 @@ constexpr uint32_t CENTRES_TILE = 256;
 hipError_t launch_count_centres(hipStream_t st, const void* records, const float4* soa, size_t soa_n, const SoaInfo& info, size_t n, const gs4d_centre_query& q,
                                 int W, int H, const uint8_t* mask, gs4d_record_stat* stats);
 
+// ---- measure.hip ----
+// gs4d_measure_records (gs4d.h): *out <- the measurement at time t, under the GS4D_MS_* flags (validated), of the selected ones of the
+// first n 96-byte records — stats: the table whose row i selects record i by `rule` (keep_row), or null: every record.  Three launches on `st`, no
+// workgroup waits for another; n == 0: the empty measurement, one launch.  Nothing but the 96 bytes of out and the scratch is written.
+constexpr uint32_t MEASURE_THREADS = 256;        // threads of a workgroup of every kernel of the call
+constexpr uint32_t MEASURE_GROUPS = 1024;        // workgroups of the two walking kernels at most (a grid stride beyond): one partial row each
+constexpr uint32_t MEASURE_ROW_WORDS = 16;       // a partial row: the first 64 bytes of a gs4d_measure, the floats as their keys (measure_record.h)
+inline uint32_t measure_groups(size_t n) { const size_t g = (n + MEASURE_THREADS - 1) / MEASURE_THREADS; return g < MEASURE_GROUPS ? (uint32_t)g : MEASURE_GROUPS; }
+// scratch: measure_scratch_words() words (the lane's): the partial rows, sized by the grid cap
+inline size_t measure_scratch_words() { return (size_t)MEASURE_GROUPS * MEASURE_ROW_WORDS; }
+hipError_t launch_measure_records(hipStream_t st, const void* records, size_t n, float t, uint32_t flags, const gs4d_record_stat* stats, const KeepRule& rule,
+                                  uint32_t* scratch, gs4d_measure* out);
+
 } // namespace gs4d

@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 #include "../csrc/centre_query.h"
+#include "../csrc/measure_record.h"
 
 namespace {
 
@@ -480,6 +481,67 @@ void gs4d_host_count_centres(size_t n, const float* rec, const gs4d_centre_query
         if (q->op == (uint32_t)GS4D_CQ_ADD) { s.pixels += 1u; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += 1ull << 24; }
         else s = gs4d_record_stat{ 0u, 0u, 0ull };
     }
+}
+
+// The definition of gs4d_measure_records (gs4d.h): what a selected record adds is the text of csrc/measure_record.h, which the kernels compile too
+// (this file is built with -ffp-contract=off) — one pass for the counts and the keyed extrema, one for the cells once the box is known.  A query the
+// device call would refuse gives the empty measurement.
+void gs4d_host_measure_records(size_t n, const float* rec, const gs4d_measure_query* q, const gs4d_record_stat* stats, const gs4d_keep_rule* rule, gs4d_measure* out) {
+    namespace ms = gs4d_measure_rec;
+    uint32_t row[ms::ROW_WORDS];
+    for (int w = 0; w < ms::ROW_WORDS; ++w) row[w] = ms::row_empty(w);
+    const uint32_t known = GS4D_MS_SKIP_HIDDEN | GS4D_MS_SKIP_DEAD;
+    const bool valid = q && (q->flags & ~known) == 0u && q->reserved[0] == 0u && q->reserved[1] == 0u && !(stats && !rule);
+    const bool invert = valid && stats && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    auto selected = [&](size_t i) {
+        if (!stats) return true;
+        const gs4d_record_stat& s = stats[i];
+        return (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert;
+    };
+    auto fields = [&](size_t i) {
+        const float* p = rec + 24 * i;
+        return ms::Fields{ { { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] }, { p[8], p[13], p[18] } };
+    };
+    if (valid) for (size_t i = 0; i < n; ++i) if (selected(i)) ms::add_record(q->t, q->flags, fields(i), row);
+    uint32_t words[ms::ROW_WORDS];
+    for (int w = 0; w < ms::ROW_WORDS; ++w) words[w] = ms::row_word(w, row[w]);
+    std::memset(out, 0, sizeof *out);
+    std::memcpy(out, words, sizeof words);
+    if (!valid || out->count == 0u) return;
+    for (size_t i = 0; i < n; ++i) {
+        if (!selected(i)) continue;
+        float m[3];
+        if (ms::place(q->t, q->flags, fields(i).c, m) != ms::MEASURED) continue;
+        for (int a = 0; a < 3; ++a) out->cell_sum[a] += ms::cell(m[a], out->lo[a], out->hi[a]);
+    }
+}
+
+int gs4d_host_measure_centre(const gs4d_measure* m, float centre3[3]) {
+    centre3[0] = centre3[1] = centre3[2] = 0.0f;
+    if (!m || m->count == 0u) return 0;
+    for (int a = 0; a < 3; ++a) {
+        const double lo = m->lo[a], hi = m->hi[a];
+        centre3[a] = (float)(lo + (hi - lo) * ((double)m->cell_sum[a] / ((double)m->count * 1048576.0)));
+    }
+    return 1;
+}
+
+// "Frame selection" (gs4d.h): the bounding sphere of the box inside the narrower half-angle of gs4d_host_perspective's frustum — th is that
+// function's own float tangent, aspect its own float quotient — seen along `orientation`.  In double.
+void gs4d_host_frame_box(const float lo[3], const float hi[3], const float orientation[3], float fov_deg, int width, int height, float eye3[3]) {
+    const float fovy = fov_deg * 0.01745329251994329576923690768489f;
+    const double th = std::tan(fovy / 2.0f), aspect = (float)width / (float)height;
+    const double half = std::atan(std::min(th, aspect * th));
+    double c[3], r2 = 0.0, o2 = 0.0;
+    for (int a = 0; a < 3; ++a) {
+        c[a] = 0.5 * ((double)lo[a] + (double)hi[a]);
+        const double h = 0.5 * ((double)hi[a] - (double)lo[a]);
+        r2 += h * h; o2 += (double)orientation[a] * (double)orientation[a];
+    }
+    double radius = std::sqrt(r2);
+    if (!(radius > 0.0) || !std::isfinite(radius)) radius = 1.0;
+    const double back = radius / std::sin(half) / std::sqrt(o2);
+    for (int a = 0; a < 3; ++a) eye3[a] = (float)(c[a] - (double)orientation[a] * back);
 }
 
 void gs4d_host_affine4(const float q_wxyz[4], float scale, const float translate[3], const float velocity[3], float time_scale, float time_offset,

@@ -719,6 +719,87 @@ typedef struct gs4d_centre_query {
 GS4D_API int gs4d_count_centres(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_centre_query* query,
                                 gs4d_buf mask /* 0: none; GS4D_CQ_SCREEN only */, gs4d_buf stats);
 
+/* ---- where a selection is: bounds and centroid of selected records (no reference counterpart) ----
+ * gs4d_count_ids, gs4d_count_centres and record statistics say WHICH records; gs4d_compact_records, gs4d_stat_cut, gs4d_edit_colours and
+ * gs4d_transform_records act on them.  gs4d_measure_records says WHERE they are: how many, the box of their centres at time t, the box of what
+ * they reach, and the sums their centroid comes from — the pivot of a rotate or scale gizmo (gs4d_host_affine4 rotates about the origin), the
+ * camera's "frame selection" (gs4d_host_frame_box), the box drawn around a selection (gs4d_draw_lines), the box a follow-up gs4d_count_centres
+ * query grows from — as one 96-byte gs4d_measure in a buffer.  gs4d_host_measure_records is this text as code.
+ *
+ * All arithmetic is float32, round to nearest, no contraction: every product and every sum is rounded on its own, in the order the parentheses
+ * give; division and sqrtf are correctly rounded.  For record i < n of the 96-byte records in data, with p = floats 0..2, mu_t = float 3,
+ * a = float 7, S[0][0], S[1][1], S[2][2] = floats 8, 13, 18, sig3 = floats 20..22, s44 = float 23:
+ *
+ * Selected.  Exactly the predicate of gs4d_edit_colours: stats == 0 selects every record; otherwise record i is selected iff row i of the
+ * gs4d_record_stat table `stats` passes `rule`: (pixels >= min_pixels && wmax >= min_wmax && wsum >= min_wsum) != invert (GS4D_KEEP_INVERT).
+ * A record that is not selected adds nothing to any field.
+ *
+ * Centre and skips (the text of gs4d_count_centres).
+ *     dt = t - mu_t;   k = (1.0f / s44) * dt;   m = p + (k * sig3)   per component.
+ * GS4D_MS_SKIP_HIDDEN skips a record iff !(a > 0).  GS4D_MS_SKIP_DEAD skips a record iff ((-0.5f * dt) * (1.0f / s44)) * dt < GS4D_TIME_DEAD_ARG;
+ * a NaN is not skipped.  A selected record that is skipped adds 1 to `skipped` and nothing else.
+ *
+ * Placed.  A selected record that is not skipped is PLACED iff m[0], m[1] and m[2] are all finite.  One that is not placed adds 1 to `unplaced`
+ * and nothing else.  The others are the MEASURED records: `count` is their number.
+ *
+ * Box.  lo[a] / hi[a] are the minimum / maximum of m[a] over the measured records in the total order of the key
+ *     key(v) = bits(v) ^ (sign bit set ? 0xFFFFFFFF : 0x80000000)        compared as unsigned integers.
+ * Under that key -0 < +0, so the BITS of a box end do not depend on the order in which anything is evaluated (with fminf they would: it may
+ * return either zero).  count == 0: lo = {+inf}, hi = {-inf}.
+ *
+ * Reach.  Three standard deviations of the spatial variance conditioned on the time, per axis a:
+ *     var = S[a][a] - ((sig3[a] * sig3[a]) * (1.0f / s44));   r = var > 0 ? 3.0f * sqrtf(var) : 0.0f        (a NaN gives 0)
+ * m[a] - r enters ext_lo[a] and m[a] + r enters ext_hi[a], each only if it is finite, as a minimum / maximum under the same key order.  An axis
+ * without a finite end holds +inf / -inf.
+ *
+ * Cell (once the box is known).  For a measured record and axis a:
+ *     d = m[a] - lo[a];   e = hi[a] - lo[a];   g = (d / e) * 1048576.0f;   cell = g >= 0 ? (uint32) min(g, 1048576.0f) : 0
+ * — the form of gs4d_spatial_order: a NaN from e == 0 or an overflowed e gives cell 0.  cell_sum[a] is the 64-bit integer sum of cell over the
+ * measured records; it is below 2^52 and never overflows.
+ *
+ * Centre.  gs4d_host_measure_centre gives, in double precision, lo + (hi - lo) * (cell_sum / (count * 2^20)) per axis, rounded to float: the
+ * centroid of the measured centres to within (hi - lo) * 2^-19 (each cell truncates by at most 2^-20 of the extent, and the float32 quotient
+ * adds less than that again).  It is unweighted: every measured record counts once.
+ *
+ * Every field is a count, an integer sum or an extremum under a total order: the same inputs give the same 96 bytes, whatever runs first.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: query == NULL, an unknown flag, a non-zero reserved word; n > 0xFFFFFFFF; data or out
+ * not a live buffer; data smaller than 96 n bytes; out smaller than 96 bytes; exactly one of stats / rule given; a rule with an unknown flag or
+ * reserved != 0; stats not a live buffer or smaller than 16 n bytes; any two of the three buffers being the same buffer.  n == 0 with otherwise
+ * valid arguments writes the empty measurement (zeros, lo = ext_lo = {+inf}, hi = ext_hi = {-inf}).  t is data, not an error.
+ *
+ * What is written: bytes 0..95 of out (reserved0, reserved1 as 0), nothing else; data and stats are never written.
+ *
+ * Ordering.  data is read as gs4d_count_centres reads its data: a later write of it waits for the kernels.  stats is read as gs4d_edit_colours
+ * reads its table: draws that add to it (gs4d_set_record_stats), issued before the call on any frame lane, are settled first, re-runs included; a
+ * draw issued afterwards that adds to it waits on the device until the kernels have read it, and a host write waits as it does for any reader.
+ * out is an ordinary written buffer, as gs4d_stat_cut's out is.  A queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is
+ * launched first.  The kernels are queued on the current frame lane; the call returns at once and starts no frame.  gs4d_buffer_invalidate
+ * hand-offs of all three buffers are honoured.  The call never builds or invalidates a SoA shadow (gs4d_debug_shadow_builds does not move), and
+ * it does not read one either: it reads the 96-byte records even where a shadow of data is current, because the diagonal of S lies in different
+ * planes of each shadow layout — reading a shadow is out of scope here.
+ *
+ * Out of scope: weighted (alpha or wsum) centroids, second moments and oriented boxes; 72-byte quad vertices and 48-byte 2D records; building a
+ * gs4d_affine4 row on the device; transforming only the selected records in place (this call supplies that pivot). */
+enum { GS4D_MS_SKIP_HIDDEN = 1, GS4D_MS_SKIP_DEAD = 2 };
+typedef struct gs4d_measure_query {
+    float    t;            /* the time the centres are taken at      */
+    uint32_t flags;        /* OR of GS4D_MS_*; any other bit: GS4D_E_INVALID */
+    uint32_t reserved[2];  /* must be 0                              */
+} gs4d_measure_query;      /* 16 bytes */
+typedef struct gs4d_measure {
+    uint32_t count;        /* records measured: selected, not skipped, placed                                    */
+    uint32_t unplaced;     /* selected, not skipped, centre not finite                                           */
+    uint32_t skipped;      /* selected, left out by a GS4D_MS_SKIP_* flag                                        */
+    uint32_t reserved0;    /* written as 0                                                                       */
+    float    lo[3], hi[3];         /* box of the centres; count == 0: {+inf}, {-inf}                             */
+    float    ext_lo[3], ext_hi[3]; /* box of centre -/+ reach; no finite end on an axis: +inf / -inf             */
+    uint64_t cell_sum[3];  /* sum over the measured records of cell[a], units of 2^-20 of (hi[a] - lo[a])        */
+    uint64_t reserved1;    /* written as 0                                                                       */
+} gs4d_measure;            /* 96 bytes */
+GS4D_API int gs4d_measure_records(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_measure_query* query,
+                                  gs4d_buf stats /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff stats == 0 */, gs4d_buf out);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -777,6 +858,19 @@ GS4D_API void gs4d_host_edit_colours(size_t n, float* records24, const gs4d_reco
  * without GS4D_CQ_SCREEN, with GS4D_CQ_SCREEN a rectangle that is empty or not inside the image) changes nothing. */
 GS4D_API void gs4d_host_count_centres(size_t n, const float* records24, const gs4d_centre_query* query, int width, int height,
                                       const uint8_t* mask /* may be NULL */, gs4d_record_stat* stats);
+/* The definition of gs4d_measure_records (the text above its declaration): *out <- the measurement of the n records of records24.  stats == NULL
+ * selects every record (rule is then ignored), else rule is not NULL.  A query the device call would refuse (NULL, an unknown flag, a non-zero
+ * reserved word) gives the empty measurement. */
+GS4D_API void gs4d_host_measure_records(size_t n, const float* records24, const gs4d_measure_query* query, const gs4d_record_stat* stats,
+                                        const gs4d_keep_rule* rule, gs4d_measure* out);
+/* The centroid of a measurement: lo + (hi - lo) * (cell_sum / (count * 2^20)) per axis, in double precision, rounded to float.  Returns 1, or 0
+ * with centre3 = {0, 0, 0} when count == 0. */
+GS4D_API int  gs4d_host_measure_centre(const gs4d_measure* m, float centre3[3]);
+/* "Frame selection": the eye from which a camera of gs4d_host_look_at(eye, orientation, up) and gs4d_host_perspective(fov_deg, width, height, ..)
+ * sees the whole box lo .. hi with its centre in the middle of the image.  The box's bounding sphere (centre (lo + hi) / 2, radius half the
+ * diagonal; a degenerate box — a radius that is zero or not finite — gets radius 1) is fitted into the narrower of the projection's two
+ * half-angles: eye = centre - normalize(orientation) * radius / sin(half_angle).  In double precision, rounded to float. */
+GS4D_API void gs4d_host_frame_box(const float lo[3], const float hi[3], const float orientation[3], float fov_deg, int width, int height, float eye3[3]);
 /* One row of gs4d_transform_records' table: the upper 3x3 of L is scale * R(q) with the R of gs4d_host_splat3d_cov (the matrix of the quaternion as
  * given, not normalised), each element one product; column 3, rows 0..2 = velocity (a source at time t lands velocity * t further on);
  * L[3, 3] = time_scale and the time row is otherwise 0; o = (translate, time_offset).  A source time t shows at time_scale * t + time_offset. */
