@@ -107,6 +107,7 @@ def _load():
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
         "gs4d_get_stats": (i32, [vp, vp]),
+        "gs4d_get_sort_stats": (i32, [vp, vp]),
         "gs4d_debug_read_projected": (i32, [vp, vp, sz]),
         "gs4d_debug_shadow_builds": (i32, [vp, u32, C.POINTER(C.c_uint64)]),
         "gs4d_host_look_at": (None, [vp, vp, vp, vp]),
@@ -1272,6 +1273,13 @@ class Context:
         return {"entries": int(st[0]) & 0xFFFFFFFF, "staged_draws": int(st[0]) >> 32, "capacity": int(st[1]) & 0xFFFFFFFFFF, "staged_misses": int(st[1]) >> 40, "reruns": int(st[2]) & 0xFFFFFFFF, "aborted_discarded": int(st[2]) >> 32, "tiles": int(st[3]) & 0xFFFFFFFF, "record_read_bytes": (int(st[3]) >> 32) & 0xFF, "composited_tiles": int(st[3]) >> 40,
                 "depth_sort_passes": int(st[4]) & 0xFFFFFFFF, "lane_streams_rejected": int(st[4]) >> 32, "tile_sort_passes": int(st[5]) & 0xFFFFFFFF, "renamed_keygens": int(st[5]) >> 32, "lanes": int(st[6]) & 0xFFFF, "lanes_sharing_a_queue": (int(st[6]) >> 16) & 0xFFFF, "fused_keygen_draws": int(st[6]) >> 32,
                 "unordered_draws": int(st[7]) & 0xFFFFFFFF, "longest_list": int(st[7]) >> 32}
+
+    def sort_stats(self):
+        """The depth sorts so far (gs4d_get_sort_stats; waits for everything queued): hybrid sorts, sort kernel launches, and the latest
+        top-digit report: its largest bucket and its buckets above the tail's capacity."""
+        st = np.zeros(4, np.uint64)
+        self._chk(_lib.gs4d_get_sort_stats(self._h, _ptr(st)))
+        return {"hybrid_sorts": int(st[0]), "sort_launches": int(st[1]), "largest_bucket": int(st[2]), "slow_buckets": int(st[3])}
 
     def debug_projected(self, n):
         out = np.empty((n, 16), np.float32)

@@ -470,8 +470,8 @@ int enqueue_keygen_sort(gs4d_ctx* c, Lane& L, const Buffer& D, size_t n, const K
         uint32_t* kh = sort_hist_slot(L.s, L.depth_sort, n, &he);
         if (!kh) return hipfail(c, he, "sort_hist_slot");
         StageTimer tm(c, timed ? GS4D_T_KEYGEN : -1);
-        L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, n, bits);
-        HIPCHK(c, launch_keygen(L.s, D.soa, soa_sig3(D.soa, D.soa_n, D.soa_info), D.soa_info, n, ks, (float*)keys, idx, kh, L.depth_sort.hist_rb, span, L.err_word()));
+        sort_plan_hist(L.depth_sort, n, bits);             // LSD passes or the hybrid: chosen before the keys exist, the producer counts the digits of that plan
+        HIPCHK(c, launch_keygen(L.s, D.soa, soa_sig3(D.soa, D.soa_n, D.soa_info), D.soa_info, n, ks, (float*)keys, idx, kh, L.depth_sort.hist_rb, L.depth_sort.hist_rows, L.depth_sort.hist_top, span, L.err_word()));
         L.depth_sort.hist_bias = ks.bias;
     }
     StageTimer t(c, sort && timed ? GS4D_T_SORT : -1);
@@ -552,7 +552,8 @@ int fill_tile_count(gs4d_ctx* c, Lane& L, const DrawArgs& a, size_t npre, bool v
         if (!kh) return hipfail(c, he, "sort_hist_slot");
         tc.keys_out = (float*)fused.keys->d; tc.idx_out = nullptr /* the depth sort that follows makes the identity index up */; tc.ghist = kh; tc.span = a.blend_order.span; tc.err = L.err_word();
         L.depth_sort.hist_bias = a.blend_order.ks.bias;
-        tc.hist_rb = L.depth_sort.hist_rb = sort_plan_rb(L.depth_sort, npre, a.blend_order.bits);
+        sort_plan_hist(L.depth_sort, npre, a.blend_order.bits);
+        tc.hist_rb = L.depth_sort.hist_rb; tc.hist_rows = L.depth_sort.hist_rows; tc.hist_top = L.depth_sort.hist_top;
     }
     return GS4D_OK;
 }
@@ -984,6 +985,11 @@ int gs4d_create(int device, int width, int height, gs4d_ctx** out) {
     const int shape_knob = getenv("GS4D_SORT_SHAPE") ? atoi(getenv("GS4D_SORT_SHAPE")) : 0, rank_knob = getenv("GS4D_SORT_RANK") ? atoi(getenv("GS4D_SORT_RANK")) : 0;
     for (int i = 0; i < c->nlanes; ++i) {
         for (SortScratch* ss : { &c->lanes[i].depth_sort, &c->lanes[i].pair_sort }) { ss->atomic_rank = c->atomic_rank; ss->shape_knob = shape_knob; ss->rank_knob = rank_knob; ss->rb_knob = getenv("GS4D_SORT_RB") ? atoi(getenv("GS4D_SORT_RB")) : 0; }
+        // GS4D_SORT_HYBRID: 0 = depth sorts are the LSD passes, as before the hybrid existed; 1 = the hybrid for every eligible span, whatever n.  GS4D_SORT_TAILCAP: keys above
+        // which a bucket of the hybrid takes the tail kernel's slow path (test hook: a runtime compare).  The tile sort (pair_sort) never plans the hybrid: it is not asked to (sort_plan_hist).
+        if (const char* ev = getenv("GS4D_SORT_HYBRID")) c->lanes[i].depth_sort.hybrid_knob = atoi(ev) != 0 ? 1 : 0;
+        if (const char* ev = getenv("GS4D_SORT_TAILCAP")) { const long v = atol(ev); if (v >= 1) c->lanes[i].depth_sort.tail_cap = (uint32_t)std::min<long>(v, 1l << 30); }
+        c->lanes[i].pair_sort.hybrid_knob = 0;
     }
     int rc = alloc_fbs(c, width, height);
     if (rc) return bail(rc);
@@ -2123,6 +2129,20 @@ int gs4d_get_stats(gs4d_ctx* c, uint64_t stats[8]) {
     int rc = resolve_pending(c); if (rc) return rc;
     stats[0] = (c->stat_entries & 0xFFFFFFFFull) | (c->stat_staged << 32); stats[1] = ((uint64_t)lane(c).pair_cap & 0xFFFFFFFFFFull) | (c->stat_staged_misses << 40); stats[2] = (c->stat_reruns & 0xFFFFFFFFull) | (c->stat_aborted_discarded << 32); stats[3] = (uint64_t)c->tiles_x * c->tiles_y | ((c->stat_shadow_bytes & 0xFFull) << 32) | ((c->stat_composited_tiles & 0xFFFFFFull) << 40);
     stats[4] = (c->stat_depth_passes & 0xFFFFFFFFull) | (c->stat_streams_rejected << 32); stats[5] = (c->stat_tile_passes & 0xFFFFFFFFull) | (c->stat_renamed << 32); stats[6] = (uint64_t)(c->nlanes & 0xFFFF) | (c->stat_lanes_sharing << 16) | (c->stat_fused << 32); stats[7] = c->stat_v2_draws | (c->stat_longest << 32);
+    return GS4D_OK;
+}
+
+int gs4d_get_sort_stats(gs4d_ctx* c, uint64_t stats[4]) {
+    if (!c || !stats) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    int rc = resolve_pending(c); if (rc) return rc;
+    rc = sync_all(c); if (rc) return rc;                // the report words are final: every queued sort has run
+    stats[0] = stats[1] = stats[2] = stats[3] = 0;
+    for (int i = 0; i < c->nlanes; ++i) {
+        const SortScratch& s = c->lanes[i].depth_sort;
+        stats[0] += s.stat_hybrid; stats[1] += s.stat_launches;
+        if (s.fb && s.fb[2]) { stats[2] = std::max<uint64_t>(stats[2], s.fb[0]); stats[3] += s.fb[1]; }
+    }
     return GS4D_OK;
 }
 

@@ -101,6 +101,17 @@ struct SortScratch {
     int hist_rb = 8;                   // digit width the producer of the pending histogram counted in (sort_plan_rb, chosen together with hist_bits)
     int rb_knob = 0;                   // test hook GS4D_SORT_RB (8 / 9): the digit width of every sort whose tile shape allows it
     uint32_t hist_bias = 0;            // ... of (key - hist_bias): a lower bound of all keys, which makes the high digits constant (and their passes skipped)
+    // The plan of the pending histogram (sort_plan_hist, chosen with hist_rb / hist_bits before the keys are produced: the producer must count the right digits):
+    //   hist_rows  how many LSD digit rows the producer counted (OS_MAX_PASSES: all, the plain LSD plan)
+    //   hist_top   >= 0: the producer also counted the 9-bit top digit (key - bias) >> hist_top into row OS_TOP_ROW
+    //   hist_hybrid  the sort is the MSD/LSD hybrid: one global pass on the top digit, then k_os_tail (hist_rows == 0)
+    int hist_rows = 4, hist_top = -1; bool hist_hybrid = false;
+    int hybrid_knob = -1;              // GS4D_SORT_HYBRID: 0 = never (the LSD passes, nothing else counted), 1 = for every eligible span at any n, unset = eligible spans of >= OS_HYBRID_MIN_N keys
+    uint32_t tail_cap = 8192;          // GS4D_SORT_TAILCAP: buckets above it take k_os_tail's slow path (at most the kernel's LDS tile)
+    // pinned + mapped status words of the latest top-digit report (k_os_tail's first workgroup, or k_os_top_stats behind a fallback sort), and the same
+    // memory as the device sees it.  [0] largest bucket, [1] buckets above tail_cap, [2] non-zero once anything was reported
+    uint32_t* fb = nullptr; uint32_t* fb_dev = nullptr;
+    uint64_t stat_hybrid = 0, stat_launches = 0;      // hybrid sorts and sort kernel launches (histogram launches included) of this scratch
     uint32_t epoch = 0;                // tag of the look-back words of the latest pass launch
     bool atomic_rank = false;          // LDS-atomic ranking verified on this device (lds_atomic_order_selftest)
     int shape_knob = 0, rank_knob = 0; // test / tuning hooks read at context creation: GS4D_SORT_SHAPE (1..6: tile shape of a pass), GS4D_SORT_RANK (1 = ballot ranking, 2 = LDS-atomic ranking)
@@ -121,6 +132,12 @@ hipError_t radix_sort_pairs(hipStream_t st, SortScratch& s, uint32_t* keys, uint
 uint32_t* sort_hist_slot(hipStream_t st, SortScratch& s, size_t n_hint, hipError_t* e_out);
 int sort_plan_rb(const SortScratch& s, size_t n, int key_bits);      // digit width (8 or 9 bits) of a sort of key_bits-bit keys
 int sort_plan_passes(int key_bits, int rb);                          // ... and the launches it takes
+// The plan of a depth sort of n keys of key_bits bits whose histograms a producer kernel is about to count: sets s.hist_rb, hist_rows, hist_top and
+// hist_hybrid (what the producer is launched with, and what radix_sort_pairs(have_hist) then executes).  The hybrid is planned for spans of 19..27 bits
+// when LDS-atomic ranking is verified, no sort test hook is set and the latest report's largest bucket fits k_os_tail's tile; a span that is eligible
+// but crowded keeps the LSD passes and has the top digit counted beside them, so that the plan can return.
+constexpr size_t OS_HYBRID_MIN_N = 32768;
+void sort_plan_hist(SortScratch& s, size_t n, int key_bits);
 hipError_t lds_atomic_order_selftest(const hipStream_t* streams, int nstreams, bool* ordered);      // on all the streams at once
 // Layout of the SoA shadow (preprocess.hip).  The repack kernel verifies what a compact layout assumes, bit for bit, for every record, and
 // reports a violation in bbox[15]; the caller then repacks in the next layout down.
@@ -134,7 +151,7 @@ struct SoaInfo { int layout = SOA_FULL; float consts[8] = { 0 }; };      // cons
 // sig3 == nullptr: a static set (SOA_STATIC3D) — mu_t and sig[3] are info.consts for every record
 // ks: what the keys are computed from (KEYSRC_REF / KEYSRC_VIEWZ, below); span: what k_keygen checks (key - ks.bias) against
 struct KeySrc;
-hipError_t launch_keygen(hipStream_t st, const float4* pos, const float4* sig3, const SoaInfo& info, size_t n, const KeySrc& ks, float* keys, uint32_t* idx, uint32_t* ghist, int rb, uint32_t span, uint32_t* err);
+hipError_t launch_keygen(hipStream_t st, const float4* pos, const float4* sig3, const SoaInfo& info, size_t n, const KeySrc& ks, float* keys, uint32_t* idx, uint32_t* ghist, int rb, int hist_rows, int hist_top, uint32_t span, uint32_t* err);
 
 // A grow-only device array used by kernels queued on `st`: nothing when `cap` elements suffice; else the stream is waited for, the old block freed
 // and one of `want` elements allocated.  After a failed allocation pointer and capacity are null / zero.
@@ -153,6 +170,7 @@ constexpr int OS_MAX_PASSES = 4;
 constexpr int OS_REPL = 8;                                   // replicas of the global histogram: bounds same-address atomic traffic
 constexpr uint32_t OS_MAX_BINS = 512;                        // digits are 8 or 9 bits wide (sort_plan_rb); a histogram row always has room for 512 bins
 constexpr size_t OS_SLOT_WORDS = (size_t)OS_REPL * OS_MAX_PASSES * OS_MAX_BINS;
+constexpr int OS_TOP_ROW = OS_MAX_PASSES - 1;                // the row of the hybrid sort's 9-bit top digit (a span of <= 27 bits has at most three LSD rows)
 #ifdef __HIPCC__
 // (threads 0..255 of the workgroup call clear and flush: each looks after bins tid and tid + 256)
 __device__ __forceinline__ void os_hist_clear(uint32_t (*h)[OS_MAX_BINS], uint32_t tid) {
@@ -163,14 +181,16 @@ __device__ __forceinline__ void os_hist_clear(uint32_t (*h)[OS_MAX_BINS], uint32
 // Skewed digits (e.g. the sign/exponent bytes of depth keys take 2-3 values) would serialise 64 LDS atomics on 2-3 addresses:
 // the lanes sharing the digit of the first unresolved lane are counted with a ballot and added by one lane, twice; the lanes
 // left after that (most lanes of a uniformly distributed digit, almost none of a skewed one) use plain LDS atomics.
-__device__ __forceinline__ void os_hist_add(uint32_t (*h)[OS_MAX_BINS], uint32_t key, bool in, int passes, int rb) {
+// top_shift >= 0: row OS_TOP_ROW counts the 9-bit digit key >> top_shift instead (passes <= OS_TOP_ROW then; passes == 0: that row alone).
+__device__ __forceinline__ void os_hist_add(uint32_t (*h)[OS_MAX_BINS], uint32_t key, bool in, int passes, int rb, int top_shift = -1) {
     const uint64_t act = __ballot(in);
     if (act == 0ull) return;
     const uint32_t lane = threadIdx.x & 63u;
 #pragma unroll
     for (int p = 0; p < OS_MAX_PASSES; ++p) {
-        if (p >= passes) break;
-        const uint32_t d = (key >> (rb * p)) & ((1u << rb) - 1u);
+        const bool top = top_shift >= 0 && p == OS_TOP_ROW;
+        if (p >= passes && !top) continue;
+        const uint32_t d = top ? (key >> top_shift) & (OS_MAX_BINS - 1u) : (key >> (rb * p)) & ((1u << rb) - 1u);
         uint64_t rem = act;
 #pragma unroll
         for (int it = 0; it < 2; ++it) {
@@ -184,9 +204,10 @@ __device__ __forceinline__ void os_hist_add(uint32_t (*h)[OS_MAX_BINS], uint32_t
         if ((rem >> lane) & 1ull) atomicAdd(&h[p][d], 1u);
     }
 }
-__device__ __forceinline__ void os_hist_flush(uint32_t (*h)[OS_MAX_BINS], uint32_t* __restrict__ ghist, int passes, uint32_t tid) {
+__device__ __forceinline__ void os_hist_flush(uint32_t (*h)[OS_MAX_BINS], uint32_t* __restrict__ ghist, int passes, uint32_t tid, int top_shift = -1) {
     uint32_t* g = ghist + (size_t)(blockIdx.x % OS_REPL) * OS_MAX_PASSES * OS_MAX_BINS;
-    for (int p = 0; p < passes; ++p) {
+    for (int p = 0; p < OS_MAX_PASSES; ++p) {
+        if (p >= passes && !(top_shift >= 0 && p == OS_TOP_ROW)) continue;
         const uint32_t v = h[p][tid], v2 = h[p][tid + 256u];
         if (v) atomicAdd(&g[p * OS_MAX_BINS + tid], v);
         if (v2) atomicAdd(&g[p * OS_MAX_BINS + tid + 256u], v2);
@@ -222,7 +243,7 @@ struct TileCount {                               // hist == nullptr: the ordered
     KeySrc ks;
     // Fused key generation (the draw executes a gs4d_keygen + gs4d_sort_pairs that were queued just before it): the projection kernel also
     // writes the caller's key and index buffers and accumulates the digit histograms of the depth sort, exactly as k_keygen would
-    float* keys_out = nullptr; uint32_t* idx_out = nullptr; uint32_t* ghist = nullptr; int hist_rb = 8; uint32_t span = 0xFFFFFFFFu; uint32_t* err = nullptr;
+    float* keys_out = nullptr; uint32_t* idx_out = nullptr; uint32_t* ghist = nullptr; int hist_rb = 8, hist_rows = OS_MAX_PASSES, hist_top = -1 /* SortScratch::hist_rows, hist_top */; uint32_t span = 0xFFFFFFFFu; uint32_t* err = nullptr;
     uint32_t* sstat = nullptr;                   // [rows]: entries of every segment (statistics for the host; every counting launch writes them)
     // Staged lists (tilelist.hip): the projection kernel itself WRITES the entries.  A workgroup counts its segment's entries per bucket, scans
     // the counts, places the entries bucket by bucket in LDS and writes them out as ONE dense block: stage_out[segment * scap + offs[b][segment] + k],

@@ -436,7 +436,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t
                 if (key > tc.span) __hip_atomic_store(tc.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // below the bias wraps to a huge value: caught too
             }
         }
-        if (FUSE_KEYS) os_hist_add(kh, key, i < i1, OS_MAX_PASSES, tc.hist_rb);
+        if (FUSE_KEYS) os_hist_add(kh, key, i < i1, tc.hist_rows, tc.hist_rb, tc.hist_top);       // a hybrid-planned sort: the top-digit row alone (one LDS atomic per record, not three)
         if (COUNT) count_buckets(h, tc.nb - 1u, (uint32_t)tc.tiles_x, r);
     };
     if (COUNT == 2) {
@@ -486,7 +486,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t
             }
         }
     }
-    if (FUSE_KEYS && threadIdx.x < 256u) os_hist_flush(kh, tc.ghist, OS_MAX_PASSES, threadIdx.x);
+    if (FUSE_KEYS && threadIdx.x < 256u) os_hist_flush(kh, tc.ghist, tc.hist_rows, threadIdx.x, tc.hist_top);
 }
 
 static PU make_pu(const Uniforms& un, int W, int H) {

@@ -25,7 +25,7 @@ namespace gs4d {
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_keygen(const float4* __restrict__ pos, const float4* __restrict__ sig3, uint32_t n, float t,
                                                 float camx, float camy, float camz, float4 vrow2 /* view row 2: V[2],V[6],V[10],V[14] */, int key_mode,
-                                                float* __restrict__ keys, uint32_t* __restrict__ idx, uint32_t* __restrict__ ghist /* digit histograms of (key - bias), for the sort */, int rb /* ... in digits of rb bits */,
+                                                float* __restrict__ keys, uint32_t* __restrict__ idx, uint32_t* __restrict__ ghist /* digit histograms of (key - bias), for the sort */, int rb /* ... in digits of rb bits */, int hist_rows, int hist_top /* SortScratch::hist_rows, hist_top */,
                                                 uint32_t bias /* host-proven lower bound of every key's bit pattern */, uint32_t span /* ... and of (key - bias) from above */, uint32_t* __restrict__ err,
                                                 float4 csig3, float cmut /* sig3 == nullptr (a static set: SOA_STATIC3D): sig[3] and mu_t of every record */) {
     __shared__ uint32_t h[OS_MAX_PASSES][OS_MAX_BINS];
@@ -58,18 +58,18 @@ __global__ __launch_bounds__(256) void k_keygen(const float4* __restrict__ pos, 
         }
         const uint32_t kb = __float_as_uint(key);
         if (in && (kb < bias || kb - bias > span)) __hip_atomic_store(err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // the bound did not hold: reported, never silently mis-sorted
-        os_hist_add(h, kb - bias, in, OS_MAX_PASSES, rb);
+        os_hist_add(h, kb - bias, in, hist_rows, rb, hist_top);
     }
     __syncthreads();
-    os_hist_flush(h, ghist, OS_MAX_PASSES, threadIdx.x);
+    os_hist_flush(h, ghist, hist_rows, threadIdx.x, hist_top);
 }
 
-hipError_t launch_keygen(hipStream_t st, const float4* pos, const float4* sig3, const SoaInfo& info, size_t n, const KeySrc& ks, float* keys, uint32_t* idx, uint32_t* ghist, int rb, uint32_t span, uint32_t* err) {
+hipError_t launch_keygen(hipStream_t st, const float4* pos, const float4* sig3, const SoaInfo& info, size_t n, const KeySrc& ks, float* keys, uint32_t* idx, uint32_t* ghist, int rb, int hist_rows, int hist_top, uint32_t span, uint32_t* err) {
     if (n == 0) return hipSuccess;
     const float4 vr = make_float4(ks.vr0, ks.vr1, ks.vr2, ks.vr3);
     const int key_mode = ks.mode == KEYSRC_VIEWZ ? GS4D_KEY_VIEW_Z : GS4D_KEY_REF_INV_EUCLID;
     const unsigned blocks = (unsigned)std::min<size_t>((n + 255) / 256, 1024);     // grid-stride: bounds the histogram flush to 1024 workgroups
-    k_keygen<<<dim3(blocks), dim3(256), 0, st>>>(pos, sig3, (uint32_t)n, ks.t, ks.camx, ks.camy, ks.camz, vr, key_mode, keys, idx, ghist, rb, ks.bias, span, err,
+    k_keygen<<<dim3(blocks), dim3(256), 0, st>>>(pos, sig3, (uint32_t)n, ks.t, ks.camx, ks.camy, ks.camz, vr, key_mode, keys, idx, ghist, rb, hist_rows, hist_top, ks.bias, span, err,
                                                      make_float4(info.consts[4], info.consts[5], info.consts[6], info.consts[7]), info.consts[0]);
     return hipGetLastError();
 }
@@ -114,7 +114,7 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, uint32_t lane
     for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(v, off, 64); if (lane >= (unsigned)off) v += t; }
     return v;
 }
-__global__ __launch_bounds__(256) void k_os_hist(const uint32_t* __restrict__ keys, uint32_t n_cap, const uint32_t* __restrict__ n_dev, int passes, int rb,
+__global__ __launch_bounds__(256) void k_os_hist(const uint32_t* __restrict__ keys, uint32_t n_cap, const uint32_t* __restrict__ n_dev, int passes, int rb, int top /* >= 0: the top-digit row as well (os_hist_add) */,
                                                  uint32_t* __restrict__ ghist /* [OS_REPL][4][OS_MAX_BINS], zero on entry */) {
     __shared__ uint32_t h[OS_MAX_PASSES][OS_MAX_BINS];
     const uint32_t n = n_dev ? min(*n_dev, n_cap) : n_cap;
@@ -131,13 +131,13 @@ __global__ __launch_bounds__(256) void k_os_hist(const uint32_t* __restrict__ ke
         for (int u = 0; u < 4; ++u) { const uint32_t i = i0 + u * stride; in[u] = i < nvec; kk[u] = in[u] ? k4[i] : make_uint4(0, 0, 0, 0); }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-            os_hist_add(h, kk[u].x, in[u], passes, rb); os_hist_add(h, kk[u].y, in[u], passes, rb);
-            os_hist_add(h, kk[u].z, in[u], passes, rb); os_hist_add(h, kk[u].w, in[u], passes, rb);
+            os_hist_add(h, kk[u].x, in[u], passes, rb, top); os_hist_add(h, kk[u].y, in[u], passes, rb, top);
+            os_hist_add(h, kk[u].z, in[u], passes, rb, top); os_hist_add(h, kk[u].w, in[u], passes, rb, top);
         }
     }
-    if (blockIdx.x == 0) { const bool in = tid < (n & 3u); os_hist_add(h, in ? keys[nvec * 4u + tid] : 0u, in, passes, rb); }      // tail keys
+    if (blockIdx.x == 0) { const bool in = tid < (n & 3u); os_hist_add(h, in ? keys[nvec * 4u + tid] : 0u, in, passes, rb, top); }      // tail keys
     __syncthreads();
-    os_hist_flush(h, ghist, passes, tid);
+    os_hist_flush(h, ghist, passes, tid, top);
 }
 
 // Which passes are live, and which buffers pass `p` reads and writes.  Returns false when pass p is skipped.
@@ -290,6 +290,72 @@ __device__ __forceinline__ uint32_t digit_excl_scan(uint32_t v, uint32_t* tmp /*
     return base + inc - v;
 }
 
+// ---- the tile-local part of a digit pass: rank, per-wave offsets, reorder in LDS (k_os_pass for a tile, k_os_tail for a bucket or a chunk of one) ----
+// A wave looks after the keys [first, end) of the tile, item j of lane l being key first + 64 j + l (ITEMS x 64 >= end - first): wave-major, item-major,
+// lane order is memory order, which is what makes the pass stable.  The digit is ((key - bias) >> shift) & mask.
+// rank[j] = how many earlier keys of the wave carry the same digit; wc (the wave's row of counters, zero on entry) ends as the wave's digit counts.
+template <int ITEMS, bool ATOMIC_RANK, int RB /* the ballot form's digit width: mask == (1 << RB) - 1 */>
+__device__ __forceinline__ void os_rank_items(const uint32_t (&key)[ITEMS], uint32_t (&rank)[ITEMS], uint32_t first, uint32_t end, uint32_t bias, int shift, uint32_t mask, uint32_t* wcw, uint32_t lane) {
+    if (ATOMIC_RANK) {
+        // rank = value returned by an LDS atomic add on the wave's digit counter.  Stable only because the LDS unit serialises the
+        // lanes of one instruction that hit the same counter in ascending lane order — not an architectural promise, so the
+        // library verifies it on the device at context creation (k_lds_order_test) and uses the ballot form below otherwise.
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+            const bool valid = (first + j * 64u + lane) < end;
+            const uint32_t d = ((key[j] - bias) >> shift) & mask;
+            rank[j] = valid ? atomicAdd(&wcw[d], 1u) : 0u;
+        }
+    } else {
+        const uint64_t lt = (1ull << lane) - 1ull;
+        volatile uint32_t* wc = wcw;
+#pragma unroll
+        for (int j = 0; j < ITEMS; ++j) {
+            const bool valid = (first + j * 64u + lane) < end;
+            const uint32_t d = ((key[j] - bias) >> shift) & mask;
+            uint64_t m = __ballot(valid);
+#pragma unroll
+            for (int b = 0; b < RB; ++b) {
+                const bool bit = (d >> b) & 1u;
+                const uint64_t bal = __ballot(bit);
+                m &= bit ? bal : ~bal;
+            }
+            rank[j] = 0;
+            if (valid) {
+                const uint32_t c = wc[d];
+                rank[j] = c + (uint32_t)__popcll(m & lt);
+                __builtin_amdgcn_wave_barrier();
+                if ((m & lt) == 0) wc[d] = c + (uint32_t)__popcll(m);
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+// thread d < BINS (behind a barrier after the ranking): the waves' counts of digit d become each wave's offset inside the tile's digit-d run; returns the tile's count
+template <int WAVES, int BINS>
+__device__ __forceinline__ uint32_t os_wave_offsets(uint32_t (*wcnt)[BINS], uint32_t tid) {
+    uint32_t cnt = 0;
+    if (tid < (uint32_t)BINS) {
+#pragma unroll
+        for (int k = 0; k < WAVES; ++k) { const uint32_t t = wcnt[k][tid]; wcnt[k][tid] = cnt; cnt += t; }
+    }
+    return cnt;
+}
+// the reorder inside LDS (behind a barrier after loff, the first local slot of every digit, was written): the tile ends in skeys / svals, digit runs in order
+template <int ITEMS>
+__device__ __forceinline__ void os_scatter_items(const uint32_t (&key)[ITEMS], const uint32_t (&val)[ITEMS], const uint32_t (&rank)[ITEMS], uint32_t first, uint32_t end, uint32_t bias, int shift, uint32_t mask,
+                                                 const uint32_t* loff, const uint32_t* wcw, uint32_t* skeys, uint32_t* svals, uint32_t lane) {
+#pragma unroll
+    for (int j = 0; j < ITEMS; ++j) {
+        if ((first + j * 64u + lane) < end) {                   // stable: wave-major, item-major, lane order == memory order
+            const uint32_t d = ((key[j] - bias) >> shift) & mask;
+            const uint32_t l = loff[d] + wcw[d] + rank[j];
+            skeys[l] = key[j];
+            svals[l] = val[j];
+        }
+    }
+}
+
 // Persistent workgroups: the grid is what fits the device at once (or one workgroup per tile if that is fewer); a workgroup draws a
 // ticket, sorts that tile, draws the next.  What does not depend on the tile (histograms -> live passes and digit bases, the
 // housekeeping for the next launch) happens once per workgroup, and a finished tile's successor starts without a dispatch.
@@ -299,6 +365,8 @@ __global__ __launch_bounds__(THREADS) void k_os_pass(OsBufs bufs, uint32_t n_cap
                                                      uint32_t* status /* [tiles][BINS] */, uint32_t* acc /* [acc_groups + supers][BINS], zero at launch */, uint32_t* acc_next /* zeroed here */, uint32_t acc_groups, uint32_t acc_words,
                                                      uint32_t epoch, uint32_t* err,
                                                      uint32_t* ticket /* zero at launch */, uint32_t* ticket_next /* zeroed here */, uint32_t bias, int identity_vals /* the payload is the identity index and has NOT been written: see radix_sort_pairs */,
+                                                     int shift /* the digit is ((key - bias) >> shift) & (BINS - 1): RB * pass for an LSD pass */, int hist_row /* the row of ghist that counts this digit */,
+                                                     int top /* the hybrid sort's global pass (radix_sort_pairs): always moves the keys, caller's buffers -> scratch 1, as the first executed pass */,
                                                      u64* stamps /* tuning aid, may be null */) {
     constexpr uint32_t TILE_KEYS = THREADS * ITEMS;
     constexpr int WAVES = THREADS / 64;
@@ -327,11 +395,14 @@ __global__ __launch_bounds__(THREADS) void k_os_pass(OsBufs bufs, uint32_t n_cap
     for (uint32_t q = tid; q < WAVES * BINS; q += THREADS) (&wcnt[0][0])[q] = 0u;
     uint32_t tot = 0, dead = 0;
     if (tid < BINS) {
-        for (int q = 0; q < passes; ++q) {
+        if (top) {                                                // (uniform) no dead-pass bookkeeping: this row is the only one counted
+#pragma unroll
+            for (int r = 0; r < OS_REPL; ++r) tot += ghist[(r * OS_MAX_PASSES + hist_row) * OS_MAX_BINS + tid];
+        } else for (int q = 0; q < passes; ++q) {
             uint32_t g = 0;
 #pragma unroll
             for (int r = 0; r < OS_REPL; ++r) g += ghist[(r * OS_MAX_PASSES + q) * OS_MAX_BINS + tid];
-            if (q == pass) tot = g;
+            if (q == hist_row) tot = g;
             if (g == n) dead |= 1u << q;                          // one digit holds every key
         }
     }
@@ -344,9 +415,8 @@ __global__ __launch_bounds__(THREADS) void k_os_pass(OsBufs bufs, uint32_t n_cap
     __syncthreads();
     uint32_t tile = s_tile;
     if (tile >= ntiles) return;                                   // uniform
-    const int shift = RB * pass;
-    int src, dst, executed, total;
-    if (!os_schedule(~s_dead, passes, pass, src, dst, executed, total)) {          // uniform: this pass is an identity
+    int src = 0, dst = 1, executed = 0, total = 1;
+    if (!top && !os_schedule(~s_dead, passes, pass, src, dst, executed, total)) {          // uniform: this pass is an identity
         // an identity payload nobody has written, and no pass at all will move anything (every key is the same): pass 0's launch writes it
         if (identity_vals && pass == 0 && total == 0) { for (uint32_t i = blockIdx.x * THREADS + tid; i < n; i += gridDim.x * THREADS) bufs.v[0][i] = i; }
         return;
@@ -373,48 +443,13 @@ __global__ __launch_bounds__(THREADS) void k_os_pass(OsBufs bufs, uint32_t n_cap
         if (first) { digit_base = digit_excl_scan<THREADS, (int)BINS>(tot, s_tmp, tid); first = false; }      // once per workgroup, under the first tile's loads
         OS_STAMP(1);
 
-        if (ATOMIC_RANK) {
-            // rank = value returned by an LDS atomic add on the wave's digit counter.  Stable only because the LDS unit serialises the
-            // lanes of one instruction that hit the same counter in ascending lane order — not an architectural promise, so the
-            // library verifies it on the device at context creation (k_lds_order_test) and uses the ballot form below otherwise.
-#pragma unroll
-            for (int j = 0; j < ITEMS; ++j) {
-                const bool valid = (wbase + j * 64u + lane) < n;
-                const uint32_t d = ((key[j] - bias) >> shift) & (BINS - 1u);
-                rank[j] = valid ? atomicAdd(&wcnt[w][d], 1u) : 0u;
-            }
-        } else {
-            const uint64_t lt = (1ull << lane) - 1ull;
-            volatile uint32_t* wc = wcnt[w];
-#pragma unroll
-            for (int j = 0; j < ITEMS; ++j) {
-                const bool valid = (wbase + j * 64u + lane) < n;
-                const uint32_t d = ((key[j] - bias) >> shift) & (BINS - 1u);
-                uint64_t m = __ballot(valid);
-#pragma unroll
-                for (int b = 0; b < RB; ++b) {
-                    const bool bit = (d >> b) & 1u;
-                    const uint64_t bal = __ballot(bit);
-                    m &= bit ? bal : ~bal;
-                }
-                rank[j] = 0;
-                if (valid) {
-                    const uint32_t c = wc[d];
-                    rank[j] = c + (uint32_t)__popcll(m & lt);
-                    __builtin_amdgcn_wave_barrier();
-                    if ((m & lt) == 0) wc[d] = c + (uint32_t)__popcll(m);
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
+        os_rank_items<ITEMS, ATOMIC_RANK, RB>(key, rank, wbase, n, bias, shift, BINS - 1u, wcnt[w], lane);
         __syncthreads();
         // thread d: counts per wave -> offsets inside the tile's digit-d run; tile count of digit d; publish it at once
-        uint32_t cnt = 0;
+        const uint32_t cnt = os_wave_offsets<WAVES, (int)BINS>(wcnt, tid);
         uint32_t garr = 0;
         const uint32_t grp = tile / OS_GROUP, sup = grp / OS_SUPER;
         if (tid < BINS) {
-#pragma unroll
-            for (int k = 0; k < WAVES; ++k) { const uint32_t t = wcnt[k][tid]; wcnt[k][tid] = cnt; cnt += t; }
             __hip_atomic_store(status + (size_t)tile * BINS + tid, os_tword(epoch, cnt), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             // {arrivals:8, sum:24} accumulator of the group (only if a later tile will read it); what it held before comes back after the
             // reorder below
@@ -427,15 +462,7 @@ __global__ __launch_bounds__(THREADS) void k_os_pass(OsBufs bufs, uint32_t n_cap
         const uint32_t lo_ = digit_excl_scan<THREADS, (int)BINS>(cnt, s_tmp, tid);
         if (tid < BINS) loff[tid] = lo_;
         __syncthreads();
-#pragma unroll
-        for (int j = 0; j < ITEMS; ++j) {
-            if ((wbase + j * 64u + lane) < n) {                   // stable: wave-major, item-major, lane order == memory order
-                const uint32_t d = ((key[j] - bias) >> shift) & (BINS - 1u);
-                const uint32_t l = loff[d] + wcnt[w][d] + rank[j];
-                skeys[l] = key[j];
-                svals[l] = val[j];
-            }
-        }
+        os_scatter_items<ITEMS>(key, val, rank, wbase, n, bias, shift, BINS - 1u, loff, wcnt[w], skeys, svals, lane);
         OS_STAMP(3);
         if (tid < BINS) {
             // the tile that completes its group (per digit: whichever arrived sixteenth) hands the group's total to the super-group: a
@@ -534,6 +561,181 @@ hipError_t lds_atomic_order_selftest(const hipStream_t* streams, int nstreams, b
     return e;
 }
 
+// ------------------------------------------------------------------------------------------------
+// The MSD/LSD hybrid for depth keys whose host-proven span is 19..27 bits (sort_plan_hist): two launches instead of three or four chained passes.
+//   launch A : k_os_pass<512, 12, true, 9> with `top` set: ONE global pass on the 9-bit top digit (key - bias) >> (key_bits - 9), caller's buffers
+//              (identity payload made up) -> scratch 1.  The array is then cut into at most 512 buckets, each still in the caller's order.
+//   launch B : k_os_tail, one workgroup per top digit.  The bucket's range comes from an exclusive scan of the top-digit histogram (no look-back, no
+//              global atomic); the bucket is loaded into LDS, its remaining key_bits - 9 bits are sorted by two stable local passes (the tile-local
+//              ranking of k_os_pass) and it goes back, coalesced, to the same range of the caller's buffers.
+// No workgroup of launch B waits for another one: no spin, no ticket, no persistent grid.
+// A bucket above `cap` keys (the LDS tile, or GS4D_SORT_TAILCAP) is sorted by the same workgroup with two LSD passes through global memory, in chunks
+// of OT_TILE keys taken in order with running digit offsets: scratch 1 -> scratch 2 -> caller's buffers, __syncthreads only.  Slow (one workgroup,
+// linear in the bucket) but exact.  The first workgroup reports the largest bucket and the number of such buckets to the host (os_top_report): a
+// crowded key distribution makes the host plan the LSD passes for the next sorts instead (sort_plan_hist).
+// ------------------------------------------------------------------------------------------------
+constexpr int OT_THREADS = 512, OT_ITEMS = 16, OT_WAVES = OT_THREADS / 64, OT_BINS = 512;
+constexpr uint32_t OT_TILE = OT_THREADS * OT_ITEMS;      // 8192 keys: the largest bucket sorted inside LDS, and the slow path's chunk
+static_assert(OT_BINS == (int)OS_MAX_BINS && OT_BINS <= OT_THREADS, "one thread per top digit and per local digit");
+// LB = bins of the local passes: 256 while both local digits are <= 8 bits (spans of <= 25 bits: the counters, offsets and running positions then leave the
+// workgroup under 80 KB of LDS, two workgroups per CU), 512 for 26- and 27-bit spans
+static_assert(OS_TOP_ROW >= 3, "SortScratch::hist_rows: a span of <= 27 bits has three LSD rows below the top-digit row");
+
+// thread d carries g = the count of top digit d; the workgroup's thread 0 writes the report (pinned host memory)
+__device__ __forceinline__ void os_top_report(uint32_t g, uint32_t cap, uint32_t* red /* __shared__[2 * OT_WAVES] */, uint32_t* fb, uint32_t tid) {
+    uint32_t mx = g, slow = g > cap ? 1u : 0u;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { mx = max(mx, (uint32_t)__shfl_xor(mx, off, 64)); slow += (uint32_t)__shfl_xor(slow, off, 64); }
+    if ((tid & 63u) == 0u) { red[tid >> 6] = mx; red[OT_WAVES + (tid >> 6)] = slow; }
+    __syncthreads();
+    if (tid == 0u) {
+#pragma unroll
+        for (int k = 1; k < OT_WAVES; ++k) { mx = max(mx, red[k]); slow += red[OT_WAVES + k]; }
+        __hip_atomic_store(fb + 0, mx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(fb + 1, slow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(fb + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+__device__ __forceinline__ uint32_t os_top_count(const uint32_t* __restrict__ ghist, uint32_t tid) {
+    uint32_t g = 0;
+#pragma unroll
+    for (int r = 0; r < OS_REPL; ++r) g += ghist[(r * OS_MAX_PASSES + OS_TOP_ROW) * OS_MAX_BINS + tid];
+    return g;
+}
+// the report alone, behind the LSD passes of a sort that is eligible for the hybrid but crowded: how the plan finds its way back
+__global__ __launch_bounds__(OT_THREADS) void k_os_top_stats(const uint32_t* __restrict__ ghist, uint32_t cap, uint32_t* fb) {
+    __shared__ uint32_t red[2 * OT_WAVES];
+    os_top_report(os_top_count(ghist, threadIdx.x), cap, red, fb, threadIdx.x);
+}
+
+// One stable pass on the digit ((key - bias) >> shift) & mask over the `count` (<= OT_TILE) keys the workgroup holds in registers (wave w: keys
+// [first, end) of them, os_rank_items' layout): they end in skeys / svals, loff[d] is the first slot of digit d.  Returns the count of digit `tid`.
+template <int LB>
+__device__ __forceinline__ uint32_t ot_local_pass(const uint32_t (&key)[OT_ITEMS], const uint32_t (&val)[OT_ITEMS], uint32_t first, uint32_t end, uint32_t bias, int shift, uint32_t mask,
+                                                  uint32_t (*wcnt)[LB], uint32_t* loff, uint32_t* s_tmp, uint32_t* skeys, uint32_t* svals, uint32_t tid) {
+    const uint32_t lane = tid & 63u, w = tid >> 6;
+    uint32_t rank[OT_ITEMS];
+    for (uint32_t q = tid; q < (uint32_t)(OT_WAVES * LB); q += OT_THREADS) (&wcnt[0][0])[q] = 0u;
+    __syncthreads();                                              // (also: everybody has read what it wanted of skeys / svals / loff)
+    os_rank_items<OT_ITEMS, true, 9>(key, rank, first, end, bias, shift, mask, wcnt[w], lane);
+    __syncthreads();
+    const uint32_t cnt = os_wave_offsets<OT_WAVES, LB>(wcnt, tid);
+    const uint32_t lo = digit_excl_scan<OT_THREADS, LB>(cnt, s_tmp, tid);
+    if (tid < (uint32_t)LB) loff[tid] = lo;
+    __syncthreads();
+    os_scatter_items<OT_ITEMS>(key, val, rank, first, end, bias, shift, mask, loff, wcnt[w], skeys, svals, lane);
+    __syncthreads();
+    return cnt;
+}
+// the keys [first, end) of `count` (<= OT_TILE) that wave w looks after: equal shares, whole rows of 64 lanes
+__device__ __forceinline__ void ot_wave_range(uint32_t count, uint32_t w, uint32_t& first, uint32_t& end) {
+    const uint32_t share = (((count + OT_WAVES - 1u) / OT_WAVES) + 63u) & ~63u;      // <= 64 * OT_ITEMS
+    first = w * share;
+    end = min(count, first + share);                              // (a wave past the end: end <= first, nothing valid)
+}
+
+template <int LB>
+__global__ __launch_bounds__(OT_THREADS) void k_os_tail(OsBufs bufs, uint32_t n, const uint32_t* __restrict__ ghist /* the slot launch A read */, uint32_t bias,
+                                                        int rem /* key bits below the top digit: 10..18 */, uint32_t cap /* <= OT_TILE */, uint32_t* fb, uint32_t* err) {
+    __shared__ uint32_t skeys[OT_TILE];
+    __shared__ uint32_t svals[OT_TILE];
+    __shared__ uint32_t wcnt[OT_WAVES][LB];
+    __shared__ uint32_t loff[LB];
+    __shared__ uint32_t gpos[LB];
+    __shared__ uint32_t s_run[2][LB];           // slow path: where the next key of each digit goes, per pass
+    __shared__ uint32_t s_tmp[OT_BINS / 64];
+    __shared__ uint32_t s_red[2 * OT_WAVES];
+    __shared__ uint32_t s_range[2];
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    {
+        const uint32_t g = os_top_count(ghist, tid);
+        const uint32_t excl = digit_excl_scan<OT_THREADS, OT_BINS>(g, s_tmp, tid);
+        if (tid == blockIdx.x) { s_range[0] = excl; s_range[1] = g; }
+        if (blockIdx.x == 0) os_top_report(g, cap, s_red, fb, tid);      // uniform
+        __syncthreads();
+    }
+    const uint32_t start = s_range[0], count = s_range[1];
+    if (count == 0u) return;                                      // uniform: an empty bucket
+    // the histogram and the keys no longer describe the same array (see k_os_pass's write-out): nothing outside [0, n) is touched
+    if (start > n || count > n - start) { if (tid == 0u) __hip_atomic_store(err, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); return; }
+    const int w0 = (rem + 1) >> 1, w1 = rem >> 1;                 // the two local digits: bits [0, w0) and [w0, rem), each <= 9 bits
+    const uint32_t m0 = (1u << w0) - 1u, m1 = (1u << w1) - 1u;
+    uint32_t key[OT_ITEMS], val[OT_ITEMS];
+    if (count <= cap) {
+        // ---- the bucket fits: load, two local passes, write back ----
+        const uint32_t* k1 = bufs.k[1] + start; const uint32_t* v1 = bufs.v[1] + start;
+        uint32_t first, end;
+        ot_wave_range(count, w, first, end);
+#pragma unroll
+        for (int j = 0; j < OT_ITEMS; ++j) {
+            const uint32_t i = first + j * 64u + lane;
+            const bool valid = i < end;
+            key[j] = valid ? k1[i] : 0xFFFFFFFFu;
+            val[j] = valid ? v1[i] : 0u;
+        }
+        (void)ot_local_pass<LB>(key, val, first, end, bias, 0, m0, wcnt, loff, s_tmp, skeys, svals, tid);
+#pragma unroll
+        for (int j = 0; j < OT_ITEMS; ++j) {
+            const uint32_t i = first + j * 64u + lane;
+            if (i < end) { key[j] = skeys[i]; val[j] = svals[i]; }
+        }
+        (void)ot_local_pass<LB>(key, val, first, end, bias, w0, m1, wcnt, loff, s_tmp, skeys, svals, tid);      // (its first barrier stands between the reads above and its writes)
+        uint32_t* k0 = bufs.k[0] + start; uint32_t* v0 = bufs.v[0] + start;
+        for (uint32_t l = tid; l < count; l += OT_THREADS) { k0[l] = skeys[l]; v0[l] = svals[l]; }
+        return;
+    }
+    // ---- the bucket does not fit: two LSD passes through global memory, chunk by chunk ----
+    if (tid < (uint32_t)LB) { s_run[0][tid] = 0u; s_run[1][tid] = 0u; }
+    __syncthreads();
+    {
+        const uint32_t* k1 = bufs.k[1] + start;
+        for (uint32_t i = tid; i < count; i += OT_THREADS) {
+            const uint32_t k = k1[i] - bias;
+            atomicAdd(&s_run[0][k & m0], 1u);
+            atomicAdd(&s_run[1][(k >> w0) & m1], 1u);
+        }
+    }
+    __syncthreads();
+    {
+        const bool mine = tid < (uint32_t)LB;
+        const uint32_t a = mine ? s_run[0][tid] : 0u, b = mine ? s_run[1][tid] : 0u;
+        const uint32_t ea = digit_excl_scan<OT_THREADS, LB>(a, s_tmp, tid);
+        const uint32_t eb = digit_excl_scan<OT_THREADS, LB>(b, s_tmp, tid);
+        if (mine) { s_run[0][tid] = ea; s_run[1][tid] = eb; }      // (every thread its own words)
+    }
+    __syncthreads();
+    for (int p = 0; p < 2; ++p) {
+        const uint32_t* kin = bufs.k[p + 1] + start; const uint32_t* vin = bufs.v[p + 1] + start;
+        uint32_t* kout = bufs.k[p == 0 ? 2 : 0] + start; uint32_t* vout = bufs.v[p == 0 ? 2 : 0] + start;
+        const int shift = p == 0 ? 0 : w0;
+        const uint32_t mask = p == 0 ? m0 : m1;
+        for (uint32_t c0 = 0; c0 < count; c0 += OT_TILE) {       // uniform
+            const uint32_t cc = min(OT_TILE, count - c0);
+            uint32_t first, end;
+            ot_wave_range(cc, w, first, end);
+#pragma unroll
+            for (int j = 0; j < OT_ITEMS; ++j) {
+                const uint32_t i = first + j * 64u + lane;
+                const bool valid = i < end;
+                key[j] = valid ? kin[c0 + i] : 0xFFFFFFFFu;
+                val[j] = valid ? vin[c0 + i] : 0u;
+            }
+            const uint32_t cnt = ot_local_pass<LB>(key, val, first, end, bias, shift, mask, wcnt, loff, s_tmp, skeys, svals, tid);
+            if (tid < (uint32_t)LB) { gpos[tid] = s_run[p][tid]; s_run[p][tid] += cnt; }      // the chunks come in order: digit d's keys of this chunk follow those of the chunks before
+            __syncthreads();
+            for (uint32_t l = tid; l < cc; l += OT_THREADS) {
+                const uint32_t k = skeys[l];
+                const uint32_t d = ((k - bias) >> shift) & mask;
+                const uint32_t o = gpos[d] + (l - loff[d]);
+                if (o >= count) { __hip_atomic_store(err, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); continue; }      // the keys changed under the sort
+                kout[o] = k; vout[o] = svals[l];
+            }
+            __syncthreads();                                      // the chunk's LDS is free again
+        }
+        __syncthreads();                                          // the pass's stores are visible to the whole workgroup before the next pass loads them
+    }
+}
+
 hipError_t sort_scratch_reserve(hipStream_t st, SortScratch& s, size_t n) {
     hipError_t e;
     if (s.cap < n) {
@@ -561,6 +763,11 @@ hipError_t sort_scratch_reserve(hipStream_t st, SortScratch& s, size_t n) {
         if (const char* e0 = getenv("GS4D_TEST_EPOCH0")) s.epoch = (uint32_t)strtoul(e0, nullptr, 0);
     }
     if (!s.totals) { if ((e = hipMalloc(&s.totals, 256 * 4)) != hipSuccess) return e; if ((e = hipMemsetAsync(s.totals, 0, 1024, st)) != hipSuccess) return e; }
+    if (!s.fb) {      // the top-digit report words: pinned + mapped, like the draws' verdict words
+        if ((e = hipHostMalloc((void**)&s.fb, 4 * 4, hipHostMallocMapped)) != hipSuccess) { s.fb = nullptr; return e; }
+        s.fb[0] = s.fb[1] = s.fb[2] = s.fb[3] = 0u;
+        if ((e = hipHostGetDevicePointer((void**)&s.fb_dev, s.fb, 0)) != hipSuccess) { (void)hipHostFree(s.fb); s.fb = s.fb_dev = nullptr; return e; }
+    }
     return hipSuccess;
 }
 
@@ -568,6 +775,7 @@ void sort_scratch_free(SortScratch& s) {
     if (s.keys2) (void)hipFree(s.keys2);
     if (s.hist) (void)hipFree(s.hist);
     if (s.totals) (void)hipFree(s.totals);
+    if (s.fb) (void)hipHostFree(s.fb);
     s = SortScratch();
 }
 
@@ -582,8 +790,24 @@ uint32_t* sort_hist_slot(hipStream_t st, SortScratch& s, size_t n_hint, hipError
     return s.hist + (s.flip ? OS_SLOT_WORDS : 0);
 }
 
+// what a sort executes: LSD digit rows counted (OS_MAX_PASSES: the plain plan), the top digit's shift (-1: not counted), and whether it is the hybrid
+struct OsPlan { int rows = OS_MAX_PASSES; int top = -1; bool hybrid = false; };
+static uint32_t os_tail_cap(const SortScratch& s) { return std::min<uint32_t>(std::max<uint32_t>(s.tail_cap, 1u), OT_TILE); }
+static OsPlan os_plan(const SortScratch& s, size_t n, int key_bits) {
+    OsPlan p;
+    const bool eligible = s.hybrid_knob != 0 && key_bits >= 19 && key_bits <= 27 && s.atomic_rank && s.rank_knob != 1 && !s.rb_knob && !s.shape_knob && s.fb &&
+                          n >= 2 && (s.hybrid_knob == 1 || n >= OS_HYBRID_MIN_N);
+    if (!eligible) return p;
+    p.top = key_bits - 9;
+    // the latest report the host has seen (no wait: a wrong guess costs slow sorts, never a wrong result)
+    const bool crowded = __atomic_load_n(&s.fb[2], __ATOMIC_RELAXED) != 0u && __atomic_load_n(&s.fb[0], __ATOMIC_RELAXED) > os_tail_cap(s);
+    if (crowded) p.rows = sort_plan_passes(key_bits, sort_plan_rb(s, n, key_bits));      // three LSD rows, the top digit beside them
+    else { p.rows = 0; p.hybrid = true; }
+    return p;
+}
+
 template <int THREADS, int ITEMS, bool ATOMIC_RANK, int RB>
-static hipError_t onesweep(hipStream_t st, SortScratch& s, uint32_t* keys, uint32_t* vals, size_t n, const uint32_t* n_dev, int passes, bool have_hist, bool identity_vals) {
+static hipError_t onesweep(hipStream_t st, SortScratch& s, uint32_t* keys, uint32_t* vals, size_t n, const uint32_t* n_dev, int passes, bool have_hist, bool identity_vals, const OsPlan& plan) {
     const uint32_t tile_keys = THREADS * ITEMS;
     const uint32_t tiles = (uint32_t)((n + tile_keys - 1) / tile_keys);
     // persistent workgroups: as many as the device holds at once (asked of the runtime once per scratch and kernel instance: the scratch's context has
@@ -610,7 +834,8 @@ static hipError_t onesweep(hipStream_t st, SortScratch& s, uint32_t* keys, uint3
     if (!have_hist) {
         if (s.hist_pending) { if ((e = hipMemsetAsync(ghist, 0, OS_SLOT_WORDS * 4, st)) != hipSuccess) return e; }   // someone else's histogram sits in the slot
         const uint32_t hist_blocks = (uint32_t)std::min<size_t>((n / 16 + 255) / 256 + 1, 256);          // few workgroups: each flushes 256 global atomics per pass
-        k_os_hist<<<dim3(hist_blocks), dim3(256), 0, st>>>(keys, (uint32_t)n, n_dev, passes, RB, ghist);
+        k_os_hist<<<dim3(hist_blocks), dim3(256), 0, st>>>(keys, (uint32_t)n, n_dev, plan.rows < OS_MAX_PASSES ? plan.rows : passes, RB, plan.top, ghist);
+        ++s.stat_launches;
     }
     s.hist_pending = false;
     s.flip ^= 1;
@@ -631,7 +856,9 @@ static hipError_t onesweep(hipStream_t st, SortScratch& s, uint32_t* keys, uint3
     b.k[0] = keys; b.v[0] = vals;
     b.k[1] = s.keys2; b.v[1] = s.vals2;
     b.k[2] = s.keys2 + s.cap; b.v[2] = s.vals2 + s.cap;
-    for (int p = 0; p < passes; ++p) {
+    // the hybrid: ONE launch of the pass kernel, on the top digit (the row the producer counted), then the tail; a fallback sort: the report behind its passes
+    const int launches = plan.hybrid ? 1 : passes;
+    for (int p = 0; p < launches; ++p) {
         ++s.epoch;
         if ((s.epoch & 0x3FFFFu) == 0u) {    // the 18-bit tile-level epoch wraps: forget every old word
             if ((e = hipMemsetAsync(status, 0, (s.hist_cap - 2 * OS_SLOT_WORDS) * 4, st)) != hipSuccess) return e;
@@ -639,8 +866,19 @@ static hipError_t onesweep(hipStream_t st, SortScratch& s, uint32_t* keys, uint3
         }
         k_os_pass<THREADS, ITEMS, ATOMIC_RANK, RB><<<dim3(grid), dim3(THREADS), 0, st>>>(b, (uint32_t)n, n_dev, p, passes, ghist, ghist_other, status, acc_base + (s.acc_flip ? acc_words : 0), acc_base + (s.acc_flip ? 0 : acc_words), (uint32_t)cap_groups, (uint32_t)acc_words,
                                                                          s.epoch & 0x3FFFFFFFu,
-                                                                         s.err ? s.err : s.totals, s.totals + 64 + (s.acc_flip ? 1 : 0), s.totals + 64 + (s.acc_flip ? 0 : 1), bias, identity_vals ? 1 : 0, (stampf && p == stamp_pass) ? stamps : nullptr);
+                                                                         s.err ? s.err : s.totals, s.totals + 64 + (s.acc_flip ? 1 : 0), s.totals + 64 + (s.acc_flip ? 0 : 1), bias, identity_vals ? 1 : 0,
+                                                                         plan.hybrid ? plan.top : RB * p, plan.hybrid ? OS_TOP_ROW : p, plan.hybrid ? 1 : 0, (stampf && p == stamp_pass) ? stamps : nullptr);
         s.acc_flip ^= 1;
+        ++s.stat_launches;
+    }
+    if (plan.hybrid) {
+        if (RB != 9 || n_dev) return hipErrorInvalidValue;
+        if (plan.top <= 16) k_os_tail<256><<<dim3(OT_BINS), dim3(OT_THREADS), 0, st>>>(b, (uint32_t)n, ghist, bias, plan.top, os_tail_cap(s), s.fb_dev, s.err ? s.err : s.totals);      // local digits of <= 8 bits
+        else k_os_tail<512><<<dim3(OT_BINS), dim3(OT_THREADS), 0, st>>>(b, (uint32_t)n, ghist, bias, plan.top, os_tail_cap(s), s.fb_dev, s.err ? s.err : s.totals);
+        ++s.stat_launches; ++s.stat_hybrid;
+    } else if (plan.top >= 0) {
+        k_os_top_stats<<<dim3(1), dim3(OT_THREADS), 0, st>>>(ghist, os_tail_cap(s), s.fb_dev);
+        ++s.stat_launches;
     }
     if (stampf && stamps) {   // tuning aid: dump per-tile wall-clock stamps (100 MHz) of one pass
         (void)hipStreamSynchronize(st);
@@ -666,6 +904,12 @@ int sort_plan_rb(const SortScratch& s, size_t n, int key_bits) {
 }
 int sort_plan_passes(int key_bits, int rb) { return std::min(OS_MAX_PASSES, std::max(2, (key_bits + rb - 1) / rb)); }      // an even number of executed passes always exists (see os_schedule)
 
+void sort_plan_hist(SortScratch& s, size_t n, int key_bits) {
+    const OsPlan p = os_plan(s, n, key_bits);
+    s.hist_rb = sort_plan_rb(s, n, key_bits);
+    s.hist_rows = p.rows; s.hist_top = p.top; s.hist_hybrid = p.hybrid;
+}
+
 hipError_t radix_sort_pairs(hipStream_t st, SortScratch& s, uint32_t* keys, uint32_t* vals, size_t n, const uint32_t* n_dev, int key_bits, bool have_hist, bool identity_vals) {
     if (n <= 1) { if (n == 1 && identity_vals) return hipMemsetAsync(vals, 0, 4, st); return hipSuccess; }      // radix_sort.hpp:260
     if (n >= (1ull << 32) - 1) return hipErrorInvalidValue;
@@ -675,6 +919,12 @@ hipError_t radix_sort_pairs(hipStream_t st, SortScratch& s, uint32_t* keys, uint
     const int rb = have_hist ? s.hist_rb : sort_plan_rb(s, n, key_bits);
     if (rb != 8 && rb != 9) return hipErrorInvalidValue;
     const int passes = sort_plan_passes(key_bits, rb);
+    // the plan: the producer's (it counted the rows of that plan), or this call's own when k_os_hist is about to count
+    OsPlan plan;
+    if (have_hist) { plan.rows = s.hist_rows; plan.top = s.hist_top; plan.hybrid = s.hist_hybrid; }
+    else if (!n_dev) plan = os_plan(s, n, key_bits);
+    s.hist_rows = OS_MAX_PASSES; s.hist_top = -1; s.hist_hybrid = false;       // (of the pending histogram, which this sort consumes)
+    if (plan.hybrid) return n_dev ? hipErrorInvalidValue : onesweep<512, 12, true, 9>(st, s, keys, vals, n, nullptr, passes, have_hist, identity_vals, plan);
     // 8192-key tiles of 512 threads x 16 keys for every size.  Rounds 2-3 ran sorts of <= 1.5M keys as 1024 x 8 (the same 12.7 us per pass alone at 10^6 keys;
     // 2-3 % more frames per second with the frame lanes overlapping, as the frame then was).  With this round's frame (staged tile lists: two launches fewer,
     // a longer projection kernel) the 512-thread form wins by 3 % at C2 — 0.0980-0.0984 against 0.1010-0.1017 ms/frame, three alternating runs each; 512 x 12:
@@ -685,8 +935,8 @@ hipError_t radix_sort_pairs(hipStream_t st, SortScratch& s, uint32_t* keys, uint
     (void)n;
     if (rb == 9 && shape == 5 && !s.shape_knob) shape = 6;
     const bool atomic_rank = s.rank_knob ? s.rank_knob == 2 : s.atomic_rank;
-#define GS4D_OS8(T, I) (atomic_rank ? onesweep<T, I, true, 8>(st, s, keys, vals, n, n_dev, passes, have_hist, identity_vals) : onesweep<T, I, false, 8>(st, s, keys, vals, n, n_dev, passes, have_hist, identity_vals))
-#define GS4D_OS(T, I) (rb == 9 ? (atomic_rank ? onesweep<T, I, true, 9>(st, s, keys, vals, n, n_dev, passes, have_hist, identity_vals) : onesweep<T, I, false, 9>(st, s, keys, vals, n, n_dev, passes, have_hist, identity_vals)) : GS4D_OS8(T, I))
+#define GS4D_OS8(T, I) (atomic_rank ? onesweep<T, I, true, 8>(st, s, keys, vals, n, n_dev, passes, have_hist, identity_vals, plan) : onesweep<T, I, false, 8>(st, s, keys, vals, n, n_dev, passes, have_hist, identity_vals, plan))
+#define GS4D_OS(T, I) (rb == 9 ? (atomic_rank ? onesweep<T, I, true, 9>(st, s, keys, vals, n, n_dev, passes, have_hist, identity_vals, plan) : onesweep<T, I, false, 9>(st, s, keys, vals, n, n_dev, passes, have_hist, identity_vals, plan)) : GS4D_OS8(T, I))
     switch (shape) {
     case 1: return rb == 8 ? GS4D_OS8(256, 8) : hipErrorInvalidValue;
     case 2: return GS4D_OS(512, 8);
