@@ -29,6 +29,7 @@ EDIT_SET, EDIT_MUL, EDIT_LERP, EDIT_COPY = 0, 1, 2, 3      # gs4d_colour_edit.op
 CQ_BOX, CQ_SPHERE, CQ_SCREEN, CQ_FRAME, CQ_SKIP_HIDDEN, CQ_SKIP_DEAD = 1, 2, 4, 8, 16, 32      # gs4d_centre_query.tests
 CQ_ADD, CQ_REMOVE = 0, 1                                   # gs4d_centre_query.op
 MS_SKIP_HIDDEN, MS_SKIP_DEAD = 1, 2                        # gs4d_measure_query.flags
+XS_PIVOT, XS_PIVOT_MEASURE = 1, 2                          # gs4d_selection_xf.flags
 TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
@@ -103,6 +104,7 @@ def _load():
         "gs4d_measure_records": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_build_records": (i32, [vp, vp, sz, u32]),
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
+        "gs4d_transform_selected": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -131,6 +133,7 @@ def _load():
         "gs4d_host_count_centres": (None, [sz, vp, vp, i32, i32, vp, vp]),
         "gs4d_host_measure_records": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_measure_centre": (i32, [vp, vp]),
+        "gs4d_host_transform_selected": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_frame_box": (None, [vp, vp, vp, f32, i32, i32, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
@@ -557,6 +560,61 @@ def measure_records_host(records, t=0.0, stats=None, skip_hidden=False, skip_dea
     out = Measure()
     _lib.gs4d_host_measure_records(n, _ptr(rec), C.byref(q), _ptr(st) if st is not None else None, _ptr(k) if st is not None else None, C.byref(out))
     return out
+
+
+class SelectionXf(C.Structure):
+    """gs4d_selection_xf (include/gs4d.h): the map, the pivot and the pivot flag of a gs4d_transform_selected call; 96 bytes."""
+    _fields_ = [("xf", Affine4), ("pivot", C.c_float * 3), ("flags", C.c_uint32)]
+
+
+def selection_xf(xf, pivot=None, measure=False):
+    """one gs4d_selection_xf (SelectionXf): xf 20 float32 (affine4) or an Affine4; pivot: a 3-tuple, the point the map is applied about
+    (XS_PIVOT); measure=True: the pivot is the centre of a Measure the call is given (XS_PIVOT_MEASURE).  Passing both is an error."""
+    if pivot is not None and measure:
+        raise TypeError("selection_xf: pivot and measure exclude each other")
+    rows = _affine_rows(xf)
+    if rows.shape[0] != 1:
+        raise ValueError("selection_xf: expected one row of 20 float32 (l[16], o[4])")
+    x = SelectionXf()
+    x.xf = Affine4.from_buffer_copy(rows[0].tobytes())
+    if pivot is not None:
+        c = _f32(pivot).ravel()
+        if c.size != 3:
+            raise ValueError("selection_xf: pivot is a 3-tuple")
+        # (the bits as they are: a float32 NaN keeps its payload)
+        C.memmove(C.addressof(x) + SelectionXf.pivot.offset, _ptr(c), 12)
+        x.flags = XS_PIVOT
+    elif measure:
+        x.flags = XS_PIVOT_MEASURE
+    return x
+
+
+def transform_selected_host(records, xf, stats=None, pivot=None, measure=None, n=None, **rule):
+    """gs4d_host_transform_selected, the definition of Context.transform_selected: a copy of records [total, 24] with the selected ones of the
+    first n (default: all) moved under xf (20 float32, an Affine4, or a SelectionXf, which then carries pivot and flag itself) about the pivot.
+    stats: a RECORD_STAT array of n rows (the rule keywords of compact_records select by it) or None: every record; pivot: a 3-tuple;
+    measure: a Measure, whose centre is the pivot.  Passing both is an error."""
+    rec = np.array(_f32(records).reshape(-1, 24), copy=True)
+    n = rec.shape[0] if n is None else int(n)
+    if n > rec.shape[0]:
+        raise ValueError("transform_selected_host: fewer than n records")
+    if stats is None and rule:
+        raise TypeError("transform_selected_host: a rule without stats")
+    st = None if stats is None else np.ascontiguousarray(stats)
+    if st is not None and (st.dtype.itemsize != 16 or st.ndim != 1 or st.shape[0] < n):
+        raise ValueError("transform_selected_host: stats must be at least n rows of 16 bytes")
+    if isinstance(xf, SelectionXf):
+        if pivot is not None:
+            raise TypeError("transform_selected_host: a SelectionXf carries its own pivot")
+        x = xf
+    else:
+        x = selection_xf(xf, pivot, measure is not None)
+    if x.flags == XS_PIVOT_MEASURE and measure is None:
+        raise TypeError("transform_selected_host: XS_PIVOT_MEASURE needs measure")
+    k = _keep_rule(**rule)
+    _lib.gs4d_host_transform_selected(n, _ptr(rec), _ptr(st) if st is not None else None, _ptr(k) if st is not None else None, C.byref(x),
+                                      C.byref(measure) if measure is not None else None)
+    return rec
 
 
 def frame_box(lo, hi, orientation, fov_deg, width, height):
@@ -1195,6 +1253,27 @@ class Context:
             if own:
                 self.delete(xf)
         return dst
+
+    # moving a selection: the selected records under a 4D affine map about a pivot, in place
+    def transform_selected(self, data, n, xf, stats=None, pivot=None, measure=None, **rule):
+        """gs4d_transform_selected: the selected ones of the first n 96-byte records of `data` <- themselves under xf (20 float32 as affine4 gives
+        them, an Affine4, or a SelectionXf, which then carries pivot and flag itself), in place.  stats: a record_stats table (count_ids,
+        count_centres, set_record_stats) whose row i selects record i by compact_records' rule keywords; None: every record.  pivot: a 3-tuple,
+        the point the map is applied about; measure: the buffer a measure_records call wrote, whose centre is the pivot — computed on the device,
+        nothing is read back.  Passing both is an error.  With the bits of transform_selected_host.  A full write of data: the next draw rebuilds
+        its SoA shadow.  Per frame: (shade_sh), (edit), transform_selected, keygen, sort, draw.  Asynchronous."""
+        if stats is None and rule:
+            raise TypeError("transform_selected: a rule without stats")
+        if pivot is not None and measure is not None:
+            raise TypeError("transform_selected: pivot and measure exclude each other")
+        if isinstance(xf, SelectionXf):
+            if pivot is not None:
+                raise TypeError("transform_selected: a SelectionXf carries its own pivot")
+            x = xf
+        else:
+            x = selection_xf(xf, pivot, measure is not None)
+        k = _keep_rule(**rule) if stats is not None else None
+        self._chk(_lib.gs4d_transform_selected(self._h, int(data), int(n), C.byref(x), int(stats or 0), _ptr(k) if k is not None else None, int(measure or 0)))
 
     def write_tensor(self, buf, tensor, offset=0):
         """A contiguous device tensor copied into the buffer `buf` at byte `offset`, with no host copy and no host synchronisation: the

@@ -1614,6 +1614,44 @@ int gs4d_transform_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf xf, siz
         });
 }
 
+// ---- a selection under an affine map about a pivot, in place ----
+int gs4d_transform_selected(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_selection_xf* xf, gs4d_buf stats, const gs4d_keep_rule* rule, gs4d_buf measure) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("transform_selected: ") + msg).c_str()); };
+    if (!xf) return bad("xf == NULL");
+    const gs4d_selection_xf x = *xf;
+    if (x.flags != 0u && x.flags != (uint32_t)GS4D_XS_PIVOT && x.flags != (uint32_t)GS4D_XS_PIVOT_MEASURE) return bad("flags must be 0, GS4D_XS_PIVOT or GS4D_XS_PIVOT_MEASURE");
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    if ((stats != 0) != (rule != nullptr)) return bad("stats and rule are given together or not at all");
+    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
+    const bool measured = x.flags == (uint32_t)GS4D_XS_PIVOT_MEASURE;
+    if (measured && measure == 0) return bad("GS4D_XS_PIVOT_MEASURE needs measure");
+    if (!measured && measure != 0) return bad("measure must be 0 unless the flag is GS4D_XS_PIVOT_MEASURE");
+    const gs4d_buf names[3] = { data, stats, measure };
+    Buffer* D = getbuf(c, data);
+    if (!D) return bad("data is not a live buffer");
+    if (const int wrong = check_record_names(c, names, 3)) return bad(wrong == 1 ? "bad buffer name" : "data, stats and measure must be different buffers");
+    Buffer* S = getbuf(c, stats); Buffer* M = getbuf(c, measure);
+    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
+    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (M && M->bytes < sizeof(gs4d_measure)) return bad("measure holds fewer than 96 bytes");
+    if (n == 0) return GS4D_OK;
+    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
+    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
+    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    // The table and the measurement are read (gs4d_edit_colours' table; an ordinary read buffer, behind the kernels that wrote it), data is written as
+    // gs4d_transform_records writes its dst: a full write whatever the table selects — position, mu_t and sig move, so the shadow, the bounding box
+    // and the key bounds of data are all stale.  The shadow is not patched: the next draw or gs4d_keygen rebuilds it.
+    return queue_on_lane(c, { S, M }, { D },
+        [&](Lane&) { return S ? scan_reserve(c, *S) : (int)GS4D_OK; },
+        [&](Lane& L) {
+            if (S) { int rc = scan_begin(c, L, *S); if (rc) return rc; }
+            HIPCHK(c, launch_transform_selected(L.s, D->d, n, x, S ? (const gs4d_record_stat*)S->d : nullptr, k, M ? (const gs4d_measure*)M->d : nullptr));
+            return S ? scan_end(c, L, *S) : (int)GS4D_OK;
+        });
+}
+
 // ---- draw ----
 static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     (void)hipSetDevice(c->device);

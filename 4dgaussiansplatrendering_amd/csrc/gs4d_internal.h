@@ -476,6 +476,14 @@ hipError_t launch_build_records(hipStream_t st, int form, const BuildParams& p, 
 constexpr uint32_t TRANSFORM_TILE = 256;
 hipError_t launch_transform_records(hipStream_t st, const void* src, size_t n, const gs4d_affine4* xf, size_t m, void* dst);
 
+// ---- transform_selected.hip ----
+// gs4d_transform_selected (gs4d.h): the selected ones of the first n 96-byte records of data <- themselves under xf (validated) — stats:
+// the table whose row i selects record i by `rule` (keep_row), or null: every record; measure: the measurement GS4D_XS_PIVOT_MEASURE takes the pivot
+// from, else null.  One workgroup per XFSEL_TILE records; nothing but the selected records < n is written.
+constexpr uint32_t XFSEL_TILE = 256;
+hipError_t launch_transform_selected(hipStream_t st, void* data, size_t n, const gs4d_selection_xf& xf, const gs4d_record_stat* stats, const KeepRule& rule,
+                                     const gs4d_measure* measure);
+
 // ---- cut.hip ----
 // gs4d_stat_cut (gs4d.h): a radix select over one field of a statistics table, most significant digit first — per digit one histogram
 // launch and one pick launch on `st`, no workgroup waits for another.

@@ -42,5 +42,38 @@ GS4D_XF_HD inline void record(const float l[16], const float o[4], const float i
     }
 }
 
+// gs4d_transform_selected (include/gs4d.h): out (24 floats) <- the record in (24 floats) under (l[16], o[4]) about the pivot c[3];
+// in and out must not overlap.  Without a pivot it is record().  With one the spatial mean goes through record() as p - c and c is added to
+// what comes out, both always, also for c == 0 (a -0 coordinate may become +0); mu_t, rgba and Sigma do not see the pivot.  csrc/transform_selected.hip
+// evaluates it on the device; tests/transform_selected_check.cpp compiles it for the CPU against gs4d_host_transform_selected — the definition.
+GS4D_XF_HD inline void record_about(const float l[16], const float o[4], bool pivot, const float c[3], const float in[24], float out[24]) {
+    if (!pivot) { record(l, o, in, out); return; }
+    float q[24];
+    GS4D_XF_UNROLL
+    for (int a = 0; a < 3; ++a) q[a] = in[a] - c[a];
+    GS4D_XF_UNROLL
+    for (int k = 3; k < 24; ++k) q[k] = in[k];
+    record(l, o, q, out);
+    GS4D_XF_UNROLL
+    for (int r = 0; r < 3; ++r) out[r] = out[r] + c[r];
+}
+
+// The centre of a measurement (the fields of a gs4d_measure) as gs4d_host_measure_centre of host/gs4d_host.cpp gives it — per axis, in double
+// precision, lo + (hi - lo) * (cell_sum / (count * 2^20)), rounded to float; count == 0: (0, 0, 0).  Every operation is rounded on its own (build
+// without contraction); double add, multiply, divide and the conversion from a 64-bit integer are correctly rounded on the device as on the host, so
+// the bits are the host's.  The fields are data: non-finite ends and a huge cell_sum give what the line gives.
+GS4D_XF_HD inline void measure_centre(unsigned int count, const float lo[3], const float hi[3], const unsigned long long cell_sum[3], float c[3]) {
+    GS4D_XF_UNROLL
+    for (int a = 0; a < 3; ++a) {
+        if (count == 0u) { c[a] = 0.0f; continue; }
+        const double l = lo[a], h = hi[a];
+        const double span = h - l;
+        const double cells = (double)count * 1048576.0;
+        const double frac = (double)cell_sum[a] / cells;
+        const double step = span * frac;
+        c[a] = (float)(l + step);
+    }
+}
+
 } // namespace gs4d_transform
 #endif

@@ -526,6 +526,34 @@ int gs4d_host_measure_centre(const gs4d_measure* m, float centre3[3]) {
     return 1;
 }
 
+// The definition of gs4d_transform_selected (gs4d.h), in place: the selection by the rule of gs4d_edit_colours; the pivot given, or
+// gs4d_host_measure_centre of the measurement; a selected record is gs4d_host_transform_records of itself with the pivot taken off its spatial mean
+// before and put back after — both always when there is a pivot flag (this file is built with -ffp-contract=off: each is one rounding).  A call the
+// device would refuse for its xf changes nothing.
+void gs4d_host_transform_selected(size_t n, float* rec, const gs4d_record_stat* stats, const gs4d_keep_rule* rule, const gs4d_selection_xf* xf,
+                                  const gs4d_measure* measure) {
+    if (!xf || xf->flags > (uint32_t)GS4D_XS_PIVOT_MEASURE) return;
+    if (xf->flags == (uint32_t)GS4D_XS_PIVOT_MEASURE && !measure) return;
+    if (stats && !rule) return;
+    const bool pivot = xf->flags != 0u;
+    float c[3] = { xf->pivot[0], xf->pivot[1], xf->pivot[2] };
+    if (xf->flags == (uint32_t)GS4D_XS_PIVOT_MEASURE) gs4d_host_measure_centre(measure, c);
+    const bool invert = stats && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    for (size_t i = 0; i < n; ++i) {
+        if (stats) {
+            const gs4d_record_stat& s = stats[i];
+            if ((s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) == invert) continue;
+        }
+        float* const p = rec + 24 * i;
+        float q[24], out[24];
+        std::memcpy(q, p, sizeof q);
+        if (pivot) for (int a = 0; a < 3; ++a) q[a] = p[a] - c[a];
+        gs4d_host_transform_records(1, q, &xf->xf, out);
+        if (pivot) for (int r = 0; r < 3; ++r) out[r] = out[r] + c[r];
+        std::memcpy(p, out, sizeof out);
+    }
+}
+
 // "Frame selection" (gs4d.h): the bounding sphere of the box inside the narrower half-angle of gs4d_host_perspective's frustum — th is that
 // function's own float tangent, aspect its own float quotient — seen along `orientation`.  In double.
 void gs4d_host_frame_box(const float lo[3], const float hi[3], const float orientation[3], float fov_deg, int width, int height, float eye3[3]) {

@@ -15,13 +15,13 @@ endif
 # keygen/sort and preprocess must round exactly like the CPU expressions they are checked against
 STRICT   := -ffp-contract=off
 
-# the build mode is a prerequisite of every object: switching between `make lib`, `make lib TUNING=1`, `make lib COUNT_IDS_PLAIN=1`, `make lib BUILD_PLAIN=1` and `make lib TRANSFORM_STAGED_LOAD=1` rebuilds all of them
-FLAGSTAMP := $(CSRC)/.flags.$(if $(TUNING),tuning,release)$(if $(COUNT_IDS_PLAIN),-plain)$(if $(BUILD_PLAIN),-buildplain)$(if $(TRANSFORM_STAGED_LOAD),-transformstagedload)
+# the build mode is a prerequisite of every object: switching between `make lib`, `make lib TUNING=1`, `make lib COUNT_IDS_PLAIN=1`, `make lib BUILD_PLAIN=1`, `make lib TRANSFORM_STAGED_LOAD=1` and `make lib XFSEL_PLAIN=1` rebuilds all of them
+FLAGSTAMP := $(CSRC)/.flags.$(if $(TUNING),tuning,release)$(if $(COUNT_IDS_PLAIN),-plain)$(if $(BUILD_PLAIN),-buildplain)$(if $(TRANSFORM_STAGED_LOAD),-transformstagedload)$(if $(XFSEL_PLAIN),-xfselplain)
 $(FLAGSTAMP):
 	rm -f $(CSRC)/.flags.*
 	touch $@
 
-OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/centres.o $(CSRC)/measure.o $(HOST)/gs4d_host.o
+OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/centres.o $(CSRC)/measure.o $(HOST)/gs4d_host.o
 
 .PHONY: all lib oracle ref refscene refdraw refgl clean demo sweep
 all: lib oracle demo sweep
@@ -64,6 +64,9 @@ $(CSRC)/build.o: $(CSRC)/build.hip $(CSRC)/build_record.h $(CSRC)/gs4d_internal.
 # make TRANSFORM_STAGED_LOAD=1: gs4d_transform_records with the input staged in LDS like the output, instead of every thread loading its own record (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/transform.o: $(CSRC)/transform.hip $(CSRC)/transform_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(TRANSFORM_STAGED_LOAD),-DGS4D_TRANSFORM_STAGED_LOAD) -c $< -o $@
+# make XFSEL_PLAIN=1: gs4d_transform_selected with every selected thread storing its own record, without the LDS staging and the wave masks (the measurement of DESIGN.md §4; never the shipped build)
+$(CSRC)/transform_selected.o: $(CSRC)/transform_selected.hip $(CSRC)/transform_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(XFSEL_PLAIN),-DGS4D_XFSEL_PLAIN) -c $< -o $@
 # make COUNT_IDS_PLAIN=1: gs4d_count_ids without its in-wave aggregation (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(COUNT_IDS_PLAIN),-DGS4D_COUNT_IDS_PLAIN) -c $< -o $@

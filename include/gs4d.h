@@ -780,7 +780,7 @@ GS4D_API int gs4d_count_centres(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs
  * planes of each shadow layout — reading a shadow is out of scope here.
  *
  * Out of scope: weighted (alpha or wsum) centroids, second moments and oriented boxes; 72-byte quad vertices and 48-byte 2D records; building a
- * gs4d_affine4 row on the device; transforming only the selected records in place (this call supplies that pivot). */
+ * gs4d_affine4 row on the device.  (Transforming only the selected records in place, about this call's centre, is gs4d_transform_selected.) */
 enum { GS4D_MS_SKIP_HIDDEN = 1, GS4D_MS_SKIP_DEAD = 2 };
 typedef struct gs4d_measure_query {
     float    t;            /* the time the centres are taken at      */
@@ -799,6 +799,70 @@ typedef struct gs4d_measure {
 } gs4d_measure;            /* 96 bytes */
 GS4D_API int gs4d_measure_records(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_measure_query* query,
                                   gs4d_buf stats /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff stats == 0 */, gs4d_buf out);
+
+/* ---- moving a selection: the selected records under a 4D affine map about a pivot, in place (no reference counterpart) ----
+ * The step between the two calls above and gs4d_transform_records: grab what a statistics table selects and move, rotate or scale it where it
+ * lies — a gizmo drag on part of a set — without reading a record or a measurement back.  gs4d_transform_records places a whole set into another
+ * buffer and refuses src == dst; gs4d_transform_selected rewrites the selected records of `data` themselves, about a pivot the caller gives or
+ * about the centre of a gs4d_measure that gs4d_measure_records has left in a buffer.  gs4d_host_transform_selected is this text as code.
+ *
+ * Selected.  Exactly the predicate of gs4d_edit_colours and gs4d_measure_records: stats == 0 selects every record i < n; otherwise record i is
+ * selected iff row i of the gs4d_record_stat table `stats` passes `rule`: (pixels >= min_pixels && wmax >= min_wmax && wsum >= min_wsum) != invert
+ * (GS4D_KEEP_INVERT).  There are no skip flags: hidden and dead records that are selected move with the rest, so an object stays whole.
+ *
+ * Pivot c.  flags == 0: there is no pivot.  GS4D_XS_PIVOT: c = pivot.  GS4D_XS_PIVOT_MEASURE: c is what gs4d_host_measure_centre gives for the 96
+ * bytes at offset 0 of `measure` — per axis, in double precision, lo + (hi - lo) * ((double)cell_sum / ((double)count * 1048576.0)), rounded to
+ * float; c = (0, 0, 0) when count == 0.  It is evaluated on the device, without contraction: double add, multiply, divide and the conversion from a
+ * 64-bit integer are correctly rounded there, so the bits equal the host's.  The bytes of `measure` are data: hostile values (NaN or infinite ends,
+ * a huge cell_sum) give what the line gives.
+ *
+ * The map.  All arithmetic is float32, round to nearest, no contraction, full products.  With l, o the fields of xf.xf, and p, S as in
+ * gs4d_transform_records:
+ *     q[a]  = pivot ? p[a] - c[a] : p[a]   (a = 0, 1, 2);     q[3] = p[3]
+ *     u[r]  = ((((l[r]*q[0]) + (l[4+r]*q[1])) + (l[8+r]*q[2])) + (l[12+r]*q[3])) + o[r]      r = 0..3
+ *     p'[r] = pivot ? u[r] + c[r] : u[r]   (r = 0, 1, 2);     p'[3] = u[3]
+ *     Sigma' = (L Sigma) L^T, rgba copied:  the text of gs4d_transform_records, all 16 elements, nothing mirrored.
+ * Without a pivot flag a selected record gets exactly the bits of gs4d_host_transform_records.  With a pivot flag the two extra operations are
+ * always performed, also for c = 0: a -0 coordinate can then become +0 — that follows from the lines above and is no exception to them.  A word
+ * that is a NaN on both sides may differ from the host's in sign and payload (the rule of gs4d_build_records).  Nothing depends on the order in
+ * which anything runs on the device.
+ *
+ * What is written.  Only the 96 bytes of the selected records < n.  A record that is not selected, every byte of data beyond record n - 1 and
+ * every byte of stats and measure are not written at all — which is more than keeping their bits.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: xf == NULL; a flags value other than 0, GS4D_XS_PIVOT or GS4D_XS_PIVOT_MEASURE;
+ * n > 0xFFFFFFFF; data not a live buffer or smaller than 96 n bytes; exactly one of stats / rule given; a rule with an unknown flag or reserved != 0;
+ * stats not a live buffer or smaller than 16 n bytes; GS4D_XS_PIVOT_MEASURE without a live `measure` of at least 96 bytes; measure != 0 without that
+ * flag; any two of the three buffers being the same buffer.  n == 0 with otherwise valid arguments is a no-op.  The map and the pivot are data:
+ * singular, non-finite and 1e30 rows give what the lines give.
+ *
+ * Ordering.  data is ordered as gs4d_transform_records orders its dst: draws that may still have to be run again from data are settled, and the
+ * kernel waits, on the device, for the lanes whose draws or key generation still read data or its shadow.  stats is ordered as gs4d_edit_colours
+ * orders its table: draws that add to it, issued before the call on any frame lane, are settled first, re-runs included; a draw issued afterwards
+ * that adds to it waits on the device until the kernel has read it.  measure is a buffer the call reads: the call orders itself, on the device,
+ * behind the gs4d_measure_records kernels that wrote it — no gs4d_finish and no read-back in between — and a later write of measure waits for this
+ * call.  A queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first.  The kernel is queued on the current frame lane;
+ * the call returns at once and starts no frame.  gs4d_buffer_invalidate hand-offs of all three buffers are honoured.
+ *
+ * The write counts as a full write of data, like gs4d_transform_records', whatever the table turns out to select: the buffer's version moves, what
+ * a sort index was sorted by is forgotten, and the next draw or gs4d_keygen rebuilds the SoA shadow once (gs4d_debug_shadow_builds goes up by
+ * exactly one per call followed by a draw).  The call order per frame is (shade) -> (edit) -> transform_selected -> keygen -> sort_pairs -> draw.
+ *
+ * The caller's other tables — the notes of gs4d_transform_records, for the selected rows only: time spans are to be recomputed when L touches
+ * time; SH tables are not rotated; the key-order note for a time scale still applies; statistics, spatial order and kept_index rows are
+ * unaffected, because no record moves in memory.
+ *
+ * Out of scope: patching the SoA shadow instead of rebuilding it; one transform per record; a time component of the pivot; weighted pivots;
+ * 72-byte quad vertices and 48-byte 2D records; duplicating a selection, which is gs4d_compact_records followed by gs4d_transform_records. */
+enum { GS4D_XS_PIVOT = 1, GS4D_XS_PIVOT_MEASURE = 2 };
+typedef struct gs4d_selection_xf {
+    gs4d_affine4 xf;      /* the map, as a row of gs4d_transform_records' table            */
+    float    pivot[3];    /* GS4D_XS_PIVOT: the pivot c; otherwise ignored                  */
+    uint32_t flags;       /* 0, GS4D_XS_PIVOT or GS4D_XS_PIVOT_MEASURE; anything else: GS4D_E_INVALID */
+} gs4d_selection_xf;      /* 96 bytes */
+GS4D_API int gs4d_transform_selected(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_selection_xf* xf,
+                                     gs4d_buf stats /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff stats == 0 */,
+                                     gs4d_buf measure /* GS4D_XS_PIVOT_MEASURE: a gs4d_measure at offset 0; otherwise 0 */);
 
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
@@ -874,6 +938,11 @@ GS4D_API void gs4d_host_measure_records(size_t n, const float* records24, const 
 /* The centroid of a measurement: lo + (hi - lo) * (cell_sum / (count * 2^20)) per axis, in double precision, rounded to float.  Returns 1, or 0
  * with centre3 = {0, 0, 0} when count == 0. */
 GS4D_API int  gs4d_host_measure_centre(const gs4d_measure* m, float centre3[3]);
+/* The definition of gs4d_transform_selected, in place on the n records of records24 (the text above its declaration): stats == NULL selects every
+ * record (rule is then ignored), else rule is not NULL; measure is read with GS4D_XS_PIVOT_MEASURE only.  A call the device would refuse for its xf
+ * (NULL, an unknown flags value, GS4D_XS_PIVOT_MEASURE without a measure) changes nothing. */
+GS4D_API void gs4d_host_transform_selected(size_t n, float* records24, const gs4d_record_stat* stats, const gs4d_keep_rule* rule,
+                                           const gs4d_selection_xf* xf, const gs4d_measure* measure);
 /* "Frame selection": the eye from which a camera of gs4d_host_look_at(eye, orientation, up) and gs4d_host_perspective(fov_deg, width, height, ..)
  * sees the whole box lo .. hi with its centre in the middle of the image.  The box's bounding sphere (centre (lo + hi) / 2, radius half the
  * diagonal; a degenerate box — a radius that is zero or not finite — gets radius 1) is fitted into the narrower of the projection's two
