@@ -30,6 +30,7 @@ CQ_BOX, CQ_SPHERE, CQ_SCREEN, CQ_FRAME, CQ_SKIP_HIDDEN, CQ_SKIP_DEAD = 1, 2, 4, 
 CQ_ADD, CQ_REMOVE = 0, 1                                   # gs4d_centre_query.op
 MS_SKIP_HIDDEN, MS_SKIP_DEAD = 1, 2                        # gs4d_measure_query.flags
 XS_PIVOT, XS_PIVOT_MEASURE = 1, 2                          # gs4d_selection_xf.flags
+NB_SKIP_HIDDEN, NB_SKIP_DEAD, NB_COUNT_SELF = 1, 2, 4      # gs4d_neighbour_query.flags
 TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
@@ -105,6 +106,7 @@ def _load():
         "gs4d_build_records": (i32, [vp, vp, sz, u32]),
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_transform_selected": (i32, [vp, u32, sz, vp, u32, vp, u32]),
+        "gs4d_count_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -134,6 +136,7 @@ def _load():
         "gs4d_host_measure_records": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_measure_centre": (i32, [vp, vp]),
         "gs4d_host_transform_selected": (None, [sz, vp, vp, vp, vp, vp]),
+        "gs4d_host_count_neighbours": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_frame_box": (None, [vp, vp, vp, f32, i32, i32, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
@@ -615,6 +618,46 @@ def transform_selected_host(records, xf, stats=None, pivot=None, measure=None, n
     _lib.gs4d_host_transform_selected(n, _ptr(rec), _ptr(st) if st is not None else None, _ptr(k) if st is not None else None, C.byref(x),
                                       C.byref(measure) if measure is not None else None)
     return rec
+
+
+class NeighbourQuery(C.Structure):
+    """gs4d_neighbour_query (include/gs4d.h): the time, the radius, the cap and the flags of a gs4d_count_neighbours call; 32 bytes."""
+    _fields_ = [("t", C.c_float), ("radius", C.c_float), ("cap", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+def neighbour_query(radius, t=0.0, cap=0xFFFFFFFF, skip_hidden=False, skip_dead=False, count_self=False):
+    """one gs4d_neighbour_query (NeighbourQuery): centres at time t, within `radius` (float32; 2^-63 <= radius < 2^64), the count saturating at
+    cap >= 1; skip_hidden / skip_dead: records of alpha <= 0 / dead at t take no part; count_self: a record that is a source counts itself."""
+    q = NeighbourQuery()
+    q.t, q.radius, q.cap = float(t), float(np.float32(radius)), int(cap)
+    q.flags = (NB_SKIP_HIDDEN if skip_hidden else 0) | (NB_SKIP_DEAD if skip_dead else 0) | (NB_COUNT_SELF if count_self else 0)
+    return q
+
+
+def count_neighbours_host(records, radius=None, t=0.0, cap=0xFFFFFFFF, source=None, skip_hidden=False, skip_dead=False, count_self=False, query=None,
+                          stats=None, **rule):
+    """gs4d_host_count_neighbours, the definition of Context.count_neighbours — the brute-force double loop: the RECORD_STAT table (a copy of
+    `stats`, rows of 16 bytes, or n zeroed rows if None) after the call on records [n, 24].  source: a table of n rows of 16 bytes whose row j
+    makes record j a source by compact_records' rule keywords, or None: every record (and no rule); query: a NeighbourQuery instead of the
+    radius and the other keywords."""
+    rec = _f32(records).reshape(-1, 24)
+    n = rec.shape[0]
+    if source is None and rule:
+        raise TypeError("count_neighbours_host: a rule without source")
+    if query is None:
+        if radius is None:
+            raise TypeError("count_neighbours_host: radius or query is needed")
+        query = neighbour_query(radius, t, cap, skip_hidden, skip_dead, count_self)
+    st = np.zeros(n, RECORD_STAT) if stats is None else np.array(np.ascontiguousarray(stats), copy=True)
+    if st.dtype.itemsize != 16 or st.ndim != 1 or st.shape[0] < n:
+        raise ValueError("count_neighbours_host: stats must be at least n rows of 16 bytes")
+    st = st.view(RECORD_STAT)                                  # (the bytes as they are, as in count_centres_host)
+    src = None if source is None else np.ascontiguousarray(source)
+    if src is not None and (src.dtype.itemsize != 16 or src.ndim != 1 or src.shape[0] < n):
+        raise ValueError("count_neighbours_host: source must be at least n rows of 16 bytes")
+    k = _keep_rule(**rule)
+    _lib.gs4d_host_count_neighbours(n, _ptr(rec), C.byref(query), _ptr(src) if src is not None else None, _ptr(k) if src is not None else None, _ptr(st))
+    return st
 
 
 def frame_box(lo, hi, orientation, fov_deg, width, height):
@@ -1113,6 +1156,41 @@ class Context:
         centre); blocks until its kernels have finished."""
         raw = self.read(out, np.uint8, C.sizeof(Measure))
         return Measure.from_buffer_copy(raw.tobytes()).as_dict()
+
+    # records relative to each other: the sources within a radius of each record (DESIGN.md §4)
+    def count_neighbours(self, stats, n, data, radius=None, t=0.0, cap=0xFFFFFFFF, source=None, skip_hidden=False, skip_dead=False, count_self=False,
+                         query=None, **rule):
+        """gs4d_count_neighbours: row i of the record_stats buffer `stats` gets c fragments of weight 1, c = min(cap, the number of source
+        records whose centre at time t lies within `radius` of that of record i < n of `data`) — records of a non-finite centre, and with
+        skip_hidden / skip_dead those of alpha <= 0 / dead at t, take no part on either side.  source: a record_stats buffer whose row j makes
+        record j a source by compact_records' rule keywords (None: every record, and no rule); count_self: a source counts itself; query: a
+        NeighbourQuery instead of the radius and the other keywords.  Nothing zeroes `stats`: calls add up.  With the bits of
+        count_neighbours_host, from a hashed grid instead of its double loop.  Asynchronous."""
+        if source is None and rule:
+            raise TypeError("count_neighbours: a rule without source")
+        if query is None:
+            if radius is None:
+                raise TypeError("count_neighbours: radius or query is needed")
+            query = neighbour_query(radius, t, cap, skip_hidden, skip_dead, count_self)
+        k = _keep_rule(**rule) if source is not None else None
+        self._chk(_lib.gs4d_count_neighbours(self._h, int(data), int(n), C.byref(query), int(source or 0), _ptr(k) if k is not None else None, int(stats)))
+
+    def grow_selection(self, n, data, source, radius, t=0.0, cap=1, skip_hidden=False, skip_dead=False, **rule):
+        """Grow a selection: a fresh zeroed table filled by one count_neighbours call with count_self, whose rule min_pixels=1 selects every record
+        within `radius` of a record that `source` selects by the rule keywords (default min_pixels=1) — a superset of the part of the selection
+        that takes part.  cap=1 is all a selection needs; a larger cap leaves the number of selected records nearby in pixels.  Growing again
+        takes the result as the source.  Asynchronous; returns the table."""
+        stats = self.record_stats(n)
+        self.count_neighbours(stats, n, data, radius, t=t, cap=cap, source=source, skip_hidden=skip_hidden, skip_dead=skip_dead, count_self=True, **rule)
+        return stats
+
+    def isolated(self, n, data, radius, k, t=0.0, skip_hidden=False, skip_dead=False):
+        """Isolated records (floaters): a fresh zeroed table with, per record that takes part, the number of OTHER records within `radius`,
+        saturating at k — ready for the rule min_pixels=k, invert=True (compact_records, hide, edit_colours), which selects the records with fewer
+        than k neighbours (those that take no part among them: their rows stay zero).  Asynchronous; returns the table."""
+        stats = self.record_stats(n)
+        self.count_neighbours(stats, n, data, radius, t=t, cap=k, skip_hidden=skip_hidden, skip_dead=skip_dead)
+        return stats
 
     # time windows: the records of a 4D set that can show anything between two times (DESIGN.md §4)
     TIME_SPAN = np.dtype([("t_first", "<f4"), ("t_last", "<f4")])

@@ -137,6 +137,7 @@ struct Lane {
     uint32_t* spatial_scratch = nullptr; size_t spatial_cap = 0;      // gs4d_spatial_order: the box and its partials (order_box_words()), then one key per record; the lane's stream orders its reuse
     uint32_t* cut_scratch = nullptr; size_t cut_cap = 0;               // gs4d_stat_cut: the state block and one partial histogram per workgroup (cut_scratch_words()); the lane's stream orders its reuse
     uint32_t* measure_scratch = nullptr; size_t measure_cap = 0;       // gs4d_measure_records: one partial row per workgroup (measure_scratch_words()); the lane's stream orders its reuse
+    uint32_t* neighbour_scratch = nullptr; size_t neighbour_cap = 0;   // gs4d_count_neighbours: candidates, bucket table, keys and sorted indices (neighbour_scratch_words()); the lane's stream orders its reuse
     uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
     uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
     gs4d_buf kg_buf = 0; uint64_t kg_ver = 0;         // key buffer whose digit histograms k_keygen left for the next sort
@@ -192,6 +193,7 @@ struct gs4d_ctx {
     int blend_src = GS4D_SRC_ALPHA, blend_dst = GS4D_ONE_MINUS_SRC_ALPHA;     // glBlendFunc state (Application.cpp:137-138, 150)
     bool defer_order = true;           // GS4D_FUSE_KEYGEN=0 switches the deferral off (test hook)
     uint64_t stat_composited_tiles = 0;      // tiles the compositing kernel of the last unordered draw was launched for (staged draws: the launch box)
+    int neighbour_phases = 4;          // measurement hook GS4D_NEIGHBOURS_PHASES (1..4), read at context creation: gs4d_count_neighbours stops behind its k-th phase (launch_count_neighbours)
     uint64_t stat_fused = 0, stat_renamed = 0, stat_shadow_bytes = 0, stat_streams_rejected = 0, stat_lanes_sharing = 0;      // lanes_sharing: lanes that had to take a stream which shares a hardware queue with another lane
     bool rename_storage = true;        // GS4D_RENAME=0 switches the storage exchange off (test hook)
     bool aux_enable = false, ids_enable = false;      // gs4d_set_aux_outputs, gs4d_set_id_outputs: what the frames cleared from now on have (gs4d_clear)
@@ -991,6 +993,7 @@ int gs4d_create(int device, int width, int height, gs4d_ctx** out) {
         if (const char* ev = getenv("GS4D_SORT_TAILCAP")) { const long v = atol(ev); if (v >= 1) c->lanes[i].depth_sort.tail_cap = (uint32_t)std::min<long>(v, 1l << 30); }
         c->lanes[i].pair_sort.hybrid_knob = 0;
     }
+    if (const char* ev = getenv("GS4D_NEIGHBOURS_PHASES")) c->neighbour_phases = std::min(4, std::max(1, atoi(ev)));
     int rc = alloc_fbs(c, width, height);
     if (rc) return bail(rc);
     *out = c;
@@ -1015,6 +1018,7 @@ void gs4d_destroy(gs4d_ctx* c) {
         if (L.spatial_scratch) (void)hipFree(L.spatial_scratch);
         if (L.cut_scratch) (void)hipFree(L.cut_scratch);
         if (L.measure_scratch) (void)hipFree(L.measure_scratch);
+        if (L.neighbour_scratch) (void)hipFree(L.neighbour_scratch);
         for (auto& sp : L.spare) { if (sp.d) (void)hipFree(sp.d); for (hipEvent_t e : sp.ev) if (e) (void)hipEventDestroy(e); }
         if (L.proj) (void)hipFree(L.proj);
         if (L.trects) (void)hipFree(L.trects);
@@ -2030,6 +2034,48 @@ int gs4d_measure_records(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_measur
             if (S) { int rc = scan_begin(c, L, *S); if (rc) return rc; }
             HIPCHK(c, launch_measure_records(L.s, D->d, n, q.t, q.flags, S ? (const gs4d_record_stat*)S->d : nullptr, k, L.measure_scratch, (gs4d_measure*)O->d));
             return S ? scan_end(c, L, *S) : (int)GS4D_OK;
+        });
+}
+
+// ---- records relative to each other: the sources within a radius of each record, as a statistics table ----
+int gs4d_count_neighbours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_neighbour_query* query, gs4d_buf source, const gs4d_keep_rule* rule, gs4d_buf stats) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("count_neighbours: ") + msg).c_str()); };
+    if (!query) return bad("query == NULL");
+    const gs4d_neighbour_query q = *query;
+    if ((q.flags & ~(uint32_t)(GS4D_NB_SKIP_HIDDEN | GS4D_NB_SKIP_DEAD | GS4D_NB_COUNT_SELF)) != 0u) return bad("unknown flag");
+    if (q.reserved[0] != 0u || q.reserved[1] != 0u || q.reserved[2] != 0u || q.reserved[3] != 0u) return bad("non-zero reserved field in the query");
+    if (q.cap == 0u) return bad("cap == 0");
+    if (!neighbour_radius_ok(q.radius)) return bad("the radius must be finite with 2^-63 <= radius < 2^64");
+    if (n >= 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
+    if ((source != 0) != (rule != nullptr)) return bad("source and rule are given together or not at all");
+    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
+    const gs4d_buf names[3] = { data, stats, source };
+    Buffer* D = getbuf(c, data); Buffer* S = getbuf(c, stats);
+    if (!D || !S) return bad("data and stats must name live buffers");
+    if (const int wrong = check_record_names(c, names, 3)) return bad(wrong == 1 ? "bad buffer name" : "data, source and stats must be different buffers");
+    Buffer* Q = getbuf(c, source);
+    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
+    if (S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (Q && Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the source buffer holds fewer than n rows");
+    if (n == 0) return GS4D_OK;
+    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
+    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
+    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    if (Q) { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
+    // stats as an "out" of queue_on_lane, as in gs4d_count_centres: a read-modify-write the lane has the table to itself for.  data is read
+    // (the 96-byte records, never a shadow: a reader leaves `version` alone), source is read as gs4d_edit_colours reads its table.
+    return queue_on_lane(c, { D, Q }, { S },
+        [&](Lane& L) {
+            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, neighbour_scratch_words(n)));
+            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));      // (the tile sort's scratch, as gs4d_spatial_order: a histogram a queued keygen has left in depth_sort stays where it is)
+            return Q ? scan_reserve(c, *Q) : (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            if (Q) { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
+            HIPCHK(c, launch_count_neighbours(L.s, L.pair_sort, D->d, n, q, Q ? (const gs4d_record_stat*)Q->d : nullptr, k, L.neighbour_scratch, (gs4d_record_stat*)S->d, c->neighbour_phases));
+            return Q ? scan_end(c, L, *Q) : (int)GS4D_OK;
         });
 }
 

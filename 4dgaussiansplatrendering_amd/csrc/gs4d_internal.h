@@ -513,6 +513,20 @@ constexpr uint32_t CENTRES_TILE = 256;
 hipError_t launch_count_centres(hipStream_t st, const void* records, const float4* soa, size_t soa_n, const SoaInfo& info, size_t n, const gs4d_centre_query& q,
                                 int W, int H, const uint8_t* mask, gs4d_record_stat* stats);
 
+// ---- neighbours.hip ----
+// gs4d_count_neighbours (gs4d.h): row i < n of stats gets c_i fragments of weight 1, c_i the number (at most q.cap) of sources whose
+// centre lies within q.radius of record i's — source: the table whose row j makes record j a source by `rule` (keep_row), or null: every record
+// that takes part.  q: validated.  Key kernel, the sort of the identity by key (`sort`: the lane's pair_sort, reserved for n), a memset, the bucket
+// kernel and the query kernel on `st`; no workgroup waits for another.  Nothing but rows < n of stats and the scratch is written.  phases < 4 (the
+// measurement hook of tools/neighbours_cost.py): stop behind the keys (1), the sort (2), the table (3) — stats is then not written.
+constexpr uint32_t NEIGHBOURS_TILE = 256;
+bool neighbour_radius_ok(float r);               // 2^-63 <= r < 2^64: r * r is a normal float32 number (neighbour_query.h)
+int neighbour_bucket_bits(size_t n);             // kb: the bucket table has 2^kb rows, 2 n <= 2^kb < 4 n inside 2^8 .. 2^30
+// scratch: neighbour_scratch_words(n) words (the lane's): n candidates of 16 bytes, the table of 2^kb rows of 8 bytes, n keys, n sorted indices
+inline size_t neighbour_scratch_words(size_t n) { return 4 * n + 2 * ((size_t)1 << neighbour_bucket_bits(n)) + 2 * n; }
+hipError_t launch_count_neighbours(hipStream_t st, SortScratch& sort, const void* records, size_t n, const gs4d_neighbour_query& q,
+                                   const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, gs4d_record_stat* stats, int phases = 4);
+
 // ---- measure.hip ----
 // gs4d_measure_records (gs4d.h): *out <- the measurement at time t, under the GS4D_MS_* flags (validated), of the selected ones of the
 // first n 96-byte records — stats: the table whose row i selects record i by `rule` (keep_row), or null: every record.  Three launches on `st`, no

@@ -23,6 +23,7 @@
 #include <vector>
 #include "../csrc/centre_query.h"
 #include "../csrc/measure_record.h"
+#include "../csrc/neighbour_query.h"
 
 namespace {
 
@@ -513,6 +514,41 @@ void gs4d_host_measure_records(size_t n, const float* rec, const gs4d_measure_qu
         float m[3];
         if (ms::place(q->t, q->flags, fields(i).c, m) != ms::MEASURED) continue;
         for (int a = 0; a < 3; ++a) out->cell_sum[a] += ms::cell(m[a], out->lo[a], out->hi[a]);
+    }
+}
+
+// The definition of gs4d_count_neighbours (gs4d.h), in place on the table: the brute-force double loop over the text of csrc/neighbour_query.h,
+// which the kernels compile too (this file is built with -ffp-contract=off), with the early exit at cap; then the row.  No search structure: this
+// is what the device's structure has to reproduce.  A query the device call would refuse changes nothing.
+void gs4d_host_count_neighbours(size_t n, const float* rec, const gs4d_neighbour_query* q, const gs4d_record_stat* source, const gs4d_keep_rule* rule,
+                                gs4d_record_stat* stats) {
+    namespace nb = gs4d_neighbour;
+    if (!q || !nb::query_ok(*q) || (source && !rule)) return;
+    if (source && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return;
+    const bool invert = source && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    const bool self = (q->flags & (uint32_t)GS4D_NB_COUNT_SELF) != 0u;
+    const float rr = q->radius * q->radius;
+    // the centres, who takes part, who is a source
+    std::vector<float> m(3 * n);
+    std::vector<uint8_t> part(n), src(n);
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = rec + 24 * i;
+        const nb::Fields r{ { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] };
+        part[i] = nb::takes_part(q->t, q->flags, r, &m[3 * i]);
+        src[i] = part[i];
+        if (src[i] && source) {
+            const gs4d_record_stat& s = source[i];
+            src[i] = (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert;
+        }
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (!part[i]) continue;
+        uint32_t c = 0;
+        for (size_t j = 0; j < n && c < q->cap; ++j)
+            if (src[j] && (j != i || self) && nb::near(&m[3 * i], &m[3 * j], rr)) ++c;
+        if (c == 0u) continue;
+        gs4d_record_stat& s = stats[i];
+        s.pixels += c; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += (uint64_t)c << 24;
     }
 }
 

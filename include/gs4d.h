@@ -864,6 +864,81 @@ GS4D_API int gs4d_transform_selected(gs4d_ctx* ctx, gs4d_buf data, size_t n, con
                                      gs4d_buf stats /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff stats == 0 */,
                                      gs4d_buf measure /* GS4D_XS_PIVOT_MEASURE: a gs4d_measure at offset 0; otherwise 0 */);
 
+/* ---- records relative to each other: how many source records lie within a radius of each record (no reference counterpart) ----
+ * Every selection above is against a fixed region.  gs4d_count_neighbours counts, for every record, the records of a SOURCE set whose centre at
+ * time t lies within r of its own, and writes the counts as rows of a gs4d_record_stat table — which makes two editor tools out of the calls that
+ * exist.  Grow a selection ("what lies within r of what I have selected"): source = the selection's table with its rule, GS4D_NB_COUNT_SELF, into
+ * a zeroed table B; B with the rule {1, 0, 0} is then a superset of the part of the selection that takes part and holds everything within r of
+ * that part, and calling again with B as the source grows further.  Isolated records, the floaters of a trained set ("fewer than k neighbours
+ * within r"): source == 0 into a zeroed table, then the rule {k, 0, 0} with GS4D_KEEP_INVERT for gs4d_compact_records (delete) or
+ * gs4d_edit_colours (hide); a cap of k is enough, and it is what keeps dense regions cheap.  gs4d_stat_cut over pixels gives the K most crowded
+ * records.  gs4d_host_count_neighbours is this text as code: the brute-force double loop.
+ *
+ * All arithmetic is float32, round to nearest, no contraction: every product and every sum is rounded on its own, in the order the parentheses
+ * give; division is correctly rounded (the convention of gs4d_count_centres).  For record i < n of the 96-byte records in data, with
+ * p = floats 0..2, mu_t = float 3, a = float 7, sig3 = floats 20..22, s44 = float 23:
+ *
+ * Centre (the text of gs4d_count_centres).
+ *     dt = t - mu_t;   k = (1.0f / s44) * dt;   m_i = p + (k * sig3)   per component.
+ *
+ * Takes part.  Record i takes part iff it is not skipped by GS4D_NB_SKIP_HIDDEN, which skips iff !(a > 0); it is not skipped by
+ * GS4D_NB_SKIP_DEAD, which skips iff ((-0.5f * dt) * (1.0f / s44)) * dt < GS4D_TIME_DEAD_ARG (a NaN is not skipped); and m_i[0], m_i[1], m_i[2]
+ * are all finite.  A record that does not take part is nobody's neighbour, and its own row keeps its bits.
+ *
+ * Source.  Record j is a source iff it takes part and is selected by exactly the predicate of gs4d_edit_colours: source == 0 selects every
+ * record; otherwise row j of the gs4d_record_stat table `source` must pass `rule`: (pixels >= min_pixels && wmax >= min_wmax &&
+ * wsum >= min_wsum) != invert (GS4D_KEEP_INVERT).
+ *
+ * Near.  With the difference taken per component, d = m_i - m_j, the pair (i, j) is near iff
+ *     ((d.x * d.x) + (d.y * d.y)) + (d.z * d.z) <= r * r.
+ * The test is symmetric in i and j.
+ *
+ * Count.  For a record i that takes part,
+ *     c_i = min(cap, #{ j < n : j is a source, j near i, and (j != i or GS4D_NB_COUNT_SELF) }).
+ * With GS4D_NB_COUNT_SELF a record that is a source counts itself.  Every record < n that takes part is a query, selected or not.
+ *
+ * The row.  If c_i >= 1, row i of stats gets what c_i fragments of weight 1 add in a draw: pixels += c_i; wmax = max(wmax, 0x3F800000);
+ * wsum += (uint64) c_i << 24 (pixels modulo 2^32, wsum modulo 2^64, as in gs4d_count_centres).  If c_i == 0, or i does not take part, the row is
+ * not written.  The call ADDS: nothing zeroes the table.  No byte beyond row n - 1 is written, and no byte of data or source is written.  Every
+ * field is an integer that depends on a set and not on an order: the same inputs give the same bytes, whatever runs first.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: query == NULL; an unknown flag; a non-zero reserved word; cap == 0; a radius that is
+ * not finite or not above 0, or whose float32 square r * r is not finite or is below FLT_MIN (that is 2^-63 <= r < 2^64: it keeps r * r a normal
+ * number, which the exactness of the search structure rests on); n >= 0xFFFFFFFF (the sort's limit, as in gs4d_spatial_order); data or stats not a live buffer;
+ * data smaller than 96 n bytes; stats smaller than 16 n bytes; exactly one of source / rule given; a rule with an unknown flag or reserved != 0;
+ * source not a live buffer or smaller than 16 n bytes; any two of the three buffers being the same buffer.  n == 0 with otherwise valid
+ * arguments is a no-op.  t is data, not an error.
+ *
+ * Ordering.  data is read as gs4d_count_centres reads its data: a later write of it waits for the kernels.  source is read as gs4d_edit_colours
+ * reads its table: draws that add to it (gs4d_set_record_stats), issued before the call on any frame lane, are settled first, re-runs included; a
+ * draw issued afterwards that adds to it waits on the device until the kernels have read it.  stats is a kernel write that keeps the contents,
+ * exactly as in gs4d_count_centres.  A queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first.  The kernels are
+ * queued on the current frame lane; the call returns at once and starts no frame.  gs4d_buffer_invalidate hand-offs of all three buffers are
+ * honoured.  The call reads the 96-byte records: it never builds, reads or invalidates a SoA shadow (gs4d_debug_shadow_builds does not move).
+ *
+ * Cost.  The device gives the brute-force result without the brute-force work: the sources are hashed by the cell of edge about 2 r their centre
+ * lies in, and a record looks only at the cells its ball can reach — at most 27, usually 8 (DESIGN.md §4 has the structure and the proof that
+ * it misses nothing).  The cost therefore depends on the data: a query costs the population of those cells.  Many sources inside one cell of
+ * edge 2 r cost O(candidates) per query even with a small cap, because candidates that are not near do not count towards it.  The lane keeps
+ * scratch of about 24 n bytes plus a bucket table of 8 bytes for each of 2 n .. 4 n buckets (at least 256), beside the sort's.  Environment, read
+ * at gs4d_create: GS4D_NEIGHBOURS_PHASES=1, 2 or 3 makes the call stop behind its key, sort or bucket-table phase — a measurement hook
+ * (tools/neighbours_cost.py): stats is then not written.
+ *
+ * Out of scope: reading a SoA shadow; a query-side selection (every record that takes part is a query); distances that use the covariance
+ * (Mahalanobis, overlap of extents); k-nearest-neighbour distances; connected components, meaning growing to a fixed point in one call; 72-byte
+ * quad vertices and 48-byte 2D records; source == stats. */
+enum { GS4D_NB_SKIP_HIDDEN = 1, GS4D_NB_SKIP_DEAD = 2, GS4D_NB_COUNT_SELF = 4 };
+typedef struct gs4d_neighbour_query {
+    float    t;           /* the time the centres are taken at                                  */
+    float    radius;      /* r                                                                  */
+    uint32_t cap;         /* the count saturates here; >= 1                                     */
+    uint32_t flags;       /* OR of GS4D_NB_*; any other bit: GS4D_E_INVALID                     */
+    uint32_t reserved[4]; /* must be 0                                                          */
+} gs4d_neighbour_query;   /* 32 bytes */
+GS4D_API int gs4d_count_neighbours(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_neighbour_query* query,
+                                   gs4d_buf source /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff source == 0 */,
+                                   gs4d_buf stats);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -943,6 +1018,12 @@ GS4D_API int  gs4d_host_measure_centre(const gs4d_measure* m, float centre3[3]);
  * (NULL, an unknown flags value, GS4D_XS_PIVOT_MEASURE without a measure) changes nothing. */
 GS4D_API void gs4d_host_transform_selected(size_t n, float* records24, const gs4d_record_stat* stats, const gs4d_keep_rule* rule,
                                            const gs4d_selection_xf* xf, const gs4d_measure* measure);
+/* The definition of gs4d_count_neighbours, in place on the n rows of stats (the text above its declaration): the brute-force double loop, with
+ * the early exit at cap.  source == NULL selects every record (rule is then ignored), else rule is not NULL; source and stats must not overlap.
+ * A query the device call would refuse (NULL, an unknown flag, a non-zero reserved word, cap == 0, a radius outside 2^-63 <= r < 2^64) changes
+ * nothing. */
+GS4D_API void gs4d_host_count_neighbours(size_t n, const float* records24, const gs4d_neighbour_query* query,
+                                         const gs4d_record_stat* source, const gs4d_keep_rule* rule, gs4d_record_stat* stats);
 /* "Frame selection": the eye from which a camera of gs4d_host_look_at(eye, orientation, up) and gs4d_host_perspective(fov_deg, width, height, ..)
  * sees the whole box lo .. hi with its centre in the middle of the image.  The box's bounding sphere (centre (lo + hi) / 2, radius half the
  * diagonal; a degenerate box — a radius that is zero or not finite — gets radius 1) is fitted into the narrower of the projection's two
