@@ -988,10 +988,17 @@ int gs4d_create(int device, int width, int height, gs4d_ctx** out) {
     for (int i = 0; i < c->nlanes; ++i) {
         for (SortScratch* ss : { &c->lanes[i].depth_sort, &c->lanes[i].pair_sort }) { ss->atomic_rank = c->atomic_rank; ss->shape_knob = shape_knob; ss->rank_knob = rank_knob; ss->rb_knob = getenv("GS4D_SORT_RB") ? atoi(getenv("GS4D_SORT_RB")) : 0; }
         // GS4D_SORT_HYBRID: 0 = depth sorts are the LSD passes, as before the hybrid existed; 1 = the hybrid for every eligible span, whatever n.  GS4D_SORT_TAILCAP: keys above
-        // which a bucket of the hybrid takes the tail kernel's slow path (test hook: a runtime compare).  The tile sort (pair_sort) never plans the hybrid: it is not asked to (sort_plan_hist).
-        if (const char* ev = getenv("GS4D_SORT_HYBRID")) c->lanes[i].depth_sort.hybrid_knob = atoi(ev) != 0 ? 1 : 0;
-        if (const char* ev = getenv("GS4D_SORT_TAILCAP")) { const long v = atol(ev); if (v >= 1) c->lanes[i].depth_sort.tail_cap = (uint32_t)std::min<long>(v, 1l << 30); }
+        // which a bucket of the hybrid takes the tail kernel's slow path (test hook: a runtime compare).  Both apply to both scratches of the lane.  Without
+        // GS4D_SORT_HYBRID the lane's other scratch (pair_sort) never plans the hybrid; with it, the one sort there that can is gs4d_count_neighbours' (kb + 1 key
+        // bits, 19..27 from 65537 records on, no producer: os_plan at the sort, k_os_hist counts the top-digit row alone, bias 0) — how the tests take the hybrid
+        // through k_os_hist.  The others stay what they are: the tile-pair sort executes the plan of hist_rows / hist_top / hist_hybrid, which only sort_plan_hist
+        // sets and nobody calls for pair_sort (every sort leaves them at the LSD plan), and has a device-side count (os_plan is not even asked); the reorder sort
+        // has ORDER_KEY_BITS = 31 key bits, outside 19..27.
         c->lanes[i].pair_sort.hybrid_knob = 0;
+        for (SortScratch* ss : { &c->lanes[i].depth_sort, &c->lanes[i].pair_sort }) {
+            if (const char* ev = getenv("GS4D_SORT_HYBRID")) ss->hybrid_knob = atoi(ev) != 0 ? 1 : 0;
+            if (const char* ev = getenv("GS4D_SORT_TAILCAP")) { const long v = atol(ev); if (v >= 1) ss->tail_cap = (uint32_t)std::min<long>(v, 1l << 30); }
+        }
     }
     if (const char* ev = getenv("GS4D_NEIGHBOURS_PHASES")) c->neighbour_phases = std::min(4, std::max(1, atoi(ev)));
     int rc = alloc_fbs(c, width, height);

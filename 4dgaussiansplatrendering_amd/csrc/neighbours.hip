@@ -11,7 +11,7 @@
 //                      — gets the bucket of its cell as its key, kb bits; any other record gets a key with bit kb set — it sorts behind every source
 //                      and is never looked up — whose low bits are the bucket of its cell too if it takes part (0 if not): the query kernel
 //                      walks the records in sorted order, and records of one cell then sit in one wave.
-//   the sort           radix_sort_pairs of the identity by key, kb + 1 bits, stable (sort.hip; the lane's tile sort never plans the hybrid: LSD passes).
+//   the sort           radix_sort_pairs of the identity by key, kb + 1 bits, stable (sort.hip; on the lane's pair_sort scratch, which plans the LSD passes unless GS4D_SORT_HYBRID is set: then 19..27 key bits — 65537 records and more — take the MSD/LSD hybrid through k_os_hist).
 //   the memset         the bucket table, 2^kb rows of {first, end}, to zero: an empty bucket is first == end.
 //   k_nb_buckets       one thread per sorted slot s that holds a source j: the centre of record j again (two 16-byte loads at a scattered record,
 //                      the same function on the same bits) stored as float4 {m.x, m.y, m.z, bits(j)} into cand[s]; and the marks: s is the first

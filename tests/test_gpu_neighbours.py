@@ -228,7 +228,11 @@ def test_the_scratch_is_re_used_at_other_sizes(gs4d):
 
 def test_a_size_of_several_sort_tiles_and_three_radix_passes(gs4d):
     """n = 70001.  A dense cube with cap 3 against the host definition (its double loop ends early), and the lattice without a cap against
-    neighbour_cases.lattice_counts (the reasoning is there; the host test pins it to the host definition at n = 4097)"""
+    neighbour_cases.lattice_counts (the reasoning is there; the host test pins it to the host definition at n = 4097).
+    Which sort runs: the call sorts kb + 1 = 19 key bits on the lane's pair_sort scratch with a histogram launch of its own (k_os_hist).  19 bits
+    are inside the spans the MSD/LSD hybrid is planned for, but that scratch plans the hybrid only when GS4D_SORT_HYBRID asks for it: with the
+    variable unset, as here, this is k_os_hist and three 8-bit LSD passes.  tests/test_gpu_sort_hybrid_edges.py runs the same calls with the
+    hybrid on (local digits of 5 + 5 bits, slow buckets) and off and compares the tables."""
     n = nc.N_BIG
     assert nc.bucket_bits(n) + 1 == 19 and n > 8 * 8192
     ctx = gs4d.Context(W, H)

@@ -14,35 +14,14 @@ import pytest
 
 import scenes
 import sort_cases as sc
+from hybrid_cases import CAM0, KEY_LO, _records, _proven, _uniform, _crowded      # the record sets: shared with test_gpu_sort_hybrid_edges.py
 from test_gpu_paths import _ctx
 from test_gpu_render import cam_mats, linf, TOL
 
 pytestmark = pytest.mark.gpu
 
-CAM0 = (0.0, 0.0, 0.0)
-KEY_LO = int(np.float32(0.26).view(np.uint32))              # the smallest key of every case: the bias
 SPAN24 = (1 << 24) - (1 << 19)                              # a 24-bit span: three 8-bit LSD passes, top digit = bits 15..23 of (key - bias)
 TAIL_TILE = 8192                                            # k_os_tail's LDS tile (OT_TILE)
-
-
-def _records(gs4d, key_bits, span):
-    """records whose keys are (about) the float bit patterns key_bits, then the two records that pin the box to [KEY_LO, KEY_LO + span]"""
-    bits = np.concatenate([np.asarray(key_bits, np.uint32), np.array([KEY_LO, KEY_LO + span], np.uint32)])
-    d = (np.float32(1.0) / bits.view(np.float32)).astype(np.float32)
-    m = d.size
-    pos4 = np.zeros((m, 4), np.float32)
-    pos4[:, 0] = d
-    q = np.tile(np.array([1.0, 0.0, 0.0, 0.0], np.float32), (m, 1))
-    one3 = np.ones((m, 3), np.float32)
-    return gs4d.build_records_4d(pos4, q, one3, np.ones(m, np.float32), np.full(m, 0.5, np.float32), np.zeros((m, 3), np.float32), np.ones((m, 4), np.float32))
-
-
-def _proven(gs4d, rec):
-    """(bias, key bits) the library proves for the buffer: the box of its x positions (everything else is zero)"""
-    lo7, hi7 = np.zeros(7, np.float32), np.zeros(7, np.float32)
-    lo7[0], hi7[0] = rec[:, 0].min(), rec[:, 0].max()
-    bias, span = gs4d.key_bounds(lo7, hi7, 0.0, CAM0)
-    return bias, max(1, int(span).bit_length())
 
 
 class _Set:
@@ -77,21 +56,6 @@ class _Set:
             assert bad.size == 0, f"{what}: {bad.size} of {n} slots differ, the first at {int(bad[0])}: got {int(got[bad[0]]):#x}, want {int(want[bad[0]]):#x}"
         return {"hybrid": after["hybrid_sorts"] - before["hybrid_sorts"], "launches": after["sort_launches"] - before["sort_launches"],
                 "largest": after["largest_bucket"], "slow": after["slow_buckets"]}
-
-
-def _uniform(n, span, seed):
-    rng = np.random.default_rng(seed)
-    return (KEY_LO + 8 + rng.integers(0, span - 16, n, dtype=np.int64)).astype(np.uint32)      # (a few patterns inside the box: 1 / (1 / k) is not k to the last bit)
-
-
-def _crowded(n, share, seed):
-    """`share` of the keys inside top digit 200 of a 24-bit span, the rest uniform"""
-    keys = _uniform(n, SPAN24, seed)
-    rng = np.random.default_rng(seed + 1)
-    m = int(n * share)
-    where = rng.choice(n, m, replace=False)
-    keys[where] = (KEY_LO + (200 << 15) + (1 << 13) + rng.integers(0, 1 << 14, m, dtype=np.int64)).astype(np.uint32)
-    return keys, m
 
 
 def _hybrid_ctx(gs4d, monkeypatch, **env):
