@@ -31,6 +31,8 @@ CQ_ADD, CQ_REMOVE = 0, 1                                   # gs4d_centre_query.o
 MS_SKIP_HIDDEN, MS_SKIP_DEAD = 1, 2                        # gs4d_measure_query.flags
 XS_PIVOT, XS_PIVOT_MEASURE = 1, 2                          # gs4d_selection_xf.flags
 NB_SKIP_HIDDEN, NB_SKIP_DEAD, NB_COUNT_SELF = 1, 2, 4      # gs4d_neighbour_query.flags
+CC_SKIP_HIDDEN, CC_SKIP_DEAD = 1, 2                        # gs4d_component_query.flags
+ID_NONE = 0xFFFFFFFF                                       # GS4D_ID_NONE: the label of a record that is no member
 TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
 CLEAR_COLOR = (0.18431373, 0.20784314, 0.25882353, 1.0)   # Application.cpp:125
@@ -107,6 +109,8 @@ def _load():
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_transform_selected": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_count_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
+        "gs4d_label_components": (i32, [vp, u32, sz, vp, u32, vp, u32, u32]),
+        "gs4d_count_labels": (i32, [vp, u32, sz, u32, vp, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -137,6 +141,8 @@ def _load():
         "gs4d_host_measure_centre": (i32, [vp, vp]),
         "gs4d_host_transform_selected": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_count_neighbours": (None, [sz, vp, vp, vp, vp, vp]),
+        "gs4d_host_label_components": (None, [sz, vp, vp, vp, vp, vp, vp]),
+        "gs4d_host_count_labels": (None, [sz, vp, vp, vp, vp]),
         "gs4d_host_frame_box": (None, [vp, vp, vp, f32, i32, i32, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
@@ -657,6 +663,69 @@ def count_neighbours_host(records, radius=None, t=0.0, cap=0xFFFFFFFF, source=No
         raise ValueError("count_neighbours_host: source must be at least n rows of 16 bytes")
     k = _keep_rule(**rule)
     _lib.gs4d_host_count_neighbours(n, _ptr(rec), C.byref(query), _ptr(src) if src is not None else None, _ptr(k) if src is not None else None, _ptr(st))
+    return st
+
+
+class ComponentQuery(C.Structure):
+    """gs4d_component_query (include/gs4d.h): the time, the radius, the cap and the flags of a gs4d_label_components call; 32 bytes."""
+    _fields_ = [("t", C.c_float), ("radius", C.c_float), ("cap", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+def component_query(radius, t=0.0, cap=0xFFFFFFFF, skip_hidden=False, skip_dead=False):
+    """one gs4d_component_query (ComponentQuery): centres at time t, members linked iff within `radius` (float32; 2^-63 <= radius < 2^64), the
+    size written to a row saturating at cap >= 1; skip_hidden / skip_dead: records of alpha <= 0 / dead at t are no members."""
+    q = ComponentQuery()
+    q.t, q.radius, q.cap = float(t), float(np.float32(radius)), int(cap)
+    q.flags = (CC_SKIP_HIDDEN if skip_hidden else 0) | (CC_SKIP_DEAD if skip_dead else 0)
+    return q
+
+
+def label_components_host(records, radius=None, t=0.0, cap=0xFFFFFFFF, source=None, skip_hidden=False, skip_dead=False, query=None, stats=None,
+                          with_stats=True, **rule):
+    """gs4d_host_label_components, the definition of Context.label_components — the brute-force double loop with a sequential union-find: (labels
+    [n] uint32, the RECORD_STAT table after the call — a copy of `stats`, or n zeroed rows if None; None with with_stats=False) on records [n, 24].
+    source: a table of n rows of 16 bytes whose row i makes record i a candidate member by compact_records' rule keywords, or None: every record
+    (and no rule); query: a ComponentQuery instead of the radius and the other keywords.  A query the device would refuse leaves the labels at
+    ID_NONE and the table as it was."""
+    rec = _f32(records).reshape(-1, 24)
+    n = rec.shape[0]
+    if source is None and rule:
+        raise TypeError("label_components_host: a rule without source")
+    if query is None:
+        if radius is None:
+            raise TypeError("label_components_host: radius or query is needed")
+        query = component_query(radius, t, cap, skip_hidden, skip_dead)
+    st = None
+    if with_stats:
+        st = np.zeros(n, RECORD_STAT) if stats is None else np.array(np.ascontiguousarray(stats), copy=True)
+        if st.dtype.itemsize != 16 or st.ndim != 1 or st.shape[0] < n:
+            raise ValueError("label_components_host: stats must be at least n rows of 16 bytes")
+        st = st.view(RECORD_STAT)
+    src = None if source is None else np.ascontiguousarray(source)
+    if src is not None and (src.dtype.itemsize != 16 or src.ndim != 1 or src.shape[0] < n):
+        raise ValueError("label_components_host: source must be at least n rows of 16 bytes")
+    k = _keep_rule(**rule)
+    labels = np.full(n, ID_NONE, np.uint32)
+    _lib.gs4d_host_label_components(n, _ptr(rec), C.byref(query), _ptr(src) if src is not None else None, _ptr(k) if src is not None else None,
+                                    _ptr(labels), _ptr(st) if st is not None else None)
+    return labels, st
+
+
+def count_labels_host(labels, seeds, stats=None, n=None, **rule):
+    """gs4d_host_count_labels, the definition of Context.count_labels: the RECORD_STAT table (a copy of `stats`, or n zeroed rows if None) after
+    the call — one fragment of weight 1 for every record < n whose label is the label of a record whose row of `seeds` (n rows of 16 bytes)
+    passes compact_records' rule keywords.  n: default all of `labels`."""
+    lab = np.ascontiguousarray(labels, np.uint32).ravel()
+    n = lab.shape[0] if n is None else int(n)
+    sd = np.ascontiguousarray(seeds)
+    if lab.shape[0] < n or sd.dtype.itemsize != 16 or sd.ndim != 1 or sd.shape[0] < n:
+        raise ValueError("count_labels_host: labels must be at least n words and seeds at least n rows of 16 bytes")
+    st = np.zeros(n, RECORD_STAT) if stats is None else np.array(np.ascontiguousarray(stats), copy=True)
+    if st.dtype.itemsize != 16 or st.ndim != 1 or st.shape[0] < n:
+        raise ValueError("count_labels_host: stats must be at least n rows of 16 bytes")
+    st = st.view(RECORD_STAT)
+    k = _keep_rule(**rule)
+    _lib.gs4d_host_count_labels(n, _ptr(lab), _ptr(sd), _ptr(k), _ptr(st))
     return st
 
 
@@ -1192,8 +1261,55 @@ class Context:
         self.count_neighbours(stats, n, data, radius, t=t, cap=k, skip_hidden=skip_hidden, skip_dead=skip_dead)
         return stats
 
+    # connected clusters: one label per record, the cluster's size as a table, what a selection touches by label
+    def label_components(self, n, data, radius=None, t=0.0, cap=0xFFFFFFFF, source=None, skip_hidden=False, skip_dead=False, labels=None, stats=None,
+                         query=None, **rule):
+        """gs4d_label_components: labels[i] (a buffer of n uint32; a new one if None) = the smallest record index of the connected component of
+        record i < n of `data` — members linked iff their centres at time t lie within `radius` of each other — or ID_NONE for a record that is
+        no member (a non-finite centre; with skip_hidden / skip_dead alpha <= 0 / dead at t; not selected by `source`).  stats: a record_stats
+        buffer whose row i gets min(cap, size of the component) fragments of weight 1 for a member (None: labels only); nothing zeroes it.
+        source: a record_stats buffer whose row i selects record i by compact_records' rule keywords (None: every record, and no rule); query: a
+        ComponentQuery instead of the radius and the other keywords.  With the bits of label_components_host.  Asynchronous; returns `labels`."""
+        if source is None and rule:
+            raise TypeError("label_components: a rule without source")
+        if query is None:
+            if radius is None:
+                raise TypeError("label_components: radius or query is needed")
+            query = component_query(radius, t, cap, skip_hidden, skip_dead)
+        k = _keep_rule(**rule) if source is not None else None
+        if labels is None:
+            labels = self.buffer(nbytes=max(16, 4 * int(n)))
+        self._chk(_lib.gs4d_label_components(self._h, int(data), int(n), C.byref(query), int(source or 0), _ptr(k) if k is not None else None, int(labels),
+                                             int(stats or 0)))
+        return labels
+
+    def count_labels(self, stats, n, labels, seeds, **rule):
+        """gs4d_count_labels: row i of the record_stats buffer `stats` gets one fragment of weight 1 iff labels[i] (a buffer of n uint32, as
+        label_components leaves it) is below n and is the label of some record < n whose row of the record_stats buffer `seeds` passes
+        compact_records' rule keywords (default min_pixels=1).  Nothing zeroes `stats`.  With the bits of count_labels_host.  Asynchronous."""
+        k = _keep_rule(**rule)
+        self._chk(_lib.gs4d_count_labels(self._h, int(labels), int(n), int(seeds), _ptr(k), int(stats)))
+
+    def small_components(self, n, data, radius, k, t=0.0, skip_hidden=False, skip_dead=False):
+        """Floater clumps: (labels, a fresh zeroed table with, per member, the size of its connected component saturating at k) — ready for the
+        rule min_pixels=k, invert=True (compact_records, edit_colours), which selects the records in clusters of fewer than k records (those that
+        are no members among them: their rows stay zero), like isolated.  Asynchronous."""
+        stats = self.record_stats(n)
+        labels = self.label_components(n, data, radius, t=t, cap=k, skip_hidden=skip_hidden, skip_dead=skip_dead, stats=stats)
+        return labels, stats
+
+    def select_connected(self, n, data, seeds, radius, t=0.0, skip_hidden=False, skip_dead=False, labels=None, **rule):
+        """Select connected: (labels, a fresh zeroed table whose rule min_pixels=1 selects every record of a connected component that holds a
+        record `seeds` selects by the rule keywords (default min_pixels=1)).  labels: a buffer label_components has filled for this edit state
+        (then `data`, radius, t and the skips are not used), or None: they are computed over every record.  Asynchronous."""
+        if labels is None:
+            labels = self.label_components(n, data, radius, t=t, skip_hidden=skip_hidden, skip_dead=skip_dead)
+        stats = self.record_stats(n)
+        self.count_labels(stats, n, labels, seeds, **rule)
+        return labels, stats
+
     # time windows: the records of a 4D set that can show anything between two times (DESIGN.md §4)
-    TIME_SPAN = np.dtype([("t_first", "<f4"), ("t_last", "<f4")])
+    TIME_SPAN =np.dtype([("t_first", "<f4"), ("t_last", "<f4")])
 
     def record_time_spans(self, data, n, min_opacity=0.0, spans=None):
         """gs4d_record_time_spans: for each of the n 96-byte records of `data`, the closed interval of float32 times outside which it provably

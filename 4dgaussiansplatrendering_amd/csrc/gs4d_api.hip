@@ -137,7 +137,7 @@ struct Lane {
     uint32_t* spatial_scratch = nullptr; size_t spatial_cap = 0;      // gs4d_spatial_order: the box and its partials (order_box_words()), then one key per record; the lane's stream orders its reuse
     uint32_t* cut_scratch = nullptr; size_t cut_cap = 0;               // gs4d_stat_cut: the state block and one partial histogram per workgroup (cut_scratch_words()); the lane's stream orders its reuse
     uint32_t* measure_scratch = nullptr; size_t measure_cap = 0;       // gs4d_measure_records: one partial row per workgroup (measure_scratch_words()); the lane's stream orders its reuse
-    uint32_t* neighbour_scratch = nullptr; size_t neighbour_cap = 0;   // gs4d_count_neighbours: candidates, bucket table, keys and sorted indices (neighbour_scratch_words()); the lane's stream orders its reuse
+    uint32_t* neighbour_scratch = nullptr; size_t neighbour_cap = 0;   // gs4d_count_neighbours and gs4d_label_components: candidates, bucket table, keys and sorted indices (neighbour_scratch_words()); gs4d_count_labels: n flag words; the lane's stream orders its reuse
     uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
     uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
     gs4d_buf kg_buf = 0; uint64_t kg_ver = 0;         // key buffer whose digit histograms k_keygen left for the next sort
@@ -237,7 +237,7 @@ int hipfail(gs4d_ctx* c, hipError_t e, const char* where) {
 }
 #define HIPCHK(c, call) do { hipError_t e__ = (call); if (e__ != hipSuccess) return hipfail((c), e__, #call); } while (0)
 
-const char* const DEVICE_CHECK_MSG = "device-side check failed (a bounded look-back wait timed out, a sort key fell outside its proven bounds, or a key buffer changed under a queued sort without gs4d_buffer_invalidate): results are invalid";
+const char* const DEVICE_CHECK_MSG = "device-side check failed (a bounded look-back wait timed out, a sort key fell outside its proven bounds, a union-find loop of gs4d_label_components ran past its trip bound, or a key buffer changed under a queued sort without gs4d_buffer_invalidate): results are invalid";
 
 Buffer* getbuf(gs4d_ctx* c, gs4d_buf b) { return (b != 0 && b < c->bufs.size() && c->bufs[b].alive) ? &c->bufs[b] : nullptr; }
 Lane& lane(gs4d_ctx* c) { return c->lanes[c->cur]; }
@@ -2083,6 +2083,85 @@ int gs4d_count_neighbours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_neigh
             if (Q) { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
             HIPCHK(c, launch_count_neighbours(L.s, L.pair_sort, D->d, n, q, Q ? (const gs4d_record_stat*)Q->d : nullptr, k, L.neighbour_scratch, (gs4d_record_stat*)S->d, c->neighbour_phases));
             return Q ? scan_end(c, L, *Q) : (int)GS4D_OK;
+        });
+}
+
+// ---- connected clusters: one label per record, optionally the cluster's size as a statistics table ----
+int gs4d_label_components(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_component_query* query, gs4d_buf source, const gs4d_keep_rule* rule, gs4d_buf labels,
+                          gs4d_buf stats) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("label_components: ") + msg).c_str()); };
+    if (!query) return bad("query == NULL");
+    const gs4d_component_query q = *query;
+    if ((q.flags & ~(uint32_t)(GS4D_CC_SKIP_HIDDEN | GS4D_CC_SKIP_DEAD)) != 0u) return bad("unknown flag");
+    if (q.reserved[0] != 0u || q.reserved[1] != 0u || q.reserved[2] != 0u || q.reserved[3] != 0u) return bad("non-zero reserved field in the query");
+    if (q.cap == 0u) return bad("cap == 0");
+    if (!neighbour_radius_ok(q.radius)) return bad("the radius must be finite with 2^-63 <= radius < 2^64");
+    if (n >= 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
+    if ((source != 0) != (rule != nullptr)) return bad("source and rule are given together or not at all");
+    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
+    const gs4d_buf names[4] = { data, labels, stats, source };
+    Buffer* D = getbuf(c, data); Buffer* B = getbuf(c, labels);
+    if (!D || !B) return bad("data and labels must name live buffers");
+    if (const int wrong = check_record_names(c, names, 4)) return bad(wrong == 1 ? "bad buffer name" : "data, source, labels and stats must be different buffers");
+    Buffer* S = getbuf(c, stats); Buffer* Q = getbuf(c, source);
+    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
+    if (B->bytes / sizeof(uint32_t) < n) return bad("labels holds fewer than n words");
+    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (Q && Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the source buffer holds fewer than n rows");
+    if (n == 0) return GS4D_OK;
+    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
+    { int rc = flush_order_if_named(c, names, 4); if (rc) return rc; }
+    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    if (Q) { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
+    // as gs4d_count_neighbours: data and source are read (the 96-byte records, never a shadow); labels is written whole, stats is a read-modify-write
+    // the lane has the table to itself for — both "out" of queue_on_lane
+    return queue_on_lane(c, { D, Q }, { B, S },
+        [&](Lane& L) {
+            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, neighbour_scratch_words(n)));
+            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));
+            return Q ? scan_reserve(c, *Q) : (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            if (Q) { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
+            HIPCHK(c, launch_label_components(L.s, L.pair_sort, D->d, n, q, Q ? (const gs4d_record_stat*)Q->d : nullptr, k, L.neighbour_scratch, (uint32_t*)B->d,
+                                              S ? (gs4d_record_stat*)S->d : nullptr, L.err_word()));
+            return Q ? scan_end(c, L, *Q) : (int)GS4D_OK;
+        });
+}
+
+// ---- what a selection touches, by label: the records whose label is the label of a seed ----
+int gs4d_count_labels(gs4d_ctx* c, gs4d_buf labels, size_t n, gs4d_buf seeds, const gs4d_keep_rule* rule, gs4d_buf stats) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("count_labels: ") + msg).c_str()); };
+    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    if (!rule) return bad("rule == NULL");
+    if (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u) return bad("unknown flag or non-zero reserved field in the rule");
+    const gs4d_buf names[3] = { labels, seeds, stats };
+    Buffer* B = getbuf(c, labels); Buffer* Q = getbuf(c, seeds); Buffer* S = getbuf(c, stats);
+    if (!B || !Q || !S) return bad("labels, seeds and stats must name live buffers");
+    if (check_record_names(c, names, 3)) return bad("labels, seeds and stats must be different buffers");
+    if (B->bytes / sizeof(uint32_t) < n) return bad("labels holds fewer than n words");
+    if (Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the seeds buffer holds fewer than n rows");
+    if (S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (n == 0) return GS4D_OK;
+    const KeepRule k{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT };
+    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
+    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
+    // labels and seeds are read (seeds as gs4d_edit_colours reads its table), stats is a read-modify-write the lane has the table to itself for.  The
+    // flag words live in the lane's neighbour scratch, whose reuse the lane's stream orders.
+    return queue_on_lane(c, { B, Q }, { S },
+        [&](Lane& L) {
+            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, n));
+            return scan_reserve(c, *Q);
+        },
+        [&](Lane& L) {
+            { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
+            HIPCHK(c, launch_count_labels(L.s, (const uint32_t*)B->d, n, (const gs4d_record_stat*)Q->d, k, L.neighbour_scratch, (gs4d_record_stat*)S->d));
+            return scan_end(c, L, *Q);
         });
 }
 

@@ -526,6 +526,27 @@ int neighbour_bucket_bits(size_t n);             // kb: the bucket table has 2^k
 inline size_t neighbour_scratch_words(size_t n) { return 4 * n + 2 * ((size_t)1 << neighbour_bucket_bits(n)) + 2 * n; }
 hipError_t launch_count_neighbours(hipStream_t st, SortScratch& sort, const void* records, size_t n, const gs4d_neighbour_query& q,
                                    const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, gs4d_record_stat* stats, int phases = 4);
+// The grid phases alone (keys, sort, memset, bucket table; `phases` as above, 3 and more: all of them), which gs4d_label_components builds on: g
+// receives where they left the structure in `scratch` — cand[s] = {centre, bits(index)} of the source in sorted slot s, table[b] = {first, end} of
+// bucket b's run of slots, keys[s] (bit kb set: not a source) and index[s] of every slot.  flags: GS4D_NB_SKIP_HIDDEN / GS4D_NB_SKIP_DEAD.
+struct NeighbourGrid { float4* cand; uint2* table; uint32_t* keys; uint32_t* index; int kb; };
+hipError_t launch_neighbour_grid(hipStream_t st, SortScratch& sort, const void* records, size_t n, float t, float radius, uint32_t flags,
+                                 const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, int phases, NeighbourGrid& g);
+
+// ---- components.hip ----
+// gs4d_label_components (gs4d.h): labels[i] <- the smallest record index of the connected component of member i < n (members: the
+// sources of launch_neighbour_grid; linked iff near), GS4D_ID_NONE for a non-member; stats != null: row i of a member gets min(q.cap, size of its
+// component) fragments of weight 1.  q: validated.  The grid phases, then the init, link and flatten kernels (a lock-free union–find on `labels`,
+// component_union.h; err: the lane's error word, raised if a trip bound runs out), with stats a memset and the size and row kernels, all on `st`; no
+// workgroup waits for another.  scratch: neighbour_scratch_words(n) words.  Nothing but the n labels, rows < n of stats and the scratch is written.
+constexpr uint32_t COMPONENTS_TILE = 256;
+hipError_t launch_label_components(hipStream_t st, SortScratch& sort, const void* records, size_t n, const gs4d_component_query& q,
+                                   const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, uint32_t* labels, gs4d_record_stat* stats,
+                                   uint32_t* err);
+// gs4d_count_labels (gs4d.h): row i < n of stats gets one fragment of weight 1 iff labels[i] < n is the label of some j < n whose row of `seeds`
+// passes `rule`.  flags: n words of scratch (the lane's).  A memset and two kernels on `st`.  Nothing but rows < n of stats and the flags is written.
+hipError_t launch_count_labels(hipStream_t st, const uint32_t* labels, size_t n, const gs4d_record_stat* seeds, const KeepRule& rule, uint32_t* flags,
+                               gs4d_record_stat* stats);
 
 // ---- measure.hip ----
 // gs4d_measure_records (gs4d.h): *out <- the measurement at time t, under the GS4D_MS_* flags (validated), of the selected ones of the

@@ -123,20 +123,19 @@ __global__ __launch_bounds__(NEIGHBOURS_TILE) void k_nb_query(const float4* __re
     stats[i] = row;
 }
 
-hipError_t launch_count_neighbours(hipStream_t st, SortScratch& sort, const void* records, size_t n, const gs4d_neighbour_query& q,
-                                   const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, gs4d_record_stat* stats, int phases) {
-    static_assert(sizeof(gs4d_record_stat) == sizeof(uint4), "a statistics row is one uint4");
-    static_assert(sizeof(gs4d_neighbour_query) == 32, "the query is 32 bytes");
-    if (!n) return hipSuccess;
+// the grid phases: keys, sort, memset, bucket table — what gs4d_count_neighbours and gs4d_label_components (components.hip) share
+hipError_t launch_neighbour_grid(hipStream_t st, SortScratch& sort, const void* records, size_t n, float t, float radius, uint32_t flags,
+                                 const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, int phases, NeighbourGrid& g) {
     const int kb = neighbour_bucket_bits(n);
-    const NbArgs a{ q.t, q.flags, q.cap, q.radius * q.radius, nb::grid(q.radius), kb };
+    const NbArgs a{ t, flags, 0u, radius * radius, nb::grid(radius), kb };
     // the scratch, in the order of neighbour_scratch_words(): candidates (16-byte aligned: first), table, keys, sorted indices
     float4* const cand = (float4*)scratch;
     uint2* const table = (uint2*)(scratch + 4 * n);
     uint32_t* const keys = scratch + 4 * n + 2 * ((size_t)1 << kb);
     uint32_t* const index = keys + n;
+    g = NeighbourGrid{ cand, table, keys, index, kb };
     const dim3 grid((uint32_t)((n + NEIGHBOURS_TILE - 1) / NEIGHBOURS_TILE)), block(NEIGHBOURS_TILE);
-    const bool col = (q.flags & (uint32_t)GS4D_NB_SKIP_HIDDEN) != 0u;
+    const bool col = (flags & (uint32_t)GS4D_NB_SKIP_HIDDEN) != 0u;
     const float4* const rec = (const float4*)records;
     if (col) k_nb_keys<true><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, (const uint4*)source, rule, keys);
     else k_nb_keys<false><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, (const uint4*)source, rule, keys);
@@ -146,9 +145,22 @@ hipError_t launch_count_neighbours(hipStream_t st, SortScratch& sort, const void
     if ((e = radix_sort_pairs(st, sort, keys, index, n, nullptr, kb + 1, false, true)) != hipSuccess || phases < 3) return e;
     if ((e = hipMemsetAsync(table, 0, sizeof(uint2) << kb, st)) != hipSuccess) return e;
     k_nb_buckets<<<grid, block, 0, st>>>(keys, index, (uint32_t)n, a, rec, cand, table);
-    if (phases < 4) return hipGetLastError();
-    if (col) k_nb_query<true><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, cand, table, keys, index, (uint4*)stats);
-    else k_nb_query<false><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, cand, table, keys, index, (uint4*)stats);
+    return hipGetLastError();
+}
+
+hipError_t launch_count_neighbours(hipStream_t st, SortScratch& sort, const void* records, size_t n, const gs4d_neighbour_query& q,
+                                   const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, gs4d_record_stat* stats, int phases) {
+    static_assert(sizeof(gs4d_record_stat) == sizeof(uint4), "a statistics row is one uint4");
+    static_assert(sizeof(gs4d_neighbour_query) == 32, "the query is 32 bytes");
+    if (!n) return hipSuccess;
+    NeighbourGrid g;
+    const hipError_t e = launch_neighbour_grid(st, sort, records, n, q.t, q.radius, q.flags, source, rule, scratch, phases, g);
+    if (e != hipSuccess || phases < 4) return e;
+    const NbArgs a{ q.t, q.flags, q.cap, q.radius * q.radius, nb::grid(q.radius), g.kb };
+    const dim3 grid((uint32_t)((n + NEIGHBOURS_TILE - 1) / NEIGHBOURS_TILE)), block(NEIGHBOURS_TILE);
+    const float4* const rec = (const float4*)records;
+    if ((q.flags & (uint32_t)GS4D_NB_SKIP_HIDDEN) != 0u) k_nb_query<true><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, g.cand, g.table, g.keys, g.index, (uint4*)stats);
+    else k_nb_query<false><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, g.cand, g.table, g.keys, g.index, (uint4*)stats);
     return hipGetLastError();
 }
 

@@ -24,6 +24,7 @@
 #include "../csrc/centre_query.h"
 #include "../csrc/measure_record.h"
 #include "../csrc/neighbour_query.h"
+#include "../csrc/component_union.h"
 
 namespace {
 
@@ -549,6 +550,77 @@ void gs4d_host_count_neighbours(size_t n, const float* rec, const gs4d_neighbour
         if (c == 0u) continue;
         gs4d_record_stat& s = stats[i];
         s.pixels += c; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += (uint64_t)c << 24;
+    }
+}
+
+// The definition of gs4d_label_components (gs4d.h): who is a member (takes_part of csrc/neighbour_query.h and the predicate of gs4d_edit_colours), the
+// brute-force double loop over every pair of members with `near`, and the union–find of csrc/component_union.h — the text the kernels compile — run
+// sequentially on plain words; then the labels and, with a table, the rows.  No search structure.  A query the device call would refuse changes
+// nothing.
+namespace {
+struct PlainParents {
+    uint32_t* p;
+    uint32_t load(uint32_t x) const { return p[x]; }
+    bool cas(uint32_t x, uint32_t is, uint32_t to) { if (p[x] != is) return false; p[x] = to; return true; }
+    void lower(uint32_t x, uint32_t v) { if (v < p[x]) p[x] = v; }
+};
+}
+void gs4d_host_label_components(size_t n, const float* rec, const gs4d_component_query* q, const gs4d_record_stat* source, const gs4d_keep_rule* rule,
+                                uint32_t* labels, gs4d_record_stat* stats) {
+    namespace nb = gs4d_neighbour;
+    if (!q || n >= 0xFFFFFFFFull || (source && !rule)) return;
+    const gs4d_neighbour_query as_nb{ q->t, q->radius, q->cap, q->flags, { q->reserved[0], q->reserved[1], q->reserved[2], q->reserved[3] } };
+    if ((q->flags & ~(uint32_t)(GS4D_CC_SKIP_HIDDEN | GS4D_CC_SKIP_DEAD)) != 0u || !nb::query_ok(as_nb)) return;
+    if (source && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return;
+    const bool invert = source && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    const float rr = q->radius * q->radius;
+    std::vector<float> m(3 * n);
+    std::vector<uint8_t> member(n);
+    std::vector<uint32_t> parent(n);
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = rec + 24 * i;
+        const nb::Fields r{ { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] };
+        member[i] = nb::takes_part(q->t, q->flags, r, &m[3 * i]);
+        if (member[i] && source) {
+            const gs4d_record_stat& s = source[i];
+            member[i] = (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert;
+        }
+        parent[i] = (uint32_t)i;
+    }
+    PlainParents mem{ parent.data() };
+    for (size_t i = 0; i < n; ++i) {
+        if (!member[i]) continue;
+        for (size_t j = 0; j < i; ++j)
+            if (member[j] && nb::near(&m[3 * i], &m[3 * j], rr)) (void)gs4d_union::unite(mem, (uint32_t)i, (uint32_t)j, (uint32_t)n);
+    }
+    std::vector<uint32_t> size(n, 0u);
+    for (size_t i = 0; i < n; ++i) {
+        labels[i] = member[i] ? gs4d_union::find(mem, (uint32_t)i, (uint32_t)n) : (uint32_t)GS4D_ID_NONE;
+        if (member[i]) ++size[labels[i]];
+    }
+    if (!stats) return;
+    for (size_t i = 0; i < n; ++i) {
+        if (!member[i]) continue;
+        const uint32_t c = std::min(q->cap, size[labels[i]]);
+        gs4d_record_stat& s = stats[i];
+        s.pixels += c; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += (uint64_t)c << 24;
+    }
+}
+
+// The definition of gs4d_count_labels (gs4d.h), in place on the table: the labels of the seeds, then one fragment for every record whose label is
+// one of them.  A word >= n is no label.
+void gs4d_host_count_labels(size_t n, const uint32_t* labels, const gs4d_record_stat* seeds, const gs4d_keep_rule* rule, gs4d_record_stat* stats) {
+    if (!rule || rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u) return;
+    const bool invert = (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    std::vector<uint8_t> hit(n, 0);
+    for (size_t j = 0; j < n; ++j) {
+        const gs4d_record_stat& s = seeds[j];
+        if (labels[j] < n && (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert) hit[labels[j]] = 1;
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (!(labels[i] < n && hit[labels[i]])) continue;
+        gs4d_record_stat& s = stats[i];
+        s.pixels += 1u; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += 1ull << 24;
     }
 }
 

@@ -925,8 +925,8 @@ GS4D_API int gs4d_transform_selected(gs4d_ctx* ctx, gs4d_buf data, size_t n, con
  * (tools/neighbours_cost.py): stats is then not written.
  *
  * Out of scope: reading a SoA shadow; a query-side selection (every record that takes part is a query); distances that use the covariance
- * (Mahalanobis, overlap of extents); k-nearest-neighbour distances; connected components, meaning growing to a fixed point in one call; 72-byte
- * quad vertices and 48-byte 2D records; source == stats. */
+ * (Mahalanobis, overlap of extents); k-nearest-neighbour distances; 72-byte quad vertices and 48-byte 2D records; source == stats.  (Connected
+ * components, meaning growing to a fixed point in one call, are gs4d_label_components below.) */
 enum { GS4D_NB_SKIP_HIDDEN = 1, GS4D_NB_SKIP_DEAD = 2, GS4D_NB_COUNT_SELF = 4 };
 typedef struct gs4d_neighbour_query {
     float    t;           /* the time the centres are taken at                                  */
@@ -938,6 +938,75 @@ typedef struct gs4d_neighbour_query {
 GS4D_API int gs4d_count_neighbours(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_neighbour_query* query,
                                    gs4d_buf source /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff source == 0 */,
                                    gs4d_buf stats);
+
+/* ---- connected clusters of a record set: which object a record belongs to (no reference counterpart) ----
+ * gs4d_count_neighbours takes one radius step.  gs4d_label_components grows to the fixed point in one call: it labels every member of a record set
+ * with the smallest record index of its connected component, where two members are linked iff they are near in the sense of
+ * gs4d_count_neighbours, and — optionally — writes the size of its component into every member's row of a gs4d_record_stat table.  Two editor
+ * tools follow.  Select connected ("the object this splat belongs to"): gs4d_count_labels marks every record whose label a seed selection
+ * touches.  Floater clumps ("clusters of fewer than k records"): cap = k into a zeroed table, then the rule {k, 0, 0} with GS4D_KEEP_INVERT for
+ * gs4d_compact_records or gs4d_edit_colours — five records 0.1 r apart and far from everything else each have four neighbours, but a cluster of
+ * five.  gs4d_host_label_components is this text as code: the brute-force double loop with a sequential union–find.
+ *
+ * Centre, Takes part and Near are the texts of gs4d_count_neighbours, word for word (float32, no contraction; GS4D_CC_SKIP_HIDDEN and
+ * GS4D_CC_SKIP_DEAD are GS4D_NB_SKIP_HIDDEN and GS4D_NB_SKIP_DEAD).
+ *
+ * Member.  Record i < n is a member iff it takes part and is selected by exactly the predicate of gs4d_edit_colours: source == 0 selects every
+ * record; otherwise row i of the table `source` must pass `rule`.  A non-member links nothing: a chain whose middle record is hidden (with
+ * GS4D_CC_SKIP_HIDDEN), dead at t (GS4D_CC_SKIP_DEAD), of a non-finite centre or unselected is two components.
+ *
+ * Graph.  Members i != j are linked iff the pair is near: ((d.x * d.x) + (d.y * d.y)) + (d.z * d.z) <= r * r, d = m_i - m_j per component.  The
+ * components are the connected components of that graph; a member without a link is a component of one.
+ *
+ * Label.  labels is n uint32 words.  For a member, labels[i] = the smallest record index in its component (its own, iff it is that record); for
+ * a non-member, labels[i] = GS4D_ID_NONE.  All n words are written; nothing beyond word n - 1 is.
+ *
+ * The row, only if stats != 0.  For a member i, c_i = min(cap, size of its component) >= 1, and row i of stats gets what c_i fragments of weight 1
+ * add in a draw, exactly as in gs4d_count_neighbours: pixels += c_i; wmax = max(wmax, 0x3F800000); wsum += (uint64) c_i << 24.  A non-member's row
+ * keeps its bits.  The call ADDS: nothing zeroes the table.  No byte beyond row n - 1 is written, and no byte of data or source is written.
+ * Every output depends on a set and not on an order: the same inputs give the same bytes, whatever runs first.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: the list of gs4d_count_neighbours (query == NULL; a flag other than GS4D_CC_*; a non-zero
+ * reserved word; cap == 0; a radius outside 2^-63 <= r < 2^64; n >= 0xFFFFFFFF; data not a live buffer or smaller than 96 n bytes; exactly one of
+ * source / rule given; a rule with an unknown flag or reserved != 0; source not a live buffer or smaller than 16 n bytes); labels not a live buffer
+ * or smaller than 4 n bytes (labels may not be 0); stats, when given, not a live buffer or smaller than 16 n bytes; any two of the four buffers
+ * being the same buffer.  n == 0 with otherwise valid arguments is a no-op.  t is data, not an error.
+ *
+ * Ordering.  As in gs4d_count_neighbours: data and source are read, and draws that add to source, issued before the call on any frame lane, are
+ * settled first; a draw issued afterwards that adds to it waits on the device until the kernels have read it.  labels is a kernel write of all n
+ * words.  stats is a kernel write that keeps the contents.  A queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched
+ * first.  The kernels are queued on the current frame lane; the call returns at once and starts no frame.  gs4d_buffer_invalidate hand-offs of
+ * all four buffers are honoured.  The call reads the 96-byte records: it never builds, reads or invalidates a SoA shadow.
+ *
+ * Cost.  The hashed grid of gs4d_count_neighbours (keys, sort, bucket table), then a lock-free union–find over the same walk of at most 27 cells:
+ * every near pair is united once, by its larger index (DESIGN.md §4 has the kernels and why the labels are unique though the order of the unions
+ * is not).  The walk is that of gs4d_count_neighbours without a cap: many members inside one cell of edge 2 r cost O(candidates) per member.  The
+ * lane's scratch is that of gs4d_count_neighbours; GS4D_NEIGHBOURS_PHASES does not apply.  Every loop of the union–find carries a trip bound; if
+ * one ever runs out the lane's device-side check is raised and gs4d_finish reports it.
+ *
+ * gs4d_count_labels: what a selection touches, by label.  A label L is hit iff L < n and some j < n has labels[j] == L and row j of the table
+ * `seeds` passing `rule`.  Row i < n of stats gets one fragment of weight 1 (the row update of gs4d_count_centres) iff labels[i] is hit; every
+ * other row keeps its bits.  A word >= n counts as GS4D_ID_NONE, whatever it holds: it is neither hit nor does it hit, and no byte outside the
+ * buffers is touched.  Labels are computed once per edit state and clicked on many times, hence a call of its own.  gs4d_host_count_labels is
+ * this text as code.  GS4D_E_INVALID, with nothing queued and nothing written: n > 0xFFFFFFFF; labels, seeds or stats not a live buffer; labels
+ * smaller than 4 n bytes; seeds or stats smaller than 16 n bytes; rule == NULL, or with an unknown flag or reserved != 0; any two of the three
+ * buffers being the same buffer.  n == 0 is a no-op.  Ordering: labels is read; seeds is read as gs4d_edit_colours reads its table (draws that
+ * add to it are settled first); stats is a kernel write that keeps the contents.  The lane keeps n words of scratch.
+ *
+ * Out of scope: components over a SoA shadow; links that use the covariance; k-nearest-neighbour graphs; relabelling incrementally after an edit;
+ * 72-byte quad vertices and 48-byte 2D records. */
+enum { GS4D_CC_SKIP_HIDDEN = 1, GS4D_CC_SKIP_DEAD = 2 };
+typedef struct gs4d_component_query {
+    float    t;           /* the time the centres are taken at                                  */
+    float    radius;      /* r: two members are linked iff they are near                        */
+    uint32_t cap;         /* the size written to a row saturates here; >= 1                     */
+    uint32_t flags;       /* OR of GS4D_CC_*; any other bit: GS4D_E_INVALID                     */
+    uint32_t reserved[4]; /* must be 0                                                          */
+} gs4d_component_query;   /* 32 bytes */
+GS4D_API int gs4d_label_components(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_component_query* query,
+                                   gs4d_buf source /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff source == 0 */,
+                                   gs4d_buf labels /* n uint32 */, gs4d_buf stats /* 0: labels only */);
+GS4D_API int gs4d_count_labels(gs4d_ctx* ctx, gs4d_buf labels, size_t n, gs4d_buf seeds, const gs4d_keep_rule* rule, gs4d_buf stats);
 
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
@@ -1024,6 +1093,15 @@ GS4D_API void gs4d_host_transform_selected(size_t n, float* records24, const gs4
  * nothing. */
 GS4D_API void gs4d_host_count_neighbours(size_t n, const float* records24, const gs4d_neighbour_query* query,
                                          const gs4d_record_stat* source, const gs4d_keep_rule* rule, gs4d_record_stat* stats);
+/* The definition of gs4d_label_components (the text above its declaration): the brute-force double loop over every pair of members, a sequential
+ * union–find, then the n words of labels and — stats != NULL — the rows of the members.  source == NULL selects every record (rule is then
+ * ignored), else rule is not NULL.  A query the device call would refuse (NULL, an unknown flag, a non-zero reserved word, cap == 0, a radius
+ * outside 2^-63 <= r < 2^64, a rule with an unknown flag or reserved != 0) changes nothing: labels is not written either. */
+GS4D_API void gs4d_host_label_components(size_t n, const float* records24, const gs4d_component_query* query,
+                                         const gs4d_record_stat* source, const gs4d_keep_rule* rule, uint32_t* labels, gs4d_record_stat* stats);
+/* The definition of gs4d_count_labels, in place on the n rows of stats.  rule == NULL, or one with an unknown flag or reserved != 0, changes nothing. */
+GS4D_API void gs4d_host_count_labels(size_t n, const uint32_t* labels, const gs4d_record_stat* seeds, const gs4d_keep_rule* rule,
+                                     gs4d_record_stat* stats);
 /* "Frame selection": the eye from which a camera of gs4d_host_look_at(eye, orientation, up) and gs4d_host_perspective(fov_deg, width, height, ..)
  * sees the whole box lo .. hi with its centre in the middle of the image.  The box's bounding sphere (centre (lo + hi) / 2, radius half the
  * diagonal; a degenerate box — a radius that is zero or not finite — gets radius 1) is fitted into the narrower of the projection's two
