@@ -32,6 +32,7 @@ MS_SKIP_HIDDEN, MS_SKIP_DEAD = 1, 2                        # gs4d_measure_query.
 XS_PIVOT, XS_PIVOT_MEASURE = 1, 2                          # gs4d_selection_xf.flags
 NB_SKIP_HIDDEN, NB_SKIP_DEAD, NB_COUNT_SELF = 1, 2, 4      # gs4d_neighbour_query.flags
 CC_SKIP_HIDDEN, CC_SKIP_DEAD = 1, 2                        # gs4d_component_query.flags
+NN_SKIP_HIDDEN, NN_SKIP_DEAD, NN_INCLUDE_SELF = 1, 2, 4    # gs4d_nearest_query.flags
 ID_NONE = 0xFFFFFFFF                                       # GS4D_ID_NONE: the label of a record that is no member
 TIME_DEAD_ARG = -106.0                                    # GS4D_TIME_DEAD_ARG: no float32 exponential is non-zero below this argument
 STAGES = ("keygen", "sort", "preprocess", "binning", "pairsort", "composite")
@@ -111,6 +112,7 @@ def _load():
         "gs4d_count_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_label_components": (i32, [vp, u32, sz, vp, u32, vp, u32, u32]),
         "gs4d_count_labels": (i32, [vp, u32, sz, u32, vp, u32]),
+        "gs4d_nearest_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32, sz, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -143,6 +145,7 @@ def _load():
         "gs4d_host_count_neighbours": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_label_components": (None, [sz, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_count_labels": (None, [sz, vp, vp, vp, vp]),
+        "gs4d_host_nearest_neighbours": (None, [sz, vp, vp, vp, vp, vp, sz, vp]),
         "gs4d_host_frame_box": (None, [vp, vp, vp, f32, i32, i32, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
@@ -729,6 +732,89 @@ def count_labels_host(labels, seeds, stats=None, n=None, **rule):
     return st
 
 
+class NearestQuery(C.Structure):
+    """gs4d_nearest_query (include/gs4d.h): the time, the radius, k and the flags of a gs4d_nearest_neighbours call; 32 bytes."""
+    _fields_ = [("t", C.c_float), ("radius", C.c_float), ("k", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 4)]
+
+
+HIT = np.dtype([("record", "<u4"), ("dist2", "<f4")])      # gs4d_neighbour_hit; an empty slot is {ID_NONE, +inf}
+
+
+def nearest_query(radius, k, t=0.0, skip_hidden=False, skip_dead=False, include_self=False):
+    """one gs4d_nearest_query (NearestQuery): centres at time t, the k (1 .. 16) nearest sources within `radius` (float32; 2^-63 <= radius <
+    2^64); skip_hidden / skip_dead: records of alpha <= 0 / dead at t take no part; include_self: a record that is a source is its own hit."""
+    q = NearestQuery()
+    q.t, q.radius, q.k = float(t), float(np.float32(radius)), int(k)
+    q.flags = (NN_SKIP_HIDDEN if skip_hidden else 0) | (NN_SKIP_DEAD if skip_dead else 0) | (NN_INCLUDE_SELF if include_self else 0)
+    return q
+
+
+def hit_stride_for(k):
+    """the smallest hit_stride that holds k hits: 8 k bytes rounded up to a multiple of 16"""
+    return 16 * ((8 * int(k) + 15) // 16)
+
+
+def nearest_neighbours_host(records, radius=None, k=3, t=0.0, source=None, skip_hidden=False, skip_dead=False, include_self=False, hits=None,
+                            hit_stride=None, stats=None, with_stats=True, query=None, **rule):
+    """gs4d_host_nearest_neighbours, the definition of Context.nearest_neighbours — the brute-force double loop: (the hit table as uint8
+    [n, hit_stride] — a copy of `hits`, or zeroed bytes if None; row[:8 k].view(HIT) are the slots — and the RECORD_STAT table after the call — a
+    copy of `stats`, or n zeroed rows if None; None with with_stats=False) on records [n, 24].  hit_stride: default hit_stride_for(k).  source: a
+    table of n rows of 16 bytes whose row j makes record j a source by compact_records' rule keywords, or None: every record (and no rule); query:
+    a NearestQuery instead of the radius, k and the other keywords.  A call the device would refuse leaves both tables as they were."""
+    rec = _f32(records).reshape(-1, 24)
+    n = rec.shape[0]
+    if source is None and rule:
+        raise TypeError("nearest_neighbours_host: a rule without source")
+    if query is None:
+        if radius is None:
+            raise TypeError("nearest_neighbours_host: radius or query is needed")
+        query = nearest_query(radius, k, t, skip_hidden, skip_dead, include_self)
+    if hit_stride is None:
+        hit_stride = hit_stride_for(query.k)
+    hit_stride = int(hit_stride)
+    ht = np.zeros((n, max(hit_stride, 1)), np.uint8) if hits is None else np.array(np.ascontiguousarray(hits).view(np.uint8).reshape(n, -1), copy=True)
+    if ht.shape[1] != max(hit_stride, 1):
+        raise ValueError("nearest_neighbours_host: hits must be n rows of hit_stride bytes")
+    st = None
+    if with_stats:
+        st = np.zeros(n, RECORD_STAT) if stats is None else np.array(np.ascontiguousarray(stats), copy=True)
+        if st.dtype.itemsize != 16 or st.ndim != 1 or st.shape[0] < n:
+            raise ValueError("nearest_neighbours_host: stats must be at least n rows of 16 bytes")
+        st = st.view(RECORD_STAT)
+    src = None if source is None else np.ascontiguousarray(source)
+    if src is not None and (src.dtype.itemsize != 16 or src.ndim != 1 or src.shape[0] < n):
+        raise ValueError("nearest_neighbours_host: source must be at least n rows of 16 bytes")
+    kr = _keep_rule(**rule)
+    _lib.gs4d_host_nearest_neighbours(n, _ptr(rec), C.byref(query), _ptr(src) if src is not None else None, _ptr(kr) if src is not None else None,
+                                      _ptr(ht), hit_stride, _ptr(st) if st is not None else None)
+    return ht, st
+
+
+def hits_of(table, k):
+    """the (n, k) HIT view of a hit table given as uint8 [n, hit_stride] (nearest_neighbours_host's, or Context.read of the buffer)"""
+    t = np.ascontiguousarray(table, np.uint8)
+    return np.ascontiguousarray(t[:, :8 * int(k)]).view(HIT).reshape(t.shape[0], int(k))
+
+
+def knn_mean_dist2(hits_array, radius=None):
+    """float32 [n]: the mean of the filled dist2 of each row of an (n, k) HIT array (a slot is filled iff its record is not ID_NONE) — the sum in
+    slot order in float32, divided by the count; a row without a filled slot gets radius ** 2 in float32 (radius is needed then).  With k = 3
+    over a point cloud this is the quantity 3DGS-style pipelines initialise scales from (distCUDA2 of simple-knn), restricted to a radius: a
+    point with fewer than 3 points within the radius averages those it has."""
+    h = np.asarray(hits_array)
+    filled = h["record"] != ID_NONE
+    cnt = filled.sum(1)
+    if radius is None and (cnt == 0).any():
+        raise ValueError("knn_mean_dist2: a row without hits needs the radius")
+    s = np.zeros(h.shape[0], np.float32)
+    for p in range(h.shape[1]):
+        s = (s + np.where(filled[:, p], h["dist2"][:, p], np.float32(0.0))).astype(np.float32)
+    fallback = np.float32(radius if radius is not None else 0.0) * np.float32(radius if radius is not None else 0.0)
+    with np.errstate(all="ignore"):
+        mean = (s / np.maximum(cnt, 1).astype(np.float32)).astype(np.float32)
+    return np.where(cnt > 0, mean, np.float32(fallback)).astype(np.float32)
+
+
 def frame_box(lo, hi, orientation, fov_deg, width, height):
     """gs4d_host_frame_box: the eye from which look_at(eye, orientation) and perspective(fov_deg, width, height, ..) show the whole box lo .. hi,
     its centre in the middle of the image ("frame selection": lo, hi of a Measure)."""
@@ -1307,6 +1393,54 @@ class Context:
         stats = self.record_stats(n)
         self.count_labels(stats, n, labels, seeds, **rule)
         return labels, stats
+
+    # the k nearest sources of every record: a neighbour list, a density-adaptive distance
+    HIT = HIT
+
+    def nearest_neighbours(self, n, data, radius=None, k=3, t=0.0, source=None, skip_hidden=False, skip_dead=False, include_self=False, hits=None,
+                           hit_stride=None, stats=None, query=None, **rule):
+        """gs4d_nearest_neighbours: the first k HIT slots of row i of `hits` (rows hit_stride bytes apart; a new buffer of n rows if None;
+        hit_stride: default hit_stride_for(k), else a multiple of 16 up to 1024 that is at least 8 k) <- the k (1 .. 16) source records nearest to
+        record i < n of `data` among those whose centre at time t lies within `radius` of its own, ordered by (dist2, record index); empty slots,
+        and all k of a record that takes no part, are {ID_NONE, +inf}; bytes of a row past 8 k keep their contents.  stats: a record_stats buffer
+        whose row i gets pixels += hits found, wmax = max(wmax, dist2 of the last of them), wsum += found << 24 (None: hits only); nothing zeroes
+        it.  source: a record_stats buffer whose row j makes record j a source by compact_records' rule keywords (None: every record, and no
+        rule); include_self: a source is its own hit; query: a NearestQuery instead of the radius, k and the other keywords.  With the bits of
+        nearest_neighbours_host, from a hashed grid instead of its double loop.  Asynchronous; returns `hits`, or (hits, stats) with a table."""
+        if source is None and rule:
+            raise TypeError("nearest_neighbours: a rule without source")
+        if query is None:
+            if radius is None:
+                raise TypeError("nearest_neighbours: radius or query is needed")
+            query = nearest_query(radius, k, t, skip_hidden, skip_dead, include_self)
+        if hit_stride is None:
+            hit_stride = hit_stride_for(query.k)
+        kr = _keep_rule(**rule) if source is not None else None
+        if hits is None:
+            hits = self.buffer(nbytes=max(16, int(n) * int(hit_stride)))
+        self._chk(_lib.gs4d_nearest_neighbours(self._h, int(data), int(n), C.byref(query), int(source or 0), _ptr(kr) if kr is not None else None, int(hits),
+                                               int(hit_stride), int(stats or 0)))
+        return hits if stats is None else (hits, stats)
+
+    def read_hits(self, hits, n, k, hit_stride=None):
+        """The (n, k) HIT array {record, dist2} of a nearest_neighbours table of stride hit_stride (default hit_stride_for(k)); blocks until the
+        kernels have finished."""
+        hit_stride = hit_stride_for(k) if hit_stride is None else int(hit_stride)
+        if int(n) == 0:
+            return np.zeros((0, int(k)), HIT)
+        return hits_of(self.read(hits, np.uint8, int(n) * hit_stride).reshape(int(n), hit_stride), k)
+
+    def sparse_records(self, n, data, radius, k, t=0.0, skip_hidden=False, skip_dead=False):
+        """Density-adaptive floaters: (hits, a fresh zeroed table filled by one nearest_neighbours call) — per record that takes part, pixels =
+        the number of other records found within `radius` (at most k) and wmax = the dist2 of the last of them.  Three selections follow without
+        another kernel:
+            compact_records(stats, n, min_pixels=k, invert=True)        fewer than k records within radius
+            compact_records(stats, n, min_wmax=x)                       the k-th neighbour (or the last one found) at dist2 >= x
+            prune_to_budget(stats, n, data, K, field="wmax")            the K records whose k-th neighbour is farthest (stat_cut over wmax)
+        — the last is the floater tool for a set whose density varies, where isolated() needs one radius for all of it.  Asynchronous."""
+        stats = self.record_stats(n)
+        hits = self.nearest_neighbours(n, data, radius, k, t=t, skip_hidden=skip_hidden, skip_dead=skip_dead, stats=stats)[0]
+        return hits, stats
 
     # time windows: the records of a 4D set that can show anything between two times (DESIGN.md §4)
     TIME_SPAN =np.dtype([("t_first", "<f4"), ("t_last", "<f4")])

@@ -137,7 +137,7 @@ struct Lane {
     uint32_t* spatial_scratch = nullptr; size_t spatial_cap = 0;      // gs4d_spatial_order: the box and its partials (order_box_words()), then one key per record; the lane's stream orders its reuse
     uint32_t* cut_scratch = nullptr; size_t cut_cap = 0;               // gs4d_stat_cut: the state block and one partial histogram per workgroup (cut_scratch_words()); the lane's stream orders its reuse
     uint32_t* measure_scratch = nullptr; size_t measure_cap = 0;       // gs4d_measure_records: one partial row per workgroup (measure_scratch_words()); the lane's stream orders its reuse
-    uint32_t* neighbour_scratch = nullptr; size_t neighbour_cap = 0;   // gs4d_count_neighbours and gs4d_label_components: candidates, bucket table, keys and sorted indices (neighbour_scratch_words()); gs4d_count_labels: n flag words; the lane's stream orders its reuse
+    uint32_t* neighbour_scratch = nullptr; size_t neighbour_cap = 0;   // gs4d_count_neighbours, gs4d_label_components and gs4d_nearest_neighbours: candidates, bucket table, keys and sorted indices (neighbour_scratch_words()); gs4d_count_labels: n flag words; the lane's stream orders its reuse
     uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
     uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
     gs4d_buf kg_buf = 0; uint64_t kg_ver = 0;         // key buffer whose digit histograms k_keygen left for the next sort
@@ -2162,6 +2162,52 @@ int gs4d_count_labels(gs4d_ctx* c, gs4d_buf labels, size_t n, gs4d_buf seeds, co
             { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
             HIPCHK(c, launch_count_labels(L.s, (const uint32_t*)B->d, n, (const gs4d_record_stat*)Q->d, k, L.neighbour_scratch, (gs4d_record_stat*)S->d));
             return scan_end(c, L, *Q);
+        });
+}
+
+// ---- the k nearest sources of every record: a table of hits, optionally the count and the last distance as a statistics table ----
+int gs4d_nearest_neighbours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_nearest_query* query, gs4d_buf source, const gs4d_keep_rule* rule, gs4d_buf hits,
+                            size_t hit_stride, gs4d_buf stats) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("nearest_neighbours: ") + msg).c_str()); };
+    if (!query) return bad("query == NULL");
+    const gs4d_nearest_query q = *query;
+    if ((q.flags & ~(uint32_t)(GS4D_NN_SKIP_HIDDEN | GS4D_NN_SKIP_DEAD | GS4D_NN_INCLUDE_SELF)) != 0u) return bad("unknown flag");
+    if (q.reserved[0] != 0u || q.reserved[1] != 0u || q.reserved[2] != 0u || q.reserved[3] != 0u) return bad("non-zero reserved field in the query");
+    if (q.k == 0u || q.k > 16u) return bad("k must be 1 to 16");
+    if (!neighbour_radius_ok(q.radius)) return bad("the radius must be finite with 2^-63 <= radius < 2^64");
+    if (n >= 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
+    if ((source != 0) != (rule != nullptr)) return bad("source and rule are given together or not at all");
+    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
+    const gs4d_buf names[4] = { data, hits, stats, source };
+    Buffer* D = getbuf(c, data); Buffer* B = getbuf(c, hits);
+    if (!D || !B) return bad("data and hits must name live buffers");
+    if (!record_stride_ok(hit_stride) || hit_stride < 8 * (size_t)q.k) return bad("hit_stride must be a multiple of 16 from 16 to 1024 that is at least 8 k");
+    if (const int wrong = check_record_names(c, names, 4)) return bad(wrong == 1 ? "bad buffer name" : "data, source, hits and stats must be different buffers");
+    Buffer* S = getbuf(c, stats); Buffer* Q = getbuf(c, source);
+    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
+    if (B->bytes / hit_stride < n) return bad("hits holds fewer than n rows of hit_stride bytes");
+    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (Q && Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the source buffer holds fewer than n rows");
+    if (n == 0) return GS4D_OK;
+    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
+    { int rc = flush_order_if_named(c, names, 4); if (rc) return rc; }
+    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    if (Q) { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
+    // as gs4d_label_components: data and source are read (the 96-byte records, never a shadow); the slots of hits are written, stats is a
+    // read-modify-write the lane has the table to itself for — both "out" of queue_on_lane
+    return queue_on_lane(c, { D, Q }, { B, S },
+        [&](Lane& L) {
+            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, neighbour_scratch_words(n)));
+            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));
+            return Q ? scan_reserve(c, *Q) : (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            if (Q) { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
+            HIPCHK(c, launch_nearest_neighbours(L.s, L.pair_sort, D->d, n, q, Q ? (const gs4d_record_stat*)Q->d : nullptr, k, L.neighbour_scratch, B->d, hit_stride,
+                                                S ? (gs4d_record_stat*)S->d : nullptr));
+            return Q ? scan_end(c, L, *Q) : (int)GS4D_OK;
         });
 }
 

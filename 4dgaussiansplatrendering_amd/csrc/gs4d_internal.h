@@ -543,6 +543,15 @@ constexpr uint32_t COMPONENTS_TILE = 256;
 hipError_t launch_label_components(hipStream_t st, SortScratch& sort, const void* records, size_t n, const gs4d_component_query& q,
                                    const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, uint32_t* labels, gs4d_record_stat* stats,
                                    uint32_t* err);
+// gs4d_nearest_neighbours (gs4d.h; nearest.hip): the first q.k gs4d_neighbour_hit slots of row i < n of hits (rows hit_stride bytes
+// apart, a multiple of 16 that is at least 8 q.k) <- the q.k nearest sources of launch_neighbour_grid within q.radius of record i by (bits(dist2),
+// index), {GS4D_ID_NONE, +inf} behind them; stats != null: row i gets the number of hits and the dist2 bits of the last one.  q: validated.  The
+// grid phases, then one query kernel on `st`; no workgroup waits for another.  scratch: neighbour_scratch_words(n) words.  Nothing but those slots,
+// rows < n of stats and the scratch is written.
+constexpr uint32_t NEAREST_TILE = 256;
+hipError_t launch_nearest_neighbours(hipStream_t st, SortScratch& sort, const void* records, size_t n, const gs4d_nearest_query& q,
+                                     const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, void* hits, size_t hit_stride,
+                                     gs4d_record_stat* stats);
 // gs4d_count_labels (gs4d.h): row i < n of stats gets one fragment of weight 1 iff labels[i] < n is the label of some j < n whose row of `seeds`
 // passes `rule`.  flags: n words of scratch (the lane's).  A memset and two kernels on `st`.  Nothing but rows < n of stats and the flags is written.
 hipError_t launch_count_labels(hipStream_t st, const uint32_t* labels, size_t n, const gs4d_record_stat* seeds, const KeepRule& rule, uint32_t* flags,

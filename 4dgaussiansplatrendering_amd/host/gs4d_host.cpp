@@ -25,6 +25,7 @@
 #include "../csrc/measure_record.h"
 #include "../csrc/neighbour_query.h"
 #include "../csrc/component_union.h"
+#include "../csrc/nearest_query.h"
 
 namespace {
 
@@ -621,6 +622,51 @@ void gs4d_host_count_labels(size_t n, const uint32_t* labels, const gs4d_record_
         if (!(labels[i] < n && hit[labels[i]])) continue;
         gs4d_record_stat& s = stats[i];
         s.pixels += 1u; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += 1ull << 24;
+    }
+}
+
+// The definition of gs4d_nearest_neighbours (gs4d.h): the brute-force double loop over the texts of csrc/neighbour_query.h and
+// csrc/nearest_query.h, which the kernels compile too (this file is built with -ffp-contract=off) — every source that is near goes into the sorted
+// list of the 16 smallest (bits(dist2), j), of which the first k are the row.  No search structure.  A call the device would refuse for its
+// query, rule or hit_stride changes nothing.
+void gs4d_host_nearest_neighbours(size_t n, const float* rec, const gs4d_nearest_query* q, const gs4d_record_stat* source, const gs4d_keep_rule* rule,
+                                  void* hits, size_t hit_stride, gs4d_record_stat* stats) {
+    namespace nb = gs4d_neighbour;
+    namespace nn = gs4d_nearest;
+    if (!q || !nn::query_ok(*q) || !nn::stride_ok(hit_stride, q->k) || n >= 0xFFFFFFFFull || (source && !rule)) return;
+    if (source && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return;
+    const bool invert = source && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    const bool self = (q->flags & (uint32_t)GS4D_NN_INCLUDE_SELF) != 0u;
+    const uint32_t skips = q->flags & (uint32_t)(GS4D_NN_SKIP_HIDDEN | GS4D_NN_SKIP_DEAD);
+    const float rr = q->radius * q->radius;
+    std::vector<float> m(3 * n);
+    std::vector<uint8_t> part(n), src(n);
+    for (size_t i = 0; i < n; ++i) {
+        const float* p = rec + 24 * i;
+        const nb::Fields r{ { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] };
+        part[i] = nb::takes_part(q->t, skips, r, &m[3 * i]);
+        src[i] = part[i];
+        if (src[i] && source) {
+            const gs4d_record_stat& s = source[i];
+            src[i] = (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert;
+        }
+    }
+    for (size_t i = 0; i < n; ++i) {
+        uint64_t best[nn::K_MAX];
+        for (uint64_t& b : best) b = nn::EMPTY;
+        if (part[i])
+            for (size_t j = 0; j < n; ++j)
+                if (src[j] && (j != i || self) && nb::near(&m[3 * i], &m[3 * j], rr)) nn::insert(best, nn::order_key(nn::dist2(&m[3 * i], &m[3 * j]), (uint32_t)j));
+        unsigned char* const row = (unsigned char*)hits + i * hit_stride;
+        uint32_t f = 0;
+        for (uint32_t p = 0; p < q->k; ++p) {
+            const uint32_t slot[2] = { (uint32_t)best[p], (uint32_t)(best[p] >> 32) };      // {record, bits(dist2)}: a gs4d_neighbour_hit
+            std::memcpy(row + 8 * p, slot, 8);
+            if (best[p] != nn::EMPTY) f = p + 1u;
+        }
+        if (!stats || f == 0u) continue;
+        gs4d_record_stat& s = stats[i];
+        s.pixels += f; s.wmax = std::max(s.wmax, (uint32_t)(best[f - 1u] >> 32)); s.wsum += (uint64_t)f << 24;
     }
 }
 

@@ -21,7 +21,7 @@ $(FLAGSTAMP):
 	rm -f $(CSRC)/.flags.*
 	touch $@
 
-OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/neighbours.o $(CSRC)/components.o $(HOST)/gs4d_host.o
+OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
 
 .PHONY: all lib oracle ref refscene refdraw refgl clean demo sweep
 all: lib oracle demo sweep
@@ -64,6 +64,9 @@ $(CSRC)/neighbours.o: $(CSRC)/neighbours.hip $(CSRC)/neighbour_query.h $(CSRC)/c
 # gs4d_label_components walks the grid of neighbours.hip with the same `near`; component_union.h is the one text of its union-find (the host library and tests/component_union_stress.cpp compile it too)
 $(CSRC)/components.o: $(CSRC)/components.hip $(CSRC)/component_union.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+# gs4d_nearest_neighbours walks the grid of neighbours.hip too; nearest_query.h is the one text of its order key, its dist2 and its sorted insertion (the host library compiles it too)
+$(CSRC)/nearest.o: $(CSRC)/nearest.hip $(CSRC)/nearest_query.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # make BUILD_PLAIN=1: gs4d_build_records with every thread storing its own record, without the LDS staging (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/build.o: $(CSRC)/build.hip $(CSRC)/build_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(BUILD_PLAIN),-DGS4D_BUILD_PLAIN) -c $< -o $@
@@ -78,7 +81,7 @@ $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Make
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(COUNT_IDS_PLAIN),-DGS4D_COUNT_IDS_PLAIN) -c $< -o $@
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gs4d_internal.h $(CSRC)/composite_common.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h include/gs4d.h
+$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -fvisibility=hidden $(STRICT) -x c++ -c $< -o $@
 
 $(LIB): $(OBJS)

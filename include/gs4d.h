@@ -925,8 +925,8 @@ GS4D_API int gs4d_transform_selected(gs4d_ctx* ctx, gs4d_buf data, size_t n, con
  * (tools/neighbours_cost.py): stats is then not written.
  *
  * Out of scope: reading a SoA shadow; a query-side selection (every record that takes part is a query); distances that use the covariance
- * (Mahalanobis, overlap of extents); k-nearest-neighbour distances; 72-byte quad vertices and 48-byte 2D records; source == stats.  (Connected
- * components, meaning growing to a fixed point in one call, are gs4d_label_components below.) */
+ * (Mahalanobis, overlap of extents); 72-byte quad vertices and 48-byte 2D records; source == stats.  (Connected components, meaning growing
+ * to a fixed point in one call, are gs4d_label_components below; the k nearest sources and their distances are gs4d_nearest_neighbours.) */
 enum { GS4D_NB_SKIP_HIDDEN = 1, GS4D_NB_SKIP_DEAD = 2, GS4D_NB_COUNT_SELF = 4 };
 typedef struct gs4d_neighbour_query {
     float    t;           /* the time the centres are taken at                                  */
@@ -993,7 +993,7 @@ GS4D_API int gs4d_count_neighbours(gs4d_ctx* ctx, gs4d_buf data, size_t n, const
  * buffers being the same buffer.  n == 0 is a no-op.  Ordering: labels is read; seeds is read as gs4d_edit_colours reads its table (draws that
  * add to it are settled first); stats is a kernel write that keeps the contents.  The lane keeps n words of scratch.
  *
- * Out of scope: components over a SoA shadow; links that use the covariance; k-nearest-neighbour graphs; relabelling incrementally after an edit;
+ * Out of scope: components over a SoA shadow; links that use the covariance; components of the kNN graph; relabelling incrementally after an edit;
  * 72-byte quad vertices and 48-byte 2D records. */
 enum { GS4D_CC_SKIP_HIDDEN = 1, GS4D_CC_SKIP_DEAD = 2 };
 typedef struct gs4d_component_query {
@@ -1007,6 +1007,75 @@ GS4D_API int gs4d_label_components(gs4d_ctx* ctx, gs4d_buf data, size_t n, const
                                    gs4d_buf source /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff source == 0 */,
                                    gs4d_buf labels /* n uint32 */, gs4d_buf stats /* 0: labels only */);
 GS4D_API int gs4d_count_labels(gs4d_ctx* ctx, gs4d_buf labels, size_t n, gs4d_buf seeds, const gs4d_keep_rule* rule, gs4d_buf stats);
+
+/* ---- the k nearest sources of every record: a neighbour list and a density-adaptive distance (no reference counterpart) ----
+ * gs4d_count_neighbours says how many sources are near a record and gs4d_label_components which cluster it belongs to; both discard WHICH sources
+ * those are.  gs4d_nearest_neighbours keeps them: for every record the k nearest sources within r, as a row of {record, dist2} hits in a table of
+ * the caller's stride, and — optionally — the squared distance to the last of them in a gs4d_record_stat table.  Three tools follow.  Scales for
+ * records built from points: the mean dist2 of the 3 nearest points is what 3DGS-style pipelines initialise the scales of gs4d_build_records from.
+ * Floaters where the density varies: one radius for gs4d_count_neighbours either marks a sparse background or finds nothing in it; the distance to
+ * the k-th neighbour adapts.  A neighbour list per record: what smoothing, colour propagation from a selection and as-rigid-as-possible drags start
+ * from.  gs4d_host_nearest_neighbours is this text as code: the brute-force double loop.
+ *
+ * Centre, Takes part, Source and Near are the texts of gs4d_count_neighbours, word for word: float32, round to nearest, no contraction;
+ * GS4D_NN_SKIP_HIDDEN and GS4D_NN_SKIP_DEAD are GS4D_NB_SKIP_HIDDEN and GS4D_NB_SKIP_DEAD; the pair (i, j) is near iff
+ *     ((d.x * d.x) + (d.y * d.y)) + (d.z * d.z) <= r * r,   d = m_i - m_j per component, r * r rounded once.
+ *
+ * Candidates.  The candidates of a record i that takes part are the sources j < n near i, with j != i unless GS4D_NN_INCLUDE_SELF.  Each has
+ *     dist2 = ((d.x * d.x) + (d.y * d.y)) + (d.z * d.z),
+ * the very value `near` compared.  It is >= +0 and not a NaN, so its bit pattern is in float order.
+ *
+ * Order.  Candidates are ordered by (bits(dist2), j) ascending: by distance, equal distances by record index.  The key is unique per j, so the
+ * first k candidates are a property of the set; nothing depends on the order in which anything runs.
+ *
+ * Row.  Row i is the hit_stride bytes at hits + i * hit_stride.  Its first k gs4d_neighbour_hit slots receive the first f_i = min(k, #candidates)
+ * candidates in that order, {j, dist2}; the remaining ones of the k receive {GS4D_ID_NONE, +inf}.  A record that does not take part gets k such
+ * empty slots.  All n rows are written; bytes of a row past 8 k keep their contents, and nothing past row n - 1 is written.  hit_stride follows
+ * the stride rule of every record call — a multiple of 16 from 16 to 1024 — with hit_stride >= 8 k: gs4d_gather_records, gs4d_compact_records and
+ * gs4d_compact_time_window then carry the table along with the records.  k is 1 .. 16.
+ *
+ * The row of stats, only if stats != 0.  A record that takes part and has f_i >= 1 gets: pixels += f_i; wmax = max(wmax, bits(dist2 of its last
+ * filled slot)), compared as the unsigned words they are; wsum += (uint64) f_i << 24.  Every other row keeps its bits.  The call ADDS: nothing
+ * zeroes the table.  Into a zeroed table this buys three selections without another kernel: the rule {k, 0, 0} with GS4D_KEEP_INVERT selects
+ * "fewer than k sources within r" (gs4d_count_neighbours' floaters); min_wmax = bits(x) selects "k-th neighbour — or the last one found — farther
+ * than about sqrt(x)" (>= in bits); and gs4d_stat_cut over GS4D_STAT_WMAX gives the threshold for "the K records whose k-th neighbour is
+ * farthest", ready for gs4d_compact_records or gs4d_edit_colours.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: the list of gs4d_count_neighbours with k == 0 || k > 16 in the place of cap == 0
+ * (query == NULL; a flag other than GS4D_NN_*; a non-zero reserved word; a radius outside 2^-63 <= r < 2^64; n >= 0xFFFFFFFF; data not a live
+ * buffer or smaller than 96 n bytes; exactly one of source / rule given; a rule with an unknown flag or reserved != 0; source not a live buffer
+ * or smaller than 16 n bytes); hits not a live buffer, or smaller than n * hit_stride bytes; a hit_stride that is not a multiple of 16 in
+ * 16 .. 1024 or is below 8 k; stats, when given, not a live buffer or smaller than 16 n bytes; any two of the four buffers being the same buffer.
+ * n == 0 with otherwise valid arguments is a no-op.  t is data, not an error.
+ *
+ * Ordering.  As in gs4d_label_components: data and source are read, and draws that add to source, issued before the call on any frame lane, are
+ * settled first; a draw issued afterwards that adds to it waits on the device until the kernels have read it.  hits is a kernel write.  stats is
+ * a kernel write that keeps the contents.  A queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first.  The kernels
+ * are queued on the current frame lane; the call returns at once and starts no frame.  gs4d_buffer_invalidate hand-offs of all four buffers are
+ * honoured.  The call reads the 96-byte records: it never builds, reads or invalidates a SoA shadow.
+ *
+ * Cost.  The hashed grid of gs4d_count_neighbours (keys, sort, bucket table), then one walk of at most 27 cells per record without a cap and
+ * without an early exit — every candidate that is near competes — with the k best kept in registers, and one scattered row write (DESIGN.md §4 has
+ * the kernel, the measured times beside gs4d_count_neighbours, and why the rows are unique though the walk order is not).  The lane's scratch is
+ * that of gs4d_count_neighbours; GS4D_NEIGHBOURS_PHASES does not apply.
+ *
+ * Out of scope: a search without a radius (a record with fewer than k sources within r gets fewer hits — the caller chooses r); k > 16;
+ * distances that use the covariance; reading a SoA shadow; 72-byte quad vertices and 48-byte 2D records. */
+enum { GS4D_NN_SKIP_HIDDEN = 1, GS4D_NN_SKIP_DEAD = 2, GS4D_NN_INCLUDE_SELF = 4 };   /* the values of GS4D_NB_* */
+typedef struct gs4d_nearest_query {
+    float    t;           /* the time the centres are taken at                                  */
+    float    radius;      /* r: only sources that are near compete                              */
+    uint32_t k;           /* hits per row; 1 .. 16                                              */
+    uint32_t flags;       /* OR of GS4D_NN_*; any other bit: GS4D_E_INVALID                     */
+    uint32_t reserved[4]; /* must be 0                                                          */
+} gs4d_nearest_query;     /* 32 bytes */
+typedef struct gs4d_neighbour_hit {
+    uint32_t record;      /* the source's record index, or GS4D_ID_NONE: an empty slot          */
+    float    dist2;       /* the squared distance `near` compared, or +inf: an empty slot       */
+} gs4d_neighbour_hit;     /* 8 bytes */
+GS4D_API int gs4d_nearest_neighbours(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_nearest_query* query,
+                                     gs4d_buf source /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff source == 0 */,
+                                     gs4d_buf hits, size_t hit_stride, gs4d_buf stats /* 0: hits only */);
 
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
@@ -1102,6 +1171,14 @@ GS4D_API void gs4d_host_label_components(size_t n, const float* records24, const
 /* The definition of gs4d_count_labels, in place on the n rows of stats.  rule == NULL, or one with an unknown flag or reserved != 0, changes nothing. */
 GS4D_API void gs4d_host_count_labels(size_t n, const uint32_t* labels, const gs4d_record_stat* seeds, const gs4d_keep_rule* rule,
                                      gs4d_record_stat* stats);
+/* The definition of gs4d_nearest_neighbours (the text above its declaration): the brute-force double loop, every source that is near inserted
+ * into the sorted list of the k smallest (bits(dist2), j); then the k slots of row i at hits + i * hit_stride and — stats != NULL — the row of
+ * the table.  source == NULL selects every record (rule is then ignored), else rule is not NULL.  A call the device would refuse for its query,
+ * rule or hit_stride (NULL, an unknown flag, a non-zero reserved word, k outside 1 .. 16, a radius outside 2^-63 <= r < 2^64, a hit_stride that
+ * is not a multiple of 16 in 16 .. 1024 or is below 8 k) changes nothing. */
+GS4D_API void gs4d_host_nearest_neighbours(size_t n, const float* records24, const gs4d_nearest_query* query,
+                                           const gs4d_record_stat* source, const gs4d_keep_rule* rule,
+                                           void* hits, size_t hit_stride, gs4d_record_stat* stats /* may be NULL */);
 /* "Frame selection": the eye from which a camera of gs4d_host_look_at(eye, orientation, up) and gs4d_host_perspective(fov_deg, width, height, ..)
  * sees the whole box lo .. hi with its centre in the middle of the image.  The box's bounding sphere (centre (lo + hi) / 2, radius half the
  * diagonal; a degenerate box — a radius that is zero or not finite — gets radius 1) is fitted into the narrower of the projection's two
