@@ -554,8 +554,13 @@ int fill_tile_count(gs4d_ctx* c, Lane& L, const DrawArgs& a, size_t npre, bool v
         if (!kh) return hipfail(c, he, "sort_hist_slot");
         tc.keys_out = (float*)fused.keys->d; tc.idx_out = nullptr /* the depth sort that follows makes the identity index up */; tc.ghist = kh; tc.span = a.blend_order.span; tc.err = L.err_word();
         L.depth_sort.hist_bias = a.blend_order.ks.bias;
-        sort_plan_hist(L.depth_sort, npre, a.blend_order.bits);
+        // A staged draw reads no key back (k_bucket_scatter, which takes the keys of an exact-list draw from the caller's buffer, does not run) and nothing
+        // observes the buffers before the sort queued behind this draw: its hybrid sort may be segment-fed — the projection leaves each segment's keys
+        // grouped by top digit in the sort's own blocks instead of the caller's key buffer, and the sort is k_os_tail alone.
+        const bool staged = v2 && L.tl.staged && L.tl.seg <= SEGFEED_BLOCK;
+        sort_plan_hist(L.depth_sort, npre, a.blend_order.bits, staged ? L.tl.rows : 0u);
         tc.hist_rb = L.depth_sort.hist_rb; tc.hist_rows = L.depth_sort.hist_rows; tc.hist_top = L.depth_sort.hist_top;
+        if (L.depth_sort.hist_segfeed) { tc.seg_pairs = L.depth_sort.seg_pairs; tc.seg_runs = L.depth_sort.seg_runs; }
     }
     return GS4D_OK;
 }
@@ -999,6 +1004,11 @@ int gs4d_create(int device, int width, int height, gs4d_ctx** out) {
             if (const char* ev = getenv("GS4D_SORT_HYBRID")) ss->hybrid_knob = atoi(ev) != 0 ? 1 : 0;
             if (const char* ev = getenv("GS4D_SORT_TAILCAP")) { const long v = atol(ev); if (v >= 1) ss->tail_cap = (uint32_t)std::min<long>(v, 1l << 30); }
         }
+        // GS4D_SORT_SEGFEED: 0 = no hybrid sort is segment-fed; 1 = the hybrid sort of every staged fused frame is (sort_plan_hist), also with GS4D_SORT_HYBRID set;
+        // unset = on, but only while GS4D_SORT_HYBRID is unset too: an explicit GS4D_SORT_HYBRID means the plans exactly as they were before the segment-fed form
+        // existed.  The depth sort's scratch only: the lane's other scratch has no producer that writes segment blocks.
+        if (const char* ev = getenv("GS4D_SORT_SEGFEED")) c->lanes[i].depth_sort.segfeed = atoi(ev) != 0;
+        else c->lanes[i].depth_sort.segfeed = getenv("GS4D_SORT_HYBRID") == nullptr;
     }
     if (const char* ev = getenv("GS4D_NEIGHBOURS_PHASES")) c->neighbour_phases = std::min(4, std::max(1, atoi(ev)));
     int rc = alloc_fbs(c, width, height);

@@ -105,7 +105,15 @@ struct SortScratch {
     //   hist_rows  how many LSD digit rows the producer counted (OS_MAX_PASSES: all, the plain LSD plan)
     //   hist_top   >= 0: the producer also counted the 9-bit top digit (key - bias) >> hist_top into row OS_TOP_ROW
     //   hist_hybrid  the sort is the MSD/LSD hybrid: one global pass on the top digit, then k_os_tail (hist_rows == 0)
-    int hist_rows = 4, hist_top = -1; bool hist_hybrid = false;
+    //   hist_segfeed the hybrid is segment-fed: a staged projection (k_project_count<SRC, true, 2>) leaves every segment's (key, index) pairs grouped by top digit
+    //                in seg_pairs and one {count, offset} word per (digit, segment) in seg_runs[512][hist_seg_rows]; the sort is k_os_tail alone, which gathers
+    //                its bucket from the segments' runs (no k_os_pass launch; the caller's key buffer holds no unsorted keys in between)
+    int hist_rows = 4, hist_top = -1; bool hist_hybrid = false, hist_segfeed = false; uint32_t hist_seg_rows = 0;
+    // the segment blocks of a segment-fed sort: SEGFEED_BLOCK pairs per segment, and the run table.  Never scratch 1 / 2: k_os_tail's slow path writes its
+    // bucket's range of those while other workgroups still read their runs.  Grown by sort_scratch_reserve while `segfeed` is set.
+    uint2* seg_pairs = nullptr; size_t seg_cap = 0;      // in pairs
+    uint32_t* seg_runs = nullptr; size_t runs_cap = 0;   // in words
+    bool segfeed = false;              // GS4D_SORT_SEGFEED: 0 = never, 1 = wherever a staged fused frame plans the hybrid, unset = on while GS4D_SORT_HYBRID is unset too
     int hybrid_knob = -1;              // GS4D_SORT_HYBRID: 0 = never (the LSD passes, nothing else counted), 1 = for every eligible span at any n, unset = eligible spans of >= OS_HYBRID_MIN_N keys
     uint32_t tail_cap = 8192;          // GS4D_SORT_TAILCAP: buckets above it take k_os_tail's slow path (at most the kernel's LDS tile)
     // pinned + mapped status words of the latest top-digit report (k_os_tail's first workgroup, or k_os_top_stats behind a fallback sort), and the same
@@ -136,8 +144,12 @@ int sort_plan_passes(int key_bits, int rb);                          // ... and 
 // hist_hybrid (what the producer is launched with, and what radix_sort_pairs(have_hist) then executes).  The hybrid is planned for spans of 19..27 bits
 // when LDS-atomic ranking is verified, no sort test hook is set and the latest report's largest bucket fits k_os_tail's tile; a span that is eligible
 // but crowded keeps the LSD passes and has the top digit counted beside them, so that the plan can return.
+// seg_rows != 0: the producer is the staged projection, with that many segments of at most SEGFEED_BLOCK records: the hybrid is then planned segment-fed
+// (hist_segfeed) where the scratch allows it (SortScratch::segfeed, storage reserved).
 constexpr size_t OS_HYBRID_MIN_N = 32768;
-void sort_plan_hist(SortScratch& s, size_t n, int key_bits);
+constexpr uint32_t SEGFEED_BLOCK = 2048;                     // pairs per segment block == STAGE_R * SEG_THREADS (static_assert in preprocess.hip)
+constexpr uint32_t SEGFEED_MAX_ROWS = 1024;                  // k_os_tail scans a run-table row with two segments per thread
+void sort_plan_hist(SortScratch& s, size_t n, int key_bits, uint32_t seg_rows = 0);
 hipError_t lds_atomic_order_selftest(const hipStream_t* streams, int nstreams, bool* ordered);      // on all the streams at once
 // Layout of the SoA shadow (preprocess.hip).  The repack kernel verifies what a compact layout assumes, bit for bit, for every record, and
 // reports a violation in bbox[15]; the caller then repacks in the next layout down.
@@ -244,6 +256,10 @@ struct TileCount {                               // hist == nullptr: the ordered
     // Fused key generation (the draw executes a gs4d_keygen + gs4d_sort_pairs that were queued just before it): the projection kernel also
     // writes the caller's key and index buffers and accumulates the digit histograms of the depth sort, exactly as k_keygen would
     float* keys_out = nullptr; uint32_t* idx_out = nullptr; uint32_t* ghist = nullptr; int hist_rb = 8, hist_rows = OS_MAX_PASSES, hist_top = -1 /* SortScratch::hist_rows, hist_top */; uint32_t span = 0xFFFFFFFFu; uint32_t* err = nullptr;
+    // Segment-fed depth sort (SortScratch::hist_segfeed; staged lists only): instead of keys_out[i] the workgroup writes its segment's (key + bias, record) pairs,
+    // grouped by the 9-bit top digit key >> hist_top and stable in record order inside a digit, to seg_pairs[segment * SEGFEED_BLOCK ...], and one word
+    // count | offset << 12 per (digit, segment) to seg_runs[digit * rows + segment].  null: keys_out is written.
+    uint2* seg_pairs = nullptr; uint32_t* seg_runs = nullptr;
     uint32_t* sstat = nullptr;                   // [rows]: entries of every segment (statistics for the host; every counting launch writes them)
     // Staged lists (tilelist.hip): the projection kernel itself WRITES the entries.  A workgroup counts its segment's entries per bucket, scans
     // the counts, places the entries bucket by bucket in LDS and writes them out as ONE dense block: stage_out[segment * scap + offs[b][segment] + k],

@@ -405,22 +405,39 @@ __global__ __launch_bounds__(256) void k_preprocess(SRC src, uint32_t n, PU u, P
 // FUSE_KEYS: it is also k_keygen (sort.hip) for these records — the key it derives the blend order from IS the depth key: written to the
 // caller's key buffer with the identity index beside it, bounds-checked, and counted into the depth sort's digit histograms.  Without
 // COUNT that is all it adds to the projection: the ordered path's form (the sort follows, then binning.hip reads the sorted index).
-template <class SRC, bool FUSE_KEYS, int COUNT>      // COUNT: 0 none (ordered path), 1 count per bucket, 2 count + place + write the segment's entries (staged lists)
+static_assert(SEGFEED_BLOCK == (uint32_t)(STAGE_R * SEG_THREADS) && SEG_THREADS / 64 == 8 && OS_MAX_PASSES == 4, "segment-fed keys: a block per staged segment; eight waves' counters, four of them in kh");
+constexpr size_t SEGFEED_LDS = (4 * OS_MAX_BINS) * 4 + (size_t)SEGFEED_BLOCK * 8;      // of stage[]: the counters of waves 4..7, then the pairs
+// SEGF: the segment-fed form of <SRC, true, 2> — an instance of its own, so that the others keep their registers
+template <class SRC, bool FUSE_KEYS, int COUNT, bool SEGF = false>      // COUNT: 0 none (ordered path), 1 count per bucket, 2 count + place + write the segment's entries (staged lists)
 __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t n, PU u, PreOut out, TileCount tc) {
     __shared__ uint32_t h[COUNT ? 1024 : 1];
     __shared__ uint32_t kh[FUSE_KEYS ? OS_MAX_PASSES : 1][OS_MAX_BINS];
     __shared__ uint32_t ws[SEG_THREADS / 64 + 1];
     extern __shared__ __attribute__((aligned(16))) uint2 stage[];      // COUNT == 2: tc.scap entries (copied out 16 bytes at a time: 16-byte base)
+    // Segment-fed depth sort (TileCount::seg_pairs): the keys do not go to the caller's buffer.  The workgroup ranks them by their 9-bit top digit
+    // and writes them, with their record indices, digit after digit into the segment's block, for k_os_tail to gather (sort.hip).  LDS, all of it free until the
+    // list entries are placed: per-wave digit counters [8][512] in kh (waves 0..3: a segment-fed producer counts no histogram row there) and stage[0, 8 KB)
+    // (waves 4..7), the reordered pairs in stage[8 KB, 24 KB) — launch_pre asks for at least 24 KB of stage[].
+    static_assert(!SEGF || (FUSE_KEYS && COUNT == 2), "segment-fed keys come from the staged, fused projection");
+    constexpr bool segf = SEGF;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t* const stage32 = reinterpret_cast<uint32_t*>(stage);
+    auto wave_row = [&](uint32_t k) -> uint32_t* { return k < 4u ? kh[FUSE_KEYS ? k : 0] : stage32 + (k - 4u) * OS_MAX_BINS; };      // the digit counters of wave k
     if (COUNT) for (uint32_t b = threadIdx.x; b < tc.nb; b += SEG_THREADS) h[b] = 0u;
     if (FUSE_KEYS && threadIdx.x < 256u) os_hist_clear(kh, threadIdx.x);
+    if (segf) for (uint32_t q = threadIdx.x; q < 4u * OS_MAX_BINS; q += SEG_THREADS) stage32[q] = 0u;
     __syncthreads();
     const uint32_t i0 = blockIdx.x * tc.seg, i1 = min(n, i0 + tc.seg);
     // staged lists: what the placing pass needs of every record this thread projected (seg <= STAGE_R * SEG_THREADS: tile_lists_plan / run_draw)
     uint32_t s_key[COUNT == 2 ? STAGE_R : 1], s_r0[COUNT == 2 ? STAGE_R : 1], s_r1[COUNT == 2 ? STAGE_R : 1];
 #pragma unroll
     for (int q = 0; q < (COUNT == 2 ? STAGE_R : 1); ++q) { s_key[q] = 0u; s_r0[q] = 1u; s_r1[q] = 0u; }
-    auto round = [&](uint32_t ib, int it) {                 // one record per thread; every lane stays for the wave-wide counting
-        const uint32_t i = ib + threadIdx.x;
+    // Round `it` of a staged segment: thread t takes record i0 + it * SEG_THREADS + t.  Segment-fed: a wave owns 256 CONSECUTIVE records, four rounds of 64 —
+    // (wave, round, lane) order is then record order, which is what makes the placing below stable (os_rank_items' layout).  Every round of a wave starts
+    // at a multiple of 64: a wave is either wholly past the end of the segment (it leaves the loop: wave-uniform, no barrier inside) or stays converged.
+    auto staged_first = [&](int it) -> uint32_t { return segf ? i0 + wave * (uint32_t)(STAGE_R * 64) + (uint32_t)it * 64u : i0 + (uint32_t)it * SEG_THREADS; };
+    auto staged_lane = [&]() -> uint32_t { return segf ? (threadIdx.x & 63u) : threadIdx.x; };
+    auto round = [&](uint32_t i, int it) {                  // one record per thread; every lane stays for the wave-wide counting
         TRect r{ 0u, 0u, 0u, 0u, 1u, 0u };
         uint32_t key = 0u;
         if (i < i1) {
@@ -431,21 +448,62 @@ __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t
                 if (COUNT == 2) { s_key[it] = key; s_r0[it] = rect.x; s_r1[it] = rect.y; }
             }
             if (FUSE_KEYS) {
-                tc.keys_out[i] = __uint_as_float(key + tc.ks.bias);          // the blend key is the depth key's bit pattern relative to the bias
-                if (tc.idx_out) tc.idx_out[i] = i;                            // null: the sort that follows makes up the identity payload itself (radix_sort_pairs)
+                if (segf) {
+                    atomicAdd(&wave_row(wave)[(key >> tc.hist_top) & (OS_MAX_BINS - 1u)], 1u);      // the wave's count of the digit; the slot comes from a second walk, below
+                } else {
+                    tc.keys_out[i] = __uint_as_float(key + tc.ks.bias);      // the blend key is the depth key's bit pattern relative to the bias
+                    if (tc.idx_out) tc.idx_out[i] = i;                        // null: the sort that follows makes up the identity payload itself (radix_sort_pairs)
+                }
                 if (key > tc.span) __hip_atomic_store(tc.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // below the bias wraps to a huge value: caught too
             }
         }
-        if (FUSE_KEYS) os_hist_add(kh, key, i < i1, tc.hist_rows, tc.hist_rb, tc.hist_top);       // a hybrid-planned sort: the top-digit row alone (one LDS atomic per record, not three)
+        if (FUSE_KEYS && !segf) os_hist_add(kh, key, i < i1, tc.hist_rows, tc.hist_rb, tc.hist_top);       // a hybrid-planned sort: the top-digit row alone (one LDS atomic per record, not three)
         if (COUNT) count_buckets(h, tc.nb - 1u, (uint32_t)tc.tiles_x, r);
     };
     if (COUNT == 2) {
 #pragma unroll
-        for (int it = 0; it < STAGE_R; ++it) { const uint32_t ib = i0 + (uint32_t)it * SEG_THREADS; if (ib >= i1) break; round(ib, it); }      // uniform trip count, registers indexed at compile time
+        for (int it = 0; it < STAGE_R; ++it) { const uint32_t ib = staged_first(it); if (ib >= i1) break; round(ib + staged_lane(), it); }      // trip count uniform in the wave, registers indexed at compile time
     } else {
-        for (uint32_t ib = i0; ib < i1; ib += SEG_THREADS) round(ib, 0);    // uniform trip count
+        for (uint32_t ib = i0; ib < i1; ib += SEG_THREADS) round(ib + threadIdx.x, 0);    // uniform trip count
     }
     __syncthreads();
+    if (segf) {
+        // thread d: the waves' counts of digit d -> each wave's first slot inside the block (digit runs in order, waves in order inside a run), the run-table
+        // word and the global top-digit histogram (what os_hist_flush would have added)
+        const uint32_t tid = threadIdx.x, lane = tid & 63u;
+        uint32_t wo[SEG_THREADS / 64], cnt = 0;
+#pragma unroll
+        for (int k = 0; k < SEG_THREADS / 64; ++k) { wo[k] = cnt; cnt += wave_row((uint32_t)k)[tid]; }
+        uint32_t inc = cnt;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(inc, off, 64); if (lane >= (unsigned)off) inc += v; }
+        if (lane == 63u) ws[wave] = inc;
+        __syncthreads();
+        uint32_t first = inc - cnt;
+#pragma unroll
+        for (int k = 0; k < SEG_THREADS / 64; ++k) if ((unsigned)k < wave) first += ws[k];
+#pragma unroll
+        for (int k = 0; k < SEG_THREADS / 64; ++k) wave_row((uint32_t)k)[tid] = first + wo[k];
+        tc.seg_runs[(size_t)tid * tc.rows + blockIdx.x] = cnt | (first << 12);      // both <= SEGFEED_BLOCK
+        if (cnt) atomicAdd(&tc.ghist[((size_t)(blockIdx.x % OS_REPL) * OS_MAX_PASSES + OS_TOP_ROW) * OS_MAX_BINS + tid], cnt);
+        __syncthreads();
+        uint2* const pairs = stage + (4 * OS_MAX_BINS * 4) / sizeof(uint2);      // behind the counters of waves 4..7: 8 KB in
+        uint32_t* const mine = wave_row(wave);
+#pragma unroll
+        for (int q = 0; q < STAGE_R; ++q) {
+            const uint32_t i = staged_first(q) + lane;
+            // Stable without a stored rank: the counter now holds the wave's next free slot of the digit, and a returning LDS atomic hands the slots out to the
+            // lanes of one instruction in ascending lane order (verified on the device at context creation — the hybrid is planned only then: os_rank_items),
+            // instruction after instruction in program order — rounds in order, lanes in order inside a round: record order.
+            if (i < i1) pairs[atomicAdd(&mine[(s_key[q] >> tc.hist_top) & (OS_MAX_BINS - 1u)], 1u)] = make_uint2(s_key[q] + tc.ks.bias, i);
+        }
+        __syncthreads();
+        // the block leaves in one piece, 16 bytes (two pairs) per thread and step; a segment of an odd number of records also stores the slot behind its last pair
+        uint4* __restrict__ dst = reinterpret_cast<uint4*>(tc.seg_pairs + (size_t)blockIdx.x * SEGFEED_BLOCK);
+        const uint4* src4 = reinterpret_cast<const uint4*>(pairs);
+        for (uint32_t k = tid; k < (i1 - i0 + 1u) / 2u; k += SEG_THREADS) dst[k] = src4[k];
+        // (ws and stage[] are written again below: behind the barriers of the counting part, which every thread reaches after the loop above)
+    }
     if (COUNT) {
         // the row of counts (one row per bucket: k_bucket_scan / k_bucket_tiles_staged walk along the segments), the segment's total and — staged —
         // the exclusive scan of the counts: where each bucket's run starts inside the segment's block.  Thread t looks after buckets 2t, 2t + 1.
@@ -473,8 +531,8 @@ __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t
                 const uint32_t nbs = (uint32_t)__ffs((int)tc.nb) - 1u;
 #pragma unroll
                 for (int q = 0; q < STAGE_R; ++q) {
-                    const uint32_t i = i0 + (uint32_t)q * SEG_THREADS + tid;
-                    if (i0 + (uint32_t)q * SEG_THREADS >= i1) break;          // uniform
+                    const uint32_t i = staged_first(q) + staged_lane();       // the record this thread projected in round q
+                    if (staged_first(q) >= i1) break;                         // uniform in the wave
                     const TRect r = i < i1 ? tile_rect(s_r0[q], s_r1[q], (uint32_t)tc.shard_rank, (uint32_t)tc.shard_world) : TRect{ 0u, 0u, 0u, 0u, 1u, 0u };
                     place_buckets(h, tc.nb - 1u, nbs, (uint32_t)tc.tiles_x, r, s_key[q], i, stage);
                 }
@@ -486,7 +544,7 @@ __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t
             }
         }
     }
-    if (FUSE_KEYS && threadIdx.x < 256u) os_hist_flush(kh, tc.ghist, tc.hist_rows, threadIdx.x, tc.hist_top);
+    if (FUSE_KEYS && !segf && threadIdx.x < 256u) os_hist_flush(kh, tc.ghist, tc.hist_rows, threadIdx.x, tc.hist_top);
 }
 
 static PU make_pu(const Uniforms& un, int W, int H) {
@@ -499,7 +557,9 @@ static PU make_pu(const Uniforms& un, int W, int H) {
 template <class SRC>
 static hipError_t launch_pre(hipStream_t st, SRC src, size_t n, const Uniforms& un, int W, int H, PreOut out, const TileCount& tc) {
     if (n == 0) return hipSuccess;
-    if (tc.hist && tc.stage_out && tc.keys_out) k_project_count<SRC, true, 2><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), (size_t)tc.scap * 8, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
+    // (segment-fed: stage[] first holds four waves' digit counters and the segment's reordered pairs, 24 KB — no more than the entries of a 1080p frame's segments need anyway)
+    if (tc.hist && tc.stage_out && tc.keys_out && tc.seg_pairs) k_project_count<SRC, true, 2, true><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), std::max<size_t>((size_t)tc.scap * 8, SEGFEED_LDS), st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
+    else if (tc.hist && tc.stage_out && tc.keys_out) k_project_count<SRC, true, 2><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), (size_t)tc.scap * 8, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
     else if (tc.hist && tc.stage_out) k_project_count<SRC, false, 2><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), (size_t)tc.scap * 8, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
     else if (tc.hist && tc.keys_out) k_project_count<SRC, true, 1><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), 0, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
     else if (tc.hist) k_project_count<SRC, false, 1><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), 0, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);

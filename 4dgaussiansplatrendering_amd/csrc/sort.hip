@@ -634,9 +634,43 @@ __device__ __forceinline__ void ot_wave_range(uint32_t count, uint32_t w, uint32
     end = min(count, first + share);                              // (a wave past the end: end <= first, nothing valid)
 }
 
-template <int LB>
+// The segment-fed source (SEG): bucket d is not a range of scratch 1 but one run per segment of the staged projection (k_project_count<SRC, true, 2>,
+// preprocess.hip), each inside that segment's block of seg_pairs.  s_word[r] = count | offset << 12 of segment r's run, s_first[r] = the runs before it: the
+// runs go to dk / dv[s_first[r] ...] in segment order — segments in record order, a run stable in record order: the bucket in the caller's order, as launch A
+// leaves it.  Eight lanes share a run (about four pairs at 10^6 keys: 489 segments x 512 digits), eight runs per lane are in flight at once, eight pairs of each a round
+// (correct at any length up to the block's 2048).
+struct OsSegSrc { const uint2* pairs; const uint32_t* runs; uint32_t rows; uint32_t* ghist_other; };
+__device__ __forceinline__ void ot_gather_runs(const uint2* __restrict__ pairs, uint32_t rows, const uint32_t* s_word, const uint32_t* s_first, uint32_t* dk, uint32_t* dv, uint32_t tid) {
+    constexpr int U = 8;                                          // runs a lane works on at once: 512 segments per step of the outer loop
+    const uint32_t sub = tid & 7u;
+    for (uint32_t r0 = tid >> 3; r0 < rows; r0 += (OT_THREADS / 8) * U) {
+        uint2 v[U]; uint32_t cnt[U], dst[U], src[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t r = r0 + (uint32_t)u * (OT_THREADS / 8);
+            const bool in = r < rows;
+            const uint32_t wd = in ? s_word[r] : 0u;
+            cnt[u] = wd & 0xFFFu; dst[u] = in ? s_first[r] : 0u; src[u] = r * SEGFEED_BLOCK + (wd >> 12);
+            // (a word from a table the producer did not write for these keys could point anywhere: the run stays inside its block whatever it says)
+            if ((wd >> 12) + cnt[u] > SEGFEED_BLOCK) cnt[u] = 0u;
+        }
+        uint32_t longest = 0u;
+#pragma unroll
+        for (int u = 0; u < U; ++u) longest = max(longest, cnt[u]);
+        // Eight pairs of every run a round, until the longest of the lane's runs is through: all loads of a round are asked for before the first is stored, so
+        // a round is one memory round trip — the densest bucket (runs of 14 pairs on average at 10^6 keys) decides how long the launch takes
+        for (uint32_t k = sub; k - sub < longest; k += 8u) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) v[u] = k < cnt[u] ? pairs[src[u] + k] : make_uint2(0u, 0u);
+#pragma unroll
+            for (int u = 0; u < U; ++u) if (k < cnt[u]) { dk[dst[u] + k] = v[u].x; dv[dst[u] + k] = v[u].y; }
+        }
+    }
+}
+
+template <int LB, bool SEG>
 __global__ __launch_bounds__(OT_THREADS) void k_os_tail(OsBufs bufs, uint32_t n, const uint32_t* __restrict__ ghist /* the slot launch A read */, uint32_t bias,
-                                                        int rem /* key bits below the top digit: 10..18 */, uint32_t cap /* <= OT_TILE */, uint32_t* fb, uint32_t* err) {
+                                                        int rem /* key bits below the top digit: 10..18 */, uint32_t cap /* <= OT_TILE */, uint32_t* fb, uint32_t* err, OsSegSrc seg) {
     __shared__ uint32_t skeys[OT_TILE];
     __shared__ uint32_t svals[OT_TILE];
     __shared__ uint32_t wcnt[OT_WAVES][LB];
@@ -645,25 +679,50 @@ __global__ __launch_bounds__(OT_THREADS) void k_os_tail(OsBufs bufs, uint32_t n,
     __shared__ uint32_t s_run[2][LB];           // slow path: where the next key of each digit goes, per pass
     __shared__ uint32_t s_tmp[OT_BINS / 64];
     __shared__ uint32_t s_red[2 * OT_WAVES];
-    __shared__ uint32_t s_range[2];
+    __shared__ uint32_t s_range[3];
+    static_assert(!SEG || OT_WAVES * LB >= 2 * (int)SEGFEED_MAX_ROWS, "the run words and their prefix borrow wcnt before the first local pass clears it");
     const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6;
+    // segment-fed: this digit's row of the run table, two segments per thread — asked for together with the histogram (neither depends on the other)
+    uint32_t wa = 0u, wb = 0u;
+    if (SEG) {
+        const uint32_t* __restrict__ row = seg.runs + (size_t)blockIdx.x * seg.rows;
+        if (2u * tid < seg.rows) wa = row[2u * tid];
+        if (2u * tid + 1u < seg.rows) wb = row[2u * tid + 1u];
+    }
     {
         const uint32_t g = os_top_count(ghist, tid);
         const uint32_t excl = digit_excl_scan<OT_THREADS, OT_BINS>(g, s_tmp, tid);
         if (tid == blockIdx.x) { s_range[0] = excl; s_range[1] = g; }
         if (blockIdx.x == 0) os_top_report(g, cap, s_red, fb, tid);      // uniform
+        // no k_os_pass runs in a segment-fed sort: the housekeeping its first launch does for the next sort — a clean histogram slot — is done here, every workgroup a slice
+        if (SEG) { constexpr uint32_t SLICE = (uint32_t)(OS_SLOT_WORDS / OT_BINS); static_assert(SLICE * OT_BINS == OS_SLOT_WORDS && SLICE <= OT_THREADS, "a slice per workgroup"); if (tid < SLICE) seg.ghist_other[blockIdx.x * SLICE + tid] = 0u; }
         __syncthreads();
     }
     const uint32_t start = s_range[0], count = s_range[1];
     if (count == 0u) return;                                      // uniform: an empty bucket
     // the histogram and the keys no longer describe the same array (see k_os_pass's write-out): nothing outside [0, n) is touched
     if (start > n || count > n - start) { if (tid == 0u) __hip_atomic_store(err, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); return; }
+    if (SEG) {
+        // the runs must add up to the histogram's count (else the table and the histogram are not of the same keys)
+        uint32_t* const s_word = &wcnt[0][0]; uint32_t* const s_first = s_word + SEGFEED_MAX_ROWS;
+        const uint32_t r = 2u * tid;
+        const uint32_t ca = wa & 0xFFFu, cb = wb & 0xFFFu;
+        const uint32_t before = digit_excl_scan<OT_THREADS, OT_BINS>(ca + cb, s_tmp, tid);
+        s_word[r] = wa; s_word[r + 1u] = wb; s_first[r] = before; s_first[r + 1u] = before + ca;
+        if (tid == OT_THREADS - 1u) s_range[2] = before + ca + cb;
+        __syncthreads();
+        if (s_range[2] != count) { if (tid == 0u) __hip_atomic_store(err, 3u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); return; }      // uniform
+        if (count <= cap) ot_gather_runs(seg.pairs, seg.rows, s_word, s_first, skeys, svals, tid);      // free: a local pass writes them only after ranking from registers
+        else ot_gather_runs(seg.pairs, seg.rows, s_word, s_first, bufs.k[1] + start, bufs.v[1] + start, tid);      // the slow path's source: this bucket's own range of scratch 1
+        __threadfence_block();
+        __syncthreads();
+    }
     const int w0 = (rem + 1) >> 1, w1 = rem >> 1;                 // the two local digits: bits [0, w0) and [w0, rem), each <= 9 bits
     const uint32_t m0 = (1u << w0) - 1u, m1 = (1u << w1) - 1u;
     uint32_t key[OT_ITEMS], val[OT_ITEMS];
     if (count <= cap) {
         // ---- the bucket fits: load, two local passes, write back ----
-        const uint32_t* k1 = bufs.k[1] + start; const uint32_t* v1 = bufs.v[1] + start;
+        const uint32_t* k1 = SEG ? skeys : bufs.k[1] + start; const uint32_t* v1 = SEG ? svals : bufs.v[1] + start;
         uint32_t first, end;
         ot_wave_range(count, w, first, end);
 #pragma unroll
@@ -743,6 +802,13 @@ hipError_t sort_scratch_reserve(hipStream_t st, SortScratch& s, size_t n) {
         s.vals2 = s.keys2 ? s.keys2 + 2 * s.cap : nullptr;
         if (e != hipSuccess) return e;
     }
+    // the segment blocks and the run table of a segment-fed sort (8 bytes a key + 2 KB a segment), for sorts a staged projection can produce: at most
+    // SEGFEED_MAX_ROWS segments of SEGFEED_BLOCK records (tile_lists_plan).  Both sized for n alone: sort_plan_hist checks the producer's segments against them.
+    if (s.segfeed && n <= (size_t)SEGFEED_MAX_ROWS * SEGFEED_BLOCK) {
+        const size_t rows = (n + SEGFEED_BLOCK - 1) / SEGFEED_BLOCK;
+        if ((e = grow_device_array(st, s.seg_pairs, s.seg_cap, rows * SEGFEED_BLOCK)) != hipSuccess) return e;
+        if ((e = grow_device_array(st, s.seg_runs, s.runs_cap, rows * OS_MAX_BINS)) != hipSuccess) return e;
+    }
     // control block: two [OS_REPL][4][OS_MAX_BINS] histogram slots (alternating), then the look-back words [tiles + groups][bins], sized for the widest digit
     const size_t tiles = (s.cap + 1023) / 1024;      // smallest tile = 1024 keys; sized for the largest sort seen (the layout depends on it)
     const size_t groups = tiles / OS_GROUP + 2, supers = groups / OS_SUPER + 2;
@@ -774,6 +840,8 @@ hipError_t sort_scratch_reserve(hipStream_t st, SortScratch& s, size_t n) {
 void sort_scratch_free(SortScratch& s) {
     if (s.keys2) (void)hipFree(s.keys2);
     if (s.hist) (void)hipFree(s.hist);
+    if (s.seg_pairs) (void)hipFree(s.seg_pairs);
+    if (s.seg_runs) (void)hipFree(s.seg_runs);
     if (s.totals) (void)hipFree(s.totals);
     if (s.fb) (void)hipHostFree(s.fb);
     s = SortScratch();
@@ -791,7 +859,8 @@ uint32_t* sort_hist_slot(hipStream_t st, SortScratch& s, size_t n_hint, hipError
 }
 
 // what a sort executes: LSD digit rows counted (OS_MAX_PASSES: the plain plan), the top digit's shift (-1: not counted), and whether it is the hybrid
-struct OsPlan { int rows = OS_MAX_PASSES; int top = -1; bool hybrid = false; };
+// segfeed: the hybrid's buckets come from the producer's segment blocks (seg_rows segments), launch A does not run
+struct OsPlan { int rows = OS_MAX_PASSES; int top = -1; bool hybrid = false; bool segfeed = false; uint32_t seg_rows = 0; };
 static uint32_t os_tail_cap(const SortScratch& s) { return std::min<uint32_t>(std::max<uint32_t>(s.tail_cap, 1u), OT_TILE); }
 static OsPlan os_plan(const SortScratch& s, size_t n, int key_bits) {
     OsPlan p;
@@ -857,7 +926,7 @@ static hipError_t onesweep(hipStream_t st, SortScratch& s, uint32_t* keys, uint3
     b.k[1] = s.keys2; b.v[1] = s.vals2;
     b.k[2] = s.keys2 + s.cap; b.v[2] = s.vals2 + s.cap;
     // the hybrid: ONE launch of the pass kernel, on the top digit (the row the producer counted), then the tail; a fallback sort: the report behind its passes
-    const int launches = plan.hybrid ? 1 : passes;
+    const int launches = plan.segfeed ? 0 : plan.hybrid ? 1 : passes;      // (segment-fed: no pass launch — the epoch and the accumulator sets stay where they are)
     for (int p = 0; p < launches; ++p) {
         ++s.epoch;
         if ((s.epoch & 0x3FFFFu) == 0u) {    // the 18-bit tile-level epoch wraps: forget every old word
@@ -873,8 +942,14 @@ static hipError_t onesweep(hipStream_t st, SortScratch& s, uint32_t* keys, uint3
     }
     if (plan.hybrid) {
         if (RB != 9 || n_dev) return hipErrorInvalidValue;
-        if (plan.top <= 16) k_os_tail<256><<<dim3(OT_BINS), dim3(OT_THREADS), 0, st>>>(b, (uint32_t)n, ghist, bias, plan.top, os_tail_cap(s), s.fb_dev, s.err ? s.err : s.totals);      // local digits of <= 8 bits
-        else k_os_tail<512><<<dim3(OT_BINS), dim3(OT_THREADS), 0, st>>>(b, (uint32_t)n, ghist, bias, plan.top, os_tail_cap(s), s.fb_dev, s.err ? s.err : s.totals);
+        const OsSegSrc seg{ s.seg_pairs, s.seg_runs, plan.seg_rows, ghist_other };
+        if (plan.segfeed && (!have_hist || !identity_vals || !seg.pairs || !seg.runs || seg.rows < 1u || seg.rows > SEGFEED_MAX_ROWS)) return hipErrorInvalidValue;      // only a producer's plan is segment-fed
+        if (plan.segfeed) {
+            if (plan.top <= 16) k_os_tail<256, true><<<dim3(OT_BINS), dim3(OT_THREADS), 0, st>>>(b, (uint32_t)n, ghist, bias, plan.top, os_tail_cap(s), s.fb_dev, s.err ? s.err : s.totals, seg);
+            else k_os_tail<512, true><<<dim3(OT_BINS), dim3(OT_THREADS), 0, st>>>(b, (uint32_t)n, ghist, bias, plan.top, os_tail_cap(s), s.fb_dev, s.err ? s.err : s.totals, seg);
+        }
+        else if (plan.top <= 16) k_os_tail<256, false><<<dim3(OT_BINS), dim3(OT_THREADS), 0, st>>>(b, (uint32_t)n, ghist, bias, plan.top, os_tail_cap(s), s.fb_dev, s.err ? s.err : s.totals, seg);      // local digits of <= 8 bits
+        else k_os_tail<512, false><<<dim3(OT_BINS), dim3(OT_THREADS), 0, st>>>(b, (uint32_t)n, ghist, bias, plan.top, os_tail_cap(s), s.fb_dev, s.err ? s.err : s.totals, seg);
         ++s.stat_launches; ++s.stat_hybrid;
     } else if (plan.top >= 0) {
         k_os_top_stats<<<dim3(1), dim3(OT_THREADS), 0, st>>>(ghist, os_tail_cap(s), s.fb_dev);
@@ -904,10 +979,14 @@ int sort_plan_rb(const SortScratch& s, size_t n, int key_bits) {
 }
 int sort_plan_passes(int key_bits, int rb) { return std::min(OS_MAX_PASSES, std::max(2, (key_bits + rb - 1) / rb)); }      // an even number of executed passes always exists (see os_schedule)
 
-void sort_plan_hist(SortScratch& s, size_t n, int key_bits) {
+void sort_plan_hist(SortScratch& s, size_t n, int key_bits, uint32_t seg_rows) {
     const OsPlan p = os_plan(s, n, key_bits);
     s.hist_rb = sort_plan_rb(s, n, key_bits);
     s.hist_rows = p.rows; s.hist_top = p.top; s.hist_hybrid = p.hybrid;
+    // segment-fed: a hybrid whose producer is the staged projection, where the knob allows it and the blocks and the run table hold that many segments
+    s.hist_segfeed = p.hybrid && s.segfeed && seg_rows >= 1u && seg_rows <= SEGFEED_MAX_ROWS && s.seg_pairs && s.seg_runs &&
+                     (size_t)seg_rows * SEGFEED_BLOCK <= s.seg_cap && (size_t)seg_rows * OS_MAX_BINS <= s.runs_cap;
+    s.hist_seg_rows = s.hist_segfeed ? seg_rows : 0u;
 }
 
 hipError_t radix_sort_pairs(hipStream_t st, SortScratch& s, uint32_t* keys, uint32_t* vals, size_t n, const uint32_t* n_dev, int key_bits, bool have_hist, bool identity_vals) {
@@ -921,9 +1000,9 @@ hipError_t radix_sort_pairs(hipStream_t st, SortScratch& s, uint32_t* keys, uint
     const int passes = sort_plan_passes(key_bits, rb);
     // the plan: the producer's (it counted the rows of that plan), or this call's own when k_os_hist is about to count
     OsPlan plan;
-    if (have_hist) { plan.rows = s.hist_rows; plan.top = s.hist_top; plan.hybrid = s.hist_hybrid; }
+    if (have_hist) { plan.rows = s.hist_rows; plan.top = s.hist_top; plan.hybrid = s.hist_hybrid; plan.segfeed = s.hist_segfeed; plan.seg_rows = s.hist_seg_rows; }
     else if (!n_dev) plan = os_plan(s, n, key_bits);
-    s.hist_rows = OS_MAX_PASSES; s.hist_top = -1; s.hist_hybrid = false;       // (of the pending histogram, which this sort consumes)
+    s.hist_rows = OS_MAX_PASSES; s.hist_top = -1; s.hist_hybrid = false; s.hist_segfeed = false; s.hist_seg_rows = 0;       // (of the pending histogram, which this sort consumes)
     if (plan.hybrid) return n_dev ? hipErrorInvalidValue : onesweep<512, 12, true, 9>(st, s, keys, vals, n, nullptr, passes, have_hist, identity_vals, plan);
     // 8192-key tiles of 512 threads x 16 keys for every size.  Rounds 2-3 ran sorts of <= 1.5M keys as 1024 x 8 (the same 12.7 us per pass alone at 10^6 keys;
     // 2-3 % more frames per second with the frame lanes overlapping, as the frame then was).  With this round's frame (staged tile lists: two launches fewer,
