@@ -9,7 +9,7 @@
 //                       symmetric layout, which differ only in where that plane lies; dense, fully coalesced, 32 bytes a record), or plane 0 and five
 //                       kernel arguments (CQ_STATIC: 16 bytes a record) — and, COL only (GS4D_CQ_SKIP_HIDDEN), the colour piece / plane for the alpha.
 //                       The test flags are run-time branches, uniform over the launch.  A mask byte is one 1-byte load at the pixel the centre falls on.
-//   the row update      a plain 16-byte load, modify, store by the one thread that owns row i.  No atomics: the call takes the table as a kernel write
+//   the row update      add_fragments: a plain 16-byte load, modify, store by the one thread that owns row i.  No atomics: the call takes the table as a kernel write
 //                       that keeps the contents (queue_on_lane's "out", gs4d_api.hip) — the draws that add to it are settled before the launch and every
 //                       later adder, reader and the host order themselves behind it — so nothing else touches the table while the kernel runs, and
 //                       within the kernel row i belongs to thread i alone.  Rows of records that do not take part are neither read nor written.
@@ -44,16 +44,8 @@ __global__ __launch_bounds__(CENTRES_TILE) void k_count_centres(CentreSrc s, uin
     }
     const gs4d_centre::Fields r{ { p.x, p.y, p.z }, p.w, alpha, { g.x, g.y, g.z }, g.w };
     if (!gs4d_centre::takes_part(q, hw, hh, r, mask)) return;
-    uint4 row = make_uint4(0u, 0u, 0u, 0u);
-    if (q.op == (uint32_t)GS4D_CQ_ADD) {
-        // one fragment of weight 1: pixels += 1, wmax = max(wmax, bits of 1.0f), wsum += 2^24 (64-bit, low word first)
-        row = stats[i];
-        row.x += 1u;
-        row.y = row.y > 0x3F800000u ? row.y : 0x3F800000u;
-        const uint64_t sum = (((uint64_t)row.w << 32) | row.z) + (1ull << 24);
-        row.z = (uint32_t)sum; row.w = (uint32_t)(sum >> 32);
-    }
-    stats[i] = row;
+    if (q.op == (uint32_t)GS4D_CQ_ADD) add_fragments(stats, i, 1u, WEIGHT_ONE_BITS);
+    else stats[i] = make_uint4(0u, 0u, 0u, 0u);
 }
 
 hipError_t launch_count_centres(hipStream_t st, const void* records, const float4* soa, size_t soa_n, const SoaInfo& info, size_t n, const gs4d_centre_query& q,

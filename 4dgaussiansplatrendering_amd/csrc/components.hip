@@ -21,27 +21,27 @@
 // Launches on one stream behind the grid phases, no LDS, kernel boundaries are the only dependencies:
 //   k_cc_init      one thread per sorted slot s: labels[index[s]] = index[s] for a member (bit kb of keys[s] clear), GS4D_ID_NONE otherwise.  The sort
 //                  permutes 0 .. n - 1, so all n words are written.
-//   k_cc_link      one thread per sorted slot that holds a member i, walking cells as k_nb_query does (range, bucket_seen, table row, candidate run,
-//                  near).  For every near candidate j < i it calls unite(i, j): each edge is handled once, by its larger endpoint.
+//   k_cc_link      one thread per sorted slot that holds a member i (neighbour_grid.h: slot_source), walking its candidates (walk_candidates).  For
+//                  every near candidate j < i it calls unite(i, j): each edge is handled once, by its larger endpoint.
 //   k_cc_flatten   one thread per record: labels[i] = find(i) for a member, stored with atomicMin.  Roots no longer change here — every unite has
 //                  returned at the kernel boundary — and every value a concurrent reader can meet in labels[i] is an ancestor of i (the old parent,
 //                  a halved one, or the root itself), so the finds of the other threads still end at the same root.
 //   with stats:    a memset of the keys array — dead by then — to zero as the size array; k_cc_sizes, integer atomicAdds into size[labels[i]], the
 //                  lanes of a wave that hold the same label adding once between them (a few rounds of ballots: with one component that holds most
 //                  of the set every add lands on one word otherwise, measured at 8 times the rest of the call); k_cc_rows, the row
-//                  update of k_nb_query with c = min(cap, size[labels[i]]): row i belongs to one thread alone.
+//                  update (add_fragments) with c = min(cap, size[labels[i]]): row i belongs to one thread alone.
 // gs4d_count_labels: a memset of n flag words; k_cl_seeds, one thread per record j whose row of `seeds` passes the rule: flag[labels[j]] = 1 (a relaxed
 // atomic store of the same value by everybody, left out where a relaxed atomic load already shows it) iff labels[j] < n; k_cl_rows, the row
-// update of k_count_centres for every i with labels[i] < n and flag[labels[i]] set.
+// update with c = 1 for every i with labels[i] < n and flag[labels[i]] set.
 // Scratch: that of gs4d_count_neighbours (neighbour_scratch_words()), nothing more.  All byte offsets are 64-bit.  Nothing but the n labels, rows
 // < n of stats and the scratch is written; records, source, seeds are only read, and only records / rows < n.
 #include "gs4d_internal.h"
 #include "neighbour_query.h"
+#include "neighbour_grid.h"
 #include "component_union.h"
 
 namespace gs4d {
 
-namespace nb = gs4d_neighbour;
 namespace un = gs4d_union;
 
 // the parent array on the device (component_union.h's policy): reads that bypass the L1, a CAS and a min at the L2
@@ -53,9 +53,6 @@ struct DeviceParents {
 };
 __device__ __forceinline__ void cc_raise(uint32_t* err) { __hip_atomic_store(err, 4u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); }
 
-// what the walking kernel is given
-struct CcArgs { float rr; nb::Grid g; int kb; };
-
 __global__ __launch_bounds__(COMPONENTS_TILE) void k_cc_init(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ index, uint32_t n, int kb,
                                                              uint32_t* __restrict__ labels) {
     const uint64_t s = (uint64_t)blockIdx.x * COMPONENTS_TILE + threadIdx.x;
@@ -65,33 +62,22 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void k_cc_init(const uint32_t* __r
     labels[i] = (keys[s] >> kb) ? (uint32_t)GS4D_ID_NONE : i;
 }
 
-__global__ __launch_bounds__(COMPONENTS_TILE) void k_cc_link(uint32_t n, CcArgs a, const float4* __restrict__ cand, const uint2* __restrict__ table,
+__global__ __launch_bounds__(COMPONENTS_TILE) void k_cc_link(uint32_t n, GridArgs a, const float4* __restrict__ cand, const uint2* __restrict__ table,
                                                              const uint32_t* __restrict__ keys, uint32_t* labels, uint32_t* err) {
     const uint64_t s0 = (uint64_t)blockIdx.x * COMPONENTS_TILE + threadIdx.x;
-    if (s0 >= n || (keys[s0] >> a.kb) != 0u) return;          // not a member
-    const float4 me = cand[s0];
-    const float m[3] = { me.x, me.y, me.z };
-    const uint32_t i = __float_as_uint(me.w);
-    if (i >= n) return;                                        // (never)
+    uint32_t i;
+    float m[3];
+    if (s0 >= n || (keys[s0] >> a.kb) != 0u || !slot_source(cand, n, s0, i, m)) return;      // not a member
     DeviceParents parents{ labels };
-    int32_t lo[3], hi[3];
-    nb::cell_range(m, a.g, lo, hi);
-    for (int32_t cz = lo[2]; cz <= hi[2]; ++cz)
-        for (int32_t cy = lo[1]; cy <= hi[1]; ++cy)
-            for (int32_t cx = lo[0]; cx <= hi[0]; ++cx) {
-                const uint32_t b = nb::bucket(cx, cy, cz, a.kb);
-                if (nb::bucket_seen(lo, hi, cx, cy, cz, b, a.kb)) continue;
-                const uint2 run = table[b];
-                const uint32_t end = run.y < n ? run.y : n;
-                for (uint32_t s = run.x; s < end; ++s) {
-                    const float4 v = cand[s];
-                    const uint32_t j = __float_as_uint(v.w);
-                    if (j >= i) continue;                      // the edge belongs to its larger endpoint (and j == i is no edge)
-                    const float mj[3] = { v.x, v.y, v.z };
-                    if (!nb::near(m, mj, a.rr)) continue;
-                    if (!un::unite(parents, i, j, n)) { cc_raise(err); return; }
-                }
-            }
+    walk_candidates(m, a.g, a.kb, n, table, cand, [&](const float4 v) {
+        const uint32_t j = __float_as_uint(v.w);
+        if (j >= i) return true;                               // the edge belongs to its larger endpoint (and j == i is no edge)
+        const float mj[3] = { v.x, v.y, v.z };
+        if (!nb::near(m, mj, a.rr)) return true;
+        if (un::unite(parents, i, j, n)) return true;
+        cc_raise(err);
+        return false;
+    });
 }
 
 __global__ __launch_bounds__(COMPONENTS_TILE) void k_cc_flatten(uint32_t n, uint32_t* labels, uint32_t* err) {
@@ -128,16 +114,6 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void k_cc_sizes(const uint32_t* __
     if (todo) (void)atomicAdd(size + l, 1u);
 }
 
-// c fragments of weight 1 into a row: pixels += c, wmax = max(wmax, bits of 1.0f), wsum += c * 2^24 (64-bit, low word first)
-__device__ __forceinline__ void cc_add_fragments(uint4* __restrict__ stats, uint64_t i, uint32_t c) {
-    uint4 row = stats[i];
-    row.x += c;
-    row.y = row.y > 0x3F800000u ? row.y : 0x3F800000u;
-    const uint64_t sum = (((uint64_t)row.w << 32) | row.z) + ((uint64_t)c << 24);
-    row.z = (uint32_t)sum; row.w = (uint32_t)(sum >> 32);
-    stats[i] = row;
-}
-
 __global__ __launch_bounds__(COMPONENTS_TILE) void k_cc_rows(const uint32_t* __restrict__ labels, uint32_t n, uint32_t cap, const uint32_t* __restrict__ size,
                                                              uint4* __restrict__ stats) {
     const uint64_t i = (uint64_t)blockIdx.x * COMPONENTS_TILE + threadIdx.x;
@@ -145,7 +121,7 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void k_cc_rows(const uint32_t* __r
     const uint32_t l = labels[i];
     if (l >= n) return;
     const uint32_t c = size[l] < cap ? size[l] : cap;
-    if (c != 0u) cc_add_fragments(stats, i, c);                // (a member counts itself: c >= 1)
+    if (c != 0u) add_fragments(stats, i, c, WEIGHT_ONE_BITS);  // (a member counts itself: c >= 1)
 }
 
 hipError_t launch_label_components(hipStream_t st, SortScratch& sort, const void* records, size_t n, const gs4d_component_query& q,
@@ -158,7 +134,7 @@ hipError_t launch_label_components(hipStream_t st, SortScratch& sort, const void
     NeighbourGrid g;
     hipError_t e = launch_neighbour_grid(st, sort, records, n, q.t, q.radius, q.flags, source, rule, scratch, 3, g);
     if (e != hipSuccess) return e;
-    const CcArgs a{ q.radius * q.radius, nb::grid(q.radius), g.kb };
+    const GridArgs a{ q.t, q.flags, q.radius * q.radius, nb::grid(q.radius), g.kb };
     const dim3 grid((uint32_t)((n + COMPONENTS_TILE - 1) / COMPONENTS_TILE)), block(COMPONENTS_TILE);
     k_cc_init<<<grid, block, 0, st>>>(g.keys, g.index, (uint32_t)n, g.kb, labels);
     k_cc_link<<<grid, block, 0, st>>>((uint32_t)n, a, g.cand, g.table, g.keys, labels, err);
@@ -186,7 +162,7 @@ __global__ __launch_bounds__(COMPONENTS_TILE) void k_cl_rows(const uint32_t* __r
     const uint64_t i = (uint64_t)blockIdx.x * COMPONENTS_TILE + threadIdx.x;
     if (i >= n) return;
     const uint32_t l = labels[i];
-    if (l < n && flags[l] != 0u) cc_add_fragments(stats, i, 1u);
+    if (l < n && flags[l] != 0u) add_fragments(stats, i, 1u, WEIGHT_ONE_BITS);
 }
 
 hipError_t launch_count_labels(hipStream_t st, const uint32_t* labels, size_t n, const gs4d_record_stat* seeds, const KeepRule& rule, uint32_t* flags,

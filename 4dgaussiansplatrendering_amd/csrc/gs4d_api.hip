@@ -899,6 +899,35 @@ int scan_end(gs4d_ctx* c, Lane& L, Buffer& S) {
     S.scan_wait = ((1u << c->nlanes) - 1u) & ~(1u << c->cur);
     return GS4D_OK;
 }
+// queue_on_lane with those three steps around it for `scanned`: the tables among `in` that draws may still ADD to (null entries: not given) —
+// reserve behind prepare, begin before launch, end behind it
+template <class Prepare, class Launch>
+int queue_scan_on_lane(gs4d_ctx* c, std::initializer_list<Buffer*> in, std::initializer_list<Buffer*> out, std::initializer_list<Buffer*> scanned,
+                       Prepare prepare, Launch launch) {
+    return queue_on_lane(c, in, out,
+        [&](Lane& L) {
+            int rc = prepare(L);
+            for (Buffer* S : scanned) if (!rc && S) rc = scan_reserve(c, *S);
+            return rc;
+        },
+        [&](Lane& L) {
+            int rc = GS4D_OK;
+            for (Buffer* S : scanned) if (!rc && S) rc = scan_begin(c, L, *S);
+            if (!rc) rc = launch(L);
+            for (Buffer* S : scanned) if (!rc && S) rc = scan_end(c, L, *S);
+            return rc;
+        });
+}
+
+// gs4d_keep_rule as the kernels take it; null — a call whose table is optional was given none — is the rule no kernel reads.  False: an unknown flag
+// or a non-zero reserved field.
+bool keep_rule_of(const gs4d_keep_rule* rule, KeepRule& out) {
+    out = KeepRule{ 0u, 0u, 0ull, 0u };
+    if (!rule) return true;
+    if (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u) return false;
+    out = KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT };
+    return true;
+}
 
 // What gs4d_compact_records and gs4d_compact_time_window share: a table of one row of `row_bytes` per record (`what` names it in the messages) decides
 // which of n records go from src to dst.  stats_table: the table is one that draws ADD to (Buffer::ev_scan).  launch(lane, table, records or null,
@@ -925,16 +954,64 @@ int compact_by_table(gs4d_ctx* c, const char* fn, const char* what, bool stats_t
     if (X) cap = (uint32_t)std::min<size_t>(cap, X->bytes / 4);
     { int rc = flush_order_if_named(c, names, 5); if (rc) return rc; }
     { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    return queue_on_lane(c, { S, R }, { D, X, C },
+    return queue_scan_on_lane(c, { S, R }, { D, X, C }, { stats_table ? S : nullptr },
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.compact_counts, L.compact_cap, std::max<size_t>(1, compact_tiles(n))));
-            return stats_table ? scan_reserve(c, *S) : (int)GS4D_OK;
+            return (int)GS4D_OK;
         },
         [&](Lane& L) {
-            if (stats_table) { int rc = scan_begin(c, L, *S); if (rc) return rc; }
             HIPCHK(c, launch(L, S->d, R ? R->d : nullptr, D ? D->d : nullptr, X ? (uint32_t*)X->d : nullptr, cap, (gs4d_compact_count*)C->d));
-            return stats_table ? scan_end(c, L, *S) : (int)GS4D_OK;
+            return (int)GS4D_OK;
         });
+}
+
+// What gs4d_count_neighbours, gs4d_label_components and gs4d_nearest_neighbours share: everything but the call's own checks, its names and its
+// launch.  The checks are decided in this order, the call's own among them at the two places they have always had.
+// The common fields of the three 32-byte queries — flags against the call's own known mask — with the verdict of the call's own check of the
+// query (cap; k): its message, or null
+struct GridQuery { float radius; uint32_t flags, known; const uint32_t* reserved; const char* query_fault; };
+// The outputs behind data: `first` is required, a row of first_row bytes per record (first_is_table: it is the statistics table itself, settled
+// like one), `stats` is the optional table behind it (0: none, or none to give).  output_fault: the verdict of the call's own check of its
+// outputs (hit_stride), decided once data and first are found live: its message, or null — first_row is not divided by before that.
+struct GridOutputs { gs4d_buf first; size_t first_row; bool first_is_table; gs4d_buf stats; const char* live, * output_fault, * different, * first_fewer; };
+// launch(lane, records, source rows or null, rule, first, stats rows or null) queues the kernels on the lane's neighbour scratch and pair_sort.
+template <class Launch>
+int grid_query(gs4d_ctx* c, const char* fn, const GridQuery& q, size_t n, gs4d_buf data, gs4d_buf source, const gs4d_keep_rule* rule, const GridOutputs& o,
+               Launch launch) {
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string(fn) + ": " + msg).c_str()); };
+    if ((q.flags & ~q.known) != 0u) return bad("unknown flag");
+    if (q.reserved[0] != 0u || q.reserved[1] != 0u || q.reserved[2] != 0u || q.reserved[3] != 0u) return bad("non-zero reserved field in the query");
+    if (q.query_fault) return bad(q.query_fault);
+    if (!neighbour_radius_ok(q.radius)) return bad("the radius must be finite with 2^-63 <= radius < 2^64");
+    if (n >= 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
+    if ((source != 0) != (rule != nullptr)) return bad("source and rule are given together or not at all");
+    KeepRule k;
+    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
+    const gs4d_buf names[4] = { data, o.first, o.stats, source };
+    Buffer* D = getbuf(c, data); Buffer* F = getbuf(c, o.first);
+    if (!D || !F) return bad(o.live);
+    if (o.output_fault) return bad(o.output_fault);
+    if (const int wrong = check_record_names(c, names, 4)) return bad(wrong == 1 ? "bad buffer name" : o.different);
+    Buffer* S = getbuf(c, o.stats); Buffer* Q = getbuf(c, source);
+    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
+    if (F->bytes / o.first_row < n) return bad(o.first_fewer);
+    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (Q && Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the source buffer holds fewer than n rows");
+    if (n == 0) return GS4D_OK;
+    { int rc = flush_order_if_named(c, names, 4); if (rc) return rc; }
+    if (o.first_is_table) { int rc = settle_stats_table(c, *F); if (rc) return rc; }
+    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    if (Q) { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
+    // data and source are read (the 96-byte records, never a shadow: a reader leaves `version` alone; source as gs4d_edit_colours reads its table).
+    // The outputs are "out" of queue_on_lane: first is written, a statistics table is a read-modify-write the lane has the table to itself for, as in
+    // gs4d_count_centres.
+    return queue_scan_on_lane(c, { D, Q }, { F, S }, { Q },
+        [&](Lane& L) {
+            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, neighbour_scratch_words(n)));
+            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));      // (the tile sort's scratch, as gs4d_spatial_order: a histogram a queued keygen has left in depth_sort stays where it is)
+            return (int)GS4D_OK;
+        },
+        [&](Lane& L) { return launch(L, D->d, Q ? (const gs4d_record_stat*)Q->d : nullptr, k, F->d, S ? (gs4d_record_stat*)S->d : nullptr); });
 }
 
 } // namespace
@@ -1370,8 +1447,8 @@ int gs4d_compact_records(gs4d_ctx* c, gs4d_buf stats, size_t n, const gs4d_keep_
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
     if (!rule) return fail(c, GS4D_E_INVALID, "compact_records: rule == NULL");
-    if (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u) return fail(c, GS4D_E_INVALID, "compact_records: unknown flag or non-zero reserved field in the rule");
-    const KeepRule k{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT };
+    KeepRule k;
+    if (!keep_rule_of(rule, k)) return fail(c, GS4D_E_INVALID, "compact_records: unknown flag or non-zero reserved field in the rule");
     return compact_by_table(c, "compact_records", "stats", true, stats, sizeof(gs4d_record_stat), n, src, stride, dst, kept_index, count,
         [&](Lane& L, const void* table, const void* records, void* out, uint32_t* index, uint32_t cap, gs4d_compact_count* cnt) {
             return launch_compact(L.s, (const gs4d_record_stat*)table, n, k, L.compact_counts, records, stride, out, index, cap, cnt);
@@ -1395,15 +1472,14 @@ int gs4d_stat_cut(gs4d_ctx* c, gs4d_buf stats, size_t n, int field, size_t budge
     const uint32_t k = (uint32_t)std::min(budget, n);
     { int rc = flush_order_if_named(c, names, 2); if (rc) return rc; }
     { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    return queue_on_lane(c, { S }, { O },
+    return queue_scan_on_lane(c, { S }, { O }, { S },
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.cut_scratch, L.cut_cap, cut_scratch_words(n)));
-            return scan_reserve(c, *S);
+            return (int)GS4D_OK;
         },
         [&](Lane& L) {
-            { int rc = scan_begin(c, L, *S); if (rc) return rc; }
             HIPCHK(c, launch_stat_cut(L.s, (const gs4d_record_stat*)S->d, n, field, k, L.cut_scratch, (gs4d_cut*)O->d));
-            return scan_end(c, L, *S);
+            return (int)GS4D_OK;
         });
 }
 
@@ -1538,7 +1614,8 @@ int gs4d_edit_colours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_colour_ed
     if (edit->reserved != 0u) return bad("non-zero reserved field in the edit");
     if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
     if ((stats != 0) != (rule != nullptr)) return bad("stats and rule are given together or not at all");
-    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
+    KeepRule k;
+    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
     const bool copy = edit->op == GS4D_EDIT_COPY;
     if (copy && from == 0) return bad("GS4D_EDIT_COPY needs from");
     if (!copy && from != 0) return bad("from must be 0 unless the op is GS4D_EDIT_COPY");
@@ -1552,7 +1629,6 @@ int gs4d_edit_colours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_colour_ed
     if (F && F->bytes / 96 < n) return bad("from holds fewer than n records");
     if (n == 0) return GS4D_OK;
     const EditOp e{ edit->op, edit->channels, { edit->value[0], edit->value[1], edit->value[2], edit->value[3] }, edit->amount };
-    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
     { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
     if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
     // A colour-only write, as gs4d_shade_sh's, extended to the alpha: nothing the library derives from a record buffer reads floats 4..7 (k_soa_repack
@@ -1560,16 +1636,15 @@ int gs4d_edit_colours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_colour_ed
     // that is current stays current — the kernel reads the old colour from its plane 1 and writes the new one there too.  Decided once the pending
     // draws are settled (a re-run may rebuild the shadow) and before any buffer state is touched.
     bool patch = false;
-    return queue_on_lane(c, { S, F }, { D },
+    return queue_scan_on_lane(c, { S, F }, { D }, { S },
         [&](Lane&) {
             patch = D->soa && D->soa_n == D->bytes / 96 && D->soa_version == D->version;
-            return S ? scan_reserve(c, *S) : (int)GS4D_OK;
+            return (int)GS4D_OK;
         },
         [&](Lane& L) {
-            if (S) { int rc = scan_begin(c, L, *S); if (rc) return rc; }
             HIPCHK(c, launch_edit_colours(L.s, D->d, n, e, S ? (const gs4d_record_stat*)S->d : nullptr, k, F ? F->d : nullptr, patch ? D->soa + D->soa_n : nullptr));
             if (patch) D->soa_version = D->version;
-            return S ? scan_end(c, L, *S) : (int)GS4D_OK;
+            return (int)GS4D_OK;
         });
 }
 
@@ -1645,7 +1720,8 @@ int gs4d_transform_selected(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_sel
     if (x.flags != 0u && x.flags != (uint32_t)GS4D_XS_PIVOT && x.flags != (uint32_t)GS4D_XS_PIVOT_MEASURE) return bad("flags must be 0, GS4D_XS_PIVOT or GS4D_XS_PIVOT_MEASURE");
     if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
     if ((stats != 0) != (rule != nullptr)) return bad("stats and rule are given together or not at all");
-    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
+    KeepRule k;
+    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
     const bool measured = x.flags == (uint32_t)GS4D_XS_PIVOT_MEASURE;
     if (measured && measure == 0) return bad("GS4D_XS_PIVOT_MEASURE needs measure");
     if (!measured && measure != 0) return bad("measure must be 0 unless the flag is GS4D_XS_PIVOT_MEASURE");
@@ -1658,18 +1734,16 @@ int gs4d_transform_selected(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_sel
     if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
     if (M && M->bytes < sizeof(gs4d_measure)) return bad("measure holds fewer than 96 bytes");
     if (n == 0) return GS4D_OK;
-    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
     { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
     if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
     // The table and the measurement are read (gs4d_edit_colours' table; an ordinary read buffer, behind the kernels that wrote it), data is written as
     // gs4d_transform_records writes its dst: a full write whatever the table selects — position, mu_t and sig move, so the shadow, the bounding box
     // and the key bounds of data are all stale.  The shadow is not patched: the next draw or gs4d_keygen rebuilds it.
-    return queue_on_lane(c, { S, M }, { D },
-        [&](Lane&) { return S ? scan_reserve(c, *S) : (int)GS4D_OK; },
+    return queue_scan_on_lane(c, { S, M }, { D }, { S },
+        [&](Lane&) { return (int)GS4D_OK; },
         [&](Lane& L) {
-            if (S) { int rc = scan_begin(c, L, *S); if (rc) return rc; }
             HIPCHK(c, launch_transform_selected(L.s, D->d, n, x, S ? (const gs4d_record_stat*)S->d : nullptr, k, M ? (const gs4d_measure*)M->d : nullptr));
-            return S ? scan_end(c, L, *S) : (int)GS4D_OK;
+            return (int)GS4D_OK;
         });
 }
 
@@ -2028,7 +2102,8 @@ int gs4d_measure_records(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_measur
     if (q.reserved[0] != 0u || q.reserved[1] != 0u) return bad("non-zero reserved field in the query");
     if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
     if ((stats != 0) != (rule != nullptr)) return bad("stats and rule are given together or not at all");
-    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
+    KeepRule k;
+    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
     const gs4d_buf names[3] = { data, out, stats };
     Buffer* D = getbuf(c, data); Buffer* O = getbuf(c, out);
     if (!D || !O) return bad("data and out must name live buffers");
@@ -2037,20 +2112,18 @@ int gs4d_measure_records(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_measur
     if (D->bytes / 96 < n) return bad("data holds fewer than n records");
     if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
     if (O->bytes < sizeof(gs4d_measure)) return bad("out holds fewer than 96 bytes");
-    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
     { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
     if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
     // data and the table are read (gs4d_count_centres' data, gs4d_edit_colours' table), out is written whole (gs4d_stat_cut's out).  The kernels read
     // the 96-byte records, never a shadow, and a reader leaves `version` alone: a current shadow stays current and none is built.
-    return queue_on_lane(c, { D, S }, { O },
+    return queue_scan_on_lane(c, { D, S }, { O }, { S },
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.measure_scratch, L.measure_cap, measure_scratch_words()));
-            return S ? scan_reserve(c, *S) : (int)GS4D_OK;
+            return (int)GS4D_OK;
         },
         [&](Lane& L) {
-            if (S) { int rc = scan_begin(c, L, *S); if (rc) return rc; }
             HIPCHK(c, launch_measure_records(L.s, D->d, n, q.t, q.flags, S ? (const gs4d_record_stat*)S->d : nullptr, k, L.measure_scratch, (gs4d_measure*)O->d));
-            return S ? scan_end(c, L, *S) : (int)GS4D_OK;
+            return (int)GS4D_OK;
         });
 }
 
@@ -2058,41 +2131,15 @@ int gs4d_measure_records(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_measur
 int gs4d_count_neighbours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_neighbour_query* query, gs4d_buf source, const gs4d_keep_rule* rule, gs4d_buf stats) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("count_neighbours: ") + msg).c_str()); };
-    if (!query) return bad("query == NULL");
+    if (!query) return fail(c, GS4D_E_INVALID, "count_neighbours: query == NULL");
     const gs4d_neighbour_query q = *query;
-    if ((q.flags & ~(uint32_t)(GS4D_NB_SKIP_HIDDEN | GS4D_NB_SKIP_DEAD | GS4D_NB_COUNT_SELF)) != 0u) return bad("unknown flag");
-    if (q.reserved[0] != 0u || q.reserved[1] != 0u || q.reserved[2] != 0u || q.reserved[3] != 0u) return bad("non-zero reserved field in the query");
-    if (q.cap == 0u) return bad("cap == 0");
-    if (!neighbour_radius_ok(q.radius)) return bad("the radius must be finite with 2^-63 <= radius < 2^64");
-    if (n >= 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
-    if ((source != 0) != (rule != nullptr)) return bad("source and rule are given together or not at all");
-    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
-    const gs4d_buf names[3] = { data, stats, source };
-    Buffer* D = getbuf(c, data); Buffer* S = getbuf(c, stats);
-    if (!D || !S) return bad("data and stats must name live buffers");
-    if (const int wrong = check_record_names(c, names, 3)) return bad(wrong == 1 ? "bad buffer name" : "data, source and stats must be different buffers");
-    Buffer* Q = getbuf(c, source);
-    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
-    if (S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
-    if (Q && Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the source buffer holds fewer than n rows");
-    if (n == 0) return GS4D_OK;
-    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
-    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
-    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    if (Q) { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
-    // stats as an "out" of queue_on_lane, as in gs4d_count_centres: a read-modify-write the lane has the table to itself for.  data is read
-    // (the 96-byte records, never a shadow: a reader leaves `version` alone), source is read as gs4d_edit_colours reads its table.
-    return queue_on_lane(c, { D, Q }, { S },
-        [&](Lane& L) {
-            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, neighbour_scratch_words(n)));
-            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));      // (the tile sort's scratch, as gs4d_spatial_order: a histogram a queued keygen has left in depth_sort stays where it is)
-            return Q ? scan_reserve(c, *Q) : (int)GS4D_OK;
-        },
-        [&](Lane& L) {
-            if (Q) { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
-            HIPCHK(c, launch_count_neighbours(L.s, L.pair_sort, D->d, n, q, Q ? (const gs4d_record_stat*)Q->d : nullptr, k, L.neighbour_scratch, (gs4d_record_stat*)S->d, c->neighbour_phases));
-            return Q ? scan_end(c, L, *Q) : (int)GS4D_OK;
+    const GridQuery g{ q.radius, q.flags, (uint32_t)(GS4D_NB_SKIP_HIDDEN | GS4D_NB_SKIP_DEAD | GS4D_NB_COUNT_SELF), q.reserved, q.cap == 0u ? "cap == 0" : nullptr };
+    const GridOutputs o{ stats, sizeof(gs4d_record_stat), true, 0, "data and stats must name live buffers", nullptr,
+                         "data, source and stats must be different buffers", "the stats buffer holds fewer than n rows" };
+    return grid_query(c, "count_neighbours", g, n, data, source, rule, o,
+        [&](Lane& L, const void* records, const gs4d_record_stat* rows, const KeepRule& k, void* table, gs4d_record_stat*) {
+            HIPCHK(c, launch_count_neighbours(L.s, L.pair_sort, records, n, q, rows, k, L.neighbour_scratch, (gs4d_record_stat*)table, c->neighbour_phases));
+            return (int)GS4D_OK;
         });
 }
 
@@ -2101,43 +2148,15 @@ int gs4d_label_components(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_compo
                           gs4d_buf stats) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("label_components: ") + msg).c_str()); };
-    if (!query) return bad("query == NULL");
+    if (!query) return fail(c, GS4D_E_INVALID, "label_components: query == NULL");
     const gs4d_component_query q = *query;
-    if ((q.flags & ~(uint32_t)(GS4D_CC_SKIP_HIDDEN | GS4D_CC_SKIP_DEAD)) != 0u) return bad("unknown flag");
-    if (q.reserved[0] != 0u || q.reserved[1] != 0u || q.reserved[2] != 0u || q.reserved[3] != 0u) return bad("non-zero reserved field in the query");
-    if (q.cap == 0u) return bad("cap == 0");
-    if (!neighbour_radius_ok(q.radius)) return bad("the radius must be finite with 2^-63 <= radius < 2^64");
-    if (n >= 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
-    if ((source != 0) != (rule != nullptr)) return bad("source and rule are given together or not at all");
-    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
-    const gs4d_buf names[4] = { data, labels, stats, source };
-    Buffer* D = getbuf(c, data); Buffer* B = getbuf(c, labels);
-    if (!D || !B) return bad("data and labels must name live buffers");
-    if (const int wrong = check_record_names(c, names, 4)) return bad(wrong == 1 ? "bad buffer name" : "data, source, labels and stats must be different buffers");
-    Buffer* S = getbuf(c, stats); Buffer* Q = getbuf(c, source);
-    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
-    if (B->bytes / sizeof(uint32_t) < n) return bad("labels holds fewer than n words");
-    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
-    if (Q && Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the source buffer holds fewer than n rows");
-    if (n == 0) return GS4D_OK;
-    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
-    { int rc = flush_order_if_named(c, names, 4); if (rc) return rc; }
-    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    if (Q) { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
-    // as gs4d_count_neighbours: data and source are read (the 96-byte records, never a shadow); labels is written whole, stats is a read-modify-write
-    // the lane has the table to itself for — both "out" of queue_on_lane
-    return queue_on_lane(c, { D, Q }, { B, S },
-        [&](Lane& L) {
-            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, neighbour_scratch_words(n)));
-            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));
-            return Q ? scan_reserve(c, *Q) : (int)GS4D_OK;
-        },
-        [&](Lane& L) {
-            if (Q) { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
-            HIPCHK(c, launch_label_components(L.s, L.pair_sort, D->d, n, q, Q ? (const gs4d_record_stat*)Q->d : nullptr, k, L.neighbour_scratch, (uint32_t*)B->d,
-                                              S ? (gs4d_record_stat*)S->d : nullptr, L.err_word()));
-            return Q ? scan_end(c, L, *Q) : (int)GS4D_OK;
+    const GridQuery g{ q.radius, q.flags, (uint32_t)(GS4D_CC_SKIP_HIDDEN | GS4D_CC_SKIP_DEAD), q.reserved, q.cap == 0u ? "cap == 0" : nullptr };
+    const GridOutputs o{ labels, sizeof(uint32_t), false, stats, "data and labels must name live buffers", nullptr,
+                         "data, source, labels and stats must be different buffers", "labels holds fewer than n words" };
+    return grid_query(c, "label_components", g, n, data, source, rule, o,
+        [&](Lane& L, const void* records, const gs4d_record_stat* rows, const KeepRule& k, void* words, gs4d_record_stat* table) {
+            HIPCHK(c, launch_label_components(L.s, L.pair_sort, records, n, q, rows, k, L.neighbour_scratch, (uint32_t*)words, table, L.err_word()));
+            return (int)GS4D_OK;
         });
 }
 
@@ -2148,7 +2167,8 @@ int gs4d_count_labels(gs4d_ctx* c, gs4d_buf labels, size_t n, gs4d_buf seeds, co
     auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("count_labels: ") + msg).c_str()); };
     if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
     if (!rule) return bad("rule == NULL");
-    if (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u) return bad("unknown flag or non-zero reserved field in the rule");
+    KeepRule k;
+    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
     const gs4d_buf names[3] = { labels, seeds, stats };
     Buffer* B = getbuf(c, labels); Buffer* Q = getbuf(c, seeds); Buffer* S = getbuf(c, stats);
     if (!B || !Q || !S) return bad("labels, seeds and stats must name live buffers");
@@ -2157,21 +2177,19 @@ int gs4d_count_labels(gs4d_ctx* c, gs4d_buf labels, size_t n, gs4d_buf seeds, co
     if (Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the seeds buffer holds fewer than n rows");
     if (S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
     if (n == 0) return GS4D_OK;
-    const KeepRule k{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT };
     { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
     { int rc = settle_stats_table(c, *S); if (rc) return rc; }
     { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
     // labels and seeds are read (seeds as gs4d_edit_colours reads its table), stats is a read-modify-write the lane has the table to itself for.  The
     // flag words live in the lane's neighbour scratch, whose reuse the lane's stream orders.
-    return queue_on_lane(c, { B, Q }, { S },
+    return queue_scan_on_lane(c, { B, Q }, { S }, { Q },
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, n));
-            return scan_reserve(c, *Q);
+            return (int)GS4D_OK;
         },
         [&](Lane& L) {
-            { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
             HIPCHK(c, launch_count_labels(L.s, (const uint32_t*)B->d, n, (const gs4d_record_stat*)Q->d, k, L.neighbour_scratch, (gs4d_record_stat*)S->d));
-            return scan_end(c, L, *Q);
+            return (int)GS4D_OK;
         });
 }
 
@@ -2180,44 +2198,18 @@ int gs4d_nearest_neighbours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_nea
                             size_t hit_stride, gs4d_buf stats) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("nearest_neighbours: ") + msg).c_str()); };
-    if (!query) return bad("query == NULL");
+    if (!query) return fail(c, GS4D_E_INVALID, "nearest_neighbours: query == NULL");
     const gs4d_nearest_query q = *query;
-    if ((q.flags & ~(uint32_t)(GS4D_NN_SKIP_HIDDEN | GS4D_NN_SKIP_DEAD | GS4D_NN_INCLUDE_SELF)) != 0u) return bad("unknown flag");
-    if (q.reserved[0] != 0u || q.reserved[1] != 0u || q.reserved[2] != 0u || q.reserved[3] != 0u) return bad("non-zero reserved field in the query");
-    if (q.k == 0u || q.k > 16u) return bad("k must be 1 to 16");
-    if (!neighbour_radius_ok(q.radius)) return bad("the radius must be finite with 2^-63 <= radius < 2^64");
-    if (n >= 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
-    if ((source != 0) != (rule != nullptr)) return bad("source and rule are given together or not at all");
-    if (rule && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return bad("unknown flag or non-zero reserved field in the rule");
-    const gs4d_buf names[4] = { data, hits, stats, source };
-    Buffer* D = getbuf(c, data); Buffer* B = getbuf(c, hits);
-    if (!D || !B) return bad("data and hits must name live buffers");
-    if (!record_stride_ok(hit_stride) || hit_stride < 8 * (size_t)q.k) return bad("hit_stride must be a multiple of 16 from 16 to 1024 that is at least 8 k");
-    if (const int wrong = check_record_names(c, names, 4)) return bad(wrong == 1 ? "bad buffer name" : "data, source, hits and stats must be different buffers");
-    Buffer* S = getbuf(c, stats); Buffer* Q = getbuf(c, source);
-    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
-    if (B->bytes / hit_stride < n) return bad("hits holds fewer than n rows of hit_stride bytes");
-    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
-    if (Q && Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the source buffer holds fewer than n rows");
-    if (n == 0) return GS4D_OK;
-    const KeepRule k = rule ? KeepRule{ rule->min_pixels, rule->min_wmax, rule->min_wsum, rule->flags & (uint32_t)GS4D_KEEP_INVERT } : KeepRule{ 0u, 0u, 0ull, 0u };
-    { int rc = flush_order_if_named(c, names, 4); if (rc) return rc; }
-    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    if (Q) { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
-    // as gs4d_label_components: data and source are read (the 96-byte records, never a shadow); the slots of hits are written, stats is a
-    // read-modify-write the lane has the table to itself for — both "out" of queue_on_lane
-    return queue_on_lane(c, { D, Q }, { B, S },
-        [&](Lane& L) {
-            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, neighbour_scratch_words(n)));
-            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));
-            return Q ? scan_reserve(c, *Q) : (int)GS4D_OK;
-        },
-        [&](Lane& L) {
-            if (Q) { int rc = scan_begin(c, L, *Q); if (rc) return rc; }
-            HIPCHK(c, launch_nearest_neighbours(L.s, L.pair_sort, D->d, n, q, Q ? (const gs4d_record_stat*)Q->d : nullptr, k, L.neighbour_scratch, B->d, hit_stride,
-                                                S ? (gs4d_record_stat*)S->d : nullptr));
-            return Q ? scan_end(c, L, *Q) : (int)GS4D_OK;
+    const GridQuery g{ q.radius, q.flags, (uint32_t)(GS4D_NN_SKIP_HIDDEN | GS4D_NN_SKIP_DEAD | GS4D_NN_INCLUDE_SELF), q.reserved,
+                       q.k == 0u || q.k > 16u ? "k must be 1 to 16" : nullptr };
+    const bool stride_ok = record_stride_ok(hit_stride) && hit_stride >= 8 * (size_t)q.k;
+    const GridOutputs o{ hits, hit_stride, false, stats, "data and hits must name live buffers",
+                         stride_ok ? nullptr : "hit_stride must be a multiple of 16 from 16 to 1024 that is at least 8 k",
+                         "data, source, hits and stats must be different buffers", "hits holds fewer than n rows of hit_stride bytes" };
+    return grid_query(c, "nearest_neighbours", g, n, data, source, rule, o,
+        [&](Lane& L, const void* records, const gs4d_record_stat* rows, const KeepRule& k, void* slots, gs4d_record_stat* table) {
+            HIPCHK(c, launch_nearest_neighbours(L.s, L.pair_sort, records, n, q, rows, k, L.neighbour_scratch, slots, hit_stride, table));
+            return (int)GS4D_OK;
         });
 }
 

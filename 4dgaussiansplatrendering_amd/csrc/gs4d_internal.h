@@ -445,6 +445,17 @@ __device__ __forceinline__ bool keep_row(const uint4 row, const KeepRule k) {
     const uint64_t wsum = (uint64_t)row.z | ((uint64_t)row.w << 32);          // gs4d_record_stat: pixels, wmax, wsum (little endian)
     return (row.x >= k.min_pixels && row.y >= k.min_wmax && wsum >= k.min_wsum) != (k.invert != 0u);
 }
+// c fragments of weight 1 into row i of a table, for every kernel that owns the row it updates (centres.hip, neighbours.hip, components.hip,
+// nearest.hip): pixels += c, wmax = max(wmax, wmax_bits), wsum += c * 2^24 (64-bit, low word first).  A plain 16-byte load, modify, store.
+constexpr uint32_t WEIGHT_ONE_BITS = 0x3F800000u;          // the bits of 1.0f: the wmax of a fragment of weight 1
+__device__ __forceinline__ void add_fragments(uint4* __restrict__ stats, uint64_t i, uint32_t c, uint32_t wmax_bits) {
+    uint4 row = stats[i];
+    row.x += c;
+    row.y = row.y > wmax_bits ? row.y : wmax_bits;
+    const uint64_t sum = (((uint64_t)row.w << 32) | row.z) + ((uint64_t)c << 24);
+    row.z = (uint32_t)sum; row.w = (uint32_t)(sum >> 32);
+    stats[i] = row;
+}
 // gs4d_time_span {t_first, t_last} against the window [t0, t1]: the two closed intervals meet (an empty span, {+inf, -inf}, meets nothing)
 __device__ __forceinline__ bool keep_row(const float2 row, const WindowRule k) { return row.x <= k.t1 && row.y >= k.t0; }
 #endif

@@ -16,53 +16,35 @@
 //   k_nb_buckets       one thread per sorted slot s that holds a source j: the centre of record j again (two 16-byte loads at a scattered record,
 //                      the same function on the same bits) stored as float4 {m.x, m.y, m.z, bits(j)} into cand[s]; and the marks: s is the first
 //                      slot of its key -> table[key].first = s, the last -> table[key].end = s + 1.
-//   k_nb_query<COL>    one thread per record, in SORTED order: thread s has the record of slot s — a source's centre and index are cand[s], any other
-//                      record is loaded through the sorted index and asked whether it takes part.  The lanes of a wave thus hold records of the
-//                      same few cells: they load the same table rows and walk the same candidate runs, which the memory system serves as
-//                      broadcasts instead of 64 scattered loads (measured: DESIGN.md §4).  The price is a scattered row update.
-//                      A record that takes part visits the cells of its range, z outermost; a cell whose bucket an earlier cell
-//                      of the range had is left out (two different cells of one range can share a bucket: walking it twice would count its
-//                      candidates twice; two different cells that share a bucket only add candidates that `near` rejects).  It loads the 8-byte
-//                      table row, walks the run of 16-byte candidates, applies `near`, leaves out j == i by index unless COUNT_SELF, and stops at
-//                      cap.  Then the row update of k_count_centres: a plain 16-byte load, modify, store — row i belongs to one thread alone, and the call
-//                      has the table to itself (queue_on_lane's "out").  Few registers, no LDS: the dependent loads (table row, then candidates)
-//                      are hidden by the other waves of the SIMD.
+//   k_nb_query<COL>    one thread per record, in SORTED order (neighbour_grid.h: slot_record, and why the sorted order pays).  A record that takes
+//                      part walks its candidates (neighbour_grid.h: walk_candidates), applies `near`, leaves out j == i by index unless COUNT_SELF,
+//                      and stops at cap.  Then the row update of k_count_centres (add_fragments): a plain 16-byte load, modify, store, scattered
+//                      here — row i belongs to one thread alone, and the call has the table to itself (queue_on_lane's "out").
 // Scratch (the lane's, neighbour_scratch_words()): cand 16 n bytes, the table 8 * 2^kb, keys and sorted indices 4 n each — 24 n bytes and the table,
 // beside the sort's own.  All byte offsets are 64-bit.  Nothing but rows < n of the table `stats` and the scratch is written; records and source are
 // only read, and only records / rows < n.
 #include "gs4d_internal.h"
 #include "neighbour_query.h"
+#include "neighbour_grid.h"
 
 namespace gs4d {
-
-namespace nb = gs4d_neighbour;
 
 bool neighbour_radius_ok(float r) { return nb::radius_ok(r); }
 int neighbour_bucket_bits(size_t n) { return nb::bucket_bits((uint64_t)n); }
 
-// what every kernel of the call is given
-struct NbArgs { float t; uint32_t flags, cap; float rr; nb::Grid g; int kb; };
-
 template <bool COL>
-__device__ __forceinline__ nb::Fields nb_fields(const float4* __restrict__ rec, uint64_t i) {
-    const float4 p = rec[i * 6u], g = rec[i * 6u + 5u];
-    const float alpha = COL ? rec[i * 6u + 1u].w : 0.0f;
-    return nb::Fields{ { p.x, p.y, p.z }, p.w, alpha, { g.x, g.y, g.z }, g.w };
-}
-
-template <bool COL>
-__global__ __launch_bounds__(NEIGHBOURS_TILE) void k_nb_keys(const float4* __restrict__ rec, uint32_t n, NbArgs a, const uint4* __restrict__ source, KeepRule k,
+__global__ __launch_bounds__(NEIGHBOURS_TILE) void k_nb_keys(const float4* __restrict__ rec, uint32_t n, GridArgs a, const uint4* __restrict__ source, KeepRule k,
                                                              uint32_t* __restrict__ keys) {
     const uint64_t i = (uint64_t)blockIdx.x * NEIGHBOURS_TILE + threadIdx.x;
     if (i >= n) return;
     float m[3];
-    const bool part = nb::takes_part(a.t, a.flags, nb_fields<COL>(rec, i), m);
+    const bool part = nb::takes_part(a.t, a.flags, grid_fields<COL>(rec, i), m);
     const bool src = part && (!source || keep_row(source[i], k));
     const uint32_t b = part ? nb::bucket(nb::cell(m[0], a.g.inv_h), nb::cell(m[1], a.g.inv_h), nb::cell(m[2], a.g.inv_h), a.kb) : 0u;
     keys[i] = src ? b : (1u << a.kb) | b;
 }
 
-__global__ __launch_bounds__(NEIGHBOURS_TILE) void k_nb_buckets(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ index, uint32_t n, NbArgs a,
+__global__ __launch_bounds__(NEIGHBOURS_TILE) void k_nb_buckets(const uint32_t* __restrict__ keys, const uint32_t* __restrict__ index, uint32_t n, GridArgs a,
                                                                 const float4* __restrict__ rec, float4* __restrict__ cand, uint2* __restrict__ table) {
     const uint64_t s = (uint64_t)blockIdx.x * NEIGHBOURS_TILE + threadIdx.x;
     if (s >= n) return;
@@ -71,63 +53,37 @@ __global__ __launch_bounds__(NEIGHBOURS_TILE) void k_nb_buckets(const uint32_t* 
     const uint32_t j = index[s];
     if (j >= n) return;                                        // (the sort permutes 0 .. n - 1: never)
     float m[3];
-    (void)gs4d_centre::centre_at(a.t, nb_fields<false>(rec, j), m);
+    (void)gs4d_centre::centre_at(a.t, grid_fields<false>(rec, j), m);
     cand[s] = make_float4(m[0], m[1], m[2], __uint_as_float(j));
     if (s == 0u || keys[s - 1u] != key) table[key].x = (uint32_t)s;
     if (s + 1u == n || keys[s + 1u] != key) table[key].y = (uint32_t)s + 1u;
 }
 
 template <bool COL>
-__global__ __launch_bounds__(NEIGHBOURS_TILE) void k_nb_query(const float4* __restrict__ rec, uint32_t n, NbArgs a, const float4* __restrict__ cand,
+__global__ __launch_bounds__(NEIGHBOURS_TILE) void k_nb_query(const float4* __restrict__ rec, uint32_t n, GridArgs a, uint32_t cap, const float4* __restrict__ cand,
                                                               const uint2* __restrict__ table, const uint32_t* __restrict__ keys,
                                                               const uint32_t* __restrict__ index, uint4* __restrict__ stats) {
     const uint64_t s0 = (uint64_t)blockIdx.x * NEIGHBOURS_TILE + threadIdx.x;
     if (s0 >= n) return;
-    // the record of sorted slot s0: a source has its centre and its index in cand[s0]; any other record is loaded and asked whether it takes part
     uint32_t i;
     float m[3];
-    if ((keys[s0] >> a.kb) == 0u) {
-        const float4 v = cand[s0];
-        m[0] = v.x; m[1] = v.y; m[2] = v.z; i = __float_as_uint(v.w);
-    } else {
-        i = index[s0];
-        if (i >= n || !nb::takes_part(a.t, a.flags, nb_fields<COL>(rec, i), m)) return;
-    }
-    if (i >= n) return;                                        // (the sort permutes 0 .. n - 1: never)
+    if (slot_record<COL>(rec, n, a, cand, keys, index, s0, i, m) < SLOT_PART) return;
     const bool self = (a.flags & (uint32_t)GS4D_NB_COUNT_SELF) != 0u;
-    int32_t lo[3], hi[3];
-    nb::cell_range(m, a.g, lo, hi);
     uint32_t c = 0;
-    for (int32_t cz = lo[2]; cz <= hi[2] && c < a.cap; ++cz)
-        for (int32_t cy = lo[1]; cy <= hi[1] && c < a.cap; ++cy)
-            for (int32_t cx = lo[0]; cx <= hi[0] && c < a.cap; ++cx) {
-                const uint32_t b = nb::bucket(cx, cy, cz, a.kb);
-                if (nb::bucket_seen(lo, hi, cx, cy, cz, b, a.kb)) continue;
-                const uint2 run = table[b];
-                const uint32_t end = run.y < n ? run.y : n;
-                for (uint32_t s = run.x; s < end; ++s) {
-                    const float4 v = cand[s];
-                    const float mj[3] = { v.x, v.y, v.z };
-                    if (!nb::near(m, mj, a.rr)) continue;
-                    if (!self && __float_as_uint(v.w) == i) continue;
-                    if (++c >= a.cap) break;
-                }
-            }
-    if (c == 0u) return;
-    // c fragments of weight 1: pixels += c, wmax = max(wmax, bits of 1.0f), wsum += c * 2^24 (64-bit, low word first)
-    uint4 row = stats[i];
-    row.x += c;
-    row.y = row.y > 0x3F800000u ? row.y : 0x3F800000u;
-    const uint64_t sum = (((uint64_t)row.w << 32) | row.z) + ((uint64_t)c << 24);
-    row.z = (uint32_t)sum; row.w = (uint32_t)(sum >> 32);
-    stats[i] = row;
+    walk_candidates(m, a.g, a.kb, n, table, cand, [&](const float4 v) {
+        const float mj[3] = { v.x, v.y, v.z };
+        if (!nb::near(m, mj, a.rr)) return true;
+        if (!self && __float_as_uint(v.w) == i) return true;
+        return ++c < cap;                                      // (cap >= 1)
+    });
+    if (c != 0u) add_fragments(stats, i, c, WEIGHT_ONE_BITS);
 }
 
 // the grid phases: keys, sort, memset, bucket table — what gs4d_count_neighbours and gs4d_label_components (components.hip) share
 hipError_t launch_neighbour_grid(hipStream_t st, SortScratch& sort, const void* records, size_t n, float t, float radius, uint32_t flags,
                                  const gs4d_record_stat* source, const KeepRule& rule, uint32_t* scratch, int phases, NeighbourGrid& g) {
     const int kb = neighbour_bucket_bits(n);
-    const NbArgs a{ t, flags, 0u, radius * radius, nb::grid(radius), kb };
+    const GridArgs a{ t, flags, radius * radius, nb::grid(radius), kb };
     // the scratch, in the order of neighbour_scratch_words(): candidates (16-byte aligned: first), table, keys, sorted indices
     float4* const cand = (float4*)scratch;
     uint2* const table = (uint2*)(scratch + 4 * n);
@@ -156,11 +112,11 @@ hipError_t launch_count_neighbours(hipStream_t st, SortScratch& sort, const void
     NeighbourGrid g;
     const hipError_t e = launch_neighbour_grid(st, sort, records, n, q.t, q.radius, q.flags, source, rule, scratch, phases, g);
     if (e != hipSuccess || phases < 4) return e;
-    const NbArgs a{ q.t, q.flags, q.cap, q.radius * q.radius, nb::grid(q.radius), g.kb };
+    const GridArgs a{ q.t, q.flags, q.radius * q.radius, nb::grid(q.radius), g.kb };
     const dim3 grid((uint32_t)((n + NEIGHBOURS_TILE - 1) / NEIGHBOURS_TILE)), block(NEIGHBOURS_TILE);
     const float4* const rec = (const float4*)records;
-    if ((q.flags & (uint32_t)GS4D_NB_SKIP_HIDDEN) != 0u) k_nb_query<true><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, g.cand, g.table, g.keys, g.index, (uint4*)stats);
-    else k_nb_query<false><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, g.cand, g.table, g.keys, g.index, (uint4*)stats);
+    if ((q.flags & (uint32_t)GS4D_NB_SKIP_HIDDEN) != 0u) k_nb_query<true><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, q.cap, g.cand, g.table, g.keys, g.index, (uint4*)stats);
+    else k_nb_query<false><<<grid, block, 0, st>>>(rec, (uint32_t)n, a, q.cap, g.cand, g.table, g.keys, g.index, (uint4*)stats);
     return hipGetLastError();
 }
 

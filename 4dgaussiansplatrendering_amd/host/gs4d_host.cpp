@@ -441,6 +441,33 @@ void gs4d_host_transform_records(size_t n, const float* rec, const gs4d_affine4*
     }
 }
 
+// ---- what the definitions that select by, or add to, a record-statistics table share ----
+namespace {
+constexpr uint32_t ONE_BITS = 0x3F800000u;                  // the bits of 1.0f: the wmax of a fragment of weight 1
+// a rule the device calls take: known flags, a zero reserved field
+bool rule_ok(const gs4d_keep_rule* rule) { return rule->reserved == 0u && (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) == 0u; }
+// whether a row passes the rule: the predicate of gs4d_compact_records (the device's keep_row)
+bool keeps(const gs4d_record_stat& s, const gs4d_keep_rule* rule) {
+    return (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != ((rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u);
+}
+// c fragments of weight 1 into a row (the device's add_fragments)
+void add_fragments(gs4d_record_stat& s, uint32_t c, uint32_t wmax_bits) { s.pixels += c; s.wmax = std::max(s.wmax, wmax_bits); s.wsum += (uint64_t)c << 24; }
+// What the three grid definitions start from: the centres at time t, who takes part under the GS4D_NB_* skips (takes_part of
+// csrc/neighbour_query.h), and who is a source — it takes part and its row of `source` passes the rule (source == null: every such record).
+struct Centres {
+    std::vector<float> m;
+    std::vector<uint8_t> part, src;
+    Centres(size_t n, const float* rec, float t, uint32_t skips, const gs4d_record_stat* source, const gs4d_keep_rule* rule) : m(3 * n), part(n), src(n) {
+        for (size_t i = 0; i < n; ++i) {
+            const float* p = rec + 24 * i;
+            const gs4d_neighbour::Fields r{ { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] };
+            part[i] = gs4d_neighbour::takes_part(t, skips, r, &m[3 * i]);
+            src[i] = part[i] && (!source || keeps(source[i], rule));
+        }
+    }
+};
+}
+
 // The definition of gs4d_edit_colours (gs4d.h), in place: the selection by the rule of gs4d_compact_records, then the edit per channel of the mask.
 // This file is built with -ffp-contract=off: the product and the sums of MUL and LERP are rounded one by one.  SET and COPY move bits.  An edit
 // the device call would refuse (unknown op, channels outside 1 .. 15) edits nothing.
@@ -448,12 +475,8 @@ void gs4d_host_edit_colours(size_t n, float* rec, const gs4d_record_stat* stats,
     if (!edit || edit->op > (uint32_t)GS4D_EDIT_COPY || edit->channels == 0u || edit->channels > 15u) return;
     if (edit->op == (uint32_t)GS4D_EDIT_COPY && !from) return;
     if (stats && !rule) return;
-    const bool invert = stats && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
     for (size_t i = 0; i < n; ++i) {
-        if (stats) {
-            const gs4d_record_stat& s = stats[i];
-            if ((s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) == invert) continue;
-        }
+        if (stats && !keeps(stats[i], rule)) continue;
         for (uint32_t ch = 0; ch < 4u; ++ch) {
             if (!((edit->channels >> ch) & 1u)) continue;
             float* const c = rec + 24 * i + 4 + ch;
@@ -481,7 +504,7 @@ void gs4d_host_count_centres(size_t n, const float* rec, const gs4d_centre_query
         const gs4d_centre::Fields r{ { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] };
         if (!gs4d_centre::takes_part(*q, hw, hh, r, mask)) continue;
         gs4d_record_stat& s = stats[i];
-        if (q->op == (uint32_t)GS4D_CQ_ADD) { s.pixels += 1u; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += 1ull << 24; }
+        if (q->op == (uint32_t)GS4D_CQ_ADD) add_fragments(s, 1u, ONE_BITS);
         else s = gs4d_record_stat{ 0u, 0u, 0ull };
     }
 }
@@ -495,12 +518,7 @@ void gs4d_host_measure_records(size_t n, const float* rec, const gs4d_measure_qu
     for (int w = 0; w < ms::ROW_WORDS; ++w) row[w] = ms::row_empty(w);
     const uint32_t known = GS4D_MS_SKIP_HIDDEN | GS4D_MS_SKIP_DEAD;
     const bool valid = q && (q->flags & ~known) == 0u && q->reserved[0] == 0u && q->reserved[1] == 0u && !(stats && !rule);
-    const bool invert = valid && stats && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
-    auto selected = [&](size_t i) {
-        if (!stats) return true;
-        const gs4d_record_stat& s = stats[i];
-        return (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert;
-    };
+    auto selected = [&](size_t i) { return !stats || keeps(stats[i], rule); };
     auto fields = [&](size_t i) {
         const float* p = rec + 24 * i;
         return ms::Fields{ { { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] }, { p[8], p[13], p[18] } };
@@ -526,31 +544,16 @@ void gs4d_host_count_neighbours(size_t n, const float* rec, const gs4d_neighbour
                                 gs4d_record_stat* stats) {
     namespace nb = gs4d_neighbour;
     if (!q || !nb::query_ok(*q) || (source && !rule)) return;
-    if (source && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return;
-    const bool invert = source && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    if (source && !rule_ok(rule)) return;
     const bool self = (q->flags & (uint32_t)GS4D_NB_COUNT_SELF) != 0u;
     const float rr = q->radius * q->radius;
-    // the centres, who takes part, who is a source
-    std::vector<float> m(3 * n);
-    std::vector<uint8_t> part(n), src(n);
+    const Centres g(n, rec, q->t, q->flags, source, rule);
     for (size_t i = 0; i < n; ++i) {
-        const float* p = rec + 24 * i;
-        const nb::Fields r{ { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] };
-        part[i] = nb::takes_part(q->t, q->flags, r, &m[3 * i]);
-        src[i] = part[i];
-        if (src[i] && source) {
-            const gs4d_record_stat& s = source[i];
-            src[i] = (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert;
-        }
-    }
-    for (size_t i = 0; i < n; ++i) {
-        if (!part[i]) continue;
+        if (!g.part[i]) continue;
         uint32_t c = 0;
         for (size_t j = 0; j < n && c < q->cap; ++j)
-            if (src[j] && (j != i || self) && nb::near(&m[3 * i], &m[3 * j], rr)) ++c;
-        if (c == 0u) continue;
-        gs4d_record_stat& s = stats[i];
-        s.pixels += c; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += (uint64_t)c << 24;
+            if (g.src[j] && (j != i || self) && nb::near(&g.m[3 * i], &g.m[3 * j], rr)) ++c;
+        if (c != 0u) add_fragments(stats[i], c, ONE_BITS);
     }
 }
 
@@ -572,22 +575,13 @@ void gs4d_host_label_components(size_t n, const float* rec, const gs4d_component
     if (!q || n >= 0xFFFFFFFFull || (source && !rule)) return;
     const gs4d_neighbour_query as_nb{ q->t, q->radius, q->cap, q->flags, { q->reserved[0], q->reserved[1], q->reserved[2], q->reserved[3] } };
     if ((q->flags & ~(uint32_t)(GS4D_CC_SKIP_HIDDEN | GS4D_CC_SKIP_DEAD)) != 0u || !nb::query_ok(as_nb)) return;
-    if (source && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return;
-    const bool invert = source && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    if (source && !rule_ok(rule)) return;
     const float rr = q->radius * q->radius;
-    std::vector<float> m(3 * n);
-    std::vector<uint8_t> member(n);
+    const Centres g(n, rec, q->t, q->flags, source, rule);
+    const std::vector<float>& m = g.m;
+    const std::vector<uint8_t>& member = g.src;                // a member is what the other two calls name a source
     std::vector<uint32_t> parent(n);
-    for (size_t i = 0; i < n; ++i) {
-        const float* p = rec + 24 * i;
-        const nb::Fields r{ { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] };
-        member[i] = nb::takes_part(q->t, q->flags, r, &m[3 * i]);
-        if (member[i] && source) {
-            const gs4d_record_stat& s = source[i];
-            member[i] = (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert;
-        }
-        parent[i] = (uint32_t)i;
-    }
+    for (size_t i = 0; i < n; ++i) parent[i] = (uint32_t)i;
     PlainParents mem{ parent.data() };
     for (size_t i = 0; i < n; ++i) {
         if (!member[i]) continue;
@@ -602,27 +596,19 @@ void gs4d_host_label_components(size_t n, const float* rec, const gs4d_component
     if (!stats) return;
     for (size_t i = 0; i < n; ++i) {
         if (!member[i]) continue;
-        const uint32_t c = std::min(q->cap, size[labels[i]]);
-        gs4d_record_stat& s = stats[i];
-        s.pixels += c; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += (uint64_t)c << 24;
+        add_fragments(stats[i], std::min(q->cap, size[labels[i]]), ONE_BITS);
     }
 }
 
 // The definition of gs4d_count_labels (gs4d.h), in place on the table: the labels of the seeds, then one fragment for every record whose label is
 // one of them.  A word >= n is no label.
 void gs4d_host_count_labels(size_t n, const uint32_t* labels, const gs4d_record_stat* seeds, const gs4d_keep_rule* rule, gs4d_record_stat* stats) {
-    if (!rule || rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u) return;
-    const bool invert = (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    if (!rule || !rule_ok(rule)) return;
     std::vector<uint8_t> hit(n, 0);
-    for (size_t j = 0; j < n; ++j) {
-        const gs4d_record_stat& s = seeds[j];
-        if (labels[j] < n && (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert) hit[labels[j]] = 1;
-    }
-    for (size_t i = 0; i < n; ++i) {
-        if (!(labels[i] < n && hit[labels[i]])) continue;
-        gs4d_record_stat& s = stats[i];
-        s.pixels += 1u; s.wmax = std::max(s.wmax, 0x3F800000u); s.wsum += 1ull << 24;
-    }
+    for (size_t j = 0; j < n; ++j)
+        if (labels[j] < n && keeps(seeds[j], rule)) hit[labels[j]] = 1;
+    for (size_t i = 0; i < n; ++i)
+        if (labels[i] < n && hit[labels[i]]) add_fragments(stats[i], 1u, ONE_BITS);
 }
 
 // The definition of gs4d_nearest_neighbours (gs4d.h): the brute-force double loop over the texts of csrc/neighbour_query.h and
@@ -634,29 +620,18 @@ void gs4d_host_nearest_neighbours(size_t n, const float* rec, const gs4d_nearest
     namespace nb = gs4d_neighbour;
     namespace nn = gs4d_nearest;
     if (!q || !nn::query_ok(*q) || !nn::stride_ok(hit_stride, q->k) || n >= 0xFFFFFFFFull || (source && !rule)) return;
-    if (source && (rule->reserved != 0u || (rule->flags & ~(uint32_t)GS4D_KEEP_INVERT) != 0u)) return;
-    const bool invert = source && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
+    if (source && !rule_ok(rule)) return;
     const bool self = (q->flags & (uint32_t)GS4D_NN_INCLUDE_SELF) != 0u;
     const uint32_t skips = q->flags & (uint32_t)(GS4D_NN_SKIP_HIDDEN | GS4D_NN_SKIP_DEAD);
     const float rr = q->radius * q->radius;
-    std::vector<float> m(3 * n);
-    std::vector<uint8_t> part(n), src(n);
-    for (size_t i = 0; i < n; ++i) {
-        const float* p = rec + 24 * i;
-        const nb::Fields r{ { p[0], p[1], p[2] }, p[3], p[7], { p[20], p[21], p[22] }, p[23] };
-        part[i] = nb::takes_part(q->t, skips, r, &m[3 * i]);
-        src[i] = part[i];
-        if (src[i] && source) {
-            const gs4d_record_stat& s = source[i];
-            src[i] = (s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) != invert;
-        }
-    }
+    const Centres g(n, rec, q->t, skips, source, rule);
+    const std::vector<float>& m = g.m;
     for (size_t i = 0; i < n; ++i) {
         uint64_t best[nn::K_MAX];
         for (uint64_t& b : best) b = nn::EMPTY;
-        if (part[i])
+        if (g.part[i])
             for (size_t j = 0; j < n; ++j)
-                if (src[j] && (j != i || self) && nb::near(&m[3 * i], &m[3 * j], rr)) nn::insert(best, nn::order_key(nn::dist2(&m[3 * i], &m[3 * j]), (uint32_t)j));
+                if (g.src[j] && (j != i || self) && nb::near(&m[3 * i], &m[3 * j], rr)) nn::insert(best, nn::order_key(nn::dist2(&m[3 * i], &m[3 * j]), (uint32_t)j));
         unsigned char* const row = (unsigned char*)hits + i * hit_stride;
         uint32_t f = 0;
         for (uint32_t p = 0; p < q->k; ++p) {
@@ -664,9 +639,7 @@ void gs4d_host_nearest_neighbours(size_t n, const float* rec, const gs4d_nearest
             std::memcpy(row + 8 * p, slot, 8);
             if (best[p] != nn::EMPTY) f = p + 1u;
         }
-        if (!stats || f == 0u) continue;
-        gs4d_record_stat& s = stats[i];
-        s.pixels += f; s.wmax = std::max(s.wmax, (uint32_t)(best[f - 1u] >> 32)); s.wsum += (uint64_t)f << 24;
+        if (stats && f != 0u) add_fragments(stats[i], f, (uint32_t)(best[f - 1u] >> 32));
     }
 }
 
@@ -692,12 +665,8 @@ void gs4d_host_transform_selected(size_t n, float* rec, const gs4d_record_stat* 
     const bool pivot = xf->flags != 0u;
     float c[3] = { xf->pivot[0], xf->pivot[1], xf->pivot[2] };
     if (xf->flags == (uint32_t)GS4D_XS_PIVOT_MEASURE) gs4d_host_measure_centre(measure, c);
-    const bool invert = stats && (rule->flags & (uint32_t)GS4D_KEEP_INVERT) != 0u;
     for (size_t i = 0; i < n; ++i) {
-        if (stats) {
-            const gs4d_record_stat& s = stats[i];
-            if ((s.pixels >= rule->min_pixels && s.wmax >= rule->min_wmax && s.wsum >= rule->min_wsum) == invert) continue;
-        }
+        if (stats && !keeps(stats[i], rule)) continue;
         float* const p = rec + 24 * i;
         float q[24], out[24];
         std::memcpy(q, p, sizeof q);

@@ -58,14 +58,14 @@ $(CSRC)/centres.o: $(CSRC)/centres.hip $(CSRC)/centre_query.h $(CSRC)/gs4d_inter
 # measure_record.h is the one text of what a record adds to gs4d_measure_records' measurement (it takes the centre and the skips from centre_query.h)
 $(CSRC)/measure.o: $(CSRC)/measure.hip $(CSRC)/measure_record.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
-# neighbour_query.h is the one text of gs4d_count_neighbours' definition and of its cell function (it takes the centre and the skips from centre_query.h)
-$(CSRC)/neighbours.o: $(CSRC)/neighbours.hip $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+# neighbour_query.h is the one text of gs4d_count_neighbours' definition and of its cell function (it takes the centre and the skips from centre_query.h); neighbour_grid.h is the one text of the device's sorted-slot fetch and cell walk, which components.hip and nearest.hip compile too
+$(CSRC)/neighbours.o: $(CSRC)/neighbours.hip $(CSRC)/neighbour_grid.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # gs4d_label_components walks the grid of neighbours.hip with the same `near`; component_union.h is the one text of its union-find (the host library and tests/component_union_stress.cpp compile it too)
-$(CSRC)/components.o: $(CSRC)/components.hip $(CSRC)/component_union.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/components.o: $(CSRC)/components.hip $(CSRC)/neighbour_grid.h $(CSRC)/component_union.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # gs4d_nearest_neighbours walks the grid of neighbours.hip too; nearest_query.h is the one text of its order key, its dist2 and its sorted insertion (the host library compiles it too)
-$(CSRC)/nearest.o: $(CSRC)/nearest.hip $(CSRC)/nearest_query.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/nearest.o: $(CSRC)/nearest.hip $(CSRC)/neighbour_grid.h $(CSRC)/nearest_query.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # make BUILD_PLAIN=1: gs4d_build_records with every thread storing its own record, without the LDS staging (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/build.o: $(CSRC)/build.hip $(CSRC)/build_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
