@@ -90,6 +90,10 @@ struct DrawArgs {
     uint32_t draw_ord = 0;          // the draw's ordinal within its frame (a re-run keeps it)
     gs4d_buf zplane = 0;            // the depth-test plane bound when the draw was issued (gs4d_set_depth_test; 0: no test) — it, too, makes the projection store depths
     gs4d_buf stats = 0; size_t stats_n = 0;      // the record-statistics buffer bound when the draw was issued and its records (gs4d_set_record_stats; 0: none)
+    // The draw builds no tile-list entry that cannot change a pixel (records of alpha 0, tiles only the discarded part of a footprint reaches: DESIGN.md §4).
+    // Decided when the draw is issued, kept by its re-runs: the default blend function (a fragment of alpha 0 and a discarded one are no-ops there; any other
+    // function is applied fragment by fragment and its entry counts are the quad's), and not a context's first splat draw, which builds every entry.
+    bool lean = false;
 };
 
 struct Framebuffer {
@@ -212,6 +216,13 @@ struct gs4d_ctx {
     // margin — no scan and no scatter kernel.  The device checks the guess; a draw that does not fit is re-run exactly.  GS4D_STAGED=0 switches it
     // off (test hook).
     bool stage_enable = true, stage_known = false, stage_box_enable = true;
+    // Entries that cannot change a pixel (preprocess.hip emit(), draws of the default blend function): records of alpha 0 get none (GS4D_CULL_ALPHA0=0
+    // switches that off), and the pixel rectangle is the smaller of the quad's box and the discard disc's (GS4D_TIGHT_RECT=0: the quad's).  Test hooks.
+    bool cull_alpha0 = true, tight_rect = true;
+    // Splat draws issued so far.  A context's FIRST draw builds every entry of every quad's box: its verdict is the first measurement the entry storage, the list
+    // capacity and the staged capacities of the following draws are sized from, and tests/test_gpu_render.py (configs[4] at full size: 5.4e8 entries, one re-run)
+    // and tests/test_gpu_capacity.py (the long tile in the image corner) pin its entry count and longest list to the quads' boxes of all records.
+    uint64_t splat_draws = 0;
     uint32_t stage_max_run = 0, stage_max_bucket = 0, stage_max_seg = 0; uint64_t stage_geom = 0;
     uint32_t stage_box_margin = 1;  // blocks added on every side of it; doubled (up to 16) whenever a draw had entries outside its box
     uint32_t stage_box = BOX_NONE;  // blocks of tiles that held entries in the last staged draw of this geometry (TileLists::box); BOX_NONE: not known
@@ -580,7 +591,8 @@ int enqueue_projection(gs4d_ctx* c, Lane& L, const DrawArgs& a, const DrawShape&
     if (s.ob && !v2) { int rc = lane_access(c, *s.ob, false); if (rc) return rc; s.ob->rd_mask |= 1u << a.lane; }
     {
         StageTimer t(c, GS4D_T_PREPROCESS);
-        const PreOut po = { L.proj, (v2 && L.tl.staged) ? nullptr : L.trects, has_aux(a.out) || a.zplane != 0 };
+        // entries that cannot change a pixel are not built (a.lean: decided when the draw was issued, draw_common)
+        const PreOut po = { L.proj, (v2 && L.tl.staged) ? nullptr : L.trects, has_aux(a.out) || a.zplane != 0, a.lean && c->cull_alpha0, a.lean && c->tight_rect };
         L.trects_in_order = false;
         TileCount tc;
         { int rc = fill_tile_count(c, L, a, s.npre, v2, fused, tc); if (rc) return rc; }
@@ -1042,6 +1054,8 @@ int gs4d_create(int device, int width, int height, gs4d_ctx** out) {
     if (const char* ev = getenv("GS4D_RENAME")) c->rename_storage = atoi(ev) != 0;
     if (const char* ev = getenv("GS4D_STAGED_BOX")) c->stage_box_enable = atoi(ev) != 0;                                   // test hook: 0 = the compositor of a staged draw is launched for every tile
     if (const char* ev = getenv("GS4D_STAGED")) c->stage_enable = atoi(ev) != 0;                                          // test hook: 0 = every unordered draw builds its lists exactly (scan + scatter)
+    if (const char* ev = getenv("GS4D_CULL_ALPHA0")) c->cull_alpha0 = atoi(ev) != 0;                                      // test hook: 0 = records of alpha 0 keep their tile-list entries
+    if (const char* ev = getenv("GS4D_TIGHT_RECT")) c->tight_rect = atoi(ev) != 0;                                        // test hook: 0 = the pixel rectangle is the quad's box
     if (const char* ev = getenv("GS4D_SLABS")) { const int v = atoi(ev); if (v >= 1 && v <= (int)V2_MAX_SLABS) { c->slabs = 1; while ((int)c->slabs < v) c->slabs *= 2u; } }      // test hook: depth slabs (a power of two)                         // test hook: instance-ordered tile lists for every draw
     auto bail = [&](int rc) { g_create_error = c->err; gs4d_destroy(c); return rc; };
     if ((e = create_lane_streams(c)) != hipSuccess) return bail(hipfail(c, e, "hipStreamCreate"));
@@ -1794,6 +1808,7 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     const bool over = a.blend_src == GS4D_SRC_ALPHA && a.blend_dst == GS4D_ONE_MINUS_SRC_ALPHA;       // any other function is applied in draw order: instance-ordered lists
     a.out = c->fbs[c->cur_fb].out; a.draw_ord = c->fbs[c->cur_fb].draws; a.zplane = c->depth_plane;
     a.stats = c->record_stats; a.stats_n = c->record_stats_n;
+    a.lean = over && c->splat_draws > 0;
     if (c->atomic_rank && c->path_pref != 1 && over) {
         Buffer* data = getbuf(c, a.data);
         bool ok = false;
@@ -1838,6 +1853,7 @@ static int draw_common(gs4d_ctx* c, DrawArgs& a) {
     a.fuse = false;                    // a re-run of this draw finds the keys written and the sort queued
     if (rc) { L.proj_n = before; return rc; }
     c->fbs[a.fb].draws++;                                   // the next splat draw into this frame has the next ordinal
+    c->splat_draws++;
     if (L.proj_n) { L.pending = true; L.pending_args = a; c->fbs[c->cur_fb].is_clear = false; L.drawn = true; if (a.v2) c->stat_v2_draws++; }   // proj_n != 0 <=> raster work was enqueued
     else L.proj_n = before;
     if (c->profiling) { if (c->prof_frame < gs4d_ctx::PROF_FRAMES && c->prof_tick % (uint64_t)c->prof_every == 0) c->prof_frame++; c->prof_tick++; }

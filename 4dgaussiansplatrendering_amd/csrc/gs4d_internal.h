@@ -387,7 +387,9 @@ hipError_t launch_soa_repack(hipStream_t st, const float* aos96, size_t n, float
 inline const float4* soa_sig3(const float4* soa, size_t n, const SoaInfo& info) { return info.layout == SOA_STATIC3D ? nullptr : soa + (info.layout == SOA_SYM ? 3 : 5) * n; }
 // Each preprocess launch also writes the packed tile rectangle of every record (pack_trect).
 // aux: the draw's image has aux outputs or the draw has a depth test — the projection stores each record's depth in the last float of its record (else 0).
-struct PreOut { float4* proj; uint32_t* trects; bool aux = false; };
+// cull_alpha0, tight: set for draws of the default blend function only (enqueue_projection).  cull_alpha0: a record whose alpha compares equal to 0 gets
+// no tile-list entry (its projected record is unchanged); tight: the pixel rectangle is cut down to the box of the fragment test's discard disc (footprint_rect.h).
+struct PreOut { float4* proj; uint32_t* trects; bool aux = false; bool cull_alpha0 = false; bool tight = false; };
 hipError_t launch_preprocess_4d(hipStream_t st, const float4* soa, size_t soa_n /* records in the buffer: the plane stride */, const SoaInfo& info, size_t n, const Uniforms& u, int W, int H, PreOut out, const TileCount& tc);
 hipError_t launch_preprocess_3d(hipStream_t st, const float* verts72, size_t n, const Uniforms& u, int W, int H, PreOut out, const TileCount& tc);
 hipError_t launch_preprocess_2d(hipStream_t st, const float* rec48, size_t n, const Uniforms& u, int W, int H, PreOut out, const TileCount& tc);

@@ -8,6 +8,7 @@
 // Compiled with -ffp-contract=off and hipcc's default IEEE divide/sqrt: everything that decides pixel coverage
 // (cx, cy, a0, a1) is bit-identical to the CPU checker, which evaluates the same expressions in the same order.
 #include "gs4d_internal.h"
+#include "footprint_rect.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -162,14 +163,11 @@ __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid,
             // conservative pixel rectangle: candidates are pixels whose centre lies within the bbox grown by a margin that
             // dominates the rounding of the coverage predicate
             float mx = 0.01f + 1e-5f * hx, my = 0.01f + 1e-5f * hy;
-            float fx0 = ceilf(cx - hx - mx - 0.5f), fx1 = floorf(cx + hx + mx - 0.5f);
-            float fy0 = ceilf(cy - hy - my - 0.5f), fy1 = floorf(cy + hy + my - 0.5f);
-            fx0 = fmaxf(fx0, 0.0f); fy0 = fmaxf(fy0, 0.0f);
-            fx1 = fminf(fx1, (float)(W - 1)); fy1 = fminf(fy1, (float)(H - 1));
-            if (fx0 <= fx1 && fy0 <= fy1) {
-                rect0 = (uint32_t)fx0 | ((uint32_t)fy0 << 16);
-                rect1 = (uint32_t)fx1 | ((uint32_t)fy1 << 16);
-            }
+            // out.tight: the fragment test also discards what lies outside a disc of the quad's plane — the rectangle is the smaller of the
+            // two boxes per axis (footprint_rect.h); hx, hy of the record stay the quad's
+            float tx = hx, ty = hy;
+            if (out.tight) gs4d_footprint::tighten(q.e0x, q.e0y, q.e1x, q.e1y, q.s0, q.s1, sx, sy, tx, ty);
+            gs4d_footprint::pixel_rect(cx, cy, tx, ty, mx, my, W, H, rect0, rect1);
         }
     }
     if (!valid) { cx = cy = a0x = a0y = a1x = a1y = hx = hy = 0.0f; alpha = 0.0f; rect0 = 1u; rect1 = 0u; depth = 0.0f; }
@@ -177,7 +175,12 @@ __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid,
     // the colour through unchanged that is a per-record operation (the 3D-Full shader multiplies by c first: clamped per fragment)
     // (fminf(fmaxf(x, 0), 1), the checker's form: a NaN colour clamps to 0 — __saturatef's compares let it through to every pixel of the footprint)
     if (clamp_rgb) { r = fminf(fmaxf(r, 0.0f), 1.0f); g = fminf(fmaxf(g, 0.0f), 1.0f); b = fminf(fmaxf(b, 0.0f), 1.0f); }
-    if (out.trects) out.trects[i] = pack_trect(rect0, rect1);      // (null: nothing downstream reads it — a staged draw writes its list entries itself)
+    // out.cull_alpha0 (a draw of the default blend function): a record whose alpha compares equal to 0 changes no pixel ("Records
+    // that cannot change a pixel") — its record stays what it is, but the lists get no entry of it: the rectangle handed to the counting and
+    // placing walks and the packed one are empty.  (The proof needs finite colours and a finite depth: w * y = 0 for w = 0.)
+    uint32_t list0 = rect0, list1 = rect1;
+    if (out.cull_alpha0 && alpha == 0.0f && fin(r) && fin(g) && fin(b) && fin(depth)) { list0 = 1u; list1 = 0u; }
+    if (out.trects) out.trects[i] = pack_trect(list0, list1);      // (null: nothing downstream reads it — a staged draw writes its list entries itself)
     float4* o = out.proj + (size_t)i * 4;
     // (x components of the two affine rows side by side, likewise y: the compositor forms u and v with packed two-float instructions)
     o[0] = make_float4(cx, cy, a0x, a1x);
@@ -188,7 +191,7 @@ __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid,
     // missing has to be merged with what memory holds.  Measured with this store left out (round 3, 10^7 records): the projection kernel
     // 373 -> 459 us; at 10^6 records no difference (40.1 / 40.4 us).
     o[3] = make_float4(hx, hy, valid ? 1.0f : 0.0f, out.aux ? depth : 0.0f);
-    return make_uint2(rect0, rect1);
+    return make_uint2(list0, list1);
 }
 
 // Unordered draw path (tilelist.hip): the projection kernel also counts, per bucket b = tile % nb, the tile-list entries of the segment

@@ -38,7 +38,8 @@ lib: $(LIB)
 
 $(CSRC)/sort.o: $(CSRC)/sort.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
-$(CSRC)/preprocess.o: $(CSRC)/preprocess.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+# footprint_rect.h is the one text of the pixel rectangle (tests/footprint_rect_check.cpp compiles it too)
+$(CSRC)/preprocess.o: $(CSRC)/preprocess.hip $(CSRC)/footprint_rect.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 $(CSRC)/lines.o: $(CSRC)/lines.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@

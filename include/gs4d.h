@@ -1087,6 +1087,11 @@ GS4D_API int gs4d_get_timeline(gs4d_ctx* ctx, float* ms, int max_frames, int* fr
 GS4D_API int gs4d_get_stats(gs4d_ctx* ctx, uint64_t stats[8]);                    /* [0] low 32 bits: tile-list entries of the last draw, high 32 bits: draws so far whose projection kernel wrote the list entries itself (staged lists: DESIGN.md 3c), [1] low 40 bits: capacity, high 24 bits: staged draws whose guess did not fit and that were re-run exactly, [2] low 32 bits: re-runs after overflow, high 32 bits: draws that aborted on the device and were cleared away unobserved (never re-run; a frame loop without read-backs checks this stays 0), [3] low 32 bits: tiles, bits 32-39: bytes per record the last 4D draw's projection read (64: static 3D splats, 72: symmetric sig, 96: anything), bits 40-63: tiles the compositing kernel of the last unordered draw was launched for (a staged draw: the box of tiles that held entries in the frames before, a few tiles wider — an entry outside it is found on the device and the draw re-run exactly, counted with the staged misses),
                                                                                       [4] low 32 bits: radix passes launched by the last gs4d_sort_pairs, high 32 bits: candidate streams gs4d_create discarded because they shared a hardware queue with a frame lane chosen before them (0 in a process without other streams), [5] low 32 bits: by the last draw's tile sort (0: the draw built unordered tile lists), high 32 bits: gs4d_keygen calls that gave their output buffers fresh storage instead of waiting for another frame lane (one key / index pair shared by all frames),
                                                                                       [6] bits 0..15: frame lanes, bits 16..31: lanes whose stream shares a hardware queue with another lane's (0 unless the process has fewer free queues than lanes: such a context runs ~10 % slower), high 32 bits: draws that generated the depth keys of the preceding gs4d_keygen themselves (see gs4d_keygen), [7] low 32 bits: draws so far on the unordered tile-list path, high 32 bits: longest tile list of the last such draw */
+/* Tile-list entries that cannot change a pixel are not built, in draws of the default blend function (GL_SRC_ALPHA, GL_ONE_MINUS_SRC_ALPHA):
+ * a record whose alpha compares equal to 0 gets no entry (its projected record is unchanged), and a record's pixel rectangle is the smaller, per axis, of
+ * its quad's box and the box of the disc outside which the fragment test discards.  Pixels, aux and ID planes, record statistics, sorted keys and permutation
+ * are bit for bit what they are without; stats[0] counts fewer entries.  A context's first splat draw builds every entry all the same.  Environment, read at gs4d_create like GS4D_STAGED (test hooks):
+ * GS4D_CULL_ALPHA0=0 keeps the entries of alpha-0 records, GS4D_TIGHT_RECT=0 keeps the quad's box. */
 /* What the depth sorts did, beside gs4d_get_stats (whose eight words keep their meaning: depth_sort_passes stays the digit passes of the LSD plan).
  * Depth keys whose host-proven span is 19..27 bits are sorted by an MSD/LSD hybrid — one global pass on the 9-bit top digit, then one launch that
  * finishes every bucket in LDS — unless the latest bucket report says that a bucket does not fit (a crowded key distribution: the LSD passes again).
