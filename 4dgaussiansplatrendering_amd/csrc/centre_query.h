@@ -6,11 +6,7 @@
 #ifndef GS4D_CENTRE_QUERY_H
 #define GS4D_CENTRE_QUERY_H
 
-#if defined(__HIPCC__)
-#define GS4D_CQ_HD __host__ __device__
-#else
-#define GS4D_CQ_HD
-#endif
+#include "hd.h"
 
 namespace gs4d_centre {
 
@@ -18,18 +14,18 @@ namespace gs4d_centre {
 struct Fields { float p[3], mu_t, a, sig3[3], s44; };
 
 // The pieces gs4d_measure_records shares (csrc/measure_record.h).  The centre at time t, that of gs4d_shade_sh and GS4D_KEY_VIEW_Z, into m; returns dt
-GS4D_CQ_HD inline float centre_at(float t, const Fields& r, float m[3]) {
+GS4D_HD inline float centre_at(float t, const Fields& r, float m[3]) {
     const float dt = t - r.mu_t;
     const float k = (1.0f / r.s44) * dt;
     m[0] = r.p[0] + (k * r.sig3[0]); m[1] = r.p[1] + (k * r.sig3[1]); m[2] = r.p[2] + (k * r.sig3[2]);
     return dt;
 }
 // the two skips: alpha not above 0; the time argument below GS4D_TIME_DEAD_ARG (a NaN is not)
-GS4D_CQ_HD inline bool hidden(const Fields& r) { return !(r.a > 0.0f); }
-GS4D_CQ_HD inline bool dead_at(float dt, const Fields& r) { return ((-0.5f * dt) * (1.0f / r.s44)) * dt < GS4D_TIME_DEAD_ARG; }
+GS4D_HD inline bool hidden(const Fields& r) { return !(r.a > 0.0f); }
+GS4D_HD inline bool dead_at(float dt, const Fields& r) { return ((-0.5f * dt) * (1.0f / r.s44)) * dt < GS4D_TIME_DEAD_ARG; }
 
 // hw, hh: half the width and the height of the context's image (W * 0.5f, H * 0.5f); mask: q.w * q.h bytes, rows bottom-up, or null
-GS4D_CQ_HD inline bool takes_part(const gs4d_centre_query& q, float hw, float hh, const Fields& r, const uint8_t* mask) {
+GS4D_HD inline bool takes_part(const gs4d_centre_query& q, float hw, float hh, const Fields& r, const uint8_t* mask) {
     const uint32_t tests = q.tests;
     float m[3];
     const float dt = centre_at(q.t, r, m);

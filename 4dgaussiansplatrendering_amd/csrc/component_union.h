@@ -24,12 +24,7 @@
 #define GS4D_COMPONENT_UNION_H
 
 #include <stdint.h>
-
-#if defined(__HIPCC__)
-#define GS4D_CU_HD __host__ __device__
-#else
-#define GS4D_CU_HD
-#endif
+#include "hd.h"
 
 namespace gs4d_union {
 
@@ -37,7 +32,7 @@ constexpr uint32_t OVERRUN = 0xFFFFFFFFu;        // what find returns when its t
 
 // the root of x's tree.  Path halving on the way: a node whose grandparent differs from its parent is lowered to it (argument 1: still an ancestor).
 template <class M>
-GS4D_CU_HD inline uint32_t find(M& mem, uint32_t x, uint32_t n) {
+GS4D_HD inline uint32_t find(M& mem, uint32_t x, uint32_t n) {
     for (uint64_t trips = 0; trips <= (uint64_t)n; ++trips) {
         const uint32_t p = mem.load(x);
         if (p == x) return x;
@@ -53,7 +48,7 @@ GS4D_CU_HD inline uint32_t find(M& mem, uint32_t x, uint32_t n) {
 
 // one tree for a and b: the larger root goes under the smaller.  false: a trip bound ran out.
 template <class M>
-GS4D_CU_HD inline bool unite(M& mem, uint32_t a, uint32_t b, uint32_t n) {
+GS4D_HD inline bool unite(M& mem, uint32_t a, uint32_t b, uint32_t n) {
     for (uint64_t trips = 0; trips <= (uint64_t)n; ++trips) {
         a = find(mem, a, n);
         b = find(mem, b, n);

@@ -25,12 +25,7 @@
 
 #include <math.h>
 #include <stdint.h>
-
-#if defined(__HIPCC__)
-#define GS4D_FR_HD __host__ __device__
-#else
-#define GS4D_FR_HD
-#endif
+#include "hd.h"
 
 namespace gs4d_footprint {
 
@@ -40,7 +35,7 @@ constexpr float FOOT_MAX_ANISO = 1024.0f;
 constexpr float FOOT_UP = 1.0f + 0x1p-20f;       // dominates the roundings of the half extent: two squares, a sum, the square root (1 ulp on the device), two products
 
 // the square root of a value in [1e-30, inf]: the device's v_sqrt_f32 is within 1 ulp there, which FOOT_UP covers
-GS4D_FR_HD inline float foot_sqrt(float x) {
+GS4D_HD inline float foot_sqrt(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_sqrtf(x);
 #else
@@ -51,7 +46,7 @@ GS4D_FR_HD inline float foot_sqrt(float x) {
 // The half extents (hx, hy) of the quad's box, as the projection computed them, cut down to the disc's box where that is smaller.
 // e0, e1: the quad's axes; s0, s1 > 0: their lengths; sx, sy: window scale.  Anything the bound does not cover — K > FOOT_MAX_ANISO, a
 // sum of squares that underflows, a NaN — leaves the quad's extent: fminf returns its other operand for a NaN.
-GS4D_FR_HD inline void tighten(float e0x, float e0y, float e1x, float e1y, float s0, float s1, float sx, float sy, float& hx, float& hy) {
+GS4D_HD inline void tighten(float e0x, float e0y, float e1x, float e1y, float s0, float s1, float sx, float sy, float& hx, float& hy) {
     const float lo = fminf(s0, s1), hi = fmaxf(s0, s1);
     if (!(hi <= FOOT_MAX_ANISO * lo)) return;
     const float ax = e0x * s0, bx = e1x * s1, ay = e0y * s0, by = e1y * s1;
@@ -62,7 +57,7 @@ GS4D_FR_HD inline void tighten(float e0x, float e0y, float e1x, float e1y, float
 
 // Pixel rectangle (x0 | y0 << 16, x1 | y1 << 16; (1, 0): empty) of the pixels of a W x H image whose centre lies within (hx, hy) of (cx, cy),
 // grown by (mx, my).  All arguments finite.
-GS4D_FR_HD inline void pixel_rect(float cx, float cy, float hx, float hy, float mx, float my, int W, int H, uint32_t& rect0, uint32_t& rect1) {
+GS4D_HD inline void pixel_rect(float cx, float cy, float hx, float hy, float mx, float my, int W, int H, uint32_t& rect0, uint32_t& rect1) {
     float fx0 = ceilf(cx - hx - mx - 0.5f), fx1 = floorf(cx + hx + mx - 0.5f);
     float fy0 = ceilf(cy - hy - my - 0.5f), fy1 = floorf(cy + hy + my - 0.5f);
     fx0 = fmaxf(fx0, 0.0f); fy0 = fmaxf(fy0, 0.0f);

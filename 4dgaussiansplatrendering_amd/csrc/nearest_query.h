@@ -12,27 +12,27 @@ namespace gs4d_nearest {
 constexpr uint32_t K_MAX = 16;
 
 // a query the device call takes: known flags, zero reserved words, 1 <= k <= 16, and the radius of gs4d_count_neighbours
-GS4D_CQ_HD inline bool query_ok(const gs4d_nearest_query& q) {
+GS4D_HD inline bool query_ok(const gs4d_nearest_query& q) {
     const uint32_t known = (uint32_t)(GS4D_NN_SKIP_HIDDEN | GS4D_NN_SKIP_DEAD | GS4D_NN_INCLUDE_SELF);
     return (q.flags & ~known) == 0u && q.reserved[0] == 0u && q.reserved[1] == 0u && q.reserved[2] == 0u && q.reserved[3] == 0u && q.k != 0u && q.k <= K_MAX &&
            gs4d_neighbour::radius_ok(q.radius);
 }
 // the stride rule of every record call, and room for the k slots
-GS4D_CQ_HD inline bool stride_ok(size_t hit_stride, uint32_t k) {
+GS4D_HD inline bool stride_ok(size_t hit_stride, uint32_t k) {
     return hit_stride >= 16 && hit_stride <= 1024 && hit_stride % 16 == 0 && hit_stride >= 8 * (size_t)k;
 }
 
 // the squared distance of two centres: the three lines of gs4d_neighbour::near, restated — the very value it compares with r * r
-GS4D_CQ_HD inline float dist2(const float a[3], const float b[3]) {
+GS4D_HD inline float dist2(const float a[3], const float b[3]) {
     const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
     return ((dx * dx) + (dy * dy)) + (dz * dz);
 }
 
-GS4D_CQ_HD inline uint32_t bits(float v) { uint32_t u; __builtin_memcpy(&u, &v, sizeof u); return u; }
+GS4D_HD inline uint32_t bits(float v) { uint32_t u; __builtin_memcpy(&u, &v, sizeof u); return u; }
 
 // The order key of candidate j at squared distance d2 (>= +0, not a NaN: its bit pattern is in float order): by distance, then by index.  The low
 // word is the `record` and the high word the bits of the `dist2` of a gs4d_neighbour_hit.
-GS4D_CQ_HD inline uint64_t order_key(float d2, uint32_t j) { return ((uint64_t)bits(d2) << 32) | j; }
+GS4D_HD inline uint64_t order_key(float d2, uint32_t j) { return ((uint64_t)bits(d2) << 32) | j; }
 // an empty slot, {GS4D_ID_NONE, +inf}: above the key of every candidate (dist2 <= r * r is finite)
 constexpr uint64_t EMPTY = ((uint64_t)0x7F800000u << 32) | 0xFFFFFFFFull;
 
@@ -40,7 +40,7 @@ constexpr uint64_t EMPTY = ((uint64_t)0x7F800000u << 32) | 0xFFFFFFFFull;
 // worst is gone after one compare; otherwise every slot takes, from the top down, its lower neighbour (the key goes below it), the key (it goes
 // here) or nothing — every index is a constant once the loop is unrolled, so the list lives in registers.
 template <int K>
-GS4D_CQ_HD inline void insert(uint64_t (&best)[K], uint64_t key) {
+GS4D_HD inline void insert(uint64_t (&best)[K], uint64_t key) {
     if (!(key < best[K - 1])) return;
 #pragma unroll
     for (int p = K - 1; p > 0; --p) {

@@ -9,6 +9,7 @@
 // (cx, cy, a0, a1) is bit-identical to the CPU checker, which evaluates the same expressions in the same order.
 #include "gs4d_internal.h"
 #include "footprint_rect.h"
+#include "depth_key.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -234,20 +235,8 @@ __device__ __forceinline__ void place_buckets(uint32_t* cur, uint32_t nbm, uint3
 // the depth key k_keygen (sort.hip) writes for this record, as a bit pattern relative to the host-proven lower bound
 __device__ __forceinline__ uint32_t blend_key_4d(const KeySrc& ks, uint32_t i, const float4& p, const float4& s) {
     if (ks.mode == KEYSRC_INDEX) return i;
-    float key;
-    if (ks.mode == KEYSRC_REF) {
-        float ct = ks.t - p.w;                             // Scenes.h:30
-        float x = p.x + s.x * ct;                          // :31-33
-        float y = p.y + s.y * ct;
-        float z = p.z + s.z * ct;
-        float dx = x - ks.camx, dy = y - ks.camy, dz = z - ks.camz;     // :317
-        key = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);                // :318
-    } else {
-        float k = (1.0f / s.w) * (ks.t - p.w);
-        float x = p.x + k * s.x, y = p.y + k * s.y, z = p.z + k * s.z;
-        float zv = ((ks.vr0 * x + ks.vr1 * y) + ks.vr2 * z) + ks.vr3;
-        key = 1.0f / fmaxf(-zv, 1e-20f);
-    }
+    const float key = ks.mode == KEYSRC_REF ? gs4d_key::ref_inv_euclid(p.x, p.y, p.z, p.w, s.x, s.y, s.z, ks.t, ks.camx, ks.camy, ks.camz)
+                                            : gs4d_key::view_z(p.x, p.y, p.z, p.w, s.x, s.y, s.z, s.w, ks.t, ks.vr0, ks.vr1, ks.vr2, ks.vr3);
     return __float_as_uint(key) - ks.bias;
 }
 

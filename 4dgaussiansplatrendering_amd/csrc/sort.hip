@@ -13,6 +13,7 @@
 // Compiled with -ffp-contract=off: the key must be bit-identical to the CPU expression
 // 1.0f / sqrtf(dx*dx + dy*dy + dz*dz) (IEEE-correct sqrt and divide are hipcc's default).
 #include "gs4d_internal.h"
+#include "depth_key.h"
 #include <algorithm>
 #include <cstdlib>
 #include <cstdio>
@@ -39,20 +40,8 @@ __global__ __launch_bounds__(256) void k_keygen(const float4* __restrict__ pos, 
             float4 p = pos[i];
             float4 s = csig3;
             if (sig3) s = sig3[i]; else p.w = cmut;        // uniform
-            if (key_mode == GS4D_KEY_REF_INV_EUCLID) {
-                float ct = t - p.w;                        // Scenes.h:30
-                float x = p.x + s.x * ct;                  // :31-33  (sig[3].xyz, NOT divided by Sigma44)
-                float y = p.y + s.y * ct;
-                float z = p.z + s.z * ct;
-                float dx = x - camx, dy = y - camy, dz = z - camz;          // :317
-                key = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);            // :318
-            } else {
-                // extra mode: view-space depth of the shader's conditioned mean (Splat4DVertexShaderInstanced.GLSL:86)
-                float k = (1.0f / s.w) * (t - p.w);
-                float x = p.x + k * s.x, y = p.y + k * s.y, z = p.z + k * s.z;
-                float zv = ((vrow2.x * x + vrow2.y * y) + vrow2.z * z) + vrow2.w;
-                key = 1.0f / fmaxf(-zv, 1e-20f);
-            }
+            if (key_mode == GS4D_KEY_REF_INV_EUCLID) key = gs4d_key::ref_inv_euclid(p.x, p.y, p.z, p.w, s.x, s.y, s.z, t, camx, camy, camz);
+            else key = gs4d_key::view_z(p.x, p.y, p.z, p.w, s.x, s.y, s.z, s.w, t, vrow2.x, vrow2.y, vrow2.z, vrow2.w);
             keys[i] = key;
             idx[i] = i;
         }

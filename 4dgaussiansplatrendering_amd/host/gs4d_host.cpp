@@ -10,6 +10,7 @@
 //   orientation of teapot splats                     4DSplatRendering/Scenes.h:268
 //   SplatData record layout                          4DSplatRendering/Scenes.h:22-37
 // GLM 0.9.9.9 evaluation order is reproduced (float32, no contraction: build with -ffp-contract=off).
+// The record builders, the transforms and the queries that a device call evaluates too are the kernels' own headers (../csrc/*.h), compiled here.
 #include "../../include/gs4d.h"
 #include <algorithm>
 #include <cmath>
@@ -21,6 +22,8 @@
 #include <sstream>
 #include <string>
 #include <vector>
+#include "../csrc/build_record.h"
+#include "../csrc/transform_record.h"
 #include "../csrc/centre_query.h"
 #include "../csrc/measure_record.h"
 #include "../csrc/neighbour_query.h"
@@ -29,12 +32,9 @@
 
 namespace {
 
-// column-major fixed-size matrices, element (col c, row r) = a[c*N + r]
-template <int N> struct Mat { float a[N * N]; float& at(int c, int r) { return a[c * N + r]; } float at(int c, int r) const { return a[c * N + r]; } };
-using Mat3 = Mat<3>;
-using Mat4 = Mat<4>;
+using gs4d_build::M3;        // column-major, element (col c, row r) = a[c * 3 + r]
+using gs4d_build::Quat;
 struct Vec3 { float x, y, z; };
-struct Q { float w, x, y, z; };
 
 inline Vec3 sub(Vec3 a, Vec3 b) { return { a.x - b.x, a.y - b.y, a.z - b.z }; }
 inline float dot(Vec3 a, Vec3 b) { const float p0 = a.x * b.x, p1 = a.y * b.y, p2 = a.z * b.z; return p0 + p1 + p2; }
@@ -42,59 +42,22 @@ inline Vec3 cross(Vec3 a, Vec3 b) { return { a.y * b.z - b.y * a.z, a.z * b.x - 
 inline Vec3 scale(Vec3 a, float s) { return { a.x * s, a.y * s, a.z * s }; }
 inline Vec3 unit(Vec3 a) { return scale(a, 1.0f / std::sqrt(dot(a, a))); }
 
-// mat3 product, element = ((a0*b0) + (a1*b1)) + (a2*b2)
-Mat3 mm(const Mat3& A, const Mat3& B) {
-    Mat3 R;
-    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) R.at(c, r) = A.at(0, r) * B.at(c, 0) + A.at(1, r) * B.at(c, 1) + A.at(2, r) * B.at(c, 2);
-    return R;
-}
-Mat3 tr(const Mat3& A) { Mat3 R; for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) R.at(c, r) = A.at(r, c); return R; }
-Mat4 mm(const Mat4& A, const Mat4& B) {
-    Mat4 R;
-    for (int c = 0; c < 4; ++c) for (int r = 0; r < 4; ++r)
-        R.at(c, r) = ((A.at(0, r) * B.at(c, 0) + A.at(1, r) * B.at(c, 1)) + A.at(2, r) * B.at(c, 2)) + A.at(3, r) * B.at(c, 3);
-    return R;
-}
-Mat4 tr(const Mat4& A) { Mat4 R; for (int c = 0; c < 4; ++c) for (int r = 0; r < 4; ++r) R.at(c, r) = A.at(r, c); return R; }
-
-Mat3 rot_of(Q q) {   // glm::mat3_cast
-    const float xx = q.x * q.x, yy = q.y * q.y, zz = q.z * q.z, xz = q.x * q.z, xy = q.x * q.y, yz = q.y * q.z, wx = q.w * q.x, wy = q.w * q.y, wz = q.w * q.z;
-    Mat3 R;
-    R.at(0, 0) = 1.0f - 2.0f * (yy + zz); R.at(0, 1) = 2.0f * (xy + wz);        R.at(0, 2) = 2.0f * (xz - wy);
-    R.at(1, 0) = 2.0f * (xy - wz);        R.at(1, 1) = 1.0f - 2.0f * (xx + zz); R.at(1, 2) = 2.0f * (yz + wx);
-    R.at(2, 0) = 2.0f * (xz + wy);        R.at(2, 1) = 2.0f * (yz - wx);        R.at(2, 2) = 1.0f - 2.0f * (xx + yy);
-    return R;
-}
-
-Q unit(Q q) {        // glm::normalize(quat)
-    const float a = q.w * q.w, b = q.x * q.x, c = q.y * q.y, d = q.z * q.z;
-    const float len = std::sqrt((a + b) + (c + d));
-    if (len <= 0.0f) return { 1.0f, 0.0f, 0.0f, 0.0f };
-    const float inv = 1.0f / len;
-    return { q.w * inv, q.x * inv, q.y * inv, q.z * inv };
-}
-
-Q quat_of(const Mat3& m) {   // glm::quat_cast
-    const float tx = m.at(0, 0) - m.at(1, 1) - m.at(2, 2);
-    const float ty = m.at(1, 1) - m.at(0, 0) - m.at(2, 2);
-    const float tz = m.at(2, 2) - m.at(0, 0) - m.at(1, 1);
-    const float tw = m.at(0, 0) + m.at(1, 1) + m.at(2, 2);
+Quat quat_of(const M3& m) {   // glm::quat_cast
+    auto at = [&m](int c, int r) { return m.a[c * 3 + r]; };
+    const float tx = at(0, 0) - at(1, 1) - at(2, 2);
+    const float ty = at(1, 1) - at(0, 0) - at(2, 2);
+    const float tz = at(2, 2) - at(0, 0) - at(1, 1);
+    const float tw = at(0, 0) + at(1, 1) + at(2, 2);
     int which = 0; float best = tw;
     if (tx > best) { best = tx; which = 1; }
     if (ty > best) { best = ty; which = 2; }
     if (tz > best) { best = tz; which = 3; }
     const float big = std::sqrt(best + 1.0f) * 0.5f;
     const float k = 0.25f / big;
-    if (which == 0) return { big, (m.at(1, 2) - m.at(2, 1)) * k, (m.at(2, 0) - m.at(0, 2)) * k, (m.at(0, 1) - m.at(1, 0)) * k };
-    if (which == 1) return { (m.at(1, 2) - m.at(2, 1)) * k, big, (m.at(0, 1) + m.at(1, 0)) * k, (m.at(2, 0) + m.at(0, 2)) * k };
-    if (which == 2) return { (m.at(2, 0) - m.at(0, 2)) * k, (m.at(0, 1) + m.at(1, 0)) * k, big, (m.at(1, 2) + m.at(2, 1)) * k };
-    return { (m.at(0, 1) - m.at(1, 0)) * k, (m.at(2, 0) + m.at(0, 2)) * k, (m.at(1, 2) + m.at(2, 1)) * k, big };
-}
-
-Mat3 sigma3(Q q, const float s[3]) {     // R * S * S * transpose(R), left to right
-    Mat3 S; std::memset(&S, 0, sizeof S); S.at(0, 0) = s[0]; S.at(1, 1) = s[1]; S.at(2, 2) = s[2];
-    const Mat3 R = rot_of(q);
-    return mm(mm(mm(R, S), S), tr(R));
+    if (which == 0) return { big, (at(1, 2) - at(2, 1)) * k, (at(2, 0) - at(0, 2)) * k, (at(0, 1) - at(1, 0)) * k };
+    if (which == 1) return { (at(1, 2) - at(2, 1)) * k, big, (at(0, 1) + at(1, 0)) * k, (at(2, 0) + at(0, 2)) * k };
+    if (which == 2) return { (at(2, 0) - at(0, 2)) * k, (at(0, 1) + at(1, 0)) * k, big, (at(1, 2) + at(2, 1)) * k };
+    return { (at(0, 1) - at(1, 0)) * k, (at(2, 0) + at(0, 2)) * k, (at(1, 2) + at(2, 1)) * k, big };
 }
 
 } // namespace
@@ -156,9 +119,8 @@ void gs4d_host_unproject(const float view[16], const float proj[16], int width, 
 // Bounds of the depth keys (arithmetic contract): every GS4D_KEY_REF_INV_EUCLID key of a record inside the box lo[7]..hi[7] of
 // (x, y, z, mu_t, velocity = sig[3].xyz), as a uint32 bit pattern, lies in [*bias, *bias + *span].  gs4d_keygen subtracts the bias inside the
 // sort's digit extraction and sizes the sort by the span.
-// The proof is monotonicity, not a margin: the key kernel (sort.hip k_keygen, preprocess.hip blend_key_4d) evaluates
-//     ct = t - mu_t;  x = p.x + v.x * ct;  dx = x - cam.x;  key = 1 / sqrt((dx*dx + dy*dy) + dz*dz)
-// in float32, and every one of these correctly rounded operations is monotone in each argument.  The same float32 operations applied to the
+// The proof is monotonicity, not a margin: the key kernels (sort.hip k_keygen, preprocess.hip blend_key_4d) evaluate gs4d_key::ref_inv_euclid of
+// csrc/depth_key.h in float32, and every one of its correctly rounded operations is monotone in each argument.  The same float32 operations applied to the
 // ends of the box (interval arithmetic; the product takes the four corners) therefore bound every intermediate of every record, rounding
 // included, whatever the size of the coordinates — and the ends overflow exactly where a record can, which leaves a bound of 0 (x = +-inf, key
 // = 0) by itself.  Only 0 * inf makes a NaN, and only a non-finite ct makes an inf factor: then, and for non-finite arguments, nothing is claimed.
@@ -280,16 +242,13 @@ void gs4d_host_quat_look_at(const float dir[3], const float up[3], float q_wxyz[
     const Vec3 right = cross({ up[0], up[1], up[2] }, back);
     const Vec3 c0 = scale(right, 1.0f / std::sqrt(std::fmax(0.00001f, dot(right, right))));
     const Vec3 c1 = cross(back, c0);
-    Mat3 B;
-    B.at(0, 0) = c0.x; B.at(0, 1) = c0.y; B.at(0, 2) = c0.z;
-    B.at(1, 0) = c1.x; B.at(1, 1) = c1.y; B.at(1, 2) = c1.z;
-    B.at(2, 0) = back.x; B.at(2, 1) = back.y; B.at(2, 2) = back.z;
-    const Q q = unit(quat_of(B));
+    const M3 B = { { c0.x, c0.y, c0.z,  c1.x, c1.y, c1.z,  back.x, back.y, back.z } };
+    const Quat q = gs4d_build::unit(quat_of(B));
     q_wxyz[0] = q.w; q_wxyz[1] = q.x; q_wxyz[2] = q.y; q_wxyz[3] = q.z;
 }
 
 void gs4d_host_splat3d_cov(const float q_wxyz[4], const float scale3[3], float cov9[9]) {
-    const Mat3 g = sigma3({ q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3] }, scale3);
+    const M3 g = gs4d_build::sigma3({ q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3] }, scale3);
     std::memcpy(cov9, g.a, sizeof g.a);
 }
 
@@ -352,93 +311,37 @@ void gs4d_host_time_variances(size_t n, const float* lifetime, const float* fade
     for (size_t i = 0; i < n; ++i) out[i] = gs4d_host_time_variance(lifetime[i], fade[i]);
 }
 
-// Splat.h:140-158 with the temporal variance sd given
-static void splat4d_cov_tvar(const float q_wxyz[4], const float scale3[3], float sd, const float dir[3], float cov16[16]) {
-    const float td[3] = { dir[0] * sd, dir[1] * sd, dir[2] * sd };
-    const Mat3 sig = sigma3({ q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3] }, scale3);
-    const float inv = 1.0f / sd;
-    Mat4 C;
-    for (int c = 0; c < 3; ++c) {
-        for (int r = 0; r < 3; ++r) C.at(c, r) = sig.at(c, r) + (td[r] * td[c]) * inv;     // sig + (1/s) * outerProduct(td, td)
-        C.at(c, 3) = td[c];
-        C.at(3, c) = td[c];
-    }
-    C.at(3, 3) = sd;
-    std::memcpy(cov16, C.a, sizeof C.a);
-}
-
+// The builders below are calls of csrc/build_record.h, the text the kernels of gs4d_build_records compile; the time variance stays here
 void gs4d_host_splat4d_cov(const float q_wxyz[4], const float scale3[3], float lifetime, float fade, const float dir[3], float cov16[16]) {
-    splat4d_cov_tvar(q_wxyz, scale3, gs4d_host_time_variance(lifetime, fade), dir, cov16);
+    gs4d_build::cov_4d_vel(q_wxyz, scale3, dir, gs4d_host_time_variance(lifetime, fade), cov16);
 }
 
 void gs4d_host_splat4d_cov2q(const float q0_wxyz[4], const float q1_wxyz[4], const float scale4[4], float cov16[16]) {
-    const Q l = unit(Q{ q0_wxyz[0], q0_wxyz[1], q0_wxyz[2], q0_wxyz[3] });
-    const Q r = unit(Q{ q1_wxyz[0], q1_wxyz[1], q1_wxyz[2], q1_wxyz[3] });
-    const Mat4 L = { { l.w, -l.x, -l.y, -l.z,  l.x, l.w, -l.z, l.y,  l.y, l.z, l.w, -l.x,  l.z, -l.y, l.x, l.w } };
-    const Mat4 R = { { r.w, -r.x, -r.y, -r.z,  r.x, r.w, r.z, -r.y,  r.y, -r.z, r.w, r.x,  r.z, r.y, -r.x, r.w } };
-    Mat4 S; std::memset(&S, 0, sizeof S);
-    for (int i = 0; i < 4; ++i) S.at(i, i) = scale4[i];
-    const Mat4 rot = mm(L, R);
-    const Mat4 g = mm(mm(mm(rot, S), tr(S)), tr(rot));
-    std::memcpy(cov16, g.a, sizeof g.a);
+    gs4d_build::cov_4d_2q(q0_wxyz, q1_wxyz, scale4, cov16);
 }
 
 void gs4d_host_build_records_3d(size_t n, const float* pos3, const float* q_wxyz, const float* scale3, const float* rgba, float* rec) {
-    for (size_t i = 0; i < n; ++i) {
-        float* o = rec + 24 * i;
-        float g[9];
-        gs4d_host_splat3d_cov(q_wxyz + 4 * i, scale3 + 3 * i, g);
-        o[0] = pos3[3 * i]; o[1] = pos3[3 * i + 1]; o[2] = pos3[3 * i + 2]; o[3] = 0.0f;         // mu_t = 0
-        std::memcpy(o + 4, rgba + 4 * i, 16);
-        for (int c = 0; c < 3; ++c) { o[8 + 4 * c] = g[3 * c]; o[9 + 4 * c] = g[3 * c + 1]; o[10 + 4 * c] = g[3 * c + 2]; o[11 + 4 * c] = 0.0f; }
-        o[20] = 0.0f; o[21] = 0.0f; o[22] = 0.0f; o[23] = 1.0f;                                 // Sigma44 = 1
-    }
+    for (size_t i = 0; i < n; ++i) gs4d_build::record_3d(pos3 + 3 * i, q_wxyz + 4 * i, scale3 + 3 * i, rgba + 4 * i, rec + 24 * i);
 }
 
 void gs4d_host_build_records_4d(size_t n, const float* pos4, const float* q_wxyz, const float* scale3, const float* lifetime, const float* fade,
                                 const float* dir3, const float* rgba, float* rec) {
-    for (size_t i = 0; i < n; ++i) {
-        float* o = rec + 24 * i;
-        std::memcpy(o, pos4 + 4 * i, 16);
-        std::memcpy(o + 4, rgba + 4 * i, 16);
-        gs4d_host_splat4d_cov(q_wxyz + 4 * i, scale3 + 3 * i, lifetime[i], fade[i], dir3 + 3 * i, o + 8);
-    }
+    for (size_t i = 0; i < n; ++i)
+        gs4d_build::record_4d_vel(pos4 + 4 * i, q_wxyz + 4 * i, scale3 + 3 * i, dir3 + 3 * i, gs4d_host_time_variance(lifetime[i], fade[i]), rgba + 4 * i, rec + 24 * i);
 }
 
 void gs4d_host_build_records_4d_tvar(size_t n, const float* pos4, const float* q_wxyz, const float* scale3, const float* dir3, const float* tvar,
                                      const float* rgba, float* rec) {
-    for (size_t i = 0; i < n; ++i) {
-        float* o = rec + 24 * i;
-        std::memcpy(o, pos4 + 4 * i, 16);
-        std::memcpy(o + 4, rgba + 4 * i, 16);
-        splat4d_cov_tvar(q_wxyz + 4 * i, scale3 + 3 * i, tvar[i], dir3 + 3 * i, o + 8);
-    }
+    for (size_t i = 0; i < n; ++i) gs4d_build::record_4d_vel(pos4 + 4 * i, q_wxyz + 4 * i, scale3 + 3 * i, dir3 + 3 * i, tvar[i], rgba + 4 * i, rec + 24 * i);
 }
 
 void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const float* q0_wxyz, const float* q1_wxyz, const float* scale4, const float* rgba, float* rec) {
-    for (size_t i = 0; i < n; ++i) {
-        float* o = rec + 24 * i;
-        std::memcpy(o, pos4 + 4 * i, 16);
-        std::memcpy(o + 4, rgba + 4 * i, 16);
-        gs4d_host_splat4d_cov2q(q0_wxyz + 4 * i, q1_wxyz + 4 * i, scale4 + 4 * i, o + 8);
-    }
+    for (size_t i = 0; i < n; ++i) gs4d_build::record_4d_2q(pos4 + 4 * i, q0_wxyz + 4 * i, q1_wxyz + 4 * i, scale4 + 4 * i, rgba + 4 * i, rec + 24 * i);
 }
 
-// The definition of gs4d_transform_records (gs4d.h): mean L p + o, covariance (L Sigma) L^T as two full mat4 products, rgba copied
+// The definition of gs4d_transform_records (gs4d.h) is csrc/transform_record.h: mean L p + o, covariance (L Sigma) L^T as two full mat4 products, rgba copied
 void gs4d_host_transform_records(size_t n, const float* rec, const gs4d_affine4* xf, float* out) {
-    Mat4 L, Lt;
-    std::memcpy(L.a, xf->l, sizeof L.a);
-    Lt = tr(L);
-    for (size_t i = 0; i < n; ++i) {
-        const float* p = rec + 24 * i;
-        float* o = out + 24 * i;
-        for (int r = 0; r < 4; ++r) o[r] = ((((L.at(0, r) * p[0]) + (L.at(1, r) * p[1])) + (L.at(2, r) * p[2])) + (L.at(3, r) * p[3])) + xf->o[r];
-        std::memcpy(o + 4, p + 4, 16);
-        Mat4 S;
-        std::memcpy(S.a, p + 8, sizeof S.a);
-        const Mat4 g = mm(mm(L, S), Lt);
-        std::memcpy(o + 8, g.a, sizeof g.a);
-    }
+    for (size_t i = 0; i < n; ++i) gs4d_transform::record(xf->l, xf->o, rec + 24 * i, out + 24 * i);
 }
 
 // ---- what the definitions that select by, or add to, a record-statistics table share ----
@@ -646,16 +549,13 @@ void gs4d_host_nearest_neighbours(size_t n, const float* rec, const gs4d_nearest
 int gs4d_host_measure_centre(const gs4d_measure* m, float centre3[3]) {
     centre3[0] = centre3[1] = centre3[2] = 0.0f;
     if (!m || m->count == 0u) return 0;
-    for (int a = 0; a < 3; ++a) {
-        const double lo = m->lo[a], hi = m->hi[a];
-        centre3[a] = (float)(lo + (hi - lo) * ((double)m->cell_sum[a] / ((double)m->count * 1048576.0)));
-    }
+    const unsigned long long cell_sum[3] ={ m->cell_sum[0], m->cell_sum[1], m->cell_sum[2] };
+    gs4d_transform::measure_centre(m->count, m->lo, m->hi, cell_sum, centre3);
     return 1;
 }
 
 // The definition of gs4d_transform_selected (gs4d.h), in place: the selection by the rule of gs4d_edit_colours; the pivot given, or
-// gs4d_host_measure_centre of the measurement; a selected record is gs4d_host_transform_records of itself with the pivot taken off its spatial mean
-// before and put back after — both always when there is a pivot flag (this file is built with -ffp-contract=off: each is one rounding).  A call the
+// gs4d_host_measure_centre of the measurement; a selected record is gs4d_transform::record_about of itself (csrc/transform_record.h).  A call the
 // device would refuse for its xf changes nothing.
 void gs4d_host_transform_selected(size_t n, float* rec, const gs4d_record_stat* stats, const gs4d_keep_rule* rule, const gs4d_selection_xf* xf,
                                   const gs4d_measure* measure) {
@@ -668,11 +568,8 @@ void gs4d_host_transform_selected(size_t n, float* rec, const gs4d_record_stat* 
     for (size_t i = 0; i < n; ++i) {
         if (stats && !keeps(stats[i], rule)) continue;
         float* const p = rec + 24 * i;
-        float q[24], out[24];
-        std::memcpy(q, p, sizeof q);
-        if (pivot) for (int a = 0; a < 3; ++a) q[a] = p[a] - c[a];
-        gs4d_host_transform_records(1, q, &xf->xf, out);
-        if (pivot) for (int r = 0; r < 3; ++r) out[r] = out[r] + c[r];
+        float out[24];
+        gs4d_transform::record_about(xf->xf.l, xf->xf.o, pivot, c, p, out);
         std::memcpy(p, out, sizeof out);
     }
 }
@@ -697,9 +594,9 @@ void gs4d_host_frame_box(const float lo[3], const float hi[3], const float orien
 
 void gs4d_host_affine4(const float q_wxyz[4], float scale, const float translate[3], const float velocity[3], float time_scale, float time_offset,
                        gs4d_affine4* out) {
-    const Mat3 R = rot_of({ q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3] });
+    const M3 R = gs4d_build::rot_of({ q_wxyz[0], q_wxyz[1], q_wxyz[2], q_wxyz[3] });
     for (int c = 0; c < 3; ++c) {
-        for (int r = 0; r < 3; ++r) out->l[4 * c + r] = scale * R.at(c, r);
+        for (int r = 0; r < 3; ++r) out->l[4 * c + r] = scale * R.a[3 * c + r];
         out->l[4 * c + 3] = 0.0f;                              // the time row
         out->l[12 + c] = velocity[c];
         out->o[c] = translate[c];

@@ -36,10 +36,13 @@ $(DEMO): $(HOST)/scene_replay.cpp $(HOST)/gs4d_compat.h include/gs4d.h $(LIB)
 	g++ -O2 -std=c++17 -Wall -o $@ $(HOST)/scene_replay.cpp -L$(PKG) -lgs4d -Wl,-rpath,'$$ORIGIN/..'
 lib: $(LIB)
 
-$(CSRC)/sort.o: $(CSRC)/sort.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+# hd.h holds GS4D_HD / GS4D_UNROLL for every header that a CPU compiler compiles too
+HD := $(CSRC)/hd.h
+# depth_key.h is the one text of the two depth-key expressions: k_keygen (sort.hip) and blend_key_4d (preprocess.hip) compile it
+$(CSRC)/sort.o: $(CSRC)/sort.hip $(CSRC)/depth_key.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # footprint_rect.h is the one text of the pixel rectangle (tests/footprint_rect_check.cpp compiles it too)
-$(CSRC)/preprocess.o: $(CSRC)/preprocess.hip $(CSRC)/footprint_rect.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/preprocess.o: $(CSRC)/preprocess.hip $(CSRC)/footprint_rect.h $(CSRC)/depth_key.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 $(CSRC)/lines.o: $(CSRC)/lines.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
@@ -54,35 +57,37 @@ $(CSRC)/shade.o: $(CSRC)/shade.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefi
 $(CSRC)/edit.o: $(CSRC)/edit.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # centre_query.h is the one text of gs4d_count_centres' definition: the kernel and the host library compile it
-$(CSRC)/centres.o: $(CSRC)/centres.hip $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/centres.o: $(CSRC)/centres.hip $(HD) $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # measure_record.h is the one text of what a record adds to gs4d_measure_records' measurement (it takes the centre and the skips from centre_query.h)
-$(CSRC)/measure.o: $(CSRC)/measure.hip $(CSRC)/measure_record.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/measure.o: $(CSRC)/measure.hip $(HD) $(CSRC)/measure_record.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # neighbour_query.h is the one text of gs4d_count_neighbours' definition and of its cell function (it takes the centre and the skips from centre_query.h); neighbour_grid.h is the one text of the device's sorted-slot fetch and cell walk, which components.hip and nearest.hip compile too
-$(CSRC)/neighbours.o: $(CSRC)/neighbours.hip $(CSRC)/neighbour_grid.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/neighbours.o: $(CSRC)/neighbours.hip $(HD) $(CSRC)/neighbour_grid.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # gs4d_label_components walks the grid of neighbours.hip with the same `near`; component_union.h is the one text of its union-find (the host library and tests/component_union_stress.cpp compile it too)
-$(CSRC)/components.o: $(CSRC)/components.hip $(CSRC)/neighbour_grid.h $(CSRC)/component_union.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/components.o: $(CSRC)/components.hip $(HD) $(CSRC)/neighbour_grid.h $(CSRC)/component_union.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # gs4d_nearest_neighbours walks the grid of neighbours.hip too; nearest_query.h is the one text of its order key, its dist2 and its sorted insertion (the host library compiles it too)
-$(CSRC)/nearest.o: $(CSRC)/nearest.hip $(CSRC)/neighbour_grid.h $(CSRC)/nearest_query.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/nearest.o: $(CSRC)/nearest.hip $(HD) $(CSRC)/neighbour_grid.h $(CSRC)/nearest_query.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+# build_record.h is the one text of the record builders: the kernel and the host library compile it (tests/build_record_check.cpp compiles it too)
 # make BUILD_PLAIN=1: gs4d_build_records with every thread storing its own record, without the LDS staging (the measurement of DESIGN.md §4; never the shipped build)
-$(CSRC)/build.o: $(CSRC)/build.hip $(CSRC)/build_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/build.o: $(CSRC)/build.hip $(CSRC)/build_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(BUILD_PLAIN),-DGS4D_BUILD_PLAIN) -c $< -o $@
+# transform_record.h is the one text of the record transforms and of the centre of a measurement: both transform kernels and the host library compile it (tests/transform_record_check.cpp and tests/transform_selected_check.cpp compile it too)
 # make TRANSFORM_STAGED_LOAD=1: gs4d_transform_records with the input staged in LDS like the output, instead of every thread loading its own record (the measurement of DESIGN.md §4; never the shipped build)
-$(CSRC)/transform.o: $(CSRC)/transform.hip $(CSRC)/transform_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/transform.o: $(CSRC)/transform.hip $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(TRANSFORM_STAGED_LOAD),-DGS4D_TRANSFORM_STAGED_LOAD) -c $< -o $@
 # make XFSEL_PLAIN=1: gs4d_transform_selected with every selected thread storing its own record, without the LDS staging and the wave masks (the measurement of DESIGN.md §4; never the shipped build)
-$(CSRC)/transform_selected.o: $(CSRC)/transform_selected.hip $(CSRC)/transform_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/transform_selected.o: $(CSRC)/transform_selected.hip $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(XFSEL_PLAIN),-DGS4D_XFSEL_PLAIN) -c $< -o $@
 # make COUNT_IDS_PLAIN=1: gs4d_count_ids without its in-wave aggregation (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(COUNT_IDS_PLAIN),-DGS4D_COUNT_IDS_PLAIN) -c $< -o $@
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gs4d_internal.h $(CSRC)/composite_common.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
+$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/transform_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -fvisibility=hidden $(STRICT) -x c++ -c $< -o $@
 
 $(LIB): $(OBJS)

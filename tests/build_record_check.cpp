@@ -1,5 +1,6 @@
-// build_record_check — the per-record text of gs4d_build_records (csrc/build_record.h, what csrc/build.hip evaluates on the device) compiled for the
-// CPU: tests/test_build_host.py builds this with `g++ -O2 -std=c++17 -ffp-contract=off` and compares its output bit for bit with the host builders.
+// build_record_check — the per-record text of gs4d_build_records (csrc/build_record.h, what csrc/build.hip evaluates on the device and the host
+// library on the CPU) compiled stand-alone: tests/test_build_host.py builds this with `g++ -O2 -std=c++17 -ffp-contract=off` and compares its output
+// bit for bit with the host builders.  Both sides are the same text, so this checks the flags and the compilers: another compiler gives the library's bits.
 //
 //   build_record_check FORM N IN OUT
 // FORM: 0 / 1 / 2 = GS4D_PARAMS_3D / _4D_VEL / _4D_2Q.  IN: the form's parameter arrays one after another, in the order of gs4d_splat_params (pos, rot,

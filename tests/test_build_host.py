@@ -1,5 +1,5 @@
 """CPU: the host side of gs4d_build_records (include/gs4d.h) — the new batch builders against the pinned per-splat functions, and the
-kernel's per-record text (csrc/build_record.h) compiled for the CPU against the host builders, bit for bit (NaN words: NaN on both sides), on every clean and hostile case."""
+per-record text the kernel and the host builders share (csrc/build_record.h) compiled stand-alone with g++ against the host builders, bit for bit (NaN words: NaN on both sides), on every clean and hostile case."""
 import ctypes
 import os
 import shutil

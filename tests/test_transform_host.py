@@ -1,5 +1,6 @@
 """CPU: the host side of gs4d_transform_records (include/gs4d.h) — gs4d_host_transform_records against the header's text restated in
-numpy float32, the kernel's per-record text (csrc/transform_record.h) compiled for the CPU against the host function, the float64 bounds, what a
+numpy float32, the per-record text the kernel and the host function share (csrc/transform_record.h) compiled stand-alone with g++ against the host
+function, the float64 bounds, what a
 transformed record means to a draw (the conditional mean and covariance), one picture with the CPU checker, gs4d_host_affine4 and the ABI."""
 import ctypes
 import os

@@ -1,6 +1,6 @@
 """CPU: the host side of gs4d_transform_selected (include/gs4d.h) — gs4d_host_transform_selected against the header's text restated in
-numpy float32 (tests/xfsel_cases.py), the kernel's per-record text and its measurement centre (csrc/transform_record.h) compiled for the CPU against
-the host functions, what stays untouched, what a rotation about the measured pivot means to a draw, the structure and the ABI."""
+numpy float32 (tests/xfsel_cases.py), the per-record text and the measurement centre that the kernel and the host functions share
+(csrc/transform_record.h) compiled stand-alone with g++ against the host functions, what stays untouched, what a rotation about the measured pivot means to a draw, the structure and the ABI."""
 import ctypes
 import os
 import shutil

@@ -1,6 +1,7 @@
-// transform_record_check — the per-record text of gs4d_transform_records (csrc/transform_record.h, what csrc/transform.hip evaluates on the device)
-// compiled for the CPU: tests/test_transform_host.py builds this with `g++ -O2 -std=c++17 -ffp-contract=off` and compares its output with
-// gs4d_host_transform_records (NaN words: NaN on both sides).
+// transform_record_check — the per-record text of gs4d_transform_records (csrc/transform_record.h, what csrc/transform.hip evaluates on the device
+// and the host library on the CPU) compiled stand-alone: tests/test_transform_host.py builds this with `g++ -O2 -std=c++17 -ffp-contract=off` and
+// compares its output with gs4d_host_transform_records (NaN words: NaN on both sides).  Both sides are the same text, so this checks the flags and the
+// compilers: another compiler gives the library's bits.
 //
 //   transform_record_check N M IN XF OUT
 // IN: N records of 24 float32.  XF: M rows of 20 float32 (l[16], o[4]).  OUT: M * N records, instance after instance.

@@ -1,7 +1,8 @@
 // transform_selected_check — the per-record text of gs4d_transform_selected and the centre of a measurement (csrc/transform_record.h, what
-// csrc/transform_selected.hip evaluates on the device) compiled for the CPU: tests/test_xfsel_host.py builds this with
-// `g++ -O2 -std=c++17 -ffp-contract=off` (and once more with -fsanitize=address,undefined) and compares its output with
-// gs4d_host_transform_selected and gs4d_host_measure_centre (NaN words: NaN on both sides).
+// csrc/transform_selected.hip evaluates on the device and the host library on the CPU) compiled stand-alone: tests/test_xfsel_host.py builds this
+// with `g++ -O2 -std=c++17 -ffp-contract=off` (and once more with -fsanitize=address,undefined) and compares its output with
+// gs4d_host_transform_selected and gs4d_host_measure_centre (NaN words: NaN on both sides).  Both sides are the same text, so this checks the flags
+// and the compilers: another compiler gives the library's bits.
 //
 //   transform_selected_check N M IN SEL XF MEASURE OUT
 // IN: N records of 24 float32.  SEL: N bytes, non-zero: the record is selected.  XF: M rows of 96 bytes (gs4d_selection_xf: l[16], o[4], pivot[3],
