@@ -109,6 +109,7 @@ def _load():
         "gs4d_build_records": (i32, [vp, vp, sz, u32]),
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_transform_selected": (i32, [vp, u32, sz, vp, u32, vp, u32]),
+        "gs4d_slice_records": (i32, [vp, u32, sz, vp, u32, sz]),
         "gs4d_count_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_label_components": (i32, [vp, u32, sz, vp, u32, vp, u32, u32]),
         "gs4d_count_labels": (i32, [vp, u32, sz, u32, vp, u32]),
@@ -137,6 +138,7 @@ def _load():
         "gs4d_host_build_records_4d_tvar": (None, [sz, vp, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_build_records_4d_2q": (None, [sz, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_transform_records": (None, [sz, vp, vp, vp]),
+        "gs4d_host_slice_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_edit_colours": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_count_centres": (None, [sz, vp, vp, i32, i32, vp, vp]),
         "gs4d_host_measure_records": (None, [sz, vp, vp, vp, vp, vp]),
@@ -301,6 +303,27 @@ def transform_records_host(records, xf):
     for j in range(rows.shape[0]):
         _lib.gs4d_host_transform_records(rec.shape[0], _ptr(rec), _ptr(rows[j]), _ptr(out[j]))
     return out[0] if single else out
+
+
+class Slice(C.Structure):
+    """gs4d_slice (include/gs4d.h): the time, the opacity floor and the two time words of a gs4d_slice_records call; 16 bytes."""
+    _fields_ = [("t", C.c_float), ("min_opacity", C.c_float), ("mu_t_out", C.c_float), ("s44_out", C.c_float)]
+
+
+def slice_query(t, min_opacity=0.0, mu_t_out=None, s44_out=1.0):
+    """one gs4d_slice (Slice): mu_t_out=None means t — the slice is drawn at the time it was taken at"""
+    return Slice(float(t), float(min_opacity), float(t if mu_t_out is None else mu_t_out), float(s44_out))
+
+
+def slice_records_host(records, t, min_opacity=0.0, mu_t_out=None, s44_out=1.0):
+    """gs4d_host_slice_records, the definition of Context.slice_records: records [n, 24] conditioned at time t as [n, 24] — the conditional centre
+    and covariance, alpha times the time opacity, mu_t = mu_t_out (None: t), Sigma44 = s44_out and a time row and column of -0.  The query is
+    evaluated as it stands, also one the device call would refuse."""
+    rec = _f32(records).reshape(-1, 24)
+    out = np.empty_like(rec)
+    q = slice_query(t, min_opacity, mu_t_out, s44_out)
+    _lib.gs4d_host_slice_records(rec.shape[0], _ptr(rec), C.byref(q), _ptr(out))
+    return out
 
 
 # gs4d_colour_edit and gs4d_keep_rule (include/gs4d.h) as numpy records
@@ -1581,6 +1604,42 @@ class Context:
             if own:
                 self.delete(xf)
         return dst
+
+    # a frame of a clip as a 3D set: the records baked at one time
+    def slice_records(self, src, n, t, min_opacity=0.0, mu_t_out=None, s44_out=1.0, dst=None, dst_first=0):
+        """gs4d_slice_records: record dst_first + i of `dst` (a new buffer of dst_first + n records if None) <- record i < n of `src` conditioned at
+        time t: the conditional centre and covariance, alpha times the time opacity floored at min_opacity, mu_t = mu_t_out (None: t), Sigma44 =
+        s44_out, a time row and column of -0 — with the bits of slice_records_host but for word 7, which is the alpha the device's draw computes.
+        A draw of the slice at uTime == mu_t_out with uMinOpacity == min_opacity <= 1 gives the bits of a draw of src at uTime == t.  A full write
+        of dst: the next draw rebuilds its SoA shadow, as the 64-byte static layout when dst holds nothing else.  Asynchronous; returns `dst`."""
+        q = slice_query(t, min_opacity, mu_t_out, s44_out)
+        if dst is None:
+            dst = self.buffer(nbytes=max(16, (int(dst_first) + int(n)) * 96))
+        self._chk(_lib.gs4d_slice_records(self._h, int(src), int(n), C.byref(q), int(dst), int(dst_first)))
+        return dst
+
+    def freeze(self, data, n, t, min_opacity=0.0, mu_t_out=None, s44_out=1.0):
+        """The 3D set that the 4D set (data, n) is at time t, without the records that show nothing there: slice_records, then the records of
+        the slice with alpha > 0 (count_centres with skip_hidden into a zeroed table, compact_records with min_pixels=1) in their old order, in
+        exact-size new buffers.  Returns (dst, kept_index, count): the set, the uint32 index in `data` of each of its records, and the
+        COMPACT_COUNT buffer, whose `kept` is their number (read_compact_count; it is settled when the call returns).  A record of alpha 0 changes no pixel under the default blend, so a draw of (dst, kept) at uTime == mu_t_out
+        (None: t) is the draw of (data, n) at t, record i of dst being record kept_index[i] of data.  For a long clip the cheaper order is
+        compact_time_window(spans, n, t, t) first and slice_records of the survivors: the slice then reads only what can show at t."""
+        sliced = self.slice_records(data, n, t, min_opacity, mu_t_out, s44_out)
+        table = self.buffer(np.zeros(max(1, int(n)), RECORD_STAT))
+        try:
+            self.count_centres(table, n, sliced, skip_hidden=True)
+            count = self.compact_records(table, n)
+            kept, _ = self.read_compact_count(count)
+            dst, kept_index = self.buffer(nbytes=max(16, kept * 96)), self.buffer(nbytes=max(16, kept * 4))
+            self.compact_records(table, n, src=sliced, dst=dst, kept_index=kept_index, count=count)
+            got, written = self.read_compact_count(count)
+        finally:
+            self.delete(table)
+            self.delete(sliced)
+        if (got, written) != (kept, kept):
+            raise Gs4dError(f"freeze: the table changed between the two passes ({kept} kept, then {got} kept / {written} written)")
+        return dst, kept_index, count
 
     # moving a selection: the selected records under a 4D affine map about a pivot, in place (DESIGN.md §4)
     def transform_selected(self, data, n, xf, stats=None, pivot=None, measure=None, **rule):

@@ -1724,6 +1724,33 @@ int gs4d_transform_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf xf, siz
         });
 }
 
+// ---- a 4D set baked at one time ----
+int gs4d_slice_records(gs4d_ctx* c, gs4d_buf src, size_t n, const gs4d_slice* q, gs4d_buf dst, size_t dst_first) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("slice_records: ") + msg).c_str()); };
+    if (!q) return bad("q == NULL");
+    const gs4d_slice s = *q;
+    if (!std::isfinite(s.t) || !std::isfinite(s.mu_t_out)) return bad("t and mu_t_out must be finite");
+    if (std::isnan(s.min_opacity)) return bad("min_opacity is a NaN");
+    if (!(s.s44_out > 0.0f)) return bad("s44_out must be above 0");
+    if (n > 0xFFFFFFFFull || dst_first > 0xFFFFFFFFull || (uint64_t)n + dst_first > 0xFFFFFFFFull) return bad("n, dst_first or dst_first + n above 2^32 - 1");
+    const gs4d_buf names[2] = { src, dst };
+    Buffer* S = getbuf(c, src); Buffer* D = getbuf(c, dst);
+    if (!S || !D) return bad("bad buffer name");
+    if (check_record_names(c, names, 2)) return bad("src and dst must be different buffers");
+    if (S->bytes / 96 < n) return bad("src holds fewer than n records");
+    if (D->bytes / 96 < dst_first + n) return bad("dst holds fewer than dst_first + n records");
+    if (n == 0) return GS4D_OK;
+    { int rc = flush_order_if_named(c, names, 2); if (rc) return rc; }
+    return queue_on_lane(c, { S }, { D },
+        [&](Lane&) { return (int)GS4D_OK; },
+        [&](Lane& L) {
+            HIPCHK(c, launch_slice_records(L.s, S->d, n, s, (char*)D->d + dst_first * 96));
+            return (int)GS4D_OK;
+        });
+}
+
 // ---- a selection under an affine map about a pivot, in place ----
 int gs4d_transform_selected(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_selection_xf* xf, gs4d_buf stats, const gs4d_keep_rule* rule, gs4d_buf measure) {
     if (!c) return GS4D_E_INVALID;

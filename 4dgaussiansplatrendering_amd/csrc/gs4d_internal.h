@@ -505,6 +505,12 @@ hipError_t launch_build_records(hipStream_t st, int form, const BuildParams& p, 
 constexpr uint32_t TRANSFORM_TILE = 256;
 hipError_t launch_transform_records(hipStream_t st, const void* src, size_t n, const gs4d_affine4* xf, size_t m, void* dst);
 
+// ---- slice.hip ----
+// gs4d_slice_records (gs4d.h): record i of dst <- record i of the n 96-byte records of src conditioned at q.t (q validated).
+// One workgroup per SLICE_TILE records; n <= 0xFFFFFFFF; nothing else of dst is touched.
+constexpr uint32_t SLICE_TILE = 256;
+hipError_t launch_slice_records(hipStream_t st, const void* src, size_t n, const gs4d_slice& q, void* dst);
+
 // ---- transform_selected.hip ----
 // gs4d_transform_selected (gs4d.h): the selected ones of the first n 96-byte records of data <- themselves under xf (validated) — stats:
 // the table whose row i selects record i by `rule` (keep_row), or null: every record; measure: the measurement GS4D_XS_PIVOT_MEASURE takes the pivot

@@ -24,6 +24,7 @@
 #include <vector>
 #include "../csrc/build_record.h"
 #include "../csrc/transform_record.h"
+#include "../csrc/slice_record.h"
 #include "../csrc/centre_query.h"
 #include "../csrc/measure_record.h"
 #include "../csrc/neighbour_query.h"
@@ -342,6 +343,11 @@ void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const float* q0_
 // The definition of gs4d_transform_records (gs4d.h) is csrc/transform_record.h: mean L p + o, covariance (L Sigma) L^T as two full mat4 products, rgba copied
 void gs4d_host_transform_records(size_t n, const float* rec, const gs4d_affine4* xf, float* out) {
     for (size_t i = 0; i < n; ++i) gs4d_transform::record(xf->l, xf->o, rec + 24 * i, out + 24 * i);
+}
+
+// The definition of gs4d_slice_records (gs4d.h) is csrc/slice_record.h: the draw's time conditioning at q->t, baked into the record
+void gs4d_host_slice_records(size_t n, const float* rec, const gs4d_slice* q, float* out) {
+    for (size_t i = 0; i < n; ++i) gs4d_slicing::record(q->t, q->min_opacity, q->mu_t_out, q->s44_out, rec + 24 * i, out + 24 * i);
 }
 
 // ---- what the definitions that select by, or add to, a record-statistics table share ----

@@ -21,7 +21,7 @@ $(FLAGSTAMP):
 	rm -f $(CSRC)/.flags.*
 	touch $@
 
-OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
+OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
 
 .PHONY: all lib oracle ref refscene refdraw refgl clean demo sweep
 all: lib oracle demo sweep
@@ -82,12 +82,15 @@ $(CSRC)/transform.o: $(CSRC)/transform.hip $(CSRC)/transform_record.h $(HD) $(CS
 # make XFSEL_PLAIN=1: gs4d_transform_selected with every selected thread storing its own record, without the LDS staging and the wave masks (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/transform_selected.o: $(CSRC)/transform_selected.hip $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(XFSEL_PLAIN),-DGS4D_XFSEL_PLAIN) -c $< -o $@
+# slice_record.h is the one text of gs4d_slice_records' definition: the kernel and the host library compile it; slice.o is built with the flags of preprocess.o, so its expf is the draw's
+$(CSRC)/slice.o: $(CSRC)/slice.hip $(CSRC)/slice_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # make COUNT_IDS_PLAIN=1: gs4d_count_ids without its in-wave aggregation (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(COUNT_IDS_PLAIN),-DGS4D_COUNT_IDS_PLAIN) -c $< -o $@
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gs4d_internal.h $(CSRC)/composite_common.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/transform_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
+$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/transform_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -fvisibility=hidden $(STRICT) -x c++ -c $< -o $@
 
 $(LIB): $(OBJS)

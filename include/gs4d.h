@@ -564,7 +564,8 @@ GS4D_API int gs4d_build_records(gs4d_ctx* ctx, const gs4d_splat_params* params, 
  *                conditioning has, as the reference does: the key's centre is the conditional centre only where Sigma44 == 1.  A time scale a gives
  *                both factors an a, so the key's displacement takes a^2 where the conditional centre's takes none: every splat of a retimed set is
  *                drawn where it belongs, but GS4D_MODE_4D_SORTED blends the set in the order of ITS keys, which for |a| != 1 is not the order of
- *                the source's.  Rotation, translation and a time offset keep the order.
+ *                the source's.  Rotation, translation and a time offset keep the order.  A set baked at the draw's time (gs4d_slice_records,
+ *                below) has no such gap: its stored centre is the conditional centre, so its reference key is the key of the centre that is drawn.
  *     statistics, spatial order and kept_index tables are indexed by record: instance j's record i is record dst_first + j * n + i.
  *
  * GS4D_E_INVALID, with nothing queued and nothing written: n, m, dst_first or dst_first + m * n above 0xFFFFFFFF; a name that is not a live buffer;
@@ -584,6 +585,67 @@ typedef struct gs4d_affine4 {
     float o[4];         /* the offset (x, y, z, t)                                        */
 } gs4d_affine4;         /* 80 bytes */
 GS4D_API int gs4d_transform_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf dst, size_t dst_first);
+
+/* ---- a frame of a clip as a 3D set: the records baked at one time (no reference counterpart) ----
+ * The draws condition a 4D record at uTime — the time opacity, the conditional centre, the conditional 3x3 covariance — inside the projection
+ * kernel, every frame.  gs4d_slice_records does that once and writes the result as records: the 3D set that the 4D set IS at time q->t, to be drawn
+ * while playback is paused, edited as a static object or exported as one frame.  The call writes record dst_first + i of dst from record i < n of
+ * src; it writes no other byte of dst and no byte of src.
+ *
+ * The definition (gs4d_host_slice_records is this text).  All arithmetic is float32, round to nearest, no contraction, full products; the order of
+ * the operations is that of the draw's conditioning.  With p = floats 0..3 of the record, S[c][r] = float 8 + 4c + r and maxf(a, b) = a >= b ? a : b:
+ *     s44 = S[3][3];  dt = t - p[3];  inv = 1.0f / s44
+ *     ot  = maxf(expf(((-0.5f * dt) * inv) * dt), min_opacity)
+ *     k   = inv * dt
+ *     a[r]  = S[r][3]      (floats 11, 15, 19: the time COLUMN, as the draw reads it)
+ *     tv[c] = inv * S[3][c]      (floats 20, 21, 22: the time row)
+ *     floats 0..2       = p[r] + (k * a[r])
+ *     float 3           = mu_t_out
+ *     floats 4..6       copied;  float 7 = ot * (float 7)
+ *     float 8 + 4c + r  = S[c][r] - (a[r] * tv[c])        c, r = 0..2
+ *     floats 11, 15, 19 (time column) and 20, 21, 22 (time row) = -0.0f;  float 23 = s44_out
+ * The zeros are NEGATIVE on purpose: at uTime == mu_t_out the draw of the slice computes dt = +0 and k = +0; k * (-0) = -0 and x + (-0) = x for
+ * every x, -0 included; (-0) * (inv * (-0)) = +0 and x - (+0) = x; expf(-0) = 1 and 1 * alpha = alpha.  With +0 in those words a coordinate or
+ * covariance element that is -0 would come back as +0.
+ *
+ * The guarantee.  With uTime == q->mu_t_out and uMinOpacity <= 1 and equal to q->min_opacity, a draw of the slice gives the bits of a draw of the
+ * source at uTime == q->t — the colour image, the aux planes, the ID planes and the record statistics, for every blend function under which the
+ * draw has them (no record is dropped: record i of the slice is record i of the source, and the projected records of the two draws are the same
+ * bits) — in GS4D_MODE_4D_DIRECT, or in GS4D_MODE_4D_SORTED with the same index buffer.
+ * The two sets' OWN keys (gs4d_keygen) are bit-equal under GS4D_KEY_VIEW_Z for records whose Sigma is bit-symmetric in its time row and column
+ * (the key reads the row, the draw the column), and under GS4D_KEY_REF_INV_EUCLID additionally only where Sigma44 is exactly 1: the reference's key
+ * does not divide by Sigma44 (the note at gs4d_transform_records).  Elsewhere the slice's reference key is the key of the centre that is DRAWN —
+ * in a slice the stored centre is the conditional centre, so both keys are right.
+ *
+ * Device precision.  Words 0..6 and 8..23 have the bits of the host function, except that a word that is a NaN on both sides may differ in sign and
+ * payload.  Word 7 goes through the device's expf: it is bit-equal to the alpha the device's own draw computes for the source record, which is what
+ * the guarantee needs, and within 5e-6 relative of the host's (the project's bar for that expression).
+ *
+ * What the slice buys.  Its eight time-related words are the same in every record, so the SoA shadow of a buffer that holds only slice records
+ * (of one mu_t_out and s44_out) is the 64-byte static-3D layout, where the 4D source reads 96 bytes per record and frame; and its records with
+ * alpha 0 are dead at every time, so gs4d_count_centres with GS4D_CQ_SKIP_HIDDEN + gs4d_compact_records remove them for good.  For a long clip
+ * gs4d_compact_time_window(spans, n, t, t) first and a slice of the survivors is the cheaper order.  Away from uTime == mu_t_out a slice fades like any static
+ * record of that Sigma44; with s44_out == +inf it does not (1 / s44_out is 0: the opacity factor is expf(-0) = 1 and the centre stays where it is,
+ * up to the sign of a zero coordinate, at every finite uTime).  Time spans are those of the slice's own time words.  The SH table is not touched
+ * (shade the source at t first).
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: q == NULL; t or mu_t_out not finite; min_opacity a NaN; s44_out a NaN or <= 0 (+inf is
+ * allowed); n, dst_first or their sum above 0xFFFFFFFF; a name that is not a live buffer; src == dst; src smaller than 96 n bytes; dst holding fewer
+ * than dst_first + n records.  n == 0 with otherwise valid arguments is a no-op.  Records are data: hostile ones give what the definition gives.
+ *
+ * Ordering, exactly that of gs4d_transform_records: a queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first; draws
+ * that may still have to be run again from dst are settled; the kernel is queued on the current frame lane, the call returns at once and starts no
+ * new frame; src is a buffer the call reads, dst one it writes (it waits, on the device, for the lanes whose draws or key generation still read dst
+ * or its shadow; later calls, other lanes and the host order themselves behind it).  gs4d_buffer_invalidate hand-offs of both buffers are honoured.
+ * It counts as a full write of dst, even with dst_first > 0: the buffer's version moves, what a sort index was sorted by is forgotten, and the next
+ * draw or gs4d_keygen rebuilds the SoA shadow once (gs4d_debug_shadow_builds goes up by one). */
+typedef struct gs4d_slice {
+    float t;            /* the time the source is conditioned at; finite                                   */
+    float min_opacity;  /* the draw's uMinOpacity: the floor of the time opacity; not a NaN                */
+    float mu_t_out;     /* float 3 of every slice record: the uTime the slice is to be drawn at; finite    */
+    float s44_out;      /* float 23 of every slice record; > 0, +inf allowed                               */
+} gs4d_slice;           /* 16 bytes */
+GS4D_API int gs4d_slice_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, const gs4d_slice* q, gs4d_buf dst, size_t dst_first);
 
 /* ---- colour edits by a selection: recolour, hide or restore selected records (no reference counterpart) ----
  * What a selection is shown with.  The selection chain ends in a statistics table — gs4d_count_ids for what a region of the ID planes shows,
@@ -1138,6 +1200,9 @@ GS4D_API void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const f
 /* The definition of gs4d_transform_records for one transform: out24 record i = records24 record i under *xf, i < n (the text above the declaration
  * of gs4d_transform_records).  out24 must not overlap records24. */
 GS4D_API void gs4d_host_transform_records(size_t n, const float* records24, const gs4d_affine4* xf, float* out24);
+/* The definition of gs4d_slice_records: out24 record i = records24 record i conditioned at q->t, i < n (the text above the declaration of
+ * gs4d_slice_records; expf is the C library's).  out24 must not overlap records24.  A query the device call would refuse is evaluated as it stands. */
+GS4D_API void gs4d_host_slice_records(size_t n, const float* records24, const gs4d_slice* q, float* out24);
 /* The definition of gs4d_edit_colours, in place on the n records of records24 (the text above its declaration): stats == NULL selects every record
  * (rule is then ignored), else rule is not NULL; from24 is read by GS4D_EDIT_COPY only and must not overlap records24.  An edit the device call
  * would refuse (an unknown op, channels outside 1 .. 15) edits nothing. */
