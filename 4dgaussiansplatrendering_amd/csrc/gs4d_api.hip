@@ -16,6 +16,7 @@
 // on the device, never on the host.  Only read-back/finish calls block, plus the validation of a draw's tile-list capacity, which
 // is deferred to the next call that could observe the draw (see resolve_pending).
 #include "gs4d_internal.h"
+#include "operands.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -859,35 +860,28 @@ static hipError_t create_lane_streams(gs4d_ctx* c) {
     return hipSuccess;
 }
 
-// ---- what the record-set calls share (compaction, time windows, spatial order, gather) ----
+// ---- what the calls on record sets and tables share: a call makes its own scalar and query checks, declares its buffer arguments once (operands.h),
+// ---- has them checked (check_operands), decides what n == 0 means, and queues its kernels from the same list (queue_operands) ----
 // the stride rule of every such call
 bool record_stride_ok(size_t stride) { return stride >= 16 && stride <= 1024 && stride % 16 == 0; }
-// names[i] != 0 must be a live buffer that none of names[0 .. i) names too.  0: they are; 1: a bad name; 2: two names of one buffer
-int check_record_names(gs4d_ctx* c, const gs4d_buf* names, int count) {
-    for (int i = 0; i < count; ++i) {
-        if (names[i] == 0) continue;
-        if (!getbuf(c, names[i])) return 1;
-        for (int j = 0; j < i; ++j) if (names[j] == names[i]) return 2;
-    }
-    return 0;
-}
-// a queued key generation / sort that names one of the buffers runs first
-int flush_order_if_named(gs4d_ctx* c, const gs4d_buf* names, int count) {
-    if (c->po.keygen) for (int i = 0; i < count; ++i) if (names[i] != 0 && (names[i] == c->po.data || names[i] == c->po.keys || names[i] == c->po.idx)) return flush_order(c);
+// "<fn>: <msg>" as the refusal of a call: GS4D_E_INVALID
+int refuse(gs4d_ctx* c, const char* fn, const std::string& msg) { return fail(c, GS4D_E_INVALID, (std::string(fn) + ": " + msg).c_str()); }
+// The buffer arguments of a call, each declared once, with the buffers check_operands has found for them (null: not given)
+struct Operands {
+    static constexpr int MAX = 8;
+    Operand op[MAX]; Buffer* buf[MAX] = {}; int count = 0; bool fits;      // (a list longer than MAX is refused by check_operands, never cut short)
+    Operands(std::initializer_list<Operand> list) : fits(list.size() <= (size_t)MAX) { for (const Operand& o : list) if (count < MAX) op[count++] = o; }
+    // the buffer of the argument `name`, and its storage (null: not given)
+    Buffer* buffer(gs4d_buf name) const { for (int i = 0; i < count; ++i) if (name != 0 && op[i].name == name) return buf[i]; return nullptr; }
+    void* ptr(gs4d_buf name) const { Buffer* B = buffer(name); return B ? B->d : nullptr; }
+};
+// The check of operands.h over the context's buffers; finds the buffers.  A fault: GS4D_E_INVALID with "<fn>: <operand> ...".
+int check_operands(gs4d_ctx* c, const char* fn, Operands& ops) {
+    if (!ops.fits) return refuse(c, fn, "more operands than Operands::MAX");
+    const OperandVerdict v = check_operand_list(ops.op, ops.count, [&](uint32_t name) { Buffer* B = getbuf(c, name); return BufferFacts{ B != nullptr, B ? B->bytes : 0 }; });
+    if (v.fault != OperandFault::None) return fail(c, GS4D_E_INVALID, operand_message(fn, ops.op, v).c_str());
+    for (int i = 0; i < ops.count; ++i) ops.buf[i] = getbuf(c, ops.op[i].name);
     return GS4D_OK;
-}
-// Kernels on the current frame lane that read the buffers `in` and overwrite the buffers `out` (null entries: not given).  prepare(lane): everything
-// that can fail without a kernel — it comes before any buffer's state is touched; launch(lane) queues the kernels.
-template <class Prepare, class Launch>
-int queue_on_lane(gs4d_ctx* c, std::initializer_list<Buffer*> in, std::initializer_list<Buffer*> out, Prepare prepare, Launch launch) {
-    // a draw that is still unvalidated may have to be run again from the buffers it was given: none of those is overwritten before that is settled
-    for (Buffer* B : out) if (B && B->touch > c->synced) { int rc = resolve_pending(c); if (rc) return rc; break; }
-    Lane& L = lane(c);
-    { int rc = prepare(L); if (rc) return rc; }
-    const unsigned me = 1u << c->cur;
-    for (Buffer* B : in) if (B) { int rc = lane_access(c, *B, false); if (rc) return rc; B->tail_mask |= me; }
-    for (Buffer* B : out) if (B) { int rc = lane_access(c, *B, true); if (rc) return rc; B->version++; B->prov_valid = false; }
-    return launch(L);
 }
 
 // A statistics table as a host read takes it: behind every draw issued so far, on every lane, re-runs included (settling draws does not move the
@@ -911,25 +905,31 @@ int scan_end(gs4d_ctx* c, Lane& L, Buffer& S) {
     S.scan_wait = ((1u << c->nlanes) - 1u) & ~(1u << c->cur);
     return GS4D_OK;
 }
-// queue_on_lane with those three steps around it for `scanned`: the tables among `in` that draws may still ADD to (null entries: not given) —
-// reserve behind prepare, begin before launch, end behind it
+// Kernels on the current frame lane over checked operands, each treated as its roles say (operands.h; an operand that is not given has none).
+// prepare(lane): everything that can fail without a kernel — it comes before any buffer's state is touched; launch(lane) queues the kernels.
 template <class Prepare, class Launch>
-int queue_scan_on_lane(gs4d_ctx* c, std::initializer_list<Buffer*> in, std::initializer_list<Buffer*> out, std::initializer_list<Buffer*> scanned,
-                       Prepare prepare, Launch launch) {
-    return queue_on_lane(c, in, out,
-        [&](Lane& L) {
-            int rc = prepare(L);
-            for (Buffer* S : scanned) if (!rc && S) rc = scan_reserve(c, *S);
-            return rc;
-        },
-        [&](Lane& L) {
-            int rc = GS4D_OK;
-            for (Buffer* S : scanned) if (!rc && S) rc = scan_begin(c, L, *S);
-            if (!rc) rc = launch(L);
-            for (Buffer* S : scanned) if (!rc && S) rc = scan_end(c, L, *S);
-            return rc;
-        });
+int queue_operands(gs4d_ctx* c, const Operands& ops, Prepare prepare, Launch launch) {
+    auto each = [&](unsigned role, auto step) { int rc = GS4D_OK; for (int i = 0; i < ops.count && !rc; ++i) if (ops.buf[i] && (ops.op[i].roles & role)) rc = step(*ops.buf[i]); return rc; };
+    // a queued key generation / sort that names one of the buffers runs first
+    if (c->po.keygen) for (int i = 0; i < ops.count; ++i) if (ops.buf[i] && (ops.op[i].name == c->po.data || ops.op[i].name == c->po.keys || ops.op[i].name == c->po.idx)) { int rc = flush_order(c); if (rc) return rc; break; }
+    { int rc = each(OP_SETTLE, [&](Buffer& B) { return settle_stats_table(c, B); }); if (rc) return rc; }
+    // a draw that is still unvalidated may have to be run again from the buffers it was given: none of those is overwritten before that is settled
+    bool touched = false;
+    (void)each(OP_WRITE, [&](Buffer& B) { touched |= B.touch > c->synced; return (int)GS4D_OK; });
+    if (touched) { int rc = resolve_pending(c); if (rc) return rc; }
+    Lane& L = lane(c);
+    { int rc = prepare(L); if (rc) return rc; }
+    { int rc = each(OP_SCAN, [&](Buffer& B) { return scan_reserve(c, B); }); if (rc) return rc; }
+    const unsigned me = 1u << c->cur;
+    { int rc = each(OP_READ, [&](Buffer& B) { int r = lane_access(c, B, false); if (!r) B.tail_mask |= me; return r; }); if (rc) return rc; }
+    { int rc = each(OP_WRITE, [&](Buffer& B) { int r = lane_access(c, B, true); if (!r) { B.version++; B.prov_valid = false; } return r; }); if (rc) return rc; }
+    { int rc = each(OP_SCAN, [&](Buffer& B) { return scan_begin(c, L, B); }); if (rc) return rc; }
+    { int rc = launch(L); if (rc) return rc; }
+    return each(OP_SCAN, [&](Buffer& B) { return scan_end(c, L, B); });
 }
+// ... for a call that has nothing to prepare
+template <class Launch>
+int queue_operands(gs4d_ctx* c, const Operands& ops, Launch launch) { return queue_operands(c, ops, [](Lane&) { return (int)GS4D_OK; }, launch); }
 
 // gs4d_keep_rule as the kernels take it; null — a call whose table is optional was given none — is the rule no kernel reads.  False: an unknown flag
 // or a non-zero reserved field.
@@ -947,83 +947,69 @@ bool keep_rule_of(const gs4d_keep_rule* rule, KeepRule& out) {
 template <class Launch>
 int compact_by_table(gs4d_ctx* c, const char* fn, const char* what, bool stats_table, gs4d_buf table, size_t row_bytes, size_t n,
                             gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count, Launch launch) {
-    auto bad = [&](const std::string& msg) { return fail(c, GS4D_E_INVALID, (std::string(fn) + ": " + msg).c_str()); };
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    if (!record_stride_ok(stride)) return bad("stride must be a multiple of 16 from 16 to 1024");
-    if (dst != 0 && src == 0) return bad("dst given without src");
-    const gs4d_buf names[5] = { table, src, dst, kept_index, count };
-    if (const int wrong = check_record_names(c, names, 5)) return bad(wrong == 1 ? "bad buffer name" : std::string(what) + ", src, dst, kept_index and count must be different buffers");
-    Buffer* S = getbuf(c, table); Buffer* C = getbuf(c, count);
-    Buffer* R = dst ? getbuf(c, src) : nullptr;                 // (the records are read only when there is somewhere to put them)
-    Buffer* D = getbuf(c, dst); Buffer* X = getbuf(c, kept_index);
-    if (!S || !C) return bad(std::string(what) + " and count must name buffers");
-    if (S->bytes / row_bytes < n) return bad(std::string("the ") + what + " buffer holds fewer than n rows");
-    if (src != 0 && getbuf(c, src)->bytes / stride < n) return bad("src holds fewer than n records");
-    if (C->bytes < sizeof(gs4d_compact_count)) return bad("count holds fewer than 8 bytes");
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    if (!record_stride_ok(stride)) return refuse(c, fn, "stride must be a multiple of 16 from 16 to 1024");
+    if (dst != 0 && src == 0) return refuse(c, fn, "dst given without src");
+    // src holds its records whenever it is given, and is read only when there is somewhere to put them; dst and kept_index hold what they hold (cap)
+    Operands ops{ { what, table, false, row_bytes, n, OP_READ | OP_SETTLE | (stats_table ? OP_SCAN : 0u) },
+                  { "src", src, true, stride, n, dst ? OP_READ : 0u },
+                  { "dst", dst, true, stride, 0, OP_WRITE },
+                  { "kept_index", kept_index, true, 4, 0, OP_WRITE },
+                  { "count", count, false, 1, sizeof(gs4d_compact_count), OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     // slots the outputs hold: no slot >= cap is ever written
     uint32_t cap = 0xFFFFFFFFu;
-    if (D) cap = (uint32_t)std::min<size_t>(cap, D->bytes / stride);
-    if (X) cap = (uint32_t)std::min<size_t>(cap, X->bytes / 4);
-    { int rc = flush_order_if_named(c, names, 5); if (rc) return rc; }
-    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    return queue_scan_on_lane(c, { S, R }, { D, X, C }, { stats_table ? S : nullptr },
+    if (Buffer* D = ops.buffer(dst)) cap = (uint32_t)std::min<size_t>(cap, D->bytes / stride);
+    if (Buffer* X = ops.buffer(kept_index)) cap = (uint32_t)std::min<size_t>(cap, X->bytes / 4);
+    return queue_operands(c, ops,
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.compact_counts, L.compact_cap, std::max<size_t>(1, compact_tiles(n))));
             return (int)GS4D_OK;
         },
         [&](Lane& L) {
-            HIPCHK(c, launch(L, S->d, R ? R->d : nullptr, D ? D->d : nullptr, X ? (uint32_t*)X->d : nullptr, cap, (gs4d_compact_count*)C->d));
+            HIPCHK(c, launch(L, ops.ptr(table), dst ? ops.ptr(src) : nullptr, ops.ptr(dst), (uint32_t*)ops.ptr(kept_index), cap, (gs4d_compact_count*)ops.ptr(count)));
             return (int)GS4D_OK;
         });
 }
 
 // What gs4d_count_neighbours, gs4d_label_components and gs4d_nearest_neighbours share: everything but the call's own checks, its names and its
-// launch.  The checks are decided in this order, the call's own among them at the two places they have always had.
+// launch.  The checks are decided in this order: the query's, the call's own two among them, then the buffers'.
 // The common fields of the three 32-byte queries — flags against the call's own known mask — with the verdict of the call's own check of the
 // query (cap; k): its message, or null
 struct GridQuery { float radius; uint32_t flags, known; const uint32_t* reserved; const char* query_fault; };
-// The outputs behind data: `first` is required, a row of first_row bytes per record (first_is_table: it is the statistics table itself, settled
-// like one), `stats` is the optional table behind it (0: none, or none to give).  output_fault: the verdict of the call's own check of its
-// outputs (hit_stride), decided once data and first are found live: its message, or null — first_row is not divided by before that.
-struct GridOutputs { gs4d_buf first; size_t first_row; bool first_is_table; gs4d_buf stats; const char* live, * output_fault, * different, * first_fewer; };
+// The outputs behind data: `first` (first_arg: what the call calls it) is required, a row of first_row bytes per record (first_is_table: it is the
+// statistics table itself, settled like one), `stats` is the optional table behind it (0: none, or none to give).  output_fault: the verdict of the
+// call's own check of its outputs (hit_stride): its message, or null — first_row is not divided by before that.
+struct GridOutputs { const char* first_arg; gs4d_buf first; size_t first_row; bool first_is_table; gs4d_buf stats; const char* output_fault; };
 // launch(lane, records, source rows or null, rule, first, stats rows or null) queues the kernels on the lane's neighbour scratch and pair_sort.
 template <class Launch>
 int grid_query(gs4d_ctx* c, const char* fn, const GridQuery& q, size_t n, gs4d_buf data, gs4d_buf source, const gs4d_keep_rule* rule, const GridOutputs& o,
                Launch launch) {
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string(fn) + ": " + msg).c_str()); };
-    if ((q.flags & ~q.known) != 0u) return bad("unknown flag");
-    if (q.reserved[0] != 0u || q.reserved[1] != 0u || q.reserved[2] != 0u || q.reserved[3] != 0u) return bad("non-zero reserved field in the query");
-    if (q.query_fault) return bad(q.query_fault);
-    if (!neighbour_radius_ok(q.radius)) return bad("the radius must be finite with 2^-63 <= radius < 2^64");
-    if (n >= 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
-    if ((source != 0) != (rule != nullptr)) return bad("source and rule are given together or not at all");
+    if ((q.flags & ~q.known) != 0u) return refuse(c, fn, "unknown flag");
+    if (q.reserved[0] != 0u || q.reserved[1] != 0u || q.reserved[2] != 0u || q.reserved[3] != 0u) return refuse(c, fn, "non-zero reserved field in the query");
+    if (q.query_fault) return refuse(c, fn, q.query_fault);
+    if (!neighbour_radius_ok(q.radius)) return refuse(c, fn, "the radius must be finite with 2^-63 <= radius < 2^64");
+    if (n >= 0xFFFFFFFFull) return refuse(c, fn, "the sort takes 2^32 - 2 records at most");
+    if ((source != 0) != (rule != nullptr)) return refuse(c, fn, "source and rule are given together or not at all");
     KeepRule k;
-    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
-    const gs4d_buf names[4] = { data, o.first, o.stats, source };
-    Buffer* D = getbuf(c, data); Buffer* F = getbuf(c, o.first);
-    if (!D || !F) return bad(o.live);
-    if (o.output_fault) return bad(o.output_fault);
-    if (const int wrong = check_record_names(c, names, 4)) return bad(wrong == 1 ? "bad buffer name" : o.different);
-    Buffer* S = getbuf(c, o.stats); Buffer* Q = getbuf(c, source);
-    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
-    if (F->bytes / o.first_row < n) return bad(o.first_fewer);
-    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
-    if (Q && Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the source buffer holds fewer than n rows");
-    if (n == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 4); if (rc) return rc; }
-    if (o.first_is_table) { int rc = settle_stats_table(c, *F); if (rc) return rc; }
-    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    if (Q) { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
+    if (!keep_rule_of(rule, k)) return refuse(c, fn, "unknown flag or non-zero reserved field in the rule");
+    if (o.output_fault) return refuse(c, fn, o.output_fault);
     // data and source are read (the 96-byte records, never a shadow: a reader leaves `version` alone; source as gs4d_edit_colours reads its table).
-    // The outputs are "out" of queue_on_lane: first is written, a statistics table is a read-modify-write the lane has the table to itself for, as in
-    // gs4d_count_centres.
-    return queue_scan_on_lane(c, { D, Q }, { F, S }, { Q },
+    // first is written; a statistics table among the outputs is a read-modify-write the lane has the table to itself for, as in gs4d_count_centres.
+    // The tables are settled in this order: first, stats, source.
+    Operands ops{ { "data", data, false, 96, n, OP_READ },
+                  { o.first_arg, o.first, false, o.first_row, n, OP_WRITE | (o.first_is_table ? OP_SETTLE : 0u) },
+                  { "stats", o.stats, true, sizeof(gs4d_record_stat), n, OP_WRITE | OP_SETTLE },
+                  { "source", source, true, sizeof(gs4d_record_stat), n, OP_READ | OP_SETTLE | OP_SCAN } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (n == 0) return GS4D_OK;
+    return queue_operands(c, ops,
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, neighbour_scratch_words(n)));
             HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));      // (the tile sort's scratch, as gs4d_spatial_order: a histogram a queued keygen has left in depth_sort stays where it is)
             return (int)GS4D_OK;
         },
-        [&](Lane& L) { return launch(L, D->d, Q ? (const gs4d_record_stat*)Q->d : nullptr, k, F->d, S ? (gs4d_record_stat*)S->d : nullptr); });
+        [&](Lane& L) { return launch(L, ops.ptr(data), (const gs4d_record_stat*)ops.ptr(source), k, ops.ptr(o.first), (gs4d_record_stat*)ops.ptr(o.stats)); });
 }
 
 } // namespace
@@ -1473,26 +1459,21 @@ int gs4d_compact_records(gs4d_ctx* c, gs4d_buf stats, size_t n, const gs4d_keep_
 int gs4d_stat_cut(gs4d_ctx* c, gs4d_buf stats, size_t n, int field, size_t budget, gs4d_buf out) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("stat_cut: ") + msg).c_str()); };
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 rows");
-    if (budget == 0) return bad("budget == 0");
-    if (field != GS4D_STAT_PIXELS && field != GS4D_STAT_WMAX && field != GS4D_STAT_WSUM) return bad("unknown field");
-    const gs4d_buf names[2] = { stats, out };
-    Buffer* S = getbuf(c, stats); Buffer* O = getbuf(c, out);
-    if (!S || !O) return bad("bad buffer name");
-    if (check_record_names(c, names, 2)) return bad("stats and out must be different buffers");
-    if (S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
-    if (O->bytes < sizeof(gs4d_cut)) return bad("out holds fewer than 16 bytes");
+    const char* const fn = "stat_cut";
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 rows");
+    if (budget == 0) return refuse(c, fn, "budget == 0");
+    if (field != GS4D_STAT_PIXELS && field != GS4D_STAT_WMAX && field != GS4D_STAT_WSUM) return refuse(c, fn, "unknown field");
+    Operands ops{ { "stats", stats, false, sizeof(gs4d_record_stat), n, OP_READ | OP_SETTLE | OP_SCAN },
+                  { "out", out, false, 1, sizeof(gs4d_cut), OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     const uint32_t k = (uint32_t)std::min(budget, n);
-    { int rc = flush_order_if_named(c, names, 2); if (rc) return rc; }
-    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    return queue_scan_on_lane(c, { S }, { O }, { S },
+    return queue_operands(c, ops,
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.cut_scratch, L.cut_cap, cut_scratch_words(n)));
             return (int)GS4D_OK;
         },
         [&](Lane& L) {
-            HIPCHK(c, launch_stat_cut(L.s, (const gs4d_record_stat*)S->d, n, field, k, L.cut_scratch, (gs4d_cut*)O->d));
+            HIPCHK(c, launch_stat_cut(L.s, (const gs4d_record_stat*)ops.ptr(stats), n, field, k, L.cut_scratch, (gs4d_cut*)ops.ptr(out)));
             return (int)GS4D_OK;
         });
 }
@@ -1501,21 +1482,15 @@ int gs4d_stat_cut(gs4d_ctx* c, gs4d_buf stats, size_t n, int field, size_t budge
 int gs4d_record_time_spans(gs4d_ctx* c, gs4d_buf data, size_t n, float min_opacity, gs4d_buf spans) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    if (n > 0xFFFFFFFFull) return fail(c, GS4D_E_INVALID, "record_time_spans: more than 2^32 - 1 records");
-    Buffer* D = getbuf(c, data); Buffer* S = getbuf(c, spans);
-    if (!D || !S) return fail(c, GS4D_E_INVALID, "record_time_spans: bad buffer name");
-    if (D == S) return fail(c, GS4D_E_INVALID, "record_time_spans: data and spans must be different buffers");
-    if (D->bytes / 96 < n || S->bytes / sizeof(gs4d_time_span) < n) return fail(c, GS4D_E_INVALID, "record_time_spans: buffers smaller than n elements");
+    const char* const fn = "record_time_spans";
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    Operands ops{ { "data", data, false, 96, n, OP_READ }, { "spans", spans, false, sizeof(gs4d_time_span), n, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (n == 0) return GS4D_OK;
-    // a queued key generation / sort that names one of the buffers runs first
-    if (c->po.keygen) for (gs4d_buf b : { data, spans }) if (b == c->po.data || b == c->po.keys || b == c->po.idx) { int rc = flush_order(c); if (rc) return rc; break; }
-    // a draw that is still unvalidated may have to be run again from the buffers it was given: spans is not overwritten before that is settled
-    if (S->touch > c->synced) { int rc = resolve_pending(c); if (rc) return rc; }
-    Lane& L = lane(c);
-    { int rc = lane_access(c, *D, false); if (rc) return rc; D->tail_mask |= 1u << c->cur; }
-    { int rc = lane_access(c, *S, true); if (rc) return rc; S->version++; S->prov_valid = false; }
-    HIPCHK(c, launch_time_spans(L.s, D->d, n, min_opacity, (gs4d_time_span*)S->d));
-    return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_time_spans(L.s, ops.ptr(data), n, min_opacity, (gs4d_time_span*)ops.ptr(spans)));
+        return (int)GS4D_OK;
+    });
 }
 
 int gs4d_compact_time_window(gs4d_ctx* c, gs4d_buf spans, size_t n, float t0, float t1, gs4d_buf src, size_t stride, gs4d_buf dst, gs4d_buf kept_index, gs4d_buf count) {
@@ -1533,21 +1508,16 @@ int gs4d_compact_time_window(gs4d_ctx* c, gs4d_buf spans, size_t n, float t0, fl
 int gs4d_spatial_order(gs4d_ctx* c, gs4d_buf src, size_t n, size_t stride, size_t pos_offset, gs4d_buf order_index) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("spatial_order: ") + msg).c_str()); };
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    if (n == 0xFFFFFFFFull) return bad("the sort takes 2^32 - 2 records at most");
-    if (!record_stride_ok(stride)) return bad("stride must be a multiple of 16 from 16 to 1024");
-    if (pos_offset % 4 != 0 || pos_offset + 12 > stride) return bad("pos_offset must be a multiple of 4 with pos_offset + 12 <= stride");
-    const gs4d_buf names[2] = { src, order_index };
-    Buffer* S = getbuf(c, src); Buffer* O = getbuf(c, order_index);
-    if (!S || !O) return bad("bad buffer name");
-    if (check_record_names(c, names, 2)) return bad("src and order_index must be different buffers");
-    if (S->bytes / stride < n) return bad("src holds fewer than n records");
-    if (O->bytes / 4 < n) return bad("order_index holds fewer than n entries");
+    const char* const fn = "spatial_order";
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    if (n == 0xFFFFFFFFull) return refuse(c, fn, "the sort takes 2^32 - 2 records at most");
+    if (!record_stride_ok(stride)) return refuse(c, fn, "stride must be a multiple of 16 from 16 to 1024");
+    if (pos_offset % 4 != 0 || pos_offset + 12 > stride) return refuse(c, fn, "pos_offset must be a multiple of 4 with pos_offset + 12 <= stride");
+    Operands ops{ { "src", src, false, stride, n, OP_READ }, { "order_index", order_index, false, 4, n, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (n == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 2); if (rc) return rc; }
     const size_t box_words = order_box_words();
-    return queue_on_lane(c, { S }, { O },
+    return queue_operands(c, ops,
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.spatial_scratch, L.spatial_cap, box_words + n));
             HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));      // (the tile sort's scratch: a histogram a queued keygen has left in depth_sort stays where it is)
@@ -1555,9 +1525,9 @@ int gs4d_spatial_order(gs4d_ctx* c, gs4d_buf src, size_t n, size_t stride, size_
         },
         [&](Lane& L) {
             uint32_t* const keys = L.spatial_scratch + box_words;
-            HIPCHK(c, launch_order_keys(L.s, S->d, n, stride, pos_offset, (float*)L.spatial_scratch, keys));
+            HIPCHK(c, launch_order_keys(L.s, ops.ptr(src), n, stride, pos_offset, (float*)L.spatial_scratch, keys));
             // the stable sort of the identity by key: the first pass that moves keys makes the indices up
-            HIPCHK(c, radix_sort_pairs(L.s, L.pair_sort, keys, (uint32_t*)O->d, n, nullptr, ORDER_KEY_BITS, false, true));
+            HIPCHK(c, radix_sort_pairs(L.s, L.pair_sort, keys, (uint32_t*)ops.ptr(order_index), n, nullptr, ORDER_KEY_BITS, false, true));
             return (int)GS4D_OK;
         });
 }
@@ -1565,53 +1535,41 @@ int gs4d_spatial_order(gs4d_ctx* c, gs4d_buf src, size_t n, size_t stride, size_
 int gs4d_gather_records(gs4d_ctx* c, gs4d_buf index, size_t m, gs4d_buf src, size_t nsrc, size_t stride, gs4d_buf dst) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("gather_records: ") + msg).c_str()); };
-    if (m > 0xFFFFFFFFull || nsrc > 0xFFFFFFFFull) return bad("more than 2^32 - 1 entries or records");
-    if (!record_stride_ok(stride) && stride != 4 && stride != 8) return bad("stride must be a multiple of 16 from 16 to 1024, or 4 or 8");
-    const gs4d_buf names[3] = { index, src, dst };
-    Buffer* X = getbuf(c, index); Buffer* S = getbuf(c, src); Buffer* D = getbuf(c, dst);
-    if (!X || !S || !D) return bad("bad buffer name");
-    if (check_record_names(c, names, 3)) return bad("index, src and dst must be different buffers");
-    if (X->bytes / 4 < m) return bad("index holds fewer than m entries");
-    if (S->bytes / stride < nsrc) return bad("src holds fewer than nsrc records");
-    if (D->bytes / stride < m) return bad("dst holds fewer than m records");
+    const char* const fn = "gather_records";
+    if (m > 0xFFFFFFFFull || nsrc > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 entries or records");
+    if (!record_stride_ok(stride) && stride != 4 && stride != 8) return refuse(c, fn, "stride must be a multiple of 16 from 16 to 1024, or 4 or 8");
+    Operands ops{ { "index", index, false, 4, m, OP_READ }, { "src", src, false, stride, nsrc, OP_READ }, { "dst", dst, false, stride, m, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (m == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
-    return queue_on_lane(c, { X, S }, { D },
-        [&](Lane&) { return (int)GS4D_OK; },
-        [&](Lane& L) {
-            HIPCHK(c, launch_gather_records(L.s, (const uint32_t*)X->d, m, S->d, nsrc, stride, D->d));
-            return (int)GS4D_OK;
-        });
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_gather_records(L.s, (const uint32_t*)ops.ptr(index), m, ops.ptr(src), nsrc, stride, ops.ptr(dst)));
+        return (int)GS4D_OK;
+    });
 }
 
 // ---- view-dependent colour ----
 int gs4d_shade_sh(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_stride, int degree, float t, const float cam_pos[3]) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("shade_sh: ") + msg).c_str()); };
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    if (degree < 0 || degree > 3) return bad("degree must be 0, 1, 2 or 3");
-    if (!record_stride_ok(sh_stride)) return bad("sh_stride must be a multiple of 16 from 16 to 1024");
-    if (sh_stride < 12u * (size_t)((degree + 1) * (degree + 1))) return bad("sh_stride holds fewer than 12 (degree + 1)^2 bytes");
-    if (!cam_pos) return bad("cam_pos == NULL");
-    const gs4d_buf names[2] = { data, sh };
-    Buffer* D = getbuf(c, data); Buffer* S = getbuf(c, sh);
-    if (!D || !S) return bad("bad buffer name");
-    if (check_record_names(c, names, 2)) return bad("data and sh must be different buffers");
-    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
-    if (S->bytes / sh_stride < n) return bad("sh holds fewer than n rows");
+    const char* const fn = "shade_sh";
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    if (degree < 0 || degree > 3) return refuse(c, fn, "degree must be 0, 1, 2 or 3");
+    if (!record_stride_ok(sh_stride)) return refuse(c, fn, "sh_stride must be a multiple of 16 from 16 to 1024");
+    if (sh_stride < 12u * (size_t)((degree + 1) * (degree + 1))) return refuse(c, fn, "sh_stride holds fewer than 12 (degree + 1)^2 bytes");
+    if (!cam_pos) return refuse(c, fn, "cam_pos == NULL");
+    Operands ops{ { "data", data, false, 96, n, OP_WRITE }, { "sh", sh, false, sh_stride, n, OP_READ } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (n == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 2); if (rc) return rc; }
+    Buffer* const D = ops.buffer(data);
     // A colour-only write: the shadow's layout choice, the bounding box and the key bounds read no colour, so a shadow that is current stays current —
     // the kernel patches its colour plane (plane 1 in every layout: k_soa_repack) and soa_version moves on with version.  Decided once the pending
     // draws are settled (a re-run may rebuild the shadow) and before any buffer state is touched.
     bool patch = false;
     const float cam[3] = { cam_pos[0], cam_pos[1], cam_pos[2] };
-    return queue_on_lane(c, { S }, { D },
+    return queue_operands(c, ops,
         [&](Lane&) { patch = D->soa && D->soa_n == D->bytes / 96 && D->soa_version == D->version; return (int)GS4D_OK; },
         [&](Lane& L) {
-            HIPCHK(c, launch_shade_sh(L.s, D->d, n, S->d, sh_stride, degree, t, cam, patch ? D->soa + D->soa_n : nullptr));
+            HIPCHK(c, launch_shade_sh(L.s, D->d, n, ops.ptr(sh), sh_stride, degree, t, cam, patch ? D->soa + D->soa_n : nullptr));
             if (patch) D->soa_version = D->version;
             return (int)GS4D_OK;
         });
@@ -1621,42 +1579,34 @@ int gs4d_shade_sh(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_s
 int gs4d_edit_colours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_colour_edit* edit, gs4d_buf stats, const gs4d_keep_rule* rule, gs4d_buf from) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("edit_colours: ") + msg).c_str()); };
-    if (!edit) return bad("edit == NULL");
-    if (edit->op != GS4D_EDIT_SET && edit->op != GS4D_EDIT_MUL && edit->op != GS4D_EDIT_LERP && edit->op != GS4D_EDIT_COPY) return bad("unknown op");
-    if (edit->channels == 0u || edit->channels > 15u) return bad("channels must be 1 .. 15");
-    if (edit->reserved != 0u) return bad("non-zero reserved field in the edit");
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    if ((stats != 0) != (rule != nullptr)) return bad("stats and rule are given together or not at all");
+    const char* const fn = "edit_colours";
+    if (!edit) return refuse(c, fn, "edit == NULL");
+    if (edit->op != GS4D_EDIT_SET && edit->op != GS4D_EDIT_MUL && edit->op != GS4D_EDIT_LERP && edit->op != GS4D_EDIT_COPY) return refuse(c, fn, "unknown op");
+    if (edit->channels == 0u || edit->channels > 15u) return refuse(c, fn, "channels must be 1 .. 15");
+    if (edit->reserved != 0u) return refuse(c, fn, "non-zero reserved field in the edit");
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    if ((stats != 0) != (rule != nullptr)) return refuse(c, fn, "stats and rule are given together or not at all");
     KeepRule k;
-    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
+    if (!keep_rule_of(rule, k)) return refuse(c, fn, "unknown flag or non-zero reserved field in the rule");
     const bool copy = edit->op == GS4D_EDIT_COPY;
-    if (copy && from == 0) return bad("GS4D_EDIT_COPY needs from");
-    if (!copy && from != 0) return bad("from must be 0 unless the op is GS4D_EDIT_COPY");
-    const gs4d_buf names[3] = { data, stats, from };
-    Buffer* D = getbuf(c, data);
-    if (!D) return bad("data is not a live buffer");
-    if (const int wrong = check_record_names(c, names, 3)) return bad(wrong == 1 ? "bad buffer name" : "data, stats and from must be different buffers");
-    Buffer* S = getbuf(c, stats); Buffer* F = getbuf(c, from);
-    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
-    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
-    if (F && F->bytes / 96 < n) return bad("from holds fewer than n records");
+    if (copy && from == 0) return refuse(c, fn, "GS4D_EDIT_COPY needs from");
+    if (!copy && from != 0) return refuse(c, fn, "from must be 0 unless the op is GS4D_EDIT_COPY");
+    Operands ops{ { "data", data, false, 96, n, OP_WRITE },
+                  { "stats", stats, true, sizeof(gs4d_record_stat), n, OP_READ | OP_SETTLE | OP_SCAN },
+                  { "from", from, true, 96, n, OP_READ } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (n == 0) return GS4D_OK;
     const EditOp e{ edit->op, edit->channels, { edit->value[0], edit->value[1], edit->value[2], edit->value[3] }, edit->amount };
-    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
-    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    Buffer* const D = ops.buffer(data);
     // A colour-only write, as gs4d_shade_sh's, extended to the alpha: nothing the library derives from a record buffer reads floats 4..7 (k_soa_repack
     // copies them to plane 1 whole; the bounding box and the key bounds read position, mu_t and sig[3].xyz, the layout choice sig and mu_t), so a shadow
     // that is current stays current — the kernel reads the old colour from its plane 1 and writes the new one there too.  Decided once the pending
     // draws are settled (a re-run may rebuild the shadow) and before any buffer state is touched.
     bool patch = false;
-    return queue_scan_on_lane(c, { S, F }, { D }, { S },
-        [&](Lane&) {
-            patch = D->soa && D->soa_n == D->bytes / 96 && D->soa_version == D->version;
-            return (int)GS4D_OK;
-        },
+    return queue_operands(c, ops,
+        [&](Lane&) { patch = D->soa && D->soa_n == D->bytes / 96 && D->soa_version == D->version; return (int)GS4D_OK; },
         [&](Lane& L) {
-            HIPCHK(c, launch_edit_colours(L.s, D->d, n, e, S ? (const gs4d_record_stat*)S->d : nullptr, k, F ? F->d : nullptr, patch ? D->soa + D->soa_n : nullptr));
+            HIPCHK(c, launch_edit_colours(L.s, D->d, n, e, (const gs4d_record_stat*)ops.ptr(stats), k, ops.ptr(from), patch ? D->soa + D->soa_n : nullptr));
             if (patch) D->soa_version = D->version;
             return (int)GS4D_OK;
         });
@@ -1666,126 +1616,94 @@ int gs4d_edit_colours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_colour_ed
 int gs4d_build_records(gs4d_ctx* c, const gs4d_splat_params* params, size_t n, gs4d_buf dst) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const std::string& msg) { return fail(c, GS4D_E_INVALID, ("build_records: " + msg).c_str()); };
-    if (!params) return bad("params == NULL");
+    const char* const fn = "build_records";
+    if (!params) return refuse(c, fn, "params == NULL");
     const gs4d_splat_params& p = *params;
-    if (p.form != GS4D_PARAMS_3D && p.form != GS4D_PARAMS_4D_VEL && p.form != GS4D_PARAMS_4D_2Q) return bad("unknown form");
-    if (p.flags != 0u || p.reserved != 0u) return bad("flags and reserved must be 0");
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    // bytes per row of every parameter in the form; 0: the form does not use it
+    if (p.form != GS4D_PARAMS_3D && p.form != GS4D_PARAMS_4D_VEL && p.form != GS4D_PARAMS_4D_2Q) return refuse(c, fn, "unknown form");
+    if (p.flags != 0u || p.reserved != 0u) return refuse(c, fn, "flags and reserved must be 0");
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    // a parameter the form does not use is 0; every other one is required
     const bool vel = p.form == GS4D_PARAMS_4D_VEL, twoq = p.form == GS4D_PARAMS_4D_2Q;
-    struct { const char* name; gs4d_buf buf; size_t row; } const rows[7] = {
-        { "pos", p.pos, p.form == GS4D_PARAMS_3D ? 12u : 16u }, { "rot", p.rot, 16 }, { "rot_r", p.rot_r, twoq ? 16u : 0u }, { "scale", p.scale, twoq ? 16u : 12u },
-        { "rgba", p.rgba, 16 }, { "dir", p.dir, vel ? 12u : 0u }, { "tvar", p.tvar, vel ? 4u : 0u } };
-    Buffer* B[7] = {};
-    for (int k = 0; k < 7; ++k) {
-        if (rows[k].row == 0) { if (rows[k].buf != 0) return bad(std::string(rows[k].name) + " must be 0 in this form"); continue; }
-        if (!(B[k] = getbuf(c, rows[k].buf))) return bad(std::string(rows[k].name) + " is not a live buffer");
-    }
-    Buffer* D = getbuf(c, dst);
-    if (!D) return bad("dst is not a live buffer");
-    const gs4d_buf names[8] = { p.pos, p.rot, p.rot_r, p.scale, p.rgba, p.dir, p.tvar, dst };
-    if (check_record_names(c, names, 8)) return bad("the parameter buffers and dst must be different buffers");
-    for (int k = 0; k < 7; ++k) if (B[k] && B[k]->bytes / rows[k].row < n) return bad(std::string(rows[k].name) + " holds fewer than n rows");
-    if (D->bytes / 96 < n) return bad("dst holds fewer than n records");
+    if (!twoq && p.rot_r != 0) return refuse(c, fn, "rot_r must be 0 in this form");
+    if (!vel && p.dir != 0) return refuse(c, fn, "dir must be 0 in this form");
+    if (!vel && p.tvar != 0) return refuse(c, fn, "tvar must be 0 in this form");
+    Operands ops{ { "pos", p.pos, false, p.form == GS4D_PARAMS_3D ? 12u : 16u, n, OP_READ }, { "rot", p.rot, false, 16, n, OP_READ },
+                  { "rot_r", p.rot_r, !twoq, 16, n, OP_READ }, { "scale", p.scale, false, twoq ? 16u : 12u, n, OP_READ },
+                  { "rgba", p.rgba, false, 16, n, OP_READ }, { "dir", p.dir, !vel, 12, n, OP_READ }, { "tvar", p.tvar, !vel, 4, n, OP_READ },
+                  { "dst", dst, false, 96, n, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (n == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 8); if (rc) return rc; }
-    return queue_on_lane(c, { B[0], B[1], B[2], B[3], B[4], B[5], B[6] }, { D },
-        [&](Lane&) { return (int)GS4D_OK; },
-        [&](Lane& L) {
-            const BuildParams bp = { B[0]->d, B[1]->d, B[2] ? B[2]->d : nullptr, B[3]->d, B[4]->d, B[5] ? B[5]->d : nullptr, B[6] ? B[6]->d : nullptr };
-            HIPCHK(c, launch_build_records(L.s, (int)p.form, bp, n, D->d));
-            return (int)GS4D_OK;
-        });
+    return queue_operands(c, ops, [&](Lane& L) {
+        const BuildParams bp = { ops.ptr(p.pos), ops.ptr(p.rot), ops.ptr(p.rot_r), ops.ptr(p.scale), ops.ptr(p.rgba), ops.ptr(p.dir), ops.ptr(p.tvar) };
+        HIPCHK(c, launch_build_records(L.s, (int)p.form, bp, n, ops.ptr(dst)));
+        return (int)GS4D_OK;
+    });
 }
 
 // ---- records under affine maps ----
 int gs4d_transform_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf dst, size_t dst_first) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("transform_records: ") + msg).c_str()); };
-    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull || dst_first > 0xFFFFFFFFull) return bad("n, m or dst_first above 2^32 - 1");
+    const char* const fn = "transform_records";
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull || dst_first > 0xFFFFFFFFull) return refuse(c, fn, "n, m or dst_first above 2^32 - 1");
     const uint64_t total = (uint64_t)n * m;                    // (both below 2^32: no overflow)
-    if (total > 0xFFFFFFFFull || dst_first + total > 0xFFFFFFFFull) return bad("dst_first + m * n above 2^32 - 1");
-    const gs4d_buf names[3] = { src, xf, dst };
-    Buffer* S = getbuf(c, src); Buffer* X = getbuf(c, xf); Buffer* D = getbuf(c, dst);
-    if (!S || !X || !D) return bad("bad buffer name");
-    if (check_record_names(c, names, 3)) return bad("src, xf and dst must be different buffers");
-    if (S->bytes / 96 < n) return bad("src holds fewer than n records");
-    if (X->bytes / sizeof(gs4d_affine4) < m) return bad("xf holds fewer than m rows");
-    if (D->bytes / 96 < dst_first + total) return bad("dst holds fewer than dst_first + m * n records");
+    if (total > 0xFFFFFFFFull || dst_first + total > 0xFFFFFFFFull) return refuse(c, fn, "dst_first + m * n above 2^32 - 1");
+    Operands ops{ { "src", src, false, 96, n, OP_READ }, { "xf", xf, false, sizeof(gs4d_affine4), m, OP_READ }, { "dst", dst, false, 96, dst_first + total, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (n == 0 || m == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
-    return queue_on_lane(c, { S, X }, { D },
-        [&](Lane&) { return (int)GS4D_OK; },
-        [&](Lane& L) {
-            HIPCHK(c, launch_transform_records(L.s, S->d, n, (const gs4d_affine4*)X->d, m, (char*)D->d + dst_first * 96));
-            return (int)GS4D_OK;
-        });
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_transform_records(L.s, ops.ptr(src), n, (const gs4d_affine4*)ops.ptr(xf), m, (char*)ops.ptr(dst) + dst_first * 96));
+        return (int)GS4D_OK;
+    });
 }
 
 // ---- a 4D set baked at one time ----
 int gs4d_slice_records(gs4d_ctx* c, gs4d_buf src, size_t n, const gs4d_slice* q, gs4d_buf dst, size_t dst_first) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("slice_records: ") + msg).c_str()); };
-    if (!q) return bad("q == NULL");
+    const char* const fn = "slice_records";
+    if (!q) return refuse(c, fn, "q == NULL");
     const gs4d_slice s = *q;
-    if (!std::isfinite(s.t) || !std::isfinite(s.mu_t_out)) return bad("t and mu_t_out must be finite");
-    if (std::isnan(s.min_opacity)) return bad("min_opacity is a NaN");
-    if (!(s.s44_out > 0.0f)) return bad("s44_out must be above 0");
-    if (n > 0xFFFFFFFFull || dst_first > 0xFFFFFFFFull || (uint64_t)n + dst_first > 0xFFFFFFFFull) return bad("n, dst_first or dst_first + n above 2^32 - 1");
-    const gs4d_buf names[2] = { src, dst };
-    Buffer* S = getbuf(c, src); Buffer* D = getbuf(c, dst);
-    if (!S || !D) return bad("bad buffer name");
-    if (check_record_names(c, names, 2)) return bad("src and dst must be different buffers");
-    if (S->bytes / 96 < n) return bad("src holds fewer than n records");
-    if (D->bytes / 96 < dst_first + n) return bad("dst holds fewer than dst_first + n records");
+    if (!std::isfinite(s.t) || !std::isfinite(s.mu_t_out)) return refuse(c, fn, "t and mu_t_out must be finite");
+    if (std::isnan(s.min_opacity)) return refuse(c, fn, "min_opacity is a NaN");
+    if (!(s.s44_out > 0.0f)) return refuse(c, fn, "s44_out must be above 0");
+    if (n > 0xFFFFFFFFull || dst_first > 0xFFFFFFFFull || (uint64_t)n + dst_first > 0xFFFFFFFFull) return refuse(c, fn, "n, dst_first or dst_first + n above 2^32 - 1");
+    Operands ops{ { "src", src, false, 96, n, OP_READ }, { "dst", dst, false, 96, (uint64_t)dst_first + n, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (n == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 2); if (rc) return rc; }
-    return queue_on_lane(c, { S }, { D },
-        [&](Lane&) { return (int)GS4D_OK; },
-        [&](Lane& L) {
-            HIPCHK(c, launch_slice_records(L.s, S->d, n, s, (char*)D->d + dst_first * 96));
-            return (int)GS4D_OK;
-        });
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_slice_records(L.s, ops.ptr(src), n, s, (char*)ops.ptr(dst) + dst_first * 96));
+        return (int)GS4D_OK;
+    });
 }
 
 // ---- a selection under an affine map about a pivot, in place ----
 int gs4d_transform_selected(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_selection_xf* xf, gs4d_buf stats, const gs4d_keep_rule* rule, gs4d_buf measure) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("transform_selected: ") + msg).c_str()); };
-    if (!xf) return bad("xf == NULL");
+    const char* const fn = "transform_selected";
+    if (!xf) return refuse(c, fn, "xf == NULL");
     const gs4d_selection_xf x = *xf;
-    if (x.flags != 0u && x.flags != (uint32_t)GS4D_XS_PIVOT && x.flags != (uint32_t)GS4D_XS_PIVOT_MEASURE) return bad("flags must be 0, GS4D_XS_PIVOT or GS4D_XS_PIVOT_MEASURE");
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    if ((stats != 0) != (rule != nullptr)) return bad("stats and rule are given together or not at all");
+    if (x.flags != 0u && x.flags != (uint32_t)GS4D_XS_PIVOT && x.flags != (uint32_t)GS4D_XS_PIVOT_MEASURE) return refuse(c, fn, "flags must be 0, GS4D_XS_PIVOT or GS4D_XS_PIVOT_MEASURE");
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    if ((stats != 0) != (rule != nullptr)) return refuse(c, fn, "stats and rule are given together or not at all");
     KeepRule k;
-    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
+    if (!keep_rule_of(rule, k)) return refuse(c, fn, "unknown flag or non-zero reserved field in the rule");
     const bool measured = x.flags == (uint32_t)GS4D_XS_PIVOT_MEASURE;
-    if (measured && measure == 0) return bad("GS4D_XS_PIVOT_MEASURE needs measure");
-    if (!measured && measure != 0) return bad("measure must be 0 unless the flag is GS4D_XS_PIVOT_MEASURE");
-    const gs4d_buf names[3] = { data, stats, measure };
-    Buffer* D = getbuf(c, data);
-    if (!D) return bad("data is not a live buffer");
-    if (const int wrong = check_record_names(c, names, 3)) return bad(wrong == 1 ? "bad buffer name" : "data, stats and measure must be different buffers");
-    Buffer* S = getbuf(c, stats); Buffer* M = getbuf(c, measure);
-    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
-    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
-    if (M && M->bytes < sizeof(gs4d_measure)) return bad("measure holds fewer than 96 bytes");
-    if (n == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
-    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    if (measured && measure == 0) return refuse(c, fn, "GS4D_XS_PIVOT_MEASURE needs measure");
+    if (!measured && measure != 0) return refuse(c, fn, "measure must be 0 unless the flag is GS4D_XS_PIVOT_MEASURE");
     // The table and the measurement are read (gs4d_edit_colours' table; an ordinary read buffer, behind the kernels that wrote it), data is written as
     // gs4d_transform_records writes its dst: a full write whatever the table selects — position, mu_t and sig move, so the shadow, the bounding box
     // and the key bounds of data are all stale.  The shadow is not patched: the next draw or gs4d_keygen rebuilds it.
-    return queue_scan_on_lane(c, { S, M }, { D }, { S },
-        [&](Lane&) { return (int)GS4D_OK; },
-        [&](Lane& L) {
-            HIPCHK(c, launch_transform_selected(L.s, D->d, n, x, S ? (const gs4d_record_stat*)S->d : nullptr, k, M ? (const gs4d_measure*)M->d : nullptr));
-            return (int)GS4D_OK;
-        });
+    Operands ops{ { "data", data, false, 96, n, OP_WRITE },
+                  { "stats", stats, true, sizeof(gs4d_record_stat), n, OP_READ | OP_SETTLE | OP_SCAN },
+                  { "measure", measure, true, 1, sizeof(gs4d_measure), OP_READ } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (n == 0) return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_transform_selected(L.s, ops.ptr(data), n, x, (const gs4d_record_stat*)ops.ptr(stats), k, (const gs4d_measure*)ops.ptr(measure)));
+        return (int)GS4D_OK;
+    });
 }
 
 // ---- draw ----
@@ -2065,71 +1983,62 @@ int gs4d_read_ids_device(gs4d_ctx* c, void* record, void* draw, void* weight, si
 int gs4d_count_ids(gs4d_ctx* c, const gs4d_id_region* region, gs4d_buf mask, gs4d_buf stats, size_t nrecords) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("count_ids: ") + msg).c_str()); };
+    const char* const fn = "count_ids";
     const gs4d_id_region g = region ? *region : gs4d_id_region{ 0, 0, c->W, c->H, 0u, 0xFFFFFFFFu, 0u, 0u };
-    if (g.reserved != 0u) return bad("non-zero reserved field in the region");
-    if (g.draw_first > g.draw_last) return bad("draw_first > draw_last");
-    if (nrecords > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    const gs4d_buf names[2] = { stats, mask };
-    Buffer* S = getbuf(c, stats); Buffer* M = getbuf(c, mask);
-    if (!S || (mask != 0 && !M)) return bad("bad buffer name");
-    if (check_record_names(c, names, 2)) return bad("mask and stats must be different buffers");
-    if (S->bytes / sizeof(gs4d_record_stat) < nrecords) return bad("the stats buffer holds fewer than nrecords rows");
-    if (g.x < 0 || g.y < 0 || g.w <= 0 || g.h <= 0 || g.w > c->W - g.x || g.h > c->H - g.y) return bad("the rectangle is empty or not inside the image");
-    if (M && M->bytes < (size_t)g.w * (size_t)g.h) return bad("the mask holds fewer than w*h bytes");
-    if (c->fbs[c->cur_fb].out < Outputs::Ids) return bad("the current frame was not cleared with ID outputs on");      // (before read_begin launches the queued order: a refused call queues nothing)
+    if (g.reserved != 0u) return refuse(c, fn, "non-zero reserved field in the region");
+    if (g.draw_first > g.draw_last) return refuse(c, fn, "draw_first > draw_last");
+    if (nrecords > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    if (g.x < 0 || g.y < 0 || g.w <= 0 || g.h <= 0 || g.w > c->W - g.x || g.h > c->H - g.y) return refuse(c, fn, "the rectangle is empty or not inside the image");
+    if (c->fbs[c->cur_fb].out < Outputs::Ids) return refuse(c, fn, "the current frame was not cleared with ID outputs on");      // (before read_begin launches the queued order: a refused call queues nothing)
+    // stats as WRITE: the lane waits for whoever wrote the table AND for whoever still reads it or adds to it, which is what a read-modify-write
+    // needs; the new version and the dropped provenance are those of any kernel write
+    Operands ops{ { "stats", stats, false, sizeof(gs4d_record_stat), nrecords, OP_WRITE | OP_SETTLE },
+                  { "mask", mask, true, 1, (uint64_t)g.w * (uint64_t)g.h, OP_READ } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (nrecords == 0) return GS4D_OK;
     // the planes as gs4d_read_ids_device takes them: the queued order launched, the frame's draws settled, every tile in memory
     { int rc = flush_order(c); if (rc) return rc; }
     { int rc = resolve_image(c, c->cur_fb); if (rc) return rc; }
-    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    // stats as an "out" of queue_on_lane: the lane waits for whoever wrote the table AND for whoever still reads it or adds to it, which is what a
-    // read-modify-write needs; the new version and the dropped provenance are those of any kernel write
-    return queue_on_lane(c, { M }, { S },
-        [&](Lane&) { return (int)GS4D_OK; },
-        [&](Lane& L) {
-            Framebuffer& F = c->fbs[c->cur_fb];
-            { int rc = fb_access(c, F); if (rc) return rc; }
-            { int rc = materialise_fb(c, F, L); if (rc) return rc; }
-            HIPCHK(c, launch_count_ids(L.s, F.ids, c->W, c->H, g, M ? (const uint8_t*)M->d : nullptr, (gs4d_record_stat*)S->d, (uint32_t)nrecords));
-            return (int)GS4D_OK;
-        });
+    return queue_operands(c, ops, [&](Lane& L) {
+        Framebuffer& F = c->fbs[c->cur_fb];
+        { int rc = fb_access(c, F); if (rc) return rc; }
+        { int rc = materialise_fb(c, F, L); if (rc) return rc; }
+        HIPCHK(c, launch_count_ids(L.s, F.ids, c->W, c->H, g, (const uint8_t*)ops.ptr(mask), (gs4d_record_stat*)ops.ptr(stats), (uint32_t)nrecords));
+        return (int)GS4D_OK;
+    });
 }
 
 // ---- selection by where a record is: a statistics table from a volume or a screen region ----
 int gs4d_count_centres(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_centre_query* query, gs4d_buf mask, gs4d_buf stats) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("count_centres: ") + msg).c_str()); };
-    if (!query) return bad("query == NULL");
+    const char* const fn = "count_centres";
+    if (!query) return refuse(c, fn, "query == NULL");
     const gs4d_centre_query q = *query;
     constexpr uint32_t known = GS4D_CQ_BOX | GS4D_CQ_SPHERE | GS4D_CQ_SCREEN | GS4D_CQ_FRAME | GS4D_CQ_SKIP_HIDDEN | GS4D_CQ_SKIP_DEAD;
-    if ((q.tests & ~known) != 0u) return bad("unknown test bit");
-    if (q.op != (uint32_t)GS4D_CQ_ADD && q.op != (uint32_t)GS4D_CQ_REMOVE) return bad("unknown op");
-    if (q.reserved != 0u) return bad("non-zero reserved field in the query");
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
+    if ((q.tests & ~known) != 0u) return refuse(c, fn, "unknown test bit");
+    if (q.op != (uint32_t)GS4D_CQ_ADD && q.op != (uint32_t)GS4D_CQ_REMOVE) return refuse(c, fn, "unknown op");
+    if (q.reserved != 0u) return refuse(c, fn, "non-zero reserved field in the query");
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
     const bool screen = (q.tests & (uint32_t)GS4D_CQ_SCREEN) != 0u;
-    const gs4d_buf names[3] = { data, stats, mask };
-    Buffer* D = getbuf(c, data); Buffer* S = getbuf(c, stats); Buffer* M = getbuf(c, mask);
-    if (!D || !S || (mask != 0 && !M)) return bad("bad buffer name");
-    if (check_record_names(c, names, 3)) return bad("data, stats and mask must be different buffers");
-    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
-    if (S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
-    if (M && !screen) return bad("a mask is given without GS4D_CQ_SCREEN");
-    if (screen && (q.x < 0 || q.y < 0 || q.w <= 0 || q.h <= 0 || q.w > c->W - q.x || q.h > c->H - q.y)) return bad("the rectangle is empty or not inside the image");
-    if (M && M->bytes < (size_t)q.w * (size_t)q.h) return bad("the mask holds fewer than w*h bytes");
+    if (mask != 0 && !screen) return refuse(c, fn, "a mask is given without GS4D_CQ_SCREEN");
+    if (screen && (q.x < 0 || q.y < 0 || q.w <= 0 || q.h <= 0 || q.w > c->W - q.x || q.h > c->H - q.y)) return refuse(c, fn, "the rectangle is empty or not inside the image");
+    // stats as WRITE, as in gs4d_count_ids: a read-modify-write the lane has the table to itself for.  data and mask are read (a mask comes with a
+    // rectangle that has been checked: w * h is its size).
+    Operands ops{ { "data", data, false, 96, n, OP_READ },
+                  { "stats", stats, false, sizeof(gs4d_record_stat), n, OP_WRITE | OP_SETTLE },
+                  { "mask", mask, true, 1, (uint64_t)q.w * (uint64_t)q.h, OP_READ } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (n == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
-    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    // stats as an "out" of queue_on_lane, as in gs4d_count_ids: a read-modify-write the lane has the table to itself for.  data and mask are read.
+    Buffer* const D = ops.buffer(data);
     // Where the fields are read: a shadow of data that is current holds the bits of the records in dense planes (k_soa_repack) — decided once the
     // pending draws are settled (a re-run may rebuild the shadow) and before any buffer state is touched.  The call reads: it never builds a shadow,
     // and a reader leaves `version` alone, so a current shadow stays current.
     bool shadow = false;
-    return queue_on_lane(c, { D, M }, { S },
+    return queue_operands(c, ops,
         [&](Lane&) { shadow = D->soa && D->soa_n == D->bytes / 96 && D->soa_version == D->version; return (int)GS4D_OK; },
         [&](Lane& L) {
-            HIPCHK(c, launch_count_centres(L.s, D->d, shadow ? D->soa : nullptr, D->soa_n, D->soa_info, n, q, c->W, c->H, M ? (const uint8_t*)M->d : nullptr, (gs4d_record_stat*)S->d));
+            HIPCHK(c, launch_count_centres(L.s, D->d, shadow ? D->soa : nullptr, D->soa_n, D->soa_info, n, q, c->W, c->H, (const uint8_t*)ops.ptr(mask), (gs4d_record_stat*)ops.ptr(stats)));
             return (int)GS4D_OK;
         });
 }
@@ -2138,34 +2047,28 @@ int gs4d_count_centres(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_centre_q
 int gs4d_measure_records(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_measure_query* query, gs4d_buf stats, const gs4d_keep_rule* rule, gs4d_buf out) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("measure_records: ") + msg).c_str()); };
-    if (!query) return bad("query == NULL");
+    const char* const fn = "measure_records";
+    if (!query) return refuse(c, fn, "query == NULL");
     const gs4d_measure_query q = *query;
-    if ((q.flags & ~(uint32_t)(GS4D_MS_SKIP_HIDDEN | GS4D_MS_SKIP_DEAD)) != 0u) return bad("unknown flag");
-    if (q.reserved[0] != 0u || q.reserved[1] != 0u) return bad("non-zero reserved field in the query");
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    if ((stats != 0) != (rule != nullptr)) return bad("stats and rule are given together or not at all");
+    if ((q.flags & ~(uint32_t)(GS4D_MS_SKIP_HIDDEN | GS4D_MS_SKIP_DEAD)) != 0u) return refuse(c, fn, "unknown flag");
+    if (q.reserved[0] != 0u || q.reserved[1] != 0u) return refuse(c, fn, "non-zero reserved field in the query");
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    if ((stats != 0) != (rule != nullptr)) return refuse(c, fn, "stats and rule are given together or not at all");
     KeepRule k;
-    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
-    const gs4d_buf names[3] = { data, out, stats };
-    Buffer* D = getbuf(c, data); Buffer* O = getbuf(c, out);
-    if (!D || !O) return bad("data and out must name live buffers");
-    if (const int wrong = check_record_names(c, names, 3)) return bad(wrong == 1 ? "bad buffer name" : "data, stats and out must be different buffers");
-    Buffer* S = getbuf(c, stats);
-    if (D->bytes / 96 < n) return bad("data holds fewer than n records");
-    if (S && S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
-    if (O->bytes < sizeof(gs4d_measure)) return bad("out holds fewer than 96 bytes");
-    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
-    if (S) { int rc = settle_stats_table(c, *S); if (rc) return rc; }
+    if (!keep_rule_of(rule, k)) return refuse(c, fn, "unknown flag or non-zero reserved field in the rule");
     // data and the table are read (gs4d_count_centres' data, gs4d_edit_colours' table), out is written whole (gs4d_stat_cut's out).  The kernels read
     // the 96-byte records, never a shadow, and a reader leaves `version` alone: a current shadow stays current and none is built.
-    return queue_scan_on_lane(c, { D, S }, { O }, { S },
+    Operands ops{ { "data", data, false, 96, n, OP_READ },
+                  { "stats", stats, true, sizeof(gs4d_record_stat), n, OP_READ | OP_SETTLE | OP_SCAN },
+                  { "out", out, false, 1, sizeof(gs4d_measure), OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    return queue_operands(c, ops,
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.measure_scratch, L.measure_cap, measure_scratch_words()));
             return (int)GS4D_OK;
         },
         [&](Lane& L) {
-            HIPCHK(c, launch_measure_records(L.s, D->d, n, q.t, q.flags, S ? (const gs4d_record_stat*)S->d : nullptr, k, L.measure_scratch, (gs4d_measure*)O->d));
+            HIPCHK(c, launch_measure_records(L.s, ops.ptr(data), n, q.t, q.flags, (const gs4d_record_stat*)ops.ptr(stats), k, L.measure_scratch, (gs4d_measure*)ops.ptr(out)));
             return (int)GS4D_OK;
         });
 }
@@ -2177,8 +2080,7 @@ int gs4d_count_neighbours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_neigh
     if (!query) return fail(c, GS4D_E_INVALID, "count_neighbours: query == NULL");
     const gs4d_neighbour_query q = *query;
     const GridQuery g{ q.radius, q.flags, (uint32_t)(GS4D_NB_SKIP_HIDDEN | GS4D_NB_SKIP_DEAD | GS4D_NB_COUNT_SELF), q.reserved, q.cap == 0u ? "cap == 0" : nullptr };
-    const GridOutputs o{ stats, sizeof(gs4d_record_stat), true, 0, "data and stats must name live buffers", nullptr,
-                         "data, source and stats must be different buffers", "the stats buffer holds fewer than n rows" };
+    const GridOutputs o{ "stats", stats, sizeof(gs4d_record_stat), true, 0, nullptr };
     return grid_query(c, "count_neighbours", g, n, data, source, rule, o,
         [&](Lane& L, const void* records, const gs4d_record_stat* rows, const KeepRule& k, void* table, gs4d_record_stat*) {
             HIPCHK(c, launch_count_neighbours(L.s, L.pair_sort, records, n, q, rows, k, L.neighbour_scratch, (gs4d_record_stat*)table, c->neighbour_phases));
@@ -2194,8 +2096,7 @@ int gs4d_label_components(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_compo
     if (!query) return fail(c, GS4D_E_INVALID, "label_components: query == NULL");
     const gs4d_component_query q = *query;
     const GridQuery g{ q.radius, q.flags, (uint32_t)(GS4D_CC_SKIP_HIDDEN | GS4D_CC_SKIP_DEAD), q.reserved, q.cap == 0u ? "cap == 0" : nullptr };
-    const GridOutputs o{ labels, sizeof(uint32_t), false, stats, "data and labels must name live buffers", nullptr,
-                         "data, source, labels and stats must be different buffers", "labels holds fewer than n words" };
+    const GridOutputs o{ "labels", labels, sizeof(uint32_t), false, stats, nullptr };
     return grid_query(c, "label_components", g, n, data, source, rule, o,
         [&](Lane& L, const void* records, const gs4d_record_stat* rows, const KeepRule& k, void* words, gs4d_record_stat* table) {
             HIPCHK(c, launch_label_components(L.s, L.pair_sort, records, n, q, rows, k, L.neighbour_scratch, (uint32_t*)words, table, L.err_word()));
@@ -2207,31 +2108,26 @@ int gs4d_label_components(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_compo
 int gs4d_count_labels(gs4d_ctx* c, gs4d_buf labels, size_t n, gs4d_buf seeds, const gs4d_keep_rule* rule, gs4d_buf stats) {
     if (!c) return GS4D_E_INVALID;
     (void)hipSetDevice(c->device);
-    auto bad = [&](const char* msg) { return fail(c, GS4D_E_INVALID, (std::string("count_labels: ") + msg).c_str()); };
-    if (n > 0xFFFFFFFFull) return bad("more than 2^32 - 1 records");
-    if (!rule) return bad("rule == NULL");
+    const char* const fn = "count_labels";
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    if (!rule) return refuse(c, fn, "rule == NULL");
     KeepRule k;
-    if (!keep_rule_of(rule, k)) return bad("unknown flag or non-zero reserved field in the rule");
-    const gs4d_buf names[3] = { labels, seeds, stats };
-    Buffer* B = getbuf(c, labels); Buffer* Q = getbuf(c, seeds); Buffer* S = getbuf(c, stats);
-    if (!B || !Q || !S) return bad("labels, seeds and stats must name live buffers");
-    if (check_record_names(c, names, 3)) return bad("labels, seeds and stats must be different buffers");
-    if (B->bytes / sizeof(uint32_t) < n) return bad("labels holds fewer than n words");
-    if (Q->bytes / sizeof(gs4d_record_stat) < n) return bad("the seeds buffer holds fewer than n rows");
-    if (S->bytes / sizeof(gs4d_record_stat) < n) return bad("the stats buffer holds fewer than n rows");
+    if (!keep_rule_of(rule, k)) return refuse(c, fn, "unknown flag or non-zero reserved field in the rule");
+    // labels and seeds are read (seeds as gs4d_edit_colours reads its table), stats is a read-modify-write the lane has the table to itself for: it
+    // is declared before seeds because it is settled before seeds.  The flag words live in the lane's neighbour scratch, whose reuse the lane's
+    // stream orders.
+    Operands ops{ { "labels", labels, false, sizeof(uint32_t), n, OP_READ },
+                  { "stats", stats, false, sizeof(gs4d_record_stat), n, OP_WRITE | OP_SETTLE },
+                  { "seeds", seeds, false, sizeof(gs4d_record_stat), n, OP_READ | OP_SETTLE | OP_SCAN } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
     if (n == 0) return GS4D_OK;
-    { int rc = flush_order_if_named(c, names, 3); if (rc) return rc; }
-    { int rc = settle_stats_table(c, *S); if (rc) return rc; }
-    { int rc = settle_stats_table(c, *Q); if (rc) return rc; }
-    // labels and seeds are read (seeds as gs4d_edit_colours reads its table), stats is a read-modify-write the lane has the table to itself for.  The
-    // flag words live in the lane's neighbour scratch, whose reuse the lane's stream orders.
-    return queue_scan_on_lane(c, { B, Q }, { S }, { Q },
+    return queue_operands(c, ops,
         [&](Lane& L) {
             HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, n));
             return (int)GS4D_OK;
         },
         [&](Lane& L) {
-            HIPCHK(c, launch_count_labels(L.s, (const uint32_t*)B->d, n, (const gs4d_record_stat*)Q->d, k, L.neighbour_scratch, (gs4d_record_stat*)S->d));
+            HIPCHK(c, launch_count_labels(L.s, (const uint32_t*)ops.ptr(labels), n, (const gs4d_record_stat*)ops.ptr(seeds), k, L.neighbour_scratch, (gs4d_record_stat*)ops.ptr(stats)));
             return (int)GS4D_OK;
         });
 }
@@ -2246,9 +2142,7 @@ int gs4d_nearest_neighbours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_nea
     const GridQuery g{ q.radius, q.flags, (uint32_t)(GS4D_NN_SKIP_HIDDEN | GS4D_NN_SKIP_DEAD | GS4D_NN_INCLUDE_SELF), q.reserved,
                        q.k == 0u || q.k > 16u ? "k must be 1 to 16" : nullptr };
     const bool stride_ok = record_stride_ok(hit_stride) && hit_stride >= 8 * (size_t)q.k;
-    const GridOutputs o{ hits, hit_stride, false, stats, "data and hits must name live buffers",
-                         stride_ok ? nullptr : "hit_stride must be a multiple of 16 from 16 to 1024 that is at least 8 k",
-                         "data, source, hits and stats must be different buffers", "hits holds fewer than n rows of hit_stride bytes" };
+    const GridOutputs o{ "hits", hits, hit_stride, false, stats, stride_ok ? nullptr : "hit_stride must be a multiple of 16 from 16 to 1024 that is at least 8 k" };
     return grid_query(c, "nearest_neighbours", g, n, data, source, rule, o,
         [&](Lane& L, const void* records, const gs4d_record_stat* rows, const KeepRule& k, void* slots, gs4d_record_stat* table) {
             HIPCHK(c, launch_nearest_neighbours(L.s, L.pair_sort, records, n, q, rows, k, L.neighbour_scratch, slots, hit_stride, table));

@@ -88,6 +88,8 @@ $(CSRC)/slice.o: $(CSRC)/slice.hip $(CSRC)/slice_record.h $(HD) $(CSRC)/gs4d_int
 # make COUNT_IDS_PLAIN=1: gs4d_count_ids without its in-wave aggregation (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(COUNT_IDS_PLAIN),-DGS4D_COUNT_IDS_PLAIN) -c $< -o $@
+# operands.h is the one text of the record-set calls' buffer-argument check (tests/operand_check.cpp compiles it too)
+$(CSRC)/gs4d_api.o: $(CSRC)/operands.h
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gs4d_internal.h $(CSRC)/composite_common.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 $(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/transform_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
