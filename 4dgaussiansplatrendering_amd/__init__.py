@@ -29,6 +29,7 @@ EDIT_SET, EDIT_MUL, EDIT_LERP, EDIT_COPY = 0, 1, 2, 3      # gs4d_colour_edit.op
 CQ_BOX, CQ_SPHERE, CQ_SCREEN, CQ_FRAME, CQ_SKIP_HIDDEN, CQ_SKIP_DEAD = 1, 2, 4, 8, 16, 32      # gs4d_centre_query.tests
 CQ_ADD, CQ_REMOVE = 0, 1                                   # gs4d_centre_query.op
 MS_SKIP_HIDDEN, MS_SKIP_DEAD = 1, 2                        # gs4d_measure_query.flags
+POSE_INDEX, POSE_BLEND4 = 0, 1                             # gs4d_pose_records: the form of a bind row
 XS_PIVOT, XS_PIVOT_MEASURE = 1, 2                          # gs4d_selection_xf.flags
 NB_SKIP_HIDDEN, NB_SKIP_DEAD, NB_COUNT_SELF = 1, 2, 4      # gs4d_neighbour_query.flags
 CC_SKIP_HIDDEN, CC_SKIP_DEAD = 1, 2                        # gs4d_component_query.flags
@@ -109,6 +110,7 @@ def _load():
         "gs4d_build_records": (i32, [vp, vp, sz, u32]),
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_transform_selected": (i32, [vp, u32, sz, vp, u32, vp, u32]),
+        "gs4d_pose_records": (i32, [vp, u32, sz, u32, sz, u32, u32, sz, u32, sz]),
         "gs4d_slice_records": (i32, [vp, u32, sz, vp, u32, sz]),
         "gs4d_count_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_label_components": (i32, [vp, u32, sz, vp, u32, vp, u32, u32]),
@@ -138,6 +140,7 @@ def _load():
         "gs4d_host_build_records_4d_tvar": (None, [sz, vp, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_build_records_4d_2q": (None, [sz, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_transform_records": (None, [sz, vp, vp, vp]),
+        "gs4d_host_pose_records": (None, [sz, vp, vp, sz, vp, u32, sz, vp]),
         "gs4d_host_slice_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_edit_colours": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_count_centres": (None, [sz, vp, vp, i32, i32, vp, vp]),
@@ -303,6 +306,50 @@ def transform_records_host(records, xf):
     for j in range(rows.shape[0]):
         _lib.gs4d_host_transform_records(rec.shape[0], _ptr(rec), _ptr(rows[j]), _ptr(out[j]))
     return out[0] if single else out
+
+
+def bind_rows(joints, weights):
+    """The bind table of pose_records' BLEND4 form as uint32 [n, 8]: per record uint32 j[4], then the bits of float32 w[4].  joints [n, k] and
+    weights [n, k] with k <= 4; missing slots are ID_NONE with weight 0 (a slot takes part iff its joint is a row of the table, whatever its weight)."""
+    j = np.asarray(joints)
+    if j.dtype.kind not in "iu":
+        raise TypeError("joints must be integers")
+    j, w = np.atleast_2d(j.astype(np.uint32)), np.atleast_2d(_f32(weights))
+    if j.shape != w.shape or j.shape[1] > 4:
+        raise ValueError("joints and weights must both be [n, k] with k <= 4")
+    out = np.empty((j.shape[0], 8), np.uint32)
+    out[:, :4], out[:, 4:] = ID_NONE, 0
+    out[:, :j.shape[1]] = j
+    out[:, 4:4 + j.shape[1]] = w.view(np.uint32)
+    return out
+
+
+def _bind_table(bind, form=None, bind_stride=None):
+    """(bytes uint8 [n * stride], form, stride) of a bind array: uint32 [n] is the INDEX form at stride 4, uint32 [n, 8] (bind_rows) the BLEND4 form at
+    stride 32; with form / bind_stride given the array is taken as the bytes of rows of that stride"""
+    a = np.ascontiguousarray(bind)
+    if form is None:
+        if a.dtype != np.uint32 or not (a.ndim == 1 or (a.ndim == 2 and a.shape[1] == 8)):
+            raise TypeError("expected a uint32 [n] array of row indices or a bind_rows [n, 8] array (or give form and bind_stride)")
+        form = POSE_INDEX if a.ndim == 1 else POSE_BLEND4
+    if bind_stride is None:
+        bind_stride = a.strides[0] if a.ndim == 2 else (4 if form == POSE_INDEX else 32)
+    return a.reshape(-1).view(np.uint8), int(form), int(bind_stride)
+
+
+def pose_records_host(records, xf, bind, form=None, bind_stride=None):
+    """gs4d_host_pose_records, the definition of Context.pose_records: records [n, 24] as [n, 24], record i under what row i of `bind` takes from
+    the rows of xf ([m, 20] float32; m may be 0) — a uint32 [n] array (INDEX) or a bind_rows array (BLEND4), or with form and bind_stride the bytes
+    of rows of that stride.  A form or stride the device call would refuse gives zeros."""
+    rec = _f32(records).reshape(-1, 24)
+    rows = _f32(xf).reshape(-1, 20)
+    table, form, bind_stride = _bind_table(bind, form, bind_stride)
+    if table.size < rec.shape[0] * bind_stride:
+        raise ValueError("bind holds fewer rows than there are records")
+    out = np.zeros_like(rec)
+    _lib.gs4d_host_pose_records(rec.shape[0], _ptr(rec), _ptr(rows) if rows.size else None, rows.shape[0], _ptr(table) if table.size else None, form, bind_stride,
+                                _ptr(out))
+    return out
 
 
 class Slice(C.Structure):
@@ -1603,6 +1650,40 @@ class Context:
         finally:
             if own:
                 self.delete(xf)
+        return dst
+
+    # one transform per record: a set posed by a table of maps
+    def pose_records(self, src, n, xf, bind, form=None, m=None, bind_stride=None, dst=None, dst_first=0):
+        """gs4d_pose_records: record dst_first + i of `dst` (a new buffer of dst_first + n records if None) <- record i < n of `src` under what row i
+        of `bind` takes from the m rows of `xf`, with the bits of pose_records_host; a row that names no row of the table copies the record.  xf: a
+        buffer of 80-byte rows (m is then required) or an [m, 20] float32 array; bind: a buffer (form is then required; bind_stride defaults to 4 /
+        32) or a uint32 [n] array of row indices (POSE_INDEX) or a bind_rows array (POSE_BLEND4).  Arrays are uploaded to temporary buffers
+        (deleting them waits for the device, so a frame loop keeps buffers of its own and updates xf with subdata).  A full write of dst: the next
+        draw rebuilds its SoA shadow.  Per frame: (shade_sh), pose, keygen, sort, draw.  Asynchronous; returns `dst`."""
+        temps = []
+        try:
+            if not isinstance(xf, (int, np.integer)):
+                rows = _f32(xf).reshape(-1, 20)
+                m = rows.shape[0]
+                xf = self.buffer(rows) if m else self.buffer(nbytes=80)
+                temps.append(xf)
+            elif m is None:
+                raise TypeError("m is required when xf is a buffer")
+            if not isinstance(bind, (int, np.integer)):
+                table, form, bind_stride = _bind_table(bind, form, bind_stride)
+                bind = self.buffer(table) if table.size else self.buffer(nbytes=32)
+                temps.append(bind)
+            else:
+                if form is None:
+                    raise TypeError("form is required when bind is a buffer")
+                if bind_stride is None:
+                    bind_stride = 4 if form == POSE_INDEX else 32
+            if dst is None:
+                dst = self.buffer(nbytes=max(16, (int(dst_first) + int(n)) * 96))
+            self._chk(_lib.gs4d_pose_records(self._h, int(src), int(n), int(xf), int(m), int(bind), int(form), int(bind_stride), int(dst), int(dst_first)))
+        finally:
+            for b in temps:
+                self.delete(b)
         return dst
 
     # a frame of a clip as a 3D set: the records baked at one time (DESIGN.md §4)

@@ -1657,6 +1657,25 @@ int gs4d_transform_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf xf, siz
     });
 }
 
+// ---- one affine map per record, indexed or blended ----
+int gs4d_pose_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf bind, uint32_t form, size_t bind_stride, gs4d_buf dst, size_t dst_first) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "pose_records";
+    if (n > 0xFFFFFFFFull || m > 0xFFFFFFFFull || dst_first > 0xFFFFFFFFull || (uint64_t)n + dst_first > 0xFFFFFFFFull) return refuse(c, fn, "n, m, dst_first or dst_first + n above 2^32 - 1");
+    if (form != GS4D_POSE_INDEX && form != GS4D_POSE_BLEND4) return refuse(c, fn, "form is neither GS4D_POSE_INDEX nor GS4D_POSE_BLEND4");
+    if (form == GS4D_POSE_INDEX ? (bind_stride < 4 || bind_stride % 4 != 0) : (bind_stride < 32 || bind_stride % 16 != 0))
+        return refuse(c, fn, form == GS4D_POSE_INDEX ? "bind_stride must be a multiple of 4, at least 4" : "bind_stride must be a multiple of 16, at least 32");
+    Operands ops{ { "src", src, false, 96, n, OP_READ }, { "xf", xf, false, sizeof(gs4d_affine4), m, OP_READ }, { "bind", bind, false, bind_stride, n, OP_READ },
+                  { "dst", dst, false, 96, (uint64_t)dst_first + n, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (n == 0) return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_pose_records(L.s, ops.ptr(src), n, (const gs4d_affine4*)ops.ptr(xf), m, ops.ptr(bind), form, bind_stride, (char*)ops.ptr(dst) + dst_first * 96));
+        return (int)GS4D_OK;
+    });
+}
+
 // ---- a 4D set baked at one time ----
 int gs4d_slice_records(gs4d_ctx* c, gs4d_buf src, size_t n, const gs4d_slice* q, gs4d_buf dst, size_t dst_first) {
     if (!c) return GS4D_E_INVALID;

@@ -505,6 +505,15 @@ hipError_t launch_build_records(hipStream_t st, int form, const BuildParams& p, 
 constexpr uint32_t TRANSFORM_TILE = 256;
 hipError_t launch_transform_records(hipStream_t st, const void* src, size_t n, const gs4d_affine4* xf, size_t m, void* dst);
 
+// ---- pose.hip ----
+// gs4d_pose_records (gs4d.h): record i of dst <- record i of the n 96-byte records of src under the row(s) of the m rows of xf that row
+// i of bind (at byte i * bind_stride; form and stride validated) names, or copied.  One workgroup per POSE_TILE records; a table of at most
+// POSE_LDS_ROWS rows is copied into LDS by every workgroup, a larger one is read from global memory.  n, m <= 0xFFFFFFFF; nothing else of dst is touched.
+constexpr uint32_t POSE_TILE = 256;
+constexpr uint32_t POSE_LDS_ROWS = 128;
+hipError_t launch_pose_records(hipStream_t st, const void* src, size_t n, const gs4d_affine4* xf, size_t m, const void* bind, uint32_t form,
+                               size_t bind_stride, void* dst);
+
 // ---- slice.hip ----
 // gs4d_slice_records (gs4d.h): record i of dst <- record i of the n 96-byte records of src conditioned at q.t (q validated).
 // One workgroup per SLICE_TILE records; n <= 0xFFFFFFFF; nothing else of dst is touched.

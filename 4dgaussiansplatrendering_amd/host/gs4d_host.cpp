@@ -24,6 +24,7 @@
 #include <vector>
 #include "../csrc/build_record.h"
 #include "../csrc/transform_record.h"
+#include "../csrc/pose_record.h"
 #include "../csrc/slice_record.h"
 #include "../csrc/centre_query.h"
 #include "../csrc/measure_record.h"
@@ -343,6 +344,28 @@ void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const float* q0_
 // The definition of gs4d_transform_records (gs4d.h) is csrc/transform_record.h: mean L p + o, covariance (L Sigma) L^T as two full mat4 products, rgba copied
 void gs4d_host_transform_records(size_t n, const float* rec, const gs4d_affine4* xf, float* out) {
     for (size_t i = 0; i < n; ++i) gs4d_transform::record(xf->l, xf->o, rec + 24 * i, out + 24 * i);
+}
+
+// The definition of gs4d_pose_records (gs4d.h) is csrc/pose_record.h: the record under the row its bind row names, under the blend of up to four, or
+// copied.  A form or a stride the device call would refuse writes nothing.
+void gs4d_host_pose_records(size_t n, const float* rec, const gs4d_affine4* xf, size_t m, const void* bind, uint32_t form, size_t bind_stride, float* out) {
+    if (form == GS4D_POSE_INDEX ? (bind_stride < 4 || bind_stride % 4 != 0) : form == GS4D_POSE_BLEND4 ? (bind_stride < 32 || bind_stride % 16 != 0) : true) return;
+    const unsigned int rows_m = m > 0xFFFFFFFFull ? 0xFFFFFFFFu : (unsigned int)m;
+    const auto rows = [xf](unsigned int j, float r[20]) { std::memcpy(r, &xf[j], sizeof(gs4d_affine4)); };
+    for (size_t i = 0; i < n; ++i) {
+        const unsigned char* const row = (const unsigned char*)bind + i * bind_stride;
+        if (form == GS4D_POSE_INDEX) {
+            uint32_t j;
+            std::memcpy(&j, row, 4);
+            gs4d_pose::index(rows, rows_m, j, rec + 24 * i, out + 24 * i);
+        } else {
+            unsigned int j[4];
+            float w[4];
+            std::memcpy(j, row, 16);
+            std::memcpy(w, row + 16, 16);
+            gs4d_pose::blend(rows, rows_m, j, w, rec + 24 * i, out + 24 * i);
+        }
+    }
 }
 
 // The definition of gs4d_slice_records (gs4d.h) is csrc/slice_record.h: the draw's time conditioning at q->t, baked into the record

@@ -15,13 +15,13 @@ endif
 # keygen/sort and preprocess must round exactly like the CPU expressions they are checked against
 STRICT   := -ffp-contract=off
 
-# the build mode is a prerequisite of every object: switching between `make lib`, `make lib TUNING=1`, `make lib COUNT_IDS_PLAIN=1`, `make lib BUILD_PLAIN=1`, `make lib TRANSFORM_STAGED_LOAD=1` and `make lib XFSEL_PLAIN=1` rebuilds all of them
-FLAGSTAMP := $(CSRC)/.flags.$(if $(TUNING),tuning,release)$(if $(COUNT_IDS_PLAIN),-plain)$(if $(BUILD_PLAIN),-buildplain)$(if $(TRANSFORM_STAGED_LOAD),-transformstagedload)$(if $(XFSEL_PLAIN),-xfselplain)
+# the build mode is a prerequisite of every object: switching between `make lib`, `make lib TUNING=1`, `make lib COUNT_IDS_PLAIN=1`, `make lib BUILD_PLAIN=1`, `make lib TRANSFORM_STAGED_LOAD=1`, `make lib XFSEL_PLAIN=1`, `make lib POSE_GLOBAL_TABLE=1` and `make lib POSE_WALK=4` rebuilds all of them
+FLAGSTAMP := $(CSRC)/.flags.$(if $(TUNING),tuning,release)$(if $(COUNT_IDS_PLAIN),-plain)$(if $(BUILD_PLAIN),-buildplain)$(if $(TRANSFORM_STAGED_LOAD),-transformstagedload)$(if $(XFSEL_PLAIN),-xfselplain)$(if $(POSE_GLOBAL_TABLE),-poseglobaltable)$(if $(POSE_WALK),-posewalk$(POSE_WALK))
 $(FLAGSTAMP):
 	rm -f $(CSRC)/.flags.*
 	touch $@
 
-OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
+OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/pose.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
 
 .PHONY: all lib oracle ref refscene refdraw refgl clean demo sweep
 all: lib oracle demo sweep
@@ -82,6 +82,10 @@ $(CSRC)/transform.o: $(CSRC)/transform.hip $(CSRC)/transform_record.h $(HD) $(CS
 # make XFSEL_PLAIN=1: gs4d_transform_selected with every selected thread storing its own record, without the LDS staging and the wave masks (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/transform_selected.o: $(CSRC)/transform_selected.hip $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(XFSEL_PLAIN),-DGS4D_XFSEL_PLAIN) -c $< -o $@
+# pose_record.h is the one text of gs4d_pose_records' definition, on top of transform_record.h: the kernel and the host library compile it (tests/pose_record_check.cpp compiles it too)
+# make POSE_GLOBAL_TABLE=1: gs4d_pose_records with every thread loading its table rows from global memory for every m, without the workgroup's copy of a small table in LDS; make POSE_WALK=4: a workgroup with the table in LDS takes 4 tiles instead of one (the measurements of DESIGN.md §4; never the shipped build)
+$(CSRC)/pose.o: $(CSRC)/pose.hip $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(POSE_GLOBAL_TABLE),-DGS4D_POSE_GLOBAL_TABLE) $(if $(POSE_WALK),-DGS4D_POSE_WALK=$(POSE_WALK)) -c $< -o $@
 # slice_record.h is the one text of gs4d_slice_records' definition: the kernel and the host library compile it; slice.o is built with the flags of preprocess.o, so its expf is the draw's
 $(CSRC)/slice.o: $(CSRC)/slice.hip $(CSRC)/slice_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
@@ -92,7 +96,7 @@ $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Make
 $(CSRC)/gs4d_api.o: $(CSRC)/operands.h
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gs4d_internal.h $(CSRC)/composite_common.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/transform_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
+$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/transform_record.h $(CSRC)/pose_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -fvisibility=hidden $(STRICT) -x c++ -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -586,6 +586,47 @@ typedef struct gs4d_affine4 {
 } gs4d_affine4;         /* 80 bytes */
 GS4D_API int gs4d_transform_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf dst, size_t dst_first);
 
+/* ---- one transform per record: a set posed by a table of maps, indexed or blended (no reference counterpart) ----
+ * gs4d_transform_records applies ONE map to every record it touches.  An articulated avatar whose splats are bound to the joints of a skeleton, a
+ * scene of rigid objects that each move on their own (one object id per record) and a particle system need a per-record choice among m maps, every
+ * frame.  gs4d_pose_records is that call: record dst_first + i of dst is written from record i < n of src, under the map that row i of bind — which
+ * starts at byte i * bind_stride of the bind buffer — takes from the m rows of xf (gs4d_affine4, 80 bytes).  It writes no other byte of dst and no
+ * byte of src, xf or bind.  src is the set in its REST pose and is never changed: every frame poses it anew into dst.
+ *
+ * The definition (gs4d_host_pose_records is this text).  All arithmetic is float32, round to nearest, no contraction, full products, in the order
+ * the parentheses give; record(l, o, in) stands for the four lines of gs4d_transform_records' definition with the row (l, o).
+ *   GS4D_POSE_INDEX   bind_stride is a multiple of 4, at least 4; the first uint32 of the row is j.
+ *       j <  m:  the record is record(xf[j].l, xf[j].o, in) — the bits of gs4d_host_transform_records with that row.
+ *       j >= m  (GS4D_ID_NONE included):  the 96 bytes are copied, NaN payloads and all.
+ *       A uint32 buffer of object ids is a bind table as it is (bind_stride 4); so is a word at the start of the rows of a wider per-record table.
+ *   GS4D_POSE_BLEND4  bind_stride is a multiple of 16, at least 32 (gs4d_gather_records and the compactions can carry the table); the row is
+ *       uint32 j[4] followed by float w[4].  Slot k = 0..3 takes part iff j[k] < m, whatever w[k] is.  For each of the 20 floats e of a row
+ *       (l[0..15], o[0..3]), going through the slots in order:
+ *           the first slot that takes part:        a[e] = w[k] * xf[j[k]][e]
+ *           every later slot that takes part:      a[e] = a[e] + (w[k] * xf[j[k]][e])
+ *       and the record is record(a.l, a.o, in): linear blend skinning.  The weights are data and are not normalised; a weight of 0 is a full product
+ *       (a NaN row under weight 0 gives NaN — leave a slot out with j[k] = GS4D_ID_NONE, not with a zero weight).  If no slot takes part the 96 bytes
+ *       are copied as above.
+ *       Consequence: a row with one participating slot of weight 1.0f gives the bits of GS4D_POSE_INDEX with that j (1.0f * x is x, -0 included).
+ * The records have the bits of the host function, except that a word that is a NaN on both sides in a transformed (not copied) record may differ in
+ * sign and payload (the rule of gs4d_transform_records).  Nothing depends on the order in which anything runs on the device.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: n, m, dst_first or dst_first + n above 0xFFFFFFFF; an unknown form; a bind_stride that
+ * breaks the form's rule; a name that is not a live buffer; any two of the four buffers being the same; src smaller than 96 n bytes; xf smaller than
+ * 80 m bytes; bind smaller than n * bind_stride bytes; dst holding fewer than dst_first + n records.  n == 0 with otherwise valid arguments is a
+ * no-op; m == 0 is valid: every record is copied.  The rows of xf and bind are data.
+ *
+ * Ordering, exactly that of gs4d_transform_records: a queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first; draws
+ * that may still have to be run again from dst are settled; the kernel is queued on the current frame lane, the call returns at once and starts no
+ * new frame; src, xf and bind are buffers the call reads (a gs4d_buffer_subdata of the next frame's xf orders itself behind it), dst one it writes.
+ * It counts as a full write of dst: the next draw or gs4d_keygen rebuilds the SoA shadow once.  Per frame: (shade) -> pose -> gs4d_keygen ->
+ * gs4d_sort_pairs -> draw.  The notes of gs4d_transform_records on time spans, the SH table (not rotated) and the depth keys hold per record.
+ * Out of scope: dual-quaternion blending, more than 4 influences, an in-place pose (src == dst), dense ids from gs4d_label_components labels. */
+#define GS4D_POSE_INDEX  0u   /* bind row: one uint32 j                                  */
+#define GS4D_POSE_BLEND4 1u   /* bind row: uint32 j[4], float w[4]  (32 bytes)           */
+GS4D_API int gs4d_pose_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf bind, uint32_t form, size_t bind_stride,
+                               gs4d_buf dst, size_t dst_first);
+
 /* ---- a frame of a clip as a 3D set: the records baked at one time (no reference counterpart) ----
  * The draws condition a 4D record at uTime — the time opacity, the conditional centre, the conditional 3x3 covariance — inside the projection
  * kernel, every frame.  gs4d_slice_records does that once and writes the result as records: the 3D set that the 4D set IS at time q->t, to be drawn
@@ -1200,6 +1241,11 @@ GS4D_API void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const f
 /* The definition of gs4d_transform_records for one transform: out24 record i = records24 record i under *xf, i < n (the text above the declaration
  * of gs4d_transform_records).  out24 must not overlap records24. */
 GS4D_API void gs4d_host_transform_records(size_t n, const float* records24, const gs4d_affine4* xf, float* out24);
+/* The definition of gs4d_pose_records: out24 record i = records24 record i under what row i of bind (at byte i * bind_stride) takes from the m rows
+ * of xf, i < n (the text above the declaration of gs4d_pose_records).  out24 must not overlap records24.  An unknown form, or a bind_stride that
+ * breaks the form's rule, writes nothing. */
+GS4D_API void gs4d_host_pose_records(size_t n, const float* records24, const gs4d_affine4* xf, size_t m, const void* bind, uint32_t form,
+                                     size_t bind_stride, float* out24);
 /* The definition of gs4d_slice_records: out24 record i = records24 record i conditioned at q->t, i < n (the text above the declaration of
  * gs4d_slice_records; expf is the C library's).  out24 must not overlap records24.  A query the device call would refuse is evaluated as it stands. */
 GS4D_API void gs4d_host_slice_records(size_t n, const float* records24, const gs4d_slice* q, float* out24);
