@@ -116,6 +116,8 @@ def _load():
         "gs4d_label_components": (i32, [vp, u32, sz, vp, u32, vp, u32, u32]),
         "gs4d_count_labels": (i32, [vp, u32, sz, u32, vp, u32]),
         "gs4d_nearest_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32, sz, u32]),
+        "gs4d_cell_labels": (i32, [vp, u32, sz, vp, u32]),
+        "gs4d_merge_records": (i32, [vp, u32, sz, u32, vp, u32, vp, u32, u32, u32, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -151,6 +153,8 @@ def _load():
         "gs4d_host_label_components": (None, [sz, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_count_labels": (None, [sz, vp, vp, vp, vp]),
         "gs4d_host_nearest_neighbours": (None, [sz, vp, vp, vp, vp, vp, sz, vp]),
+        "gs4d_host_cell_labels": (None, [sz, vp, vp, vp]),
+        "gs4d_host_merge_records": (None, [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_frame_box": (None, [vp, vp, vp, f32, i32, i32, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
@@ -860,6 +864,75 @@ def nearest_neighbours_host(records, radius=None, k=3, t=0.0, source=None, skip_
     return ht, st
 
 
+class CellGrid(C.Structure):
+    """gs4d_cell_grid (include/gs4d.h): the low corner, the cell edges and the cell counts of a gs4d_cell_labels call along x, y, z, t; 64 bytes."""
+    _fields_ = [("lo", C.c_float * 4), ("edge", C.c_float * 4), ("dims", C.c_uint32 * 4), ("reserved", C.c_uint32 * 4)]
+
+
+class MergeQuery(C.Structure):
+    """gs4d_merge_query (include/gs4d.h): the alpha clamp of a gs4d_merge_records call; 16 bytes."""
+    _fields_ = [("alpha_max", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+MERGE_GROUP = np.dtype([("label", "<u4"), ("size", "<u4"), ("first", "<u4"), ("reserved", "<u4")])          # gs4d_merge_group
+MERGE_COUNT = np.dtype([("groups", "<u4"), ("written", "<u4"), ("members", "<u4"), ("left_out", "<u4")])   # gs4d_merge_count
+
+
+def cell_grid(lo, edge, dims):
+    """one gs4d_cell_grid (CellGrid): lo, edge and dims of up to four entries (x, y, z, t); a missing axis gets lo 0, edge 1 and ONE cell, so three
+    entries give the grid of a static or sliced set.  edge may be one number for every axis given."""
+    lo = [float(v) for v in np.atleast_1d(lo)]
+    dims = [int(v) for v in np.atleast_1d(dims)]
+    edge = [float(v) for v in np.atleast_1d(edge)]
+    if len(edge) == 1:
+        edge = edge * len(dims)
+    if not (len(lo) == len(edge) == len(dims) <= 4):
+        raise ValueError("cell_grid: lo, edge and dims must have the same number of entries, at most 4")
+    g = CellGrid()
+    for a in range(4):
+        g.lo[a], g.edge[a], g.dims[a] = (lo[a], edge[a], dims[a]) if a < len(dims) else (0.0, 1.0, 1)
+    return g
+
+
+def cell_labels_host(records, grid):
+    """gs4d_host_cell_labels, the definition of Context.cell_labels: uint32 [n], the cell of every record of records [n, 24] in `grid` (a CellGrid).
+    A grid the device call would refuse gives zeros."""
+    rec = _f32(records).reshape(-1, 24)
+    labels = np.zeros(rec.shape[0], np.uint32)
+    _lib.gs4d_host_cell_labels(rec.shape[0], _ptr(rec), C.byref(grid), _ptr(labels))
+    return labels
+
+
+def merge_query(alpha_max=1.0):
+    """one gs4d_merge_query (MergeQuery)"""
+    q = MergeQuery()
+    q.alpha_max = float(alpha_max)
+    return q
+
+
+def merge_records_host(records, labels, alpha_max=1.0, stats=None, query=None, **rule):
+    """gs4d_host_merge_records, the definition of Context.merge_records: (out float32 [n, 24] whose first `groups` rows are the merged records and
+    the rest zeros, groups MERGE_GROUP [n] likewise, member_group uint32 [n], count: one MERGE_COUNT row) of records [n, 24] under labels uint32
+    [n].  stats: a RECORD_STAT array of n rows (the rule keywords of compact_records let a record be a member by it) or None: every record; query:
+    a MergeQuery instead of alpha_max.  A call the device would refuse gives zeros."""
+    rec = _f32(records).reshape(-1, 24)
+    n = rec.shape[0]
+    lab = np.ascontiguousarray(labels, dtype=np.uint32)
+    if lab.shape != (n,):
+        raise ValueError("merge_records_host: labels must be n uint32 words")
+    if stats is None and rule:
+        raise TypeError("merge_records_host: a rule without stats")
+    st = None if stats is None else np.ascontiguousarray(stats)
+    if st is not None and (st.dtype.itemsize != 16 or st.ndim != 1 or st.shape[0] < n):
+        raise ValueError("merge_records_host: stats must be at least n rows of 16 bytes")
+    q = merge_query(alpha_max) if query is None else query
+    k = _keep_rule(**rule)
+    out, groups, member_group, count = np.zeros((n, 24), np.float32), np.zeros(n, MERGE_GROUP), np.zeros(n, np.uint32), np.zeros(1, MERGE_COUNT)
+    _lib.gs4d_host_merge_records(n, _ptr(rec), _ptr(lab), C.byref(q), _ptr(st) if st is not None else None, _ptr(k) if st is not None else None,
+                                 _ptr(out), _ptr(groups), _ptr(member_group), _ptr(count))
+    return out, groups, member_group, count[0]
+
+
 def hits_of(table, k):
     """the (n, k) HIT view of a hit table given as uint8 [n, hit_stride] (nearest_neighbours_host's, or Context.read of the buffer)"""
     t = np.ascontiguousarray(table, np.uint8)
@@ -1381,6 +1454,49 @@ class Context:
         centre); blocks until its kernels have finished."""
         raw = self.read(out, np.uint8, C.sizeof(Measure))
         return Measure.from_buffer_copy(raw.tobytes()).as_dict()
+
+    # a coarser level of detail: a label per record from a cell grid, one moment-matched record per labelled group (DESIGN.md §4)
+    def cell_labels(self, data, n, grid, labels=None):
+        """gs4d_cell_labels: labels[i] (a buffer of n uint32; a new one if None) = the cell of the rest mean of record i < n of `data` in `grid` (a
+        CellGrid: cell_grid), ID_NONE where a coordinate that is looked at is a NaN.  With the bits of cell_labels_host.  Asynchronous; returns
+        `labels`."""
+        if labels is None:
+            labels = self.buffer(nbytes=max(16, 4 * int(n)))
+        self._chk(_lib.gs4d_cell_labels(self._h, int(data), int(n), C.byref(grid), int(labels)))
+        return labels
+
+    def merge_records(self, data, n, labels, alpha_max=1.0, stats=None, dst=None, groups=None, member_group=None, count=None, query=None, **rule):
+        """gs4d_merge_records: one record per group of members of equal label among the first n 96-byte records of `data` — the group's mass-weighted
+        mean, covariance and colour, alpha from the preserved mass clamped at alpha_max — into `dst` (a new buffer of n records if None), in
+        ascending label.  labels: a buffer of n uint32 (cell_labels, label_components; ID_NONE: no member).  stats: a record_stats buffer whose row i
+        lets record i be a member by compact_records' rule keywords (None: every record, and no rule).  groups: a buffer of MERGE_GROUP rows
+        {label, size, first} or None; member_group: a buffer of n uint32 (the group of every record, ID_NONE for a non-member) or None; count: a
+        buffer of 16 bytes (a new one if None) that receives the MERGE_COUNT.  No slot past what dst and groups hold is written.  With the bits of
+        merge_records_host.  A full write of dst: the next draw rebuilds its SoA shadow.  Asynchronous; returns (dst, count)."""
+        if stats is None and rule:
+            raise TypeError("merge_records: a rule without stats")
+        q = merge_query(alpha_max) if query is None else query
+        k = _keep_rule(**rule) if stats is not None else None
+        if dst is None:
+            dst = self.buffer(nbytes=max(16, 96 * int(n)))
+        if count is None:
+            count = self.buffer(nbytes=MERGE_COUNT.itemsize)
+        self._chk(_lib.gs4d_merge_records(self._h, int(data), int(n), int(labels), C.byref(q), int(stats or 0), _ptr(k) if k is not None else None,
+                                          int(dst), int(groups or 0), int(member_group or 0), int(count)))
+        return dst, count
+
+    def read_merge_count(self, count):
+        """The MERGE_COUNT row (groups, written, members, left_out) of a merge_records call; blocks until its kernels have finished."""
+        return self.read(count, np.uint32, 4).view(MERGE_COUNT)[0]
+
+    def lod(self, data, n, grid, alpha_max=1.0):
+        """A coarser level of detail of the first n records of `data`: cell_labels in `grid`, then merge_records over those labels.  Asynchronous;
+        returns (dst, count) — read_merge_count(count).written records of dst are the set to draw."""
+        labels = self.cell_labels(data, n, grid)
+        try:
+            return self.merge_records(data, n, labels, alpha_max=alpha_max)
+        finally:
+            self.delete(labels)
 
     # records relative to each other: the sources within a radius of each record (DESIGN.md §4)
     def count_neighbours(self, stats, n, data, radius=None, t=0.0, cap=0xFFFFFFFF, source=None, skip_hidden=False, skip_dead=False, count_self=False,

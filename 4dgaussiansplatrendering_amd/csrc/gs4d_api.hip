@@ -17,6 +17,7 @@
 // is deferred to the next call that could observe the draw (see resolve_pending).
 #include "gs4d_internal.h"
 #include "operands.h"
+#include "merge_record.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -2165,6 +2166,68 @@ int gs4d_nearest_neighbours(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_nea
     return grid_query(c, "nearest_neighbours", g, n, data, source, rule, o,
         [&](Lane& L, const void* records, const gs4d_record_stat* rows, const KeepRule& k, void* slots, gs4d_record_stat* table) {
             HIPCHK(c, launch_nearest_neighbours(L.s, L.pair_sort, records, n, q, rows, k, L.neighbour_scratch, slots, hit_stride, table));
+            return (int)GS4D_OK;
+        });
+}
+
+// ---- a label per record from a 4D cell grid ----
+int gs4d_cell_labels(gs4d_ctx* c, gs4d_buf data, size_t n, const gs4d_cell_grid* grid, gs4d_buf labels) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "cell_labels";
+    if (!grid) return refuse(c, fn, "grid == NULL");
+    const gs4d_cell_grid g = *grid;
+    if (!gs4d_merge::grid_ok(g.edge, g.dims, g.reserved))
+        return refuse(c, fn, "dims must be 1 .. 65536 with a product of at most 0xFFFFFFFE, edge finite and > 0 where dims > 1, reserved 0");
+    if (n > 0xFFFFFFFFull) return refuse(c, fn, "more than 2^32 - 1 records");
+    // data is read (the 96-byte records, never a shadow: a reader leaves `version` alone), labels is written
+    Operands ops{ { "data", data, false, 96, n, OP_READ }, { "labels", labels, false, sizeof(uint32_t), n, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (n == 0) return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_cell_labels(L.s, ops.ptr(data), n, g, (uint32_t*)ops.ptr(labels)));
+        return (int)GS4D_OK;
+    });
+}
+
+// ---- one moment-matched record per labelled group ----
+int gs4d_merge_records(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf labels, const gs4d_merge_query* query, gs4d_buf stats, const gs4d_keep_rule* rule,
+                       gs4d_buf dst, gs4d_buf groups, gs4d_buf member_group, gs4d_buf count) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "merge_records";
+    if (!query) return refuse(c, fn, "q == NULL");
+    const gs4d_merge_query q = *query;
+    if (!(gs4d_merge::finite(q.alpha_max) && q.alpha_max > 0.0f)) return refuse(c, fn, "alpha_max must be finite and > 0");
+    if (q.flags != 0u || q.reserved[0] != 0u || q.reserved[1] != 0u) return refuse(c, fn, "flags or a reserved field of the query is not 0");
+    if (n >= 0xFFFFFFFFull) return refuse(c, fn, "the sort takes 2^32 - 2 records at most");
+    if ((stats != 0) != (rule != nullptr)) return refuse(c, fn, "stats and rule are given together or not at all");
+    KeepRule k;
+    if (!keep_rule_of(rule, k)) return refuse(c, fn, "unknown flag or non-zero reserved field in the rule");
+    // data, labels and the table are read (gs4d_measure_records' data and table); dst is written as gs4d_transform_records writes its own (a full
+    // write: the next draw repacks the shadow once), and holds what it holds (cap), like groups; member_group and count are written whole.
+    Operands ops{ { "data", data, false, 96, n, OP_READ },
+                  { "labels", labels, false, sizeof(uint32_t), n, OP_READ },
+                  { "stats", stats, true, sizeof(gs4d_record_stat), n, OP_READ | OP_SETTLE | OP_SCAN },
+                  { "dst", dst, false, 96, 0, OP_WRITE },
+                  { "groups", groups, true, sizeof(gs4d_merge_group), 0, OP_WRITE },
+                  { "member_group", member_group, true, sizeof(uint32_t), n, OP_WRITE },
+                  { "count", count, false, 1, sizeof(gs4d_merge_count), OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    // slots the outputs hold: no slot >= cap is ever written
+    uint32_t cap = (uint32_t)std::min<size_t>(0xFFFFFFFFu, ops.buffer(dst)->bytes / 96);
+    if (Buffer* G = ops.buffer(groups)) cap = (uint32_t)std::min<size_t>(cap, G->bytes / sizeof(gs4d_merge_group));
+    return queue_operands(c, ops,
+        [&](Lane& L) {
+            if (n == 0) return (int)GS4D_OK;
+            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, merge_scratch_words(n)));
+            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));      // (the tile sort's scratch, as gs4d_spatial_order: a histogram a queued keygen has left in depth_sort stays where it is)
+            return (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            HIPCHK(c, launch_merge_records(L.s, L.pair_sort, ops.ptr(data), n, (const uint32_t*)ops.ptr(labels), q.alpha_max, (const gs4d_record_stat*)ops.ptr(stats), k,
+                                           L.neighbour_scratch, ops.ptr(dst), (gs4d_merge_group*)ops.ptr(groups), (uint32_t*)ops.ptr(member_group), cap,
+                                           (gs4d_merge_count*)ops.ptr(count)));
             return (int)GS4D_OK;
         });
 }

@@ -614,4 +614,21 @@ inline size_t measure_scratch_words() { return (size_t)MEASURE_GROUPS * MEASURE_
 hipError_t launch_measure_records(hipStream_t st, const void* records, size_t n, float t, uint32_t flags, const gs4d_record_stat* stats, const KeepRule& rule,
                                   uint32_t* scratch, gs4d_measure* out);
 
+// ---- merge.hip ----
+// gs4d_cell_labels (gs4d.h): labels[i] <- the cell of record i < n of the 96-byte records in `grid` (validated).  One launch; n == 0: none.
+hipError_t launch_cell_labels(hipStream_t st, const void* records, size_t n, const gs4d_cell_grid& grid, uint32_t* labels);
+// gs4d_merge_records (gs4d.h): one record per group of members with one label — the key kernel, the stable sort of the identity by key
+// (`sort`: the lane's pair_sort, reserved for n), the count / scan / head kernels over the sorted keys and the group kernel, all on `st`; no workgroup
+// waits for another.  alpha_max: validated; stats: the table whose row i lets record i be a member by `rule` (keep_row), or null: every record;
+// groups, member_group: null: none; cap: slots dst and groups hold (no slot >= cap is written); *count always receives the gs4d_merge_count
+// (n == 0: zeros, one launch).  n <= 0xFFFFFFFE.  Nothing but those outputs, the n words of member_group and the scratch is written.
+constexpr uint32_t MERGE_TILE = 2048;            // sorted keys per workgroup of the counting and the head kernel (8 per thread)
+inline size_t merge_tiles(size_t n) { return (n + MERGE_TILE - 1) / MERGE_TILE; }
+// scratch: merge_scratch_words(n) words (the lane's neighbour scratch): keys, sorted indices and run starts of n words each (each rounded up to 16
+// bytes), one word per tile (rounded up likewise), the state block {groups, members, 0, 0}
+inline size_t merge_scratch_words(size_t n) { return 3 * ((n + 3) & ~(size_t)3) + ((merge_tiles(n) + 3) & ~(size_t)3) + 4; }
+hipError_t launch_merge_records(hipStream_t st, SortScratch& sort, const void* records, size_t n, const uint32_t* labels, float alpha_max,
+                                const gs4d_record_stat* stats, const KeepRule& rule, uint32_t* scratch, void* dst, gs4d_merge_group* groups,
+                                uint32_t* member_group, uint32_t cap, gs4d_merge_count* count);
+
 } // namespace gs4d

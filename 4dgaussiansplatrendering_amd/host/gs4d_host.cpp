@@ -28,6 +28,7 @@
 #include "../csrc/slice_record.h"
 #include "../csrc/centre_query.h"
 #include "../csrc/measure_record.h"
+#include "../csrc/merge_record.h"
 #include "../csrc/neighbour_query.h"
 #include "../csrc/component_union.h"
 #include "../csrc/nearest_query.h"
@@ -541,6 +542,54 @@ void gs4d_host_count_labels(size_t n, const uint32_t* labels, const gs4d_record_
         if (labels[j] < n && keeps(seeds[j], rule)) hit[labels[j]] = 1;
     for (size_t i = 0; i < n; ++i)
         if (labels[i] < n && hit[labels[i]]) add_fragments(stats[i], 1u, ONE_BITS);
+}
+
+// The definition of gs4d_cell_labels (gs4d.h) is cell_label of csrc/merge_record.h
+void gs4d_host_cell_labels(size_t n, const float* rec, const gs4d_cell_grid* grid, uint32_t* labels) {
+    if (!grid || !gs4d_merge::grid_ok(grid->edge, grid->dims, grid->reserved)) return;
+    for (size_t i = 0; i < n; ++i) labels[i] = gs4d_merge::cell_label(grid->lo, grid->edge, grid->dims, rec + 24 * i);
+}
+
+// The definition of gs4d_merge_records (gs4d.h) over the text of csrc/merge_record.h, which the kernels compile too (this file is built with
+// -ffp-contract=off): the members, a stable sort of them by label, and per run of equal labels either the member itself or the eight interleaved
+// slots, their fixed tree and the moments.  One thread, one loop.
+void gs4d_host_merge_records(size_t n, const float* rec, const uint32_t* labels, const gs4d_merge_query* q, const gs4d_record_stat* stats,
+                             const gs4d_keep_rule* rule, float* out, gs4d_merge_group* groups, uint32_t* member_group, gs4d_merge_count* count) {
+    namespace mg = gs4d_merge;
+    if (!q || !(mg::finite(q->alpha_max) && q->alpha_max > 0.0f) || q->flags != 0u || q->reserved[0] != 0u || q->reserved[1] != 0u) return;
+    if (n >= 0xFFFFFFFFull || (stats != nullptr) != (rule != nullptr) || (rule && !rule_ok(rule))) return;
+    std::vector<uint32_t> member;
+    for (size_t i = 0; i < n; ++i) {
+        float a;
+        const bool is = labels[i] != mg::NONE && (!stats || keeps(stats[i], rule)) && mg::member_mass(rec + 24 * i, a);
+        if (is) member.push_back((uint32_t)i);
+        if (member_group) member_group[i] = mg::NONE;
+    }
+    std::stable_sort(member.begin(), member.end(), [labels](uint32_t x, uint32_t y) { return labels[x] < labels[y]; });
+    uint32_t g = 0;
+    for (size_t first = 0, end; first < member.size(); first = end, ++g) {
+        const uint32_t label = labels[member[first]];
+        for (end = first + 1; end < member.size() && labels[member[end]] == label; ++end) {}
+        float* const o = out + 24 * (size_t)g;
+        if (end - first == 1) {
+            std::memcpy(o, rec + 24 * (size_t)member[first], 96);
+        } else {
+            const float* const origin = rec + 24 * (size_t)member[first];
+            mg::Sums slot[mg::SLOTS];
+            for (int s = 0; s < mg::SLOTS; ++s) mg::clear(slot[s]);
+            for (size_t k = first; k < end; ++k) {
+                const float* const r = rec + 24 * (size_t)member[k];
+                float a;
+                (void)mg::member_mass(r, a);
+                mg::add_member(slot[(k - first) % mg::SLOTS], origin, a, r);
+            }
+            mg::join_slots(slot);
+            mg::finish(slot[0], origin, q->alpha_max, o);
+        }
+        if (groups) groups[g] = gs4d_merge_group{ label, (uint32_t)(end - first), member[first], 0u };
+        if (member_group) for (size_t k = first; k < end; ++k) member_group[member[k]] = g;
+    }
+    *count = gs4d_merge_count{ g, g, (uint32_t)member.size(), (uint32_t)(n - member.size()) };
 }
 
 // The definition of gs4d_nearest_neighbours (gs4d.h): the brute-force double loop over the texts of csrc/neighbour_query.h and

@@ -1180,6 +1180,104 @@ GS4D_API int gs4d_nearest_neighbours(gs4d_ctx* ctx, gs4d_buf data, size_t n, con
                                      gs4d_buf source /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff source == 0 */,
                                      gs4d_buf hits, size_t hit_stride, gs4d_buf stats /* 0: hits only */);
 
+/* ---- a label per record from a 4D cell grid (no reference counterpart) ----
+ * gs4d_cell_labels writes labels[i], i < n: the cell of record i of the 96-byte records in data in a regular grid of space-time.  The cell of axis
+ * a (x, y, z, t) is taken from the record's REST mean, words 0..3: there is no time conditioning.  gs4d_host_cell_labels is this text as code.
+ *   An axis with dims[a] == 1 has cell 0; its coordinate, lo[a] and edge[a] are not looked at (a static or sliced set: dims[3] = 1).
+ *   Otherwise  g = (p - lo[a]) / edge[a]  in float32, the difference and the quotient each rounded on its own.
+ *       g a NaN:  the record's label is GS4D_ID_NONE, whatever the other axes give.
+ *       else      cell = g >= 0 ? (uint32_t)fminf(floorf(g), (float)(dims[a] - 1)) : 0 — the border cells take what lies outside.
+ *   label = ((c3 * dims[2] + c2) * dims[1] + c1) * dims[0] + c0.
+ * All n words are written and nothing else; data is only read, the 16-byte mean of each record.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: grid == NULL; a dims[a] of 0 or above 65536; a product of the four above 0xFFFFFFFE
+ * (every label is below GS4D_ID_NONE); an edge[a] that is not finite and > 0 on an axis with dims[a] > 1; a non-zero reserved word;
+ * n > 0xFFFFFFFF; data or labels not a live buffer, the same buffer, data smaller than 96 n bytes or labels smaller than 4 n bytes.  lo is data.
+ * n == 0 with otherwise valid arguments is a no-op.
+ *
+ * Ordering: data is read, labels is a kernel write of n words; a queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched
+ * first; one launch of one thread per record on the current frame lane; the call returns at once and starts no frame.  It reads the 96-byte
+ * records: it never builds, reads or invalidates a SoA shadow. */
+typedef struct gs4d_cell_grid {
+    float    lo[4];        /* the low corner of cell 0 along x, y, z, t                              */
+    float    edge[4];      /* the cell's edge along each axis; finite and > 0 where dims[a] > 1      */
+    uint32_t dims[4];      /* cells along each axis, 1 .. 65536; the product at most 0xFFFFFFFE      */
+    uint32_t reserved[4];  /* must be 0                                                              */
+} gs4d_cell_grid;          /* 64 bytes */
+GS4D_API int gs4d_cell_labels(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d_cell_grid* grid, gs4d_buf labels /* uint32[n] */);
+
+/* ---- one moment-matched record per labelled group: a coarser level of detail (no reference counterpart) ----
+ * Frame time follows the number of records.  gs4d_merge_records replaces the members of every group of equal label by ONE Gaussian with the group's
+ * first and second moments — the merge step of the level-of-detail hierarchies of 3DGS — and writes the smaller set.  The labels come from
+ * gs4d_cell_labels (a coarser set for what is far away), from gs4d_label_components ("collapse this clump into one splat") or from the caller.
+ * The result is inexact by design; the definition below is exact: gs4d_host_merge_records is this text as code, and the device gives its bits.
+ *
+ * Area-time and mass, float32, every product, difference and sum rounded on its own in the order the parentheses give, sqrtf correctly rounded.
+ * S(c,r) is float 8 + 4c + r of the record, Sxx = S(0,0), Syy = S(1,1), Szz = S(2,2), S44 = S(3,3):
+ *     e2 = ((Sxx*Syy - S(1,0)*S(0,1)) + (Sxx*Szz - S(2,0)*S(0,2))) + (Syy*Szz - S(2,1)*S(1,2))
+ *     area_time(rec) = sqrtf(S44 * e2)          mass(rec) = alpha * area_time(rec)          (alpha: float 7)
+ * e2 is the second elementary symmetric polynomial of the spatial block, a proxy of the mean projected area: a flat disc (one scale 0) has
+ * e2 > 0 where a determinant would give 0.  S44 is the time extent.  A needle (two scales 0) has no area: where its e2 cancels to <= 0 in
+ * float32 it has no mass and is no member.
+ *
+ * Member.  Record i < n is a member iff labels[i] != GS4D_ID_NONE; stats == 0 or row i of the gs4d_record_stat table `stats` passes `rule`
+ * (the predicate of gs4d_edit_colours); a_i = mass(rec_i) is finite and > 0; and words 0..6 and 8..23 are all finite.  Everything a member adds
+ * is finite: no NaN arises, and the outputs are compared bit for bit without an exemption.  A non-member is counted in left_out and appears
+ * nowhere in dst.
+ *
+ * Groups.  A group is the set of members with one label.  Groups are numbered g = 0, 1, ... in ascending label.  The members of a group are taken
+ * in ascending record index, k = 0, 1, ....
+ *
+ * A group of one member gives that member's 24 words as they are.
+ *
+ * A larger group accumulates in double, every operation rounded on its own, with the origin c = words 0..3 of member 0, d = (double)mu_k - (double)c
+ * (four components) and a = (double)a_k.  Member k adds into slot s = k mod 8:
+ *     W[s]       += a
+ *     M[s][r]    += a * d[r]                                       r = 0..3
+ *     Q[s][c][r] += a * ((double)S(c,r) + d[r] * d[c])             r <= c: the stored triangle, read from float 8 + 4c + r
+ *     C[s][j]    += a * (double)rgb[j]                             j = 0..2 (floats 4..6)
+ * The eight slots — an empty one is +0.0 — are always combined as ((0+1)+(2+3))+((4+5)+(6+7)), field by field.  Then
+ *     m[r] = M[r] / W                     mu_out[r] = (float)((double)c[r] + m[r])
+ *     S_out(c,r) = S_out(r,c) = (float)(Q[c][r] / W - m[r] * m[c])
+ *     rgb_out[j] = (float)(C[j] / W)
+ *     v = W / (double)area_time(out), taken on the output words just written
+ *     alpha_out = v < (double)alpha_max ? (float)v : alpha_max
+ * A zero or NaN area gives alpha_max.  Mass is preserved unless the clamp acts.  The eight interleaved slots with a fixed tree are what lets
+ * eight lanes share a group and still give the host's bits.  SH tables are not merged: groups and member_group carry rows along.
+ *
+ * Outputs.  Group g writes slot g of dst (96 bytes) and groups[g] = {label, size, first = its smallest member index, 0}.  member_group[i], i < n,
+ * is g for a member of group g and GS4D_ID_NONE for a non-member: true group numbers, also beyond `written`.  count always receives
+ * {groups, written = min(groups, capacity), members, left_out = n - members}, where capacity = min(dst bytes / 96, groups bytes / 16) over the
+ * outputs given.  Slots >= capacity are never written and keep their bytes, the rule of gs4d_compact_records.  n == 0 writes {0, 0, 0, 0}.  No
+ * byte of data, labels or stats is written.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: q == NULL; alpha_max not finite or not > 0; flags or a reserved word != 0;
+ * n > 0xFFFFFFFE (the sort takes 2^32 - 2 keys at most); exactly one of stats / rule given; a rule with an unknown flag or reserved != 0; data,
+ * labels, dst or count not a live buffer; stats, groups or member_group, when given, not a live buffer; data smaller than 96 n bytes, labels or
+ * member_group smaller than 4 n bytes, stats smaller than 16 n bytes, count smaller than 16 bytes; any two of the buffers being the same buffer.
+ *
+ * Ordering.  data, labels and stats are read, the table as gs4d_measure_records reads its own: draws that add to it, issued before the call on
+ * any frame lane, are settled first, and a draw issued afterwards that adds to it waits on the device until the kernels have read it.  dst is
+ * written as gs4d_transform_records writes its own: draws that may still have to be run again from it are settled, and the call counts as a full
+ * write — the next draw or gs4d_keygen rebuilds its SoA shadow once.  groups, member_group and count are kernel writes.  A queued gs4d_keygen /
+ * gs4d_sort_pairs that names one of the buffers is launched first.  The kernels are queued on the current frame lane; the call returns at once
+ * and starts no frame.  Read count with gs4d_buffer_read.
+ *
+ * Cost.  A key kernel, the library's stable 32-bit sort of the identity by key, a count / scan / scatter over the sorted keys, and a segmented
+ * reduction with eight lanes per group.  The lane keeps about 12 n bytes of scratch beside the sort's.  A group of a million
+ * members is walked by eight lanes: a documented corner.
+ * Out of scope: choosing a level per view or per cell at draw time; merging SH tables. */
+typedef struct gs4d_merge_query {
+    float    alpha_max;    /* the clamp of a merged record's alpha; finite and > 0                   */
+    uint32_t flags;        /* must be 0                                                              */
+    uint32_t reserved[2];  /* must be 0                                                              */
+} gs4d_merge_query;        /* 16 bytes */
+typedef struct gs4d_merge_group { uint32_t label, size, first, reserved; } gs4d_merge_group;       /* 16 bytes */
+typedef struct gs4d_merge_count { uint32_t groups, written, members, left_out; } gs4d_merge_count; /* 16 bytes */
+GS4D_API int gs4d_merge_records(gs4d_ctx* ctx, gs4d_buf data, size_t n, gs4d_buf labels, const gs4d_merge_query* q,
+                                gs4d_buf stats /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff stats == 0 */,
+                                gs4d_buf dst, gs4d_buf groups /* 0 ok */, gs4d_buf member_group /* 0 ok */, gs4d_buf count);
+
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
                                                                                       Each timed stage costs two event records in a timed frame (they break back-to-back kernel dispatch: ~2 us each on the device) */
@@ -1287,6 +1385,17 @@ GS4D_API void gs4d_host_label_components(size_t n, const float* records24, const
 /* The definition of gs4d_count_labels, in place on the n rows of stats.  rule == NULL, or one with an unknown flag or reserved != 0, changes nothing. */
 GS4D_API void gs4d_host_count_labels(size_t n, const uint32_t* labels, const gs4d_record_stat* seeds, const gs4d_keep_rule* rule,
                                      gs4d_record_stat* stats);
+/* The definition of gs4d_cell_labels (the text above its declaration): labels[i] of the n records of records24.  A grid the device call would
+ * refuse (NULL included) writes nothing. */
+GS4D_API void gs4d_host_cell_labels(size_t n, const float* records24, const gs4d_cell_grid* grid, uint32_t* labels);
+/* The definition of gs4d_merge_records (the text above its declaration): out24 receives one record per group (room for n records covers every
+ * case), groups one row per group and member_group n words (either may be NULL), *count the four counts; there is no capacity: written == groups.
+ * stats == NULL (with rule == NULL) lets every record be a member.  A query the device call would refuse (NULL, an alpha_max that is not finite
+ * and > 0, flags or reserved != 0), n > 0xFFFFFFFE, exactly one of stats / rule given, or a rule with an unknown flag or reserved != 0 writes
+ * nothing. */
+GS4D_API void gs4d_host_merge_records(size_t n, const float* records24, const uint32_t* labels, const gs4d_merge_query* q,
+                                      const gs4d_record_stat* stats, const gs4d_keep_rule* rule,
+                                      float* out24, gs4d_merge_group* groups, uint32_t* member_group, gs4d_merge_count* count);
 /* The definition of gs4d_nearest_neighbours (the text above its declaration): the brute-force double loop, every source that is near inserted
  * into the sorted list of the k smallest (bits(dist2), j); then the k slots of row i at hits + i * hit_stride and — stats != NULL — the row of
  * the table.  source == NULL selects every record (rule is then ignored), else rule is not NULL.  A call the device would refuse for its query,
