@@ -117,6 +117,91 @@ def records(n, stride):
     return ((i * np.uint64(2654435761) + w * np.uint64(40503)) & np.uint64(0xFFFFFFFF)).astype(np.uint32)
 
 
+# ---- past one round of the scan ------------------------------------------------------------------------------------------------------------------
+# k_compact_scan (csrc/compact.hip) is ONE workgroup of 1024 threads that walks the per-tile counts in rounds of 1024 words; what the earlier rounds
+# kept travels in one LDS word.  Round r covers tiles [1024 r, 1024 (r + 1)), records [r * ROUND, (r + 1) * ROUND).
+COMPACT_TILE = 2048                                       # records per tile (gs4d_internal.h)
+SCAN_THREADS = 1024                                       # tile counts per round of the scan
+ROUND = SCAN_THREADS * COMPACT_TILE                       # records per round: 2 097 152
+ROUND_SIZES = (ROUND, ROUND + 1, ROUND + COMPACT_TILE + 1, 2 * ROUND + 1)      # one full round and nothing behind it; one tile in round 2; two; three rounds
+ROUND_PATTERNS = ("sparse", "seam", "first_round", "last_round")
+
+
+def tile_counts(mask):
+    """kept rows per tile of COMPACT_TILE records: what k_compact_count stores"""
+    return np.add.reduceat(mask.astype(np.int64), np.arange(0, mask.size, COMPACT_TILE))
+
+
+def round_sums(mask):
+    """kept rows per round of the scan: the sums of SCAN_THREADS consecutive tile counts"""
+    t = tile_counts(mask)
+    return np.add.reduceat(t, np.arange(0, t.size, SCAN_THREADS))
+
+
+def round_mask(pattern, n):
+    """which of n > ROUND - COMPACT_TILE records a pattern keeps:
+    sparse       about 3 % of the rows, the first and the last row among them: kept rows in every tile of every round;
+    seam         about half of the rows of the last tile of round 1 and of the first tile of round 2 (where n has one), nothing else;
+    first_round  about 3 % of the rows of round 1, nothing behind it: the count comes out of the carry alone;
+    last_round   about 3 % of the rows of the last round (its last row among them), nothing in front of it."""
+    rng = np.random.default_rng(seed(f"round/{pattern}/{n}"))
+    m = np.zeros(n, bool)
+    last = (n - 1) // ROUND * ROUND                       # first record of the last round
+    if pattern == "sparse":
+        m = rng.uniform(size=n) < 0.03
+        for t0 in range(0, n, COMPACT_TILE):              # every tile, whatever the draw gave
+            if not m[t0:t0 + COMPACT_TILE].any():
+                m[t0] = True
+        m[0] = m[n - 1] = True
+    elif pattern == "seam":
+        lo, hi = ROUND - COMPACT_TILE, min(n, ROUND + COMPACT_TILE)
+        m[lo:hi] = rng.uniform(size=hi - lo) < 0.5
+        m[ROUND - 1] = True
+        if n > ROUND:
+            m[ROUND] = True
+    elif pattern == "first_round":
+        m[:ROUND] = rng.uniform(size=ROUND) < 0.03
+        m[ROUND - 1] = True
+    elif pattern == "last_round":
+        m[last:] = rng.uniform(size=n - last) < 0.03
+        m[n - 1] = True
+    else:
+        raise KeyError(pattern)
+    return m
+
+
+def assert_round_pattern(pattern, n, mask):
+    """the property a round pattern is named for, from the per-tile and per-round sums (numpy alone: runs without a device).  A case that has
+    degenerated — no second round, an empty seam tile, a kept row in a round that should be empty — fails here."""
+    tiles, rounds = tile_counts(mask), round_sums(mask)
+    ntiles = -(-n // COMPACT_TILE)
+    nrounds = -(-ntiles // SCAN_THREADS)
+    assert tiles.size == ntiles and rounds.size == nrounds and int(rounds.sum()) == int(mask.sum())
+    assert nrounds == {ROUND: 1, ROUND + 1: 2, ROUND + COMPACT_TILE + 1: 2, 2 * ROUND + 1: 3}[n], "the sizes are named for their rounds"
+    assert ntiles - SCAN_THREADS * (nrounds - 1) == {ROUND: 1024, ROUND + 1: 1, ROUND + COMPACT_TILE + 1: 2, 2 * ROUND + 1: 1}[n], "tiles in the last round"
+    if pattern == "sparse":
+        assert (tiles > 0).all() and (rounds > 0).all() and 0.02 * n < mask.sum() < 0.04 * n
+    elif pattern == "seam":
+        seam = [t for t in (SCAN_THREADS - 1, SCAN_THREADS) if t < ntiles]
+        assert (tiles[seam] > 0).all() and int(tiles[seam].sum()) == int(mask.sum()), "kept rows in the two tiles at the seam and nowhere else"
+        assert len(seam) == (2 if n > ROUND else 1)
+    elif pattern == "first_round":
+        assert rounds[0] > 1000 and not rounds[1:].any() and tiles[SCAN_THREADS - 1] > 0, "kept rows in round 1 (its last tile too) and in no other"
+    elif pattern == "last_round":
+        assert rounds[-1] > 0 and not rounds[:-1].any() and mask[n - 1], "kept rows in the last round and in no other"
+    else:
+        raise KeyError(pattern)
+
+
+def round_table(mask):
+    """a STAT table that RULES['visible'] (min_pixels = 1) keeps exactly where mask says: pixels 1 or 0"""
+    st = np.zeros(mask.size, STAT)
+    st["pixels"] = mask
+    st["wmax"] = BITS_1_255
+    st["wsum"] = 1
+    return st
+
+
 def loop_reference(stats, rule, cap_dst, cap_idx, invert=False):
     """the contract as a plain Python loop (small tables): -> (indices written, kept, written)"""
     min_pixels, min_wmax, min_wsum = rule

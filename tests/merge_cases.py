@@ -58,6 +58,64 @@ def passes(stats, min_pixels=1, invert=False):
     return (stats["pixels"] >= min_pixels) != invert
 
 
+# ---- past one round of the scan ------------------------------------------------------------------------------------------------------------------
+# k_merge_scan (csrc/merge.hip) is ONE workgroup of 1024 threads that walks the per-tile head counts in rounds of 1024 words; the groups of the
+# earlier rounds travel in one LDS word.
+SCAN_THREADS = 1024
+ROUND = SCAN_THREADS * MERGE_TILE                            # sorted slots per round of the scan
+ROUND_N = ROUND + MERGE_TILE + 1                             # 1026 tiles: two of them in round 2
+ROUND_CASES = ("heads_in_round_2", "rule", "no_heads_in_round_2")
+
+
+def round_records(gs4d):
+    """ROUND_N clean 4d_vel records: a pool of a few thousand that members_of accepts, taken round and round"""
+    pool = tc.records(gs4d, "4d_vel", 3000)
+    pool = pool[members_of(pool, np.zeros(pool.shape[0], u32))]
+    assert pool.shape[0] > 2000
+    return np.ascontiguousarray(np.resize(pool, (ROUND_N, 24)))
+
+
+def round_labels(case, gs4d):
+    """(labels, stats table or None, rule keywords) of ROUND_N records that are all members where their label and the rule let them:
+    heads_in_round_2     about ROUND_N / 7 labels, multiples of 3, at random, and one record alone with the largest label: every record is a member,
+                         and the one slot of the last tile is a head;
+    rule                 the random labels, 300 records without one, and a table whose rule min_pixels = 1 leaves out another 700: the members end
+                         in the first tile of round 2;
+    no_heads_in_round_2  the last 2 * MERGE_TILE + 501 records without a label: the non-members are a suffix of the sorted keys longer than two tiles, the
+                         members end in the last tile but one of round 1."""
+    n = ROUND_N
+    rng = np.random.default_rng(0x524E + ROUND_CASES.index(case))
+    lab = rng.integers(0, n // 7, n).astype(u32) * u32(3)
+    stats, rule = None, {}
+    if case == "no_heads_in_round_2":
+        lab[n - (2 * MERGE_TILE + 501):] = ID_NONE
+    elif case == "heads_in_round_2":
+        lab[n // 3] = 0xFFFFFFFE
+    if case == "rule":
+        out = rng.choice(n, 1000, replace=False)
+        lab[out[:300]] = ID_NONE
+        stats, rule = np.zeros(n, gs4d.RECORD_STAT), {"min_pixels": 1}
+        stats["pixels"], stats["wmax"], stats["wsum"] = 1, 1.0, 1 << 24
+        stats["pixels"][out[300:]] = 0
+    return lab, stats, rule
+
+
+def assert_round_labels(case, labels, member):
+    """the property the case is named for, from the stable-sorted member labels (numpy alone).  Returns the number of groups."""
+    keys = np.sort(labels[member], kind="stable")
+    heads = np.flatnonzero(np.r_[True, keys[1:] != keys[:-1]])
+    per_tile = np.bincount(heads // MERGE_TILE, minlength=ROUND_N // MERGE_TILE + 1)
+    assert per_tile.size == SCAN_THREADS + 2 and ROUND_N - keys.size < (MERGE_TILE if case != "no_heads_in_round_2" else ROUND_N)
+    assert (per_tile[:SCAN_THREADS - 1] > 0).all(), "heads in every tile of round 1 in front of its last"
+    if case == "no_heads_in_round_2":
+        assert keys.size == ROUND - MERGE_TILE - 500 and not per_tile[SCAN_THREADS - 1:].any(), "no member, so no head, behind tile 1022: none in round 2"
+    elif case == "rule":
+        assert per_tile[SCAN_THREADS] > 0 and per_tile[SCAN_THREADS + 1] == 0 and heads[-1] >= ROUND, "heads in the first tile of round 2"
+    else:
+        assert keys.size == ROUND_N and per_tile[SCAN_THREADS] > 0 and per_tile[SCAN_THREADS + 1] == 1 and heads[-1] == ROUND_N - 1, "heads in both tiles of round 2"
+    return heads.size
+
+
 # ---- the header's text -------------------------------------------------------------------------------------------------------------------------
 def S(rec, c, r):
     return rec[..., 8 + 4 * c + r]

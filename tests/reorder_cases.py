@@ -153,6 +153,38 @@ def positions(name, n):
 
 ALL_PATTERNS = PATTERNS + tuple(f"hostile/{k}" for k in HOSTILE)
 
+# ---- past the grid of the box kernel ----
+# k_order_box (csrc/reorder.hip) has at most ORDER_BOX_GROUPS workgroups of 256 threads; past ORDER_BOX_GROUPS * 256 records every thread strides.
+ORDER_BOX_GROUPS = 1024                                    # gs4d_internal.h
+FIRST_TRIP = ORDER_BOX_GROUPS * 256                        # records the grid covers in one trip of the stride loop
+STRIDE_SIZE = FIRST_TRIP + 257                             # a second trip for every thread of the first workgroup and one thread of the second
+STRIDE_TRIPS = ("second", "first")                         # the trip whose records hold the six extremes of the box
+
+
+def stride_positions(trip):
+    """STRIDE_SIZE positions in [-3, 5]^3 whose six box extremes (-100 or +100 on one axis each) are held by six records of the given trip of
+    k_order_box's stride loop alone — "second": records >= FIRST_TRIP, on the first and last lane of a wave, the last thread of the workgroup and
+    the one record of the second workgroup; "first": records < FIRST_TRIP.  The second trip also holds three unplaced records and eleven that
+    share their position, and so their key, with a record of the first trip."""
+    p = uniform(STRIDE_SIZE, "stride")
+    at = FIRST_TRIP + np.array([0, 63, 64, 130, 255, 256]) if trip == "second" else np.array([0, 255, 256, 70_001, FIRST_TRIP - 257, FIRST_TRIP - 1])
+    for k, i in enumerate(at):
+        p[i, k % 3] = np.float32(-100.0 if k < 3 else 100.0)
+    p[FIRST_TRIP + 1], p[FIRST_TRIP + 65], p[FIRST_TRIP + 200] = f32([np.nan, 0, 0]), f32([0, np.inf, 0]), f32([1, 1, -np.inf])
+    p[FIRST_TRIP + 10:FIRST_TRIP + 21] = p[5]
+    return f32(p)
+
+
+def assert_stride_positions(trip, pos):
+    """the property the case is named for (numpy alone): every extreme of the box is reached in the named trip only, and strictly"""
+    ok = placed(pos)
+    idx = np.flatnonzero(ok)
+    here = idx >= FIRST_TRIP if trip == "second" else idx < FIRST_TRIP
+    assert pos.shape[0] == STRIDE_SIZE and 0 < (~ok).sum() and (np.flatnonzero(~ok) >= FIRST_TRIP).all()
+    for a in range(3):
+        v = pos[ok, a]
+        assert v[here].min() == -100.0 and v[here].max() == 100.0 and v[~here].min() > -4.0 and v[~here].max() < 6.0, f"axis {a}"
+
 
 # ---- records ----
 def records_with_positions(pos, stride, pos_offset):

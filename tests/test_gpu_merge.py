@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 import merge_cases as mc
+import neighbour_cases as nc
+import reorder_cases as rc
 import scenes
 import transform_cases as tc
 
@@ -239,4 +241,91 @@ def test_lod_of_a_cube_set_draws(gs4d, cube_records, edge):
     assert float(np.abs(img.astype(np.float64) - full.astype(np.float64)).mean()) < 0.25
     ctx.finish()                                                                      # reports device-side check failures
     assert ctx.shadow_builds(dst) == 1
+    ctx.close()
+
+
+# ---- 4. scratch re-use ---------------------------------------------------------------------------------------------------------------------------
+class Outputs:
+    """sentinel-filled dst, groups, member_group and count of one merge of n records, a guard buffer behind them; nothing is read before read()"""
+
+    def __init__(self, ctx, n):
+        self.ctx, self.n = ctx, n
+        self.sizes = ((n + 3) * 96 + 32, (n + 3) * 16 + 8, 4 * n + 16, 32)
+        self.dst, self.groups, self.mg, self.count = (mc.fill(ctx, b) for b in self.sizes)
+        self.guard = mc.fill(ctx, mc.GUARD)
+
+    def queue(self, data, lab, alpha_max):
+        self.ctx.merge_records(data, self.n, lab, alpha_max, dst=self.dst, groups=self.groups, member_group=self.mg, count=self.count)
+
+    def read(self, gs4d, what):
+        """-> (what assert_device_equals_host takes, every byte of the four buffers); what lies behind the written part still holds the sentinel"""
+        ctx, n = self.ctx, self.n
+        raw = [ctx.read(b, np.uint8, size) for b, size in zip((self.dst, self.groups, self.mg, self.count), self.sizes)]
+        c = raw[3][:16].view(gs4d.MERGE_COUNT)[0]
+        w = int(c["written"])
+        assert w == int(c["groups"]) <= n, f"{what}: count {c}"
+        for a, used in zip(raw, (96 * w, 16 * w, 4 * n, 16)):
+            assert (a[used:] == mc.SENTINEL).all(), f"{what}: bytes behind the written part of an output changed"
+        assert mc.untouched(ctx, self.guard), f"{what}: the guard buffer changed"
+        got = (raw[0][:96 * w].view(f32).reshape(w, 24), raw[1][:16 * w].view(gs4d.MERGE_GROUP), raw[2][:4 * n].view(u32), c)
+        return got, b"".join(a.tobytes() for a in raw)
+
+    def delete(self):
+        for b in (self.dst, self.groups, self.mg, self.count, self.guard):
+            self.ctx.delete(b)
+
+
+def test_the_scratch_is_shared_with_the_grid_queries_and_the_spatial_order_at_other_sizes(gs4d):
+    """large, small, large again on one lane; behind every merge a gs4d_count_neighbours, gs4d_label_components or gs4d_spatial_order call of another
+    size and the same merge once more, the three queued without a read or a finish between them.  The merge keeps keys, sorted indices, run starts,
+    tile counts and the state block at offsets of the lane's neighbour_scratch that depend on n (launch_merge_records, csrc/merge.hip: keys = scratch,
+    index = keys + n4, ...) and sorts through the lane's pair_sort; the grid queries lay out the same scratch by their own n, the spatial order sizes
+    the same pair_sort.  A call that kept a pointer or a size of the scratch from an earlier, larger or smaller call — or a scratch that is grown
+    while a queued kernel still uses the old storage — would give the second merge other run starts or keys: its dst, groups or member_group would
+    differ from the first merge's and from the host definition's."""
+    ctx = gs4d.Context(64, 64)
+    assert ctx.stats()["lanes"] >= 1
+    other = nc.case("cube", 1025)
+    odata, ostats = ctx.buffer(other.rec), ctx.record_stats(other.n)
+    want_counts = nc.host(other.rec, other.t, other.r, 0xFFFFFFFF, 0, nc.table("zero", other.n))
+    want_labels = gs4d.label_components_host(other.rec, other.r, with_stats=False)[0]
+    opos = rc.positions("uniform", 70_001)
+    osrc, want_order = ctx.buffer(rc.records_with_positions(opos, 16, 0)), rc.order(opos)
+    for step, n in enumerate((4100, 9, 2049, 769, 4100)):
+        what = f"step {step}, n = {n}"
+        rec, labels = tc.records(gs4d, "4d_vel", n), mc.mixed_labels(n, step)
+        alpha_max = (1.0, 0.25, 1e-3)[step % 3]
+        host = gs4d.merge_records_host(rec, labels, alpha_max)
+        assert int(host[3]["groups"]) >= 2 and int(host[3]["left_out"]) >= 0
+        data, lab = ctx.buffer(rec), ctx.buffer(labels)
+        first, second = Outputs(ctx, n), Outputs(ctx, n)
+        olabels, oindex = mc.fill(ctx, 4 * other.n + 16), mc.fill(ctx, 4 * 70_001 + 16)
+        ctx.subdata(ostats, nc.table("zero", other.n))
+        # ---- the three calls, nothing read or finished between them
+        first.queue(data, lab, alpha_max)
+        if step % 3 == 0:
+            ctx.count_neighbours(ostats, other.n, odata, other.r)
+        elif step % 3 == 1:
+            ctx.label_components(other.n, odata, other.r, labels=olabels)
+        else:
+            ctx.spatial_order(osrc, 70_001, stride=16, order_index=oindex)
+        second.queue(data, lab, alpha_max)
+        # ---- only now
+        got2, bytes2 = second.read(gs4d, f"{what}, again")
+        got1, bytes1 = first.read(gs4d, what)
+        mc.assert_device_equals_host(what, got1, host)
+        mc.assert_device_equals_host(f"{what}, again", got2, host)
+        assert bytes2 == bytes1, f"{what}: the second merge differs from the first"
+        if step % 3 == 0:
+            assert ctx.read(ostats, nc.STAT, other.n).tobytes() == want_counts.tobytes(), f"{what}: count_neighbours between the merges"
+        elif step % 3 == 1:
+            assert np.array_equal(ctx.read(olabels, u32, other.n), want_labels) and mc.untouched(ctx, olabels, 16, offset=4 * other.n), f"{what}: label_components between the merges"
+        else:
+            assert np.array_equal(ctx.read(oindex, u32, 70_001), want_order) and mc.untouched(ctx, oindex, 16, offset=4 * 70_001), f"{what}: spatial_order between the merges"
+        assert mc.same_bytes(ctx, data, rec) and mc.same_bytes(ctx, lab, labels), f"{what}: an input changed"
+        first.delete()
+        second.delete()
+        for b in (data, lab, olabels, oindex):
+            ctx.delete(b)
+    ctx.finish()                                                                      # reports device-side check failures
     ctx.close()

@@ -181,3 +181,8 @@ def window_table(n, finite=False):
     return out
 
 
+def mask_table(mask):
+    """a SPAN table that the window [24, 26] keeps exactly where mask says: a kept span ends at 24 exactly, a dropped one one float below"""
+    out = np.zeros(mask.size, SPAN)
+    out["t_last"] = np.where(mask, np.float32(24.0), np.nextafter(np.float32(24.0), -INF))
+    return out
