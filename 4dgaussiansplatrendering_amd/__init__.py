@@ -118,6 +118,8 @@ def _load():
         "gs4d_nearest_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32, sz, u32]),
         "gs4d_cell_labels": (i32, [vp, u32, sz, vp, u32]),
         "gs4d_merge_records": (i32, [vp, u32, sz, u32, vp, u32, vp, u32, u32, u32, u32]),
+        "gs4d_lod_append": (i32, [vp, u32, sz, u32, sz, sz, u32, u32, sz]),
+        "gs4d_lod_cut": (i32, [vp, u32, u32, sz, vp, u32, u32, u32, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
         "gs4d_get_timings": (i32, [vp, vp]),
         "gs4d_get_timeline": (i32, [vp, vp, i32, vp]),
@@ -155,6 +157,7 @@ def _load():
         "gs4d_host_nearest_neighbours": (None, [sz, vp, vp, vp, vp, vp, sz, vp]),
         "gs4d_host_cell_labels": (None, [sz, vp, vp, vp]),
         "gs4d_host_merge_records": (None, [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gs4d_host_lod_cut": (None, [sz, vp, vp, vp, vp, vp, vp, vp, sz]),
         "gs4d_host_frame_box": (None, [vp, vp, vp, f32, i32, i32, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
         "gs4d_host_scene_linear": (None, [sz, vp, i32, f32, f32, vp, f32, f32, f32, vp]),
@@ -933,6 +936,64 @@ def merge_records_host(records, labels, alpha_max=1.0, stats=None, query=None, *
     return out, groups, member_group, count[0]
 
 
+class LodQuery(C.Structure):
+    """gs4d_lod_query (include/gs4d.h): the eye, the time, the ratio and the level table of a gs4d_lod_cut call; 112 bytes."""
+    _fields_ = [("eye", C.c_float * 3), ("t", C.c_float), ("ratio", C.c_float), ("near_dist", C.c_float), ("levels", C.c_uint32), ("flags", C.c_uint32),
+                ("level_first", C.c_uint32 * 17), ("reserved", C.c_uint32 * 3)]
+
+
+LOD_COUNT = np.dtype([("drawn", "<u4"), ("written", "<u4"), ("tested", "<u4"), ("drawn_leaves", "<u4")])   # gs4d_lod_count
+
+
+class LodForest:
+    """A forest of merged levels on the device (Context.build_lod, Context.lod_append): `nodes`, a buffer of n 96-byte records laid out level by level
+    with the leaves first, `parent`, a buffer of n uint32, and level_first, the first node of every level with n behind the last."""
+
+    def __init__(self, nodes, parent, level_first):
+        self.nodes, self.parent = nodes, parent
+        self.level_first = [int(v) for v in level_first]
+        self.levels, self.n = len(self.level_first) - 1, self.level_first[-1]
+
+
+def lod_query(level_first, eye, t, ratio, near=0.0):
+    """one gs4d_lod_query (LodQuery): level_first holds levels + 1 entries, the last one the node count"""
+    first = [int(v) for v in level_first]
+    if not 2 <= len(first) <= 17:
+        raise ValueError("lod_query: level_first must hold 2 .. 17 entries (1 .. 16 levels and the node count)")
+    q = LodQuery()
+    q.eye[0], q.eye[1], q.eye[2] = (float(v) for v in eye)
+    q.t, q.ratio, q.near_dist, q.levels = float(t), float(ratio), float(near), len(first) - 1
+    for k, v in enumerate(first):
+        q.level_first[k] = v
+    return q
+
+
+def lod_ratio(fov_deg, height, pixels, sigmas=3.0):
+    """The ratio of lod_cut at which a node stops being refined once `sigmas` standard deviations of its largest rest extent cover at most `pixels`
+    pixels of an image `height` pixels high under a vertical field of view of fov_deg: a length s at distance d covers s / d * (height / 2) /
+    tan(fov / 2) pixels, and lod_cut compares sqrt(variance) / d with the ratio."""
+    return float(pixels) * 2.0 * float(np.tan(np.radians(float(fov_deg)) * 0.5)) / (float(sigmas) * float(height))
+
+
+def lod_cut_host(records, parent, query, capacity=None, stats=None):
+    """gs4d_host_lod_cut, the definition of Context.lod_cut: (dst float32 [capacity, 24] whose first `written` rows are the cut and the rest zeros,
+    cut_index uint32 [capacity] likewise, stats — a copy of `stats` (RECORD_STAT rows) or n zeroed rows — with one fragment added to the row of every
+    DRAW node, count: one LOD_COUNT row) of the forest records [n, 24] / parent uint32 [n] under `query` (a LodQuery).  capacity: n if None.  A
+    query the device call would refuse gives zeros."""
+    rec = _f32(records).reshape(-1, 24)
+    n = rec.shape[0]
+    par = np.ascontiguousarray(parent, dtype=np.uint32)
+    if par.shape != (n,):
+        raise ValueError("lod_cut_host: parent must be n uint32 words")
+    cap = n if capacity is None else int(capacity)
+    st = np.zeros(n, RECORD_STAT) if stats is None else np.array(stats, copy=True)
+    if st.dtype.itemsize != 16 or st.ndim != 1 or st.shape[0] < n:
+        raise ValueError("lod_cut_host: stats must be at least n rows of 16 bytes")
+    dst, index, count = np.zeros((max(cap, 1), 24), np.float32), np.zeros(max(cap, 1), np.uint32), np.zeros(1, LOD_COUNT)
+    _lib.gs4d_host_lod_cut(n, _ptr(rec), _ptr(par), C.byref(query), _ptr(dst), _ptr(index), _ptr(st), _ptr(count), cap)
+    return dst[:cap], index[:cap], st, count[0]
+
+
 def hits_of(table, k):
     """the (n, k) HIT view of a hit table given as uint8 [n, hit_stride] (nearest_neighbours_host's, or Context.read of the buffer)"""
     t = np.ascontiguousarray(table, np.uint8)
@@ -1497,6 +1558,68 @@ class Context:
             return self.merge_records(data, n, labels, alpha_max=alpha_max)
         finally:
             self.delete(labels)
+
+    # the view's cut through a forest of merged levels
+    def lod_append(self, level, m, nodes, parent, first, member_group=None, child_first=0, c=0):
+        """gs4d_lod_append: the m 96-byte records of `level` become nodes first .. first + m - 1 of the forest buffers `nodes` / `parent`, with parent
+        word ID_NONE; with member_group (merge_records' output over the c nodes from child_first on) those nodes get their parents: first +
+        member_group[i], or ID_NONE where that word is not below m.  Asynchronous."""
+        self._chk(_lib.gs4d_lod_append(self._h, int(level), int(m), int(member_group or 0), int(child_first), int(c), int(nodes), int(parent), int(first)))
+
+    def build_lod(self, data, n, grids, alpha_max=1.0):
+        """A LodForest over the first n records of `data`: level 0 is the set itself, and for each CellGrid of `grids`, coarser each time, the level
+        above is merge_records of the level below under cell_labels in that grid (a counting merge, one count read-back, then the merge into an
+        exact-size buffer), linked with lod_append through member_group.  At most 15 grids.  Blocking: once per upload, not per frame."""
+        grids = list(grids)
+        if len(grids) > 15:
+            raise ValueError("build_lod: at most 15 grids (16 levels)")
+        levels, links, made = [(data, int(n))], [], []
+        try:
+            for grid in grids:
+                prev, pn = levels[-1]
+                labels = self.cell_labels(prev, pn, grid)
+                made.append(labels)
+                none = self.buffer(nbytes=16)                  # (holds no record: the merge counts)
+                made.append(none)
+                _, count = self.merge_records(prev, pn, labels, alpha_max=alpha_max, dst=none)
+                made.append(count)
+                groups = int(self.read_merge_count(count)["groups"])
+                dst, member_group = self.buffer(nbytes=max(16, 96 * groups)), self.buffer(nbytes=max(16, 4 * pn))
+                made += [dst, member_group]
+                self.merge_records(prev, pn, labels, alpha_max=alpha_max, dst=dst, member_group=member_group, count=count)
+                levels.append((dst, groups))
+                links.append(member_group)
+            first = [0]
+            for _, m in levels:
+                first.append(first[-1] + m)
+            nodes, parent = self.buffer(nbytes=max(16, 96 * first[-1])), self.buffer(nbytes=max(16, 4 * first[-1]))
+            for k, (buf, m) in enumerate(levels):
+                if k == 0:
+                    self.lod_append(buf, m, nodes, parent, 0)
+                else:
+                    self.lod_append(buf, m, nodes, parent, first[k], member_group=links[k - 1], child_first=first[k - 1], c=levels[k - 1][1])
+            return LodForest(nodes, parent, first)
+        finally:
+            for b in made:
+                self.delete(b)
+
+    def lod_cut(self, forest, eye, t, ratio, near=0.0, dst=None, cut_index=None, stats=None, count=None, query=None):
+        """gs4d_lod_cut: the cut of a camera at `eye` and the time t through `forest` (a LodForest) — from the roots down, a node is drawn where its
+        largest rest variance is at most (ratio * distance) ** 2 (lod_ratio; distances below `near` count as it) or it is a leaf, and refined
+        otherwise.  The drawn nodes go to `dst` (96 bytes each) and their indices to `cut_index` in ascending node index, as far as those hold;
+        `stats` (a record_stats buffer of forest.n rows) gets one fragment per drawn node; any of the three may be None.  count: a buffer of 16
+        bytes (a new one if None) that receives the LOD_COUNT.  query: a LodQuery instead of eye, t, ratio and near.  With the words of
+        lod_cut_host.  A full write of dst.  Asynchronous; returns `count`."""
+        q = lod_query(forest.level_first, eye, t, ratio, near) if query is None else query
+        if count is None:
+            count = self.buffer(nbytes=LOD_COUNT.itemsize)
+        self._chk(_lib.gs4d_lod_cut(self._h, int(forest.nodes), int(forest.parent), int(forest.n), C.byref(q), int(dst or 0), int(cut_index or 0),
+                                    int(stats or 0), int(count)))
+        return count
+
+    def read_lod_count(self, count):
+        """The LOD_COUNT row (drawn, written, tested, drawn_leaves) of a lod_cut call; blocks until its kernels have finished."""
+        return self.read(count, np.uint32, 4).view(LOD_COUNT)[0]
 
     # records relative to each other: the sources within a radius of each record (DESIGN.md §4)
     def count_neighbours(self, stats, n, data, radius=None, t=0.0, cap=0xFFFFFFFF, source=None, skip_hidden=False, skip_dead=False, count_self=False,

@@ -1,6 +1,7 @@
 // compact.hip — stable stream compaction of a record set by a table of one row per record (include/gs4d.h):
-// gs4d_compact_records (16-byte statistics rows, KeepRule) and gs4d_compact_time_window (8-byte time spans, WindowRule) are the two instantiations
-// of the same three kernels; k_time_spans, at the end, writes the table of the second (gs4d_record_time_spans).
+// gs4d_compact_records (16-byte statistics rows, KeepRule), gs4d_compact_time_window (8-byte time spans, WindowRule) and the last step of gs4d_lod_cut
+// (1-byte node states, DrawRule; lod.hip) are the three instantiations of the same three kernels; k_time_spans, at the end, writes the table of the
+// second (gs4d_record_time_spans).
 //
 // Three launches on one stream, no workgroup ever waits for another (kernel boundaries are the only dependencies):
 //   k_compact_count    one workgroup per tile of COMPACT_TILE records: loads the table rows (16 bytes of statistics here; in general sizeof(Row)),
@@ -23,6 +24,7 @@ static_assert(CT_ROUNDS * CT_WAVES <= 64, "one wave scans the (round, wave) coun
 // a row past the end of the table (never kept: keep_flags tests the index as well)
 __device__ __forceinline__ uint4 zero_row(const uint4*) { return make_uint4(0u, 0u, 0u, 0u); }
 __device__ __forceinline__ float2 zero_row(const float2*) { return make_float2(0.0f, 0.0f); }
+__device__ __forceinline__ uint8_t zero_row(const uint8_t*) { return (uint8_t)0; }
 
 // Round r of a tile: thread t looks at local record r * CT_THREADS + t, so that a wave reads 1 KiB of consecutive rows and ascending
 // (round, wave, lane) is ascending record order.  All rows of a thread are loaded before the first is used.
@@ -149,6 +151,11 @@ hipError_t launch_compact(hipStream_t st, const gs4d_time_span* spans, size_t n,
                           const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count) {
     static_assert(sizeof(gs4d_time_span) == sizeof(float2), "a time span is one float2");
     return launch_compact_rows(st, (const float2*)spans, n, rule, tile_counts, src, stride, dst, kept_index, cap, count);
+}
+// gs4d_lod_cut's state plane: a row is one byte, a wave reads 64 consecutive bytes a round
+hipError_t launch_compact(hipStream_t st, const uint8_t* states, size_t n, const DrawRule& rule, uint32_t* tile_counts,
+                          const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count) {
+    return launch_compact_rows(st, states, n, rule, tile_counts, src, stride, dst, kept_index, cap, count);
 }
 
 // ---- gs4d_record_time_spans ----

@@ -18,6 +18,8 @@
 #include "gs4d_internal.h"
 #include "operands.h"
 #include "merge_record.h"
+#include "lod_query.h"
+#include "lod_operands.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -144,6 +146,7 @@ struct Lane {
     uint32_t* cut_scratch = nullptr; size_t cut_cap = 0;               // gs4d_stat_cut: the state block and one partial histogram per workgroup (cut_scratch_words()); the lane's stream orders its reuse
     uint32_t* measure_scratch = nullptr; size_t measure_cap = 0;       // gs4d_measure_records: one partial row per workgroup (measure_scratch_words()); the lane's stream orders its reuse
     uint32_t* neighbour_scratch = nullptr; size_t neighbour_cap = 0;   // gs4d_count_neighbours, gs4d_label_components and gs4d_nearest_neighbours: candidates, bucket table, keys and sorted indices (neighbour_scratch_words()); gs4d_count_labels: n flag words; the lane's stream orders its reuse
+    uint8_t* lod_state = nullptr; size_t lod_cap = 0;                  // gs4d_lod_cut: the state plane, one byte per node (its tile counts: compact_counts); the lane's stream orders its reuse
     uint32_t* host_total = nullptr; uint32_t* host_total_dev = nullptr;   // the host verdict words of the last draw (HT_*, gs4d_internal.h), pinned + mapped, and the same memory as the device sees it
     uint32_t* err_word() const { return &host_total_dev[HT_ERROR]; }     // the error word every kernel may raise
     gs4d_buf kg_buf = 0; uint64_t kg_ver = 0;         // key buffer whose digit histograms k_keygen left for the next sort
@@ -1114,6 +1117,7 @@ void gs4d_destroy(gs4d_ctx* c) {
         if (L.cut_scratch) (void)hipFree(L.cut_scratch);
         if (L.measure_scratch) (void)hipFree(L.measure_scratch);
         if (L.neighbour_scratch) (void)hipFree(L.neighbour_scratch);
+        if (L.lod_state) (void)hipFree(L.lod_state);
         for (auto& sp : L.spare) { if (sp.d) (void)hipFree(sp.d); for (hipEvent_t e : sp.ev) if (e) (void)hipEventDestroy(e); }
         if (L.proj) (void)hipFree(L.proj);
         if (L.trects) (void)hipFree(L.trects);
@@ -2228,6 +2232,54 @@ int gs4d_merge_records(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf labels, co
             HIPCHK(c, launch_merge_records(L.s, L.pair_sort, ops.ptr(data), n, (const uint32_t*)ops.ptr(labels), q.alpha_max, (const gs4d_record_stat*)ops.ptr(stats), k,
                                            L.neighbour_scratch, ops.ptr(dst), (gs4d_merge_group*)ops.ptr(groups), (uint32_t*)ops.ptr(member_group), cap,
                                            (gs4d_merge_count*)ops.ptr(count)));
+            return (int)GS4D_OK;
+        });
+}
+
+// ---- the view's cut through a forest of merged levels ----
+int gs4d_lod_append(gs4d_ctx* c, gs4d_buf level, size_t m, gs4d_buf member_group, size_t child_first, size_t cn, gs4d_buf nodes, gs4d_buf parent, size_t first) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "lod_append";
+    if (const char* fault = lod_append_fault(m, member_group != 0, child_first, cn, first)) return refuse(c, fn, fault);
+    Operand list[LOD_APPEND_OPERANDS];                         // (lod_operands.h: what the call does with each)
+    lod_append_operands(list, level, m, member_group, cn, nodes, parent, first);
+    Operands ops{ list[0], list[1], list[2], list[3] };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (m == 0 && cn == 0) return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_lod_append(L.s, ops.ptr(level), m, (const uint32_t*)ops.ptr(member_group), child_first, cn, ops.ptr(nodes), (uint32_t*)ops.ptr(parent), first));
+        return (int)GS4D_OK;
+    });
+}
+
+int gs4d_lod_cut(gs4d_ctx* c, gs4d_buf nodes, gs4d_buf parent, size_t n, const gs4d_lod_query* query, gs4d_buf dst, gs4d_buf cut_index, gs4d_buf stats, gs4d_buf count) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "lod_cut";
+    if (!query) return refuse(c, fn, "q == NULL");
+    const gs4d_lod_query q = *query;
+    if (!gs4d_lod::query_ok(q, n))
+        return refuse(c, fn, "n at most 2^32 - 2; levels 1 .. 16; level_first from 0, not decreasing, to n; ratio >= 0; near_dist finite and >= 0; flags and reserved 0");
+    static_assert(sizeof(gs4d_record_stat) == 16 && sizeof(gs4d_lod_count) == 16, "the rows of lod_operands.h");
+    Operand list[LOD_CUT_OPERANDS];                            // (lod_operands.h: what the call does with each)
+    lod_cut_operands(list, nodes, parent, n, dst, cut_index, stats, count);
+    Operands ops{ list[0], list[1], list[2], list[3], list[4], list[5] };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    // slots the outputs hold: no slot >= cap is ever written
+    uint32_t cap = 0xFFFFFFFFu;
+    if (Buffer* D = ops.buffer(dst)) cap = (uint32_t)std::min<size_t>(cap, D->bytes / 96);
+    if (Buffer* X = ops.buffer(cut_index)) cap = (uint32_t)std::min<size_t>(cap, X->bytes / 4);
+    return queue_operands(c, ops,
+        [&](Lane& L) {
+            if (n == 0) return (int)GS4D_OK;
+            HIPCHK(c, grow_device_array(L.s, L.lod_state, L.lod_cap, (n + 15) & ~(size_t)15));
+            HIPCHK(c, grow_device_array(L.s, L.compact_counts, L.compact_cap, std::max<size_t>(1, compact_tiles(n))));
+            return (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            HIPCHK(c, launch_lod_cut(L.s, ops.ptr(nodes), (const uint32_t*)ops.ptr(parent), n, q, L.lod_state, L.compact_counts, ops.ptr(dst), (uint32_t*)ops.ptr(cut_index),
+                                     (gs4d_record_stat*)ops.ptr(stats), cap, (gs4d_lod_count*)ops.ptr(count)));
             return (int)GS4D_OK;
         });
 }

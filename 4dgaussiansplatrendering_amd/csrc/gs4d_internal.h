@@ -439,6 +439,11 @@ hipError_t launch_compact(hipStream_t st, const gs4d_record_stat* stats, size_t 
 struct WindowRule { float t0, t1; };
 hipError_t launch_compact(hipStream_t st, const gs4d_time_span* spans, size_t n, const WindowRule& rule, uint32_t* tile_counts,
                           const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count);
+// gs4d_lod_cut: the same three kernels on a plane of one state byte per node; node i is kept iff its byte equals rule.state.  `count` receives
+// {kept, min(kept, cap)} in its first 8 bytes
+struct DrawRule { uint32_t state; };
+hipError_t launch_compact(hipStream_t st, const uint8_t* states, size_t n, const DrawRule& rule, uint32_t* tile_counts,
+                          const void* src, size_t stride, void* dst, uint32_t* kept_index, uint32_t cap, gs4d_compact_count* count);
 // gs4d_record_time_spans: spans[i] of the n 96-byte records in `data` (one launch; n == 0: none)
 hipError_t launch_time_spans(hipStream_t st, const void* data, size_t n, float min_opacity, gs4d_time_span* spans);
 #ifdef __HIPCC__
@@ -460,6 +465,8 @@ __device__ __forceinline__ void add_fragments(uint4* __restrict__ stats, uint64_
 }
 // gs4d_time_span {t_first, t_last} against the window [t0, t1]: the two closed intervals meet (an empty span, {+inf, -inf}, meets nothing)
 __device__ __forceinline__ bool keep_row(const float2 row, const WindowRule k) { return row.x <= k.t1 && row.y >= k.t0; }
+// a state byte of gs4d_lod_cut's plane against the state that is kept
+__device__ __forceinline__ bool keep_row(const uint8_t row, const DrawRule k) { return (uint32_t)row == k.state; }
 #endif
 
 // ---- reorder.hip ----
@@ -630,5 +637,20 @@ inline size_t merge_scratch_words(size_t n) { return 3 * ((n + 3) & ~(size_t)3) 
 hipError_t launch_merge_records(hipStream_t st, SortScratch& sort, const void* records, size_t n, const uint32_t* labels, float alpha_max,
                                 const gs4d_record_stat* stats, const KeepRule& rule, uint32_t* scratch, void* dst, gs4d_merge_group* groups,
                                 uint32_t* member_group, uint32_t cap, gs4d_merge_count* count);
+
+// ---- lod.hip ----
+// gs4d_lod_append (gs4d.h): nodes[first + j] <- the 96 bytes of level[j], parent[first + j] <- GS4D_ID_NONE, j < m; parent[child_first + i]
+// <- first + member_group[i] where that word is below m, else GS4D_ID_NONE, i < c (member_group null: c == 0).  child_first + c <= first and
+// first + m <= 0xFFFFFFFE (validated).  One launch; m == 0 and c == 0: none.  Nothing else is written.
+hipError_t launch_lod_append(hipStream_t st, const void* level, size_t m, const uint32_t* member_group, size_t child_first, size_t c,
+                             void* nodes, uint32_t* parent, size_t first);
+// gs4d_lod_cut (gs4d.h): the cut of q (validated for n) through the forest of n 96-byte nodes and n parent words — a clearing launch, one
+// launch per level (or run of small levels) from the top down over the state plane, and the three compaction kernels over the plane, all on `st`; no
+// workgroup waits for another.  state: n bytes of scratch, tile_counts: compact_tiles(n) words (the lane's); dst, cut_index, stats: null: none; cap:
+// slots dst and cut_index hold (no slot >= cap is written); *count always receives the gs4d_lod_count (n == 0: zeros, one launch).  Nothing but those
+// outputs, the rows of the DRAW nodes in stats and the scratch is written.
+constexpr uint32_t LOD_TILE = 1024;              // nodes per workgroup of the level kernel (4 per thread)
+hipError_t launch_lod_cut(hipStream_t st, const void* nodes, const uint32_t* parent, size_t n, const gs4d_lod_query& q, uint8_t* state,
+                          uint32_t* tile_counts, void* dst, uint32_t* cut_index, gs4d_record_stat* stats, uint32_t cap, gs4d_lod_count* count);
 
 } // namespace gs4d

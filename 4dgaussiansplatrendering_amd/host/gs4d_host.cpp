@@ -29,6 +29,7 @@
 #include "../csrc/centre_query.h"
 #include "../csrc/measure_record.h"
 #include "../csrc/merge_record.h"
+#include "../csrc/lod_query.h"
 #include "../csrc/neighbour_query.h"
 #include "../csrc/component_union.h"
 #include "../csrc/nearest_query.h"
@@ -590,6 +591,39 @@ void gs4d_host_merge_records(size_t n, const float* rec, const uint32_t* labels,
         if (member_group) for (size_t k = first; k < end; ++k) member_group[member[k]] = g;
     }
     *count = gs4d_merge_count{ g, g, (uint32_t)member.size(), (uint32_t)(n - member.size()) };
+}
+
+// The definition of gs4d_lod_cut (gs4d.h) over the text of csrc/lod_query.h, which the kernel compiles too (this file is built with
+// -ffp-contract=off): the levels from the top down, one state per node, then the DRAW nodes in ascending index.  A query the device call would
+// refuse writes nothing.
+void gs4d_host_lod_cut(size_t n, const float* rec, const uint32_t* parent, const gs4d_lod_query* q, float* dst, uint32_t* cut_index,
+                       gs4d_record_stat* stats, gs4d_lod_count* count, size_t capacity) {
+    namespace lod = gs4d_lod;
+    if (!q || !lod::query_ok(*q, n)) return;
+    const lod::View view = lod::view_of(*q);
+    std::vector<uint8_t> state(n, (uint8_t)lod::STOP);
+    uint32_t tested = 0, drawn = 0, drawn_leaves = 0;
+    for (int k = (int)q->levels - 1; k >= 0; --k) {
+        const uint32_t next_first = q->level_first[k + 1];
+        for (size_t i = q->level_first[k]; i < next_first; ++i) {
+            const uint32_t p = parent[i];
+            if (lod::is_child(p, next_first, (uint32_t)n) && state[p] != lod::DESCEND) continue;      // STOP: nothing of its record is looked at
+            ++tested;
+            const bool leaf = i < q->level_first[1];
+            state[i] = lod::tested_state(leaf, !leaf && lod::fine(view, rec + 24 * i));
+            if (state[i] == lod::DRAW && leaf) ++drawn_leaves;
+        }
+    }
+    for (size_t i = 0; i < n; ++i) {
+        if (state[i] != lod::DRAW) continue;
+        if (drawn < capacity) {
+            if (dst) std::memcpy(dst + 24 * (size_t)drawn, rec + 24 * i, 96);
+            if (cut_index) cut_index[drawn] = (uint32_t)i;
+        }
+        if (stats) add_fragments(stats[i], 1u, ONE_BITS);
+        ++drawn;
+    }
+    *count = gs4d_lod_count{ drawn, (uint32_t)(drawn < capacity ? drawn : capacity), tested, drawn_leaves };
 }
 
 // The definition of gs4d_nearest_neighbours (gs4d.h): the brute-force double loop over the texts of csrc/neighbour_query.h and

@@ -1266,7 +1266,7 @@ GS4D_API int gs4d_cell_labels(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d
  * Cost.  A key kernel, the library's stable 32-bit sort of the identity by key, a count / scan / scatter over the sorted keys, and a segmented
  * reduction with eight lanes per group.  The lane keeps about 12 n bytes of scratch beside the sort's.  A group of a million
  * members is walked by eight lanes: a documented corner.
- * Out of scope: choosing a level per view or per cell at draw time; merging SH tables. */
+ * Out of scope: merging SH tables.  Choosing a level per view at draw time is gs4d_lod_cut, below, over a forest of such levels. */
 typedef struct gs4d_merge_query {
     float    alpha_max;    /* the clamp of a merged record's alpha; finite and > 0                   */
     uint32_t flags;        /* must be 0                                                              */
@@ -1277,6 +1277,78 @@ typedef struct gs4d_merge_count { uint32_t groups, written, members, left_out; }
 GS4D_API int gs4d_merge_records(gs4d_ctx* ctx, gs4d_buf data, size_t n, gs4d_buf labels, const gs4d_merge_query* q,
                                 gs4d_buf stats /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff stats == 0 */,
                                 gs4d_buf dst, gs4d_buf groups /* 0 ok */, gs4d_buf member_group /* 0 ok */, gs4d_buf count);
+
+/* ---- the view's cut through a hierarchy of merged levels (no reference counterpart) ----
+ * gs4d_merge_records builds one coarser level of a set.  A camera inside a large scene wants fine records near the eye and merged records far
+ * away, chosen again every frame: gs4d_lod_append assembles the levels into a forest on the device, once, and gs4d_lod_cut walks the forest for a
+ * camera and a time and writes the records to draw.  gs4d_host_lod_cut is the definition below as code, and the device gives its words.
+ *
+ * The forest is two buffers: nodes, N 96-byte records, and parent, N uint32; N <= 0xFFFFFFFE.  The nodes are laid out level by level: level 0, the
+ * leaves (the full set), first, each coarser level behind it.  level_first[0 .. levels] gives the first node of every level: level_first[0] == 0,
+ * the entries do not decrease, level_first[levels] == N, levels is 1 .. 16.  Node i of level k is a CHILD iff
+ * level_first[k + 1] <= parent[i] && parent[i] < N; otherwise it is a ROOT — GS4D_ID_NONE, a parent in its own level or a lower one, a parent past
+ * the end.  Parent words are data, never an error.  A parent lies in a strictly higher level, so a walk over the levels from the top down has
+ * decided every parent when it reaches a child.
+ *
+ * gs4d_lod_append, one level per call.  nodes[first + j] receives the 96 bytes of level[j], j < m, with their bits kept (NaN payloads included);
+ * parent[first + j] = GS4D_ID_NONE, j < m; with member_group given, parent[child_first + i] = member_group[i] < m ? first + member_group[i] :
+ * GS4D_ID_NONE, i < c — a record gs4d_merge_records left out and a group beyond `written` become roots.  member_group == 0 requires c == 0: the
+ * leaf level.  Nothing else is written.  m == 0 and c == 0 with otherwise valid arguments is a no-op.
+ * GS4D_E_INVALID, with nothing queued and nothing written: child_first + c > first; first + m > 0xFFFFFFFE; level, nodes or parent — or
+ * member_group, when given — not a live buffer; two arguments naming the same buffer; level smaller than 96 m bytes, member_group smaller than 4 c
+ * bytes, nodes smaller than 96 (first + m) bytes, parent smaller than 4 (first + m) bytes; member_group == 0 with c != 0.
+ * Ordering: level and member_group are read; nodes is written as gs4d_transform_records writes a dst with dst_first; parent is a kernel write that
+ * keeps the rest of its contents.  One launch on the current frame lane; the records travel in 16-byte pieces, the parent words one by one (first
+ * and child_first are any index: a run of words has no alignment to rely on).
+ *
+ * gs4d_lod_cut.  Fine — float32, every product and every sum rounded on its own in the order the parentheses give, no contraction, no square root:
+ *     m     = the centre of the node at q.t: with dt = t - mu_t and k = (1 / S44) * dt, m = p + k * sig3 per component (floats 0..2, 3, 20..22, 23:
+ *             the centre of gs4d_count_centres)
+ *     d     = m - eye per component             dist2 = ((d.x*d.x) + (d.y*d.y)) + (d.z*d.z)
+ *     n2    = near_dist * near_dist             e = dist2 > n2 ? dist2 : n2          (a NaN distance counts as near)
+ *     v     = Sxx; if (Syy > v) v = Syy; if (Szz > v) v = Szz         (floats 8, 13, 18: the rest variances, which bound the conditional ones)
+ *     fine  = v <= (ratio * ratio) * e
+ * A NaN on either side of the last comparison is not fine.  ratio = 0 makes nothing with a positive extent fine; ratio = +inf makes everything
+ * with a non-NaN extent fine at a distance e > 0.
+ * State, the levels taken from the top down: a root is TESTED; a child is tested iff its parent's state is DESCEND, otherwise its state is STOP and
+ * nothing of its record is looked at; a tested node is DRAW iff it is fine or it is a leaf (i < level_first[1]), otherwise DESCEND.  On every chain
+ * of valid parent links exactly one node is DRAW: the topmost fine one, or the leaf — whether or not the extents grow towards the roots.
+ * Outputs.  The DRAW nodes in ascending node index go to dst, 96 bytes each with their bits kept, their indices to cut_index; slots at or beyond
+ * capacity = min(dst bytes / 96, cut_index bytes / 4) over the outputs given are never written and keep their bytes, the rule of
+ * gs4d_compact_records.  count always receives {drawn, written = min(drawn, capacity), tested, drawn_leaves}; n == 0 writes {0, 0, 0, 0}.  With
+ * stats given, every DRAW node adds one fragment of weight 1 to its row of the gs4d_record_stat table (n rows), the GS4D_CQ_ADD of
+ * gs4d_count_centres; other rows keep their bits — gs4d_edit_colours (tint the levels) and the rest of the selection chain then act on the cut.
+ * No byte of nodes or parent is written.
+ * GS4D_E_INVALID, with nothing queued and nothing written: q == NULL; levels outside 1 .. 16; a level_first that is not as above; ratio a NaN or
+ * below 0; near_dist not finite or below 0; flags or a reserved word != 0; n > 0xFFFFFFFE; nodes, parent or count not a live buffer; dst, cut_index
+ * or stats, when given, not a live buffer; nodes smaller than 96 n bytes, parent smaller than 4 n bytes, stats smaller than 16 n bytes, count smaller
+ * than 16 bytes; two arguments naming the same buffer.  eye, t and every word of the buffers are data.
+ * Ordering.  nodes and parent are read.  dst is written as gs4d_transform_records writes its own: a full write, the next draw repacks its shadow
+ * once.  cut_index and count are kernel writes; stats is handled exactly as gs4d_count_centres handles its table.  A queued gs4d_keygen /
+ * gs4d_sort_pairs that names one of the buffers is launched first.  The kernels are queued on the current frame lane; the call returns at once and
+ * starts no frame.  It reads the 96-byte records: it never builds or invalidates a SoA shadow.  The frame loop is
+ * gs4d_lod_cut -> gs4d_keygen -> gs4d_sort_pairs -> draw on (dst, count.drawn), with count read back or dst sized for the worst case.
+ * Cost.  One launch per level from the top down over a plane of one state byte per node in lane scratch (consecutive levels that fit one workgroup
+ * together share a launch), then the three kernels of gs4d_compact_records over the plane.  A node whose parent is not DESCEND costs its parent
+ * word, the parent's state byte and its own: the cost follows the cut, not the forest.
+ * Out of scope: blending between a node and its children across the threshold; SH tables (cut_index carries rows along); frustum tests
+ * (gs4d_count_centres has the screen test); choosing the grids; a forest that skips the state plane. */
+GS4D_API int gs4d_lod_append(gs4d_ctx* ctx, gs4d_buf level, size_t m,
+                             gs4d_buf member_group /* 0 ok */, size_t child_first, size_t c,
+                             gs4d_buf nodes, gs4d_buf parent, size_t first);
+typedef struct gs4d_lod_query {
+    float    eye[3];          /* camera position, world                                  */
+    float    t;               /* the time the centres are taken at                       */
+    float    ratio;           /* extent / distance at or below which a node is fine      */
+    float    near_dist;       /* distances below it count as it; finite, >= 0            */
+    uint32_t levels;          /* 1 .. 16                                                 */
+    uint32_t flags;           /* must be 0                                               */
+    uint32_t level_first[17];
+    uint32_t reserved[3];     /* must be 0 */
+} gs4d_lod_query;             /* 112 bytes */
+typedef struct gs4d_lod_count { uint32_t drawn, written, tested, drawn_leaves; } gs4d_lod_count;   /* 16 bytes */
+GS4D_API int gs4d_lod_cut(gs4d_ctx* ctx, gs4d_buf nodes, gs4d_buf parent, size_t n, const gs4d_lod_query* q,
+                          gs4d_buf dst /* 0 ok */, gs4d_buf cut_index /* 0 ok */, gs4d_buf stats /* 0 ok */, gs4d_buf count);
 
 /* ---- measurement / test hooks ---- */
 GS4D_API int gs4d_set_profiling(gs4d_ctx* ctx, int stage_mask);                   /* bit (1 << GS4D_T_x) times stage x; 0 = off, 0x3F = every stage; bits 8..15 = k: time only every k-th frame (0 = every frame).
@@ -1396,6 +1468,12 @@ GS4D_API void gs4d_host_cell_labels(size_t n, const float* records24, const gs4d
 GS4D_API void gs4d_host_merge_records(size_t n, const float* records24, const uint32_t* labels, const gs4d_merge_query* q,
                                       const gs4d_record_stat* stats, const gs4d_keep_rule* rule,
                                       float* out24, gs4d_merge_group* groups, uint32_t* member_group, gs4d_merge_count* count);
+/* The definition of gs4d_lod_cut (the text above its declaration) as a plain loop over the levels from the top down, over the text of
+ * csrc/lod_query.h: the states of the n nodes of records24 under parent, then the DRAW nodes in ascending index into the first
+ * min(drawn, capacity) slots of dst24 and cut_index (either may be NULL), one fragment into the row of every DRAW node of stats (may be NULL),
+ * and *count.  A query the device call would refuse (NULL included) writes nothing. */
+GS4D_API void gs4d_host_lod_cut(size_t n, const float* records24, const uint32_t* parent, const gs4d_lod_query* q,
+                                float* dst24, uint32_t* cut_index, gs4d_record_stat* stats, gs4d_lod_count* count, size_t capacity);
 /* The definition of gs4d_nearest_neighbours (the text above its declaration): the brute-force double loop, every source that is near inserted
  * into the sorted list of the k smallest (bits(dist2), j); then the k slots of row i at hits + i * hit_stride and — stats != NULL — the row of
  * the table.  source == NULL selects every record (rule is then ignored), else rule is not NULL.  A call the device would refuse for its query,
