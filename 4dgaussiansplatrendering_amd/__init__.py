@@ -118,6 +118,8 @@ def _load():
         "gs4d_nearest_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32, sz, u32]),
         "gs4d_cell_labels": (i32, [vp, u32, sz, vp, u32]),
         "gs4d_merge_records": (i32, [vp, u32, sz, u32, vp, u32, vp, u32, u32, u32, u32]),
+        "gs4d_merge_rows": (i32, [vp, u32, sz, u32, u32, vp, u32, sz, u32]),
+        "gs4d_copy_rows": (i32, [vp, u32, sz, sz, sz, u32, sz]),
         "gs4d_lod_append": (i32, [vp, u32, sz, u32, sz, sz, u32, u32, sz]),
         "gs4d_lod_cut": (i32, [vp, u32, u32, sz, vp, u32, u32, u32, u32]),
         "gs4d_set_profiling": (i32, [vp, i32]),
@@ -157,6 +159,7 @@ def _load():
         "gs4d_host_nearest_neighbours": (None, [sz, vp, vp, vp, vp, vp, sz, vp]),
         "gs4d_host_cell_labels": (None, [sz, vp, vp, vp]),
         "gs4d_host_merge_records": (None, [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "gs4d_host_merge_rows": (None, [sz, vp, vp, vp, vp, vp, sz, sz, vp]),
         "gs4d_host_lod_cut": (None, [sz, vp, vp, vp, vp, vp, vp, vp, sz]),
         "gs4d_host_frame_box": (None, [vp, vp, vp, f32, i32, i32, vp]),
         "gs4d_host_affine4": (None, [vp, f32, vp, vp, f32, f32, vp]),
@@ -936,6 +939,51 @@ def merge_records_host(records, labels, alpha_max=1.0, stats=None, query=None, *
     return out, groups, member_group, count[0]
 
 
+class RowsQuery(C.Structure):
+    """gs4d_rows_query (include/gs4d.h): the row stride and the merged width of a gs4d_merge_rows call; 16 bytes."""
+    _fields_ = [("stride", C.c_uint32), ("width", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def rows_query(stride, width=None):
+    """one gs4d_rows_query (RowsQuery); width: every float32 word of the stride if None"""
+    q = RowsQuery()
+    q.stride, q.width = int(stride), int(stride) // 4 if width is None else int(width)
+    return q
+
+
+def merge_rows_host(rows, member_group, records=None, stride=None, width=None, dst=None, dst_first=0, query=None):
+    """gs4d_host_merge_rows, the definition of Context.merge_rows: (dst, count) — dst, uint8 [capacity, stride], is a copy of `dst` (or, if None,
+    zeros of room for dst_first + the largest group value + 1 rows) in which row dst_first + g holds the merged row of group g; count: one
+    MERGE_COUNT row.  rows: the table, n rows of `stride` bytes (any dtype; stride: the bytes of a row of a 2-d array if None); member_group:
+    uint32 [n]; records: float32 [n, 24], the weights by their mass, or None: unit weights; query: a RowsQuery instead of stride and width.  A
+    call the device would refuse changes nothing."""
+    table = np.ascontiguousarray(rows)
+    mg = np.ascontiguousarray(member_group, dtype=np.uint32)
+    n = mg.shape[0]
+    if query is None:
+        if stride is None:
+            stride = table.shape[1] * table.itemsize if table.ndim == 2 else None
+        if stride is None:
+            raise ValueError("merge_rows_host: stride is needed for a table that is not 2-d")
+        query = rows_query(stride, width)
+    stride = int(query.stride)
+    raw = table.reshape(-1).view(np.uint8)
+    if mg.ndim != 1 or raw.size < n * stride:
+        raise ValueError("merge_rows_host: member_group must be n uint32 words and rows at least n rows of `stride` bytes")
+    rec = None if records is None else _f32(records).reshape(-1, 24)
+    if rec is not None and rec.shape[0] < n:
+        raise ValueError("merge_rows_host: records must be at least n rows of 24 floats")
+    if dst is None:
+        named = mg[mg != ID_NONE]
+        out = np.zeros((int(dst_first) + (int(named.max()) + 1 if named.size else 0), max(stride, 1)), np.uint8)
+    else:
+        out = np.array(np.ascontiguousarray(dst).reshape(-1).view(np.uint8), copy=True)
+        out = out[:out.size // max(stride, 1) * max(stride, 1)].reshape(-1, max(stride, 1))
+    count = np.zeros(1, MERGE_COUNT)
+    _lib.gs4d_host_merge_rows(n, _ptr(rec) if rec is not None else None, _ptr(mg), _ptr(raw), C.byref(query), _ptr(out), int(dst_first), out.shape[0], _ptr(count))
+    return out, count[0]
+
+
 class LodQuery(C.Structure):
     """gs4d_lod_query (include/gs4d.h): the eye, the time, the ratio and the level table of a gs4d_lod_cut call; 112 bytes."""
     _fields_ = [("eye", C.c_float * 3), ("t", C.c_float), ("ratio", C.c_float), ("near_dist", C.c_float), ("levels", C.c_uint32), ("flags", C.c_uint32),
@@ -947,12 +995,15 @@ LOD_COUNT = np.dtype([("drawn", "<u4"), ("written", "<u4"), ("tested", "<u4"), (
 
 class LodForest:
     """A forest of merged levels on the device (Context.build_lod, Context.lod_append): `nodes`, a buffer of n 96-byte records laid out level by level
-    with the leaves first, `parent`, a buffer of n uint32, and level_first, the first node of every level with n behind the last."""
+    with the leaves first, `parent`, a buffer of n uint32, and level_first, the first node of every level with n behind the last.  A forest built
+    over a table with a row per record (an SH table) carries `rows`, a buffer of n rows of row_stride bytes laid out like `nodes` whose first
+    row_width float32 words are merged (Context.merge_rows); the three are None without a table."""
 
-    def __init__(self, nodes, parent, level_first):
+    def __init__(self, nodes, parent, level_first, rows=None, row_stride=None, row_width=None):
         self.nodes, self.parent = nodes, parent
         self.level_first = [int(v) for v in level_first]
         self.levels, self.n = len(self.level_first) - 1, self.level_first[-1]
+        self.rows, self.row_stride, self.row_width = rows, row_stride, row_width
 
 
 def lod_query(level_first, eye, t, ratio, near=0.0):
@@ -1566,14 +1617,50 @@ class Context:
         member_group[i], or ID_NONE where that word is not below m.  Asynchronous."""
         self._chk(_lib.gs4d_lod_append(self._h, int(level), int(m), int(member_group or 0), int(child_first), int(c), int(nodes), int(parent), int(first)))
 
-    def build_lod(self, data, n, grids, alpha_max=1.0):
+    def merge_rows(self, member_group, n, rows, stride, width=None, data=None, dst=None, dst_first=0, count=None, query=None):
+        """gs4d_merge_rows: row dst_first + g of `dst` <- the mean of the rows of the members of group g — the records i < n with member_group[i]
+        == g (a buffer of n uint32, merge_records' output; ID_NONE: no member) whose first `width` float32 words of their row of `rows` (n rows of
+        `stride` bytes) are finite — weighted by the mass of merge_records of the 96-byte records of `data`, or plainly if data is None: the SH
+        row of a merged record.  width: every word of the stride if None.  dst: a new buffer of dst_first + n rows if None; rows of groups without
+        members and rows past what dst holds are not written.  count: a buffer of 16 bytes (a new one if None) that receives the MERGE_COUNT.
+        query: a RowsQuery instead of stride and width.  With the bits of merge_rows_host.  Asynchronous; returns (dst, count)."""
+        q = rows_query(stride, width) if query is None else query
+        if dst is None:
+            dst = self.buffer(nbytes=max(16, (int(dst_first) + int(n)) * int(q.stride)))
+        if count is None:
+            count = self.buffer(nbytes=MERGE_COUNT.itemsize)
+        self._chk(_lib.gs4d_merge_rows(self._h, int(data or 0), int(n), int(member_group), int(rows), C.byref(q), int(dst), int(dst_first), int(count)))
+        return dst, count
+
+    def copy_rows(self, src, m, stride, dst=None, src_first=0, dst_first=0):
+        """gs4d_copy_rows: rows dst_first .. of `dst` (a new buffer of dst_first + m rows if None) <- rows src_first .. src_first + m - 1 of `src`,
+        `stride` bytes each (a multiple of 16 up to 1024), bits kept; the rest of dst keeps its contents.  Asynchronous; returns `dst`."""
+        if dst is None:
+            dst = self.buffer(nbytes=max(16, (int(dst_first) + int(m)) * int(stride)))
+        self._chk(_lib.gs4d_copy_rows(self._h, int(src), int(src_first), int(m), int(stride), int(dst), int(dst_first)))
+        return dst
+
+    def build_lod(self, data, n, grids, alpha_max=1.0, rows=None, row_stride=None, row_width=None):
         """A LodForest over the first n records of `data`: level 0 is the set itself, and for each CellGrid of `grids`, coarser each time, the level
         above is merge_records of the level below under cell_labels in that grid (a counting merge, one count read-back, then the merge into an
-        exact-size buffer), linked with lod_append through member_group.  At most 15 grids.  Blocking: once per upload, not per frame."""
+        exact-size buffer), linked with lod_append through member_group.  rows: a table of n rows of row_stride bytes (an SH table; row_width:
+        the float32 words of a row that are merged, all of them if None) — the forest then carries a table with a row per node: the leaf rows by
+        copy_rows, every level above by merge_rows of the level below under the same member_group (into a buffer of the level's own, since a call
+        cannot read and write one buffer, then copy_rows).  At most 15 grids.  Blocking: once per upload, not per frame."""
         grids = list(grids)
         if len(grids) > 15:
             raise ValueError("build_lod: at most 15 grids (16 levels)")
+        if rows is None:
+            if row_stride is not None or row_width is not None:
+                raise TypeError("build_lod: row_stride or row_width without rows")
+            return self._build_lod(data, n, grids, alpha_max, None, None)
+        if row_stride is None:
+            raise TypeError("build_lod: rows without row_stride")
+        return self._build_lod(data, n, grids, alpha_max, rows, rows_query(row_stride, row_width))
+
+    def _build_lod(self, data, n, grids, alpha_max, rows, rq):
         levels, links, made = [(data, int(n))], [], []
+        tables = [rows]
         try:
             for grid in grids:
                 prev, pn = levels[-1]
@@ -1587,6 +1674,12 @@ class Context:
                 dst, member_group = self.buffer(nbytes=max(16, 96 * groups)), self.buffer(nbytes=max(16, 4 * pn))
                 made += [dst, member_group]
                 self.merge_records(prev, pn, labels, alpha_max=alpha_max, dst=dst, member_group=member_group, count=count)
+                if rows is not None:
+                    # zeros first: a group whose members all have a non-finite row gets no merged row
+                    table = self.buffer(np.zeros(max(16, int(rq.stride) * groups), np.uint8))
+                    made.append(table)
+                    self.merge_rows(member_group, pn, tables[-1], rq.stride, data=prev, dst=table, count=count, query=rq)
+                    tables.append(table)
                 levels.append((dst, groups))
                 links.append(member_group)
             first = [0]
@@ -1598,7 +1691,12 @@ class Context:
                     self.lod_append(buf, m, nodes, parent, 0)
                 else:
                     self.lod_append(buf, m, nodes, parent, first[k], member_group=links[k - 1], child_first=first[k - 1], c=levels[k - 1][1])
-            return LodForest(nodes, parent, first)
+            if rows is None:
+                return LodForest(nodes, parent, first)
+            forest_rows = self.buffer(nbytes=max(16, int(rq.stride) * first[-1]))
+            for k, (_, m) in enumerate(levels):
+                self.copy_rows(tables[k], m, rq.stride, dst=forest_rows, dst_first=first[k])
+            return LodForest(nodes, parent, first, rows=forest_rows, row_stride=int(rq.stride), row_width=int(rq.width))
         finally:
             for b in made:
                 self.delete(b)
@@ -1616,6 +1714,14 @@ class Context:
         self._chk(_lib.gs4d_lod_cut(self._h, int(forest.nodes), int(forest.parent), int(forest.n), C.byref(q), int(dst or 0), int(cut_index or 0),
                                     int(stats or 0), int(count)))
         return count
+
+    def lod_rows(self, forest, cut_index, m, dst=None):
+        """The rows of a cut: gather_records of forest.rows (a LodForest built with a table) through the cut_index of lod_cut, m of its entries —
+        slot j of `dst` (a new buffer if None) <- the row of node cut_index[j].  Per frame: lod_cut, lod_rows, shade_sh, keygen, sort, draw.
+        Asynchronous; returns `dst`."""
+        if forest.rows is None:
+            raise ValueError("lod_rows: the forest carries no rows (build_lod(..., rows=...))")
+        return self.gather_records(cut_index, m, forest.rows, forest.n, stride=forest.row_stride, dst=dst)
 
     def read_lod_count(self, count):
         """The LOD_COUNT row (drawn, written, tested, drawn_leaves) of a lod_cut call; blocks until its kernels have finished."""

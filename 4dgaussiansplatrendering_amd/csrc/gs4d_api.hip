@@ -20,6 +20,7 @@
 #include "merge_record.h"
 #include "lod_query.h"
 #include "lod_operands.h"
+#include "rows_operands.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -2234,6 +2235,50 @@ int gs4d_merge_records(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf labels, co
                                            (gs4d_merge_count*)ops.ptr(count)));
             return (int)GS4D_OK;
         });
+}
+
+// ---- one merged row of a table per group: the SH row of a merged record ----
+int gs4d_merge_rows(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf member_group, gs4d_buf rows, const gs4d_rows_query* query, gs4d_buf dst, size_t dst_first,
+                    gs4d_buf count) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "merge_rows";
+    const gs4d_rows_query q = query ? *query : gs4d_rows_query{ 0u, 0u, 0u, 0u };
+    if (const char* fault = merge_rows_fault(query != nullptr, q.stride, q.width, q.flags, q.reserved, n, dst_first)) return refuse(c, fn, fault);
+    static_assert(sizeof(gs4d_merge_count) == 16, "the rows of rows_operands.h");
+    Operand list[MERGE_ROWS_OPERANDS];                         // (rows_operands.h: what the call does with each)
+    merge_rows_operands(list, data, n, member_group, rows, q.stride, dst, count);
+    Operands ops{ list[0], list[1], list[2], list[3], list[4] };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    const size_t capacity = ops.buffer(dst)->bytes / q.stride;  // rows dst holds: no row >= capacity is ever written
+    return queue_operands(c, ops,
+        [&](Lane& L) {
+            if (n == 0) return (int)GS4D_OK;
+            HIPCHK(c, grow_device_array(L.s, L.neighbour_scratch, L.neighbour_cap, merge_rows_scratch_words(n)));
+            HIPCHK(c, sort_scratch_reserve(L.s, L.pair_sort, n));      // (the tile sort's scratch, as gs4d_merge_records)
+            return (int)GS4D_OK;
+        },
+        [&](Lane& L) {
+            HIPCHK(c, launch_merge_rows(L.s, L.pair_sort, ops.ptr(data), n, (const uint32_t*)ops.ptr(member_group), ops.ptr(rows), q, L.neighbour_scratch, ops.ptr(dst),
+                                        dst_first, capacity, (gs4d_merge_count*)ops.ptr(count)));
+            return (int)GS4D_OK;
+        });
+}
+
+int gs4d_copy_rows(gs4d_ctx* c, gs4d_buf src, size_t src_first, size_t m, size_t stride, gs4d_buf dst, size_t dst_first) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "copy_rows";
+    if (const char* fault = copy_rows_fault(src_first, m, stride, dst_first)) return refuse(c, fn, fault);
+    Operand list[COPY_ROWS_OPERANDS];                          // (rows_operands.h: what the call does with each)
+    copy_rows_operands(list, src, src_first, m, stride, dst, dst_first);
+    Operands ops{ list[0], list[1] };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (m == 0) return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_copy_rows(L.s, ops.ptr(src), src_first, m, stride, ops.ptr(dst), dst_first));
+        return (int)GS4D_OK;
+    });
 }
 
 // ---- the view's cut through a forest of merged levels ----

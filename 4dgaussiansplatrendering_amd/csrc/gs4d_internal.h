@@ -637,6 +637,24 @@ inline size_t merge_scratch_words(size_t n) { return 3 * ((n + 3) & ~(size_t)3) 
 hipError_t launch_merge_records(hipStream_t st, SortScratch& sort, const void* records, size_t n, const uint32_t* labels, float alpha_max,
                                 const gs4d_record_stat* stats, const KeepRule& rule, uint32_t* scratch, void* dst, gs4d_merge_group* groups,
                                 uint32_t* member_group, uint32_t cap, gs4d_merge_count* count);
+// The run starts of n > 0 sorted keys, members first and GS4D_ID_NONE behind them (k_merge_count, k_merge_scan, k_merge_heads): start[g] <- the
+// sorted slot of group g's first member, state <- {groups, members}, *count <- {groups, min(groups, cap), members, n - members}, and with
+// member_group given member_group[index[s]] <- the group of sorted slot s.  counts: one word per tile of MERGE_TILE keys.
+hipError_t launch_merge_run_starts(hipStream_t st, const uint32_t* keys, const uint32_t* index, size_t n, uint32_t* counts, uint32_t cap,
+                                   gs4d_merge_count* count, uint32_t* state, uint32_t* start, uint32_t* member_group);
+
+// ---- merge_rows.hip ----
+// gs4d_merge_rows (gs4d.h): one row per value of member_group among the members — a key kernel, the stable sort of the identity by key
+// (`sort`: the lane's pair_sort, reserved for n), the run starts of merge.hip, one thread that counts the written rows, and the row reduction, all on
+// `st`; no workgroup waits for another.  records: null: unit weights; q: validated; capacity: rows of `stride` bytes dst holds (no row >= capacity is
+// written); *count always receives the gs4d_merge_count (n == 0: zeros, one launch).  n, dst_first <= 0xFFFFFFFE.  Nothing but those rows, the count
+// and the scratch is written.
+// scratch: merge_rows_scratch_words(n) words (the lane's neighbour scratch): the layout of merge_scratch_words(n), then one mass word per record
+inline size_t merge_rows_scratch_words(size_t n) { return merge_scratch_words(n) + ((n + 3) & ~(size_t)3); }
+hipError_t launch_merge_rows(hipStream_t st, SortScratch& sort, const void* records, size_t n, const uint32_t* member_group, const void* rows,
+                             const gs4d_rows_query& q, uint32_t* scratch, void* dst, size_t dst_first, size_t capacity, gs4d_merge_count* count);
+// gs4d_copy_rows (gs4d.h): rows dst_first .. of dst <- the m rows of `stride` bytes from src_first on of src, in 16-byte pieces.  One launch; m == 0: none.
+hipError_t launch_copy_rows(hipStream_t st, const void* src, size_t src_first, size_t m, size_t stride, void* dst, size_t dst_first);
 
 // ---- lod.hip ----
 // gs4d_lod_append (gs4d.h): nodes[first + j] <- the 96 bytes of level[j], parent[first + j] <- GS4D_ID_NONE, j < m; parent[child_first + i]

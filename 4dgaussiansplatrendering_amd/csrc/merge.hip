@@ -226,6 +226,16 @@ __global__ __launch_bounds__(MG_THREADS) void k_merge_groups(const f32x4* __rest
 
 __global__ void k_merge_empty(uint4* __restrict__ count) { *count = make_uint4(0u, 0u, 0u, 0u); }
 
+// the run starts of n sorted keys (gs4d_internal.h): k_merge_count, k_merge_scan and k_merge_heads, which gs4d_merge_rows (merge_rows.hip) runs too
+hipError_t launch_merge_run_starts(hipStream_t st, const uint32_t* keys, const uint32_t* index, size_t n, uint32_t* counts, uint32_t cap,
+                                   gs4d_merge_count* count, uint32_t* state, uint32_t* start, uint32_t* member_group) {
+    const uint32_t ntiles = (uint32_t)merge_tiles(n);
+    k_merge_count<<<dim3(ntiles), dim3(MG_THREADS), 0, st>>>(keys, (uint64_t)n, counts);
+    k_merge_scan<<<dim3(1), dim3(1024), 0, st>>>(counts, ntiles, keys, (uint32_t)n, cap, (uint4*)count, state);
+    k_merge_heads<<<dim3(ntiles), dim3(MG_THREADS), 0, st>>>(keys, index, (uint64_t)n, counts, start, member_group);
+    return hipGetLastError();
+}
+
 hipError_t launch_merge_records(hipStream_t st, SortScratch& sort, const void* records, size_t n, const uint32_t* labels, float alpha_max,
                                 const gs4d_record_stat* stats, const KeepRule& rule, uint32_t* scratch, void* dst, gs4d_merge_group* groups,
                                 uint32_t* member_group, uint32_t cap, gs4d_merge_count* count) {
@@ -245,10 +255,7 @@ hipError_t launch_merge_records(hipStream_t st, SortScratch& sort, const void* r
     k_merge_keys<<<dim3(per_record), dim3(MG_THREADS), 0, st>>>((const f32x4*)records, (uint32_t)n, labels, (const uint4*)stats, rule, keys);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = radix_sort_pairs(st, sort, keys, index, n, nullptr, 32, false, true)) != hipSuccess) return e;
-    k_merge_count<<<dim3(ntiles), dim3(MG_THREADS), 0, st>>>(keys, (uint64_t)n, counts);
-    k_merge_scan<<<dim3(1), dim3(1024), 0, st>>>(counts, ntiles, keys, (uint32_t)n, cap, (uint4*)count, state);
-    k_merge_heads<<<dim3(ntiles), dim3(MG_THREADS), 0, st>>>(keys, index, (uint64_t)n, counts, start, member_group);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = launch_merge_run_starts(st, keys, index, n, counts, cap, count, state, start, member_group)) != hipSuccess) return e;
     if (cap) {
         const uint64_t most = n < cap ? n : cap;                // groups that can be written
         k_merge_groups<<<dim3((uint32_t)((most + MG_GROUPS_PER_WG - 1) / MG_GROUPS_PER_WG)), dim3(MG_THREADS), 0, st>>>(

@@ -29,6 +29,7 @@
 #include "../csrc/centre_query.h"
 #include "../csrc/measure_record.h"
 #include "../csrc/merge_record.h"
+#include "../csrc/merge_rows_record.h"
 #include "../csrc/lod_query.h"
 #include "../csrc/neighbour_query.h"
 #include "../csrc/component_union.h"
@@ -591,6 +592,14 @@ void gs4d_host_merge_records(size_t n, const float* rec, const uint32_t* labels,
         if (member_group) for (size_t k = first; k < end; ++k) member_group[member[k]] = g;
     }
     *count = gs4d_merge_count{ g, g, (uint32_t)member.size(), (uint32_t)(n - member.size()) };
+}
+
+// The definition of gs4d_merge_rows (gs4d.h) is host_merge_rows of csrc/merge_rows_record.h, whose word functions the kernels compile too
+void gs4d_host_merge_rows(size_t n, const float* rec, const uint32_t* member_group, const void* rows, const gs4d_rows_query* q, void* dst, size_t dst_first,
+                          size_t capacity, gs4d_merge_count* count) {
+    static_assert(sizeof(gs4d_merge_count) == 4 * sizeof(uint32_t), "the count is four words");
+    if (!q) return;
+    gs4d_rows::host_merge_rows(n, rec, member_group, rows, q->stride, q->width, q->flags, q->reserved, dst, dst_first, capacity, &count->groups);
 }
 
 // The definition of gs4d_lod_cut (gs4d.h) over the text of csrc/lod_query.h, which the kernel compiles too (this file is built with

@@ -15,13 +15,13 @@ endif
 # keygen/sort and preprocess must round exactly like the CPU expressions they are checked against
 STRICT   := -ffp-contract=off
 
-# the build mode is a prerequisite of every object: switching between `make lib`, `make lib TUNING=1`, `make lib COUNT_IDS_PLAIN=1`, `make lib BUILD_PLAIN=1`, `make lib TRANSFORM_STAGED_LOAD=1`, `make lib XFSEL_PLAIN=1`, `make lib POSE_GLOBAL_TABLE=1` and `make lib POSE_WALK=4` rebuilds all of them
-FLAGSTAMP := $(CSRC)/.flags.$(if $(TUNING),tuning,release)$(if $(COUNT_IDS_PLAIN),-plain)$(if $(BUILD_PLAIN),-buildplain)$(if $(TRANSFORM_STAGED_LOAD),-transformstagedload)$(if $(XFSEL_PLAIN),-xfselplain)$(if $(POSE_GLOBAL_TABLE),-poseglobaltable)$(if $(POSE_WALK),-posewalk$(POSE_WALK))
+# the build mode is a prerequisite of every object: switching between `make lib`, `make lib TUNING=1`, `make lib COUNT_IDS_PLAIN=1`, `make lib BUILD_PLAIN=1`, `make lib TRANSFORM_STAGED_LOAD=1`, `make lib XFSEL_PLAIN=1`, `make lib POSE_GLOBAL_TABLE=1`, `make lib POSE_WALK=4`, `make lib ROWS_MASS_RECOMPUTE=1` and `make lib ROWS_CHUNK=16` rebuilds all of them
+FLAGSTAMP := $(CSRC)/.flags.$(if $(TUNING),tuning,release)$(if $(COUNT_IDS_PLAIN),-plain)$(if $(BUILD_PLAIN),-buildplain)$(if $(TRANSFORM_STAGED_LOAD),-transformstagedload)$(if $(XFSEL_PLAIN),-xfselplain)$(if $(POSE_GLOBAL_TABLE),-poseglobaltable)$(if $(POSE_WALK),-posewalk$(POSE_WALK))$(if $(ROWS_MASS_RECOMPUTE),-rowsmassrecompute)$(if $(ROWS_CHUNK),-rowschunk$(ROWS_CHUNK))
 $(FLAGSTAMP):
 	rm -f $(CSRC)/.flags.*
 	touch $@
 
-OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/pose.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/merge.o $(CSRC)/lod.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
+OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/pose.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/merge.o $(CSRC)/merge_rows.o $(CSRC)/lod.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
 
 .PHONY: all lib oracle ref refscene refdraw refgl clean demo sweep
 all: lib oracle demo sweep
@@ -65,6 +65,10 @@ $(CSRC)/measure.o: $(CSRC)/measure.hip $(HD) $(CSRC)/measure_record.h $(CSRC)/ce
 # merge_record.h is the one text of gs4d_cell_labels' and gs4d_merge_records' definitions: the kernels and the host library compile it (tests/merge_record_check.cpp compiles it too; gs4d_api.o takes the grid check from it)
 $(CSRC)/merge.o: $(CSRC)/merge.hip $(HD) $(CSRC)/merge_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+# merge_rows_record.h is the one text of gs4d_merge_rows' definition, on top of merge_record.h: the kernels and the host library compile it (tests/merge_rows_check.cpp compiles it too; gs4d_api.o takes the two row calls' checks and operand lists from rows_operands.h)
+# make ROWS_MASS_RECOMPUTE=1: the row reduction computes every member's mass again from its record instead of reading the word the key kernel left in scratch; make ROWS_CHUNK=16 (or 4, or 32): the words of a row one sub-group reduces, instead of 8 (the measurements of DESIGN.md §4; never the shipped build)
+$(CSRC)/merge_rows.o: $(CSRC)/merge_rows.hip $(HD) $(CSRC)/merge_rows_record.h $(CSRC)/merge_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(ROWS_MASS_RECOMPUTE),-DGS4D_ROWS_MASS_RECOMPUTE) $(if $(ROWS_CHUNK),-DGS4D_ROWS_CHUNK=$(ROWS_CHUNK)) -c $< -o $@
 # lod_query.h is the one text of gs4d_lod_cut's predicates (it takes the centre from centre_query.h): the kernel and the host library compile it (tests/lod_query_check.cpp compiles it too; gs4d_api.o takes the query check from it, and the two calls' operand lists from lod_operands.h); lod.o is built with the flags of shade.o and centres.o
 $(CSRC)/lod.o: $(CSRC)/lod.hip $(HD) $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
@@ -99,10 +103,10 @@ $(CSRC)/slice.o: $(CSRC)/slice.hip $(CSRC)/slice_record.h $(HD) $(CSRC)/gs4d_int
 $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(COUNT_IDS_PLAIN),-DGS4D_COUNT_IDS_PLAIN) -c $< -o $@
 # operands.h is the one text of the record-set calls' buffer-argument check (tests/operand_check.cpp compiles it too)
-$(CSRC)/gs4d_api.o: $(CSRC)/operands.h $(CSRC)/merge_record.h $(CSRC)/lod_operands.h $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(HD)
+$(CSRC)/gs4d_api.o: $(CSRC)/operands.h $(CSRC)/merge_record.h $(CSRC)/lod_operands.h $(CSRC)/rows_operands.h $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(HD)
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gs4d_internal.h $(CSRC)/composite_common.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/transform_record.h $(CSRC)/pose_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/merge_record.h $(CSRC)/lod_query.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
+$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/transform_record.h $(CSRC)/pose_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/merge_record.h $(CSRC)/merge_rows_record.h $(CSRC)/lod_query.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -fvisibility=hidden $(STRICT) -x c++ -c $< -o $@
 
 $(LIB): $(OBJS)

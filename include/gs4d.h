@@ -1243,7 +1243,8 @@ GS4D_API int gs4d_cell_labels(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d
  *     v = W / (double)area_time(out), taken on the output words just written
  *     alpha_out = v < (double)alpha_max ? (float)v : alpha_max
  * A zero or NaN area gives alpha_max.  Mass is preserved unless the clamp acts.  The eight interleaved slots with a fixed tree are what lets
- * eight lanes share a group and still give the host's bits.  SH tables are not merged: groups and member_group carry rows along.
+ * eight lanes share a group and still give the host's bits.  Tables with a row per record — SH tables — are merged by gs4d_merge_rows, below,
+ * under member_group.
  *
  * Outputs.  Group g writes slot g of dst (96 bytes) and groups[g] = {label, size, first = its smallest member index, 0}.  member_group[i], i < n,
  * is g for a member of group g and GS4D_ID_NONE for a non-member: true group numbers, also beyond `written`.  count always receives
@@ -1266,7 +1267,7 @@ GS4D_API int gs4d_cell_labels(gs4d_ctx* ctx, gs4d_buf data, size_t n, const gs4d
  * Cost.  A key kernel, the library's stable 32-bit sort of the identity by key, a count / scan / scatter over the sorted keys, and a segmented
  * reduction with eight lanes per group.  The lane keeps about 12 n bytes of scratch beside the sort's.  A group of a million
  * members is walked by eight lanes: a documented corner.
- * Out of scope: merging SH tables.  Choosing a level per view at draw time is gs4d_lod_cut, below, over a forest of such levels. */
+ * SH tables are merged by gs4d_merge_rows, below.  Choosing a level per view at draw time is gs4d_lod_cut, over a forest of such levels. */
 typedef struct gs4d_merge_query {
     float    alpha_max;    /* the clamp of a merged record's alpha; finite and > 0                   */
     uint32_t flags;        /* must be 0                                                              */
@@ -1277,6 +1278,67 @@ typedef struct gs4d_merge_count { uint32_t groups, written, members, left_out; }
 GS4D_API int gs4d_merge_records(gs4d_ctx* ctx, gs4d_buf data, size_t n, gs4d_buf labels, const gs4d_merge_query* q,
                                 gs4d_buf stats /* 0: every record */, const gs4d_keep_rule* rule /* NULL iff stats == 0 */,
                                 gs4d_buf dst, gs4d_buf groups /* 0 ok */, gs4d_buf member_group /* 0 ok */, gs4d_buf count);
+
+/* ---- merged rows of a table: the SH row of a merged record (no reference counterpart) ----
+ * A trained set keeps its colour in an SH table that gs4d_shade_sh evaluates every frame.  That evaluation is linear in the coefficients before
+ * its clamp, and gs4d_merge_records defines a merged colour as the mass-weighted mean of the members' colours: so the mass-weighted mean of the
+ * members' rows is the SH row of a merged record.  gs4d_merge_rows is that mean over any float32 table with a row per record, under the
+ * member_group a gs4d_merge_records call wrote (or any other grouping).  gs4d_host_merge_rows is this text as code, and the device gives its bits.
+ *
+ * The table.  Row i is the q->stride bytes at rows + i*stride; stride is a multiple of 16, 16 .. 1024 (the rule of gs4d_shade_sh), the same for
+ * rows and dst.  Words 0 .. width-1 of a row (float32) are merged, 1 <= width <= stride / 4; the words at or past width are padding: never looked
+ * at, whatever their bits.
+ *
+ * Weight.  With data given, a_i = mass(rec_i) of gs4d_merge_records, float32, and ok_i is that call's condition on the record: a_i finite and
+ * > 0, words 0..6 and 8..23 finite.  With data == 0, a_i = 1.0f and ok_i holds: a plain mean of rows, for tables that are not colour.
+ *
+ * Member.  Record i < n is a member iff member_group[i] != GS4D_ID_NONE, ok_i, and words 0 .. width-1 of row i are all finite.  Everything a
+ * member adds is finite: the outputs are compared bit for bit without an exemption.
+ *
+ * Groups.  A group is the set of members with one value g of member_group; the values need not be dense.  The members of a group are taken in
+ * ascending record index, k = 0, 1, ....
+ *
+ * A group of one member gives words 0 .. width-1 of its member's row with their bits kept.
+ *
+ * A larger group accumulates in double, every operation rounded on its own, a = (double)a_k.  Member k adds into slot s = k mod 8:
+ *     W[s]    += a
+ *     R[s][j] += a * (double)row_k[j]                              j < width
+ * The eight slots — an empty one is +0.0 — are combined as ((0+1)+(2+3))+((4+5)+(6+7)), then out[j] = (float)(R[j] / W).  This is the rule by
+ * which gs4d_merge_records forms rgb_out: a table whose row is floats 4..6 of its record, merged under the member_group that call wrote, gives
+ * that call's rgb_out bits for every group.
+ *
+ * Outputs.  Group g writes row dst_first + g of dst (computed in 64 bits): words 0 .. width-1 as above, the words from width to stride / 4 as
+ * +0.0.  A row at or beyond capacity = dst bytes / stride is never written, and neither is the row of a g without members: both keep their bytes
+ * (the capacity rule of gs4d_compact_records).  count always receives a gs4d_merge_count: groups = distinct values among the members, written =
+ * those whose row lies below capacity, members, left_out = n - members.  n == 0 writes {0, 0, 0, 0}.  No byte of data, member_group or rows is
+ * written.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: q == NULL; a stride that breaks the rule; width == 0 or 4 width > stride; flags or
+ * reserved != 0; n > 0xFFFFFFFE (the sort takes 2^32 - 2 keys at most); dst_first > 0xFFFFFFFE; member_group, rows, dst or count — or data, when
+ * given — not a live buffer; any two of the buffers being the same buffer; data smaller than 96 n bytes, member_group smaller than 4 n bytes, rows
+ * smaller than n * stride bytes, count smaller than 16 bytes.  Every word of the buffers is data.
+ *
+ * Ordering.  data, member_group and rows are read.  dst and count are kernel writes; dst keeps the rows the call does not name.  A queued
+ * gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first.  The kernels are queued on the current frame lane; the call
+ * returns at once and starts no frame.  It reads the 96-byte records: it never builds, reads or invalidates a SoA shadow.
+ *
+ * Cost.  The key kernel, sort and run starts of gs4d_merge_records, then a reduction with eight lanes per (group, 8 words of the row)
+ * (DESIGN.md §4).  The lane keeps about 16 n bytes of scratch beside the sort's.
+ *
+ * gs4d_copy_rows: rows src_first .. src_first + m - 1 of src go to rows dst_first .. of dst, `stride` bytes each (the rule above) with their bits
+ * kept, in 16-byte pieces, one launch: the table counterpart of gs4d_lod_append's record copy, which lays the rows of a forest out level by level.
+ * src is read; dst is a kernel write that keeps the rest of its contents.  m == 0 with otherwise valid arguments is a no-op.  GS4D_E_INVALID, with
+ * nothing queued and nothing written: a stride that breaks the rule; m, src_first or dst_first above 2^32 - 1; src or dst not a live buffer, or
+ * the same buffer; src smaller than (src_first + m) * stride bytes, dst smaller than (dst_first + m) * stride bytes. */
+typedef struct gs4d_rows_query {
+    uint32_t stride;       /* bytes per row of rows AND of dst: a multiple of 16, 16 .. 1024 (the rule of gs4d_shade_sh) */
+    uint32_t width;        /* float32 words of a row that are merged: 1 .. stride / 4                */
+    uint32_t flags;        /* must be 0                                                              */
+    uint32_t reserved;     /* must be 0                                                              */
+} gs4d_rows_query;         /* 16 bytes */
+GS4D_API int gs4d_merge_rows(gs4d_ctx* ctx, gs4d_buf data /* 0: unit weights */, size_t n, gs4d_buf member_group, gs4d_buf rows,
+                             const gs4d_rows_query* q, gs4d_buf dst, size_t dst_first, gs4d_buf count);
+GS4D_API int gs4d_copy_rows(gs4d_ctx* ctx, gs4d_buf src, size_t src_first, size_t m, size_t stride, gs4d_buf dst, size_t dst_first);
 
 /* ---- the view's cut through a hierarchy of merged levels (no reference counterpart) ----
  * gs4d_merge_records builds one coarser level of a set.  A camera inside a large scene wants fine records near the eye and merged records far
@@ -1331,7 +1393,10 @@ GS4D_API int gs4d_merge_records(gs4d_ctx* ctx, gs4d_buf data, size_t n, gs4d_buf
  * Cost.  One launch per level from the top down over a plane of one state byte per node in lane scratch (consecutive levels that fit one workgroup
  * together share a launch), then the three kernels of gs4d_compact_records over the plane.  A node whose parent is not DESCEND costs its parent
  * word, the parent's state byte and its own: the cost follows the cut, not the forest.
- * Out of scope: blending between a node and its children across the threshold; SH tables (cut_index carries rows along); frustum tests
+ * A forest's SH table has one row per node, the merged levels' rows from gs4d_merge_rows laid out with gs4d_copy_rows; gs4d_gather_records
+ * through cut_index gives the rows of the cut, and the frame loop becomes gs4d_lod_cut -> gs4d_gather_records (rows) -> gs4d_shade_sh ->
+ * gs4d_keygen -> gs4d_sort_pairs -> draw.
+ * Out of scope: blending between a node and its children across the threshold; frustum tests
  * (gs4d_count_centres has the screen test); choosing the grids; a forest that skips the state plane. */
 GS4D_API int gs4d_lod_append(gs4d_ctx* ctx, gs4d_buf level, size_t m,
                              gs4d_buf member_group /* 0 ok */, size_t child_first, size_t c,
@@ -1468,6 +1533,11 @@ GS4D_API void gs4d_host_cell_labels(size_t n, const float* records24, const gs4d
 GS4D_API void gs4d_host_merge_records(size_t n, const float* records24, const uint32_t* labels, const gs4d_merge_query* q,
                                       const gs4d_record_stat* stats, const gs4d_keep_rule* rule,
                                       float* out24, gs4d_merge_group* groups, uint32_t* member_group, gs4d_merge_count* count);
+/* The definition of gs4d_merge_rows (the text above its declaration) over the text of csrc/merge_rows_record.h: group g of the n rows of `rows`
+ * under member_group goes to row dst_first + g of the `capacity` rows of dst, and *count receives the four counts.  records24 == NULL: unit
+ * weights.  A query the device call would refuse (NULL included), n or dst_first > 0xFFFFFFFE writes nothing. */
+GS4D_API void gs4d_host_merge_rows(size_t n, const float* records24, const uint32_t* member_group, const void* rows, const gs4d_rows_query* q,
+                                   void* dst, size_t dst_first, size_t capacity, gs4d_merge_count* count);
 /* The definition of gs4d_lod_cut (the text above its declaration) as a plain loop over the levels from the top down, over the text of
  * csrc/lod_query.h: the states of the n nodes of records24 under parent, then the DRAW nodes in ascending index into the first
  * min(drawn, capacity) slots of dst24 and cut_index (either may be NULL), one fragment into the row of every DRAW node of stats (may be NULL),
