@@ -5,34 +5,26 @@
 //   k_build_records<FORM>  one workgroup of BUILD_TILE threads per BUILD_TILE records.  Thread r of the workgroup owns record r of the tile: it loads
 //                          its rows — a 16-byte row with one 16-byte load, a 12-byte row with one 12-byte load; consecutive lanes read consecutive
 //                          rows, so every fetched line is used — and evaluates the record with the text of build_record.h (this file is built with
-//                          the flags of preprocess.hip: round to nearest, no contraction, correctly rounded division and square root).  The cost is
-//                          the output: a thread that stored its own record would put 16 of every 96 bytes on a line per store instruction.  The
-//                          records are staged in LDS instead, six 16-byte pieces per record at a pitch of 7 pieces (odd, as in k_shade_sh: the lanes
-//                          of a 16-byte LDS access fall on different slots of the bank row), and the workgroup then writes the tile's 6 * slots
-//                          pieces with coalesced 16-byte stores.  GS4D_BUILD_PLAIN (make lib BUILD_PLAIN=1) leaves the staging out: the measurement
-//                          of DESIGN.md §4, never the shipped build.
+//                          the flags of preprocess.hip: round to nearest, no contraction, correctly rounded division and square root).  The records
+//                          leave through the staged tile of record_tile.h.  GS4D_BUILD_PLAIN (make lib BUILD_PLAIN=1) leaves the staging out, every
+//                          thread storing its own record: the measurement of DESIGN.md §4, never the shipped build.
 // All byte offsets are 64-bit.  Of the parameters only rows < n are read; of dst only records < n are written.
 #include "gs4d_internal.h"
 #include "build_record.h"
+#include "record_tile.h"
 
 namespace gs4d {
 
 constexpr uint32_t BUILD_THREADS = BUILD_TILE;
-constexpr uint32_t BUILD_PIECES = 6;                  // 16-byte pieces of a record
-#ifndef GS4D_BUILD_PLAIN
-constexpr uint32_t BUILD_PITCH = 7;                   // pieces between two records in LDS
-#endif
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 struct __attribute__((packed, aligned(4))) f32x3 { float x, y, z; };      // a 12-byte row: rows are 4-byte aligned only
 
 template <int FORM>
 __global__ __launch_bounds__(BUILD_THREADS) void k_build_records(BuildParams p, uint32_t n, f32x4* __restrict__ dst) {
 #ifndef GS4D_BUILD_PLAIN
-    __shared__ f32x4 stage[BUILD_TILE * BUILD_PITCH];
+    __shared__ f32x4 stage[BUILD_TILE * RECORD_PITCH];
 #endif
     const uint64_t rec0 = (uint64_t)blockIdx.x * BUILD_TILE;
-    const uint64_t left = (uint64_t)n - rec0;                                            // (the grid has no workgroup past the end: left >= 1)
-    const uint32_t slots = left < BUILD_TILE ? (uint32_t)left : BUILD_TILE;
+    const uint32_t slots = tile_slots((uint64_t)n - rec0, BUILD_TILE);     // (the grid has no workgroup past the end: >= 1)
     if (threadIdx.x < slots) {
         const uint64_t i = rec0 + threadIdx.x;
         const f32x4 q = ((const f32x4*)p.rot)[i], col = ((const f32x4*)p.rgba)[i];
@@ -55,29 +47,22 @@ __global__ __launch_bounds__(BUILD_THREADS) void k_build_records(BuildParams p, 
             gs4d_build::record_4d_2q(pos, qq, q1, s, c, o);
         }
 #ifdef GS4D_BUILD_PLAIN
-        f32x4* const out = dst + i * BUILD_PIECES;
+        put_record(o, dst + i * RECORD_PIECES);
 #else
-        f32x4* const out = stage + threadIdx.x * BUILD_PITCH;
+        put_record(o, stage + threadIdx.x * RECORD_PITCH);
 #endif
-#pragma unroll
-        for (uint32_t k = 0; k < BUILD_PIECES; ++k) out[k] = f32x4{ o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3] };
     }
 #ifndef GS4D_BUILD_PLAIN
     __syncthreads();
-    // work item j of the tile is piece j % 6 of record j / 6, and the tile's pieces are contiguous in dst
-    f32x4* const tile = dst + rec0 * BUILD_PIECES;
-    const uint32_t pieces = slots * BUILD_PIECES;
-#pragma unroll
-    for (uint32_t u = 0; u < BUILD_PIECES; ++u) {
-        const uint32_t j = threadIdx.x + u * BUILD_THREADS;
-        if (j < pieces) { const uint32_t r = j / BUILD_PIECES; tile[j] = stage[r * BUILD_PITCH + (j - r * BUILD_PIECES)]; }
-    }
+    store_staged<BUILD_THREADS>(dst + rec0 * RECORD_PIECES, stage, threadIdx.x, slots * RECORD_PIECES);
 #endif
 }
 
 hipError_t launch_build_records(hipStream_t st, int form, const BuildParams& p, size_t n, void* dst) {
     if (!n) return hipSuccess;
-    const dim3 grid((uint32_t)((n + BUILD_TILE - 1) / BUILD_TILE)), block(BUILD_THREADS);
+    const uint64_t groups = ((uint64_t)n + BUILD_TILE - 1) / BUILD_TILE;
+    if (groups * BUILD_THREADS > 0xFFFFFFFFull) return hipErrorInvalidValue;             // one grid: gridDim.x * blockDim.x stays below 2^32
+    const dim3 grid((uint32_t)groups), block(BUILD_THREADS);
     switch (form) {
         case GS4D_PARAMS_3D: k_build_records<GS4D_PARAMS_3D><<<grid, block, 0, st>>>(p, (uint32_t)n, (f32x4*)dst); break;
         case GS4D_PARAMS_4D_VEL: k_build_records<GS4D_PARAMS_4D_VEL><<<grid, block, 0, st>>>(p, (uint32_t)n, (f32x4*)dst); break;

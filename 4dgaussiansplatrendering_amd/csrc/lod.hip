@@ -25,6 +25,7 @@
 // nodes and parent are only read, and only rows < n; a parent's state is read only for p < n.
 #include "gs4d_internal.h"
 #include "lod_query.h"
+#include "record_tile.h"      // f32x4
 
 namespace gs4d {
 
@@ -32,7 +33,6 @@ namespace lod = gs4d_lod;
 constexpr uint32_t LOD_THREADS = 256, LOD_WAVES = LOD_THREADS / 64, LOD_ROUNDS = LOD_TILE / LOD_THREADS;
 static_assert(LOD_TILE % LOD_THREADS == 0 && LOD_ROUNDS >= 1, "whole rounds");
 static_assert(sizeof(gs4d_lod_count) == sizeof(uint4) && sizeof(gs4d_lod_query) == 112 && offsetof(gs4d_lod_count, tested) == 8, "the structures of gs4d.h");
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- gs4d_lod_append ----
 __global__ __launch_bounds__(LOD_THREADS) void k_lod_append(const uint4* __restrict__ level, uint64_t m, const uint32_t* __restrict__ member_group, uint64_t c,

@@ -26,6 +26,7 @@
 // offsets are 64-bit.  No slot >= cap of dst or groups is written; records, labels and table are only read, and only rows < n.
 #include "gs4d_internal.h"
 #include "merge_record.h"
+#include "record_tile.h"      // f32x4
 
 namespace gs4d {
 
@@ -36,7 +37,6 @@ constexpr uint32_t MG_GROUPS_PER_WG = MG_THREADS / MG_SUB;
 static_assert(MG_SUB == (uint32_t)mg::SLOTS, "one lane per slot");
 static_assert(MG_ROUNDS * MG_WAVES <= 64 && MERGE_TILE % MG_THREADS == 0, "one wave scans the (round, wave) counts of a tile");
 static_assert(sizeof(gs4d_merge_group) == sizeof(uint4) && sizeof(gs4d_merge_count) == sizeof(uint4) && sizeof(gs4d_cell_grid) == 64, "the structures of gs4d.h");
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ---- gs4d_cell_labels ----
 __global__ __launch_bounds__(MG_THREADS) void k_cell_labels(const f32x4* __restrict__ rec, uint32_t n, gs4d_cell_grid g, uint32_t* __restrict__ labels) {

@@ -24,6 +24,7 @@
 // of dst is written; records, member_group and rows are only read, and only rows < n.
 #include "gs4d_internal.h"
 #include "merge_rows_record.h"
+#include "record_tile.h"      // f32x4
 
 namespace gs4d {
 
@@ -40,7 +41,6 @@ constexpr uint32_t CHUNK_PIECES = ROWS_CHUNK / 4;
 static_assert(RW_SUB == (uint32_t)mr::SLOTS, "one lane per slot");
 static_assert(ROWS_CHUNK % 4 == 0 && CHUNK_PIECES >= 1 && CHUNK_PIECES <= RW_SUB, "a lane of the sub-group stores one 16-byte piece of the chunk");
 static_assert(sizeof(gs4d_rows_query) == 16 && sizeof(gs4d_merge_count) == sizeof(uint4), "the structures of gs4d.h");
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ void load_record24(const f32x4* __restrict__ rec, uint64_t i, float r[24]) {
     const f32x4* const p = rec + i * 6u;

@@ -2,15 +2,14 @@
 // a gs4d_affine4 table — one row by index (GS4D_POSE_INDEX) or up to four rows blended by weight (GS4D_POSE_BLEND4) — or copied where the row names
 // no row of the table.
 //
-// One launch (more only past 2^22 workgroups), no workgroup ever waits for another:
+// One launch (more only past RECORD_MAX_GRID workgroups), no workgroup ever waits for another:
 //   k_pose_records  one workgroup of POSE_TILE threads per tile of POSE_TILE records; it takes the tiles t0 + blockIdx.x, + gridDim.x, ... below t1.
-//                   What it keeps from k_transform_records (transform.hip): thread r loads record r of the tile with six 16-byte loads and
-//                   evaluates it with the text of pose_record.h (this file is built with the flags of preprocess.hip: round to nearest, no
-//                   contraction); the results — copied records too, so every tile is written whole — are staged in LDS, six 16-byte pieces per
-//                   record at a pitch of 7 pieces, and after one barrier the workgroup writes the tile's contiguous pieces with coalesced
-//                   16-byte stores.  The bind row is one 4-byte load (INDEX) or two 16-byte loads (BLEND4) per thread.
-//                   What is new is the gather of the table rows, 80 bytes per row and up to four rows per record, by a per-lane index.  Three
-//                   builds were measured:
+//                   Thread r loads record r of the tile with six 16-byte loads and evaluates it with the text of pose_record.h (this file is
+//                   built with the flags of preprocess.hip: round to nearest, no contraction); the results — copied records too, so every tile
+//                   is written whole — leave through the staged tile of record_tile.h.  The bind row is one 4-byte load (INDEX) or two 16-byte
+//                   loads (BLEND4) per thread.
+//                   What is particular is the gather of the table rows, 80 bytes per row and up to four rows per record, by a per-lane index.
+//                   Three builds were measured:
 //                     rows from LDS, one tile   the shipped build: for m <= POSE_LDS_ROWS the workgroup copies the table into LDS (coalesced
 //                                               16-byte loads, from the L2 after the first workgroups) and every thread reads its rows from
 //                                               there; a larger table goes the way below.  One tile per workgroup.
@@ -23,21 +22,17 @@
 // pointer given.
 #include "gs4d_internal.h"
 #include "pose_record.h"
+#include "record_tile.h"
 
 namespace gs4d {
 
 constexpr uint32_t POSE_THREADS = POSE_TILE;
-constexpr uint32_t POSE_PIECES = 6;                   // 16-byte pieces of a record
-constexpr uint32_t POSE_PITCH = 7;                    // pieces between two records in LDS
 constexpr uint32_t POSE_ROW_PIECES = 5;               // 16-byte pieces of a gs4d_affine4
-constexpr uint32_t POSE_MAX_GRID = 1u << 22;          // workgroups per launch: gridDim.x * blockDim.x stays below 2^32
 #ifndef GS4D_POSE_WALK
 #define GS4D_POSE_WALK 1
 #endif
 constexpr uint32_t POSE_WALK = GS4D_POSE_WALK;        // tiles a workgroup with the table in LDS takes
 static_assert(POSE_WALK >= 1 && POSE_WALK <= 64, "make lib POSE_WALK=<1..64>");
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 // rows(j, r): the 20 floats of row j of a table of 16-byte pieces, in global memory or in LDS
 struct PoseRows {
@@ -53,26 +48,23 @@ template <uint32_t FORM, bool LDS_TABLE>
 __global__ __launch_bounds__(POSE_THREADS) void k_pose_records(const f32x4* __restrict__ src, uint32_t n, const f32x4* __restrict__ xf, uint32_t m,
                                                                const unsigned char* __restrict__ bind, uint64_t bind_stride, uint32_t t0, uint32_t t1,
                                                                f32x4* __restrict__ dst) {
-    __shared__ f32x4 stage[POSE_TILE * POSE_PITCH];
+    __shared__ f32x4 stage[POSE_TILE * RECORD_PITCH];
     __shared__ f32x4 table[LDS_TABLE ? POSE_LDS_ROWS * POSE_ROW_PIECES : 1];
     if (LDS_TABLE) {                                                                     // (m <= POSE_LDS_ROWS: launch_pose_records)
         for (uint32_t u = threadIdx.x; u < m * POSE_ROW_PIECES; u += POSE_THREADS) table[u] = xf[u];
         __syncthreads();
     }
     const PoseRows rows{ LDS_TABLE ? table : xf };
-    f32x4* const mine = stage + threadIdx.x * POSE_PITCH;
+    f32x4* const mine = stage + threadIdx.x * RECORD_PITCH;
     for (uint64_t t = (uint64_t)t0 + blockIdx.x; t < t1; t += gridDim.x) {               // (uniform in the workgroup: every thread meets every barrier)
         const uint64_t rec0 = t * POSE_TILE;
-        const uint64_t left = (uint64_t)n - rec0;                                        // (t < t1 <= tiles: left >= 1)
-        const uint32_t slots = left < POSE_TILE ? (uint32_t)left : POSE_TILE;
-        const uint32_t pieces = slots * POSE_PIECES;
+        const uint32_t slots = tile_slots((uint64_t)n - rec0, POSE_TILE);     // (t < t1 <= tiles: >= 1)
         if (threadIdx.x < slots) {
             const uint64_t i = rec0 + threadIdx.x;
-            const f32x4* const rec = src + i * POSE_PIECES;
+            const f32x4* const rec = src + i * RECORD_PIECES;
             const unsigned char* const row = bind + i * bind_stride;
             float in[24], o[24];
-#pragma unroll
-            for (uint32_t k = 0; k < POSE_PIECES; ++k) { const f32x4 v = rec[k]; in[4 * k] = v.x; in[4 * k + 1] = v.y; in[4 * k + 2] = v.z; in[4 * k + 3] = v.w; }
+            load_record(rec, in);
             if (FORM == GS4D_POSE_INDEX) {
                 gs4d_pose::index(rows, m, *(const uint32_t*)row, in, o);
             } else {
@@ -82,17 +74,20 @@ __global__ __launch_bounds__(POSE_THREADS) void k_pose_records(const f32x4* __re
                 const float w[4] = { wv.x, wv.y, wv.z, wv.w };
                 gs4d_pose::blend(rows, m, j, w, in, o);
             }
-#pragma unroll
-            for (uint32_t k = 0; k < POSE_PIECES; ++k) mine[k] = f32x4{ o[4 * k], o[4 * k + 1], o[4 * k + 2], o[4 * k + 3] };
+            put_record(o, mine);
         }
         __syncthreads();
-        f32x4* const tile = dst + rec0 * POSE_PIECES;
+        // store_staged<POSE_THREADS> of record_tile.h, spelled out.  Here the walk stands in a loop, its slot arithmetic is moved in front of the
+        // loop, and with the call the compiler puts it in front of the kernel's argument loads too: every wave then starts some 30
+        // instructions later
+        f32x4* const tile = dst + rec0 * RECORD_PIECES;
+        const uint32_t pieces = slots * RECORD_PIECES;
 #pragma unroll
-        for (uint32_t u = 0; u < POSE_PIECES; ++u) {
+        for (uint32_t u = 0; u < RECORD_PIECES; ++u) {
             const uint32_t j = threadIdx.x + u * POSE_THREADS;
-            if (j < pieces) { const uint32_t r = j / POSE_PIECES; tile[j] = stage[r * POSE_PITCH + (j - r * POSE_PIECES)]; }
+            if (j < pieces) { const uint32_t r = j / RECORD_PIECES; tile[j] = stage[r * RECORD_PITCH + (j - r * RECORD_PIECES)]; }
         }
-        __syncthreads();                                                                 // the next tile's records are staged over these
+        __syncthreads();                                                            // the next tile's records are staged over these
     }
 }
 
@@ -100,15 +95,11 @@ template <uint32_t FORM, bool LDS_TABLE>
 static hipError_t launch_form(hipStream_t st, const void* src, uint32_t n, const void* xf, uint32_t m, const void* bind, size_t bind_stride, void* dst) {
     constexpr uint32_t walk = LDS_TABLE ? POSE_WALK : 1u;                                // tiles per workgroup
     const uint32_t tiles = (uint32_t)(((uint64_t)n + POSE_TILE - 1) / POSE_TILE);        // (n <= 0xFFFFFFFF: tiles <= 2^24)
-    for (uint32_t t0 = 0; t0 < tiles; ) {
-        const uint32_t span = tiles - t0 < POSE_MAX_GRID * walk ? tiles - t0 : POSE_MAX_GRID * walk;
-        k_pose_records<FORM, LDS_TABLE><<<dim3((span + walk - 1) / walk), dim3(POSE_THREADS), 0, st>>>((const f32x4*)src, n, (const f32x4*)xf, m, (const unsigned char*)bind,
-                                                                                                       (uint64_t)bind_stride, t0, t0 + span, (f32x4*)dst);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        t0 += span;
-    }
-    return hipSuccess;
+    return launch_runs(tiles, [&](uint64_t t0, uint32_t span) {                          // spans of tiles: walk of them to a workgroup
+        k_pose_records<FORM, LDS_TABLE><<<dim3(walk_grid(span, walk)), dim3(POSE_THREADS), 0, st>>>((const f32x4*)src, n, (const f32x4*)xf, m, (const unsigned char*)bind,
+                                                                                                    (uint64_t)bind_stride, (uint32_t)t0, (uint32_t)t0 + span, (f32x4*)dst);
+        return hipGetLastError();
+    }, RECORD_MAX_GRID * walk);
 }
 
 template <uint32_t FORM>

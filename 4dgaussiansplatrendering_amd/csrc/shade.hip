@@ -13,12 +13,12 @@
 // All byte offsets are 64-bit.  Nothing outside floats 4..6 of records < n (and .xyz of the same entries of the plane) is written; of the table
 // only the first 16 Q bytes of rows < n are read.
 #include "gs4d_internal.h"
+#include "record_tile.h"      // f32x4
 
 namespace gs4d {
 
 constexpr uint32_t SH_THREADS = SHADE_TILE;
 constexpr float SH_INF = __builtin_huge_valf();
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // the constants of the 3DGS reference implementation (computeColorFromSH), rounded to float32
 constexpr float SH_C0 = 0.28209479177387814f, SH_C1 = 0.4886025119029199f;

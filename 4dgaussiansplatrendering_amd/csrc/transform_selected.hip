@@ -2,7 +2,7 @@
 // under one 4D affine map about a pivot — mean L (mu - c) + o + c, covariance L Sigma L^T, colour copied — the pivot given, or taken on the device
 // from the 96 bytes of a gs4d_measure.
 //
-// One launch (more only past 2^22 workgroups), no workgroup ever waits for another and no wave waits for another — there is no barrier:
+// One launch (more only past RECORD_MAX_GRID workgroups), no workgroup ever waits for another and no wave waits for another — there is no barrier:
 //   k_transform_selected  one workgroup of XFSEL_TILE threads per XFSEL_TILE records, each wave on its own 64 of them.  Thread r loads row r of the
 //                         tile's table rows first (one 16-byte load, 1 KiB of consecutive rows per wave, through keep_row: the predicate of
 //                         gs4d_edit_colours); the ballot of the wave's selected lanes is its selected mask, uniform in the wave.  A wave in which
@@ -12,80 +12,63 @@
 //                         and the pivot are kernel arguments, uniform; with GS4D_XS_PIVOT_MEASURE the pivot is gs4d_transform::measure_centre
 //                         of the measurement, read with uniform loads and evaluated in double by the waves that hold a selected record — the
 //                         same value in every lane, no launch of its own.
-//                         The output is what costs, as in k_transform_records: a thread that stores its own record puts 16 of every 96 bytes
-//                         on a line per store instruction.  A wave with at least XFSEL_STAGE_MIN selected records stages them in its own
-//                         quarter of the LDS array instead, six 16-byte pieces per record at a pitch of 7 pieces (odd: the lanes of a 16-byte
-//                         LDS access fall on different slots of the bank row), and then walks the 6 * 64 contiguous pieces of its records with
-//                         coalesced 16-byte stores, leaving out the pieces of records whose bit in the selected mask is clear: a run of
-//                         selected records is written as whole lines, and a record that is not selected is never touched.  The LDS operations
-//                         of one wave execute in order, so the wave needs no barrier between staging and walking — only a wavefront-scope
-//                         fence, which keeps the compiler from moving the reads up.  A wave with fewer selected records lets each of them
-//                         store its own six pieces: the walk's six masked store instructions and the LDS round trip cost more than the few
-//                         partial lines (the threshold is measured: DESIGN.md §4).  GS4D_XFSEL_PLAIN (make lib XFSEL_PLAIN=1) is the plain
-//                         form throughout — no LDS: the measurement of DESIGN.md §4, never the shipped build.
+//                         A wave with at least XFSEL_STAGE_MIN selected records stages them in its own quarter of the LDS array — the
+//                         staged tile of record_tile.h, a wave's 64 records wide — and then walks the 6 * 64 contiguous pieces of its records,
+//                         leaving out the pieces of records whose bit in the selected mask is clear: a run of selected records is written as
+//                         whole lines, and a record that is not selected is never touched.  The LDS operations of one wave execute in order,
+//                         so the wave needs no barrier between staging and walking — only a wavefront-scope fence, which keeps the compiler
+//                         from moving the reads up.  A wave with fewer selected records lets each of them store its own six pieces: the
+//                         walk's six masked store instructions and the LDS round trip cost more than the few partial lines (the threshold is
+//                         measured: DESIGN.md §4).  GS4D_XFSEL_PLAIN (make lib XFSEL_PLAIN=1) is the plain form throughout — no LDS: the
+//                         measurement of DESIGN.md §4, never the shipped build.
 // All byte offsets are 64-bit.  Threads past n neither load nor store; of stats only rows < n are read, of measure its first 96 bytes; of data only
 // the selected records < n are read and written.
 #include "gs4d_internal.h"
 #include "transform_record.h"
+#include "record_tile.h"
 
 namespace gs4d {
 
 constexpr uint32_t XFSEL_THREADS = XFSEL_TILE;
 constexpr uint32_t XFSEL_WAVE = 64;
-constexpr uint32_t XFSEL_PIECES = 6;                  // 16-byte pieces of a record
-constexpr uint32_t XFSEL_PITCH = 7;                   // pieces between two records in LDS
-constexpr uint32_t XFSEL_MAX_GRID = 1u << 22;         // workgroups per launch: gridDim.x * blockDim.x stays below 2^32
 #ifndef GS4D_XFSEL_STAGE_MIN
 #define GS4D_XFSEL_STAGE_MIN 8
 #endif
 constexpr uint32_t XFSEL_STAGE_MIN = GS4D_XFSEL_STAGE_MIN;      // selected records of a wave from which it stages its stores
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 static_assert(XFSEL_TILE % XFSEL_WAVE == 0, "whole waves");
 
 // the record at rec under x about its pivot, to `to` (the record itself, or its slots in LDS)
-template <class To>
-__device__ __forceinline__ void move_record(const f32x4* rec, const gs4d_selection_xf& x, const gs4d_measure* __restrict__ measure, To to) {
+__device__ __forceinline__ void move_record(const f32x4* rec, const gs4d_selection_xf& x, const gs4d_measure* __restrict__ measure, f32x4* to) {
     const bool pivot = x.flags != 0u;                                                    // (GS4D_XS_PIVOT or GS4D_XS_PIVOT_MEASURE: validated)
     float c[3] = { x.pivot[0], x.pivot[1], x.pivot[2] };
     if (x.flags == (uint32_t)GS4D_XS_PIVOT_MEASURE) gs4d_transform::measure_centre(measure->count, measure->lo, measure->hi, (const unsigned long long*)measure->cell_sum, c);
     float in[24], o[24];
-#pragma unroll
-    for (uint32_t p = 0; p < XFSEL_PIECES; ++p) { const f32x4 v = rec[p]; in[4 * p] = v.x; in[4 * p + 1] = v.y; in[4 * p + 2] = v.z; in[4 * p + 3] = v.w; }
+    load_record(rec, in);
     gs4d_transform::record_about(x.xf.l, x.xf.o, pivot, c, in, o);
-#pragma unroll
-    for (uint32_t p = 0; p < XFSEL_PIECES; ++p) to[p] = f32x4{ o[4 * p], o[4 * p + 1], o[4 * p + 2], o[4 * p + 3] };
+    put_record(o, to);
 }
 
 __global__ __launch_bounds__(XFSEL_THREADS) void k_transform_selected(f32x4* data, uint32_t n, gs4d_selection_xf x, const uint4* __restrict__ stats, KeepRule k,
                                                                       const gs4d_measure* __restrict__ measure, uint32_t wg0) {
     const uint64_t rec0 = (uint64_t)(wg0 + blockIdx.x) * XFSEL_TILE;                     // (< n <= 0xFFFFFFFF: launch_transform_selected)
-    const uint64_t left = (uint64_t)n - rec0;                                            // (the grid has no workgroup past the end: left >= 1)
-    const uint32_t slots = left < XFSEL_TILE ? (uint32_t)left : XFSEL_TILE;
+    const uint32_t slots = tile_slots((uint64_t)n - rec0, XFSEL_TILE);                   // (the grid has no workgroup past the end: >= 1)
     const bool selected = threadIdx.x < slots && (!stats || keep_row(stats[rec0 + threadIdx.x], k));
     const uint64_t mask = __ballot(selected);                                            // the wave's selected records, bit = lane
     if (mask == 0ull) return;
-    f32x4* const rec = data + (rec0 + threadIdx.x) * XFSEL_PIECES;
+    f32x4* const rec = data + (rec0 + threadIdx.x) * RECORD_PIECES;
 #ifndef GS4D_XFSEL_PLAIN
     if ((uint32_t)__popcll(mask) >= XFSEL_STAGE_MIN) {                                   // (uniform in the wave)
-        __shared__ f32x4 stage[XFSEL_TILE * XFSEL_PITCH];
+        __shared__ f32x4 stage[XFSEL_TILE * RECORD_PITCH];
         const uint32_t lane = threadIdx.x & (XFSEL_WAVE - 1u), first = threadIdx.x - lane;      // first: the wave's first record of the tile (< slots: mask != 0)
-        f32x4* const mine = stage + first * XFSEL_PITCH;                                 // this wave's quarter; no other wave reads or writes it
-        if (selected) move_record(rec, x, measure, mine + lane * XFSEL_PITCH);
+        f32x4* const mine = stage + first * RECORD_PITCH;                                // this wave's quarter; no other wave reads or writes it
+        if (selected) move_record(rec, x, measure, mine + lane * RECORD_PITCH);
         // (the wave's LDS writes are performed before its LDS reads below: one wave's LDS operations execute in order)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // work item j of the wave is piece j % 6 of its record j / 6, and the pieces of its records are contiguous in data
-        const uint32_t mine_slots = slots - first < XFSEL_WAVE ? slots - first : XFSEL_WAVE;
-        const uint32_t pieces = mine_slots * XFSEL_PIECES;
-        f32x4* const run = data + (rec0 + first) * XFSEL_PIECES;
-#pragma unroll
-        for (uint32_t u = 0; u < XFSEL_PIECES; ++u) {
-            const uint32_t j = lane + u * XFSEL_WAVE;
-            if (j >= pieces) continue;
-            const uint32_t r = j / XFSEL_PIECES;
-            if ((mask >> r) & 1ull) run[j] = mine[r * XFSEL_PITCH + (j - r * XFSEL_PIECES)];
-        }
+        // the wave's records are a tile of their own, XFSEL_WAVE wide, that begins at record `first` of the workgroup's
+        store_staged<XFSEL_WAVE>(data + (rec0 + first) * RECORD_PIECES, mine, lane, tile_slots(slots - first, XFSEL_WAVE) * RECORD_PIECES,
+                                 [mask](uint32_t r) { return ((mask >> r) & 1ull) != 0ull; });
         return;
     }
 #endif
@@ -99,13 +82,10 @@ hipError_t launch_transform_selected(hipStream_t st, void* data, size_t n, const
     if (n > 0xFFFFFFFFull) return hipErrorInvalidValue;
     if (xf.flags == (uint32_t)GS4D_XS_PIVOT_MEASURE ? !measure : xf.flags > (uint32_t)GS4D_XS_PIVOT) return hipErrorInvalidValue;
     const uint64_t groups = (n + XFSEL_TILE - 1) / XFSEL_TILE;
-    for (uint64_t g0 = 0; g0 < groups; g0 += XFSEL_MAX_GRID) {
-        const uint64_t g = groups - g0 < XFSEL_MAX_GRID ? groups - g0 : XFSEL_MAX_GRID;
-        k_transform_selected<<<dim3((uint32_t)g), dim3(XFSEL_THREADS), 0, st>>>((f32x4*)data, (uint32_t)n, xf, (const uint4*)stats, rule, measure, (uint32_t)g0);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+    return launch_runs(groups, [&](uint64_t g0, uint32_t g) {
+        k_transform_selected<<<dim3(g), dim3(XFSEL_THREADS), 0, st>>>((f32x4*)data, (uint32_t)n, xf, (const uint4*)stats, rule, measure, (uint32_t)g0);
+        return hipGetLastError();
+    });
 }
 
 } // namespace gs4d

@@ -52,7 +52,7 @@ $(CSRC)/reorder.o: $(CSRC)/reorder.hip $(CSRC)/gs4d_internal.h include/gs4d.h Ma
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 $(CSRC)/cut.o: $(CSRC)/cut.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
-$(CSRC)/shade.o: $(CSRC)/shade.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/shade.o: $(CSRC)/shade.hip $(CSRC)/record_tile.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 $(CSRC)/edit.o: $(CSRC)/edit.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
@@ -63,14 +63,14 @@ $(CSRC)/centres.o: $(CSRC)/centres.hip $(HD) $(CSRC)/centre_query.h $(CSRC)/gs4d
 $(CSRC)/measure.o: $(CSRC)/measure.hip $(HD) $(CSRC)/measure_record.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # merge_record.h is the one text of gs4d_cell_labels' and gs4d_merge_records' definitions: the kernels and the host library compile it (tests/merge_record_check.cpp compiles it too; gs4d_api.o takes the grid check from it)
-$(CSRC)/merge.o: $(CSRC)/merge.hip $(HD) $(CSRC)/merge_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/merge.o: $(CSRC)/merge.hip $(CSRC)/record_tile.h $(HD) $(CSRC)/merge_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # merge_rows_record.h is the one text of gs4d_merge_rows' definition, on top of merge_record.h: the kernels and the host library compile it (tests/merge_rows_check.cpp compiles it too; gs4d_api.o takes the two row calls' checks and operand lists from rows_operands.h)
 # make ROWS_MASS_RECOMPUTE=1: the row reduction computes every member's mass again from its record instead of reading the word the key kernel left in scratch; make ROWS_CHUNK=16 (or 4, or 32): the words of a row one sub-group reduces, instead of 8 (the measurements of DESIGN.md §4; never the shipped build)
-$(CSRC)/merge_rows.o: $(CSRC)/merge_rows.hip $(HD) $(CSRC)/merge_rows_record.h $(CSRC)/merge_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/merge_rows.o: $(CSRC)/merge_rows.hip $(CSRC)/record_tile.h $(HD) $(CSRC)/merge_rows_record.h $(CSRC)/merge_record.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(ROWS_MASS_RECOMPUTE),-DGS4D_ROWS_MASS_RECOMPUTE) $(if $(ROWS_CHUNK),-DGS4D_ROWS_CHUNK=$(ROWS_CHUNK)) -c $< -o $@
 # lod_query.h is the one text of gs4d_lod_cut's predicates (it takes the centre from centre_query.h): the kernel and the host library compile it (tests/lod_query_check.cpp compiles it too; gs4d_api.o takes the query check from it, and the two calls' operand lists from lod_operands.h); lod.o is built with the flags of shade.o and centres.o
-$(CSRC)/lod.o: $(CSRC)/lod.hip $(HD) $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/lod.o: $(CSRC)/lod.hip $(CSRC)/record_tile.h $(HD) $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # neighbour_query.h is the one text of gs4d_count_neighbours' definition and of its cell function (it takes the centre and the skips from centre_query.h); neighbour_grid.h is the one text of the device's sorted-slot fetch and cell walk, which components.hip and nearest.hip compile too
 $(CSRC)/neighbours.o: $(CSRC)/neighbours.hip $(HD) $(CSRC)/neighbour_grid.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
@@ -81,23 +81,24 @@ $(CSRC)/components.o: $(CSRC)/components.hip $(HD) $(CSRC)/neighbour_grid.h $(CS
 # gs4d_nearest_neighbours walks the grid of neighbours.hip too; nearest_query.h is the one text of its order key, its dist2 and its sorted insertion (the host library compiles it too)
 $(CSRC)/nearest.o: $(CSRC)/nearest.hip $(HD) $(CSRC)/neighbour_grid.h $(CSRC)/nearest_query.h $(CSRC)/neighbour_query.h $(CSRC)/centre_query.h $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+# record_tile.h is the one text of a tile of 96-byte records — the record load, the put, the staged store and load in LDS, f32x4 — and of the host loop that launches the kernels in runs of workgroups (tests/record_tile_check.cpp compiles its plain part too)
 # build_record.h is the one text of the record builders: the kernel and the host library compile it (tests/build_record_check.cpp compiles it too)
 # make BUILD_PLAIN=1: gs4d_build_records with every thread storing its own record, without the LDS staging (the measurement of DESIGN.md §4; never the shipped build)
-$(CSRC)/build.o: $(CSRC)/build.hip $(CSRC)/build_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/build.o: $(CSRC)/build.hip $(CSRC)/record_tile.h $(CSRC)/build_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(BUILD_PLAIN),-DGS4D_BUILD_PLAIN) -c $< -o $@
 # transform_record.h is the one text of the record transforms and of the centre of a measurement: both transform kernels and the host library compile it (tests/transform_record_check.cpp and tests/transform_selected_check.cpp compile it too)
 # make TRANSFORM_STAGED_LOAD=1: gs4d_transform_records with the input staged in LDS like the output, instead of every thread loading its own record (the measurement of DESIGN.md §4; never the shipped build)
-$(CSRC)/transform.o: $(CSRC)/transform.hip $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/transform.o: $(CSRC)/transform.hip $(CSRC)/record_tile.h $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(TRANSFORM_STAGED_LOAD),-DGS4D_TRANSFORM_STAGED_LOAD) -c $< -o $@
 # make XFSEL_PLAIN=1: gs4d_transform_selected with every selected thread storing its own record, without the LDS staging and the wave masks (the measurement of DESIGN.md §4; never the shipped build)
-$(CSRC)/transform_selected.o: $(CSRC)/transform_selected.hip $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/transform_selected.o: $(CSRC)/transform_selected.hip $(CSRC)/record_tile.h $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(XFSEL_PLAIN),-DGS4D_XFSEL_PLAIN) -c $< -o $@
 # pose_record.h is the one text of gs4d_pose_records' definition, on top of transform_record.h: the kernel and the host library compile it (tests/pose_record_check.cpp compiles it too)
 # make POSE_GLOBAL_TABLE=1: gs4d_pose_records with every thread loading its table rows from global memory for every m, without the workgroup's copy of a small table in LDS; make POSE_WALK=4: a workgroup with the table in LDS takes 4 tiles instead of one (the measurements of DESIGN.md §4; never the shipped build)
-$(CSRC)/pose.o: $(CSRC)/pose.hip $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/pose.o: $(CSRC)/pose.hip $(CSRC)/record_tile.h $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(POSE_GLOBAL_TABLE),-DGS4D_POSE_GLOBAL_TABLE) $(if $(POSE_WALK),-DGS4D_POSE_WALK=$(POSE_WALK)) -c $< -o $@
 # slice_record.h is the one text of gs4d_slice_records' definition: the kernel and the host library compile it; slice.o is built with the flags of preprocess.o, so its expf is the draw's
-$(CSRC)/slice.o: $(CSRC)/slice.hip $(CSRC)/slice_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+$(CSRC)/slice.o: $(CSRC)/slice.hip $(CSRC)/record_tile.h $(CSRC)/slice_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # make COUNT_IDS_PLAIN=1: gs4d_count_ids without its in-wave aggregation (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)

@@ -13,7 +13,8 @@ Outputs are sentinel-filled, hold a few bytes more than their slots and are foll
 
 Where the line is: only calls whose records may have a stride of 1024 bytes can pass 4 GiB with a few million records.  The calls on 96-byte records
 (merge, transform, pose, slice, the grid queries) would need 44.7 M records and 4.3 GB of real records for it and are not tested there; neither
-are gs4d_shade_sh and gs4d_nearest_neighbours with rows of 1024 bytes, nor the splits of a launch at 2^30 records (the *_MAX_GRID constants).
+are gs4d_shade_sh and gs4d_nearest_neighbours with rows of 1024 bytes, nor the splits of a launch at 2^30 records (RECORD_MAX_GRID: the loop
+itself is driven on the CPU by tests/record_tile_check.cpp).
 All calls go through the Python binding over the C ABI."""
 import numpy as np
 import pytest
