@@ -301,29 +301,65 @@ struct Src2D { const float* recs; };
 
 __device__ __forceinline__ uint2 project_4d(const float4& pos, const float4& col, const float4& s0, const float4& s1, const float4& s2, const float4& s3,
                                             uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key);
-__device__ __forceinline__ uint2 project_record(const Src4D& src, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
+// A record as loaded, before any of it is used: load_record issues all of a record's loads together, project_record(src, rec, ...) projects what they
+// brought.  The staged loop of k_project_count loads round it + 1's record before it computes round it (the stores through PreOut may alias the source
+// planes as far as the compiler knows: it hoists no load across them by itself).
+struct Rec4D { float4 pos, col, s0, s1, s2, s3; };
+struct Rec4DSym { float4 pos, col, U, V; float2 W; };
+struct Rec4DStatic { float4 A, col, B, C; };
+struct LoadHere {};      // no loaded record: project_record(src, LoadHere, ...) loads where it projects
+__device__ __forceinline__ Rec4D load_record(const Src4D& src, uint32_t i) {
     const float4* __restrict__ soa = src.soa;
     const size_t ps = src.stride;
-    const float4 pos = soa[i], col = soa[ps + i];
-    const float4 s0 = soa[2 * ps + i], s1 = soa[3 * ps + i], s2 = soa[4 * ps + i], s3 = soa[5 * ps + i];
-    return project_4d(pos, col, s0, s1, s2, s3, i, u, out, ks, key);
+    Rec4D r;
+    r.pos = soa[i]; r.col = soa[ps + i];
+    r.s0 = soa[2 * ps + i]; r.s1 = soa[3 * ps + i]; r.s2 = soa[4 * ps + i]; r.s3 = soa[5 * ps + i];
+    return r;
 }
-__device__ __forceinline__ uint2 project_record(const Src4DSym& src, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
+__device__ __forceinline__ Rec4DSym load_record(const Src4DSym& src, uint32_t i) {
     const float4* __restrict__ soa = src.soa;
     const size_t ps = src.stride;
-    const float4 pos = soa[i], col = soa[ps + i], U = soa[2 * ps + i], V = soa[3 * ps + i];
-    const float2 W = reinterpret_cast<const float2*>(soa + 4 * ps)[i];
+    Rec4DSym r;
+    r.pos = soa[i]; r.col = soa[ps + i]; r.U = soa[2 * ps + i]; r.V = soa[3 * ps + i];
+    r.W = reinterpret_cast<const float2*>(soa + 4 * ps)[i];
+    return r;
+}
+__device__ __forceinline__ Rec4DStatic load_record(const Src4DStatic& src, uint32_t i) {
+    const float4* __restrict__ soa = src.soa;
+    const size_t ps = src.stride;
+    Rec4DStatic r;
+    r.A = soa[i]; r.col = soa[ps + i]; r.B = soa[2 * ps + i]; r.C = soa[3 * ps + i];
+    return r;
+}
+// arrived: from here on the record's registers hold what was loaded.  An empty statement that reads and "writes" every field: the compiler waits for the
+// loads before it, and can move nothing that is computed from the record to before it.
+__device__ __forceinline__ void arrived(float4& a) { asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w)); }
+__device__ __forceinline__ void arrived(Rec4DStatic& r) { arrived(r.A); arrived(r.col); arrived(r.B); arrived(r.C); }
+__device__ __forceinline__ void arrived(LoadHere&) {}
+// load_ahead: what the staged loop requests a round ahead — the record of a static source, nothing of any other (their rounds load where they project).
+// Measured (profiles/r11_experiments.txt items 3, 4): the static frame gains; the 96-byte source's kernel, six loads and 24 registers a round ahead,
+// got 4 % slower alone and its frames showed no gain; the symmetric layout was left out untested, not because it failed (no workload of the benchmark reads it); Src3D and Src2D are never staged at scale.
+__device__ __forceinline__ Rec4DStatic load_ahead(const Src4DStatic& src, uint32_t i) { return load_record(src, i); }
+template <class SRC>
+__device__ __forceinline__ LoadHere load_ahead(const SRC&, uint32_t) { return LoadHere{}; }
+__device__ __forceinline__ uint2 project_record(const Src4D&, const Rec4D& r, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
+    return project_4d(r.pos, r.col, r.s0, r.s1, r.s2, r.s3, i, u, out, ks, key);
+}
+__device__ __forceinline__ uint2 project_record(const Src4DSym&, const Rec4DSym& r, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
+    const float4& U = r.U; const float4& V = r.V; const float2& W = r.W;
     // sig[c] = column c; the mirrored elements are the same bits (verified by the repack kernel)
-    return project_4d(pos, col, make_float4(U.x, U.y, U.z, V.x), make_float4(U.y, U.w, W.x, V.y), make_float4(U.z, W.x, W.y, V.z), V, i, u, out, ks, key);
+    return project_4d(r.pos, r.col, make_float4(U.x, U.y, U.z, V.x), make_float4(U.y, U.w, W.x, V.y), make_float4(U.z, W.x, W.y, V.z), V, i, u, out, ks, key);
 }
-__device__ __forceinline__ uint2 project_record(const Src4DStatic& src, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
-    const float4* __restrict__ soa = src.soa;
-    const size_t ps = src.stride;
-    const float4 A = soa[i], col = soa[ps + i], B = soa[2 * ps + i], C = soa[3 * ps + i];
+__device__ __forceinline__ uint2 project_record(const Src4DStatic& src, const Rec4DStatic& r, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
+    const float4& A = r.A; const float4& B = r.B; const float4& C = r.C;
     const float* c = src.cs.v;
-    return project_4d(make_float4(A.x, A.y, A.z, c[0]), col, make_float4(A.w, B.x, B.y, c[1]), make_float4(B.z, B.w, C.x, c[2]), make_float4(C.y, C.z, C.w, c[3]), make_float4(c[4], c[5], c[6], c[7]),
+    return project_4d(make_float4(A.x, A.y, A.z, c[0]), r.col, make_float4(A.w, B.x, B.y, c[1]), make_float4(B.z, B.w, C.x, c[2]), make_float4(C.y, C.z, C.w, c[3]), make_float4(c[4], c[5], c[6], c[7]),
                       i, u, out, ks, key);
 }
+// load, then project: what every caller that has no record in registers runs
+__device__ __forceinline__ uint2 project_record(const Src4D& src, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, load_record(src, i), n, i, u, out, ks, key); }
+__device__ __forceinline__ uint2 project_record(const Src4DSym& src, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, load_record(src, i), n, i, u, out, ks, key); }
+__device__ __forceinline__ uint2 project_record(const Src4DStatic& src, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, load_record(src, i), n, i, u, out, ks, key); }
 __device__ __forceinline__ uint2 project_4d(const float4& pos, const float4& col, const float4& s0, const float4& s1, const float4& s2, const float4& s3,
                                             uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
     float s44 = s3.w;
@@ -383,6 +419,9 @@ __device__ __forceinline__ uint2 project_record(const Src2D& src, uint32_t, uint
     return emit(out, i, valid, q, kx * psx, ky * psy, kx, ky, u.W, u.H, rec[4], rec[5], rec[6], rec[7], true, 0.0f);      // 2D records have no depth
 }
 
+template <class SRC>
+__device__ __forceinline__ uint2 project_record(const SRC& src, LoadHere, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, n, i, u, out, ks, key); }
+
 // One thread per record (the ordered path).
 template <class SRC>
 __global__ __launch_bounds__(256) void k_preprocess(SRC src, uint32_t n, PU u, PreOut out, TileCount tc) {
@@ -429,11 +468,11 @@ __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t
     // at a multiple of 64: a wave is either wholly past the end of the segment (it leaves the loop: wave-uniform, no barrier inside) or stays converged.
     auto staged_first = [&](int it) -> uint32_t { return segf ? i0 + wave * (uint32_t)(STAGE_R * 64) + (uint32_t)it * 64u : i0 + (uint32_t)it * SEG_THREADS; };
     auto staged_lane = [&]() -> uint32_t { return segf ? (threadIdx.x & 63u) : threadIdx.x; };
-    auto round = [&](uint32_t i, int it) {                  // one record per thread; every lane stays for the wave-wide counting
+    auto round = [&](uint32_t i, int it, const auto& rec) {      // one record per thread (rec: loaded earlier, or LoadHere); every lane stays for the wave-wide counting
         TRect r{ 0u, 0u, 0u, 0u, 1u, 0u };
         uint32_t key = 0u;
         if (i < i1) {
-            const uint2 rect = project_record(src, n, i, u, out, tc.ks, key);
+            const uint2 rect = project_record(src, rec, n, i, u, out, tc.ks, key);
             if (COUNT) {
                 if (!FUSE_KEYS && COUNT == 1) tc.skey[i] = key;               // fused: k_bucket_scatter takes the key from the caller's key buffer, written just below
                 r = tile_rect(rect.x, rect.y, (uint32_t)tc.shard_rank, (uint32_t)tc.shard_world);
@@ -453,10 +492,28 @@ __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t
         if (COUNT) count_buckets(h, tc.nb - 1u, (uint32_t)tc.tiles_x, r);
     };
     if (COUNT == 2) {
+        // Software-pipelined (sources with a load_ahead of their own): round it + 1's record is requested before anything of round it is computed, and arrives while round it projects, stores
+        // and counts.  No address at or beyond the segment's end is ever formed (the last plane of a buffer as long as the draw ends exactly there): a
+        // lane whose record lies at or past i1, and every lane of a round that does not exist, asks for the segment's last record, i1 - 1 >= i0, again —
+        // a line its wave or its neighbour has just had — and round() projects nothing for it.  The request stands under no branch on purpose: under
+        // either guard of the round the compiler merges the registers being loaded with "not loaded" where the branch ends, copies them there, and waits
+        // for the loads in front of the copies — where they were issued (profiles/r11_experiments.txt item 2).
+        // rec[it] is written by request(it) alone and read by round it alone, and two are live at a time.  arrived() marks where round it starts: the
+        // wait for its record stands there, behind round it - 1's stores, and nothing computed from the record can be moved up into round it - 1.
+        decltype(load_ahead(src, 0u)) rec[STAGE_R];
+        auto request = [&](int it) { rec[it] = load_ahead(src, min(staged_first(it) + staged_lane(), i1 - 1u)); };
+        request(0);
 #pragma unroll
-        for (int it = 0; it < STAGE_R; ++it) { const uint32_t ib = staged_first(it); if (ib >= i1) break; round(ib + staged_lane(), it); }      // trip count uniform in the wave, registers indexed at compile time
+        for (int it = 0; it < STAGE_R; ++it) {      // trip count uniform in the wave, registers indexed at compile time
+            const uint32_t ib = staged_first(it);
+            if (ib >= i1) break;
+            const uint32_t i = ib + staged_lane();
+            arrived(rec[it]);
+            if (it + 1 < STAGE_R) request(it + 1);
+            round(i, it, rec[it]);
+        }
     } else {
-        for (uint32_t ib = i0; ib < i1; ib += SEG_THREADS) round(ib + threadIdx.x, 0);    // uniform trip count
+        for (uint32_t ib = i0; ib < i1; ib += SEG_THREADS) round(ib + threadIdx.x, 0, LoadHere{});    // uniform trip count
     }
     __syncthreads();
     if (segf) {
