@@ -21,19 +21,10 @@ constexpr int BIN_ITEMS = 4;         // (8 per thread held 154 VGPRs = ONE workg
                                      //  4: 90 VGPRs, two workgroups per CU, 10^7 rectangle gathers in 248 us instead of 322 = 84 % of the device's gather rate)
 constexpr int BIN_WAVES = BIN_THREADS / 64;
 
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        uint32_t t = __shfl_up(v, off, 64);
-        if ((threadIdx.x & 63) >= (unsigned)off) v += t;
-    }
-    return v;
-}
-
 // exclusive scan over the threads of a block; returns the exclusive prefix, total = block sum
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum /* __shared__[BIN_WAVES] */, uint32_t& total) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t inc = wave_incl_scan(v);
+    uint32_t inc = wave_incl_scan_u32(v, lane);
     __syncthreads();                      // protect wsum from the previous round
     if (lane == 63) wsum[w] = inc;
     __syncthreads();

@@ -64,9 +64,7 @@ __global__ __launch_bounds__(1024) void k_compact_scan(uint32_t* __restrict__ co
     for (uint32_t base = 0; base < ntiles; base += 1024u) {
         const uint32_t i = base + threadIdx.x;
         const uint32_t v = i < ntiles ? counts[i] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if ((int)lane >= d) incl += o; }
+        const uint32_t incl = wave_incl_scan_u32(v, lane);
         if (lane == 63u) wave_sum[wave] = incl;
         const uint32_t carry = carry_s;
         __syncthreads();
@@ -100,9 +98,7 @@ __global__ __launch_bounds__(CT_THREADS) void k_compact_scatter(const Row* __res
     __syncthreads();
     if (threadIdx.x < 64u) {
         const uint32_t v = threadIdx.x < CT_ROUNDS * CT_WAVES ? part[threadIdx.x] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if ((int)lane >= d) incl += o; }
+        const uint32_t incl = wave_incl_scan_u32(v, lane);
         part[threadIdx.x] = incl - v;
         if (threadIdx.x == 63u) total_s = incl;
     }

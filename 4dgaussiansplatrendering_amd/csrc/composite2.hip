@@ -46,9 +46,7 @@ struct WaveSort {
         const uint32_t sum = (cc.x + cc.y) + (cc.z + cc.w);
         const bool all = cc.x == E || cc.y == E || cc.z == E || cc.w == E;
         if (__ballot(all) != 0ull) return;                                         // uniform: one digit holds every key — a stable identity
-        uint32_t inc = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(inc, off, 64); if (lane >= (unsigned)off) inc += t; }
+        const uint32_t inc = wave_incl_scan_u32(sum, lane);
         uint32_t run = inc - sum;
         __syncthreads();                                                            // (everybody has read the counts)
         reinterpret_cast<uint4*>(cnt)[lane] = make_uint4(run, run + c[0], run + c[0] + c[1], run + c[0] + c[1] + c[2]);

@@ -98,9 +98,7 @@ __global__ __launch_bounds__(CUT_PICK_THREADS) void k_cut_pick(const uint32_t* _
     uint32_t count = 0;
 #pragma unroll
     for (uint32_t q = 0; q < CUT_PICK_SLICES; ++q) count += part[q][mybin];
-    uint32_t incl = count;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if ((int)lane >= d) incl += o; }
+    uint32_t incl = wave_incl_scan_u32(count, lane);
     if (scans && lane == 63u) wave_sum[wave] = incl;
     __syncthreads();
     if (!scans) return;

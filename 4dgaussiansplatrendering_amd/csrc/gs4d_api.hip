@@ -561,24 +561,28 @@ int order_source(gs4d_ctx* c, Lane& L, const DrawArgs& a, bool regen, bool prepr
 struct FusedBuffers { Buffer* keys = nullptr; Buffer* idx = nullptr; };
 // what the projection kernel does beside projecting: count or write the list entries (unordered: L.tl), generate depth keys and their histograms (fused)
 int fill_tile_count(gs4d_ctx* c, Lane& L, const DrawArgs& a, size_t npre, bool v2, const FusedBuffers& fused, TileCount& tc) {
-    if (v2 && L.tl.staged) { tc.stage_out = L.tl.blocks; tc.scap = L.tl.scap; tc.offs = L.tl.hist + L.tl.hist_cap; tc.abort_word = L.bin.total + TOT_ABORT; tc.seq = L.tl.seq; }
-    if (v2) { tc.sstat = L.tl.sstat; tc.hist = L.tl.hist; tc.skey = L.tl.skey; tc.nb = L.tl.nb; tc.seg = L.tl.seg; tc.rows = L.tl.rows; tc.tiles_x = c->tiles_x; tc.shard_rank = a.shard_rank; tc.shard_world = a.shard_world; tc.ks = a.blend_order.ks; }
+    const bool staged = v2 && L.tl.staged;
+    uint32_t* kh = nullptr;
     if (a.fuse) {
-        tc.ks = a.blend_order.ks;
         if (!fused.keys || !fused.idx) return fail(c, GS4D_E_INVALID, "draw: the key buffers of the queued key generation have been deleted");
         hipError_t he = hipSuccess;
-        uint32_t* kh = sort_hist_slot(L.s, L.depth_sort, npre, &he);
+        kh = sort_hist_slot(L.s, L.depth_sort, npre, &he);
         if (!kh) return hipfail(c, he, "sort_hist_slot");
-        tc.keys_out = (float*)fused.keys->d; tc.idx_out = nullptr /* the depth sort that follows makes the identity index up */; tc.ghist = kh; tc.span = a.blend_order.span; tc.err = L.err_word();
         L.depth_sort.hist_bias = a.blend_order.ks.bias;
         // A staged draw reads no key back (k_bucket_scatter, which takes the keys of an exact-list draw from the caller's buffer, does not run) and nothing
         // observes the buffers before the sort queued behind this draw: its hybrid sort may be segment-fed — the projection leaves each segment's keys
         // grouped by top digit in the sort's own blocks instead of the caller's key buffer, and the sort is k_os_tail alone.
-        const bool staged = v2 && L.tl.staged && L.tl.seg <= SEGFEED_BLOCK;
-        sort_plan_hist(L.depth_sort, npre, a.blend_order.bits, staged ? L.tl.rows : 0u);
-        tc.hist_rb = L.depth_sort.hist_rb; tc.hist_rows = L.depth_sort.hist_rows; tc.hist_top = L.depth_sort.hist_top;
-        if (L.depth_sort.hist_segfeed) { tc.seg_pairs = L.depth_sort.seg_pairs; tc.seg_runs = L.depth_sort.seg_runs; }
+        sort_plan_hist(L.depth_sort, npre, a.blend_order.bits, staged && L.tl.seg <= SEGFEED_BLOCK ? L.tl.rows : 0u);
     }
+    // the form, decided here and nowhere else (hist_segfeed: what sort_plan_hist has just planned — with segments only, so SegmentFed comes with Stage)
+    tc.lists = !v2 ? ProjLists::None : staged ? ProjLists::Stage : ProjLists::Count;
+    tc.keys = !a.fuse ? ProjKeys::None : L.depth_sort.hist_segfeed ? ProjKeys::SegmentFed : ProjKeys::Write;
+    if (v2 || a.fuse) tc.ks = a.blend_order.ks;
+    if (tc.lists != ProjLists::None) { tc.seg = L.tl.seg; tc.hist = L.tl.hist; tc.rows = L.tl.rows; tc.skey = L.tl.skey; tc.nb = L.tl.nb; tc.tiles_x = c->tiles_x; tc.shard_rank = a.shard_rank; tc.shard_world = a.shard_world; tc.sstat = L.tl.sstat; }
+    if (tc.lists == ProjLists::Stage) { tc.stage_out = L.tl.blocks; tc.scap = L.tl.scap; tc.offs = L.tl.hist + L.tl.hist_cap; tc.abort_word = L.bin.total + TOT_ABORT; tc.seq = L.tl.seq; }
+    if (tc.keys != ProjKeys::None) { tc.ghist = kh; tc.hist_rb = L.depth_sort.hist_rb; tc.hist_rows = L.depth_sort.hist_rows; tc.hist_top = L.depth_sort.hist_top; tc.span = a.blend_order.span; tc.err = L.err_word(); }
+    if (tc.keys == ProjKeys::Write) tc.keys_out = (float*)fused.keys->d;      // (idx_out stays null: the depth sort that follows makes the identity index up)
+    if (tc.keys == ProjKeys::SegmentFed) { tc.seg_pairs = L.depth_sort.seg_pairs; tc.seg_runs = L.depth_sort.seg_runs; }
     return GS4D_OK;
 }
 

@@ -56,7 +56,7 @@ struct Uniforms {
 // Every draw is validated after the fact.  Its kernels leave what they found in the lane's DEVICE words (BinScratch::total, TOT_*), the kernels that
 // follow read them there, and a copy for the host lands in the lane's pinned, mapped HOST words (Lane::host_total, HT_*), which resolve_lane
 // decodes behind the lane's event.  The two arrays do NOT share a layout.  Paths: ordered (binning.hip, composite.hip), exact = unordered with
-// exact lists (k_bucket_scan, k_bucket_scatter, k_bucket_tiles, k_composite_v2), staged = unordered with staged lists (k_project_count<.., 2>,
+// exact lists (k_bucket_scan, k_bucket_scatter, k_bucket_tiles, k_composite_v2), staged = unordered with staged lists (k_project_count<SRC, Stage, ..>,
 // k_bucket_tiles_staged, k_composite_v2).  A word that a path does not write keeps what an earlier draw of the lane left.
 constexpr int VERDICT_WORDS = 16;                // 64 bytes each: bin_scratch_reserve, gs4d_create
 // Device words, zeroed when they are allocated:
@@ -105,7 +105,7 @@ struct SortScratch {
     //   hist_rows  how many LSD digit rows the producer counted (OS_MAX_PASSES: all, the plain LSD plan)
     //   hist_top   >= 0: the producer also counted the 9-bit top digit (key - bias) >> hist_top into row OS_TOP_ROW
     //   hist_hybrid  the sort is the MSD/LSD hybrid: one global pass on the top digit, then k_os_tail (hist_rows == 0)
-    //   hist_segfeed the hybrid is segment-fed: a staged projection (k_project_count<SRC, true, 2>) leaves every segment's (key, index) pairs grouped by top digit
+    //   hist_segfeed the hybrid is segment-fed: a staged projection (k_project_count<SRC, Stage, SegmentFed>) leaves every segment's (key, index) pairs grouped by top digit
     //                in seg_pairs and one {count, offset} word per (digit, segment) in seg_runs[512][hist_seg_rows]; the sort is k_os_tail alone, which gathers
     //                its bucket from the segments' runs (no k_os_pass launch; the caller's key buffer holds no unsorted keys in between)
     int hist_rows = 4, hist_top = -1; bool hist_hybrid = false, hist_segfeed = false; uint32_t hist_seg_rows = 0;
@@ -184,6 +184,12 @@ constexpr uint32_t OS_MAX_BINS = 512;                        // digits are 8 or 
 constexpr size_t OS_SLOT_WORDS = (size_t)OS_REPL * OS_MAX_PASSES * OS_MAX_BINS;
 constexpr int OS_TOP_ROW = OS_MAX_PASSES - 1;                // the row of the hybrid sort's 9-bit top digit (a span of <= 27 bits has at most three LSD rows)
 #ifdef __HIPCC__
+// the one wave scan of the kernels: the inclusive sum of v over lanes 0..lane of the wave (lane = threadIdx.x & 63; every lane of the wave calls it)
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, uint32_t lane) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(v, off, 64); if (lane >= (unsigned)off) v += t; }
+    return v;
+}
 // (threads 0..255 of the workgroup call clear and flush: each looks after bins tid and tid + 256)
 __device__ __forceinline__ void os_hist_clear(uint32_t (*h)[OS_MAX_BINS], uint32_t tid) {
 #pragma unroll
@@ -246,31 +252,48 @@ struct BlendOrder { KeySrc ks; int bits = 32; uint32_t span = 0xFFFFFFFFu; };
 // "The n records of buffer `data` at version data_ver, in that order": what a lane's last gs4d_keygen keyed, and what a sort index holds once
 // gs4d_sort_pairs has sorted exactly those keys with their identity index.
 struct SortedBy { BlendOrder order; gs4d_buf data = 0; uint64_t data_ver = 0; size_t n = 0; };
-struct TileCount {                               // hist == nullptr: the ordered path (no counting in the projection kernel)
+// What the projection kernel does beside projecting, as a named form (fill_tile_count decides it; launch_pre switches on it).  The seven legal pairs:
+//   lists None,  keys None | Write                 the ordered path (None, None: k_preprocess, one thread per record; every other pair: k_project_count)
+//   lists Count, keys None | Write                 the unordered path with exact lists: entries counted per bucket (k_bucket_scan and k_bucket_scatter follow)
+//   lists Stage, keys None | Write | SegmentFed    staged lists: the entries are counted, placed and written by the projection kernel itself
+// keys Write and SegmentFed (fused key generation) exist for the 4D sources only: no quad or 2D draw is ever fused (draw_common).  Any other pair:
+// hipErrorInvalidValue.
+enum class ProjLists : uint8_t { None, Count, Stage };
+enum class ProjKeys : uint8_t { None, Write, SegmentFed };
+// The struct is the kernels' argument block: its fields keep the order they had before the form got its name (moving them moves the kernel's argument
+// loads, and three of the staged 4D instances then allocate other registers: profiles/r12_kernel_resources_*.txt), so each field says which form reads it.
+struct TileCount {
+    // lists Count, Stage:
     uint32_t* hist = nullptr;                    // [nb][rows]: entries that the records of segment `row` put into bucket b = tile % nb
     uint32_t rows = 0;
-    uint32_t* skey = nullptr;                    // [records] blend-order key of every record
-    uint32_t nb = 0, seg = 0;                    // buckets (a power of two), records per segment (a multiple of SEG_THREADS; one workgroup walks one segment)
+    uint32_t* skey = nullptr;                    // [records] blend-order key of every record (lists Count, keys None writes it: k_bucket_scatter reads it)
+    uint32_t nb = 0, seg = 0;                    // buckets (a power of two); seg, every k_project_count form: records per segment (a multiple of SEG_THREADS; one workgroup walks one segment)
     int tiles_x = 0, shard_rank = 0, shard_world = 1;
+    // every form: the blend order's key (default: the record index)
     KeySrc ks;
-    // Fused key generation (the draw executes a gs4d_keygen + gs4d_sort_pairs that were queued just before it): the projection kernel also
-    // writes the caller's key and index buffers and accumulates the digit histograms of the depth sort, exactly as k_keygen would
+    // keys Write, SegmentFed — fused key generation (the draw executes a gs4d_keygen + gs4d_sort_pairs that were queued just before it): the projection
+    // kernel also generates the depth keys, bounds-checks them and accumulates the digit histograms of the depth sort, exactly as k_keygen would.
+    // keys_out, idx_out, keys Write alone: the caller's key buffer (idx_out null: the sort that follows makes the identity index up itself)
     float* keys_out = nullptr; uint32_t* idx_out = nullptr; uint32_t* ghist = nullptr; int hist_rb = 8, hist_rows = OS_MAX_PASSES, hist_top = -1 /* SortScratch::hist_rows, hist_top */; uint32_t span = 0xFFFFFFFFu; uint32_t* err = nullptr;
-    // Segment-fed depth sort (SortScratch::hist_segfeed; staged lists only): instead of keys_out[i] the workgroup writes its segment's (key + bias, record) pairs,
+    // keys SegmentFed (SortScratch::hist_segfeed; with lists Stage only): instead of keys_out[i] the workgroup writes its segment's (key + bias, record) pairs,
     // grouped by the 9-bit top digit key >> hist_top and stable in record order inside a digit, to seg_pairs[segment * SEGFEED_BLOCK ...], and one word
-    // count | offset << 12 per (digit, segment) to seg_runs[digit * rows + segment].  null: keys_out is written.
+    // count | offset << 12 per (digit, segment) to seg_runs[digit * rows + segment]
     uint2* seg_pairs = nullptr; uint32_t* seg_runs = nullptr;
+    // lists Count, Stage:
     uint32_t* sstat = nullptr;                   // [rows]: entries of every segment (statistics for the host; every counting launch writes them)
-    // Staged lists (tilelist.hip): the projection kernel itself WRITES the entries.  A workgroup counts its segment's entries per bucket, scans
+    // lists Stage (tilelist.hip): the projection kernel itself WRITES the entries.  A workgroup counts its segment's entries per bucket, scans
     // the counts, places the entries bucket by bucket in LDS and writes them out as ONE dense block: stage_out[segment * scap + offs[b][segment] + k],
-    // k < hist[b][segment].  A segment with more than scap entries stores `seq` into *abort_word instead.  null: count only.
+    // k < hist[b][segment].  A segment with more than scap entries stores `seq` into *abort_word instead.
     uint2* stage_out = nullptr; uint32_t scap = 0; uint32_t* offs = nullptr; uint32_t* abort_word = nullptr; uint32_t seq = 0;
+    // the form (the host reads it: launch_pre; the kernels have it as template arguments)
+    ProjLists lists = ProjLists::None;
+    ProjKeys keys = ProjKeys::None;
 };
 constexpr uint32_t V2_MAX_LIST = 1024;           // longest list the compositor sorts in LDS (beyond ~1000 entries per tile its LDS footprint costs more occupancy than the ordered path's two sort passes cost time).  Longer per-tile lists are cut into depth slabs (below); beyond V2_MAX_SLABS a draw uses the ordered path
 constexpr uint32_t V2_MAX_SLABS = 64;           // a tile's list is kept as `slabs` sub-lists by equal ranges of the blend key: far slab first, each ordered by itself in the compositor (one wave lane holds a sub-list's table entry: <= 64)
 constexpr int STAGE_R = 4;                       // staged lists: records per thread of a segment (kept in registers between the counting and the placing pass): seg <= STAGE_R * SEG_THREADS
 constexpr uint32_t STAGE_MAX_SCAP = 5120;        // ... and entries of a segment block (LDS: 8 bytes each beside the 12 KB the projection kernel has already)
-constexpr int SEG_THREADS = 512;                 // workgroup size of the kernels that walk a segment of records (k_preprocess<.., true>, k_bucket_scatter)
+constexpr int SEG_THREADS = 512;                 // workgroup size of the kernels that walk a segment of records (k_project_count, k_bucket_scatter)
 // list capacities the compositor is instantiated for (64 entries per lane-register): the smallest one >= n
 inline uint32_t v2_list_capacity(uint32_t n) {
     static const uint32_t ladder[] = { 64, 128, 192, 256, 384, 512, 768, 1024 };

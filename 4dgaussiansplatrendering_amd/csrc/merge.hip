@@ -112,9 +112,7 @@ __global__ __launch_bounds__(1024) void k_merge_scan(uint32_t* __restrict__ coun
     for (uint32_t base = 0; base < ntiles; base += 1024u) {
         const uint32_t i = base + threadIdx.x;
         const uint32_t v = i < ntiles ? counts[i] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if ((int)lane >= d) incl += o; }
+        const uint32_t incl = wave_incl_scan_u32(v, lane);
         if (lane == 63u) wave_sum[wave] = incl;
         const uint32_t carry = carry_s;
         __syncthreads();
@@ -151,9 +149,7 @@ __global__ __launch_bounds__(MG_THREADS) void k_merge_heads(const uint32_t* __re
     __syncthreads();
     if (threadIdx.x < 64u) {
         const uint32_t v = threadIdx.x < MG_ROUNDS * MG_WAVES ? part[threadIdx.x] : 0u;
-        uint32_t incl = v;
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(incl, d, 64); if ((int)lane >= d) incl += o; }
+        const uint32_t incl = wave_incl_scan_u32(v, lane);
         part[threadIdx.x] = incl - v;
     }
     __syncthreads();

@@ -12,6 +12,7 @@
 #include "depth_key.h"
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 namespace gs4d {
 
@@ -197,28 +198,13 @@ __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid,
 
 // Unordered draw path (tilelist.hip): the projection kernel also counts, per bucket b = tile % nb, the tile-list entries of the segment
 // of records its workgroup walks (LDS atomics; the row of counts is stored once at the end) and stores each record's blend-order key.
-// Called by all 64 lanes of the wave (`r.count` == 0 for lanes without a record): footprints of more than 16 tiles are counted by the
-// whole wave.
-__device__ __forceinline__ void count_buckets(uint32_t* h, uint32_t nbm, uint32_t tiles_x, const TRect& r) {
+// The wave's walk over the tiles of its 64 footprints: f(tile, key, rec) once per tile, with the key and the index of the record the tile belongs to.
+// Called by all 64 lanes of the wave (`r.count` == 0 for lanes without a record): a lane walks a footprint of at most 16 tiles by itself; one of more is
+// broadcast, record and key with it, and walked by the whole wave.
+template <class F>
+__device__ __forceinline__ void wave_for_each_tile(const TRect& r, uint32_t tiles_x, uint32_t key, uint32_t rec, F f) {
     const bool big = r.count > 16u;
-    if (!big) for_each_tile(r, tiles_x, [&](uint32_t t) { atomicAdd(&h[t & nbm], 1u); });
-    uint64_t m = __ballot(big);
-    const uint32_t lane = threadIdx.x & 63u;
-    while (m) {
-        const int src = __ffsll((long long)m) - 1;
-        m &= m - 1ull;
-        TRect rr;
-        rr.tx0 = __shfl(r.tx0, src, 64); rr.ty0 = __shfl(r.ty0, src, 64); rr.wx = __shfl(r.wx, src, 64);
-        rr.rows = __shfl(r.rows, src, 64); rr.tstep = __shfl(r.tstep, src, 64); rr.count = __shfl(r.count, src, 64);
-        for (uint32_t j = lane; j < rr.count; j += 64u) atomicAdd(&h[tile_of(rr, j, tiles_x) & nbm], 1u);
-    }
-}
-
-// Staged lists, second pass: the same walk again, every entry placed in the workgroup's LDS block at the position a returning LDS atomic on
-// its bucket's cursor hands out (the cursors start at the scanned counts of the first pass).
-__device__ __forceinline__ void place_buckets(uint32_t* cur, uint32_t nbm, uint32_t nbs, uint32_t tiles_x, const TRect& r, uint32_t key, uint32_t rec, uint2* stage) {
-    const bool big = r.count > 16u;
-    if (!big) for_each_tile(r, tiles_x, [&](uint32_t t) { stage[atomicAdd(&cur[t & nbm], 1u)] = make_uint2(key, ((t >> nbs) << 24) | rec); });
+    if (!big) for_each_tile(r, tiles_x, [&](uint32_t t) { f(t, key, rec); });
     uint64_t m = __ballot(big);
     const uint32_t lane = threadIdx.x & 63u;
     while (m) {
@@ -228,8 +214,17 @@ __device__ __forceinline__ void place_buckets(uint32_t* cur, uint32_t nbm, uint3
         rr.tx0 = __shfl(r.tx0, src, 64); rr.ty0 = __shfl(r.ty0, src, 64); rr.wx = __shfl(r.wx, src, 64);
         rr.rows = __shfl(r.rows, src, 64); rr.tstep = __shfl(r.tstep, src, 64); rr.count = __shfl(r.count, src, 64);
         const uint32_t key2 = __shfl(key, src, 64), rec2 = __shfl(rec, src, 64);
-        for (uint32_t j = lane; j < rr.count; j += 64u) { const uint32_t t = tile_of(rr, j, tiles_x); stage[atomicAdd(&cur[t & nbm], 1u)] = make_uint2(key2, ((t >> nbs) << 24) | rec2); }
+        for (uint32_t j = lane; j < rr.count; j += 64u) f(tile_of(rr, j, tiles_x), key2, rec2);
     }
+}
+// first pass: the entries per bucket
+__device__ __forceinline__ void count_buckets(uint32_t* h, uint32_t nbm, uint32_t tiles_x, const TRect& r) {
+    wave_for_each_tile(r, tiles_x, 0u, 0u, [&](uint32_t t, uint32_t, uint32_t) { atomicAdd(&h[t & nbm], 1u); });
+}
+// Staged lists, second pass: the same walk again, every entry placed in the workgroup's LDS block at the position a returning LDS atomic on
+// its bucket's cursor hands out (the cursors start at the scanned counts of the first pass).
+__device__ __forceinline__ void place_buckets(uint32_t* cur, uint32_t nbm, uint32_t nbs, uint32_t tiles_x, const TRect& r, uint32_t key, uint32_t rec, uint2* stage) {
+    wave_for_each_tile(r, tiles_x, key, rec, [&](uint32_t t, uint32_t k, uint32_t i) { stage[atomicAdd(&cur[t & nbm], 1u)] = make_uint2(k, ((t >> nbs) << 24) | i); });
 }
 
 // the depth key k_keygen (sort.hip) writes for this record, as a bit pattern relative to the host-proven lower bound
@@ -307,7 +302,7 @@ __device__ __forceinline__ uint2 project_4d(const float4& pos, const float4& col
 struct Rec4D { float4 pos, col, s0, s1, s2, s3; };
 struct Rec4DSym { float4 pos, col, U, V; float2 W; };
 struct Rec4DStatic { float4 A, col, B, C; };
-struct LoadHere {};      // no loaded record: project_record(src, LoadHere, ...) loads where it projects
+struct LoadHere {};      // no loaded record: project_record(src, LoadHere{}, ...) loads where it projects
 __device__ __forceinline__ Rec4D load_record(const Src4D& src, uint32_t i) {
     const float4* __restrict__ soa = src.soa;
     const size_t ps = src.stride;
@@ -356,10 +351,9 @@ __device__ __forceinline__ uint2 project_record(const Src4DStatic& src, const Re
     return project_4d(make_float4(A.x, A.y, A.z, c[0]), r.col, make_float4(A.w, B.x, B.y, c[1]), make_float4(B.z, B.w, C.x, c[2]), make_float4(C.y, C.z, C.w, c[3]), make_float4(c[4], c[5], c[6], c[7]),
                       i, u, out, ks, key);
 }
-// load, then project: what every caller that has no record in registers runs
-__device__ __forceinline__ uint2 project_record(const Src4D& src, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, load_record(src, i), n, i, u, out, ks, key); }
-__device__ __forceinline__ uint2 project_record(const Src4DSym& src, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, load_record(src, i), n, i, u, out, ks, key); }
-__device__ __forceinline__ uint2 project_record(const Src4DStatic& src, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, load_record(src, i), n, i, u, out, ks, key); }
+// load, then project: what every caller that has no record in registers runs (the 4D sources; Src3D and Src2D read their record where they project, below)
+template <class SRC>
+__device__ __forceinline__ uint2 project_record(const SRC& src, LoadHere, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, load_record(src, i), n, i, u, out, ks, key); }
 __device__ __forceinline__ uint2 project_4d(const float4& pos, const float4& col, const float4& s0, const float4& s1, const float4& s2, const float4& s3,
                                             uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
     float s44 = s3.w;
@@ -383,7 +377,7 @@ __device__ __forceinline__ uint2 project_4d(const float4& pos, const float4& col
     return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, col.x, col.y, col.z, ot * col.w, true, depth);
 }
 
-__device__ __forceinline__ uint2 project_record(const Src3D& src, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key) {
+__device__ __forceinline__ uint2 project_record(const Src3D& src, LoadHere, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key) {
     const float* v = src.verts + (size_t)72 * i;      // vertex 0 of the quad: {vpos2, spos3, col4, sig9}
     float C[3][3];
 #pragma unroll
@@ -396,7 +390,7 @@ __device__ __forceinline__ uint2 project_record(const Src3D& src, uint32_t, uint
     return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, v[5], v[6], v[7], v[8], false, depth);
 }
 
-__device__ __forceinline__ uint2 project_record(const Src2D& src, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key) {
+__device__ __forceinline__ uint2 project_record(const Src2D& src, LoadHere, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key) {
     const float* rec = src.recs + (size_t)12 * i;
     const float* P = u.P;
     float x = rec[0], y = rec[1];
@@ -419,181 +413,214 @@ __device__ __forceinline__ uint2 project_record(const Src2D& src, uint32_t, uint
     return emit(out, i, valid, q, kx * psx, ky * psy, kx, ky, u.W, u.H, rec[4], rec[5], rec[6], rec[7], true, 0.0f);      // 2D records have no depth
 }
 
-template <class SRC>
-__device__ __forceinline__ uint2 project_record(const SRC& src, LoadHere, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, n, i, u, out, ks, key); }
-
 // One thread per record (the ordered path).
 template <class SRC>
 __global__ __launch_bounds__(256) void k_preprocess(SRC src, uint32_t n, PU u, PreOut out, TileCount tc) {
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     uint32_t key;
-    (void)project_record(src, n, i, u, out, tc.ks, key);
+    (void)project_record(src, LoadHere{}, n, i, u, out, tc.ks, key);
 }
 
-// Unordered path (COUNT): workgroup w walks records [w * seg, (w + 1) * seg), SEG_THREADS per round, and leaves the counts of its segment
+// ---- k_project_count: a workgroup projects one segment of the records, and does what the form asks beside (TileCount, gs4d_internal.h) ----
+// lists Count, Stage (the unordered path): workgroup w walks records [w * seg, (w + 1) * seg), SEG_THREADS per round, and leaves the counts of its segment
 // per bucket.
-// FUSE_KEYS: it is also k_keygen (sort.hip) for these records — the key it derives the blend order from IS the depth key: written to the
-// caller's key buffer with the identity index beside it, bounds-checked, and counted into the depth sort's digit histograms.  Without
-// COUNT that is all it adds to the projection: the ordered path's form (the sort follows, then binning.hip reads the sorted index).
+// keys Write, SegmentFed: it is also k_keygen (sort.hip) for these records — the key it derives the blend order from IS the depth key: written to the
+// caller's key buffer with the identity index beside it, bounds-checked, and counted into the depth sort's digit histograms.  With lists None
+// that is all it adds to the projection: the ordered path's form (the sort follows, then binning.hip reads the sorted index).
+// Segment-fed depth sort (keys SegmentFed): the keys do not go to the caller's buffer.  The workgroup ranks them by their 9-bit top digit
+// and writes them, with their record indices, digit after digit into the segment's block, for k_os_tail to gather (sort.hip).
 static_assert(SEGFEED_BLOCK == (uint32_t)(STAGE_R * SEG_THREADS) && SEG_THREADS / 64 == 8 && OS_MAX_PASSES == 4, "segment-fed keys: a block per staged segment; eight waves' counters, four of them in kh");
-constexpr size_t SEGFEED_LDS = (4 * OS_MAX_BINS) * 4 + (size_t)SEGFEED_BLOCK * 8;      // of stage[]: the counters of waves 4..7, then the pairs
-// SEGF: the segment-fed form of <SRC, true, 2> — an instance of its own, so that the others keep their registers
-template <class SRC, bool FUSE_KEYS, int COUNT, bool SEGF = false>      // COUNT: 0 none (ordered path), 1 count per bucket, 2 count + place + write the segment's entries (staged lists)
+
+// The workgroup's LDS.  stage[] is the dynamic part — lists Stage: tc.scap list entries.  A segment-fed producer has all of it free until the list entries are
+// placed, and kh as well (it counts no histogram row there): per-wave digit counters [8][512] in kh (waves 0..3) and stage[0, 8 KB) (waves 4..7), the
+// reordered pairs in stage[8 KB, 24 KB) — launch_segments asks for at least SEGFEED_LDS bytes of stage[].
+constexpr size_t SEGFEED_COUNTERS = (4 * OS_MAX_BINS) * 4;                             // bytes of stage[]: the counters of waves 4..7
+constexpr size_t SEGFEED_LDS = SEGFEED_COUNTERS + (size_t)SEGFEED_BLOCK * 8;           // ... then the pairs
+struct ProjLds {
+    uint32_t* h;                        // lists: the segment's entries per bucket; placing pass: the buckets' cursors
+    uint32_t (*kh)[OS_MAX_BINS];        // keys Write: the digit histograms (os_hist_*); keys SegmentFed: the digit counters of waves 0..3
+    uint32_t* ws;                       // the wave sums of a block scan
+    uint2* stage;
+    __device__ __forceinline__ uint32_t* stage32() const { return reinterpret_cast<uint32_t*>(stage); }
+    __device__ __forceinline__ uint32_t* wave_row(uint32_t k) const { return k < 4u ? kh[k] : stage32() + (k - 4u) * OS_MAX_BINS; }      // segment-fed: the digit counters of wave k
+    __device__ __forceinline__ uint2* pairs() const { return stage + SEGFEED_COUNTERS / sizeof(uint2); }                                  // segment-fed: the reordered pairs
+};
+
+// Round `it` of a staged segment [i0, i1): thread t takes record i0 + it * SEG_THREADS + t.  Segment-fed: a wave owns 256 CONSECUTIVE records, four rounds of 64 —
+// (wave, round, lane) order is then record order, which is what makes the placing of the pairs stable (os_rank_items' layout).  Every round of a wave starts
+// at a multiple of 64: a wave is either wholly past the end of the segment (it leaves the loop: wave-uniform, no barrier inside) or stays converged.
+template <bool SEGF>
+struct StagedRounds {
+    uint32_t i0, i1, wave;
+    __device__ __forceinline__ uint32_t first(int it) const { return SEGF ? i0 + wave * (uint32_t)(STAGE_R * 64) + (uint32_t)it * 64u : i0 + (uint32_t)it * SEG_THREADS; }
+    __device__ __forceinline__ uint32_t lane() const { return SEGF ? (threadIdx.x & 63u) : threadIdx.x; }
+    __device__ __forceinline__ uint32_t record(int it) const { return first(it) + lane(); }              // the record this thread projects in round `it`
+    __device__ __forceinline__ uint32_t ahead(int it) const { return min(record(it), i1 - 1u); }         // ... and the one it requests for it: never beyond the segment's last
+};
+// staged lists: what the placing pass needs of every record this thread projected (seg <= STAGE_R * SEG_THREADS: tile_lists_plan / run_draw)
+template <int R> struct KeptRecords { uint32_t key[R], r0[R], r1[R]; };
+
+// One round of one record per thread (rec: loaded earlier, or LoadHere): project it, keep {key, rectangle} for the placing pass, write or count its depth key,
+// count its list entries per bucket.  Every lane stays for the wave-wide counting.
+template <ProjLists LISTS, ProjKeys KEYS, class SRC, class REC, int R>
+__device__ __forceinline__ void project_round(const SRC& src, const REC& rec, uint32_t n, uint32_t i, uint32_t i1, int it, uint32_t wave, const PU& u, const PreOut& out,
+                                              const TileCount& tc, const ProjLds& lds, KeptRecords<R>& kept) {
+    TRect r{ 0u, 0u, 0u, 0u, 1u, 0u };
+    uint32_t key = 0u;
+    if (i < i1) {
+        const uint2 rect = project_record(src, rec, n, i, u, out, tc.ks, key);
+        if constexpr (LISTS != ProjLists::None) {
+            if (LISTS == ProjLists::Count && KEYS == ProjKeys::None) tc.skey[i] = key;               // fused: k_bucket_scatter takes the key from the caller's key buffer, written just below
+            r = tile_rect(rect.x, rect.y, (uint32_t)tc.shard_rank, (uint32_t)tc.shard_world);
+            if constexpr (LISTS == ProjLists::Stage) { kept.key[it] = key; kept.r0[it] = rect.x; kept.r1[it] = rect.y; }
+        }
+        if constexpr (KEYS != ProjKeys::None) {
+            if constexpr (KEYS == ProjKeys::SegmentFed) {
+                atomicAdd(&lds.wave_row(wave)[(key >> tc.hist_top) & (OS_MAX_BINS - 1u)], 1u);      // the wave's count of the digit; the slot comes from a second walk (segfeed_epilogue)
+            } else {
+                tc.keys_out[i] = __uint_as_float(key + tc.ks.bias);      // the blend key is the depth key's bit pattern relative to the bias
+                if (tc.idx_out) tc.idx_out[i] = i;                        // null: the sort that follows makes up the identity payload itself (radix_sort_pairs)
+            }
+            if (key > tc.span) __hip_atomic_store(tc.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // below the bias wraps to a huge value: caught too
+        }
+    }
+    if constexpr (KEYS == ProjKeys::Write) os_hist_add(lds.kh, key, i < i1, tc.hist_rows, tc.hist_rb, tc.hist_top);       // a hybrid-planned sort: the top-digit row alone (one LDS atomic per record, not three)
+    if constexpr (LISTS != ProjLists::None) count_buckets(lds.h, tc.nb - 1u, (uint32_t)tc.tiles_x, r);
+}
+
+// Segment-fed keys, after the rounds: the segment's (key, record) pairs leave grouped by top digit, stable in record order.
+__device__ __forceinline__ void segfeed_epilogue(const TileCount& tc, const StagedRounds<true>& sr, const ProjLds& lds, const KeptRecords<STAGE_R>& kept) {
+    // thread d: the waves' counts of digit d -> each wave's first slot inside the block (digit runs in order, waves in order inside a run), the run-table
+    // word and the global top-digit histogram (what os_hist_flush would have added)
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    uint32_t wo[SEG_THREADS / 64], cnt = 0;
+#pragma unroll
+    for (int k = 0; k < SEG_THREADS / 64; ++k) { wo[k] = cnt; cnt += lds.wave_row((uint32_t)k)[tid]; }
+    const uint32_t inc = wave_incl_scan_u32(cnt, lane);
+    if (lane == 63u) lds.ws[sr.wave] = inc;
+    __syncthreads();
+    uint32_t first = inc - cnt;
+#pragma unroll
+    for (int k = 0; k < SEG_THREADS / 64; ++k) if ((unsigned)k < sr.wave) first += lds.ws[k];
+#pragma unroll
+    for (int k = 0; k < SEG_THREADS / 64; ++k) lds.wave_row((uint32_t)k)[tid] = first + wo[k];
+    tc.seg_runs[(size_t)tid * tc.rows + blockIdx.x] = cnt | (first << 12);      // both <= SEGFEED_BLOCK
+    if (cnt) atomicAdd(&tc.ghist[((size_t)(blockIdx.x % OS_REPL) * OS_MAX_PASSES + OS_TOP_ROW) * OS_MAX_BINS + tid], cnt);
+    __syncthreads();
+    uint2* const pairs = lds.pairs();
+    uint32_t* const mine = lds.wave_row(sr.wave);
+#pragma unroll
+    for (int q = 0; q < STAGE_R; ++q) {
+        const uint32_t i = sr.first(q) + lane;
+        // Stable without a stored rank: the counter now holds the wave's next free slot of the digit, and a returning LDS atomic hands the slots out to the
+        // lanes of one instruction in ascending lane order (verified on the device at context creation — the hybrid is planned only then: os_rank_items),
+        // instruction after instruction in program order — rounds in order, lanes in order inside a round: record order.
+        if (i < sr.i1) pairs[atomicAdd(&mine[(kept.key[q] >> tc.hist_top) & (OS_MAX_BINS - 1u)], 1u)] = make_uint2(kept.key[q] + tc.ks.bias, i);
+    }
+    __syncthreads();
+    // the block leaves in one piece, 16 bytes (two pairs) per thread and step; a segment of an odd number of records also stores the slot behind its last pair
+    uint4* __restrict__ dst = reinterpret_cast<uint4*>(tc.seg_pairs + (size_t)blockIdx.x * SEGFEED_BLOCK);
+    const uint4* src4 = reinterpret_cast<const uint4*>(pairs);
+    for (uint32_t k = tid; k < (sr.i1 - sr.i0 + 1u) / 2u; k += SEG_THREADS) dst[k] = src4[k];
+    // (ws and stage[] are written again by count_epilogue: behind the barriers of its scan, which every thread reaches after the loop above)
+}
+
+// Lists, after the rounds: the row of counts (one row per bucket: k_bucket_scan / k_bucket_tiles_staged walk along the segments), the segment's total and — staged —
+// the exclusive scan of the counts: where each bucket's run starts inside the segment's block; then the entries are placed there and the block stored.
+// Thread t looks after buckets 2t, 2t + 1.
+template <ProjLists LISTS, class ROUNDS, int R>
+__device__ __forceinline__ void count_epilogue(const TileCount& tc, const ROUNDS& sr, const ProjLds& lds, const KeptRecords<R>& kept) {
+    uint32_t* const h = lds.h;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6, b0 = 2u * tid;
+    const uint32_t c0 = b0 < tc.nb ? h[b0] : 0u, c1 = b0 + 1u < tc.nb ? h[b0 + 1u] : 0u, sum = c0 + c1;
+    // (written out, not wave_incl_scan_u32: with the call here two of the static staged instances allocate other registers, profiles/r12_kernel_resources_*.txt)
+    uint32_t inc = sum;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(inc, off, 64); if (lane >= (unsigned)off) inc += v; }
+    if (lane == 63u) lds.ws[w] = inc;
+    __syncthreads();
+    uint32_t base = 0, total = 0;
+#pragma unroll
+    for (int k = 0; k < SEG_THREADS / 64; ++k) { const uint32_t v = lds.ws[k]; if ((unsigned)k < w) base += v; total += v; }
+    const uint32_t o0 = base + inc - sum, o1 = o0 + c0;
+    if (b0 < tc.nb) tc.hist[(size_t)b0 * tc.rows + blockIdx.x] = c0;
+    if (b0 + 1u < tc.nb) tc.hist[(size_t)(b0 + 1u) * tc.rows + blockIdx.x] = c1;
+    if (tid == 0u) tc.sstat[blockIdx.x] = total;
+    if constexpr (LISTS == ProjLists::Stage) {
+        if (b0 < tc.nb) { tc.offs[(size_t)b0 * tc.rows + blockIdx.x] = o0; h[b0] = o0; }
+        if (b0 + 1u < tc.nb) { tc.offs[(size_t)(b0 + 1u) * tc.rows + blockIdx.x] = o1; h[b0 + 1u] = o1; }
+        const bool fits = total <= tc.scap;            // uniform (every thread added up the same ws[])
+        if (!fits && tid == 0u) *tc.abort_word = tc.seq;      // the block cannot hold this segment: the draw is re-run with exact lists (every writer stores the same value)
+        __syncthreads();
+        if (fits) {
+            const uint32_t nbs = (uint32_t)__ffs((int)tc.nb) - 1u;
+#pragma unroll
+            for (int q = 0; q < STAGE_R; ++q) {
+                const uint32_t i = sr.record(q);                          // the record this thread projected in round q
+                if (sr.first(q) >= sr.i1) break;                          // uniform in the wave
+                const TRect r = i < sr.i1 ? tile_rect(kept.r0[q], kept.r1[q], (uint32_t)tc.shard_rank, (uint32_t)tc.shard_world) : TRect{ 0u, 0u, 0u, 0u, 1u, 0u };
+                place_buckets(h, tc.nb - 1u, nbs, (uint32_t)tc.tiles_x, r, kept.key[q], i, lds.stage);
+            }
+            __syncthreads();
+            // the block leaves the workgroup in one piece: consecutive threads, consecutive 16-byte pieces
+            uint4* __restrict__ dst = reinterpret_cast<uint4*>(tc.stage_out + (size_t)blockIdx.x * tc.scap);
+            const uint4* src4 = reinterpret_cast<const uint4*>(lds.stage);
+            for (uint32_t k = tid; k < (total + 1u) / 2u; k += SEG_THREADS) dst[k] = src4[k];
+        }
+    }
+}
+
+// SegmentFed: the segment-fed form of <SRC, Stage, Write> — an instance of its own, so that the others keep their registers
+template <class SRC, ProjLists LISTS, ProjKeys KEYS>      // the form: TileCount::lists, TileCount::keys
 __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t n, PU u, PreOut out, TileCount tc) {
-    __shared__ uint32_t h[COUNT ? 1024 : 1];
-    __shared__ uint32_t kh[FUSE_KEYS ? OS_MAX_PASSES : 1][OS_MAX_BINS];
+    constexpr bool COUNTS = LISTS != ProjLists::None, STAGES = LISTS == ProjLists::Stage, KEYED = KEYS != ProjKeys::None, SEGF = KEYS == ProjKeys::SegmentFed;
+    static_assert(!SEGF || STAGES, "segment-fed keys come from the staged, fused projection");
+    __shared__ uint32_t h[COUNTS ? 1024 : 1];
+    __shared__ uint32_t kh[KEYED ? OS_MAX_PASSES : 1][OS_MAX_BINS];
     __shared__ uint32_t ws[SEG_THREADS / 64 + 1];
-    extern __shared__ __attribute__((aligned(16))) uint2 stage[];      // COUNT == 2: tc.scap entries (copied out 16 bytes at a time: 16-byte base)
-    // Segment-fed depth sort (TileCount::seg_pairs): the keys do not go to the caller's buffer.  The workgroup ranks them by their 9-bit top digit
-    // and writes them, with their record indices, digit after digit into the segment's block, for k_os_tail to gather (sort.hip).  LDS, all of it free until the
-    // list entries are placed: per-wave digit counters [8][512] in kh (waves 0..3: a segment-fed producer counts no histogram row there) and stage[0, 8 KB)
-    // (waves 4..7), the reordered pairs in stage[8 KB, 24 KB) — launch_pre asks for at least 24 KB of stage[].
-    static_assert(!SEGF || (FUSE_KEYS && COUNT == 2), "segment-fed keys come from the staged, fused projection");
-    constexpr bool segf = SEGF;
+    extern __shared__ __attribute__((aligned(16))) uint2 stage[];      // (copied out 16 bytes at a time: 16-byte base)
+    const ProjLds lds{ h, kh, ws, stage };
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    uint32_t* const stage32 = reinterpret_cast<uint32_t*>(stage);
-    auto wave_row = [&](uint32_t k) -> uint32_t* { return k < 4u ? kh[FUSE_KEYS ? k : 0] : stage32 + (k - 4u) * OS_MAX_BINS; };      // the digit counters of wave k
-    if (COUNT) for (uint32_t b = threadIdx.x; b < tc.nb; b += SEG_THREADS) h[b] = 0u;
-    if (FUSE_KEYS && threadIdx.x < 256u) os_hist_clear(kh, threadIdx.x);
-    if (segf) for (uint32_t q = threadIdx.x; q < 4u * OS_MAX_BINS; q += SEG_THREADS) stage32[q] = 0u;
+    if (COUNTS) for (uint32_t b = threadIdx.x; b < tc.nb; b += SEG_THREADS) h[b] = 0u;
+    if (KEYED && threadIdx.x < 256u) os_hist_clear(kh, threadIdx.x);
+    if (SEGF) for (uint32_t q = threadIdx.x; q < SEGFEED_COUNTERS / 4; q += SEG_THREADS) lds.stage32()[q] = 0u;
     __syncthreads();
     const uint32_t i0 = blockIdx.x * tc.seg, i1 = min(n, i0 + tc.seg);
-    // staged lists: what the placing pass needs of every record this thread projected (seg <= STAGE_R * SEG_THREADS: tile_lists_plan / run_draw)
-    uint32_t s_key[COUNT == 2 ? STAGE_R : 1], s_r0[COUNT == 2 ? STAGE_R : 1], s_r1[COUNT == 2 ? STAGE_R : 1];
+    const StagedRounds<SEGF> sr{ i0, i1, wave };
+    KeptRecords<STAGES ? STAGE_R : 1> kept;
 #pragma unroll
-    for (int q = 0; q < (COUNT == 2 ? STAGE_R : 1); ++q) { s_key[q] = 0u; s_r0[q] = 1u; s_r1[q] = 0u; }
-    // Round `it` of a staged segment: thread t takes record i0 + it * SEG_THREADS + t.  Segment-fed: a wave owns 256 CONSECUTIVE records, four rounds of 64 —
-    // (wave, round, lane) order is then record order, which is what makes the placing below stable (os_rank_items' layout).  Every round of a wave starts
-    // at a multiple of 64: a wave is either wholly past the end of the segment (it leaves the loop: wave-uniform, no barrier inside) or stays converged.
-    auto staged_first = [&](int it) -> uint32_t { return segf ? i0 + wave * (uint32_t)(STAGE_R * 64) + (uint32_t)it * 64u : i0 + (uint32_t)it * SEG_THREADS; };
-    auto staged_lane = [&]() -> uint32_t { return segf ? (threadIdx.x & 63u) : threadIdx.x; };
-    auto round = [&](uint32_t i, int it, const auto& rec) {      // one record per thread (rec: loaded earlier, or LoadHere); every lane stays for the wave-wide counting
-        TRect r{ 0u, 0u, 0u, 0u, 1u, 0u };
-        uint32_t key = 0u;
-        if (i < i1) {
-            const uint2 rect = project_record(src, rec, n, i, u, out, tc.ks, key);
-            if (COUNT) {
-                if (!FUSE_KEYS && COUNT == 1) tc.skey[i] = key;               // fused: k_bucket_scatter takes the key from the caller's key buffer, written just below
-                r = tile_rect(rect.x, rect.y, (uint32_t)tc.shard_rank, (uint32_t)tc.shard_world);
-                if (COUNT == 2) { s_key[it] = key; s_r0[it] = rect.x; s_r1[it] = rect.y; }
-            }
-            if (FUSE_KEYS) {
-                if (segf) {
-                    atomicAdd(&wave_row(wave)[(key >> tc.hist_top) & (OS_MAX_BINS - 1u)], 1u);      // the wave's count of the digit; the slot comes from a second walk, below
-                } else {
-                    tc.keys_out[i] = __uint_as_float(key + tc.ks.bias);      // the blend key is the depth key's bit pattern relative to the bias
-                    if (tc.idx_out) tc.idx_out[i] = i;                        // null: the sort that follows makes up the identity payload itself (radix_sort_pairs)
-                }
-                if (key > tc.span) __hip_atomic_store(tc.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // below the bias wraps to a huge value: caught too
-            }
-        }
-        if (FUSE_KEYS && !segf) os_hist_add(kh, key, i < i1, tc.hist_rows, tc.hist_rb, tc.hist_top);       // a hybrid-planned sort: the top-digit row alone (one LDS atomic per record, not three)
-        if (COUNT) count_buckets(h, tc.nb - 1u, (uint32_t)tc.tiles_x, r);
-    };
-    if (COUNT == 2) {
+    for (int q = 0; q < (STAGES ? STAGE_R : 1); ++q) { kept.key[q] = 0u; kept.r0[q] = 1u; kept.r1[q] = 0u; }
+    if constexpr (STAGES) {
+        // The rounds of a staged segment, with their look-ahead.
         // Software-pipelined (sources with a load_ahead of their own): round it + 1's record is requested before anything of round it is computed, and arrives while round it projects, stores
         // and counts.  No address at or beyond the segment's end is ever formed (the last plane of a buffer as long as the draw ends exactly there): a
-        // lane whose record lies at or past i1, and every lane of a round that does not exist, asks for the segment's last record, i1 - 1 >= i0, again —
-        // a line its wave or its neighbour has just had — and round() projects nothing for it.  The request stands under no branch on purpose: under
+        // lane whose record lies at or past i1, and every lane of a round that does not exist, asks for the segment's last record, i1 - 1 >= i0, again (StagedRounds::ahead) —
+        // a line its wave or its neighbour has just had — and project_round projects nothing for it.  The request stands under no branch on purpose: under
         // either guard of the round the compiler merges the registers being loaded with "not loaded" where the branch ends, copies them there, and waits
         // for the loads in front of the copies — where they were issued (profiles/r11_experiments.txt item 2).
         // rec[it] is written by request(it) alone and read by round it alone, and two are live at a time.  arrived() marks where round it starts: the
         // wait for its record stands there, behind round it - 1's stores, and nothing computed from the record can be moved up into round it - 1.
+        // (The loop stands here, and request is a lambda: as a function of its own, or with the assignment written out, every staged instance allocates other
+        // registers — the static ones 26 fewer — profiles/r12_kernel_resources_*.txt.)
         decltype(load_ahead(src, 0u)) rec[STAGE_R];
-        auto request = [&](int it) { rec[it] = load_ahead(src, min(staged_first(it) + staged_lane(), i1 - 1u)); };
+        auto request = [&](int it) { rec[it] = load_ahead(src, sr.ahead(it)); };
         request(0);
 #pragma unroll
         for (int it = 0; it < STAGE_R; ++it) {      // trip count uniform in the wave, registers indexed at compile time
-            const uint32_t ib = staged_first(it);
+            const uint32_t ib = sr.first(it);
             if (ib >= i1) break;
-            const uint32_t i = ib + staged_lane();
+            const uint32_t i = ib + sr.lane();
             arrived(rec[it]);
             if (it + 1 < STAGE_R) request(it + 1);
-            round(i, it, rec[it]);
+            project_round<LISTS, KEYS>(src, rec[it], n, i, i1, it, wave, u, out, tc, lds, kept);
         }
-    } else {
-        for (uint32_t ib = i0; ib < i1; ib += SEG_THREADS) round(ib + threadIdx.x, 0, LoadHere{});    // uniform trip count
     }
+    else for (uint32_t ib = i0; ib < i1; ib += SEG_THREADS) project_round<LISTS, KEYS>(src, LoadHere{}, n, ib + threadIdx.x, i1, 0, wave, u, out, tc, lds, kept);    // uniform trip count
     __syncthreads();
-    if (segf) {
-        // thread d: the waves' counts of digit d -> each wave's first slot inside the block (digit runs in order, waves in order inside a run), the run-table
-        // word and the global top-digit histogram (what os_hist_flush would have added)
-        const uint32_t tid = threadIdx.x, lane = tid & 63u;
-        uint32_t wo[SEG_THREADS / 64], cnt = 0;
-#pragma unroll
-        for (int k = 0; k < SEG_THREADS / 64; ++k) { wo[k] = cnt; cnt += wave_row((uint32_t)k)[tid]; }
-        uint32_t inc = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(inc, off, 64); if (lane >= (unsigned)off) inc += v; }
-        if (lane == 63u) ws[wave] = inc;
-        __syncthreads();
-        uint32_t first = inc - cnt;
-#pragma unroll
-        for (int k = 0; k < SEG_THREADS / 64; ++k) if ((unsigned)k < wave) first += ws[k];
-#pragma unroll
-        for (int k = 0; k < SEG_THREADS / 64; ++k) wave_row((uint32_t)k)[tid] = first + wo[k];
-        tc.seg_runs[(size_t)tid * tc.rows + blockIdx.x] = cnt | (first << 12);      // both <= SEGFEED_BLOCK
-        if (cnt) atomicAdd(&tc.ghist[((size_t)(blockIdx.x % OS_REPL) * OS_MAX_PASSES + OS_TOP_ROW) * OS_MAX_BINS + tid], cnt);
-        __syncthreads();
-        uint2* const pairs = stage + (4 * OS_MAX_BINS * 4) / sizeof(uint2);      // behind the counters of waves 4..7: 8 KB in
-        uint32_t* const mine = wave_row(wave);
-#pragma unroll
-        for (int q = 0; q < STAGE_R; ++q) {
-            const uint32_t i = staged_first(q) + lane;
-            // Stable without a stored rank: the counter now holds the wave's next free slot of the digit, and a returning LDS atomic hands the slots out to the
-            // lanes of one instruction in ascending lane order (verified on the device at context creation — the hybrid is planned only then: os_rank_items),
-            // instruction after instruction in program order — rounds in order, lanes in order inside a round: record order.
-            if (i < i1) pairs[atomicAdd(&mine[(s_key[q] >> tc.hist_top) & (OS_MAX_BINS - 1u)], 1u)] = make_uint2(s_key[q] + tc.ks.bias, i);
-        }
-        __syncthreads();
-        // the block leaves in one piece, 16 bytes (two pairs) per thread and step; a segment of an odd number of records also stores the slot behind its last pair
-        uint4* __restrict__ dst = reinterpret_cast<uint4*>(tc.seg_pairs + (size_t)blockIdx.x * SEGFEED_BLOCK);
-        const uint4* src4 = reinterpret_cast<const uint4*>(pairs);
-        for (uint32_t k = tid; k < (i1 - i0 + 1u) / 2u; k += SEG_THREADS) dst[k] = src4[k];
-        // (ws and stage[] are written again below: behind the barriers of the counting part, which every thread reaches after the loop above)
-    }
-    if (COUNT) {
-        // the row of counts (one row per bucket: k_bucket_scan / k_bucket_tiles_staged walk along the segments), the segment's total and — staged —
-        // the exclusive scan of the counts: where each bucket's run starts inside the segment's block.  Thread t looks after buckets 2t, 2t + 1.
-        const uint32_t tid = threadIdx.x, lane = tid & 63u, w = tid >> 6, b0 = 2u * tid;
-        const uint32_t c0 = b0 < tc.nb ? h[b0] : 0u, c1 = b0 + 1u < tc.nb ? h[b0 + 1u] : 0u, sum = c0 + c1;
-        uint32_t inc = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(inc, off, 64); if (lane >= (unsigned)off) inc += v; }
-        if (lane == 63u) ws[w] = inc;
-        __syncthreads();
-        uint32_t base = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < SEG_THREADS / 64; ++k) { const uint32_t v = ws[k]; if ((unsigned)k < w) base += v; total += v; }
-        const uint32_t o0 = base + inc - sum, o1 = o0 + c0;
-        if (b0 < tc.nb) tc.hist[(size_t)b0 * tc.rows + blockIdx.x] = c0;
-        if (b0 + 1u < tc.nb) tc.hist[(size_t)(b0 + 1u) * tc.rows + blockIdx.x] = c1;
-        if (tid == 0u) tc.sstat[blockIdx.x] = total;
-        if (COUNT == 2) {
-            if (b0 < tc.nb) { tc.offs[(size_t)b0 * tc.rows + blockIdx.x] = o0; h[b0] = o0; }
-            if (b0 + 1u < tc.nb) { tc.offs[(size_t)(b0 + 1u) * tc.rows + blockIdx.x] = o1; h[b0 + 1u] = o1; }
-            const bool fits = total <= tc.scap;            // uniform (every thread added up the same ws[])
-            if (!fits && tid == 0u) *tc.abort_word = tc.seq;      // the block cannot hold this segment: the draw is re-run with exact lists (every writer stores the same value)
-            __syncthreads();
-            if (fits) {
-                const uint32_t nbs = (uint32_t)__ffs((int)tc.nb) - 1u;
-#pragma unroll
-                for (int q = 0; q < STAGE_R; ++q) {
-                    const uint32_t i = staged_first(q) + staged_lane();       // the record this thread projected in round q
-                    if (staged_first(q) >= i1) break;                         // uniform in the wave
-                    const TRect r = i < i1 ? tile_rect(s_r0[q], s_r1[q], (uint32_t)tc.shard_rank, (uint32_t)tc.shard_world) : TRect{ 0u, 0u, 0u, 0u, 1u, 0u };
-                    place_buckets(h, tc.nb - 1u, nbs, (uint32_t)tc.tiles_x, r, s_key[q], i, stage);
-                }
-                __syncthreads();
-                // the block leaves the workgroup in one piece: consecutive threads, consecutive 16-byte pieces
-                uint4* __restrict__ dst = reinterpret_cast<uint4*>(tc.stage_out + (size_t)blockIdx.x * tc.scap);
-                const uint4* src4 = reinterpret_cast<const uint4*>(stage);
-                for (uint32_t k = tid; k < (total + 1u) / 2u; k += SEG_THREADS) dst[k] = src4[k];
-            }
-        }
-    }
-    if (FUSE_KEYS && !segf && threadIdx.x < 256u) os_hist_flush(kh, tc.ghist, tc.hist_rows, threadIdx.x, tc.hist_top);
+    if constexpr (SEGF) segfeed_epilogue(tc, sr, lds, kept);
+    if constexpr (COUNTS) count_epilogue<LISTS>(tc, sr, lds, kept);
+    if constexpr (KEYS == ProjKeys::Write) if (threadIdx.x < 256u) os_hist_flush(kh, tc.ghist, tc.hist_rows, threadIdx.x, tc.hist_top);
 }
 
 static PU make_pu(const Uniforms& un, int W, int H) {
@@ -603,23 +630,47 @@ static PU make_pu(const Uniforms& un, int W, int H) {
     return u;
 }
 
+// One launch shape for every form of k_project_count: a workgroup per segment of tc.seg records, stage[] as the form needs it.
+// (segment-fed: stage[] first holds four waves' digit counters and the segment's reordered pairs, 24 KB — no more than the entries of a 1080p frame's segments need anyway)
+template <class SRC, ProjLists LISTS, ProjKeys KEYS>
+static hipError_t launch_segments(hipStream_t st, const SRC& src, size_t n, const PU& pu, const PreOut& out, const TileCount& tc) {
+    size_t lds = LISTS == ProjLists::Stage ? (size_t)tc.scap * 8 : 0;
+    if (KEYS == ProjKeys::SegmentFed) lds = std::max(lds, SEGFEED_LDS);
+    k_project_count<SRC, LISTS, KEYS><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), lds, st>>>(src, (uint32_t)n, pu, out, tc);
+    return hipGetLastError();
+}
+// fused key generation: the 4D sources alone (draw_common fuses a GS4D_MODE_4D_SORTED draw without quads, nothing else) — Src3D and Src2D have no such instance
+template <class SRC> constexpr bool HAS_KEYS = !std::is_same<SRC, Src3D>::value && !std::is_same<SRC, Src2D>::value;
 template <class SRC>
 static hipError_t launch_pre(hipStream_t st, SRC src, size_t n, const Uniforms& un, int W, int H, PreOut out, const TileCount& tc) {
     if (n == 0) return hipSuccess;
-    // (segment-fed: stage[] first holds four waves' digit counters and the segment's reordered pairs, 24 KB — no more than the entries of a 1080p frame's segments need anyway)
-    if (tc.hist && tc.stage_out && tc.keys_out && tc.seg_pairs) k_project_count<SRC, true, 2, true><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), std::max<size_t>((size_t)tc.scap * 8, SEGFEED_LDS), st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
-    else if (tc.hist && tc.stage_out && tc.keys_out) k_project_count<SRC, true, 2><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), (size_t)tc.scap * 8, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
-    else if (tc.hist && tc.stage_out) k_project_count<SRC, false, 2><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), (size_t)tc.scap * 8, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
-    else if (tc.hist && tc.keys_out) k_project_count<SRC, true, 1><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), 0, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
-    else if (tc.hist) k_project_count<SRC, false, 1><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), 0, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
-    else if (tc.keys_out) {
-        // segments sized so that at most 2048 workgroups flush digit histograms (1024 global atomics each)
-        TileCount t2 = tc;
-        t2.seg = (uint32_t)std::max<size_t>(4096, (((n + 2047) / 2048) + SEG_THREADS - 1) / SEG_THREADS * SEG_THREADS);
-        k_project_count<SRC, true, 0><<<dim3((unsigned)((n + t2.seg - 1) / t2.seg)), dim3(SEG_THREADS), 0, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, t2);
+    using L = ProjLists; using K = ProjKeys;
+    const PU pu = make_pu(un, W, H);
+    switch (tc.keys) {
+    case K::None:
+        switch (tc.lists) {
+        case L::None: k_preprocess<SRC><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(src, (uint32_t)n, pu, out, tc); return hipGetLastError();
+        case L::Count: return launch_segments<SRC, L::Count, K::None>(st, src, n, pu, out, tc);
+        case L::Stage: return launch_segments<SRC, L::Stage, K::None>(st, src, n, pu, out, tc);
+        }
+        break;
+    case K::Write:
+        if constexpr (HAS_KEYS<SRC>) switch (tc.lists) {
+        case L::None: {
+            // segments sized so that at most 2048 workgroups flush digit histograms (1024 global atomics each)
+            TileCount t2 = tc;
+            t2.seg = (uint32_t)std::max<size_t>(4096, (((n + 2047) / 2048) + SEG_THREADS - 1) / SEG_THREADS * SEG_THREADS);
+            return launch_segments<SRC, L::None, K::Write>(st, src, n, pu, out, t2);
+        }
+        case L::Count: return launch_segments<SRC, L::Count, K::Write>(st, src, n, pu, out, tc);
+        case L::Stage: return launch_segments<SRC, L::Stage, K::Write>(st, src, n, pu, out, tc);
+        }
+        break;
+    case K::SegmentFed:
+        if constexpr (HAS_KEYS<SRC>) if (tc.lists == L::Stage) return launch_segments<SRC, L::Stage, K::SegmentFed>(st, src, n, pu, out, tc);
+        break;
     }
-    else k_preprocess<SRC><<<dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st>>>(src, (uint32_t)n, make_pu(un, W, H), out, tc);
-    return hipGetLastError();
+    return hipErrorInvalidValue;      // a pair the kernel has no instance for
 }
 hipError_t launch_preprocess_4d(hipStream_t st, const float4* soa, size_t soa_n, const SoaInfo& info, size_t n, const Uniforms& un, int W, int H, PreOut out, const TileCount& tc) {
     if (info.layout == SOA_STATIC3D) { Src4DStatic s{ soa, (uint32_t)soa_n, SoaConsts() }; for (int k = 0; k < 8; ++k) s.cs.v[k] = info.consts[k]; return launch_pre(st, s, n, un, W, H, out, tc); }

@@ -98,11 +98,6 @@ typedef unsigned long long u64;
 
 struct OsBufs { uint32_t* k[3]; uint32_t* v[3]; };      // [0] caller's buffers, [1],[2] scratch
 
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t t = __shfl_up(v, off, 64); if (lane >= (unsigned)off) v += t; }
-    return v;
-}
 __global__ __launch_bounds__(256) void k_os_hist(const uint32_t* __restrict__ keys, uint32_t n_cap, const uint32_t* __restrict__ n_dev, int passes, int rb, int top /* >= 0: the top-digit row as well (os_hist_add) */,
                                                  uint32_t* __restrict__ ghist /* [OS_REPL][4][OS_MAX_BINS], zero on entry */) {
     __shared__ uint32_t h[OS_MAX_PASSES][OS_MAX_BINS];
@@ -623,7 +618,7 @@ __device__ __forceinline__ void ot_wave_range(uint32_t count, uint32_t w, uint32
     end = min(count, first + share);                              // (a wave past the end: end <= first, nothing valid)
 }
 
-// The segment-fed source (SEG): bucket d is not a range of scratch 1 but one run per segment of the staged projection (k_project_count<SRC, true, 2>,
+// The segment-fed source (SEG): bucket d is not a range of scratch 1 but one run per segment of the staged projection (k_project_count<SRC, Stage, SegmentFed>,
 // preprocess.hip), each inside that segment's block of seg_pairs.  s_word[r] = count | offset << 12 of segment r's run, s_first[r] = the runs before it: the
 // runs go to dk / dv[s_first[r] ...] in segment order — segments in record order, a run stable in record order: the bucket in the caller's order, as launch A
 // leaves it.  Eight lanes share a run (about four pairs at 10^6 keys: 489 segments x 512 digits), eight runs per lane are in flight at once, eight pairs of each a round

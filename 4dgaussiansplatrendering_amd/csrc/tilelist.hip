@@ -9,7 +9,7 @@
 //
 //   bucket b = tile % nb   (interleaved: the dense image centre spreads over all buckets),   nb a power of two, tile / nb < 256
 //
-//   k_preprocess<.., true>  (preprocess.hip) walks segment w of the records (one workgroup, `seg` records) and leaves
+//   k_project_count<SRC, Count, ..>  (preprocess.hip) walks segment w of the records (one workgroup, `seg` records) and leaves
 //                           hist[b][w] = entries its records put into bucket b            (LDS atomics, plain stores)
 //   k_bucket_scan           one wave per bucket: exclusive scan along w -> offs[w][b], the slot of run (w, b) inside bucket b; the workgroup
 //                           that finishes last turns the bucket totals into bucket starts and checks the capacity
@@ -20,7 +20,7 @@
 //   k_composite_v2          (composite2.hip)
 //
 // Staged lists (round 4): once a draw of a scene has reported its fullest segment, longest (bucket, segment) run and fullest bucket, the draws
-// that follow skip the scan and the scatter: k_project_count<.., 2> counts, scans and PLACES its segment's entries in LDS and writes them out as
+// that follow skip the scan and the scatter: k_project_count<SRC, Stage, ..> counts, scans and PLACES its segment's entries in LDS and writes them out as
 // one dense block, k_bucket_tiles_staged reads bucket b's run out of every block.  Capacities are guesses (statistics + margin) that the
 // device checks; a draw that does not fit raises total[TOT_ABORT] and is re-run with the exact kernels above.
 //
@@ -80,9 +80,7 @@ __global__ __launch_bounds__(256) void k_bucket_scan(const uint32_t* __restrict_
         for (int j = 0; j < 16; ++j) {
             if ((uint32_t)j * 64u >= rows) break;
             mxr = max(mxr, c[j]);
-            uint32_t inc = c[j];
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(inc, off, 64); if (lane >= (unsigned)off) inc += v; }
+            const uint32_t inc = wave_incl_scan_u32(c[j], lane);
             const uint32_t w = (uint32_t)j * 64u + lane;
             if (w < rows) offs[(size_t)w * nb + b] = carry + inc - c[j];
             carry += __shfl(inc, 63, 64);
@@ -198,9 +196,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bucket_tiles(const uint2* __rest
     const uint32_t cpt = (nc + BT_THREADS - 1u) / BT_THREADS, q0 = tid * cpt;
     uint32_t sum = 0, mx = 0;
     for (uint32_t k = 0; k < cpt; ++k) { const uint32_t q = q0 + k; const uint32_t c = q < nc ? cnt[q] : 0u; sum += c; mx = max(mx, c); }
-    uint32_t inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(inc, off, 64); if (lane >= (unsigned)off) inc += v; }
+    const uint32_t inc = wave_incl_scan_u32(sum, lane);
     if (lane == 63u) ws[w] = inc;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, off, 64));
@@ -235,7 +231,7 @@ __global__ __launch_bounds__(BT_THREADS) void k_bucket_tiles(const uint2* __rest
     // (the entry count, the longest list and the flags reach the host through the compositing kernel that follows: no hand-off here)
 }
 
-// Staged draws: no scan and no scatter kernel ran.  The projection kernel (preprocess.hip, k_project_count<.., 2>) wrote every segment's entries as
+// Staged draws: no scan and no scatter kernel ran.  The projection kernel (preprocess.hip, k_project_count<SRC, Stage, ..>) wrote every segment's entries as
 // one dense block, bucket after bucket: bucket b's run of segment w is blocks[w * scap + offs[b][w] + k], k < hist[b][w].  This workgroup reads its
 // bucket's counts and offsets, turns the counts into a prefix (entry i of the bucket -> run, slot), and gives every thread the same number of
 // CONSECUTIVE entries of the bucket (ceil(T / THREADS) <= KMAX, kept in registers between counting and placing): one binary search for a thread's first
@@ -268,9 +264,7 @@ __global__ __launch_bounds__(THREADS) void k_bucket_tiles_staged(const uint2* __
         spill |= o > scap || c[k] > scap - o;
         tsum += c[k]; tmax = max(tmax, c[k]);
     }
-    uint32_t pinc = tsum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(pinc, off, 64); if (lane >= (unsigned)off) pinc += v; }
+    const uint32_t pinc = wave_incl_scan_u32(tsum, lane);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) tmax = max(tmax, (uint32_t)__shfl_xor(tmax, off, 64));
     const bool wspill = __ballot(spill) != 0ull;
@@ -321,9 +315,7 @@ __global__ __launch_bounds__(THREADS) void k_bucket_tiles_staged(const uint2* __
     const uint32_t cpt = (nc + THREADS - 1u) / THREADS, q0c = tid * cpt;
     uint32_t sum = 0, mx = 0;
     for (uint32_t k = 0; k < cpt; ++k) { const uint32_t q = q0c + k; const uint32_t cq = q < nc ? cnt[q] : 0u; sum += cq; mx = max(mx, cq); }
-    uint32_t inc = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t v = __shfl_up(inc, off, 64); if (lane >= (unsigned)off) inc += v; }
+    const uint32_t inc = wave_incl_scan_u32(sum, lane);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) mx = max(mx, (uint32_t)__shfl_xor(mx, off, 64));
     if (lane == 63u) ws[w] = inc;

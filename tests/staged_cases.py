@@ -1,6 +1,6 @@
 """Scenes for tests/test_gpu_staged_misses.py, and the host's guesses for staged tile lists recomputed from projected records.
 
-A staged draw (csrc/preprocess.hip, k_project_count<.., 2>; csrc/tilelist.hip, k_bucket_tiles_staged) runs on guesses the host made from the
+A staged draw (csrc/preprocess.hip, k_project_count<SRC, Stage, ..>; csrc/tilelist.hip, k_bucket_tiles_staged) runs on guesses the host made from the
 statistics of earlier draws of the same scene (csrc/gs4d_api.hip, run_draw / resolve_lane):
 
 * scap       entries a segment block holds: the fullest segment + an eighth + 64, rounded up to 64;

@@ -502,7 +502,7 @@ def test_projection_matrix_contract_and_near_plane_clip(gs4d, oracle, monkeypatc
     ctx.close()
 
 
-# ---- key generation executed by the draw that consumes it (gs4d_keygen / gs4d_sort_pairs queued, k_project_count<., true>) ----
+# ---- key generation executed by the draw that consumes it (gs4d_keygen / gs4d_sort_pairs queued, k_project_count<SRC, .., Write>) ----
 def _frames_with_late_reads(ctx, gs4d, rec, cams, W, H, key_mode=None):
     """The reference's frame (Scenes.h:305-345): keygen, sort, draw - nothing looks at the key buffers in between; read them afterwards."""
     n = rec.shape[0]

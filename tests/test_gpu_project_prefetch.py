@@ -1,4 +1,4 @@
-"""The staged projection loads round it + 1's record while it computes round it (csrc/preprocess.hip: k_project_count<SRC, FUSE_KEYS, 2, SEGF>,
+"""The staged projection loads round it + 1's record while it computes round it (csrc/preprocess.hip: k_project_count<SRC, Stage, KEYS>,
 load_record / project_record / arrived), through the C ABI, at the ends of segments — where a look-ahead reaches past what a wave or a workgroup
 owns.
 

@@ -1,4 +1,4 @@
-"""The segment-fed depth sort of a staged, fused frame (csrc/preprocess.hip: k_project_count<SRC, true, 2, true> writes every segment's (key, index)
+"""The segment-fed depth sort of a staged, fused frame (csrc/preprocess.hip: k_project_count<SRC, Stage, SegmentFed> writes every segment's (key, index)
 pairs grouped by top digit; csrc/sort.hip: k_os_tail<LB, true> gathers its bucket from the segments' runs, no k_os_pass launch), through the C ABI.
 
 Every case draws frames as the reference's loop does — Clear -> key loop -> sort -> Draw, the draw executing the key generation and the sort — on

@@ -1,4 +1,4 @@
-"""GPU: staged tile lists (csrc/tilelist.hip, k_bucket_tiles_staged; csrc/preprocess.hip, k_project_count<.., 2>).  Once a draw of a scene has
+"""GPU: staged tile lists (csrc/tilelist.hip, k_bucket_tiles_staged; csrc/preprocess.hip, k_project_count<SRC, Stage, ..>).  Once a draw of a scene has
 reported its fullest segment, its longest (bucket, segment) run and its fullest bucket, the following draws let the projection kernel count, scan
 and place its segment's list entries in LDS and write them out as one dense block — no scan and no scatter kernel.  The capacities are guesses
 (statistics plus a margin) that the device checks; a draw that does not fit is re-run exactly.  The picture must not depend on which way the lists
