@@ -111,6 +111,7 @@ def _load():
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_transform_selected": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_pose_records": (i32, [vp, u32, sz, u32, sz, u32, u32, sz, u32, sz]),
+        "gs4d_warp_records": (i32, [vp, u32, sz, u32, vp, u32, sz]),
         "gs4d_slice_records": (i32, [vp, u32, sz, vp, u32, sz]),
         "gs4d_count_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_label_components": (i32, [vp, u32, sz, vp, u32, vp, u32, u32]),
@@ -147,6 +148,7 @@ def _load():
         "gs4d_host_build_records_4d_2q": (None, [sz, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_transform_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_pose_records": (None, [sz, vp, vp, sz, vp, u32, sz, vp]),
+        "gs4d_host_warp_records": (None, [sz, vp, vp, vp, vp]),
         "gs4d_host_slice_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_edit_colours": (None, [sz, vp, vp, vp, vp, vp]),
         "gs4d_host_count_centres": (None, [sz, vp, vp, i32, i32, vp, vp]),
@@ -359,6 +361,62 @@ def pose_records_host(records, xf, bind, form=None, bind_stride=None):
     out = np.zeros_like(rec)
     _lib.gs4d_host_pose_records(rec.shape[0], _ptr(rec), _ptr(rows) if rows.size else None, rows.shape[0], _ptr(table) if table.size else None, form, bind_stride,
                                 _ptr(out))
+    return out
+
+
+class Lattice(C.Structure):
+    """gs4d_lattice (include/gs4d.h): where node 0 stands, the nodes per unit, the nodes per axis (x, y, z, t) and the clamp bits of a
+    gs4d_warp_records call; 64 bytes."""
+    _fields_ = [("lo", C.c_float * 4), ("inv", C.c_float * 4), ("dims", C.c_uint32 * 4), ("clamp", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
+def lattice(lo, hi, dims, clamp=""):
+    """one gs4d_lattice (Lattice) whose first nodes stand at lo and whose last nodes at hi (4 floats each: x, y, z, t), dims nodes along each axis:
+    inv[a] = (dims[a] - 1) / (hi[a] - lo[a]) rounded to float32, 0 for an axis of one node (which takes no part).  clamp: a string over "xyzt",
+    the axes along which a centre outside the lattice is moved to its face instead of leaving the record as it is."""
+    lo64, hi64 = np.asarray(lo, np.float64).reshape(4), np.asarray(hi, np.float64).reshape(4)
+    d = [int(v) for v in dims]
+    if len(d) != 4:
+        raise ValueError("dims must hold 4 node counts (x, y, z, t)")
+    if set(clamp) - set("xyzt"):
+        raise ValueError('clamp must be a string over "xyzt"')
+    with np.errstate(all="ignore"):                          # (hi == lo gives inf: data like any other, nobody is inside then)
+        inv = [(d[a] - 1) / (hi64[a] - lo64[a]) if d[a] >= 2 else 0.0 for a in range(4)]
+    bits = sum(1 << "xyzt".index(ch) for ch in set(clamp))
+    return Lattice((C.c_float * 4)(*lo64), (C.c_float * 4)(*inv), (C.c_uint32 * 4)(*d), bits, (C.c_uint32 * 3)(0, 0, 0))
+
+
+def lattice_points(lat):
+    """the positions of the nodes of a Lattice as float32 [nt, nz, ny, nx, 4] (the order of the nodes in memory), lo[a] + i / inv[a] along an axis
+    of two or more nodes and lo[a] along an axis of one: a displacement field is f(points) - points."""
+    axes = []
+    for a in range(4):
+        i = np.arange(lat.dims[a], dtype=np.float64)
+        axes.append(lat.lo[a] + (i / float(lat.inv[a]) if lat.dims[a] >= 2 else 0.0 * i))
+    t, z, y, x = np.meshgrid(axes[3], axes[2], axes[1], axes[0], indexing="ij")
+    return np.ascontiguousarray(np.stack([x, y, z, t], -1), np.float32)
+
+
+def _lattice_nodes(nodes, lat):
+    """the nodes of a lattice as float32 [count, 4]"""
+    count = int(lat.dims[0]) * int(lat.dims[1]) * int(lat.dims[2]) * int(lat.dims[3])
+    a = _f32(nodes).reshape(-1, 4)
+    if a.shape[0] != count:
+        raise ValueError(f"the lattice has {count} nodes, the array {a.shape[0]}")
+    return a
+
+
+def warp_records_host(records, nodes, lat):
+    """gs4d_host_warp_records, the definition of Context.warp_records: records [n, 24] as [n, 24], record i through the map of the Lattice `lat`
+    whose nodes (dx, dy, dz, dt) are `nodes` ([nt, nz, ny, nx, 4] or anything of that size), linearised at the record's centre; a record whose
+    centre is not inside the lattice is copied.  A lattice the device call would refuse gives zeros."""
+    rec = _f32(records).reshape(-1, 24)
+    a = _f32(nodes).reshape(-1, 4)
+    out = np.zeros_like(rec)
+    count = int(lat.dims[0]) * int(lat.dims[1]) * int(lat.dims[2]) * int(lat.dims[3])
+    if all(1 <= int(d) <= 65535 for d in lat.dims) and count <= 1 << 28 and a.shape[0] != count:      # (a lattice that is refused reads no node)
+        raise ValueError(f"the lattice has {count} nodes, the array {a.shape[0]}")
+    _lib.gs4d_host_warp_records(rec.shape[0], _ptr(rec), _ptr(a) if a.size else None, C.byref(lat), _ptr(out))
     return out
 
 
@@ -2029,6 +2087,25 @@ class Context:
         finally:
             for b in temps:
                 self.delete(b)
+        return dst
+
+    # a map that varies from point to point: a set deformed through a 4D lattice
+    def warp_records(self, src, n, nodes, lat, dst=None, dst_first=0):
+        """gs4d_warp_records: record dst_first + i of `dst` (a new buffer of dst_first + n records if None) <- record i < n of `src` through the map
+        x' = x + D(x) of the Lattice `lat` (lattice()), linearised at the record's centre, with the bits of warp_records_host; a record whose centre
+        is not inside the lattice is copied.  nodes: a buffer of 16-byte nodes (dx, dy, dz, dt), or an array of the lattice's size, which is
+        uploaded to a temporary buffer (deleting it waits for the device, so a frame loop keeps a buffer of its own and updates it with subdata).
+        A full write of dst: the next draw rebuilds its SoA shadow.  Per frame: (shade_sh), warp, keygen, sort, draw.  Asynchronous; returns `dst`."""
+        own = not isinstance(nodes, (int, np.integer))
+        if own:
+            nodes = self.buffer(_lattice_nodes(nodes, lat))
+        try:
+            if dst is None:
+                dst = self.buffer(nbytes=max(16, (int(dst_first) + int(n)) * 96))
+            self._chk(_lib.gs4d_warp_records(self._h, int(src), int(n), int(nodes), C.byref(lat), int(dst), int(dst_first)))
+        finally:
+            if own:
+                self.delete(nodes)
         return dst
 
     # a frame of a clip as a 3D set: the records baked at one time (DESIGN.md §4)

@@ -18,6 +18,7 @@
 #include "gs4d_internal.h"
 #include "operands.h"
 #include "merge_record.h"
+#include "warp_record.h"
 #include "lod_query.h"
 #include "lod_operands.h"
 #include "rows_operands.h"
@@ -1682,6 +1683,25 @@ int gs4d_pose_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf xf, size_t m
     if (n == 0) return GS4D_OK;
     return queue_operands(c, ops, [&](Lane& L) {
         HIPCHK(c, launch_pose_records(L.s, ops.ptr(src), n, (const gs4d_affine4*)ops.ptr(xf), m, ops.ptr(bind), form, bind_stride, (char*)ops.ptr(dst) + dst_first * 96));
+        return (int)GS4D_OK;
+    });
+}
+
+// ---- a set deformed through a 4D lattice ----
+int gs4d_warp_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf nodes, const gs4d_lattice* lat, gs4d_buf dst, size_t dst_first) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "warp_records";
+    if (!lat) return refuse(c, fn, "lat == NULL");
+    const gs4d_lattice q = *lat;
+    const uint64_t count = gs4d_warp::node_count(q.dims, q.clamp, q.pad);
+    if (!count) return refuse(c, fn, "a dim that is 0 or above 65535, more than 2^28 nodes, clamp bits above 3 or a non-zero pad");
+    if (n > 0xFFFFFFFFull || dst_first > 0xFFFFFFFFull || (uint64_t)n + dst_first > 0xFFFFFFFFull) return refuse(c, fn, "n, dst_first or dst_first + n above 2^32 - 1");
+    Operands ops{ { "src", src, false, 96, n, OP_READ }, { "nodes", nodes, false, 16, count, OP_READ }, { "dst", dst, false, 96, (uint64_t)dst_first + n, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (n == 0) return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_warp_records(L.s, ops.ptr(src), n, ops.ptr(nodes), (uint32_t)count, q, (char*)ops.ptr(dst) + dst_first * 96));
         return (int)GS4D_OK;
     });
 }

@@ -544,6 +544,15 @@ constexpr uint32_t POSE_LDS_ROWS = 128;
 hipError_t launch_pose_records(hipStream_t st, const void* src, size_t n, const gs4d_affine4* xf, size_t m, const void* bind, uint32_t form,
                                size_t bind_stride, void* dst);
 
+// ---- warp.hip ----
+// gs4d_warp_records (gs4d.h): record i of dst <- record i of the n 96-byte records of src through the lattice `lat` (validated: `count`
+// is its node count) of 16-byte nodes, or copied.  One workgroup per WARP_TILE records; a lattice of at most WARP_LDS_NODES nodes is copied into LDS
+// by every workgroup, a larger one is read from global memory — 0: the shipped build reads every lattice from global memory, which measured faster or
+// equal at every size (make lib WARP_LDS_NODES=512 builds the other).  n <= 0xFFFFFFFF; nothing else of dst is touched.
+constexpr uint32_t WARP_TILE = 256;
+constexpr uint32_t WARP_LDS_NODES = 0;
+hipError_t launch_warp_records(hipStream_t st, const void* src, size_t n, const void* nodes, uint32_t count, const gs4d_lattice& lat, void* dst);
+
 // ---- slice.hip ----
 // gs4d_slice_records (gs4d.h): record i of dst <- record i of the n 96-byte records of src conditioned at q.t (q validated).
 // One workgroup per SLICE_TILE records; n <= 0xFFFFFFFF; nothing else of dst is touched.

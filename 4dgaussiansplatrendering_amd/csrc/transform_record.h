@@ -13,14 +13,9 @@
 
 namespace gs4d_transform {
 
-// out (24 floats) <- the record in (24 floats) under (l[16], o[4]); in and out must not overlap
-GS4D_HD inline void record(const float l[16], const float o[4], const float in[24], float out[24]) {
-    // the mean: L p + o
-    GS4D_UNROLL
-    for (int r = 0; r < 4; ++r) out[r] = ((((l[r] * in[0]) + (l[4 + r] * in[1])) + (l[8 + r] * in[2])) + (l[12 + r] * in[3])) + o[r];
-    // rgba
-    GS4D_UNROLL
-    for (int k = 4; k < 8; ++k) out[k] = in[k];
+// floats 8..23 of out <- L Sigma L^T of the record in (24 floats): the T and Sigma' lines of the definition (gs4d_warp_records takes them with the
+// L of its lattice: warp_record.h); in and out must not overlap
+GS4D_HD inline void sigma(const float l[16], const float in[24], float out[24]) {
     // T = L Sigma
     float T[16];
     GS4D_UNROLL
@@ -35,6 +30,17 @@ GS4D_HD inline void record(const float l[16], const float o[4], const float in[2
         GS4D_UNROLL
         for (int r = 0; r < 4; ++r) out[8 + 4 * c + r] = (((T[r] * l[c]) + (T[4 + r] * l[4 + c])) + (T[8 + r] * l[8 + c])) + (T[12 + r] * l[12 + c]);
     }
+}
+
+// out (24 floats) <- the record in (24 floats) under (l[16], o[4]); in and out must not overlap
+GS4D_HD inline void record(const float l[16], const float o[4], const float in[24], float out[24]) {
+    // the mean: L p + o
+    GS4D_UNROLL
+    for (int r = 0; r < 4; ++r) out[r] = ((((l[r] * in[0]) + (l[4 + r] * in[1])) + (l[8 + r] * in[2])) + (l[12 + r] * in[3])) + o[r];
+    // rgba
+    GS4D_UNROLL
+    for (int k = 4; k < 8; ++k) out[k] = in[k];
+    sigma(l, in, out);
 }
 
 // gs4d_transform_selected (include/gs4d.h): out (24 floats) <- the record in (24 floats) under (l[16], o[4]) about the pivot c[3];

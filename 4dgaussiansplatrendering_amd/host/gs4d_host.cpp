@@ -25,6 +25,7 @@
 #include "../csrc/build_record.h"
 #include "../csrc/transform_record.h"
 #include "../csrc/pose_record.h"
+#include "../csrc/warp_record.h"
 #include "../csrc/slice_record.h"
 #include "../csrc/centre_query.h"
 #include "../csrc/measure_record.h"
@@ -368,6 +369,17 @@ void gs4d_host_pose_records(size_t n, const float* rec, const gs4d_affine4* xf, 
             std::memcpy(w, row + 16, 16);
             gs4d_pose::blend(rows, rows_m, j, w, rec + 24 * i, out + 24 * i);
         }
+    }
+}
+
+// The definition of gs4d_warp_records (gs4d.h) is csrc/warp_record.h: the record through the lattice's map linearised at its centre, or copied.  A
+// lattice the device call would refuse writes nothing.
+void gs4d_host_warp_records(size_t n, const float* rec, const float* nodes4, const gs4d_lattice* lat, float* out) {
+    if (!lat || !gs4d_warp::node_count(lat->dims, lat->clamp, lat->pad)) return;
+    const auto nodes = [nodes4](unsigned int j, float v[4]) { std::memcpy(v, nodes4 + 4 * (size_t)j, 16); };
+    for (size_t i = 0; i < n; ++i) {
+        if (lat->dims[3] >= 2u) gs4d_warp::record<true>(nodes, lat->lo, lat->inv, lat->dims, lat->clamp, rec + 24 * i, out + 24 * i);
+        else gs4d_warp::record<false>(nodes, lat->lo, lat->inv, lat->dims, lat->clamp, rec + 24 * i, out + 24 * i);
     }
 }
 

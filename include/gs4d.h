@@ -627,6 +627,68 @@ GS4D_API int gs4d_transform_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_
 GS4D_API int gs4d_pose_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf bind, uint32_t form, size_t bind_stride,
                                gs4d_buf dst, size_t dst_first);
 
+/* ---- a map that varies from point to point: a set deformed through a 4D lattice (no reference counterpart) ----
+ * gs4d_transform_records and gs4d_pose_records apply affine maps.  A cage or free-form deformation in an editor (bend, bulge, taper), a baked
+ * deformation field with a time axis (how a static or a 4D set is animated non-rigidly) and a retiming field (a region that plays slower or later
+ * than the rest) need a map that varies smoothly from point to point.  gs4d_warp_records is that call: record dst_first + i of dst is written from
+ * record i < n of src through the map x' = x + D(x), D being the multilinear interpolant of a lattice of displacement nodes, linearised at the
+ * record's own centre: mean' = mu + D(mu), Sigma' = L Sigma L^T with L = I + grad D(mu), a full 4x4 matrix.  A time column of grad D gives velocity,
+ * a dt component retiming.  It writes no other byte of dst and no byte of src or nodes.  src is never changed: every frame warps it anew into dst.
+ *
+ * The lattice (gs4d_lattice, read on the host at the call) has dims[a] nodes along axis a = 0..3 (x, y, z, t); node 0 stands at lo[a] and there are
+ * inv[a] nodes per unit.  nodes holds dims[0] * dims[1] * dims[2] * dims[3] nodes of 16 bytes: float d[4], the displacement (dx, dy, dz, dt) at the
+ * node; node (x, y, z, t) is at index ((t * dims[2] + z) * dims[1] + y) * dims[0] + x.
+ *
+ * The definition (gs4d_host_warp_records is this text).  All arithmetic follows the rules of gs4d_transform_records: float32, round to nearest, no
+ * contraction, full products, in the order the parentheses give.  p[a] = float a of the record (float 3 is mu_t).
+ *   Per axis a, with d = dims[a]:
+ *     d == 1   the axis does not take part: its node index is 0, the tree below has no level for it, and column a of G is four +0.0f, not
+ *              computed.  A static lattice has dims[3] == 1; a 2D sheet and a single node (a pure translation) fall out of the same rule.
+ *     d >= 2   u = (p[a] - lo[a]) * inv[a];  top = (float)(d - 1).
+ *              If bit a of clamp is set: u < 0.0f becomes 0.0f, u > top becomes top; whether either happened is remembered.
+ *              The record is INSIDE on a iff u >= 0.0f && u <= top (a NaN is never inside, with or without the clamp).
+ *              i = min((uint32)u, d - 2), converted only when inside;  f = u - (float)i  (u == top gives i = d - 2, f = 1).
+ *              If the clamp changed u, column a of G is four +0.0f: the clamped field is constant along a.
+ *   A record that is not inside on every axis with d >= 2 is copied: the 96 bytes, NaN payloads and all (the rule of gs4d_pose_records for
+ *   j >= m).  Consequence: for every bit pattern of the record, of lo and of inv, only nodes of the lattice are read, and no value but
+ *   0 <= u <= 65534 is converted to an integer.  lo and inv are data and are not validated.
+ *   The interpolation is one fixed tree per component k = 0..3 of d, over the 2 x 2 x 2 x 2 nodes at i[a], i[a] + 1 (one node on an axis with
+ *   d == 1), reducing x, then y, then z, then t; a level whose axis has d == 1 is skipped.
+ *     a value step of a pair (a, b) along axis a:    a + (f[a] * (b - a))
+ *     D[k]      the tree of value steps.
+ *     G[k][a]   (d D_k / d x_a of that interpolant) the levels before a are value steps, those of D; level a is (b - a) * inv[a] in the place of
+ *               the value step; the levels after a are value steps on those differences.
+ *     l[4c + r] = (r == c ? 1.0f : 0.0f) + G[r][c]
+ *   The record of an inside centre:  floats 0..3 = p[r] + D[r];  floats 4..7 copied;  Sigma' by the T = L Sigma and Sigma' = T L^T lines of
+ *   gs4d_transform_records' definition with this l — all 16 elements are evaluated, nothing is mirrored.  A folded map (det L <= 0) gives what the
+ *   lines give.
+ *   Consequences:  a lattice whose nodes are all +0.0f leaves Sigma with the bits of gs4d_host_transform_records under the identity row (and the
+ *   mean as p[r] + 0.0f).  An axis of two equal finite nodes without a -0 gives, on a finite set inside it, the same bits as that axis with one node.
+ * The records have the bits of the host function, except that a word that is a NaN on both sides of a warped (not copied) record may differ in sign
+ * and payload (the rule of gs4d_transform_records).  Nothing depends on the order in which anything runs on the device.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: lat == NULL; a dim that is 0 or above 65535; more than 1 << 28 nodes; clamp bits above 3
+ * or a non-zero pad; n, dst_first or dst_first + n above 0xFFFFFFFF; a name that is not a live buffer; any two of the three buffers being the same;
+ * src smaller than 96 n bytes; nodes smaller than 16 bytes times the node count; dst holding fewer than dst_first + n records.  n == 0 with
+ * otherwise valid arguments is a no-op.  The nodes are data: NaN, Inf and huge displacements give what the definition gives.
+ *
+ * Ordering, exactly that of gs4d_pose_records: a queued gs4d_keygen / gs4d_sort_pairs that names one of the buffers is launched first; draws that
+ * may still have to be run again from dst are settled; the kernel is queued on the current frame lane, the call returns at once and starts no new
+ * frame; src and nodes are buffers the call reads (a gs4d_buffer_subdata of the next frame's nodes orders itself behind it), dst one it writes.
+ * It counts as a full write of dst: the next draw or gs4d_keygen rebuilds the SoA shadow once.  Per frame: (shade) -> warp -> gs4d_keygen ->
+ * gs4d_sort_pairs -> draw.  The notes of gs4d_transform_records hold per record: time spans must be computed again when the lattice has a time axis
+ * or a dt component; the SH table is not rotated; the depth-key remark holds.
+ * Out of scope: an in-place warp (src == dst), a statistics rule that selects which records warp, higher-order (B-spline) lattices, rotating SH
+ * rows, reporting folded records. */
+typedef struct gs4d_lattice {
+    float    lo[4];     /* where node 0 stands on x, y, z, t                         */
+    float    inv[4];    /* nodes per unit along each axis (1 / spacing)              */
+    uint32_t dims[4];   /* nodes per axis, each 1..65535, their product <= 1 << 28   */
+    uint32_t clamp;     /* bit a set: axis a clamps; bits 4..31 must be 0            */
+    uint32_t pad[3];    /* must be 0                                                 */
+} gs4d_lattice;         /* 64 bytes */
+GS4D_API int gs4d_warp_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_buf nodes, const gs4d_lattice* lat, gs4d_buf dst, size_t dst_first);
+
 /* ---- a frame of a clip as a 3D set: the records baked at one time (no reference counterpart) ----
  * The draws condition a 4D record at uTime — the time opacity, the conditional centre, the conditional 3x3 covariance — inside the projection
  * kernel, every frame.  gs4d_slice_records does that once and writes the result as records: the 3D set that the 4D set IS at time q->t, to be drawn
@@ -1481,6 +1543,10 @@ GS4D_API void gs4d_host_transform_records(size_t n, const float* records24, cons
  * breaks the form's rule, writes nothing. */
 GS4D_API void gs4d_host_pose_records(size_t n, const float* records24, const gs4d_affine4* xf, size_t m, const void* bind, uint32_t form,
                                      size_t bind_stride, float* out24);
+/* The definition of gs4d_warp_records: out24 record i = records24 record i through the lattice *lat of the nodes nodes4 (4 floats each), i < n (the
+ * text above the declaration of gs4d_warp_records).  out24 must not overlap records24.  A lattice the device call would refuse (NULL included)
+ * writes nothing. */
+GS4D_API void gs4d_host_warp_records(size_t n, const float* records24, const float* nodes4, const gs4d_lattice* lat, float* out24);
 /* The definition of gs4d_slice_records: out24 record i = records24 record i conditioned at q->t, i < n (the text above the declaration of
  * gs4d_slice_records; expf is the C library's).  out24 must not overlap records24.  A query the device call would refuse is evaluated as it stands. */
 GS4D_API void gs4d_host_slice_records(size_t n, const float* records24, const gs4d_slice* q, float* out24);
