@@ -108,6 +108,7 @@ def _load():
         "gs4d_count_centres": (i32, [vp, u32, sz, vp, u32, u32]),
         "gs4d_measure_records": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_build_records": (i32, [vp, vp, sz, u32]),
+        "gs4d_decompose_records": (i32, [vp, u32, sz, sz, vp]),
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_transform_selected": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_pose_records": (i32, [vp, u32, sz, u32, sz, u32, u32, sz, u32, sz]),
@@ -146,6 +147,7 @@ def _load():
         "gs4d_host_time_variances": (None, [sz, vp, vp, vp]),
         "gs4d_host_build_records_4d_tvar": (None, [sz, vp, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_build_records_4d_2q": (None, [sz, vp, vp, vp, vp, vp, vp]),
+        "gs4d_host_decompose_records": (None, [sz, vp, u32, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_transform_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_pose_records": (None, [sz, vp, vp, sz, vp, u32, sz, vp]),
         "gs4d_host_warp_records": (None, [sz, vp, vp, vp, vp]),
@@ -280,6 +282,32 @@ def build_records_4d_2q(pos4, q0_wxyz, q1_wxyz, scale4, rgba):
     rec = np.empty((n, 24), np.float32)
     _lib.gs4d_host_build_records_4d_2q(n, _ptr(pos4), _ptr(q0), _ptr(q1), _ptr(s), _ptr(col), _ptr(rec))
     return rec
+
+
+# floats per row of the parameters a record decomposes into, per form, in the order of gs4d_splat_params (PARAMS_4D_2Q is not decomposed)
+PARAM_ROWS = {PARAMS_3D: {"pos": 3, "rot": 4, "scale": 3, "rgba": 4}, PARAMS_4D_VEL: {"pos": 4, "rot": 4, "scale": 3, "rgba": 4, "dir": 3, "tvar": 1}}
+
+
+def _param_names(form, only):
+    rows = PARAM_ROWS.get(int(form))
+    if rows is None:
+        raise ValueError("decompose_records: the form is PARAMS_3D or PARAMS_4D_VEL (a 4D record of any origin can be taken out as PARAMS_4D_VEL)")
+    names = tuple(rows) if only is None else tuple(only)
+    if not names or set(names) - set(rows):
+        raise ValueError(f"decompose_records: `only` names at least one of {tuple(rows)}")
+    return rows, names
+
+
+def decompose_records_host(records, form, only=None):
+    """gs4d_host_decompose_records, the definition of Context.decompose_records and the inverse of build_records_3d / build_records_4d_tvar: records
+    [n, 24] as a dict {name: float32 [n, k]} of the parameters of the form — PARAMS_3D: pos (3), rot (w x y z), scale (3), rgba; PARAMS_4D_VEL: pos
+    (4), rot, scale, rgba, dir (3), tvar (1).  The scales descend, the quaternion is of unit length with w >= 0.  only: the names wanted (all)."""
+    rows, names = _param_names(form, only)
+    rec = _f32(records).reshape(-1, 24)
+    n = rec.shape[0]
+    out = {k: np.empty((n, rows[k]), np.float32) for k in names}
+    _lib.gs4d_host_decompose_records(n, _ptr(rec), int(form), *(_ptr(out[k]) if k in out else None for k in ("pos", "rot", "scale", "rgba", "dir", "tvar")))
+    return out
 
 
 class Affine4(C.Structure):
@@ -1137,9 +1165,14 @@ def frame_box(lo, hi, orientation, fov_deg, width, height):
 
 
 class SplatParams(C.Structure):
-    """gs4d_splat_params (include/gs4d.h): the form and the parameter buffers of a gs4d_build_records call."""
+    """gs4d_splat_params (include/gs4d.h): the form and the parameter buffers of a gs4d_build_records call, or the destinations of a
+    gs4d_decompose_records call (Context.decompose_records returns one; Context.build_records takes it in the place of the form)."""
     _fields_ = [("form", C.c_uint32), ("flags", C.c_uint32), ("pos", C.c_uint32), ("rot", C.c_uint32), ("rot_r", C.c_uint32), ("scale", C.c_uint32),
                 ("rgba", C.c_uint32), ("dir", C.c_uint32), ("tvar", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def buffers(self):
+        """{name: buffer} of the buffers that are given"""
+        return {k: getattr(self, k) for k in ("pos", "rot", "rot_r", "scale", "rgba", "dir", "tvar") if getattr(self, k)}
 
 
 class CameraInput(C.Structure):
@@ -2024,7 +2057,9 @@ class Context:
         PARAMS_3D: pos (3 floats), rot (w x y z), scale (3), rgba; PARAMS_4D_VEL: pos (x y z mu_t), rot, scale (3), dir (3), tvar (1: see
         time_variance), rgba; PARAMS_4D_2Q: pos (4), rot, rot_r, scale (4), rgba — with the bits of build_records_3d / build_records_4d_tvar /
         build_records_4d_2q.  A full write of dst: the next draw rebuilds its SoA shadow.  Per frame: build, (shade_sh), keygen, sort, draw.
-        Asynchronous; returns `dst`."""
+        Asynchronous; returns `dst`.  form may be the SplatParams that decompose_records returned: its form and its buffers."""
+        if isinstance(form, SplatParams):
+            form, buffers = form.form, {**form.buffers(), **buffers}
         unknown = set(buffers) - set(self.PARAM_BUFFERS)
         if unknown:
             raise TypeError(f"build_records: unknown parameter buffer(s) {sorted(unknown)}")
@@ -2033,6 +2068,37 @@ class Context:
         params = SplatParams(int(form), 0, *(int(buffers.get(k) or 0) for k in self.PARAM_BUFFERS), 0)
         self._chk(_lib.gs4d_build_records(self._h, C.byref(params), int(n), int(dst)))
         return dst
+
+    # records back to parameters: a set edited on the device taken out for a trainer or a file
+    def decompose_records(self, src, n, form, src_first=0, only=None, **buffers):
+        """gs4d_decompose_records: row i < n of every destination from record src_first + i of `src`, with the bits of decompose_records_host —
+        PARAMS_3D: pos (3 floats), rot (w x y z), scale (3), rgba; PARAMS_4D_VEL: pos (4), rot, scale, rgba, dir (3), tvar (1).  Destinations are
+        given by name (pos=buffer, ...); those of `only` (default: all of the form) that are not given are allocated.  With neither rot nor scale
+        the eigen-solve does not run.  src is not written and its shadow not touched.  Asynchronous; returns the SplatParams of the destinations,
+        which build_records accepts back and read_params reads."""
+        unknown = set(buffers) - set(self.PARAM_BUFFERS)
+        if unknown:
+            raise TypeError(f"decompose_records: unknown destination(s) {sorted(unknown)}")
+        rows, names = _param_names(form, tuple(buffers) if only is None and buffers else only)
+        use = {k: int(v) for k, v in buffers.items() if v}
+        made = []
+        try:
+            for k in names:
+                if k not in use:
+                    use[k] = self.buffer(nbytes=max(16, int(n) * 4 * rows[k]))
+                    made.append(use[k])
+            params = SplatParams(int(form), 0, *(use.get(k, 0) for k in self.PARAM_BUFFERS), 0)
+            self._chk(_lib.gs4d_decompose_records(self._h, int(src), int(n), int(src_first), C.byref(params)))
+        except Exception:
+            for b in made:
+                self.delete(b)
+            raise
+        return params
+
+    def read_params(self, params, n):
+        """The first n rows of every buffer of a SplatParams as {name: float32 [n, k]} (blocking reads)."""
+        rows = dict(PARAM_ROWS.get(params.form, {"pos": 4, "rot": 4, "scale": 4, "rgba": 4}), rot_r=4)
+        return {k: self.read(b, np.float32, int(n) * rows[k]).reshape(int(n), rows[k]) for k, b in params.buffers().items()}
 
     # placing a set: the records under 4D affine maps (DESIGN.md §4)
     def transform_records(self, src, n, xf, m=1, dst=None, dst_first=0):
@@ -2186,6 +2252,27 @@ class Context:
         rc = _hip().hipMemcpyAsync(C.c_void_p(dptr + offset), C.c_void_p(tensor.data_ptr()), nbytes, 3, C.c_void_p(stream))      # 3: hipMemcpyDeviceToDevice
         if rc != 0:
             raise Gs4dError(f"write_tensor: hipMemcpyAsync failed ({rc})")
+
+    def read_tensor(self, buf, tensor, offset=0):
+        """The other direction: the bytes of the buffer `buf` from byte `offset` copied into a contiguous device tensor, with no host copy and no
+        host synchronisation — gs4d_buffer_invalidate makes the tensor's current stream (named with set_stream, as for write_tensor) wait for the
+        kernels the library has queued on the buffer, e.g. a decompose_records that writes it; the copy runs on that stream behind them."""
+        import torch
+        if not (isinstance(tensor, torch.Tensor) and tensor.is_cuda and tensor.is_contiguous()):
+            raise ValueError("read_tensor: expected a contiguous device tensor")
+        stream = torch.cuda.current_stream(tensor.device).cuda_stream
+        if not stream or stream != getattr(self, "_stream", None):
+            raise Gs4dError("read_tensor: name the tensor's current stream with set_stream first (a stream of your own, not the default stream)")
+        nbytes = tensor.numel() * tensor.element_size()
+        dptr, size = self.device_ptr(buf)
+        if offset < 0 or offset + nbytes > size:
+            raise ValueError(f"read_tensor: {nbytes} bytes at offset {offset} are not inside a buffer of {size} bytes")
+        if nbytes == 0:
+            return
+        self.invalidate(buf)
+        rc = _hip().hipMemcpyAsync(C.c_void_p(tensor.data_ptr()), C.c_void_p(dptr + offset), nbytes, 3, C.c_void_p(stream))      # 3: hipMemcpyDeviceToDevice
+        if rc != 0:
+            raise Gs4dError(f"read_tensor: hipMemcpyAsync failed ({rc})")
 
     def shadow_builds(self, buf):
         """gs4d_debug_shadow_builds: how many times the SoA shadow of this record buffer has been (re)built."""

@@ -1651,6 +1651,35 @@ int gs4d_build_records(gs4d_ctx* c, const gs4d_splat_params* params, size_t n, g
     });
 }
 
+// ---- records back to parameters ----
+int gs4d_decompose_records(gs4d_ctx* c, gs4d_buf src, size_t n, size_t src_first, const gs4d_splat_params* out) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "decompose_records";
+    if (!out) return refuse(c, fn, "out == NULL");
+    const gs4d_splat_params& p = *out;
+    if (p.form == GS4D_PARAMS_4D_2Q) return refuse(c, fn, "form GS4D_PARAMS_4D_2Q is not decomposed: take a 4D record out as GS4D_PARAMS_4D_VEL");
+    if (p.form != GS4D_PARAMS_3D && p.form != GS4D_PARAMS_4D_VEL) return refuse(c, fn, "unknown form");
+    if (p.flags != 0u || p.reserved != 0u) return refuse(c, fn, "flags and reserved must be 0");
+    if (n > 0xFFFFFFFFull || src_first > 0xFFFFFFFFull || (uint64_t)n + src_first > 0xFFFFFFFFull) return refuse(c, fn, "n, src_first or src_first + n above 2^32 - 1");
+    const bool vel = p.form == GS4D_PARAMS_4D_VEL;
+    if (p.rot_r != 0) return refuse(c, fn, "rot_r must be 0");
+    if (!vel && p.dir != 0) return refuse(c, fn, "dir must be 0 in this form");
+    if (!vel && p.tvar != 0) return refuse(c, fn, "tvar must be 0 in this form");
+    if (!(p.pos | p.rot | p.scale | p.rgba | p.dir | p.tvar)) return refuse(c, fn, "no destination given: at least one of pos, rot, scale, rgba, dir, tvar");
+    // every destination is optional; src is read as records, never through its SoA shadow
+    Operands ops{ { "src", src, false, 96, (uint64_t)src_first + n, OP_READ }, { "pos", p.pos, true, vel ? 16u : 12u, n, OP_WRITE },
+                  { "rot", p.rot, true, 16, n, OP_WRITE }, { "scale", p.scale, true, 12, n, OP_WRITE }, { "rgba", p.rgba, true, 16, n, OP_WRITE },
+                  { "dir", p.dir, true, 12, n, OP_WRITE }, { "tvar", p.tvar, true, 4, n, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (n == 0) return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        const DecomposeOut o = { ops.ptr(p.pos), ops.ptr(p.rot), ops.ptr(p.scale), ops.ptr(p.rgba), ops.ptr(p.dir), ops.ptr(p.tvar) };
+        HIPCHK(c, launch_decompose_records(L.s, (int)p.form, (const char*)ops.ptr(src) + src_first * 96, n, o));
+        return (int)GS4D_OK;
+    });
+}
+
 // ---- records under affine maps ----
 int gs4d_transform_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf dst, size_t dst_first) {
     if (!c) return GS4D_E_INVALID;

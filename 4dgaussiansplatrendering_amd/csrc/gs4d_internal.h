@@ -529,6 +529,15 @@ constexpr uint32_t BUILD_TILE = 256;
 struct BuildParams { const void *pos, *rot, *rot_r, *scale, *rgba, *dir, *tvar; };
 hipError_t launch_build_records(hipStream_t st, int form, const BuildParams& p, size_t n, void* dst);
 
+// ---- decompose.hip ----
+// gs4d_decompose_records (gs4d.h): row i of every destination array given (null: not wanted; rows of tightly packed float32 with the
+// sizes of BuildParams) from record i of the n 96-byte records of src, in the form GS4D_PARAMS_3D or GS4D_PARAMS_4D_VEL.  One workgroup per
+// DECOMPOSE_TILE records; the instance without the eigen-solve runs when neither rot nor scale is given.  n <= 0xFFFFFFFF; nothing past row n - 1 is
+// touched.
+constexpr uint32_t DECOMPOSE_TILE = 256;
+struct DecomposeOut { void *pos, *rot, *scale, *rgba, *dir, *tvar; };
+hipError_t launch_decompose_records(hipStream_t st, int form, const void* src, size_t n, const DecomposeOut& o);
+
 // ---- transform.hip ----
 // gs4d_transform_records (gs4d.h): record j * n + i of dst <- record i of the n 96-byte records of src under row j of the m rows of xf.
 // One workgroup per TRANSFORM_TILE records and row; m * n <= 0xFFFFFFFF; nothing else of dst is touched.

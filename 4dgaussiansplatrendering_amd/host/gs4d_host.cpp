@@ -23,6 +23,7 @@
 #include <string>
 #include <vector>
 #include "../csrc/build_record.h"
+#include "../csrc/decompose_record.h"
 #include "../csrc/transform_record.h"
 #include "../csrc/pose_record.h"
 #include "../csrc/warp_record.h"
@@ -343,6 +344,32 @@ void gs4d_host_build_records_4d_tvar(size_t n, const float* pos4, const float* q
 
 void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const float* q0_wxyz, const float* q1_wxyz, const float* scale4, const float* rgba, float* rec) {
     for (size_t i = 0; i < n; ++i) gs4d_build::record_4d_2q(pos4 + 4 * i, q0_wxyz + 4 * i, q1_wxyz + 4 * i, scale4 + 4 * i, rgba + 4 * i, rec + 24 * i);
+}
+
+// The definition of gs4d_decompose_records (gs4d.h) is csrc/decompose_record.h: the builders above, backwards.  A destination that is null is not
+// wanted; the eigen-solve is left out when neither q_wxyz nor scale3 is.  A form the device call would refuse writes nothing; dir3 and tvar are not
+// written in the 3D form.
+extern "C++" {
+template <int FORM, bool SOLVE>
+static void decompose_rows(size_t n, const float* rec, float* pos, float* q, float* scale3, float* rgba, float* dir3, float* tvar) {
+    constexpr size_t pw = FORM == GS4D_PARAMS_3D ? 3 : 4;
+    for (size_t i = 0; i < n; ++i) {
+        gs4d_decompose::Splat s;
+        gs4d_decompose::record<FORM, SOLVE>(rec + 24 * i, s);
+        if (pos) std::memcpy(pos + pw * i, s.pos, 4 * pw);
+        if (SOLVE && q) std::memcpy(q + 4 * i, s.q, 16);
+        if (SOLVE && scale3) std::memcpy(scale3 + 3 * i, s.s, 12);
+        if (rgba) std::memcpy(rgba + 4 * i, s.rgba, 16);
+        if (FORM != GS4D_PARAMS_3D && dir3) std::memcpy(dir3 + 3 * i, s.dir, 12);
+        if (FORM != GS4D_PARAMS_3D && tvar) tvar[i] = s.tvar;
+    }
+}
+}
+void gs4d_host_decompose_records(size_t n, const float* rec, uint32_t form, float* pos, float* q_wxyz, float* scale3, float* rgba, float* dir3, float* tvar) {
+    if (form != GS4D_PARAMS_3D && form != GS4D_PARAMS_4D_VEL) return;
+    const bool vel = form == GS4D_PARAMS_4D_VEL, solve = q_wxyz || scale3;
+    (vel ? (solve ? &decompose_rows<GS4D_PARAMS_4D_VEL, true> : &decompose_rows<GS4D_PARAMS_4D_VEL, false>)
+         : (solve ? &decompose_rows<GS4D_PARAMS_3D, true> : &decompose_rows<GS4D_PARAMS_3D, false>))(n, rec, pos, q_wxyz, scale3, rgba, dir3, tvar);
 }
 
 // The definition of gs4d_transform_records (gs4d.h) is csrc/transform_record.h: mean L p + o, covariance (L Sigma) L^T as two full mat4 products, rgba copied

@@ -21,7 +21,7 @@ $(FLAGSTAMP):
 	rm -f $(CSRC)/.flags.*
 	touch $@
 
-OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/pose.o $(CSRC)/warp.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/merge.o $(CSRC)/merge_rows.o $(CSRC)/lod.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
+OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/decompose.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/pose.o $(CSRC)/warp.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/merge.o $(CSRC)/merge_rows.o $(CSRC)/lod.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
 
 .PHONY: all lib oracle ref refscene refdraw refgl clean demo sweep
 all: lib oracle demo sweep
@@ -86,6 +86,9 @@ $(CSRC)/nearest.o: $(CSRC)/nearest.hip $(HD) $(CSRC)/neighbour_grid.h $(CSRC)/ne
 # make BUILD_PLAIN=1: gs4d_build_records with every thread storing its own record, without the LDS staging (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/build.o: $(CSRC)/build.hip $(CSRC)/record_tile.h $(CSRC)/build_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(BUILD_PLAIN),-DGS4D_BUILD_PLAIN) -c $< -o $@
+# decompose_record.h is the one text of gs4d_decompose_records' definition, on top of build_record.h: the kernel and the host library compile it (tests/decompose_record_check.cpp compiles it too); decompose.o is built with the flags of build.o
+$(CSRC)/decompose.o: $(CSRC)/decompose.hip $(CSRC)/record_tile.h $(CSRC)/decompose_record.h $(CSRC)/build_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # transform_record.h is the one text of the record transforms and of the centre of a measurement: both transform kernels and the host library compile it (tests/transform_record_check.cpp and tests/transform_selected_check.cpp compile it too)
 # make TRANSFORM_STAGED_LOAD=1: gs4d_transform_records with the input staged in LDS like the output, instead of every thread loading its own record (the measurement of DESIGN.md §4; never the shipped build)
 $(CSRC)/transform.o: $(CSRC)/transform.hip $(CSRC)/record_tile.h $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
@@ -111,7 +114,7 @@ $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Make
 $(CSRC)/gs4d_api.o: $(CSRC)/operands.h $(CSRC)/merge_record.h $(CSRC)/warp_record.h $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(CSRC)/lod_operands.h $(CSRC)/rows_operands.h $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(HD)
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gs4d_internal.h $(CSRC)/composite_common.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/transform_record.h $(CSRC)/pose_record.h $(CSRC)/warp_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/merge_record.h $(CSRC)/merge_rows_record.h $(CSRC)/lod_query.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
+$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/decompose_record.h $(CSRC)/transform_record.h $(CSRC)/pose_record.h $(CSRC)/warp_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/merge_record.h $(CSRC)/merge_rows_record.h $(CSRC)/lod_query.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -fvisibility=hidden $(STRICT) -x c++ -c $< -o $@
 
 $(LIB): $(OBJS)

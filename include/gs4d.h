@@ -530,6 +530,46 @@ typedef struct gs4d_splat_params {
 } gs4d_splat_params;    /* 40 bytes */
 GS4D_API int gs4d_build_records(gs4d_ctx* ctx, const gs4d_splat_params* params, size_t n, gs4d_buf dst);
 
+/* ---- records back to parameters: the inverse of gs4d_build_records ----
+ * A set that was merged, sliced, warped, posed or compacted on the device goes back to a trainer, a 3DGS / 4DGS file or another viewer as position,
+ * quaternion, scales and colour: row i of every buffer named in *out is written from record src_first + i of src, i < n.  *out is read as the list
+ * of DESTINATIONS, with the row sizes of gs4d_build_records.  Any destination may be 0, "not wanted" (only rot: normals — the last column of its
+ * matrix is the shortest axis; only scale: a regulariser); at least one must be given; rot_r must be 0; dir and tvar must be 0 in the 3D form.
+ * The call writes rows [0, n) of the named buffers and no other byte of any buffer; src is never written.
+ *
+ * The definition (gs4d_host_decompose_records is this text; csrc/decompose_record.h holds it once for the host and the kernel).  All arithmetic is
+ * float32, round to nearest, no contraction, correctly rounded division and square root; only + - * / and the square root are used.
+ *     GS4D_PARAMS_3D      pos = floats 0..2.  Sigma3 = the spatial block of the record, of which the LOWER triangle is read (floats 8, 9, 10, 13, 14,
+ *                         18); the upper triangle, mu_t, the time row and column and Sigma44 are not looked at.  A 4D set whose CONDITIONAL
+ *                         covariance at a time is meant goes through gs4d_slice_records first.
+ *     GS4D_PARAMS_4D_VEL  pos = floats 0..3, tvar = Sigma44 (float 23), td = floats 20..22, dir = td / tvar (one division each), Sigma3 = the
+ *                         lower triangle of the spatial block - (td_r * td_c) * (1 / tvar): the builder's own terms, subtracted.  Every 4x4
+ *                         covariance with Sigma44 > 0 has this decomposition, so every 4D record — 2Q-built, merged, warped, posed — can be taken out
+ *                         in this form.
+ *     GS4D_PARAMS_4D_2Q   refused (it needs a 4x4 eigen-solve and the factoring of an SO(4) matrix into two quaternions).
+ *     rgba                floats 4..7, bit copies.
+ *     rot, scale          Sigma3 -> (q, s) with Sigma3 ~ ((R S) S) R^T, R the matrix of q, by a cyclic Jacobi eigen-solve of a fixed number of
+ *                         sweeps over the pairs (0,1), (0,2), (1,2).  The canonical choice makes the outputs a function of the record: s holds the
+ *                         standard deviations in descending order, ties keeping the lower original axis first; an eigenvalue that is negative or a
+ *                         zero of either sign gives the scale +0; R's third column is the cross product of the first two (a proper rotation); q
+ *                         (w x y z) is of unit length with w >= 0, and of the two quaternions with w == 0 (a zero of either sign, which is kept)
+ *                         the one whose first non-zero component of x, y, z is positive.
+ * Hostile records are data: a NaN, an Inf, 1e30, an indefinite Sigma3 or Sigma44 <= 0 give what this arithmetic gives, with no trap and no
+ * device-side check.  The rows have the bits of the host function, except that a word that is a NaN on both sides may differ in sign and payload
+ * (the rule of gs4d_build_records).  Anisotropy beyond what a float32 covariance resolves (variance ratios from about 2^24) comes back with a smallest
+ * scale of 0: the record itself has lost the short axis.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: out == NULL; an unknown form or GS4D_PARAMS_4D_2Q; flags or reserved != 0; n, src_first
+ * or src_first + n > 0xFFFFFFFF; no destination given; rot_r given, or dir or tvar given in the 3D form; a name that is not a live buffer; any two
+ * of the named buffers (src included) being the same buffer; src smaller than src_first + n records; a destination smaller than n rows.  n == 0 with
+ * otherwise valid arguments is a no-op.
+ *
+ * Ordering, as gs4d_build_records with the roles exchanged: src is a buffer the call reads — its 96-byte records, never its SoA shadow, which is
+ * neither built nor invalidated (gs4d_debug_shadow_builds does not move) — and every destination one it writes.  The kernel is queued on the
+ * current frame lane and the call returns at once.  gs4d_buffer_invalidate hand-offs are honoured in both directions: a destination handed to the
+ * caller's stream with gs4d_buffer_device_ptr + gs4d_buffer_invalidate after the call holds the rows when read on that stream, with no host copy. */
+GS4D_API int gs4d_decompose_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, size_t src_first, const gs4d_splat_params* out);
+
 /* ---- placing a record set: the records under a 4D affine map ----
  * A record carries a world-space mean and a 4x4 space-time covariance, and the draws have no model matrix.  gs4d_transform_records places a set
  * on the device: a Gaussian under x' = L x + o stays a Gaussian, with mean L mu + o and covariance L Sigma L^T, and with L a full 4x4 matrix one
@@ -1535,6 +1575,10 @@ GS4D_API void gs4d_host_build_records_4d_tvar(size_t n, const float* pos4, const
                                               const float* rgba, float* records24);
 GS4D_API void gs4d_host_build_records_4d_2q(size_t n, const float* pos4, const float* q0_wxyz, const float* q1_wxyz, const float* scale4, const float* rgba,
                                             float* records24);
+/* The definition of gs4d_decompose_records: row i of every array given from records24 record i, i < n, in the form GS4D_PARAMS_3D (pos: 3 floats a
+ * row; dir3 and tvar are not written) or GS4D_PARAMS_4D_VEL (pos: 4 floats a row) — the text above the declaration of gs4d_decompose_records.  An
+ * array that is NULL is not wanted.  Any other form writes nothing. */
+GS4D_API void gs4d_host_decompose_records(size_t n, const float* records24, uint32_t form, float* pos, float* q_wxyz, float* scale3, float* rgba, float* dir3, float* tvar);
 /* The definition of gs4d_transform_records for one transform: out24 record i = records24 record i under *xf, i < n (the text above the declaration
  * of gs4d_transform_records).  out24 must not overlap records24. */
 GS4D_API void gs4d_host_transform_records(size_t n, const float* records24, const gs4d_affine4* xf, float* out24);
