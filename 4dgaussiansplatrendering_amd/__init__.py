@@ -30,6 +30,7 @@ CQ_BOX, CQ_SPHERE, CQ_SCREEN, CQ_FRAME, CQ_SKIP_HIDDEN, CQ_SKIP_DEAD = 1, 2, 4, 
 CQ_ADD, CQ_REMOVE = 0, 1                                   # gs4d_centre_query.op
 MS_SKIP_HIDDEN, MS_SKIP_DEAD = 1, 2                        # gs4d_measure_query.flags
 POSE_INDEX, POSE_BLEND4 = 0, 1                             # gs4d_pose_records: the form of a bind row
+SH_EACH = 2                                                # gs4d_rotate_sh: no bind table, every map to every row
 XS_PIVOT, XS_PIVOT_MEASURE = 1, 2                          # gs4d_selection_xf.flags
 NB_SKIP_HIDDEN, NB_SKIP_DEAD, NB_COUNT_SELF = 1, 2, 4      # gs4d_neighbour_query.flags
 CC_SKIP_HIDDEN, CC_SKIP_DEAD = 1, 2                        # gs4d_component_query.flags
@@ -112,6 +113,7 @@ def _load():
         "gs4d_transform_records": (i32, [vp, u32, sz, u32, sz, u32, sz]),
         "gs4d_transform_selected": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_pose_records": (i32, [vp, u32, sz, u32, sz, u32, u32, sz, u32, sz]),
+        "gs4d_rotate_sh": (i32, [vp, u32, sz, sz, i32, u32, sz, u32, u32, sz, u32, sz]),
         "gs4d_warp_records": (i32, [vp, u32, sz, u32, vp, u32, sz]),
         "gs4d_slice_records": (i32, [vp, u32, sz, vp, u32, sz]),
         "gs4d_count_neighbours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
@@ -150,6 +152,8 @@ def _load():
         "gs4d_host_decompose_records": (None, [sz, vp, u32, vp, vp, vp, vp, vp, vp]),
         "gs4d_host_transform_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_pose_records": (None, [sz, vp, vp, sz, vp, u32, sz, vp]),
+        "gs4d_host_sh_rotation": (i32, [vp, vp]),
+        "gs4d_host_rotate_sh": (None, [sz, vp, sz, i32, vp, sz, vp, u32, sz, vp]),
         "gs4d_host_warp_records": (None, [sz, vp, vp, vp, vp]),
         "gs4d_host_slice_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_edit_colours": (None, [sz, vp, vp, vp, vp, vp]),
@@ -389,6 +393,61 @@ def pose_records_host(records, xf, bind, form=None, bind_stride=None):
     out = np.zeros_like(rec)
     _lib.gs4d_host_pose_records(rec.shape[0], _ptr(rec), _ptr(rows) if rows.size else None, rows.shape[0], _ptr(table) if table.size else None, form, bind_stride,
                                 _ptr(out))
+    return out
+
+
+def sh_rotation(l):
+    """gs4d_host_sh_rotation: (ok, d) — the band matrices of gs4d_rotate_sh for the 16 floats of a map's l (a row of 20 floats is taken by its first
+    16), float32 [84] with D_1 at 0 (3 x 3), D_2 at 9 (5 x 5), D_3 at 34 (7 x 7), row-major, word 83 = 0; ok is False, d zeros, where the map does
+    not rotate."""
+    a = _f32(l).reshape(-1)
+    if a.size not in (16, 20):
+        raise ValueError("expected the 16 floats of l (or a row of 20)")
+    a = np.ascontiguousarray(a[:16])
+    d = np.zeros(84, np.float32)
+    ok = bool(_lib.gs4d_host_sh_rotation(_ptr(a), _ptr(d)))
+    return ok, d
+
+
+def _sh_table(rows, stride=None):
+    """(float32 [n, stride / 4], stride) of a table given as float32 [n, words] or uint8 [n, stride] rows, or flat with its stride; a 2-D table
+    whose rows are not `stride` bytes wide is refused"""
+    a = np.ascontiguousarray(rows)
+    if a.dtype == np.uint8:
+        if a.shape[-1] % 4:
+            raise ValueError("rows of bytes must be a multiple of 4 wide")
+        a = a.view(np.float32)
+    a = _f32(a)
+    if a.ndim != 2:
+        if stride is None:
+            raise ValueError("a flat table needs its stride")
+        a = a.reshape(-1, int(stride) // 4)
+    if stride is None:
+        stride = a.shape[1] * 4
+    if a.shape[1] * 4 != int(stride):
+        raise ValueError("the rows are not `stride` bytes wide")
+    return a, int(stride)
+
+
+def rotate_sh_host(rows, xf, degree, bind=None, form=None, bind_stride=None, stride=None):
+    """gs4d_host_rotate_sh, the definition of Context.rotate_sh: the table `rows` (float32 [n, stride / 4]) under the maps of xf ([m, 20] float32; m
+    may be 0).  bind None: SH_EACH, [m * n, stride / 4] with row j * n + i = row i under map j; else a uint32 [n] array (INDEX) or a bind_rows
+    array (BLEND4), or with form and bind_stride the bytes of rows of that stride: [n, stride / 4].  Arguments the device call would refuse give
+    zeros."""
+    table, stride = _sh_table(rows, stride)
+    maps = _f32(xf).reshape(-1, 20)
+    n, m = table.shape[0], maps.shape[0]
+    if bind is None:
+        form = SH_EACH if form is None else form
+        bt, bind_stride = None, 0 if bind_stride is None else bind_stride
+        out = np.zeros((m * n if form == SH_EACH else n, table.shape[1]), np.float32)
+    else:
+        bt, form, bind_stride = _bind_table(bind, form, bind_stride)
+        if bt.size < n * bind_stride:
+            raise ValueError("bind holds fewer rows than the table")
+        out = np.zeros_like(table)
+    _lib.gs4d_host_rotate_sh(n, _ptr(table) if table.size else None, stride, int(degree), _ptr(maps) if maps.size else None, m,
+                             None if bt is None else (_ptr(bt) if bt.size else _ptr(np.zeros(1, np.uint8))), int(form), int(bind_stride), _ptr(out) if out.size else None)
     return out
 
 
@@ -2150,6 +2209,45 @@ class Context:
             if dst is None:
                 dst = self.buffer(nbytes=max(16, (int(dst_first) + int(n)) * 96))
             self._chk(_lib.gs4d_pose_records(self._h, int(src), int(n), int(xf), int(m), int(bind), int(form), int(bind_stride), int(dst), int(dst_first)))
+        finally:
+            for b in temps:
+                self.delete(b)
+        return dst
+
+    # an SH table turned with the maps that move its records
+    def rotate_sh(self, src, n, xf, degree, m=1, bind=None, form=None, bind_stride=None, stride=None, dst=None, dst_first=0):
+        """gs4d_rotate_sh: a rotated copy of the first n rows of the SH table `src` (stride bytes a row, default the minimal row of the degree) in
+        `dst` (a new buffer if None), with the bits of rotate_sh_host.  bind None: SH_EACH — row dst_first + j * n + i <- row i under map j < m of
+        `xf`, the layout of transform_records.  Else row dst_first + i <- row i under the map row i of `bind` chooses, as pose_records: pass the
+        same xf, bind, form and m again.  xf: a buffer of 80-byte rows (with m) or an [m, 20] float32 array; bind: a buffer (form is then
+        required) or a uint32 [n] / bind_rows array.  Arrays are uploaded to temporary buffers.  Per frame: pose, rotate_sh, shade_sh (on the
+        posed set with the true camera), keygen, sort, draw.  Asynchronous; returns `dst`."""
+        temps = []
+        try:
+            if stride is None:
+                stride = sh_row_bytes(degree)
+            if not isinstance(xf, (int, np.integer)):
+                rows = _f32(xf).reshape(-1, 20)
+                m = rows.shape[0]
+                xf = self.buffer(rows) if m else self.buffer(nbytes=80)
+                temps.append(xf)
+            if bind is None:
+                form = SH_EACH if form is None else form
+                bind, bind_stride = 0, 0 if bind_stride is None else bind_stride
+            elif not isinstance(bind, (int, np.integer)):
+                table, form, bind_stride = _bind_table(bind, form, bind_stride)
+                bind = self.buffer(table) if table.size else self.buffer(nbytes=32)
+                temps.append(bind)
+            else:
+                if form is None:
+                    raise TypeError("form is required when bind is a buffer")
+                if bind_stride is None:
+                    bind_stride = 4 if form == POSE_INDEX else 32
+            if dst is None:
+                total = int(m) * int(n) if form == SH_EACH else int(n)
+                dst = self.buffer(nbytes=max(16, (int(dst_first) + total) * int(stride)))
+            self._chk(_lib.gs4d_rotate_sh(self._h, int(src), int(n), int(stride), int(degree), int(xf), int(m), int(bind), int(form), int(bind_stride), int(dst),
+                                          int(dst_first)))
         finally:
             for b in temps:
                 self.delete(b)

@@ -22,6 +22,7 @@
 #include "lod_query.h"
 #include "lod_operands.h"
 #include "rows_operands.h"
+#include "sh_rotate_operands.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -1712,6 +1713,26 @@ int gs4d_pose_records(gs4d_ctx* c, gs4d_buf src, size_t n, gs4d_buf xf, size_t m
     if (n == 0) return GS4D_OK;
     return queue_operands(c, ops, [&](Lane& L) {
         HIPCHK(c, launch_pose_records(L.s, ops.ptr(src), n, (const gs4d_affine4*)ops.ptr(xf), m, ops.ptr(bind), form, bind_stride, (char*)ops.ptr(dst) + dst_first * 96));
+        return (int)GS4D_OK;
+    });
+}
+
+// ---- an SH table turned with the maps that move its records ----
+int gs4d_rotate_sh(gs4d_ctx* c, gs4d_buf src, size_t n, size_t stride, int degree, gs4d_buf xf, size_t m, gs4d_buf bind, uint32_t form, size_t bind_stride, gs4d_buf dst,
+                   size_t dst_first) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "rotate_sh";
+    static_assert(SHROT_INDEX == GS4D_POSE_INDEX && SHROT_BLEND4 == GS4D_POSE_BLEND4 && SHROT_EACH == GS4D_SH_EACH && sizeof(gs4d_affine4) == 80, "the forms and rows of sh_rotate_operands.h");
+    if (const char* fault = rotate_sh_fault(n, stride, degree, m, bind != 0, form, bind_stride, dst_first)) return refuse(c, fn, fault);
+    Operand list[ROTATE_SH_OPERANDS];                          // (sh_rotate_operands.h: what the call does with each)
+    rotate_sh_operands(list, src, n, stride, xf, m, bind, form, bind_stride, dst, dst_first);
+    Operands ops{ list[0], list[1], list[2], list[3] };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (n == 0 || (form == GS4D_SH_EACH && m == 0)) return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_rotate_sh(L.s, ops.ptr(src), n, stride, degree, (const gs4d_affine4*)ops.ptr(xf), m, bind ? ops.ptr(bind) : nullptr, form, bind_stride,
+                                   (char*)ops.ptr(dst) + dst_first * stride));
         return (int)GS4D_OK;
     });
 }

@@ -553,6 +553,16 @@ constexpr uint32_t POSE_LDS_ROWS = 128;
 hipError_t launch_pose_records(hipStream_t st, const void* src, size_t n, const gs4d_affine4* xf, size_t m, const void* bind, uint32_t form,
                                size_t bind_stride, void* dst);
 
+// ---- sh_rotate.hip ----
+// gs4d_rotate_sh (gs4d.h): rows of dst (from the pointer given: row j * n + i with GS4D_SH_EACH, else row i) <- row i of the n rows of
+// `stride` bytes of src under the map of the m rows of xf that the form (validated, bind and bind_stride with it) chooses, or copied.  One workgroup
+// per SHROT_TILE rows (SHROT_TILE_3 at degree 3) and, with GS4D_SH_EACH, per map; every thread builds the matrices of its row's map in registers.
+// n, m, m * n <= 0xFFFFFFFF; nothing else of dst is touched.
+constexpr uint32_t SHROT_TILE = 256;
+constexpr uint32_t SHROT_TILE_3 = 128;
+hipError_t launch_rotate_sh(hipStream_t st, const void* src, size_t n, size_t stride, int degree, const gs4d_affine4* xf, size_t m, const void* bind,
+                            uint32_t form, size_t bind_stride, void* dst);
+
 // ---- warp.hip ----
 // gs4d_warp_records (gs4d.h): record i of dst <- record i of the n 96-byte records of src through the lattice `lat` (validated: `count`
 // is its node count) of 16-byte nodes, or copied.  One workgroup per WARP_TILE records; a lattice of at most WARP_LDS_NODES nodes is copied into LDS

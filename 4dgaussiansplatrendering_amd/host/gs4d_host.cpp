@@ -26,6 +26,8 @@
 #include "../csrc/decompose_record.h"
 #include "../csrc/transform_record.h"
 #include "../csrc/pose_record.h"
+#include "../csrc/sh_rotate_record.h"
+#include "../csrc/sh_rotate_operands.h"
 #include "../csrc/warp_record.h"
 #include "../csrc/slice_record.h"
 #include "../csrc/centre_query.h"
@@ -397,6 +399,58 @@ void gs4d_host_pose_records(size_t n, const float* rec, const gs4d_affine4* xf, 
             gs4d_pose::blend(rows, rows_m, j, w, rec + 24 * i, out + 24 * i);
         }
     }
+}
+
+// The definition of gs4d_rotate_sh (gs4d.h) is csrc/sh_rotate_record.h: the frame of a map's spatial block, the band matrices of that frame, and the
+// row under them — or the row copied, where it names no map or its map does not rotate.  Arguments the device call would refuse (the scalar rules
+// of csrc/sh_rotate_operands.h) write nothing.
+int gs4d_host_sh_rotation(const float l[16], float d[84]) {
+    return gs4d_shrot::rotation<3>(l, d) ? 1 : 0;
+}
+} // extern "C"
+namespace {
+template <int DEGREE>
+void rotate_sh_rows(size_t n, const unsigned char* rows, size_t stride, const gs4d_affine4* xf, size_t m, const unsigned char* bind, uint32_t form, size_t bind_stride,
+                    unsigned char* out) {
+    constexpr size_t used = 12u * (size_t)gs4d_shrot::coeffs(DEGREE);
+    const unsigned int rows_m = (unsigned int)m;
+    const auto table = [xf](unsigned int j, float r[20]) { std::memcpy(r, &xf[j], sizeof(gs4d_affine4)); };
+    const size_t instances = form == GS4D_SH_EACH ? m : 1;
+    for (size_t inst = 0; inst < instances; ++inst)
+        for (size_t i = 0; i < n; ++i) {
+            const unsigned char* const row = rows + i * stride;
+            unsigned char* const to = out + (inst * n + i) * stride;
+            std::memcpy(to, row, stride);
+            if (DEGREE == 0) continue;
+            float a[20];
+            bool mapped;
+            if (form == GS4D_SH_EACH) {
+                table((unsigned int)inst, a);
+                mapped = true;
+            } else if (form == GS4D_POSE_INDEX) {
+                uint32_t j;
+                std::memcpy(&j, bind + i * bind_stride, 4);
+                mapped = gs4d_shrot::index_map(table, rows_m, j, a);
+            } else {
+                unsigned int j[4];
+                float w[4];
+                std::memcpy(j, bind + i * bind_stride, 16);
+                std::memcpy(w, bind + i * bind_stride + 16, 16);
+                mapped = gs4d_pose::blend4(table, rows_m, j, w, a);
+            }
+            if (!mapped) continue;
+            float c[used / 4];
+            std::memcpy(c, row, used);
+            if (gs4d_shrot::coefficients<DEGREE>(a, c)) std::memcpy(to + 12, c + 3, used - 12);      // (words 0..2 are the copy's)
+        }
+}
+}
+extern "C" {
+void gs4d_host_rotate_sh(size_t n, const void* rows, size_t stride, int degree, const gs4d_affine4* xf, size_t m, const void* bind, uint32_t form, size_t bind_stride,
+                         void* out) {
+    if (gs4d::rotate_sh_fault(n, stride, degree, m, bind != nullptr, form, bind_stride, 0)) return;
+    (degree == 0 ? &rotate_sh_rows<0> : degree == 1 ? &rotate_sh_rows<1> : degree == 2 ? &rotate_sh_rows<2> : &rotate_sh_rows<3>)(
+        n, (const unsigned char*)rows, stride, xf, m, (const unsigned char*)bind, form, bind_stride, (unsigned char*)out);
 }
 
 // The definition of gs4d_warp_records (gs4d.h) is csrc/warp_record.h: the record through the lattice's map linearised at its centre, or copied.  A

@@ -21,7 +21,7 @@ $(FLAGSTAMP):
 	rm -f $(CSRC)/.flags.*
 	touch $@
 
-OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/decompose.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/pose.o $(CSRC)/warp.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/merge.o $(CSRC)/merge_rows.o $(CSRC)/lod.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
+OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/decompose.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/pose.o $(CSRC)/sh_rotate.o $(CSRC)/warp.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/merge.o $(CSRC)/merge_rows.o $(CSRC)/lod.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
 
 .PHONY: all lib oracle ref refscene refdraw refgl clean demo sweep
 all: lib oracle demo sweep
@@ -100,6 +100,9 @@ $(CSRC)/transform_selected.o: $(CSRC)/transform_selected.hip $(CSRC)/record_tile
 # make POSE_GLOBAL_TABLE=1: gs4d_pose_records with every thread loading its table rows from global memory for every m, without the workgroup's copy of a small table in LDS; make POSE_WALK=4: a workgroup with the table in LDS takes 4 tiles instead of one (the measurements of DESIGN.md §4; never the shipped build)
 $(CSRC)/pose.o: $(CSRC)/pose.hip $(CSRC)/record_tile.h $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(POSE_GLOBAL_TABLE),-DGS4D_POSE_GLOBAL_TABLE) $(if $(POSE_WALK),-DGS4D_POSE_WALK=$(POSE_WALK)) -c $< -o $@
+# sh_rotate_record.h is the one text of gs4d_rotate_sh's definition — the frame of a map, the band matrices, a row under them — on top of pose_record.h: the kernel and the host library compile it (tests/sh_rotate_check.cpp compiles it too; gs4d_api.o and the host library take the call's checks and operand list from sh_rotate_operands.h); sh_rotate.o is built with the flags of pose.o
+$(CSRC)/sh_rotate.o: $(CSRC)/sh_rotate.hip $(CSRC)/record_tile.h $(CSRC)/sh_rotate_record.h $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # warp_record.h is the one text of gs4d_warp_records' definition, on top of pose_record.h and transform_record.h: the kernel and the host library compile it (tests/warp_record_check.cpp compiles it too; gs4d_api.o takes the lattice check from it); warp.o is built with the flags of pose.o
 # make WARP_LDS_NODES=512: gs4d_warp_records with the workgroup's copy in LDS of a lattice of at most 512 nodes, instead of every thread loading its nodes from global memory for every lattice; make WARP_GLOBAL_LATTICE=1 takes that copy out of such a build again (the measurements of DESIGN.md §4; the LDS copy is never the shipped build)
 $(CSRC)/warp.o: $(CSRC)/warp.hip $(CSRC)/record_tile.h $(CSRC)/warp_record.h $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
@@ -111,10 +114,10 @@ $(CSRC)/slice.o: $(CSRC)/slice.hip $(CSRC)/record_tile.h $(CSRC)/slice_record.h 
 $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(COUNT_IDS_PLAIN),-DGS4D_COUNT_IDS_PLAIN) -c $< -o $@
 # operands.h is the one text of the record-set calls' buffer-argument check (tests/operand_check.cpp compiles it too)
-$(CSRC)/gs4d_api.o: $(CSRC)/operands.h $(CSRC)/merge_record.h $(CSRC)/warp_record.h $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(CSRC)/lod_operands.h $(CSRC)/rows_operands.h $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(HD)
+$(CSRC)/gs4d_api.o: $(CSRC)/operands.h $(CSRC)/merge_record.h $(CSRC)/warp_record.h $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(CSRC)/lod_operands.h $(CSRC)/rows_operands.h $(CSRC)/sh_rotate_operands.h $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(HD)
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gs4d_internal.h $(CSRC)/composite_common.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/decompose_record.h $(CSRC)/transform_record.h $(CSRC)/pose_record.h $(CSRC)/warp_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/merge_record.h $(CSRC)/merge_rows_record.h $(CSRC)/lod_query.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
+$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/decompose_record.h $(CSRC)/transform_record.h $(CSRC)/pose_record.h $(CSRC)/sh_rotate_record.h $(CSRC)/sh_rotate_operands.h $(CSRC)/operands.h $(CSRC)/warp_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/merge_record.h $(CSRC)/merge_rows_record.h $(CSRC)/lod_query.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -fvisibility=hidden $(STRICT) -x c++ -c $< -o $@
 
 $(LIB): $(OBJS)

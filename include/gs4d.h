@@ -596,10 +596,13 @@ GS4D_API int gs4d_decompose_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, size_
  * The other per-record tables of the set:
  *     time spans (gs4d_record_time_spans)  are those of the SOURCE records.  When L touches time — a time row other than (0, 0, 0, 1), a time offset
  *                or a velocity column — they must be computed again for the transformed set; a purely spatial placement keeps them.
- *     SH table (gs4d_shade_sh)  is not rotated.  For a rigid map M, shade the SOURCE set with the camera mapped through the inverse (cam_pos' =
- *                M^-1 cam_pos, the time mapped back likewise), then transform: the call order per frame is
- *                shade -> transform -> gs4d_keygen -> gs4d_sort_pairs -> draw.  Under a map that is not rigid the colours are those of the source's
- *                directions.
+ *     SH table (gs4d_shade_sh)  is not rotated by this call; gs4d_rotate_sh (below) writes the rotated table, with the same xf and m
+ *                (GS4D_SH_EACH: row j*n + i for instance j), and the moved set is shaded with it and the true camera:
+ *                transform -> rotate_sh -> shade_sh -> gs4d_keygen -> gs4d_sort_pairs -> draw.  For ONE rigid map M over a whole set the cheaper
+ *                route moves no table: shade the SOURCE set with the camera mapped through the inverse (cam_pos' = M^-1 cam_pos, the time mapped
+ *                back likewise), then transform: shade -> transform -> gs4d_keygen -> gs4d_sort_pairs -> draw.  That route cannot serve m > 1
+ *                instances that face different ways, nor a set that is written back out with gs4d_decompose_records.  Under a map that is
+ *                not a similarity gs4d_rotate_sh turns the table by the Gram-Schmidt frame of the map's spatial block.
  *     depth keys (gs4d_keygen, GS4D_KEY_REF_INV_EUCLID)  move a centre by sig[3].xyz * (t - mu_t) without the division by Sigma44 that the draws'
  *                conditioning has, as the reference does: the key's centre is the conditional centre only where Sigma44 == 1.  A time scale a gives
  *                both factors an a, so the key's displacement takes a^2 where the conditional centre's takes none: every splat of a retimed set is
@@ -660,12 +663,109 @@ GS4D_API int gs4d_transform_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_
  * that may still have to be run again from dst are settled; the kernel is queued on the current frame lane, the call returns at once and starts no
  * new frame; src, xf and bind are buffers the call reads (a gs4d_buffer_subdata of the next frame's xf orders itself behind it), dst one it writes.
  * It counts as a full write of dst: the next draw or gs4d_keygen rebuilds the SoA shadow once.  Per frame: (shade) -> pose -> gs4d_keygen ->
- * gs4d_sort_pairs -> draw.  The notes of gs4d_transform_records on time spans, the SH table (not rotated) and the depth keys hold per record.
+ * gs4d_sort_pairs -> draw for a set of constant colours; a set with an SH table takes gs4d_rotate_sh (below) with the same xf, m, bind, form and
+ * bind_stride, since every record has a map of its own and no one camera serves them all:
+ *     pose -> rotate_sh -> shade_sh (on the posed set, with the true camera) -> gs4d_keygen -> gs4d_sort_pairs -> draw.
+ * The notes of gs4d_transform_records on time spans and the depth keys hold per record.
  * Out of scope: dual-quaternion blending, more than 4 influences, an in-place pose (src == dst), dense ids from gs4d_label_components labels. */
 #define GS4D_POSE_INDEX  0u   /* bind row: one uint32 j                                  */
 #define GS4D_POSE_BLEND4 1u   /* bind row: uint32 j[4], float w[4]  (32 bytes)           */
 GS4D_API int gs4d_pose_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_buf xf, size_t m, gs4d_buf bind, uint32_t form, size_t bind_stride,
                                gs4d_buf dst, size_t dst_first);
+
+/* ---- turning an SH table with the maps that move its records (no reference counterpart) ----
+ * gs4d_transform_records and gs4d_pose_records move records and copy their colour; the view-dependent part of a trained set's colour lives in its
+ * SH table (gs4d_shade_sh), whose rows belong to the orientation the set was trained in.  gs4d_rotate_sh writes a rotated copy of such a table on
+ * the device, the map of every row chosen exactly as the record calls choose it: the xf buffer and the bind table of the record call are passed
+ * again unchanged, and shading the moved set with the rotated table and the true camera gives the colours the set would show had it been trained
+ * in its new place.
+ *
+ * Rows are those of gs4d_shade_sh: float32, c_k of channel ch at row[3k + ch]; stride is a multiple of 16, 16 .. 1024, at least 12 (degree + 1)^2.
+ * Where a row goes:
+ *   GS4D_SH_EACH       bind must be 0, bind_stride is not looked at.  Row dst_first + j*n + i of dst is row i < n of src under map j < m of xf: the
+ *                      layout of gs4d_transform_records.
+ *   GS4D_POSE_INDEX, GS4D_POSE_BLEND4   row dst_first + i of dst is row i < n of src under the map that row i of bind chooses among the m rows of
+ *                      xf, by the rules of gs4d_pose_records word for word: INDEX takes row j < m and copies for j >= m (GS4D_ID_NONE included);
+ *                      BLEND4 slots take part iff j[k] < m, the 16 floats of l are the blended a[0..15] of that definition (full products, a weight of
+ *                      0 is multiplied like any other), and a row no slot of which takes part is copied.  bind_stride as there: a multiple of 4, at
+ *                      least 4 / a multiple of 16, at least 32.
+ * What is written: always the whole row.  Words 0..2 (the DC term) and every byte past 12 (degree + 1)^2 are copied bit for bit from the source
+ * row: a table with a payload behind the coefficients keeps it.  At degree 0 the call is a tiled row copy (the m * n rows of instancing).  A row
+ * whose map does not rotate (below), or that names no map, is copied byte for byte, NaN payloads included.  No other byte of dst is written; no
+ * byte of src, xf or bind is written.
+ *
+ * The rotation of a map (gs4d_host_sh_rotation is this text).  Only the spatial block is looked at: a_c[r] = l[4c + r], r, c < 3; time row, time
+ * column and offset take no part.  R is the Gram-Schmidt frame of the columns in the order 0, 1, 2, in float32, round to nearest, no contraction
+ * (every product and every sum below is rounded on its own, in the order its parentheses give), with correctly rounded division and square root:
+ *     dot(a, b) = ((a[0]*b[0]) + (a[1]*b[1])) + (a[2]*b[2])
+ *     n0 = dot(a0, a0)                                              e0 = a0 * (1.0f / sqrtf(n0))
+ *     u1 = a1 - (dot(e0, a1) * e0)                                  n1 = dot(u1, u1)      e1 = u1 * (1.0f / sqrtf(n1))
+ *     u2 = (a2 - (dot(e0, a2) * e0)) - (dot(e1, a2) * e1)           n2 = dot(u2, u2)      e2 = u2 * (1.0f / sqrtf(n2))
+ * per component.  If any of n0, n1, n2 is not > 0 or not finite — a zero, singular, NaN or overflowing block, or one so small that its squared
+ * length underflows — the map DOES NOT ROTATE (the later steps are not evaluated).  R[r][c] = e_c[r].  A similarity (a rotation times a uniform
+ * scale, all gs4d_host_affine4 produces) gives its rotation back up to rounding; a mirror stays a mirror (e2 is not forced right-handed); a blended
+ * skinning matrix gets the frame its columns span.
+ *
+ * The band matrices, defined by the basis, constants and signs of gs4d_shade_sh: for every unit d and every band L = 1, 2, 3
+ *     sum_k c'_k b_k(d) = sum_k c_k b_k(R^T d)          which gives c'_L = D_L c_L, D_L of size 3x3, 5x5, 7x7.
+ * D_L(m, n) has m, n = -L .. L; coefficient k = L^2 + L + m.
+ *   D_1 needs no arithmetic: b_1..b_3 = C1 * (-y, z, -x), so D_1 = P R P^T with the signed permutation P of (x, y, z) -> (-y, z, -x):
+ *     D_1(i, j) = s_i s_j R[a_i][a_j],  a = (1, 2, 0), s = (-1, +1, -1) for i, j = -1, 0, 1        (a move or a negation)
+ *   D_2 from D_1 and D_1, D_3 from D_1 and D_2 by the recurrences of Ivanic and Ruedenberg (J. Phys. Chem. 100 (1996) 6342; 102 (1998) 9099): the
+ *   basis of gs4d_shade_sh is the real spherical harmonics seen through the half turn about z, (x, y, z) -> (-x, -y, z), which is what the signs of
+ *   P carry, so the recurrences apply to D_1 as it stands.  With Dp = D_(L-1) and E = L - 1:
+ *     P(i, a, n) =  (D_1(i, 1)*Dp(a, E)) - (D_1(i, -1)*Dp(a, -E))        for n ==  L
+ *                   (D_1(i, 1)*Dp(a, -E)) + (D_1(i, -1)*Dp(a, E))        for n == -L
+ *                   D_1(i, 0)*Dp(a, n)                                   otherwise
+ *     U = P(0, m, n)
+ *     V = P(1, 1, n) + P(-1, -1, n)            m == 0           W = P(1, m+1, n) + P(-1, -m-1, n)       m > 0
+ *         P(1, 0, n)                           m == 1               P(1, m-1, n) - P(-1, -m+1, n)       m < 0
+ *         P(-1, 0, n)                          m == -1
+ *         P(1, m-1, n) - P(-1, -m+1, n)        m > 1
+ *         P(1, m+1, n) + P(-1, -m-1, n)        m < -1
+ *     D_L(m, n) = ((u*U) + (v*V)) + (w*W)      a term whose coefficient is a zero of the tables is left out (u: |m| == L; w: m == 0 or |m| >= L - 1)
+ *   The coefficients depend on |m| and |n|, each rounded to float32 from
+ *     u = sqrt((L+m)(L-m) / den)     v = (m == 0 ? -1 : 1) * sqrt((1 + [m == 0]) (L+|m|-1)(L+|m|) / den) / 2, times sqrt 2 where |m| == 1
+ *     w = -sqrt((L-|m|-1)(L-|m|) / den) / 2          den = (L+n)(L-n) for |n| < L, 2L(2L-1) for |n| == L
+ *   row |m| = 0 .. L, column |n| = 0 .. L:
+ *     u, L = 2: { 1, 1.1547005383792515, 0.57735026918962573 }  { 0.8660254037844386, 1, 0.5 }  { 0, 0, 0 }
+ *     v, L = 2: { -0.5, -0.57735026918962573, -0.28867513459481287 }  { 0.8660254037844386, 1, 0.5 }  { 0.8660254037844386, 1, 0.5 }
+ *     w, L = 2: all 0
+ *     u, L = 3: { 1, 1.0606601717798212, 1.3416407864998738, 0.54772255750516607 }  { 0.94280904158206336, 1, 1.2649110640673518, 0.5163977794943222 }
+ *               { 0.7453559924999299, 0.79056941504209488, 1, 0.40824829046386302 }  { 0, 0, 0, 0 }
+ *     v, L = 3: { -0.57735026918962573, -0.61237243569579447, -0.7745966692414834, -0.31622776601683794 }
+ *               { 0.81649658092772603, 0.8660254037844386, 1.0954451150103321, 0.44721359549995793 }
+ *               { 0.7453559924999299, 0.79056941504209488, 1, 0.40824829046386302 }  { 0.9128709291752769, 0.96824583655185426, 1.2247448713915889, 0.5 }
+ *     w, L = 3: row 1 = { -0.23570226039551584, -0.25, -0.31622776601683794, -0.12909944487358055 }, every other row 0
+ *   Only + - * are used.  Being homogeneous of degree L in R, D_L of a mirror is what the defining identity asks of it.
+ * Layout of d[84], all row-major: D_1 at 0, D_2 at 9, D_3 at 34, word 83 is 0.
+ * The application, per channel and output coefficient i of a band, in ascending j:
+ *     acc = D[i][0]*c_0      then      acc = acc + (D[i][j]*c_j)      j = 1 .. 2L
+ * Consequences.  Under the identity map (any positive power-of-two scale of it included) the frame is exact, every D_L is the unit matrix with
+ * zeros of either sign around it, and every finite row comes back with its values and, for every word that is not a zero, its bits; a -0
+ * coefficient does NOT promise to keep its sign (a sum of zeros of both signs is +0).  A non-finite coefficient spreads through its band and
+ * channel as the products give.  Two quarter turns about z give the half turn's bits.
+ * The device gives the bits of gs4d_host_rotate_sh, except that a word that is a NaN on both sides in a rotated (not copied) row may differ in sign
+ * and payload.  Nothing depends on the order in which anything runs on the device.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: n, m or dst_first above 0xFFFFFFFF, and so m * n and dst_first + m * n (GS4D_SH_EACH) or
+ * dst_first + n (the other forms); a degree outside 0 .. 3; a stride that breaks the rule; an unknown form; bind != 0 with GS4D_SH_EACH, bind == 0
+ * with the other two; a bind_stride that breaks the form's rule; a name that is not a live buffer; any two buffers being the same; src smaller than
+ * n * stride bytes; xf smaller than 80 m; bind smaller than n * bind_stride; dst holding fewer rows than the call writes past dst_first.  n == 0 is
+ * a no-op, and so is m == 0 with GS4D_SH_EACH; m == 0 with a bind table copies every row.  The rows of xf, bind and src are data.
+ *
+ * Ordering, that of gs4d_copy_rows: the kernel is queued on the current frame lane and the call returns at once; src, xf and bind are buffers the
+ * call reads, dst one it writes, keeping the rows it does not name.  A table is not a record buffer: no shadow is built or invalidated.  The frame
+ * loops:
+ *     pose -> rotate_sh -> shade_sh (on the posed set, with the true camera) -> gs4d_keygen -> gs4d_sort_pairs -> draw
+ *     transform -> rotate_sh -> shade_sh -> ...        for instances (GS4D_SH_EACH, the same xf and m)
+ * For ONE rigid map over a whole set the camera-inverse route of gs4d_transform_records stays the cheaper choice: it moves no table.
+ * Out of scope: gs4d_warp_records (a warp needs the local rotation of its Jacobian) and gs4d_transform_selected (a selection needs a rule operand);
+ * degrees above 3; an in-place rotation (src == dst). */
+#define GS4D_SH_EACH 2u   /* no bind table: every map to every row, the layout of gs4d_transform_records */
+GS4D_API int gs4d_rotate_sh(gs4d_ctx* ctx, gs4d_buf src, size_t n, size_t stride, int degree,
+                            gs4d_buf xf, size_t m, gs4d_buf bind /* 0 with GS4D_SH_EACH */, uint32_t form, size_t bind_stride,
+                            gs4d_buf dst, size_t dst_first);
 
 /* ---- a map that varies from point to point: a set deformed through a 4D lattice (no reference counterpart) ----
  * gs4d_transform_records and gs4d_pose_records apply affine maps.  A cage or free-form deformation in an editor (bend, bulge, taper), a baked
@@ -717,9 +817,10 @@ GS4D_API int gs4d_pose_records(gs4d_ctx* ctx, gs4d_buf src, size_t n, gs4d_buf x
  * frame; src and nodes are buffers the call reads (a gs4d_buffer_subdata of the next frame's nodes orders itself behind it), dst one it writes.
  * It counts as a full write of dst: the next draw or gs4d_keygen rebuilds the SoA shadow once.  Per frame: (shade) -> warp -> gs4d_keygen ->
  * gs4d_sort_pairs -> draw.  The notes of gs4d_transform_records hold per record: time spans must be computed again when the lattice has a time axis
- * or a dt component; the SH table is not rotated; the depth-key remark holds.
+ * or a dt component; the SH table is not rotated, and gs4d_rotate_sh does not serve a warp (it takes affine maps; a warp would need the local
+ * rotation of its Jacobian at every record); the depth-key remark holds.
  * Out of scope: an in-place warp (src == dst), a statistics rule that selects which records warp, higher-order (B-spline) lattices, rotating SH
- * rows, reporting folded records. */
+ * rows by the warp's local rotation, reporting folded records. */
 typedef struct gs4d_lattice {
     float    lo[4];     /* where node 0 stands on x, y, z, t                         */
     float    inv[4];    /* nodes per unit along each axis (1 / spacing)              */
@@ -1054,7 +1155,8 @@ GS4D_API int gs4d_measure_records(gs4d_ctx* ctx, gs4d_buf data, size_t n, const 
  * exactly one per call followed by a draw).  The call order per frame is (shade) -> (edit) -> transform_selected -> keygen -> sort_pairs -> draw.
  *
  * The caller's other tables — the notes of gs4d_transform_records, for the selected rows only: time spans are to be recomputed when L touches
- * time; SH tables are not rotated; the key-order note for a time scale still applies; statistics, spatial order and kept_index rows are
+ * time; SH tables are not rotated, and gs4d_rotate_sh does not serve a selection (it has no rule operand: rotate a compacted copy of the
+ * selected rows, or pose with a bind table, instead); the key-order note for a time scale still applies; statistics, spatial order and kept_index rows are
  * unaffected, because no record moves in memory.
  *
  * Out of scope: patching the SoA shadow instead of rebuilding it; one transform per record; a time component of the pivot; weighted pivots;
@@ -1587,6 +1689,14 @@ GS4D_API void gs4d_host_transform_records(size_t n, const float* records24, cons
  * breaks the form's rule, writes nothing. */
 GS4D_API void gs4d_host_pose_records(size_t n, const float* records24, const gs4d_affine4* xf, size_t m, const void* bind, uint32_t form,
                                      size_t bind_stride, float* out24);
+/* The rotation of a map, of gs4d_rotate_sh (the text above its declaration): from the 16 floats of l, the band matrices D_1 at d[0], D_2 at d[9],
+ * D_3 at d[34], all row-major, word 83 = 0, and 1; or 0, with d not written, where the map does not rotate. */
+GS4D_API int  gs4d_host_sh_rotation(const float l[16], float d[84]);   /* 1: d holds the matrices; 0: this map does not rotate */
+/* The definition of gs4d_rotate_sh: the rows of `out` (stride bytes each; m * n of them with GS4D_SH_EACH, row j*n + i = row i under map j, else n)
+ * from the n rows of `rows` under the maps the form chooses among the m rows of xf (bind: NULL with GS4D_SH_EACH).  out must not overlap rows.
+ * Arguments the device call would refuse write nothing. */
+GS4D_API void gs4d_host_rotate_sh(size_t n, const void* rows, size_t stride, int degree, const gs4d_affine4* xf, size_t m,
+                                  const void* bind, uint32_t form, size_t bind_stride, void* out);
 /* The definition of gs4d_warp_records: out24 record i = records24 record i through the lattice *lat of the nodes nodes4 (4 floats each), i < n (the
  * text above the declaration of gs4d_warp_records).  out24 must not overlap records24.  A lattice the device call would refuse (NULL included)
  * writes nothing. */
