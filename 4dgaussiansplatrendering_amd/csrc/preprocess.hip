@@ -10,6 +10,7 @@
 #include "gs4d_internal.h"
 #include "footprint_rect.h"
 #include "depth_key.h"
+#include "proj_tile.h"
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -145,9 +146,19 @@ __device__ __forceinline__ void eigen2(float u00, float u01, float u10, float u1
 
 __device__ __forceinline__ bool fin(float x) { return isfinite(x); }
 
-// Window-space set-up + record store.  ncx,ncy = NDC centre; kx,ky = NDC scale of the quad offset; depth = -z_view of the centre (0: none).
+// The projected record as its four 16-byte pieces, in the registers of the thread that projected it: emit() fills it, and its caller sends it to
+// out.proj — by itself (store_record) or through its wave (proj_tile.h).
+struct ProjRecord { float4 o[proj_tile::PIECES]; };
+// every thread stores its own record: k_preprocess, and the k_project_count instances of a source that does not store through the wave (WAVE_STORE)
+__device__ __forceinline__ void store_record(const PreOut& out, uint32_t i, const ProjRecord& p) {
+    float4* o = out.proj + (size_t)i * 4;
+#pragma unroll
+    for (uint32_t k = 0; k < proj_tile::PIECES; ++k) o[k] = p.o[k];
+}
+
+// Window-space set-up + the record (into `p`: the caller stores it).  ncx,ncy = NDC centre; kx,ky = NDC scale of the quad offset; depth = -z_view of the centre (0: none).
 __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid, const Quad& q, float ncx, float ncy, float kx, float ky,
-                                      int W, int H, float r, float g, float b, float alpha, bool clamp_rgb, float depth) {
+                                      int W, int H, float r, float g, float b, float alpha, bool clamp_rgb, float depth, ProjRecord& p) {
     float cx = 0, cy = 0, a0x = 0, a0y = 0, a1x = 0, a1y = 0, hx = 0, hy = 0;
     uint32_t rect0 = 1u, rect1 = 0u;           // empty
     if (valid) {
@@ -183,7 +194,7 @@ __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid,
     uint32_t list0 = rect0, list1 = rect1;
     if (out.cull_alpha0 && alpha == 0.0f && fin(r) && fin(g) && fin(b) && fin(depth)) { list0 = 1u; list1 = 0u; }
     if (out.trects) out.trects[i] = pack_trect(list0, list1);      // (null: nothing downstream reads it — a staged draw writes its list entries itself)
-    float4* o = out.proj + (size_t)i * 4;
+    float4* const o = p.o;
     // (x components of the two affine rows side by side, likewise y: the compositor forms u and v with packed two-float instructions)
     o[0] = make_float4(cx, cy, a0x, a1x);
     o[1] = make_float4(a0y, a1y, r, g);
@@ -191,7 +202,8 @@ __device__ __forceinline__ uint2 emit(const PreOut& out, uint32_t i, bool valid,
     // Nothing but gs4d_debug_read_projected and the compositor of a draw with aux outputs (the depth) reads the fourth float4 — and it is
     // written all the same: the record is one 64-byte line, and a line written whole goes to memory as it is, while a line with 16 bytes
     // missing has to be merged with what memory holds.  Measured with this store left out (round 3, 10^7 records): the projection kernel
-    // 373 -> 459 us; at 10^6 records no difference (40.1 / 40.4 us).
+    // 373 -> 459 us; at 10^6 records no difference (40.1 / 40.4 us).  (True whichever way the pieces leave: a wave that stores its records through
+    // LDS, proj_tile.h, writes whole lines only because the fourth piece is among them.)
     o[3] = make_float4(hx, hy, valid ? 1.0f : 0.0f, out.aux ? depth : 0.0f);
     return make_uint2(list0, list1);
 }
@@ -295,7 +307,7 @@ struct Src3D { const float* verts; };
 struct Src2D { const float* recs; };
 
 __device__ __forceinline__ uint2 project_4d(const float4& pos, const float4& col, const float4& s0, const float4& s1, const float4& s2, const float4& s3,
-                                            uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key);
+                                            uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key, ProjRecord& p);
 // A record as loaded, before any of it is used: load_record issues all of a record's loads together, project_record(src, rec, ...) projects what they
 // brought.  The staged loop of k_project_count loads round it + 1's record before it computes round it (the stores through PreOut may alias the source
 // planes as far as the compiler knows: it hoists no load across them by itself).
@@ -337,25 +349,34 @@ __device__ __forceinline__ void arrived(LoadHere&) {}
 __device__ __forceinline__ Rec4DStatic load_ahead(const Src4DStatic& src, uint32_t i) { return load_record(src, i); }
 template <class SRC>
 __device__ __forceinline__ LoadHere load_ahead(const SRC&, uint32_t) { return LoadHere{}; }
-__device__ __forceinline__ uint2 project_record(const Src4D&, const Rec4D& r, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
-    return project_4d(r.pos, r.col, r.s0, r.s1, r.s2, r.s3, i, u, out, ks, key);
+// WAVE_STORE: whether the k_project_count instances of a source send their records to out.proj through the wave's stage in LDS, as whole 64-byte lines
+// (proj_tile.h), or every thread stores its own.  The stage costs an instance 6-8 VGPRs (profiles/r16_kernel_resources_*.txt): a source opts in where
+// its instances keep their workgroups per CU and its frames gain — the static source does; the 96-byte source's staged instances
+// would lose their third workgroup per CU, the symmetric one has no workload of the benchmark, Src3D and Src2D are never staged at scale.
+// make lib PROJ_PLAIN_STORE=1: no source does (the measurement of round 16; never the shipped build).
+template <class SRC> constexpr bool WAVE_STORE = false;
+#if !defined(GS4D_PROJ_PLAIN_STORE)
+template <> constexpr bool WAVE_STORE<Src4DStatic> = true;
+#endif
+__device__ __forceinline__ uint2 project_record(const Src4D&, const Rec4D& r, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key, ProjRecord& p) {
+    return project_4d(r.pos, r.col, r.s0, r.s1, r.s2, r.s3, i, u, out, ks, key, p);
 }
-__device__ __forceinline__ uint2 project_record(const Src4DSym&, const Rec4DSym& r, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
+__device__ __forceinline__ uint2 project_record(const Src4DSym&, const Rec4DSym& r, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key, ProjRecord& p) {
     const float4& U = r.U; const float4& V = r.V; const float2& W = r.W;
     // sig[c] = column c; the mirrored elements are the same bits (verified by the repack kernel)
-    return project_4d(r.pos, r.col, make_float4(U.x, U.y, U.z, V.x), make_float4(U.y, U.w, W.x, V.y), make_float4(U.z, W.x, W.y, V.z), V, i, u, out, ks, key);
+    return project_4d(r.pos, r.col, make_float4(U.x, U.y, U.z, V.x), make_float4(U.y, U.w, W.x, V.y), make_float4(U.z, W.x, W.y, V.z), V, i, u, out, ks, key, p);
 }
-__device__ __forceinline__ uint2 project_record(const Src4DStatic& src, const Rec4DStatic& r, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
+__device__ __forceinline__ uint2 project_record(const Src4DStatic& src, const Rec4DStatic& r, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key, ProjRecord& p) {
     const float4& A = r.A; const float4& B = r.B; const float4& C = r.C;
     const float* c = src.cs.v;
     return project_4d(make_float4(A.x, A.y, A.z, c[0]), r.col, make_float4(A.w, B.x, B.y, c[1]), make_float4(B.z, B.w, C.x, c[2]), make_float4(C.y, C.z, C.w, c[3]), make_float4(c[4], c[5], c[6], c[7]),
-                      i, u, out, ks, key);
+                      i, u, out, ks, key, p);
 }
 // load, then project: what every caller that has no record in registers runs (the 4D sources; Src3D and Src2D read their record where they project, below)
 template <class SRC>
-__device__ __forceinline__ uint2 project_record(const SRC& src, LoadHere, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) { return project_record(src, load_record(src, i), n, i, u, out, ks, key); }
+__device__ __forceinline__ uint2 project_record(const SRC& src, LoadHere, uint32_t n, uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key, ProjRecord& p) { return project_record(src, load_record(src, i), n, i, u, out, ks, key, p); }
 __device__ __forceinline__ uint2 project_4d(const float4& pos, const float4& col, const float4& s0, const float4& s1, const float4& s2, const float4& s3,
-                                            uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key) {
+                                            uint32_t i, const PU& u, const PreOut& out, const KeySrc& ks, uint32_t& key, ProjRecord& p) {
     float s44 = s3.w;
     float dt = u.time - pos.w;
     float ot = maxf_glsl(expf(-0.5f * dt * (1.0f / s44) * dt), u.min_opacity);     // :48-51, 83
@@ -374,10 +395,10 @@ __device__ __forceinline__ uint2 project_4d(const float4& pos, const float4& col
     Quad q; float ncx = 0, ncy = 0, depth = 0;
     bool valid = project3d(u, mx, my, mz, C, q, ncx, ncy, depth);
     key = blend_key_4d(ks, i, pos, s3);
-    return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, col.x, col.y, col.z, ot * col.w, true, depth);
+    return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, col.x, col.y, col.z, ot * col.w, true, depth, p);
 }
 
-__device__ __forceinline__ uint2 project_record(const Src3D& src, LoadHere, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key) {
+__device__ __forceinline__ uint2 project_record(const Src3D& src, LoadHere, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key, ProjRecord& p) {
     const float* v = src.verts + (size_t)72 * i;      // vertex 0 of the quad: {vpos2, spos3, col4, sig9}
     float C[3][3];
 #pragma unroll
@@ -387,10 +408,10 @@ __device__ __forceinline__ uint2 project_record(const Src3D& src, LoadHere, uint
     Quad q; float ncx = 0, ncy = 0, depth = 0;
     bool valid = project3d(u, v[2], v[3], v[4], C, q, ncx, ncy, depth);
     key = i;
-    return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, v[5], v[6], v[7], v[8], false, depth);
+    return emit(out, i, valid, q, ncx, ncy, u.P[0], u.P[5], u.W, u.H, v[5], v[6], v[7], v[8], false, depth, p);
 }
 
-__device__ __forceinline__ uint2 project_record(const Src2D& src, LoadHere, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key) {
+__device__ __forceinline__ uint2 project_record(const Src2D& src, LoadHere, uint32_t, uint32_t i, const PU& u, const PreOut& out, const KeySrc&, uint32_t& key, ProjRecord& p) {
     const float* rec = src.recs + (size_t)12 * i;
     const float* P = u.P;
     float x = rec[0], y = rec[1];
@@ -410,7 +431,7 @@ __device__ __forceinline__ uint2 project_record(const Src2D& src, LoadHere, uint
     bool valid = (clipw > 0.0f) && !(clipz < -clipw || clipz > clipw);
     float kx = P[0] / clipw, ky = P[5] / clipw;
     key = i;
-    return emit(out, i, valid, q, kx * psx, ky * psy, kx, ky, u.W, u.H, rec[4], rec[5], rec[6], rec[7], true, 0.0f);      // 2D records have no depth
+    return emit(out, i, valid, q, kx * psx, ky * psy, kx, ky, u.W, u.H, rec[4], rec[5], rec[6], rec[7], true, 0.0f, p);     // 2D records have no depth
 }
 
 // One thread per record (the ordered path).
@@ -419,7 +440,9 @@ __global__ __launch_bounds__(256) void k_preprocess(SRC src, uint32_t n, PU u, P
     const uint32_t i = blockIdx.x * 256u + threadIdx.x;
     if (i >= n) return;
     uint32_t key;
-    (void)project_record(src, LoadHere{}, n, i, u, out, tc.ks, key);
+    ProjRecord p;
+    (void)project_record(src, LoadHere{}, n, i, u, out, tc.ks, key, p);
+    store_record(out, i, p);
 }
 
 // ---- k_project_count: a workgroup projects one segment of the records, and does what the form asks beside (TileCount, gs4d_internal.h) ----
@@ -437,11 +460,17 @@ static_assert(SEGFEED_BLOCK == (uint32_t)(STAGE_R * SEG_THREADS) && SEG_THREADS 
 // reordered pairs in stage[8 KB, 24 KB) — launch_segments asks for at least SEGFEED_LDS bytes of stage[].
 constexpr size_t SEGFEED_COUNTERS = (4 * OS_MAX_BINS) * 4;                             // bytes of stage[]: the counters of waves 4..7
 constexpr size_t SEGFEED_LDS = SEGFEED_COUNTERS + (size_t)SEGFEED_BLOCK * 8;           // ... then the pairs
+// A source with WAVE_STORE: during the rounds stage[] also holds the eight waves' record stages (proj_tile.h) — from its first byte, or behind the counters of a
+// segment-fed producer, which are live then.  Everything else of stage[] is written only behind the barrier that ends the rounds.
+constexpr size_t WAVE_STAGES_BYTES = proj_tile::stage_bytes(SEG_THREADS / 64, proj_tile::PITCH);
+constexpr size_t wave_stages_at(bool segf) { return segf ? SEGFEED_COUNTERS : 0; }
 struct ProjLds {
     uint32_t* h;                        // lists: the segment's entries per bucket; placing pass: the buckets' cursors
     uint32_t (*kh)[OS_MAX_BINS];        // keys Write: the digit histograms (os_hist_*); keys SegmentFed: the digit counters of waves 0..3
     uint32_t* ws;                       // the wave sums of a block scan
     uint2* stage;
+    float4* records;                    // WAVE_STORE: this wave's stage for the records of a round (proj_tile.h), laid over stage[] — which is idle during the rounds but for the
+                                        // segment-fed form's counters, and the stages stand behind those (wave_stages_at)
     __device__ __forceinline__ uint32_t* stage32() const { return reinterpret_cast<uint32_t*>(stage); }
     __device__ __forceinline__ uint32_t* wave_row(uint32_t k) const { return k < 4u ? kh[k] : stage32() + (k - 4u) * OS_MAX_BINS; }      // segment-fed: the digit counters of wave k
     __device__ __forceinline__ uint2* pairs() const { return stage + SEGFEED_COUNTERS / sizeof(uint2); }                                  // segment-fed: the reordered pairs
@@ -468,8 +497,11 @@ __device__ __forceinline__ void project_round(const SRC& src, const REC& rec, ui
                                               const TileCount& tc, const ProjLds& lds, KeptRecords<R>& kept) {
     TRect r{ 0u, 0u, 0u, 0u, 1u, 0u };
     uint32_t key = 0u;
+    const uint32_t lane = threadIdx.x & 63u;
     if (i < i1) {
-        const uint2 rect = project_record(src, rec, n, i, u, out, tc.ks, key);
+        ProjRecord p;
+        const uint2 rect = project_record(src, rec, n, i, u, out, tc.ks, key, p);
+        if constexpr (WAVE_STORE<SRC>) proj_tile::put_record(lds.records, lane, p.o); else store_record(out, i, p);
         if constexpr (LISTS != ProjLists::None) {
             if (LISTS == ProjLists::Count && KEYS == ProjKeys::None) tc.skey[i] = key;               // fused: k_bucket_scatter takes the key from the caller's key buffer, written just below
             r = tile_rect(rect.x, rect.y, (uint32_t)tc.shard_rank, (uint32_t)tc.shard_world);
@@ -484,6 +516,14 @@ __device__ __forceinline__ void project_round(const SRC& src, const REC& rec, ui
             }
             if (key > tc.span) __hip_atomic_store(tc.err, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);      // below the bias wraps to a huge value: caught too
         }
+    }
+    if constexpr (WAVE_STORE<SRC>) {
+        // All 64 lanes are here, and lane 0's record is a multiple of 64 in every form (a segment starts at a multiple of SEG_THREADS, a round and a wave's share of it
+        // at multiples of 64): the wave's records below i1 are one contiguous piece of out.proj, and leave as whole lines.  Wave-level ordering is all it takes.
+        const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane((int)(i - lane));
+        proj_tile::wave_sync();
+        proj_tile::store_staged(out.proj + (size_t)first * proj_tile::PIECES, lds.records, lane, proj_tile::wave_have(first, i1));
+        proj_tile::wave_sync();      // the next round's puts stay behind these reads
     }
     if constexpr (KEYS == ProjKeys::Write) os_hist_add(lds.kh, key, i < i1, tc.hist_rows, tc.hist_rb, tc.hist_top);       // a hybrid-planned sort: the top-digit row alone (one LDS atomic per record, not three)
     if constexpr (LISTS != ProjLists::None) count_buckets(lds.h, tc.nb - 1u, (uint32_t)tc.tiles_x, r);
@@ -580,8 +620,9 @@ __global__ __launch_bounds__(SEG_THREADS) void k_project_count(SRC src, uint32_t
     __shared__ uint32_t kh[KEYED ? OS_MAX_PASSES : 1][OS_MAX_BINS];
     __shared__ uint32_t ws[SEG_THREADS / 64 + 1];
     extern __shared__ __attribute__((aligned(16))) uint2 stage[];      // (copied out 16 bytes at a time: 16-byte base)
-    const ProjLds lds{ h, kh, ws, stage };
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    float4* const records = WAVE_STORE<SRC> ? reinterpret_cast<float4*>(reinterpret_cast<char*>(stage) + wave_stages_at(SEGF)) + proj_tile::record_slot(wave * proj_tile::WAVE, proj_tile::PITCH) : nullptr;
+    const ProjLds lds{ h, kh, ws, stage, records };
     if (COUNTS) for (uint32_t b = threadIdx.x; b < tc.nb; b += SEG_THREADS) h[b] = 0u;
     if (KEYED && threadIdx.x < 256u) os_hist_clear(kh, threadIdx.x);
     if (SEGF) for (uint32_t q = threadIdx.x; q < SEGFEED_COUNTERS / 4; q += SEG_THREADS) lds.stage32()[q] = 0u;
@@ -636,6 +677,7 @@ template <class SRC, ProjLists LISTS, ProjKeys KEYS>
 static hipError_t launch_segments(hipStream_t st, const SRC& src, size_t n, const PU& pu, const PreOut& out, const TileCount& tc) {
     size_t lds = LISTS == ProjLists::Stage ? (size_t)tc.scap * 8 : 0;
     if (KEYS == ProjKeys::SegmentFed) lds = std::max(lds, SEGFEED_LDS);
+    if (WAVE_STORE<SRC>) lds = std::max(lds, wave_stages_at(KEYS == ProjKeys::SegmentFed) + WAVE_STAGES_BYTES);      // forms None and Count have no other use of stage[]
     k_project_count<SRC, LISTS, KEYS><<<dim3((unsigned)((n + tc.seg - 1) / tc.seg)), dim3(SEG_THREADS), lds, st>>>(src, (uint32_t)n, pu, out, tc);
     return hipGetLastError();
 }

@@ -15,8 +15,8 @@ endif
 # keygen/sort and preprocess must round exactly like the CPU expressions they are checked against
 STRICT   := -ffp-contract=off
 
-# the build mode is a prerequisite of every object: switching between `make lib`, `make lib TUNING=1`, `make lib COUNT_IDS_PLAIN=1`, `make lib BUILD_PLAIN=1`, `make lib TRANSFORM_STAGED_LOAD=1`, `make lib XFSEL_PLAIN=1`, `make lib POSE_GLOBAL_TABLE=1`, `make lib POSE_WALK=4`, `make lib WARP_LDS_NODES=512`, `make lib WARP_GLOBAL_LATTICE=1`, `make lib ROWS_MASS_RECOMPUTE=1` and `make lib ROWS_CHUNK=16` rebuilds all of them
-FLAGSTAMP := $(CSRC)/.flags.$(if $(TUNING),tuning,release)$(if $(COUNT_IDS_PLAIN),-plain)$(if $(BUILD_PLAIN),-buildplain)$(if $(TRANSFORM_STAGED_LOAD),-transformstagedload)$(if $(XFSEL_PLAIN),-xfselplain)$(if $(POSE_GLOBAL_TABLE),-poseglobaltable)$(if $(POSE_WALK),-posewalk$(POSE_WALK))$(if $(WARP_LDS_NODES),-warpldsnodes$(WARP_LDS_NODES))$(if $(WARP_GLOBAL_LATTICE),-warpgloballattice)$(if $(ROWS_MASS_RECOMPUTE),-rowsmassrecompute)$(if $(ROWS_CHUNK),-rowschunk$(ROWS_CHUNK))
+# the build mode is a prerequisite of every object: switching between `make lib`, `make lib TUNING=1`, `make lib COUNT_IDS_PLAIN=1`, `make lib BUILD_PLAIN=1`, `make lib TRANSFORM_STAGED_LOAD=1`, `make lib XFSEL_PLAIN=1`, `make lib POSE_GLOBAL_TABLE=1`, `make lib POSE_WALK=4`, `make lib WARP_LDS_NODES=512`, `make lib WARP_GLOBAL_LATTICE=1`, `make lib ROWS_MASS_RECOMPUTE=1`, `make lib ROWS_CHUNK=16`, `make lib PROJ_PLAIN_STORE=1` and `make lib PROJ_PITCH=4` rebuilds all of them
+FLAGSTAMP := $(CSRC)/.flags.$(if $(TUNING),tuning,release)$(if $(COUNT_IDS_PLAIN),-plain)$(if $(BUILD_PLAIN),-buildplain)$(if $(TRANSFORM_STAGED_LOAD),-transformstagedload)$(if $(XFSEL_PLAIN),-xfselplain)$(if $(POSE_GLOBAL_TABLE),-poseglobaltable)$(if $(POSE_WALK),-posewalk$(POSE_WALK))$(if $(WARP_LDS_NODES),-warpldsnodes$(WARP_LDS_NODES))$(if $(WARP_GLOBAL_LATTICE),-warpgloballattice)$(if $(ROWS_MASS_RECOMPUTE),-rowsmassrecompute)$(if $(ROWS_CHUNK),-rowschunk$(ROWS_CHUNK))$(if $(PROJ_PLAIN_STORE),-projplainstore)$(if $(PROJ_PITCH),-projpitch$(PROJ_PITCH))
 $(FLAGSTAMP):
 	rm -f $(CSRC)/.flags.*
 	touch $@
@@ -42,8 +42,10 @@ HD := $(CSRC)/hd.h
 $(CSRC)/sort.o: $(CSRC)/sort.hip $(CSRC)/depth_key.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 # footprint_rect.h is the one text of the pixel rectangle (tests/footprint_rect_check.cpp compiles it too)
-$(CSRC)/preprocess.o: $(CSRC)/preprocess.hip $(CSRC)/footprint_rect.h $(CSRC)/depth_key.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
-	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+# proj_tile.h is the one text of a wave's stage of projected records — the put, the whole-line store, the slots (tests/proj_tile_check.cpp compiles its plain part too)
+# make PROJ_PLAIN_STORE=1: k_project_count with every thread storing its own projected record, whatever the source; make PROJ_PITCH=4: the records of a wave's stage back to back instead of five pieces apart (the measurements of DESIGN.md §9 round 16; never the shipped build)
+$(CSRC)/preprocess.o: $(CSRC)/preprocess.hip $(CSRC)/proj_tile.h $(CSRC)/footprint_rect.h $(CSRC)/depth_key.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(PROJ_PLAIN_STORE),-DGS4D_PROJ_PLAIN_STORE) $(if $(PROJ_PITCH),-DGS4D_PROJ_PITCH=$(PROJ_PITCH)) -c $< -o $@
 $(CSRC)/lines.o: $(CSRC)/lines.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 $(CSRC)/compact.o: $(CSRC)/compact.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
