@@ -105,6 +105,8 @@ def _load():
         "gs4d_spatial_order": (i32, [vp, u32, sz, sz, sz, u32]),
         "gs4d_gather_records": (i32, [vp, u32, sz, u32, sz, sz, u32]),
         "gs4d_shade_sh": (i32, [vp, u32, sz, u32, sz, i32, f32, vp]),
+        "gs4d_shade_sh_t": (i32, [vp, u32, sz, u32, sz, vp]),
+        "gs4d_collapse_sh": (i32, [vp, u32, sz, u32, sz, vp, u32, sz]),
         "gs4d_edit_colours": (i32, [vp, u32, sz, vp, u32, vp, u32]),
         "gs4d_count_centres": (i32, [vp, u32, sz, vp, u32, u32]),
         "gs4d_measure_records": (i32, [vp, u32, sz, vp, u32, vp, u32]),
@@ -154,6 +156,9 @@ def _load():
         "gs4d_host_pose_records": (None, [sz, vp, vp, sz, vp, u32, sz, vp]),
         "gs4d_host_sh_rotation": (i32, [vp, vp]),
         "gs4d_host_rotate_sh": (None, [sz, vp, sz, i32, vp, sz, vp, u32, sz, vp]),
+        "gs4d_host_sh_time_weights": (None, [vp, f32, vp, C.POINTER(i32)]),
+        "gs4d_host_collapse_sh": (None, [sz, vp, vp, sz, vp, vp, sz]),
+        "gs4d_host_shade_sh_t": (None, [sz, vp, vp, sz, vp]),
         "gs4d_host_warp_records": (None, [sz, vp, vp, vp, vp]),
         "gs4d_host_slice_records": (None, [sz, vp, vp, vp]),
         "gs4d_host_edit_colours": (None, [sz, vp, vp, vp, vp, vp]),
@@ -505,6 +510,66 @@ def warp_records_host(records, nodes, lat):
         raise ValueError(f"the lattice has {count} nodes, the array {a.shape[0]}")
     _lib.gs4d_host_warp_records(rec.shape[0], _ptr(rec), _ptr(a) if a.size else None, C.byref(lat), _ptr(out))
     return out
+
+
+class ShTime(C.Structure):
+    """gs4d_sh_time (include/gs4d.h): the degrees, the time, 1 / period of the cosine series and the camera position of a gs4d_shade_sh_t or
+    gs4d_collapse_sh call; 32 bytes."""
+    _fields_ = [("degree", C.c_int32), ("degree_t", C.c_int32), ("t", C.c_float), ("inv_period", C.c_float), ("cam_pos", C.c_float * 3),
+                ("reserved", C.c_uint32)]
+
+
+def sh_time_query(degree, degree_t, t, inv_period, cam_pos=(0.0, 0.0, 0.0)):
+    """one gs4d_sh_time (ShTime); inv_period is 1 / T of the cosine series (4DGS: 1 / time_duration); cam_pos matters to shade_sh_t only"""
+    cam = _f32(cam_pos).reshape(3)
+    return ShTime(int(degree), int(degree_t), float(t), float(inv_period), (C.c_float * 3)(*(float(v) for v in cam)), 0)
+
+
+def _sh_time(q, degree=None, degree_t=None, t=None, inv_period=None, cam_pos=None):
+    return q if isinstance(q, ShTime) else sh_time_query(degree, degree_t, t, inv_period, (0.0, 0.0, 0.0) if cam_pos is None else cam_pos)
+
+
+def sh_time_weights(degree_t, t, inv_period, mu_t):
+    """gs4d_host_sh_time_weights: (w float32 [2], mask) for a record whose float 3 is mu_t — w[n - 1] weighs block n = 1 .. degree_t of a 4D SH
+    row, bit n - 1 of mask says whether the block takes part (w of one that does not: 0)."""
+    q = sh_time_query(0, degree_t, t, inv_period)
+    w, mask = np.zeros(2, np.float32), C.c_int(0)
+    _lib.gs4d_host_sh_time_weights(C.byref(q), C.c_float(np.float32(mu_t)), _ptr(w), C.byref(mask))
+    return w, mask.value
+
+
+def _sh_table_t(sh, n, sh_stride):
+    table = np.ascontiguousarray(sh).view(np.uint8).reshape(-1)
+    if table.size < n * sh_stride:
+        raise ValueError(f"the table holds fewer than {n} rows of {sh_stride} bytes")
+    return table
+
+
+def collapse_sh_host(records, sh, degree, degree_t, t, inv_period, sh_stride=None, dst_stride=None):
+    """gs4d_host_collapse_sh, the definition of Context.collapse_sh: the 4D SH table `sh` (rows of sh_stride bytes, default sh_row_bytes_t(degree,
+    degree_t)) of the records [n, 24] collapsed at time t: float32 [n, dst_stride / 4] (default sh_row_bytes(degree)) — the effective row, zeros
+    behind it.  Arguments the device call would refuse give zeros."""
+    rec = _f32(records).reshape(-1, 24)
+    n = rec.shape[0]
+    sh_stride = sh_row_bytes_t(degree, degree_t) if sh_stride is None else int(sh_stride)
+    dst_stride = sh_row_bytes(degree) if dst_stride is None else int(dst_stride)
+    table = _sh_table_t(sh, n, sh_stride)
+    out = np.zeros((n, dst_stride // 4), np.float32)
+    q = sh_time_query(degree, degree_t, t, inv_period)
+    _lib.gs4d_host_collapse_sh(n, _ptr(rec), _ptr(table) if table.size else None, sh_stride, C.byref(q), _ptr(out) if out.size else None, dst_stride)
+    return out
+
+
+def shade_sh_t_host(records, sh, degree, degree_t, t, inv_period, cam_pos, sh_stride=None):
+    """gs4d_host_shade_sh_t, the definition of Context.shade_sh_t: a copy of the records [n, 24] with floats 4..6 <- the colour of their rows of the
+    4D SH table `sh` at time t, seen from cam_pos.  Arguments the device call would refuse give the records back."""
+    rec = _f32(records).reshape(-1, 24).copy()
+    n = rec.shape[0]
+    sh_stride = sh_row_bytes_t(degree, degree_t) if sh_stride is None else int(sh_stride)
+    table = _sh_table_t(sh, n, sh_stride)
+    q = sh_time_query(degree, degree_t, t, inv_period, cam_pos)
+    _lib.gs4d_host_shade_sh_t(n, _ptr(rec), _ptr(table) if table.size else None, sh_stride, C.byref(q))
+    return rec
 
 
 class Slice(C.Structure):
@@ -1321,6 +1386,33 @@ def sh_rows(f_dc, f_rest, degree, stride=None):
     return rows
 
 
+def sh_row_bytes_t(degree, degree_t):
+    """The minimal row of gs4d_shade_sh_t's table: 12 (degree + 1)^2 (degree_t + 1) bytes rounded up to 16 — 576 at degree 3 / degree_t 2."""
+    return (12 * (int(degree) + 1) ** 2 * (int(degree_t) + 1) + 15) // 16 * 16
+
+
+def sh_rows_t(features, degree, degree_t, src_degree=3, stride=None):
+    """The table of gs4d_shade_sh_t from a 4DGS checkpoint: features [n, (src_degree + 1)^2 B, 3], coefficient-major with B >= degree_t + 1 blocks
+    of (src_degree + 1)^2 coefficients (cat(features_dc, features_rest)).  Returns uint8 [n, stride] (default: the minimal stride): float32
+    row[3 (b K + k) + channel] for the first K = (degree + 1)^2 coefficients k of the first degree_t + 1 blocks b, zero padded to the stride."""
+    degree, degree_t, src_degree = int(degree), int(degree_t), int(src_degree)
+    if not 0 <= degree <= 3 or not 0 <= degree_t <= 2 or src_degree < degree:
+        raise ValueError("sh_rows_t: degree must be 0 .. 3, degree_t 0 .. 2, src_degree >= degree")
+    K, KS = (degree + 1) ** 2, (src_degree + 1) ** 2
+    f = _f32(features)
+    if f.ndim != 3 or f.shape[2] != 3 or f.shape[1] % KS or f.shape[1] // KS < degree_t + 1:
+        raise ValueError("sh_rows_t: features must be [n, (src_degree + 1)^2 B, 3] with B >= degree_t + 1")
+    n = f.shape[0]
+    stride = sh_row_bytes_t(degree, degree_t) if stride is None else int(stride)
+    used = 12 * K * (degree_t + 1)
+    if stride % 16 or not 16 <= stride <= 1024 or stride < used:
+        raise ValueError("sh_rows_t: stride must be a multiple of 16 from 16 to 1024 that holds 12 (degree + 1)^2 (degree_t + 1) bytes")
+    coeff = np.ascontiguousarray(f.reshape(n, -1, KS, 3)[:, :degree_t + 1, :K, :])
+    rows = np.zeros((n, stride), np.uint8)
+    rows[:, :used] = coeff.reshape(n, used // 4).view(np.uint8)
+    return rows
+
+
 _hip_runtime = None
 
 
@@ -2083,6 +2175,32 @@ class Context:
             sh_stride = sh_row_bytes(degree)
         self._chk(_lib.gs4d_shade_sh(self._h, int(data), int(n), int(sh), int(sh_stride), int(degree), float(t), _ptr(_f32(cam_pos))))
 
+    # time-varying view-dependent colour: SH times a cosine series in time, the colour model of trained 4D sets
+    def shade_sh_t(self, data, n, sh, degree, degree_t, t, inv_period, cam_pos, sh_stride=None):
+        """gs4d_shade_sh_t: floats 4..6 of the first n 96-byte records of `data` <- the colour of their rows of the 4D table `sh` (degree_t + 1
+        blocks of (degree + 1)^2 coefficients, see sh_rows_t; block b weighted by cos(2 pi b (t - mu_t) inv_period)) seen from cam_pos at time t,
+        with the bits of shade_sh_t_host — and of shade_sh on collapse_sh's rows.  sh_stride: bytes per row (default sh_row_bytes_t(degree,
+        degree_t)).  degree may be a ShTime, which then carries everything but the buffers.  A colour-only write: a current SoA shadow is patched,
+        not rebuilt.  Per frame: shade_sh_t, keygen, sort, draw.  Asynchronous."""
+        q = _sh_time(degree, degree, degree_t, t, inv_period, cam_pos)
+        if sh_stride is None:
+            sh_stride = sh_row_bytes_t(q.degree, q.degree_t)
+        self._chk(_lib.gs4d_shade_sh_t(self._h, int(data), int(n), int(sh), int(sh_stride), C.byref(q)))
+
+    def collapse_sh(self, data, n, sh, degree, degree_t, t, inv_period, sh_stride=None, dst=None, dst_stride=None):
+        """gs4d_collapse_sh: row i < n of `dst` (a new buffer if None; dst_stride bytes a row, default sh_row_bytes(degree)) <- the 3DGS row that
+        row i of the 4D table `sh` is at time t for the mu_t of record i of `data`, zeros behind it, with the bits of collapse_sh_host: shade_sh of
+        the rows at `degree` gives what shade_sh_t gives.  data and sh are only read.  Asynchronous; returns `dst`."""
+        q = _sh_time(degree, degree, degree_t, t, inv_period)
+        if sh_stride is None:
+            sh_stride = sh_row_bytes_t(q.degree, q.degree_t)
+        if dst_stride is None:
+            dst_stride = sh_row_bytes(q.degree)
+        if dst is None:
+            dst = self.buffer(nbytes=max(16, int(n) * int(dst_stride)))
+        self._chk(_lib.gs4d_collapse_sh(self._h, int(data), int(n), int(sh), int(sh_stride), C.byref(q), int(dst), int(dst_stride)))
+        return dst
+
     # colour edits by a selection: recolour, hide or restore selected records (DESIGN.md §4)
     COLOUR_EDIT = COLOUR_EDIT
 
@@ -2291,7 +2409,9 @@ class Context:
         exact-size new buffers.  Returns (dst, kept_index, count): the set, the uint32 index in `data` of each of its records, and the
         COMPACT_COUNT buffer, whose `kept` is their number (read_compact_count; it is settled when the call returns).  A record of alpha 0 changes no pixel under the default blend, so a draw of (dst, kept) at uTime == mu_t_out
         (None: t) is the draw of (data, n) at t, record i of dst being record kept_index[i] of data.  For a long clip the cheaper order is
-        compact_time_window(spans, n, t, t) first and slice_records of the survivors: the slice then reads only what can show at t."""
+        compact_time_window(spans, n, t, t) first and slice_records of the survivors: the slice then reads only what can show at t.  A source
+        with a 4D SH table keeps its view dependence: collapse_sh of the source's table at t, then gather_records of the collapsed rows through
+        kept_index — shade_sh of (dst, kept) at time mu_t_out with those rows gives the colours shade_sh_t gives the source at t."""
         sliced = self.slice_records(data, n, t, min_opacity, mu_t_out, s44_out)
         table = self.buffer(np.zeros(max(1, int(n)), RECORD_STAT))
         try:

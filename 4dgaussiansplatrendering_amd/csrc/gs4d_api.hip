@@ -23,6 +23,7 @@
 #include "lod_operands.h"
 #include "rows_operands.h"
 #include "sh_rotate_operands.h"
+#include "sh_time_record.h"
 #include <cstdio>
 #include <cstring>
 #include <cstdlib>
@@ -1585,6 +1586,47 @@ int gs4d_shade_sh(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_s
             if (patch) D->soa_version = D->version;
             return (int)GS4D_OK;
         });
+}
+
+// ---- time-varying view-dependent colour ----
+int gs4d_shade_sh_t(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_stride, const gs4d_sh_time* q) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "shade_sh_t";
+    if (!q) return refuse(c, fn, "q == NULL");
+    const gs4d_sh_time query = *q;
+    if (const char* fault = gs4d_sht::query_fault(n, query.degree, query.degree_t, query.reserved, sh_stride)) return refuse(c, fn, fault);
+    Operands ops{ { "data", data, false, 96, n, OP_WRITE }, { "sh", sh, false, sh_stride, n, OP_READ } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (n == 0) return GS4D_OK;
+    Buffer* const D = ops.buffer(data);
+    // the colour-only write of gs4d_shade_sh: the same decision, at the same point
+    bool patch = false;
+    return queue_operands(c, ops,
+        [&](Lane&) { patch = D->soa && D->soa_n == D->bytes / 96 && D->soa_version == D->version; return (int)GS4D_OK; },
+        [&](Lane& L) {
+            HIPCHK(c, launch_shade_sh_t(L.s, D->d, n, ops.ptr(sh), sh_stride, query, patch ? D->soa + D->soa_n : nullptr));
+            if (patch) D->soa_version = D->version;
+            return (int)GS4D_OK;
+        });
+}
+
+int gs4d_collapse_sh(gs4d_ctx* c, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_stride, const gs4d_sh_time* q, gs4d_buf dst, size_t dst_stride) {
+    if (!c) return GS4D_E_INVALID;
+    (void)hipSetDevice(c->device);
+    const char* const fn = "collapse_sh";
+    if (!q) return refuse(c, fn, "q == NULL");
+    const gs4d_sh_time query = *q;
+    if (const char* fault = gs4d_sht::query_fault(n, query.degree, query.degree_t, query.reserved, sh_stride)) return refuse(c, fn, fault);
+    if (const char* fault = gs4d_sht::dst_stride_fault(query.degree, dst_stride)) return refuse(c, fn, fault);
+    // tables are not record buffers, and data is a read operand: the ordering of gs4d_rotate_sh
+    Operands ops{ { "data", data, false, 96, n, OP_READ }, { "sh", sh, false, sh_stride, n, OP_READ }, { "dst", dst, false, dst_stride, n, OP_WRITE } };
+    { int rc = check_operands(c, fn, ops); if (rc) return rc; }
+    if (n == 0) return GS4D_OK;
+    return queue_operands(c, ops, [&](Lane& L) {
+        HIPCHK(c, launch_collapse_sh(L.s, ops.ptr(data), n, ops.ptr(sh), sh_stride, query, ops.ptr(dst), dst_stride));
+        return (int)GS4D_OK;
+    });
 }
 
 // ---- colour edits by a selection ----

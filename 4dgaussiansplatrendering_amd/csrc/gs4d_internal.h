@@ -512,6 +512,16 @@ hipError_t launch_gather_records(hipStream_t st, const uint32_t* index, size_t m
 constexpr uint32_t SHADE_TILE = 256;
 hipError_t launch_shade_sh(hipStream_t st, void* records, size_t n, const void* sh, size_t sh_stride, int degree, float t, const float cam[3], float4* plane1);
 
+// ---- shade_time.hip ----
+// gs4d_shade_sh_t (gs4d.h): floats 4..6 of the first n 96-byte records <- the colour of row i of `sh`, a row of q.degree_t + 1 blocks of
+// 12 (q.degree + 1)^2 bytes (sh_stride bytes per row, a multiple of 16 that holds them), folded at time q.t and seen from q.cam_pos; q validated.
+// plane1 as in launch_shade_sh, which serves q.degree_t == 0.  One workgroup per SHADE_T_TILE records.
+constexpr uint32_t SHADE_T_TILE = 256;
+hipError_t launch_shade_sh_t(hipStream_t st, void* records, size_t n, const void* sh, size_t sh_stride, const gs4d_sh_time& q, float4* plane1);
+// gs4d_collapse_sh: row i of dst (dst_stride bytes per row, a multiple of 16 that holds 12 (q.degree + 1)^2 bytes) <- the effective row of row i of
+// `sh` at time q.t for the mu_t of record i, zeros behind it.  n <= 0xFFFFFFFF; nothing past row n - 1 of dst is touched.
+hipError_t launch_collapse_sh(hipStream_t st, const void* records, size_t n, const void* sh, size_t sh_stride, const gs4d_sh_time& q, void* dst, size_t dst_stride);
+
 // ---- edit.hip ----
 // gs4d_edit_colours (gs4d.h): floats 4..7 of the selected ones of the first n 96-byte records edited by e (validated).  stats: the table
 // whose row i selects record i by `rule` (keep_row), or null: every record.  from: the n 96-byte records GS4D_EDIT_COPY takes the colour from, else

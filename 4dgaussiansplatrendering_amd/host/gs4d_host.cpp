@@ -28,6 +28,7 @@
 #include "../csrc/pose_record.h"
 #include "../csrc/sh_rotate_record.h"
 #include "../csrc/sh_rotate_operands.h"
+#include "../csrc/sh_time_record.h"
 #include "../csrc/warp_record.h"
 #include "../csrc/slice_record.h"
 #include "../csrc/centre_query.h"
@@ -451,6 +452,52 @@ void gs4d_host_rotate_sh(size_t n, const void* rows, size_t stride, int degree, 
     if (gs4d::rotate_sh_fault(n, stride, degree, m, bind != nullptr, form, bind_stride, 0)) return;
     (degree == 0 ? &rotate_sh_rows<0> : degree == 1 ? &rotate_sh_rows<1> : degree == 2 ? &rotate_sh_rows<2> : &rotate_sh_rows<3>)(
         n, (const unsigned char*)rows, stride, xf, m, (const unsigned char*)bind, form, bind_stride, (unsigned char*)out);
+}
+
+// The definitions of gs4d_shade_sh_t and gs4d_collapse_sh (gs4d.h) are csrc/sh_time_record.h: the weights of the time blocks from the record's mu_t,
+// the effective row they fold a 4D row into, and gs4d_shade_sh's colour of a record from that row.  Arguments the device calls would refuse write nothing.
+void gs4d_host_sh_time_weights(const gs4d_sh_time* q, float mu_t, float w[2], int* mask) {
+    w[0] = w[1] = 0.0f;
+    *mask = 0;
+    if (!q || q->degree_t < 0 || q->degree_t > gs4d_sht::MAX_DEGREE_T) return;
+    *mask = (int)gs4d_sht::weights(q->degree_t, q->t, q->inv_period, mu_t, w);
+}
+} // extern "C"
+namespace {
+// e <- the effective row of row i for record i
+void effective_row_at(size_t i, const float* rec, const unsigned char* sh, size_t sh_stride, const gs4d_sh_time& q, float e[48]) {
+    float row[48 * 3], w[2];
+    std::memcpy(row, sh + i * sh_stride, 4u * gs4d_sht::row_words_t(q.degree, q.degree_t));
+    const uint32_t mask = gs4d_sht::weights(q.degree_t, q.t, q.inv_period, rec[24 * i + 3], w);
+    gs4d_sht::effective_row(q.degree, q.degree_t, row, w, mask, e);
+}
+}
+extern "C" {
+void gs4d_host_collapse_sh(size_t n, const float* rec, const void* sh, size_t sh_stride, const gs4d_sh_time* q, void* dst, size_t dst_stride) {
+    if (!q || gs4d_sht::query_fault(n, q->degree, q->degree_t, q->reserved, sh_stride) || gs4d_sht::dst_stride_fault(q->degree, dst_stride)) return;
+    const size_t used = 4u * gs4d_sht::row_words(q->degree);
+    for (size_t i = 0; i < n; ++i) {
+        float e[48];
+        effective_row_at(i, rec, (const unsigned char*)sh, sh_stride, *q, e);
+        unsigned char* const to = (unsigned char*)dst + i * dst_stride;
+        std::memcpy(to, e, used);
+        std::memset(to + used, 0, dst_stride - used);
+    }
+}
+
+void gs4d_host_shade_sh_t(size_t n, float* rec, const void* sh, size_t sh_stride, const gs4d_sh_time* q) {
+    if (!q || gs4d_sht::query_fault(n, q->degree, q->degree_t, q->reserved, sh_stride)) return;
+    for (size_t i = 0; i < n; ++i) {
+        float e[48], *const r = rec + 24 * i;
+        effective_row_at(i, rec, (const unsigned char*)sh, sh_stride, *q, e);
+        const float* const cam = q->cam_pos;
+        switch (q->degree) {
+        case 0: gs4d_sht::colour<0>(r, r + 20, q->t, cam[0], cam[1], cam[2], e, r + 4); break;
+        case 1: gs4d_sht::colour<1>(r, r + 20, q->t, cam[0], cam[1], cam[2], e, r + 4); break;
+        case 2: gs4d_sht::colour<2>(r, r + 20, q->t, cam[0], cam[1], cam[2], e, r + 4); break;
+        default: gs4d_sht::colour<3>(r, r + 20, q->t, cam[0], cam[1], cam[2], e, r + 4); break;
+        }
+    }
 }
 
 // The definition of gs4d_warp_records (gs4d.h) is csrc/warp_record.h: the record through the lattice's map linearised at its centre, or copied.  A

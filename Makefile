@@ -21,7 +21,7 @@ $(FLAGSTAMP):
 	rm -f $(CSRC)/.flags.*
 	touch $@
 
-OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/decompose.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/pose.o $(CSRC)/sh_rotate.o $(CSRC)/warp.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/merge.o $(CSRC)/merge_rows.o $(CSRC)/lod.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
+OBJS := $(CSRC)/gs4d_api.o $(CSRC)/sort.o $(CSRC)/preprocess.o $(CSRC)/binning.o $(CSRC)/composite.o $(CSRC)/tilelist.o $(CSRC)/composite2.o $(CSRC)/lines.o $(CSRC)/compact.o $(CSRC)/reorder.o $(CSRC)/cut.o $(CSRC)/select.o $(CSRC)/shade.o $(CSRC)/shade_time.o $(CSRC)/edit.o $(CSRC)/build.o $(CSRC)/decompose.o $(CSRC)/transform.o $(CSRC)/transform_selected.o $(CSRC)/pose.o $(CSRC)/sh_rotate.o $(CSRC)/warp.o $(CSRC)/slice.o $(CSRC)/centres.o $(CSRC)/measure.o $(CSRC)/merge.o $(CSRC)/merge_rows.o $(CSRC)/lod.o $(CSRC)/neighbours.o $(CSRC)/components.o $(CSRC)/nearest.o $(HOST)/gs4d_host.o
 
 .PHONY: all lib oracle ref refscene refdraw refgl clean demo sweep
 all: lib oracle demo sweep
@@ -55,6 +55,9 @@ $(CSRC)/reorder.o: $(CSRC)/reorder.hip $(CSRC)/gs4d_internal.h include/gs4d.h Ma
 $(CSRC)/cut.o: $(CSRC)/cut.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 $(CSRC)/shade.o: $(CSRC)/shade.hip $(CSRC)/record_tile.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
+	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
+# sh_time_record.h is the one text of gs4d_shade_sh_t's and gs4d_collapse_sh's definition — the weights of the time blocks, the effective row, gs4d_shade_sh's colour from a row: the kernels and the host library compile it (tests/sh_time_check.cpp compiles it too; gs4d_api.o takes the two calls' scalar checks from it); shade_time.o is built with the flags of shade.o
+$(CSRC)/shade_time.o: $(CSRC)/shade_time.hip $(CSRC)/record_tile.h $(CSRC)/sh_time_record.h $(HD) $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
 $(CSRC)/edit.o: $(CSRC)/edit.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) -c $< -o $@
@@ -116,10 +119,10 @@ $(CSRC)/slice.o: $(CSRC)/slice.hip $(CSRC)/record_tile.h $(CSRC)/slice_record.h 
 $(CSRC)/select.o: $(CSRC)/select.hip $(CSRC)/gs4d_internal.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) $(STRICT) $(if $(COUNT_IDS_PLAIN),-DGS4D_COUNT_IDS_PLAIN) -c $< -o $@
 # operands.h is the one text of the record-set calls' buffer-argument check (tests/operand_check.cpp compiles it too)
-$(CSRC)/gs4d_api.o: $(CSRC)/operands.h $(CSRC)/merge_record.h $(CSRC)/warp_record.h $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(CSRC)/lod_operands.h $(CSRC)/rows_operands.h $(CSRC)/sh_rotate_operands.h $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(HD)
+$(CSRC)/gs4d_api.o: $(CSRC)/operands.h $(CSRC)/merge_record.h $(CSRC)/warp_record.h $(CSRC)/pose_record.h $(CSRC)/transform_record.h $(CSRC)/lod_operands.h $(CSRC)/rows_operands.h $(CSRC)/sh_rotate_operands.h $(CSRC)/sh_time_record.h $(CSRC)/lod_query.h $(CSRC)/centre_query.h $(HD)
 $(CSRC)/%.o: $(CSRC)/%.hip $(CSRC)/gs4d_internal.h $(CSRC)/composite_common.h include/gs4d.h Makefile $(FLAGSTAMP)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/decompose_record.h $(CSRC)/transform_record.h $(CSRC)/pose_record.h $(CSRC)/sh_rotate_record.h $(CSRC)/sh_rotate_operands.h $(CSRC)/operands.h $(CSRC)/warp_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/merge_record.h $(CSRC)/merge_rows_record.h $(CSRC)/lod_query.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
+$(HOST)/gs4d_host.o: $(HOST)/gs4d_host.cpp $(CSRC)/build_record.h $(CSRC)/decompose_record.h $(CSRC)/transform_record.h $(CSRC)/pose_record.h $(CSRC)/sh_rotate_record.h $(CSRC)/sh_rotate_operands.h $(CSRC)/sh_time_record.h $(CSRC)/operands.h $(CSRC)/warp_record.h $(CSRC)/slice_record.h $(HD) $(CSRC)/centre_query.h $(CSRC)/measure_record.h $(CSRC)/merge_record.h $(CSRC)/merge_rows_record.h $(CSRC)/lod_query.h $(CSRC)/neighbour_query.h $(CSRC)/component_union.h $(CSRC)/nearest_query.h include/gs4d.h
 	$(HIPCC) -O2 -std=c++17 -fPIC -fvisibility=hidden $(STRICT) -x c++ -c $< -o $@
 
 $(LIB): $(OBJS)

@@ -767,6 +767,82 @@ GS4D_API int gs4d_rotate_sh(gs4d_ctx* ctx, gs4d_buf src, size_t n, size_t stride
                             gs4d_buf xf, size_t m, gs4d_buf bind /* 0 with GS4D_SH_EACH */, uint32_t form, size_t bind_stride,
                             gs4d_buf dst, size_t dst_first);
 
+/* ---- time-varying view-dependent colour: spherical harmonics times a cosine series in time (no reference counterpart) ----
+ * The colour model of trained 4D sets (4DGS and its successors; the sets GS4D_PARAMS_4D_2Q builds the records of) is not the 3DGS table of
+ * gs4d_shade_sh: per channel it holds degree_t + 1 BLOCKS of SH coefficients, block n weighted by cos(2 pi n (t - mu_t) / T).  gs4d_shade_sh_t
+ * evaluates that model every frame, as gs4d_shade_sh evaluates a 3DGS table; gs4d_collapse_sh writes, for one time, the ordinary 3DGS row every 4D
+ * row comes to — the table of a frame frozen by gs4d_slice_records, which gs4d_shade_sh then shades from any camera.  Both are one definition:
+ *     gs4d_shade_sh_t(data, sh)  writes the bits of  gs4d_shade_sh(data, gs4d_collapse_sh(data, sh))  at q->degree, q->t, q->cam_pos.
+ *
+ * The table.  Row i is the sh_stride bytes at sh + i*sh_stride, float32 with the channels interleaved as in gs4d_shade_sh, block after block: with
+ * K = (degree + 1)^2, coefficient k of block n, channel ch, is row[3 (n K + k) + ch] — at degree 3 the 4DGS tensor [N, 16 (degree_t + 1), 3] as
+ * it stands.  sh_stride: a multiple of 16, 16 .. 1024, and >= 12 K (degree_t + 1) (minimal rows: 576 bytes at degree 3 / degree_t 2).  A lower
+ * degree_t reads a prefix of the same row.  A lower degree does NOT: the pitch of the blocks is K, so a table laid out for degree 3 cannot be read
+ * at degree 2 (lay the rows out again; reading a lower degree out of a higher one is out of scope).  Only the first 12 K (degree_t + 1) bytes,
+ * rounded up to 16, are ever read.
+ *
+ * The weights.  Arithmetic as everywhere: float32, round to nearest, no contraction, every product and sum rounded on its own in the order
+ * written.  With mu_t = float 3 of record i:
+ *     u = (t - mu_t) * inv_period
+ *     for n = 1 .. degree_t:
+ *         v = (float)n * u
+ *         block n TAKES PART iff v is finite          (else it is left out: a NaN / Inf t, mu_t or inv_period is data)
+ *         r = v - rintf(v)                            (exact; |v| >= 2^23 gives r = 0 and w = 1)
+ *         a = fabsf(r);  neg = a > 0.25f;  x = neg ? 0.5f - a : a        (exact)
+ *         s = x*x
+ *         p = T6;  p = (p*s) + T5;  p = (p*s) + T4;  p = (p*s) + T3;  p = (p*s) + T2;  p = (p*s) + T1
+ *         c = (p*s) + 1.0f
+ *         w_n = neg ? -c : c
+ *     T_j = float32((-1)^j (2 pi)^(2j) / (2j)!), j = 1 .. 6:
+ *         -19.739208802178716, 64.93939402266828, -85.45681720669371, 60.24464137187664, -26.426256783374388, 7.903536371318465
+ *         (bits c19de9e6 4281e0f8 c2aae9e4 4270fa83 c1d368f9 40fce9c5)
+ * Over every float32 x in [0, 0.25], |c - cos(2 pi x)| <= 1.561e-7, c stays in [0, 1], c(0) = 1 and c(0.25) = 0 exactly: w(0) = 1, w(+-1/2) = -1, w
+ * is even and |w| <= 1.  r, a and x being exact, 1.561e-7 is the whole error of w_n against cos(2 pi v) of the float32 v (cosf(2 pi v) in float32 is
+ * off by 2.0e-7 at |v| <= 1/2, 7.9e-7 at |v| <= 2, 4.8e-5 at |v| <= 100).
+ *
+ * The effective row.  Per word j < 3 K, c_(n,j) being word j of block n:
+ *     e_j = c_(0,j);   if block 1 takes part: e_j = e_j + (w_1 * c_(1,j));   if block 2 takes part: e_j = e_j + (w_2 * c_(2,j))
+ *
+ * gs4d_collapse_sh writes e_0 .. e_(3K-1) to row i < n of dst and zeros from word 3 K to dst_stride / 4.  dst_stride: a multiple of 16, 16 .. 1024,
+ * >= 12 K.  Nothing past row n - 1 of dst is written; data and sh are read only, and of a record only float 3 is used; q->cam_pos is ignored.
+ * degree_t == 0 copies the prefix.
+ *
+ * gs4d_shade_sh_t writes floats 4..6 of record i < n with exactly what gs4d_shade_sh at q->degree, q->t and q->cam_pos writes from the row e: its
+ * direction, basis, sum order, DC-only rule and clamp, unchanged.  degree_t == 0, or no block taking part, gives the bits of gs4d_shade_sh on the
+ * same table.  UNLIKE the 4DGS rasterizer, whose direction runs from the camera to the REST mean of the splat, the direction runs to the
+ * time-conditioned mean the draw projects, as in gs4d_shade_sh.  The device gives the bits of gs4d_host_collapse_sh and gs4d_host_shade_sh_t,
+ * except that a word of a collapsed row that is a NaN on both sides may differ in sign and payload.  Nothing depends on the order in which
+ * anything runs on the device.
+ *
+ * gs4d_merge_rows and 4D tables: the effective row is linear in the coefficients only among members with EQUAL mu_t (the weights are the
+ * record's); merging 4D rows word by word is right for such groups only.  Posing a 4D table: every block rotates with the same band matrices, so
+ * at degree 3 with sh_stride == 192 (degree_t + 1) a table of n rows IS a table of (degree_t + 1) n rows of 192 bytes, which gs4d_rotate_sh turns
+ * as it stands — GS4D_SH_EACH with one map, or GS4D_POSE_INDEX with every bind word repeated degree_t + 1 times.
+ *
+ * GS4D_E_INVALID, with nothing queued and nothing written: q == NULL; degree outside 0 .. 3; degree_t outside 0 .. 2; reserved != 0; n >
+ * 0xFFFFFFFF; an sh_stride or dst_stride that breaks its rule; a name that is not a live buffer; any two named buffers being the same; data smaller
+ * than 96 n bytes, sh smaller than n * sh_stride, dst smaller than n * dst_stride.  n == 0 is a no-op.  t, inv_period and cam_pos are data.
+ *
+ * Ordering.  gs4d_shade_sh_t: that of gs4d_shade_sh, gs4d_buffer_invalidate hand-offs included, and the same COLOUR-ONLY write — a current SoA
+ * shadow gets its colour plane patched and stays current; per frame shade_sh_t -> gs4d_keygen -> gs4d_sort_pairs -> draw.  gs4d_collapse_sh: that
+ * of gs4d_rotate_sh — tables are not record buffers, data and sh are buffers the call reads, dst one it writes; no shadow is built or invalidated.
+ * A frozen frame that keeps its view dependence: gs4d_slice_records at t (kept_index), gs4d_collapse_sh of the source at t, gs4d_gather_records of
+ * the collapsed rows through kept_index; gs4d_shade_sh of the frozen set at t == mu_t_out then gives the colours gs4d_shade_sh_t gives the source
+ * (bit for bit where the time column and the time row of a record's sig hold the same bits: the slice conditions with the column, the shade
+ * with the row).
+ * Out of scope: degree_t > 2; fp16 tables; a lower degree out of a higher-degree 4D table; collapsing into the shadow. */
+typedef struct gs4d_sh_time {
+    int32_t  degree;      /* 0 .. 3: the SH degree, K = (degree + 1)^2 coefficients per block */
+    int32_t  degree_t;    /* 0 .. 2: blocks 0 .. degree_t are read */
+    float    t;           /* the time */
+    float    inv_period;  /* 1 / T of the cosine series (4DGS: 1 / time_duration), computed by the caller */
+    float    cam_pos[3];  /* gs4d_shade_sh_t only; gs4d_collapse_sh ignores it */
+    uint32_t reserved;    /* 0 */
+} gs4d_sh_time;           /* 32 bytes */
+GS4D_API int gs4d_shade_sh_t(gs4d_ctx* ctx, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_stride, const gs4d_sh_time* q);
+GS4D_API int gs4d_collapse_sh(gs4d_ctx* ctx, gs4d_buf data, size_t n, gs4d_buf sh, size_t sh_stride, const gs4d_sh_time* q,
+                              gs4d_buf dst, size_t dst_stride);
+
 /* ---- a map that varies from point to point: a set deformed through a 4D lattice (no reference counterpart) ----
  * gs4d_transform_records and gs4d_pose_records apply affine maps.  A cage or free-form deformation in an editor (bend, bulge, taper), a baked
  * deformation field with a time axis (how a static or a 4D set is animated non-rigidly) and a retiming field (a region that plays slower or later
@@ -1697,6 +1773,15 @@ GS4D_API int  gs4d_host_sh_rotation(const float l[16], float d[84]);   /* 1: d h
  * Arguments the device call would refuse write nothing. */
 GS4D_API void gs4d_host_rotate_sh(size_t n, const void* rows, size_t stride, int degree, const gs4d_affine4* xf, size_t m,
                                   const void* bind, uint32_t form, size_t bind_stride, void* out);
+/* The weights of gs4d_shade_sh_t / gs4d_collapse_sh (the text above their declarations) for a record whose float 3 is mu_t: w[n - 1] = w_n of block
+ * n = 1 .. q->degree_t, bit n - 1 of *mask set iff block n takes part (w of a block that does not, or that is above degree_t: 0).  q->degree,
+ * q->cam_pos and q->reserved are not looked at; a degree_t outside 0 .. 2 gives no block. */
+GS4D_API void gs4d_host_sh_time_weights(const gs4d_sh_time* q, float mu_t, float w[2], int* mask);
+/* The definition of gs4d_collapse_sh: row i of dst (dst_stride bytes) = the effective row of row i of sh (sh_stride bytes) at q->t for record i of
+ * records24, zeros behind it, i < n.  dst must not overlap sh.  Arguments the device call would refuse write nothing. */
+GS4D_API void gs4d_host_collapse_sh(size_t n, const float* records24, const void* sh, size_t sh_stride, const gs4d_sh_time* q, void* dst, size_t dst_stride);
+/* The definition of gs4d_shade_sh_t, in place on floats 4..6 of the n records of records24.  Arguments the device call would refuse write nothing. */
+GS4D_API void gs4d_host_shade_sh_t(size_t n, float* records24, const void* sh, size_t sh_stride, const gs4d_sh_time* q);
 /* The definition of gs4d_warp_records: out24 record i = records24 record i through the lattice *lat of the nodes nodes4 (4 floats each), i < n (the
  * text above the declaration of gs4d_warp_records).  out24 must not overlap records24.  A lattice the device call would refuse (NULL included)
  * writes nothing. */
